@@ -1,15 +1,25 @@
 #!/usr/bin/env python3
 """Benchmark of the GIMS matcher hot path on MI355X:  image-pairs/sec at 2 x N keypoints.
 
-    python bench.py --gpus N --steps K --warmup W [--kpts 4096 --pairs 8] [--sinkhorn-iters 100]
+    python bench.py --gpus N --steps K --warmup W [--kpts 4096 --pairs 8] [--sinkhorn-iters 100] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the whole hot path (adaptive graph build -> GraphSAGE -> keypoint encoder ->
 18-layer self/cross attention -> Sinkhorn -> mutual matching) over one ragged batch of synthetic image pairs
 per GPU, through the production path (`GMatcher.match_pairs`: the 18 layers run from the replayed launch
-table; the library records a HIP event after each of its launches, on the launch stream).  Inputs are
+table; with --full the library records a HIP event after each of its launches, on the launch stream).  Inputs are
 resident in HBM before the timed region.
 
-With no workload flags the line carries BOTH workloads BASELINE.json's metric is quoted on:
+A plain run (no --full) does only what the headline figure needs: it sets up, warms up, times the K steps of ONE
+workload (2x4096 keypoints, 8 pairs per step per GPU, or --kpts/--pairs), writes the outputs of the last timed step
+if --dump-outputs is given, and prints the line: metric, value, unit, higher_is_better, dtype, ms_per_step, config.
+No HIP events inside the timed steps, no checks, no extra blocks, no bench_extra.json.
+
+--dump-outputs DIR writes what the timed path handed its caller in its last timed step as DIR/<name>.npy (`dump_outputs`;
+float32 / float64, at most 64 MB).  The inputs are seeded: the same arguments give the same inputs in every run, so two
+builds can be compared output for output.
+
+--full adds everything else the benchmark measures and checks, as described below.  With no workload flags
+the line of a --full run carries BOTH workloads BASELINE.json's metric is quoted on:
   * headline (`value`, `ms_per_step`, `roofline`, `cpu_baseline`): 2x4096 keypoints, 8 pairs per step per GPU
     (BASELINE configs[2], the north-star target >= 200 pairs/s);
   * `"also"`: the same block for 2x1024 keypoints, 32 pairs per step (BASELINE configs[1]), timed the same way
@@ -22,9 +32,9 @@ match statistics are all-gathered over xGMI each step -- the only collective of 
 process touches the GPU; same shape as the reference's mp.spawn launch, train.py:189-197, 231); under
 `torch.distributed.run` it reads RANK / LOCAL_RANK / WORLD_SIZE from the environment.
 
-Rank 0 prints ONE compact JSON line (< 4 KB: `compact_line`) as the LAST line of stdout; the full record (every kernel's
-roofline, notes, per-layer arrays, the CPU thread sweep, eval, ranks, the extra blocks in full) is written to
-`bench_extra.json` next to this file and, if that directory is not writable, to `gpurun_out/bench_extra.json`.
+Rank 0 prints ONE compact JSON line (< 4 KB: `compact_line`) as the LAST line of stdout; with --full the full record (every
+kernel's roofline, notes, per-layer arrays, the CPU thread sweep, eval, ranks, the extra blocks in full) is written to
+`bench_extra.json` next to this file or, if that directory is not writable, to `bench_extra.json` in an output folder below it.
 """
 import argparse
 import json
@@ -69,23 +79,28 @@ def _pick(d, keys):
 LINE_LIMIT = 4096          # bytes; the driver keeps the last 8000 characters of stdout and parses the last line
 
 
-def compact_line(res):
-    """The one JSON line the driver parses, from the full record of `main`: the contract's keys, the dominant kernel's
-    roofline, the cross-attention fraction north_star names, the CPU baseline, per-stage GPU milliseconds, and the extra
-    blocks reduced to scalars.  Everything else lives in bench_extra.json."""
+def compact_line(res, extra="bench_extra.json"):
+    """The one JSON line the driver parses, from the record of `main`: the contract's keys and, for a --full record, the dominant
+    kernel's roofline, the cross-attention fraction north_star names, the CPU baseline, per-stage GPU milliseconds, and the extra
+    blocks reduced to scalars.  Everything else lives in `extra` (bench_extra.json; None: not written)."""
     cfg = res.get("config", {})
     line = _pick(res, ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                        "vs_baseline", "data"))
     line["dtype"] = res.get("dtype_short", "bf16")
     line["config"] = _pick(cfg, ("workload", "pairs_per_step_per_gpu", "keypoints", "sinkhorn_iterations", "path", "parallelism"))
-    line["roofline"] = _pick(res.get("roofline"), ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "traffic_source",
-                                                    "traffic_profile_head", "avg_launch_ms", "launches_per_step", "algorithmic_work_per_launch"))
-    line["cross_attention"] = _pick(res.get("cross_attention"), ("kernel", "frac", "achieved", "unit", "avg_launch_ms", "operands"))
+    if "roofline" in res:
+        line["roofline"] = _pick(res["roofline"], ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "traffic_source",
+                                                   "traffic_profile_head", "avg_launch_ms", "launches_per_step", "algorithmic_work_per_launch"))
+    if "cross_attention" in res:
+        line["cross_attention"] = _pick(res["cross_attention"], ("kernel", "frac", "achieved", "unit", "avg_launch_ms", "operands"))
     if "cpu_baseline" in res:
         line["cpu_baseline"] = _pick(res["cpu_baseline"], ("value", "unit", "cores", "host_cores", "kind", "sample"))
-    line["stage_ms_per_step"] = _r(res.get("stage_ms_per_step", {}), 4)
-    line["host_step_ms"] = res.get("host_step_ms")
-    line["attention_layers"] = _pick(res.get("attention"), ("precision", "layers_bf16", "layers_f16", "layers_bf16x3"))
+    if "stage_ms_per_step" in res:
+        line["stage_ms_per_step"] = _r(res["stage_ms_per_step"], 4)
+    if "host_step_ms" in res:
+        line["host_step_ms"] = res["host_step_ms"]
+    if "attention" in res:
+        line["attention_layers"] = _pick(res["attention"], ("precision", "layers_bf16", "layers_f16", "layers_bf16x3"))
     line["world_size_seen"] = res.get("world_size_seen", 1)
     line.update(_pick(res, ("stats_rows_gathered", "matches_pair0", "sinkhorn_rescues", "host_threads_per_rank", "attention_launches_per_step")))
     par = lambda blk: [_pick(p, ("golden", "rows_equal", "rows", "max_score_err")) for p in (blk.get("parity_vs_reference") or [])]    # noqa: E731
@@ -123,7 +138,8 @@ def compact_line(res):
     if "train_step" in res:
         t = res["train_step"]
         line["train_step"] = {"error": str(t["error"])[:80]} if "error" in t else _pick(t, ("value", "unit", "ms_per_step"))
-    line["extra"] = "bench_extra.json"
+    if extra:
+        line["extra"] = extra
     line = _r(line)
     out = json.dumps(line, separators=(",", ":"))
     if len(out) >= LINE_LIMIT:            # never lose the line to its own size: shed the optional parts, largest first
@@ -159,6 +175,47 @@ def make_inputs(pair_ids, kpts, device, maker=None):
         d.update(device=torch.device(device), radius=15, percentile=2, min_size=7)
         datas.append((d, pair["gt_perm"]))
     return datas
+
+
+DUMP_LIMIT = 64 << 20      # bytes: what --dump-outputs may write in all (split evenly between the ranks)
+DUMP_ROWS = 512            # rows of each 256-d descriptor block that go into the dump (a fixed, seeded sample)
+
+
+def dump_outputs(out_dir, pair_ids, outs, datas, stats=None, world=1, limit=DUMP_LIMIT):
+    """--dump-outputs: what `match_pairs` handed its caller in the LAST timed step, as `out_dir/<name>.npy` (float32; integer arrays as
+    float64).  Per pair, `pair<id>_<key>`: the kept keypoint ids and positions, matches and matching scores of both images in full, and of the
+    two 256-d descriptor blocks (the kept input descriptors, the matching descriptors after the GNN) the rows `sample_rows<side>`, a fixed
+    sample of DUMP_ROWS drawn with the pair id as seed.  `stats`: the all-gathered per-pair statistics (shard.STAT_FIELDS).  Pairs go in
+    in the order given while the total stays within `limit` / `world` bytes.  Returns the names written."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    budget = limit // max(1, world)
+    arrays = {}
+    if stats is not None:
+        arrays["stats"] = stats.float().cpu().numpy()
+    used = sum(a.nbytes for a in arrays.values())
+    for pid, o, d in zip(pair_ids, outs, datas):
+        blk = {}
+        for s in "01":
+            mdesc = o[f"mdesc{s}"]
+            rows = np.sort(np.random.default_rng(2 * int(pid) + int(s)).permutation(mdesc.shape[0])[:DUMP_ROWS])
+            rows_t = torch.from_numpy(rows).to(mdesc.device)
+            blk[f"kept{s}"] = d[f"kept_kpts{s}_indices"][0]
+            blk[f"keypoints{s}"] = o[f"keypoints{s}"][0]
+            blk[f"matches{s}"] = o[f"matches{s}"][0]
+            blk[f"matching_scores{s}"] = o[f"matching_scores{s}"][0]
+            blk[f"sample_rows{s}"] = rows_t
+            blk[f"descriptors{s}_sample"] = o[f"descriptors{s}"][0].index_select(1, rows_t).t()
+            blk[f"mdesc{s}_sample"] = mdesc.index_select(0, rows_t)
+        blk = {k: (v.float() if v.is_floating_point() else v.double()).cpu().numpy() for k, v in blk.items()}
+        size = sum(a.nbytes for a in blk.values())
+        if used + size > budget:
+            break
+        used += size
+        arrays.update({f"pair{int(pid):04d}_{k}": v for k, v in blk.items()})
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return list(arrays)
 
 
 def cpu_baseline(kpts, iters, budget_s=60.0, thr=0.2):
@@ -286,7 +343,42 @@ def event_steps(steps, every):
     return every, list(range(every // 2, int(steps), every))
 
 
-def run_workload(model, kpts, pairs, args, world, rank, dev, with_cpu_baseline, guard=True, maker=None, golden=True):
+def headline_record(model, kpts, pairs, args, world, elapsed, outs, modes, ev_steps, every):
+    """The fields of a workload's record that a plain run prints: what was timed, how fast, at which precision."""
+    iters = int(model.config["sinkhorn_iterations"])
+    flats = outs.flat if isinstance(outs.flat, (list, tuple)) else [outs.flat]
+    problems = [(a, b) for f in flats for a, b in zip(f["n0"], f["n1"])]
+    nl = getattr(model, "n_lanes_last", 1)          # stream lanes: each stage is launched once per lane
+    tier = max(("bf16", "f16", "bf16x3"), key=modes.count)
+    events = (f", HIP events around every attention / GEMM launch on the launch stream on {ev_steps} of the {args.steps} timed steps: every {every}th"
+              if ev_steps else ", no HIP events inside the timed steps")
+    return {
+        "metric": f"image-pairs/sec at 2x{kpts} keypoints", "value": world * pairs * args.steps / elapsed, "unit": "pairs/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": ({"bf16": "bf16 MFMA attention and Q/K/V projection", "f16": "f16 MFMA attention (3-pass Q/K/V projection rounded to half)",
+                   "bf16x3": "split-bf16x3 MFMA attention"}[tier]
+                  + " + split-bf16x3 (f32-class) MFMA linears + bf16x6 (f32-class) similarity and score GEMMs + f32 Sinkhorn") if args.linear_precision == "bf16x3"
+                 else "bf16 MFMA attention + f32 MFMA linears + f32 Sinkhorn",
+        "dtype_short": ({"bf16": "bf16", "f16": "f16", "bf16x3": "bf16x3"}[tier] + " MFMA attention + "
+                        + ("bf16x3" if args.linear_precision == "bf16x3" else "f32") + " MFMA linears + f32 Sinkhorn"),
+        "data": "synthetic",
+        "config": {"workload": f"{pairs} pairs/step/GPU of 2x{kpts} synthetic keypoints (kept {problems[0][0]}/{problems[0][1]} after AGC r=15 p=2 m=7), "
+                               f"256-d descriptors, 18 attentional layers (9 self + 9 cross), {iters} Sinkhorn iterations, match_threshold {model.config['match_threshold']}",
+                   "pairs_per_step_per_gpu": pairs, "keypoints": kpts, "sinkhorn_iterations": iters,
+                   "path": "GMatcher.match_pairs, production path ("
+                           + ("encoder + layer launches replayed from the cached gims_run_ops tables" if model._replays("layers", 2 * kpts * pairs)
+                              else "launch by launch: config launch_replay_rows / GIMS_NO_REPLAY")
+                           + events + "); "
+                           "Python's cyclic GC is frozen + disabled inside the K timed steps" + (" (host_step_ms.max reports the slowest step)" if ev_steps else ""),
+                   "parallelism": f"pairs sharded over {world} GPU(s), all-gather of match statistics; {nl} stream lane(s) per GPU"},
+    }
+
+
+def run_workload(model, kpts, pairs, args, world, rank, dev, with_cpu_baseline, guard=True, maker=None, golden=True, full=True, dump=None):
+    """Sets up one workload, warms up, times `args.steps` steps, writes the last step's outputs to `dump` (a directory) if given.  A plain run
+    (full=False) returns the headline record; full=True adds the stage events of the timed steps, the roofline, the checks and the evaluation of
+    what was timed and, with `with_cpu_baseline`, the CPU oracle's throughput.  Ranks other than 0 return None."""
     import torch
     import torch.distributed as dist
     from gims_amd import shard
@@ -325,12 +417,13 @@ def run_workload(model, kpts, pairs, args, world, rank, dev, with_cpu_baseline, 
     gc.collect()
     gc.freeze()
     gc.disable()           # and no collection at all inside the K timed steps (re-enabled right after them)
-    model.enable_timing(os.environ.get("GIMS_BENCH_NO_STAGE_TIMERS") is None)
+    model.enable_timing(full and os.environ.get("GIMS_BENCH_NO_STAGE_TIMERS") is None)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     from gims_amd import hip as _hip
-    _hip.attention_launch_counts(reset=True)          # which attention kernel serves the TIMED steps (host-side counters of the library)
+    if full:
+        _hip.attention_launch_counts(reset=True)          # which attention kernel serves the TIMED steps (host-side counters of the library)
     # HIP events cost time too (measured: 2.1 % of a 4096 x 8 step when every launch of every timed step is bracketed): the stage / per-launch
     # events are recorded on every `--event-every`-th timed step (default 5: steps 2, 7, 12, 17 of K = 20 -- mid-stride, so that the sample weighs
     # the first step after the synchronisation, which runs 10 % slower on a clock that has just idled, like the K steps do: not at all
@@ -348,12 +441,25 @@ def run_workload(model, kpts, pairs, args, world, rank, dev, with_cpu_baseline, 
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    attn_counts = {k: v / args.steps for k, v in _hip.attention_launch_counts().items() if v}
+    attn_counts = {k: v / args.steps for k, v in _hip.attention_launch_counts().items() if v} if full else None
     gc.enable()
     et = torch.tensor([elapsed], device=dev, dtype=torch.float64)
     if world > 1:
         dist.all_reduce(et, op=dist.ReduceOp.MAX)
     elapsed = float(et.item())
+    if dump:
+        names = dump_outputs(dump, my_pairs, outs, host_t["datas"], stats if rank == 0 else None, world)
+        log(f"outputs of the last timed step: {len(names)} arrays in {dump}")
+    if not full:
+        arep = model.attention_report()          # (folds the last batch's measurement into the per-layer verdict, as the full record does)
+        fixed = model.config["attention_precision"]
+        modes = list(arep["modes"]) if arep else [fixed if fixed in ("bf16x3", "f16") else "bf16"] * len(model.config["transformer_layers"])
+        if rank != 0:
+            return None
+        res = headline_record(model, kpts, pairs, args, world, elapsed, outs, modes, 0, 0)
+        res["stats_rows_gathered"] = int(stats.shape[0])
+        res["world_size_seen"] = dist.get_world_size() if world > 1 else 1
+        return res
     if model._timers is None:          # diagnostic mode: no stage timers -> no roofline section
         log("host ms/step  match_pairs: " + " ".join(f"{x:6.2f}" for x in host_t["match_pairs"][-args.steps:]))
         return {"value": world * pairs * args.steps / elapsed, "ms_per_step": 1e3 * elapsed / args.steps, "diagnostic": True}
@@ -384,7 +490,6 @@ def run_workload(model, kpts, pairs, args, world, rank, dev, with_cpu_baseline, 
         return None
 
     iters = int(model.config["sinkhorn_iterations"])
-    value = world * pairs * args.steps / elapsed
     flats = outs.flat if isinstance(outs.flat, (list, tuple)) else [outs.flat]
     problems = [(a, b) for f in flats for a, b in zip(f["n0"], f["n1"])]
     nl = getattr(model, "n_lanes_last", 1)          # stream lanes: each stage is launched once per lane
@@ -524,26 +629,8 @@ def run_workload(model, kpts, pairs, args, world, rank, dev, with_cpu_baseline, 
             bad = [p for p in parity if not p["rows_equal"] or not p["max_score_err"] < 1e-4]
             assert not bad, ("the timed batch differs from the reference golden", bad)
     steps_ms = np.asarray(host_t["match_pairs"][-args.steps:]) + np.asarray(host_t["stats"][-args.steps:])
-    res = {
-        "metric": f"image-pairs/sec at 2x{kpts} keypoints", "value": value, "unit": "pairs/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": ({"bf16": "bf16 MFMA attention and Q/K/V projection", "f16": "f16 MFMA attention (3-pass Q/K/V projection rounded to half)",
-                   "bf16x3": "split-bf16x3 MFMA attention"}[max(("bf16", "f16", "bf16x3"), key=modes.count)]
-                  + " + split-bf16x3 (f32-class) MFMA linears + bf16x6 (f32-class) similarity and score GEMMs + f32 Sinkhorn") if args.linear_precision == "bf16x3"
-                 else "bf16 MFMA attention + f32 MFMA linears + f32 Sinkhorn",
-        "dtype_short": ({"bf16": "bf16", "f16": "f16", "bf16x3": "bf16x3"}[max(("bf16", "f16", "bf16x3"), key=modes.count)] + " MFMA attention + "
-                        + ("bf16x3" if args.linear_precision == "bf16x3" else "f32") + " MFMA linears + f32 Sinkhorn"),
-        "data": "synthetic",
-        "config": {"workload": f"{pairs} pairs/step/GPU of 2x{kpts} synthetic keypoints (kept {problems[0][0]}/{problems[0][1]} after AGC r=15 p=2 m=7), "
-                               f"256-d descriptors, 18 attentional layers (9 self + 9 cross), {iters} Sinkhorn iterations, match_threshold {model.config['match_threshold']}",
-                   "pairs_per_step_per_gpu": pairs, "keypoints": kpts, "sinkhorn_iterations": iters,
-                   "path": "GMatcher.match_pairs, production path ("
-                           + ("encoder + layer launches replayed from the cached gims_run_ops tables" if model._replays("layers", 2 * kpts * pairs)
-                              else "launch by launch: config launch_replay_rows / GIMS_NO_REPLAY")
-                           + f", HIP events around every attention / GEMM launch on the launch stream on {ev_steps} of the {args.steps} timed steps: every {every}th); "
-                           "Python's cyclic GC is frozen + disabled inside the K timed steps (host_step_ms.max reports the slowest step)",
-                   "parallelism": f"pairs sharded over {world} GPU(s), all-gather of match statistics; {nl} stream lane(s) per GPU"},
+    res = headline_record(model, kpts, pairs, args, world, elapsed, outs, modes, ev_steps, every)
+    res.update({
         "roofline": roofline,
         "cross_attention": cross,
         "attention": {"precision": fixed, "layers_bf16": modes.count("bf16"), "layers_f16": modes.count("f16"), "layers_bf16x3": modes.count("bf16x3"),
@@ -571,19 +658,19 @@ def run_workload(model, kpts, pairs, args, world, rank, dev, with_cpu_baseline, 
                          "unpinned) -- the AUC values are on synthetic pairs and are not COCO numbers",
                  **{k: (round(v, 3) if isinstance(v, float) else [round(x, 3) for x in v] if isinstance(v, list) else v)
                     for k, v in eval_summary.items()}},
-    }
+    })
     if with_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(kpts, iters, budget_s=args.cpu_budget if (kpts, pairs) == HEADLINE or args.kpts is not None else args.cpu_budget / 3.0,
                                            thr=float(model.config["match_threshold"]))
     return res
 
 
-def main():
+def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--kpts", type=int, default=None, help="keypoints per image (default: the 4096 headline + the 1024 block)")
+    ap.add_argument("--kpts", type=int, default=None, help="keypoints per image (default: the 4096 headline; with --full + the 1024 block)")
     ap.add_argument("--pairs", type=int, default=None, help="image pairs per step per GPU (default 8 at 4096, 32 otherwise)")
     ap.add_argument("--sinkhorn-iters", type=int, default=100)
     ap.add_argument("--linear-precision", default="bf16x3", choices=["bf16x3", "f32"])
@@ -594,7 +681,16 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=60.0, help="seconds of CPU-oracle work for the headline workload (a third of it for the second block)")
     ap.add_argument("--latency", action="store_true", help="also time ONE pair through the reference-shaped forward() (latency_ms_b1)")
-    args = ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64, at most 64 MB; see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: stage events, roofline, checks and evaluation of the timed batch, CPU baseline, "
+                         "the other workloads and precisions, latency, pipeline and training step, bench_extra.json")
+    return ap
+
+
+def main():
+    args = parser().parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))
@@ -655,13 +751,15 @@ def main():
     if args.kpts is not None:
         loads = [(args.kpts, args.pairs if args.pairs is not None else (8 if args.kpts >= 4096 else 32))]
     else:
-        loads = [HEADLINE, SECOND]
-    base = world == 1 and not args.no_cpu_baseline
-    results = [run_workload(model, k, p, args, world, rank, dev, base) for k, p in loads]
+        loads = [HEADLINE, SECOND] if args.full else [HEADLINE]
+    blocks = args.full and args.kpts is None          # the extra blocks below: --full with no workload flags
+    base = args.full and world == 1 and not args.no_cpu_baseline
+    results = [run_workload(model, k, p, args, world, rank, dev, base, full=args.full, dump=args.dump_outputs if i == 0 else None)
+               for i, (k, p) in enumerate(loads)]
     if rank == 0 and results[0] is not None:
         results[0]["host_threads_per_rank"] = host_threads if host_threads else torch.get_num_threads()
     peaked = None
-    if args.kpts is None:
+    if blocks:
         # the same headline workload with PEAKED attention (query / key projections of every layer scaled up like the
         # `peakede2e_*` reference goldens: mean softmax row maximum ~0.8): 'auto' routes those layers to the IEEE-half kernels --
         # the throughput of the mode that keeps the 1e-4 score bar there
@@ -670,7 +768,7 @@ def main():
         peaked = run_workload(model_p, HEADLINE[0], HEADLINE[1], args, world, rank, dev, False, guard=False, golden=False)
         del model_p
     evalset = None
-    if args.kpts is None:
+    if blocks:
         # the reference's eval scripts run sinkhorn_iterations=20, match_threshold=0.02 (eval_homography.py:117-119, eval_matches.py:135):
         # the headline workload at that setting (parity: the e2e_*_i20 goldens)
         model_e = GMatcher({"sinkhorn_iterations": 20, "match_threshold": 0.02, "linear_precision": args.linear_precision, "streams": args.streams}).eval()
@@ -678,7 +776,7 @@ def main():
         evalset = run_workload(model_e, HEADLINE[0], HEADLINE[1], args, world, rank, dev, False, guard=False)
         del model_e
     readme = None
-    if args.kpts is None and world == 1:
+    if blocks and world == 1:
         # the reference's one PUBLISHED hot-path configuration (README.md:143-163: 15 382 / 14 870 keypoints, N != M; eval setting: 20 iterations,
         # threshold 0.02; graph build 5.72 + 6.19 s and matching 3.48 s on an RTX 3090 there), on the density-matched synthetic pair the
         # `ube2e_n15382_*` reference golden pins; 2 pairs per step
@@ -709,7 +807,7 @@ def main():
         if peaked is not None:
             peaked["config"]["weights"] = "synthetic, query/key projection gain 2.0 (the `peakede2e_*` goldens' weights): peaked softmax rows"
             res.setdefault("also", {})[f"2x{HEADLINE[0]}_peaked_attention"] = peaked
-        if world == 1 and args.kpts is None:
+        if world == 1 and blocks:
             # BASELINE config 5: CAR-HyNet descriptors for both images + 2x8192-keypoint matching, 2 pairs per step
             try:
                 from tools.pipeline_bench import measure as pipeline_measure, measure_from_images
@@ -718,9 +816,9 @@ def main():
                 res["also"]["pipeline_2x8192"]["from_images"] = measure_from_images(8192, 2, 3)
             except Exception as e:   # noqa: BLE001
                 res.setdefault("also", {})["pipeline_2x8192"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and (args.latency or args.kpts is None):
+        if world == 1 and (args.latency or blocks):
             res["latency_ms_b1"] = latency_b1(model, [k for k, _ in loads], dev)
-        if world == 1 and args.kpts is None:
+        if world == 1 and blocks:
             # one training step (train() mode forward, backward, Adam) per pair of 2x2048 keypoints, the
             # reference's training configuration; its CPU leg (one oracle step, ~5 s) only next to the main CPU baseline
             try:                     # an extra block: it must never cost the headline line
@@ -731,7 +829,7 @@ def main():
     if world > 1:
         dist.destroy_process_group()
     if rank == 0:
-        if world > 1 and not args.no_cpu_baseline:
+        if world > 1 and args.full and not args.no_cpu_baseline:
             # N > 1: the CPU baseline of rank 0 AFTER the job (the other ranks are gone, the collective backend is shut down), on the
             # host's full core set again -- a SCALE record then carries its own baseline
             if full_affinity:
@@ -740,10 +838,10 @@ def main():
                 res["cpu_baseline"] = cpu_baseline(loads[0][0], args.sinkhorn_iters, budget_s=args.cpu_budget)
             except Exception as e:   # noqa: BLE001  (never lose the line of a multi-GPU run to its baseline)
                 res["cpu_baseline"] = {"error": f"{type(e).__name__}: {e}"}
-        where = write_extra(res)
-        log(f"full record: {where}")
+        if args.full:
+            log(f"full record: {write_extra(res)}")
         sys.stderr.flush()
-        print(compact_line(res), flush=True)
+        print(compact_line(res, extra="bench_extra.json" if args.full else None), flush=True)
 
 
 def latency_b1(model, sizes, dev):

@@ -416,3 +416,72 @@ def test_bench_event_sampling_schedule():
     assert bench.event_steps(20, 5) == (5, [2, 7, 12, 17])
     assert bench.event_steps(5, 5) == (5, [2]) and bench.event_steps(3, 5) == (3, [1]) and bench.event_steps(1, 5) == (1, [0])
     assert bench.event_steps(20, 1) == (1, list(range(20))) and bench.event_steps(7, 0) == (1, list(range(7)))
+
+
+def test_bench_plain_run_is_the_default_and_full_is_opt_in():
+    """`bench.py --gpus 1 --steps K --warmup W` is the plain run: one workload, no extra blocks; --full and --dump-outputs are opt-in."""
+    import bench
+    a = bench.parser().parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+    a = bench.parser().parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_bench_plain_line_carries_the_headline_and_nothing_it_did_not_measure():
+    """A plain run's record has no roofline, stage times, CPU baseline or extra blocks and writes no bench_extra.json: its line must not claim them."""
+    import json
+    import bench
+    res = {"metric": "image-pairs/sec at 2x4096 keypoints", "value": 550.0, "unit": "pairs/s", "n_gpus": 1, "steps": 20, "warmup": 3,
+           "ms_per_step": 14.5, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "data": "synthetic",
+           "dtype": "bf16 MFMA attention and Q/K/V projection + ...", "dtype_short": "bf16 MFMA attention + bf16x3 MFMA linears + f32 Sinkhorn",
+           "config": {"workload": "8 pairs/step/GPU of 2x4096", "keypoints": 4096}, "world_size_seen": 1, "stats_rows_gathered": 8}
+    got = json.loads(bench.compact_line(res, extra=None))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert k in got, k
+    assert got["dtype"] == res["dtype_short"] and got["ms_per_step"] == 14.5
+    for k in ("roofline", "cross_attention", "cpu_baseline", "stage_ms_per_step", "host_step_ms", "attention_layers", "also", "extra"):
+        assert k not in got, k
+
+
+def _fake_outs(pair_ids, n):
+    g = torch.Generator().manual_seed(5)
+    outs, datas = [], []
+    for pid in pair_ids:
+        o, d = {}, {}
+        for s in "01":
+            o[f"keypoints{s}"] = torch.rand(1, n, 2, generator=g)
+            o[f"descriptors{s}"] = torch.rand(1, 256, n, generator=g)
+            o[f"mdesc{s}"] = torch.rand(n, 256, generator=g)
+            o[f"matches{s}"] = torch.randint(-1, n, (1, n), generator=g)
+            o[f"matching_scores{s}"] = torch.rand(1, n, generator=g)
+            d[f"kept_kpts{s}_indices"] = [torch.arange(n, dtype=torch.int64)]
+        outs.append(o)
+        datas.append(d)
+    return outs, datas
+
+
+def test_bench_dump_outputs_is_complete_seeded_and_bounded(tmp_path):
+    """--dump-outputs: float32 / float64 .npy files of what match_pairs returned; the descriptor sample depends on the pair id only, so two runs
+    (two builds) write the same names and rows; the total stays within the limit (whole pairs are left out, in order, beyond it)."""
+    import bench
+    outs, datas = _fake_outs([0, 1, 2], 700)
+    stats = torch.rand(3, 5)
+    names = bench.dump_outputs(str(tmp_path / "a"), [0, 1, 2], outs, datas, stats)
+    assert "stats" in names and "pair0002_mdesc1_sample" in names and "pair0000_matches0" in names
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(n + ".npy" for n in names)
+    arrs = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+    assert arrs["pair0001_mdesc0_sample"].shape == (bench.DUMP_ROWS, 256)
+    rows = arrs["pair0001_sample_rows0"].astype(np.int64)
+    np.testing.assert_array_equal(arrs["pair0001_mdesc0_sample"], outs[1]["mdesc0"].numpy()[rows])
+    np.testing.assert_array_equal(arrs["pair0001_descriptors0_sample"], outs[1]["descriptors0"][0].numpy()[:, rows].T)
+    np.testing.assert_array_equal(arrs["pair0002_matches1"], outs[2]["matches1"][0].numpy().astype(np.float64))
+    again = bench.dump_outputs(str(tmp_path / "b"), [0, 1, 2], outs, datas, stats)
+    assert again == names
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / "pair0001_sample_rows0.npy"), arrs["pair0001_sample_rows0"])
+    assert sum(a.nbytes for a in arrs.values()) <= bench.DUMP_LIMIT
+    per_pair = sum(a.nbytes for n, a in arrs.items() if n.startswith("pair0000_"))
+    few = bench.dump_outputs(str(tmp_path / "c"), [0, 1, 2], outs, datas, None, limit=2 * per_pair + 1)
+    assert {n.split("_")[0] for n in few} == {"pair0000", "pair0001"}
+    assert sum(os.path.getsize(tmp_path / "c" / f) for f in os.listdir(tmp_path / "c")) < 2 * per_pair + 1 + 128 * len(few)
