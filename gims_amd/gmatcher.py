@@ -505,14 +505,16 @@ class GMatcher(nn.Module):
     _lane = 0
 
     # ------------------------------------------------------------------ ragged core: 2P images -> P pair results
-    def _run(self, images, radius, percentile, min_size):
+    def _run(self, images, radius, percentile, min_size, delaunay=False):
         """images: list of dicts {kp (N,2) f32, de (N,D) f32 point-major, sc (N,), shape}; consecutive entries
         (2p, 2p+1) form pair p.  Every pair may keep a different number of keypoints (ragged batch)."""
-        return self._run_rest(self._run_build(images, radius, percentile, min_size))
+        return self._run_rest(self._run_build(images, radius, percentile, min_size, delaunay=delaunay))
 
-    def _run_build(self, images, radius, percentile, min_size, robust=False):
+    def _run_build(self, images, radius, percentile, min_size, robust=False, delaunay=False):
         """Phase 1: enqueue the adaptive graph construction (asynchronous; no host sync).  robust: the graph build histograms every
-        similarity instead of predicting where the percentile lies (the repeat after a build reported a missed prediction)."""
+        similarity instead of predicting where the percentile lies (the repeat after a build reported a missed prediction).
+        delaunay: D-GIMS -- the Delaunay triangulation of the keypoints instead (gims_delaunay_build: every keypoint kept; radius,
+        percentile and min_size have no effect); it fills the same kept / indptr / indices / info slots."""
         cfg = self.config
         dev = images[0]["kp"].device
         D = cfg['descriptor_dim']
@@ -535,8 +537,11 @@ class GMatcher(nn.Module):
             info_all = torch.empty((len(images), 8), dtype=torch.int32, device=dev)
             agc_imgs = hip.make_agc_images([dict(kpts=g["kp"], desc=g["de"], kept=g["kept"], indptr=g["indptr"],
                                                  indices=g["indices"], info=info_all[i]) for i, g in enumerate(images)])
-            aflags = hip.AGC_ROBUST if robust else 0        # (the default flow never stores the N x N half matrix: half the workspace)
-            hip.agc_build(agc_imgs, radius, percentile, min_size, self._buf("agc", hip.agc_workspace_bytes(agc_imgs, aflags)), flags=aflags)
+            if delaunay:
+                hip.delaunay_build(agc_imgs, self._buf("delaunay", hip.delaunay_workspace_bytes(agc_imgs)))
+            else:
+                aflags = hip.AGC_ROBUST if robust else 0        # (the default flow never stores the N x N half matrix: half the workspace)
+                hip.agc_build(agc_imgs, radius, percentile, min_size, self._buf("agc", hip.agc_workspace_bytes(agc_imgs, aflags)), flags=aflags)
             # everything of the next stage that does not depend on the kept counts is prepared NOW, while the GPU builds the
             # graphs: after the host sync only two cumsums stand between the counts and the next launch
             ptab = hip.pack_table([(g["kp"].data_ptr(), g["de"].data_ptr(), g["de"].stride(0), g["sc"].data_ptr(),
@@ -554,16 +559,25 @@ class GMatcher(nn.Module):
                         indptr=torch.empty((n_up + 1,), dtype=torch.int32, device=dev),
                         indices=torch.empty((ec * n_up + 1,), dtype=torch.int32, device=dev))
         return dict(images=images, info_all=info_all, pool=pool, ptab=ptab, norm3=norm3, bufs=bufs, params=(radius, percentile, min_size),
-                    robust=robust)
+                    robust=robust, delaunay=delaunay)
 
     _edge_cap = 64
 
     @staticmethod
-    def _agc_retry(flags, robust):
+    def _agc_retry(flags, robust, delaunay=False):
         """What to do with the flag words (info[7]) of a graph build: 'robust' -- some image's predicted percentile window was missed: ALL its
         outputs are void, its overflow bit included (a void threshold can keep any number of edges), so this comes first; 'grow' -- an edge
-        buffer overflowed; None -- the build stands.  A robust build cannot report a miss."""
+        buffer overflowed; None -- the build stands.  A robust build cannot report a miss.  A Delaunay build (delaunay=True) is never
+        repeated as robust: a degenerate image raises ValueError (the reference raises scipy's QhullError there), stars that disagree raise."""
         flags = np.asarray(flags)
+        if delaunay:
+            bad = np.nonzero(flags & hip.DT_INFO_DEGENERATE)[0]
+            if len(bad):
+                i = int(bad[0])
+                raise ValueError(f"delaunay: image {i} of the batch (pair {i // 2}, keypoints{i % 2}) has fewer than 3 distinct keypoints, "
+                                 "all its keypoints on one line, or a non-finite coordinate: it has no Delaunay triangulation")
+            if (flags & (hip.DT_INFO_ASYMMETRIC | hip.AGC_INFO_WINDOW_MISSED)).any():
+                raise hip.GimsHipError("delaunay graph: the per-point stars of a build did not agree (asymmetric adjacency)")
         if (flags & hip.AGC_INFO_WINDOW_MISSED).any():
             if robust:
                 raise hip.GimsHipError("adaptive graph: the robust flow reported a missed percentile window")
@@ -591,7 +605,7 @@ class GMatcher(nn.Module):
         torch.cuda.current_stream().synchronize()
         infos = pin[:info_all.shape[0]].numpy().copy()
         self._sync_ms = 1e3 * (time.perf_counter() - ts0)
-        action = self._agc_retry(infos[:, 7], bool(ctx.get("robust")))
+        action = self._agc_retry(infos[:, 7], bool(ctx.get("robust")), bool(ctx.get("delaunay")))
         if action == "robust":
             # the percentile window predicted from the similarity sample did not provably hold the threshold (gims_agc_build_ex): the
             # outputs of this build are void; the repeat histograms every similarity
@@ -670,7 +684,7 @@ class GMatcher(nn.Module):
         St = lambda name: GMatcher._Stage(self, name)   # noqa: E731
         G = self._gather(ctx)
         if G is None:
-            return self._run_rest(self._run_build(images, *ctx["params"]))
+            return self._run_rest(self._run_build(images, *ctx["params"], delaunay=bool(ctx.get("delaunay"))))
         feat, kpts_all, score_all, seg = G["feat"], G["kpts_all"], G["score_all"], G["seg"]
         indptr_all, indices_all, norm3, n_tot = G["indptr_all"], G["indices_all"], G["norm3"], G["n_tot"]
         # ---- GraphSAGE over the merged CSR of all images (gmatcher.py:145-162, 268-269)
@@ -1051,8 +1065,8 @@ class GMatcher(nn.Module):
         return uv[torch.from_numpy(self._status_offs).to(uv.device)].cpu().numpy()
 
     def _check_call(self, data, kwargs):
-        if data.get('delaunay', False):
-            raise NotImplementedError("delaunay=True is broken in the reference snapshot (UnboundLocalError, gmatcher.py:250)")
+        if data.get('delaunay', False) and kwargs.get('mode', 'test') == "train":
+            raise NotImplementedError("D-GIMS training (delaunay=True with mode='train') is not supported")
         if data['keypoints0'].device.type != "cuda":
             raise hip.GimsHipError("GMatcher runs on the GPU only (no CPU fallback): move the inputs to 'cuda'")
 
@@ -1080,7 +1094,7 @@ class GMatcher(nn.Module):
         'auto' table up -- the batch ran that layer on operands that did not suffice and the caller repeats it on the new table."""
         images = self._ingest([(data['keypoints' + side][b], data['descriptors' + side][b], data['scores' + side][b],
                                 data['image' + side].shape) for b in range(B) for side in ("0", "1")])
-        items, pairs, mdesc = self._run(images, radius, percentile, min_size)
+        items, pairs, mdesc = self._run(images, radius, percentile, min_size, delaunay=bool(data.get('delaunay', False)))
         # what the host needs back -- the kept-index lists the reference returns as Python lists, and the Sinkhorn status words --
         # travels in asynchronous copies into one pinned buffer behind ONE stream synchronisation (three blocking read-backs cost
         # ~0.1 ms of a 5 ms single-pair call)
@@ -1205,6 +1219,11 @@ class GMatcher(nn.Module):
                 raise ValueError(f"match_pairs: pair {i} asks for radius / percentile / min_size = "
                                  f"{(data.get('radius', 25), data.get('percentile', 7), data.get('min_size', 8))}, pair 0 for {params}; "
                                  "all pairs of one call share the adaptive-graph parameters (call match_pairs once per setting)")
+        delaunay = bool(d0.get('delaunay', False))
+        for i, data in enumerate(datas):
+            if bool(data.get('delaunay', False)) != delaunay:
+                raise ValueError(f"match_pairs: pair {i} asks for delaunay={bool(data.get('delaunay', False))}, pair 0 for delaunay={delaunay}; "
+                                 "all pairs of one call share the graph construction (call match_pairs once per setting)")
         cur = torch.cuda.current_stream()
         if n_lanes > 1:
             # independent sub-batches on separate HIP streams: the HBM-bound stages of one lane (Sinkhorn, epilogues) overlap
@@ -1220,7 +1239,7 @@ class GMatcher(nn.Module):
                 self._lane = gi
                 raw = [(data['keypoints' + side][0], data['descriptors' + side][0], data['scores' + side][0], data['image' + side].shape)
                        for data in grp for side in ("0", "1")]
-                ctxs.append(self._run_build(self._ingest(raw), *params))
+                ctxs.append(self._run_build(self._ingest(raw), *params, delaunay=delaunay))
         tm1 = time.perf_counter()
         outs, flats = [], []
         for gi, grp in enumerate(groups):

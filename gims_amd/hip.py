@@ -214,6 +214,8 @@ _SIGNATURES = {
                                  C.c_size_t, C.c_void_p]),
     "gims_agc_build_ex": (C.c_int, [C.POINTER(AgcImage), C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_void_p,
                                     C.c_size_t, C.c_void_p]),
+    "gims_delaunay_workspace_bytes": (C.c_size_t, [C.POINTER(AgcImage), C.c_int32]),
+    "gims_delaunay_build": (C.c_int, [C.POINTER(AgcImage), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "gims_ingest_images": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
     "gims_pack_graphs": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
@@ -694,11 +696,17 @@ def gather_rows(src, idx, out):
 
 
 def make_agc_images(items):
-    """items: dicts with kpts [n,2], desc [n,d] (point-major f32), kept [n], indptr [n+1], indices [cap], info [8]."""
+    """items: dicts with kpts [n,2], desc [n,d] (point-major f32), kept [n], indptr [n+1], indices [cap], info [8].
+    desc may be None for delaunay_build (which reads keypoints only)."""
     arr = (AgcImage * len(items))()
     for i, it in enumerate(items):
-        de = it["desc"]
-        assert de.stride(1) == 1 and it["kpts"].is_contiguous()
+        de = it.get("desc")
+        assert it["kpts"].is_contiguous()
+        if de is None:
+            arr[i] = AgcImage(_p(_dev(it["kpts"], torch.float32)), None, 0, it["kpts"].shape[0], 0,
+                              _p(it["kept"]), _p(it["indptr"]), _p(it["indices"]), it["indices"].numel(), _p(it["info"]))
+            continue
+        assert de.stride(1) == 1
         arr[i] = AgcImage(_p(_dev(it["kpts"], torch.float32)), _p(_dev(de, torch.float32)), de.stride(0), de.shape[0], de.shape[1],
                           _p(it["kept"]), _p(it["indptr"]), _p(it["indices"]), it["indices"].numel(), _p(it["info"]))
     return arr
@@ -730,6 +738,25 @@ def agc_build(images, radius, percentile, min_size, work: torch.Tensor, flags=0)
     lib = load()
     _check(lib.gims_agc_build_ex(images, len(images), float(radius), float(percentile), int(min_size), int(flags), _p(work),
                                  work.numel() * work.element_size(), _stream()), "gims_agc_build_ex")
+
+
+DT_INFO_DEGENERATE, DT_INFO_ASYMMETRIC = 4, 8     # bits of info[7] set by delaunay_build (bit 0: AGC_INFO_OVERFLOW, same meaning)
+
+
+def delaunay_workspace_bytes(images) -> int:
+    """Scratch bytes of delaunay_build(images, ...)."""
+    nmax = max(int(im.n) for im in images)
+    if nmax > agc_max_keypoints():
+        raise GimsHipError(f"delaunay graph: an image has {nmax} keypoints, more than the library's limit of {agc_max_keypoints()} per image "
+                           "(gims_agc_max_keypoints) -- reduce max_keypoints or split the image")
+    return int(load().gims_delaunay_workspace_bytes(images, len(images)))
+
+
+def delaunay_build(images, work: torch.Tensor):
+    """Asynchronous Delaunay-graph build (D-GIMS) for a batch of images made by make_agc_images; see include/gims_hip.h.  After the stream
+    is synchronised, info[7] must be checked: DT_INFO_DEGENERATE / DT_INFO_ASYMMETRIC / AGC_INFO_OVERFLOW void the image's graph."""
+    lib = load()
+    _check(lib.gims_delaunay_build(images, len(images), _p(work), work.numel() * work.element_size(), _stream()), "gims_delaunay_build")
 
 
 def _upload_structs(arr, device):

@@ -358,6 +358,29 @@ int gims_agc_build(const gims_agc_image* h_images /* HOST array */, int32_t n_im
 int gims_agc_build_ex(const gims_agc_image* h_images /* HOST array */, int32_t n_images, double radius, double percentile,
                       int32_t min_size, int32_t flags, void* work, size_t work_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Delaunay graph construction for a BATCH of images (D-GIMS: the reference's build_graph_from_keypoints_Delaunay, models/agc.py:718-751,
+ * which forward() calls instead of the adaptive build when data['delaunay'] is set), every stage one launch for all images (blockIdx.y =
+ * image), no host synchronisation.  Same image descriptor as gims_agc_build; `desc` / `ldd` / `d` are not read.
+ * Per image: the Delaunay triangulation of kpts [n][2] f32 as an undirected graph, written as a bidirectional CSR in ORIGINAL keypoint ids
+ * (neighbours ascending): kept[n] = 0..n-1, indptr[n+1], indices[max_edges_dir]; info[8] = {n_kept = n, n_dir_edges, n_undirected_edges,
+ * n_duplicates, n_hull_vertices, n_exact_fallbacks, 0, flags}.
+ *   Exact duplicate coordinates: the LOWEST id of each group of identical (x, y) is the vertex, the others are isolated (degree 0).
+ *   Cocircular ties: resolved by a symbolic perturbation of the lifted coordinate by id (gims_amd/csrc/delaunay_pred.h states the rule): one
+ *   deterministic triangulation.  Predicates are exact (float64 filter, exact expansion fallback; n_exact_fallbacks counts the points
+ *   whose star needed the fallback).
+ *   flags: bit 0 = the directed edges did not fit max_edges_dir (n_dir_edges says how many there are; the CSR is void);
+ *          bit 2 (GIMS_DT_INFO_DEGENERATE) = fewer than 3 distinct points, all points collinear, or a non-finite coordinate: no triangulation;
+ *          bit 3 (GIMS_DT_INFO_ASYMMETRIC) = the stars did not agree (an edge present in one direction only): the result must not be used.
+ * `work` is scratch of at least gims_delaunay_workspace_bytes(images, n_images) bytes (about 46 bytes per keypoint).
+ * LIMIT: 1 <= n <= gims_agc_max_keypoints() = 32768 keypoints per image (GIMS_EINVAL outside).
+ * Asynchronous; read info[] after synchronising the stream.
+ */
+#define GIMS_DT_INFO_DEGENERATE 4
+#define GIMS_DT_INFO_ASYMMETRIC 8
+size_t gims_delaunay_workspace_bytes(const gims_agc_image* h_images /* HOST array */, int32_t n_images);
+int gims_delaunay_build(const gims_agc_image* h_images /* HOST array */, int32_t n_images, void* work, size_t work_bytes, void* stream);
+
 /* Ingest a batch of images given in the reference's layout (descriptors channel-major (D,N), gmatcher.py:245) into
  * one row-concatenated point-major buffer: desc_out[row_off_i + n, :] = desc_i[:, n], same for keypoints and scores.
  * One launch for the whole batch (64x64 LDS-tile transpose). */
