@@ -11,6 +11,11 @@ Keypoint DETECTION stays what the caller provides: ``detector(img) -> keypoints`
 ``pt, size, angle, response, octave``, or a structured array with those fields); by default OpenCV's SIFT with the
 reference's parameters when ``cv2`` is importable.  The patch arithmetic restates OpenCV's uint8 fixed-point resampling;
 it is PARITY UNPINNED against OpenCV itself (see csrc/patches.hip and DESIGN.md).
+
+``sift_detect_device`` is the detector on the device (csrc/sift.hip, OpenCV 4.x SIFT detect restated): it returns
+per image a dict of device tensors that ``keypoint_arrays``, ``filter_max_num``, ``pad_training_keypoints`` and
+``extract_patches`` take without a host round trip.  ``device_front_end`` is ``sift_forward_device`` with that detector, batched
+over ``data['image']``; ``Matching({'front_end': frontend.device_front_end})`` selects it (the default stays OpenCV's).
 """
 from __future__ import annotations
 
@@ -20,9 +25,19 @@ import torch
 from . import hip
 
 
+def _is_device_dict(kps):
+    return isinstance(kps, dict) and torch.is_tensor(kps.get("pt"))
+
+
 def keypoint_arrays(kps):
     """cv2.KeyPoint-like objects (or a structured array / dict of arrays) -> (kp4 float32 [n, 4] = x, y, size, angle;
-    octave int32 [n]; response float32 [n])."""
+    octave int32 [n]; response float32 [n]).  A dict of tensors (what sift_detect_device returns) gives tensors on its device."""
+    if _is_device_dict(kps):
+        pt = kps["pt"].reshape(-1, 2).float()
+        kp4 = torch.cat([pt, kps["size"].float()[:, None], kps["angle"].float()[:, None]], 1).contiguous()
+        resp = kps.get("response")
+        resp = resp.float() if resp is not None else torch.zeros(len(pt), dtype=torch.float32, device=pt.device)
+        return kp4, kps["octave"].to(torch.int32).contiguous(), resp.contiguous()
     if isinstance(kps, dict):
         pt = np.asarray(kps["pt"], dtype=np.float32).reshape(-1, 2)
         kp4 = np.concatenate([pt, np.asarray(kps["size"], np.float32)[:, None], np.asarray(kps["angle"], np.float32)[:, None]], 1)
@@ -49,14 +64,27 @@ def extract_patches(img, kps, device=None):
     t = t.to(dev).contiguous()
     kp4, octv, _ = keypoint_arrays(kps)
     pyr, levels, dev_levels = hip.pyramid_build(t)
-    out, bad = hip.patch_extract(pyr, dev_levels, len(levels), torch.from_numpy(kp4).to(dev), torch.from_numpy(octv).to(dev))
+    out, bad = hip.patch_extract(pyr, dev_levels, len(levels), _on(kp4, dev), _on(octv, dev))
     if len(kp4) and int(bad.item()):
         raise IndexError(f"{int(bad.item())} keypoint(s) reference a pyramid level that does not exist (octave / layer out of range)")
     return out
 
 
+def _on(a, dev):
+    return a.to(dev).contiguous() if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+
 def filter_max_num(kps, max_num):
-    """filterMaxNumDesc (utils/common.py:710-718): the max_num keypoints with the largest response, in descending order."""
+    """filterMaxNumDesc (utils/common.py:710-718): the max_num keypoints with the largest response, in descending order.
+    For a dict of device tensors (sift_detect_device) the order is descending response, equal responses in the detector's
+    order (a stable sort; multi-orientation keypoints share a response).  The reference's np.argsort + fliplr leaves the
+    order of equal responses to NumPy's unstable sort, so the two forms agree apart from ties."""
+    if _is_device_dict(kps):
+        n = len(kps["pt"])
+        if 0 < max_num < n:
+            idx = torch.sort(kps["response"], descending=True, stable=True)[1][:max_num]
+            return {k: v[idx] for k, v in kps.items()}
+        return kps
     if 0 < max_num < len(kps):
         responses = [k.response for k in kps]
         idxs = np.fliplr(np.reshape(np.argsort(responses), (1, -1))).reshape(-1)
@@ -78,7 +106,20 @@ def pad_training_keypoints(kps, max_keypoints, img_shape):
     (n, 2) block scaled by the width, then the y column redrawn and scaled by the height), so a seeded run places them where
     the reference does -- as size-1 keypoints, so that every image of a training batch carries exactly max_keypoints
     (train.py:107-110 stacks them).  The reference passes the locations through ``cv2.SIFT.compute`` (682-685), which may
-    drop points OpenCV considers too close to the border: NOT restated (OpenCV is not available here; parity unpinned)."""
+    drop points OpenCV considers too close to the border: NOT restated (OpenCV is not available here; parity unpinned).
+    A dict of device tensors is padded on its device, with the same np.random sequence."""
+    if _is_device_dict(kps):
+        n = len(kps["pt"])
+        if max_keypoints <= 0 or n >= max_keypoints:
+            return kps
+        to_add = max_keypoints - n
+        coordinates = np.random.random((to_add, 2)) * img_shape[1]
+        coordinates[:, 1] = np.random.random(to_add) * img_shape[0]
+        dev = kps["pt"].device
+        pad = {"pt": torch.from_numpy(coordinates.astype(np.float32)).to(dev), "size": torch.ones(to_add, device=dev),
+               "angle": torch.full((to_add,), -1.0, device=dev), "response": torch.zeros(to_add, device=dev),
+               "octave": torch.zeros(to_add, dtype=torch.int32, device=dev)}
+        return {k: torch.cat([kps[k], pad[k].to(kps[k].dtype)]) for k in pad}
     kps = list(kps)
     if max_keypoints <= 0 or len(kps) >= max_keypoints:
         return kps
@@ -98,6 +139,28 @@ def _default_detector():
     return lambda img: sift.detect(img, None)
 
 
+def sift_detect_device(img_or_batch, device=None):
+    """OpenCV SIFT detect (utils/common.py:838-857 parameters) on the device: uint8 [H, W, 3] (BGR) / [H, W] -> a dict of device
+    tensors pt [n, 2], size, angle, response, octave; a batch [B, H, W(, 3)] (array, tensor or list of equal-size images) -> a
+    list of such dicts.  Images of one size go through the kernels together."""
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    if isinstance(img_or_batch, (list, tuple)):
+        return [sift_detect_device(im, dev) for im in img_or_batch] if len({tuple(np.shape(im)) for im in img_or_batch}) > 1 else \
+            sift_detect_device(torch.stack([torch.as_tensor(np.asarray(im) if not torch.is_tensor(im) else im) for im in img_or_batch]), dev)
+    t = img_or_batch if torch.is_tensor(img_or_batch) else torch.from_numpy(np.ascontiguousarray(img_or_batch))
+    single = t.dim() == 2 or (t.dim() == 3 and t.shape[2] == 3)       # [H, W, 3] is one BGR image, [B, H, W] a gray batch
+    t = t.to(dev)
+    out = hip.sift_detect(t.unsqueeze(0) if single else t)
+    return out[0] if single else out
+
+
+def device_front_end(data, device):
+    """``sift_forward_device`` with ``sift_detect_device`` as the detector, the detection batched over ``data['image']``.  Hand it to
+    ``Matching`` as ``config['front_end']``."""
+    dets = iter(sift_detect_device(list(data["image"]) if not torch.is_tensor(data["image"]) else data["image"], device))
+    return sift_forward_device(data, device, detector=lambda img: next(dets))
+
+
 def sift_forward_device(data, device, detector=None):
     """``utils.common.sift_forward`` (common.py:837-893; ``data['is_train']``: pad_training_keypoints) with patches and descriptors on the device.
     data: {'image': uint8 [B, H, W, 3], 'max_keypoints': int, 'carhynet': gims_amd.carhynet.CARHyNet (or any object with
@@ -108,7 +171,8 @@ def sift_forward_device(data, device, detector=None):
     kpts, descs, scores = [], [], []
     for img in data["image"]:
         img = np.asarray(img.cpu() if torch.is_tensor(img) else img)
-        k = filter_max_num(list(det(img)), data.get("max_keypoints", -1))
+        k = det(img)
+        k = filter_max_num(k if _is_device_dict(k) else list(k), data.get("max_keypoints", -1))
         if data.get("is_train", False):
             k = pad_training_keypoints(k, data.get("max_keypoints", -1), img.shape)
         kp4, _, resp = keypoint_arrays(k)
@@ -118,7 +182,7 @@ def sift_forward_device(data, device, detector=None):
                 d = net._forward_nhwc(patches)[0]
         else:                                                 # the reference's HyNetnetFeature2D: NumPy in, NumPy out
             d = torch.from_numpy(np.asarray(net.compute_des_batches(patches.cpu().numpy(), True), dtype=np.float32)).to(device)
-        kpts.append(torch.from_numpy(np.ascontiguousarray(kp4[:, :2])).to(device))
+        kpts.append(_on(kp4[:, :2], device))
         descs.append(torch.cat([d, d], dim=1).permute(1, 0).to(device))
-        scores.append(torch.from_numpy(resp).to(device))
+        scores.append(_on(resp, device))
     return {"keypoints": kpts, "scores": scores, "descriptors": descs}

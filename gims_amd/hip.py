@@ -103,6 +103,18 @@ class PyrLevel(C.Structure):
     _fields_ = [("offset", C.c_int64), ("h", C.c_int32), ("w", C.c_int32)]
 
 
+SIFT_MAX_OCTAVES, SIFT_MAX_RADIUS, SIFT_SLOTS = 16, 16, 18
+
+
+class SiftInfo(C.Structure):
+    """gims_sift_info (include/gims_hip.h): what gims_sift_layout reports for one image size."""
+    _fields_ = [("h", C.c_int32), ("w", C.c_int32), ("n_octaves", C.c_int32), ("reserved", C.c_int32),
+                ("image_floats", C.c_int64), ("scratch_floats", C.c_int64),
+                ("oct_h", C.c_int32 * SIFT_MAX_OCTAVES), ("oct_w", C.c_int32 * SIFT_MAX_OCTAVES),
+                ("gauss_offset", C.c_int64 * SIFT_MAX_OCTAVES), ("dog_offset", C.c_int64 * SIFT_MAX_OCTAVES),
+                ("sigma", C.c_double * 6), ("ksize", C.c_int32 * 6), ("kernel", (C.c_float * (SIFT_MAX_RADIUS + 1)) * 6)]
+
+
 class LossPair(C.Structure):
     _fields_ = [("scores", C.c_void_p), ("ld", C.c_int64), ("n", C.c_int32), ("m", C.c_int32), ("uv", C.c_void_p),
                 ("kept0", C.c_void_p), ("kept1", C.c_void_p)]
@@ -238,6 +250,12 @@ _SIGNATURES = {
     "gims_pyramid_build": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gims_patch_extract": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gims_patch_affine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gims_sift_layout": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(SiftInfo)]),
+    "gims_sift_pyramid": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gims_sift_detect": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gims_sift_compact": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gims_sinkhorn_history_floats": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "gims_sinkhorn_history": (C.c_int, [C.POINTER(OtProblem), C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "gims_sinkhorn_backward_workspace_bytes": (C.c_size_t, [C.POINTER(OtProblem), C.c_int32]),
@@ -1116,6 +1134,95 @@ def patch_extract(pyr: torch.Tensor, dev_levels: torch.Tensor, n_levels: int, kp
     bad = torch.empty(1, dtype=torch.int32, device=pyr.device)
     _check(load().gims_patch_extract(_p(pyr), _p(dev_levels), n_levels, _p(kp4), _p(kp_octave), n, _p(out), _p(bad), _stream()), "gims_patch_extract")
     return out, bad
+
+def sift_layout(h: int, w: int) -> SiftInfo:
+    """gims_sift_layout (host only): octave sizes, level offsets, blur sigmas, kernel sizes and half kernels for an h x w image."""
+    info = SiftInfo()
+    _check(load().gims_sift_layout(int(h), int(w), C.byref(info)), "gims_sift_layout")
+    return info
+
+
+def _sift_images(images: torch.Tensor):
+    t = images if torch.is_tensor(images) else torch.as_tensor(images)
+    if t.dtype != torch.uint8 or t.dim() not in (3, 4) or (t.dim() == 4 and t.shape[3] not in (1, 3)):
+        raise ValueError("SIFT detection takes uint8 [B, H, W, 3] (BGR) or [B, H, W] (gray) images")
+    if t.dim() == 3:
+        t = t.unsqueeze(-1)
+    return t.contiguous()
+
+
+def sift_pyramid(images: torch.Tensor):
+    """The Gaussian and DoG levels gims_sift_detect works on (a test hook): images uint8 [B, H, W, 3] / [B, H, W] on the device ->
+    (gauss, dog) with gauss[b][o][i] float32 [h_o, w_o] (6 per octave) and dog[b][o][i] (5 per octave), views of one buffer."""
+    t = _sift_images(images)
+    assert t.is_cuda
+    B, H, W, c = t.shape
+    L = sift_layout(H, W)
+    pyr = torch.empty(B * L.image_floats, dtype=torch.float32, device=t.device)
+    scratch = torch.empty(B * L.scratch_floats, dtype=torch.float32, device=t.device)
+    _check(load().gims_sift_pyramid(_p(t), B, H, W, c, _p(pyr), _p(scratch), _stream()), "gims_sift_pyramid")
+    gauss, dog = [], []
+    for b in range(B):
+        base = b * L.image_floats
+        gb, db = [], []
+        for o in range(L.n_octaves):
+            h, w = L.oct_h[o], L.oct_w[o]
+            gb.append([pyr[base + L.gauss_offset[o] + i * h * w: base + L.gauss_offset[o] + (i + 1) * h * w].view(h, w) for i in range(6)])
+            db.append([pyr[base + L.dog_offset[o] + i * h * w: base + L.dog_offset[o] + (i + 1) * h * w].view(h, w) for i in range(5)])
+        gauss.append(gb)
+        dog.append(db)
+    return gauss, dog
+
+
+def sift_detect(images: torch.Tensor, cand_cap: int | None = None):
+    """OpenCV SIFT detect on the device for a batch of equal-size images: uint8 [B, H, W, 3] (BGR) or [B, H, W] ->
+    one dict per image of device tensors pt f32 [n, 2], size, angle, response f32 [n], octave int32 [n], in OpenCV's output order.
+    Every pixel and keypoint is computed by the HIP kernels; the stable key sorts between them are torch plumbing.  The one host
+    read per call is the final count (with the extremum count: when it exceeds the candidate capacity the buffers grow and the
+    call repeats, so nothing is dropped)."""
+    t = _sift_images(images)
+    assert t.is_cuda
+    B, H, W, c = t.shape
+    L = sift_layout(H, W)
+    dev = t.device
+    lib = load()
+    pyr = torch.empty(B * L.image_floats, dtype=torch.float32, device=dev)
+    scratch = torch.empty(B * L.scratch_floats, dtype=torch.float32, device=dev)
+    cap = int(cand_cap) if cand_cap else B * max(4096, H * W // 16)
+    stat = torch.empty(B + 1, dtype=torch.int32, device=dev)          # counts per image, then the extremum count
+    while True:
+        S = cap * SIFT_SLOTS
+        cand = torch.empty(cap * 4, dtype=torch.int32, device=dev)
+        sf = torch.empty(5 * S, dtype=torch.float32, device=dev)
+        sk = torch.empty(3 * S, dtype=torch.int64, device=dev)
+        si = torch.empty(2 * S, dtype=torch.int32, device=dev)
+        stat.zero_()
+        _check(lib.gims_sift_detect(_p(t), B, H, W, c, _p(pyr), _p(scratch), _p(cand), cap, _p(stat[B:]), _p(sf), _p(sk), _p(si), _stream()),
+               "gims_sift_detect")
+        perm = torch.sort(sk[:S], stable=True)[1]                           # octave desc, response desc
+        for key in (sk[S:2 * S], sk[2 * S:], si[S:]):                        # size desc, angle asc; x asc, y asc; image
+            perm = perm[torch.sort(key[perm], stable=True)[1]]
+        keep = torch.empty(S, dtype=torch.int32, device=dev)
+        _check(lib.gims_sift_compact(_p(perm), S, B, cap, _p(sf), _p(sk), _p(si), _p(keep), None, None, None, None, None, None, None,
+                                     _stream()), "gims_sift_compact")
+        pos = torch.cumsum(keep, 0)
+        pt = torch.empty((S, 2), dtype=torch.float32, device=dev)
+        size, angle, resp = (torch.empty(S, dtype=torch.float32, device=dev) for _ in range(3))
+        octave = torch.empty(S, dtype=torch.int32, device=dev)
+        _check(lib.gims_sift_compact(_p(perm), S, B, cap, _p(sf), _p(sk), _p(si), _p(keep), _p(pos), _p(pt), _p(size), _p(angle), _p(resp),
+                                     _p(octave), _p(stat), _stream()), "gims_sift_compact")
+        host = stat.cpu().tolist()
+        if host[B] <= cap:
+            break
+        cap = host[B] + host[B] // 4 + 1024
+    out, off = [], 0
+    for b in range(B):
+        n = host[b]
+        out.append({"pt": pt[off:off + n], "size": size[off:off + n], "angle": angle[off:off + n], "response": resp[off:off + n],
+                    "octave": octave[off:off + n]})
+        off += n
+    return out
+
 
 def patch_affine(kp4: torch.Tensor, kp_octave: torch.Tensor):
     """The 2x3 warp matrix (f64 [N, 2, 3]) and pyramid level (int32 [N]) gims_patch_extract derives per keypoint (library.py:96-106)."""

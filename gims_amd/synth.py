@@ -407,3 +407,31 @@ def make_patches(n: int, seed: int):
         field = off[:, None, None] + amp[:, None, None] * np.sin(fx[:, None, None] * xx[None] + fy[:, None, None] * yy[None] + ph[:, None, None])
         out[..., c] = field
     return np.clip(out + 0.03 * noise, 0.0, 1.0).astype(np.float32)
+
+
+def make_textured_image(h: int, w: int, seed: int, gray: bool = False) -> np.ndarray:
+    """Seeded synthetic photograph for the SIFT detector: a sum of oriented sinusoids, Gaussian blobs of several scales and a few
+    bright rectangles, with mild noise.  uint8 BGR [h, w, 3] (or [h, w] when gray)."""
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
+    ch = 1 if gray else 3
+    img = np.full((h, w, ch), 110.0)
+    u = uniform(seed, 0, 4096)
+    k = 0
+
+    def nxt():
+        nonlocal k
+        k += 1
+        return float(u[k - 1])
+    for c in range(ch):
+        for _ in range(6):
+            fx, fy, ph, a = 0.02 + 0.3 * nxt(), 0.02 + 0.3 * nxt(), 6.283 * nxt(), 4 + 14 * nxt()
+            img[..., c] += a * np.sin(fx * xx + fy * yy + ph)
+    for _ in range(40):
+        cx, cy, s, a = w * nxt(), h * nxt(), 1.5 + 12 * nxt(), 60 * (nxt() - 0.5)
+        img += (a * np.exp(-((xx - cx) ** 2 + (yy - cy) ** 2) / (2 * s * s)))[..., None]
+    for _ in range(8):
+        x0, y0 = int(w * nxt()), int(h * nxt())
+        img[y0:y0 + int(5 + 40 * nxt()), x0:x0 + int(5 + 40 * nxt())] += 50 * (nxt() - 0.5)
+    img += 3 * normal(seed, 1, img.size).reshape(img.shape)
+    out = np.clip(np.rint(img), 0, 255).astype(np.uint8)
+    return out[..., 0] if gray else out

@@ -765,6 +765,38 @@ typedef struct gims_adam_tensor { float* param; const float* grad; float* exp_av
 typedef struct gims_adam_group { double lr, beta1, beta2, eps, weight_decay; int64_t step; } gims_adam_group;
 int gims_adam_step(const gims_adam_tensor* tensors, int32_t count, const gims_adam_group* groups, int32_t n_groups /* <= 8 */, void* stream);
 
+/* ---- SIFT keypoint detection (gims_amd/csrc/sift.hip): OpenCV 4.x SIFT_create(0, 3, 0.001, 80, 1.6).detect,
+ * restated for uint8 BGR [n][h][w][3] or gray [n][h][w][1] images of one size, every image of a batch in the same launches.
+ * gims_sift_layout (host only): octave sizes, float offsets of the Gaussian (6 per octave) and DoG (5) levels inside ONE image's
+ *   pyramid of image_floats floats, the blur sigmas, kernel sizes and half kernels (kernel[i][j] = tap j from the centre).
+ * gims_sift_pyramid: img -> pyr [n][image_floats] (scratch: [n][scratch_floats]); a test hook, gims_sift_detect runs it too.
+ * gims_sift_detect: pyramid + extrema + refinement + orientation.  cand: int32 [cand_cap][4]; *counter (device) = the number of
+ *   3x3x3 extrema, which may exceed cand_cap (then the caller grows the buffers and calls again).  Slots: cand_cap * GIMS_SIFT_SLOTS
+ *   entries, SoA -- slot_f32 [5][S] (x, y, size, angle, response before the firstOctave rescale), slot_i32 [2][S] (packed octave,
+ *   image; image = n_images marks an empty slot), slot_keys int64 [3][S]: stable-sort by key 0, then 1, then 2, then image to get
+ *   removeDuplicatedSorted's order (x, y ascending, size descending, angle ascending, response descending, octave descending).
+ * gims_sift_compact: with pos == NULL writes keep [n] (the first of each run of equal image / x / y / size / angle, in perm order);
+ *   with pos = inclusive prefix sum of keep, writes the kept keypoints with the firstOctave = -1 rescale and counts[image] += 1. */
+#define GIMS_SIFT_MAX_OCTAVES 16
+#define GIMS_SIFT_MAX_RADIUS 16
+#define GIMS_SIFT_SLOTS 18
+typedef struct gims_sift_info {
+  int32_t h, w, n_octaves, reserved;
+  int64_t image_floats, scratch_floats;
+  int32_t oct_h[GIMS_SIFT_MAX_OCTAVES], oct_w[GIMS_SIFT_MAX_OCTAVES];
+  int64_t gauss_offset[GIMS_SIFT_MAX_OCTAVES], dog_offset[GIMS_SIFT_MAX_OCTAVES];
+  double sigma[6];
+  int32_t ksize[6];
+  float kernel[6][GIMS_SIFT_MAX_RADIUS + 1];
+} gims_sift_info;
+int gims_sift_layout(int32_t h, int32_t w, gims_sift_info* info /* HOST */);
+int gims_sift_pyramid(const uint8_t* img, int32_t n_images, int32_t h, int32_t w, int32_t c, float* pyr, float* scratch, void* stream);
+int gims_sift_detect(const uint8_t* img, int32_t n_images, int32_t h, int32_t w, int32_t c, float* pyr, float* scratch, int32_t* cand,
+                     int32_t cand_cap, int32_t* counter, float* slot_f32, int64_t* slot_keys, int32_t* slot_i32, void* stream);
+int gims_sift_compact(const int64_t* perm, int64_t n, int32_t n_images, int32_t cand_cap, float* slot_f32, int64_t* slot_keys, int32_t* slot_i32,
+                      int32_t* keep, const int64_t* pos, float* pt, float* size, float* angle, float* response, int32_t* octave, int32_t* counts,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
