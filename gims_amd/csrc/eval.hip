@@ -485,3 +485,165 @@ extern "C" int gims_eval_pairs(const gims_eval_pair* pairs, int32_t n_pairs, flo
   GIMS_LAUNCH_CHECK();
   return GIMS_OK;
 }
+
+// ---------------------------------------------------------------------------------------------- training labels
+// torch_find_matches (utils/preprocess_utils.py:98-132) through the GT-matching kernels above, then the match_indexes rows of
+// train.py:118-125: [k, i0, i1] for the matches (i1 ascending, iteration after iteration), [k, miss0, -1], [k, -1, miss1], pair
+// after pair.  The homographies are read on the device; the row count is the caller's one host read.
+namespace gims {
+
+// the ground-truth homography of each pair from device memory into the descriptor table
+__global__ __launch_bounds__(64) void lab_setup_kernel(EvalDev* __restrict__ ev, const float* __restrict__ hs, int32_t* __restrict__ itr_all,
+                                                       int64_t n1_total) {
+  const int p = blockIdx.x, t = threadIdx.x;
+  if (t < 9) ev[p].hgt[t] = hs[9 * p + t];
+  for (int64_t j = (int64_t)p * 64 + t; j < n1_total; j += (int64_t)gridDim.x * 64) itr_all[j] = -1;
+}
+
+// the iteration in which keypoint j of image 1 found its partner
+__global__ __launch_bounds__(256) void lab_iter_kernel(const EvalDev* __restrict__ ev, int32_t* const* __restrict__ itr, int it) {
+  const EvalDev& e = ev[blockIdx.y];
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j < e.n1 && e.gt1[j] >= 0 && itr[blockIdx.y][j] < 0) itr[blockIdx.y][j] = it;
+}
+
+// exclusive prefix of a 0/1 flag over the 1024 threads of the block; *total receives the block's count
+__device__ __forceinline__ int block_prefix(bool flag, int* s_wave, int& total) {
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const unsigned long long bal = __ballot(flag);
+  const int below = __popcll(bal & ((1ull << lane) - 1ull));
+  __syncthreads();
+  if (lane == 0) s_wave[wave] = __popcll(bal);
+  __syncthreads();
+  int before = 0;
+  total = 0;
+  for (int w = 0; w < 16; ++w) {
+    before += w < wave ? s_wave[w] : 0;
+    total += s_wave[w];
+  }
+  return before + below;
+}
+
+// pass 0: rows per pair = n0 + n1 - matches (one workgroup per pair); pass 1: ordered compaction into rows at the pair's offset
+template <int PASS>
+__global__ __launch_bounds__(1024) void lab_rows_kernel(const EvalDev* __restrict__ ev, int32_t* const* __restrict__ itr, int n_iters,
+                                                        int32_t* __restrict__ counts, int64_t* __restrict__ rows, int64_t* __restrict__ total) {
+  __shared__ int s_wave[16];
+  __shared__ int s_red;
+  const int p = blockIdx.x, t = threadIdx.x;
+  const EvalDev& e = ev[p];
+  if (PASS == 0) {
+    if (t == 0) s_red = 0;
+    __syncthreads();
+    int m = 0;
+    for (int j = t; j < e.n1; j += 1024) m += e.gt1[j] >= 0;
+    atomicAdd(&s_red, m);
+    __syncthreads();
+    if (t == 0) counts[p] = e.n0 + e.n1 - s_red;
+    return;
+  }
+  int64_t off = 0;
+  for (int q = 0; q < p; ++q) off += counts[q];
+  if (p == (int)gridDim.x - 1 && t == 0) total[0] = off + counts[p];
+  const int32_t* it_of = itr[p];
+  int cnt;
+  for (int it = 0; it < n_iters; ++it)
+    for (int j0 = 0; j0 < e.n1; j0 += 1024) {
+      const int j = j0 + t;
+      const bool f = j < e.n1 && it_of[j] == it;
+      const int pos = block_prefix(f, s_wave, cnt);
+      if (f) { int64_t* r = rows + 3 * (off + pos); r[0] = p; r[1] = e.gt1[j]; r[2] = j; }
+      off += cnt;
+    }
+  for (int i0 = 0; i0 < e.n0; i0 += 1024) {
+    const int i = i0 + t;
+    const bool f = i < e.n0 && e.alive0[i];
+    const int pos = block_prefix(f, s_wave, cnt);
+    if (f) { int64_t* r = rows + 3 * (off + pos); r[0] = p; r[1] = i; r[2] = -1; }
+    off += cnt;
+  }
+  for (int j0 = 0; j0 < e.n1; j0 += 1024) {
+    const int j = j0 + t;
+    const bool f = j < e.n1 && e.alive1[j];
+    const int pos = block_prefix(f, s_wave, cnt);
+    if (f) { int64_t* r = rows + 3 * (off + pos); r[0] = p; r[1] = -1; r[2] = j; }
+    off += cnt;
+  }
+}
+
+static size_t label_pair_bytes(const gims_label_pair& p) {
+  return al256e((size_t)p.n0 * 8) + 3 * al256e((size_t)p.n0 * 4) + al256e((size_t)p.n0) + 4 * al256e((size_t)p.n1 * 4);
+}
+
+}  // namespace gims
+
+extern "C" size_t gims_train_labels_workspace_bytes(const gims_label_pair* pairs, int32_t n_pairs) {
+  using namespace gims;
+  if (!pairs || n_pairs <= 0) return 0;
+  size_t b = al256e(sizeof(EvalDev) * (size_t)n_pairs) + al256e(sizeof(int32_t*) * (size_t)n_pairs) + al256e(4 * (size_t)n_pairs);
+  for (int i = 0; i < n_pairs; ++i) b += label_pair_bytes(pairs[i]);
+  return b;
+}
+
+extern "C" int gims_train_labels(const gims_label_pair* pairs, int32_t n_pairs, const float* homographies, float dist_thresh, int32_t n_iters,
+                                 int64_t* rows, int64_t* total, void* work, size_t work_bytes, void* stream) {
+  using namespace gims;
+  GIMS_CHECK_ARG(pairs && n_pairs > 0 && n_pairs <= 65535 && homographies && rows && total && work, "gims_train_labels: null / empty arguments");
+  GIMS_CHECK_ARG(n_iters >= 0 && n_iters <= 64, "gims_train_labels: bad iteration count");
+  GIMS_CHECK_ARG(work_bytes >= gims_train_labels_workspace_bytes(pairs, n_pairs), "gims_train_labels: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<EvalDev> h(n_pairs);
+  std::vector<int32_t*> hitr(n_pairs);
+  char* base = (char*)work;
+  size_t off = al256e(sizeof(EvalDev) * (size_t)n_pairs);
+  int32_t* const* ditr = (int32_t* const*)(base + off);
+  off += al256e(sizeof(int32_t*) * (size_t)n_pairs);
+  int32_t* counts = (int32_t*)(base + off);
+  off += al256e(4 * (size_t)n_pairs);
+  // the per-pair iteration arrays sit back to back so that the setup kernel initialises them in one sweep
+  int64_t n1_total = 0;
+  for (int i = 0; i < n_pairs; ++i) n1_total += al256e((size_t)pairs[i].n1 * 4) / 4;
+  int32_t* itr_all = (int32_t*)(base + off);
+  off += (size_t)n1_total * 4;
+  int64_t itr_off = 0;
+  int maxn0 = 0, maxn1 = 0;
+  for (int i = 0; i < n_pairs; ++i) {
+    const gims_label_pair& p = pairs[i];
+    GIMS_CHECK_ARG(p.n0 > 0 && p.n1 > 0 && p.kpts0 && p.kpts1, "gims_train_labels: pair %d has an empty shape or a null pointer", i);
+    EvalDev d;
+    memset(&d, 0, sizeof(d));
+    d.kp0 = p.kpts0; d.kp1 = p.kpts1;
+    d.n0 = p.n0; d.n1 = p.n1;
+    d.proj = (float*)(base + off); off += al256e((size_t)p.n0 * 8);
+    d.alive0 = (int32_t*)(base + off); off += al256e((size_t)p.n0 * 4);
+    d.min1 = (int32_t*)(base + off); off += al256e((size_t)p.n0 * 4);
+    d.gt0 = (int32_t*)(base + off); off += al256e((size_t)p.n0 * 4);
+    d.inlier = (uint8_t*)(base + off); off += al256e((size_t)p.n0);
+    d.alive1 = (int32_t*)(base + off); off += al256e((size_t)p.n1 * 4);
+    d.min2 = (int32_t*)(base + off); off += al256e((size_t)p.n1 * 4);
+    d.gt1 = (int32_t*)(base + off); off += al256e((size_t)p.n1 * 4);
+    hitr[i] = itr_all + itr_off;
+    itr_off += al256e((size_t)p.n1 * 4) / 4;
+    h[i] = d;
+    maxn0 = p.n0 > maxn0 ? p.n0 : maxn0;
+    maxn1 = p.n1 > maxn1 ? p.n1 : maxn1;
+  }
+  int rc = upload_table(h.data(), sizeof(EvalDev) * (size_t)n_pairs, work, s);
+  if (rc != GIMS_OK) return rc;
+  rc = upload_table(hitr.data(), sizeof(int32_t*) * (size_t)n_pairs, (void*)ditr, s);
+  if (rc != GIMS_OK) return rc;
+  EvalDev* dev = (EvalDev*)work;
+  hipLaunchKernelGGL(lab_setup_kernel, dim3(n_pairs), dim3(64), 0, s, dev, homographies, itr_all, n1_total);
+  const int mx = maxn0 > maxn1 ? maxn0 : maxn1;
+  hipLaunchKernelGGL(eval_warp_kernel, dim3(cdiv(mx, 256), n_pairs), dim3(256), 0, s, (const EvalDev*)dev);
+  for (int it = 0; it < n_iters; ++it) {
+    hipLaunchKernelGGL(eval_argmin_kernel<true>, dim3(cdiv(maxn0, 4), n_pairs), dim3(256), 0, s, (const EvalDev*)dev);
+    hipLaunchKernelGGL(eval_argmin_kernel<false>, dim3(cdiv(maxn1, 4), n_pairs), dim3(256), 0, s, (const EvalDev*)dev);
+    hipLaunchKernelGGL(eval_mutual_kernel, dim3(cdiv(maxn1, 256), n_pairs), dim3(256), 0, s, (const EvalDev*)dev, dist_thresh);
+    hipLaunchKernelGGL(lab_iter_kernel, dim3(cdiv(maxn1, 256), n_pairs), dim3(256), 0, s, (const EvalDev*)dev, ditr, it);
+  }
+  hipLaunchKernelGGL(lab_rows_kernel<0>, dim3(n_pairs), dim3(1024), 0, s, (const EvalDev*)dev, ditr, n_iters, counts, rows, total);
+  hipLaunchKernelGGL(lab_rows_kernel<1>, dim3(n_pairs), dim3(1024), 0, s, (const EvalDev*)dev, ditr, n_iters, counts, rows, total);
+  GIMS_LAUNCH_CHECK();
+  return GIMS_OK;
+}

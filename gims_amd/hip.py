@@ -159,6 +159,10 @@ class EvalPair(C.Structure):
                 ("gt0", C.c_void_p), ("inlier", C.c_void_p), ("record", C.c_void_p), ("homographies", C.c_void_p)]
 
 
+class LabelPair(C.Structure):
+    _fields_ = [("kpts0", C.c_void_p), ("kpts1", C.c_void_p), ("n0", C.c_int32), ("n1", C.c_int32)]
+
+
 _SIGNATURES = {
     "gims_abi_version": (C.c_int, []),
     "gims_last_error": (C.c_char_p, []),
@@ -256,6 +260,13 @@ _SIGNATURES = {
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gims_sift_compact": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gims_warp_invert": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "gims_warp_perspective": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                        C.c_void_p, C.c_void_p]),
+    "gims_resize": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "gims_train_labels_workspace_bytes": (C.c_size_t, [C.POINTER(LabelPair), C.c_int32]),
+    "gims_train_labels": (C.c_int, [C.POINTER(LabelPair), C.c_int32, C.c_void_p, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_size_t, C.c_void_p]),
     "gims_sinkhorn_history_floats": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "gims_sinkhorn_history": (C.c_int, [C.POINTER(OtProblem), C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "gims_sinkhorn_backward_workspace_bytes": (C.c_size_t, [C.POINTER(OtProblem), C.c_int32]),
@@ -1506,3 +1517,74 @@ def adam_step(table, groups):
         gt[i].lr, gt[i].beta1, gt[i].beta2, gt[i].eps, gt[i].weight_decay, gt[i].step = (float(g["lr"]), float(g["beta1"]), float(g["beta2"]), float(g["eps"]),
                                                                                       float(g["weight_decay"]), int(g["step"]))
     _check(load().gims_adam_step(table.ctypes.data_as(C.POINTER(AdamTensor)), len(table), gt, len(groups), _stream()), "gims_adam_step")
+
+
+# ------------------------------------------------------------------------------------------------ training data from images
+INTER_LINEAR, INTER_AREA = 1, 3          # cv2's values (GIMS_INTER_* in include/gims_hip.h)
+
+
+def _image_batch(images: torch.Tensor):
+    if images.dtype != torch.uint8 or images.dim() not in (3, 4) or not images.is_cuda or (images.dim() == 4 and images.shape[3] not in (1, 3)):
+        raise ValueError("image warps take device uint8 [B, H, W, 3] or [B, H, W] images")
+    t = images.contiguous()
+    return t if t.dim() == 4 else t.unsqueeze(-1)
+
+
+def warp_invert(m):
+    """cv::invert(M, DECOMP_LU) of float64 [n, 3, 3] matrices on the host (gims_warp_invert): what warp_perspective samples through."""
+    import numpy as np
+    a = np.ascontiguousarray(np.asarray(m, dtype=np.float64).reshape(-1, 9))
+    out = np.empty_like(a)
+    _check(load().gims_warp_invert(a.ctypes.data, len(a), out.ctypes.data), "gims_warp_invert")
+    return out.reshape(-1, 3, 3)
+
+
+def warp_perspective(images: torch.Tensor, ms, dsize, out=None):
+    """cv2.warpPerspective(img, M, dsize) (INTER_LINEAR, BORDER_CONSTANT 0) for a batch: images uint8 [B, H, W(, 3)] on the device,
+    ms float64-convertible [B, 3, 3] (host), dsize (w, h) -> uint8 [B, h, w(, 3)] on the device.  One launch for the batch."""
+    import numpy as np
+    t = _image_batch(images)
+    B, H, W, c = t.shape
+    dw, dh = int(dsize[0]), int(dsize[1])
+    m = np.ascontiguousarray(np.asarray(ms, dtype=np.float64).reshape(B, 9))
+    res = out if out is not None else torch.empty((B, dh, dw, c), dtype=torch.uint8, device=t.device)
+    assert res.shape == (B, dh, dw, c) and res.dtype == torch.uint8 and res.is_contiguous()
+    work = torch.empty(9 * B, dtype=torch.float64, device=t.device)
+    _check(load().gims_warp_perspective(_p(t), B, H, W, c, m.ctypes.data, _p(res), dh, dw, _p(work), _stream()), "gims_warp_perspective")
+    return res if images.dim() == 4 else res.squeeze(-1)
+
+
+def resize(images: torch.Tensor, dsize, interpolation=INTER_LINEAR, out=None):
+    """cv2.resize(img, dsize, interpolation) for INTER_LINEAR / INTER_AREA on a batch of device uint8 [B, H, W(, 3)] images."""
+    t = _image_batch(images)
+    B, H, W, c = t.shape
+    dw, dh = int(dsize[0]), int(dsize[1])
+    res = out if out is not None else torch.empty((B, dh, dw, c), dtype=torch.uint8, device=t.device)
+    assert res.shape == (B, dh, dw, c) and res.dtype == torch.uint8 and res.is_contiguous()
+    _check(load().gims_resize(_p(t), B, H, W, c, _p(res), dh, dw, int(interpolation), _stream()), "gims_resize")
+    return res if images.dim() == 4 else res.squeeze(-1)
+
+
+def train_labels(kpts0, kpts1, homographies: torch.Tensor, dist_thresh=3.0, n_iters=1):
+    """torch_find_matches per pair + the match_indexes rows of train.py:118-125 (gims_train_labels): kpts0 / kpts1 sequences of device
+    float32 [n, 2] (or [B, n, 2] tensors), homographies device float32 [B, 3, 3] -> int64 [R, 3] on the device.  The row count is the one
+    host read."""
+    B = len(kpts0)
+    assert len(kpts1) == B and homographies.shape[0] == B
+    k0 = [k.float().contiguous() for k in kpts0]
+    k1 = [k.float().contiguous() for k in kpts1]
+    hs = homographies.to(torch.float32).reshape(B, 9).contiguous()
+    dev = hs.device
+    arr = (LabelPair * B)()
+    for i in range(B):
+        assert k0[i].is_cuda and k1[i].is_cuda and k0[i].shape[-1] == 2 and k1[i].shape[-1] == 2
+        arr[i] = LabelPair(_p(k0[i]), _p(k1[i]), k0[i].shape[0], k1[i].shape[0])
+    lib = load()
+    need = int(lib.gims_train_labels_workspace_bytes(arr, B))
+    work = torch.empty(need, dtype=torch.uint8, device=dev)
+    cap = sum(int(k0[i].shape[0]) + int(k1[i].shape[0]) for i in range(B))
+    rows = torch.empty((cap, 3), dtype=torch.int64, device=dev)
+    total = torch.zeros(1, dtype=torch.int64, device=dev)
+    _check(lib.gims_train_labels(arr, B, _p(hs), float(dist_thresh), int(n_iters), _p(rows), _p(total), _p(work), need, _stream()),
+           "gims_train_labels")
+    return rows[:int(total.item())]

@@ -797,6 +797,28 @@ int gims_sift_compact(const int64_t* perm, int64_t n, int32_t n_images, int32_t 
                       int32_t* keep, const int64_t* pos, float* pt, float* size, float* angle, float* response, int32_t* octave, int32_t* counts,
                       void* stream);
 
+/* ---- Training data from images (gims_amd/csrc/warp.hip, eval.hip): the reference's COCO_loader / train.py data path.
+ * gims_warp_invert (host only): cv::invert(M, DECOMP_LU) of n row-major float64 3x3 matrices (determinant / cofactor path; singular -> 0).
+ * gims_warp_perspective: cv2.warpPerspective(src, M, (dw, dh)), INTER_LINEAR, BORDER_CONSTANT 0, for uint8 [n][sh][sw][c] -> [n][dh][dw][c],
+ *   c = 1 or 3; m: HOST float64 [n][9] forward matrices (inverted here like the line above); work: device, >= 72 * n bytes, 16-aligned.
+ * gims_resize: cv2.resize(src, (dw, dh), interpolation) for GIMS_INTER_LINEAR / GIMS_INTER_AREA, same layout (OpenCV's path choice:
+ *   copy, area-fast, general area, linear with area-mode coefficients).
+ * gims_train_labels: torch_find_matches(kpts0, kpts1, H, dist_thresh, n_iters) for n_pairs pairs and the match_indexes rows of
+ *   train.py:118-125 -- rows int64 [sum(n0 + n1)][3] (capacity), filled from row 0 pair after pair: [k, i0, i1] (i1 ascending within an
+ *   iteration, iteration after iteration), [k, miss0, -1], [k, -1, miss1]; *total (device int64) = the number of rows written.
+ *   homographies: DEVICE float32 [n_pairs][9].  Keypoints: DEVICE float32 [n][2]. */
+#define GIMS_INTER_LINEAR 1
+#define GIMS_INTER_AREA 3
+typedef struct gims_label_pair { const float* kpts0; const float* kpts1; int32_t n0, n1; } gims_label_pair;
+int gims_warp_invert(const double* m /* HOST */, int32_t n, double* minv /* HOST */);
+int gims_warp_perspective(const uint8_t* src, int32_t n, int32_t sh, int32_t sw, int32_t c, const double* m /* HOST */, uint8_t* dst, int32_t dh,
+                          int32_t dw, double* work, void* stream);
+int gims_resize(const uint8_t* src, int32_t n, int32_t sh, int32_t sw, int32_t c, uint8_t* dst, int32_t dh, int32_t dw, int32_t interpolation,
+                void* stream);
+size_t gims_train_labels_workspace_bytes(const gims_label_pair* h_pairs /* HOST array */, int32_t n_pairs);
+int gims_train_labels(const gims_label_pair* h_pairs /* HOST array */, int32_t n_pairs, const float* homographies, float dist_thresh,
+                      int32_t n_iters, int64_t* rows, int64_t* total, void* work, size_t work_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
