@@ -134,4 +134,7 @@ class Adam(torch.optim.Optimizer):
                 sel = table[(table["group"] >= lo) & (table["group"] < lo + 8)].copy()
                 sel["group"] -= lo
                 hip.adam_step(np.ascontiguousarray(sel), hyper[lo:lo + 8])
+        # the kernel wrote the parameters through raw pointers: bump their version counters as an in-place torch op would, so that
+        # caches keyed on them (GMatcher's packed weights, bin_score among them) see the update
+        torch.autograd.graph.increment_version([p for _, p in active])
         return loss

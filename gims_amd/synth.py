@@ -235,12 +235,14 @@ def state_dict_spec(descriptor_dim=256, keypoint_encoder=(32, 64, 128, 256), n_l
     return spec
 
 
-def make_state_dict(seed: int = 123, bias_std: float = 0.02, bn_jitter: float = 0.2, gains=None, head_gains=None, num_heads: int = 4, **kw):
+def make_state_dict(seed: int = 123, bias_std: float = 0.02, bn_jitter: float = 0.2, gains=None, head_gains=None, num_heads: int = 4,
+                    bin_score: float = 1.0, **kw):
     """Synthetic GMatcher weights as {name: np.ndarray}.
 
     Conv/linear weights ~ N(0, g^2/fan_in); biases ~ N(0, bias_std^2) (non-zero so the bias
     paths are exercised); BatchNorm gamma/var ~ 1 +- bn_jitter, beta/mean small -- so the
-    BN-folding path is exercised as well.  ``bin_score`` = 1 (gmatcher.py:206).  ``gains`` overrides / extends GAINS (see
+    BN-folding path is exercised as well.  ``bin_score`` (the dustbin logit alpha) defaults to 1 (gmatcher.py:206) and is stored
+    rounded to float32; it draws no random stream, so changing it leaves every other tensor bit-identical.  ``gains`` overrides / extends GAINS (see
     ``_gain_for``): e.g. ``{"attn.proj.0": 1.2, "attn.proj.1": 1.2}`` sharpens the attention of every layer.
     ``head_gains``: ``{(layer, head): g}`` multiplies the query and key projection rows of ONE head of one attentional layer (the
     reference interleaves heads: output channel c belongs to head c % num_heads, gmatcher.py:111) by g, bias included -- that
@@ -251,7 +253,7 @@ def make_state_dict(seed: int = 123, bias_std: float = 0.02, bn_jitter: float = 
         n = int(np.prod(shape)) if len(shape) else 1
         stream = 1000 + i
         if name == "bin_score":
-            a = np.array(1.0, dtype=np.float32)
+            a = np.array(bin_score, dtype=np.float32)
         elif name.endswith("num_batches_tracked"):
             a = np.array(0, dtype=np.int64)
         elif name.endswith(".a_2"):

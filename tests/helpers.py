@@ -60,7 +60,11 @@ def compare_with_golden(out, data, g, thr, score_tol=1e-4):
     bad = np.nonzero((m0 != r0) & safe0)[0]
     assert len(bad) == 0, f"{len(bad)} well-conditioned match indices differ, e.g. rows {bad[:5]}: {m0[bad[:5]]} vs {r0[bad[:5]]}"
     same = m0 == r0
-    err = np.abs(s0 - rs0)[same & (r0 >= 0)].max()
+    if (r0 >= 0).any():
+        err = np.abs(s0 - rs0)[same & (r0 >= 0)].max()
+    else:                                                        # the reference matched nothing (a dustbin above every score): neither may we
+        assert (m0 < 0).all() and (m1 < 0).all(), f"{int((m0 >= 0).sum())} matches where the reference has none"
+        err = 0.0
     assert err < score_tol, f"matching_scores0 max err {err:.3e}"
     # ... and in practice EVERY row agrees, ill-conditioned ones included: asserted, so that a regression on those rows is
     # seen (a failure here with zero well-conditioned mismatches means a reference decision flipped on a sub-1e-3 margin)
@@ -70,7 +74,7 @@ def compare_with_golden(out, data, g, thr, score_tol=1e-4):
     if score_tol == 1e-4:
         assert np.abs(s1 - rs1).max() < 1e-4                     # every row, matched or not
     else:                                                        # a fixture with its own (documented) bar: matched rows
-        assert np.abs(s1 - rs1)[(m1 == r1) & (r1 >= 0)].max() < score_tol
+        assert np.abs(s1 - rs1)[(m1 == r1) & (r1 >= 0)].max(initial=0.0) < score_tol
     return dict(n=len(m0), mismatched_unsafe=mismatched_unsafe, score_err=float(err))
 
 
@@ -95,9 +99,29 @@ def safe_rows(ot, thr, ref_matches0, ref_scores0, eps=1e-3):
     return safe
 
 
+def alpha_pair(g):
+    """The synthetic pair of a fixture of tools/gen_golden_alpha.py, regenerated from its ``pair`` spec: [kind (0: make_pair,
+    1: make_pair_unbalanced), n0, n1, n_common, seed, canvas w, canvas h (0: synth's default)]."""
+    from gims_amd import synth
+    kind, n0, n1, nc, seed, cw, ch = [int(x) for x in g["pair"]]
+    canvas = (cw, ch) if cw else None
+    return synth.make_pair(n0, seed, canvas=canvas) if kind == 0 else synth.make_pair_unbalanced(n0, n1, nc, seed, canvas=canvas)
+
+
+def fixture_state_dict(g):
+    """The synthetic weights a fixture was made with: its stored weight seed and bin_score where it has them (tools/gen_golden_alpha.py),
+    synth's defaults (seed 123, bin_score 1) otherwise."""
+    from gims_amd import synth
+    if "bin_score" not in g:
+        return synth.make_state_dict(123)
+    return synth.make_state_dict(int(g["weight_seed"]), bin_score=float(g["bin_score"]))
+
+
 def train_pairs(name, g):
     """The synthetic pairs of a trainloss_* fixture (regenerated from seeds; the fixture stores only outputs)."""
     from gims_amd import synth
+    if "pair" in g:                                              # binloss_* / binstep_*: the pair spec is stored
+        return [alpha_pair(g)]
     return {"trainloss_n256_s1002_i100": lambda: [synth.make_pair(256, 1002)],
             "trainloss_n1024_s1000_i100": lambda: [synth.make_pair(1024, 1000)],
             "trainloss_n1024sparse_s2001_i20": lambda: [synth.make_pair(1024, 2001, canvas=(800, 600))],

@@ -9,7 +9,7 @@ import torch
 
 from gims_amd import GMatcher, Matching, synth
 from oracle import gims_oracle as O
-from tests.helpers import compare_with_golden as _compare, check_score_gradients, golden_names, make_rare_pair, load_golden, pair_to_data, safe_rows, train_data, train_pairs
+from tests.helpers import compare_with_golden as _compare, alpha_pair, check_score_gradients, fixture_state_dict, golden_names, make_rare_pair, load_golden, pair_to_data, safe_rows, train_data, train_pairs
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
@@ -56,6 +56,64 @@ def test_e2e_vs_reference_golden(models, monkeypatch, name, prec, sinkhorn):
     a = np.stack([src.cpu().numpy(), dst.cpu().numpy()], 1)
     b = np.stack([g["out/dgl_src1"], g["out/dgl_dst1"]], 1)
     np.testing.assert_array_equal(a[np.lexsort((a[:, 1], a[:, 0]))], b[np.lexsort((b[:, 1], b[:, 0]))])
+
+
+_ALPHA_MODELS = {}
+
+
+def _alpha_model(g, prec="bf16x3"):
+    """A settled GMatcher with the weights of a tools/gen_golden_alpha.py fixture (its weight seed and bin_score), one per setting."""
+    rad, pct, ms, iters = [int(x) for x in g["meta"]]
+    key = (int(g["weight_seed"]), float(g["bin_score"]), iters, float(g["match_threshold"]), prec)
+    if key not in _ALPHA_MODELS:
+        m = GMatcher({"sinkhorn_iterations": iters, "match_threshold": float(g["match_threshold"]), "linear_precision": prec}).eval()
+        m.load_state_dict(fixture_state_dict(g))
+        _settle(m)
+        _ALPHA_MODELS[key] = m
+    return _ALPHA_MODELS[key]
+
+
+@pytest.mark.parametrize("sinkhorn", ["streamed", "resident"])
+@pytest.mark.parametrize("name", golden_names("bine2e_") + golden_names("seede2e_"))
+def test_e2e_alpha_and_weight_seeds_vs_reference_golden(monkeypatch, name, sinkhorn):
+    """forward() against the reference at dustbin logits that compete with the scores (bine2e_*: -2, p10 / p50 / p90 of the pair's row
+    maxima, above every score -- nothing matched) and with two more weight seeds at bin_score = 1 (seede2e_*), on both Sinkhorn paths, at
+    compare_with_golden's bars.  Every other e2e fixture sits at bin_score = 1, far below the row maxima (~45-95)."""
+    monkeypatch.setenv("GIMS_OT_RESIDENT", "0" if sinkhorn == "streamed" else "2")
+    g = load_golden(name)
+    rad, pct, ms, _ = [int(x) for x in g["meta"]]
+    data = pair_to_data(alpha_pair(g), rad, pct, ms, device="cuda")
+    # bin_score inside the row-max range (p10 / p50 / p90): a matched row's score exp(log P) = s is no longer saturated by a far dustbin, it
+    # moves by s (1 - s) per unit of score error; the default precision's score matrix (bf16x3 linears) then gives 1.1e-4 ... 1.9e-4
+    # (measured on both Sinkhorn paths, indices all exact), f32 linears stay within 1e-4 (next test).  Elsewhere: the 1e-4 bar.
+    tol = 2.5e-4 if name.endswith(("_ap10", "_ap50", "_ap90")) else 1e-4
+    out = _alpha_model(g)(data)
+    print(name, float(g["bin_score"]), sinkhorn, _compare(out, data, g, float(g["match_threshold"]), score_tol=tol))
+
+
+@pytest.mark.parametrize("sinkhorn", ["streamed", "resident"])
+@pytest.mark.parametrize("name", [n for n in golden_names("bine2e_") if n.endswith(("_ap10", "_ap50", "_ap90"))])
+def test_e2e_alpha_f32_linears_vs_reference_golden(monkeypatch, name, sinkhorn):
+    """linear_precision='f32' at every bin_score inside the row-max range, at the 1e-4 bar."""
+    monkeypatch.setenv("GIMS_OT_RESIDENT", "0" if sinkhorn == "streamed" else "2")
+    g = load_golden(name)
+    rad, pct, ms, _ = [int(x) for x in g["meta"]]
+    data = pair_to_data(alpha_pair(g), rad, pct, ms, device="cuda")
+    out = _alpha_model(g, "f32")(data)
+    print(name, float(g["bin_score"]), sinkhorn, _compare(out, data, g, float(g["match_threshold"])))
+
+
+def test_match_pairs_alpha_batch_vs_reference_golden():
+    """match_pairs on one ragged batch of the bine2e_* fixtures that share bin_score = -2 and the (100, 0.2) setting (256 x 252 and
+    1498 x 896 kept keypoints), each pair against its own fixture."""
+    names = [n for n in golden_names("bine2e_") if n.endswith("_i100_am2")]
+    assert len(names) == 2
+    gs = [load_golden(n) for n in names]
+    assert len({(float(g["bin_score"]), int(g["meta"][3])) for g in gs}) == 1
+    datas = [pair_to_data(alpha_pair(g), *[int(x) for x in g["meta"][:3]], device="cuda") for g in gs]
+    outs = _alpha_model(gs[0]).match_pairs(datas)
+    for n, g, d, o in zip(names, gs, datas, outs):
+        print(n, _compare(o, d, g, float(g["match_threshold"])))
 
 
 def _unbalanced(name):
@@ -726,16 +784,17 @@ def test_matching_without_keypoints_through_a_front_end(synth_sd):
 
 
 @pytest.mark.parametrize("sinkhorn", ["streamed", "resident"])
-@pytest.mark.parametrize("name", golden_names("trainloss_"))
-def test_train_loss_forward_vs_reference_golden(synth_sd, monkeypatch, name, sinkhorn):
+@pytest.mark.parametrize("name", golden_names("trainloss_") + golden_names("binloss_"))
+def test_train_loss_forward_vs_reference_golden(monkeypatch, name, sinkhorn):
     """mode='train' (train.py:136 -> gmatcher.py:254, 309-386), forward value: (loss, pos_loss, neg_loss) within 1e-4 of what the
     reference returned for the same pairs / ground-truth rows / weights (module in eval mode: running-statistics BatchNorm)."""
     monkeypatch.setenv("GIMS_OT_RESIDENT", "0" if sinkhorn == "streamed" else "2")
     g = load_golden(name)
     pairs = train_pairs(name, g)
+    sd = fixture_state_dict(g)                       # binloss_*: the fixture's bin_score
     m = GMatcher({"sinkhorn_iterations": int(g["meta"][4]), "pos_loss_weight": float(g["pos_loss_weight"]),
                   "neg_loss_weight": float(g["neg_loss_weight"])}).eval()
-    m.load_state_dict(synth_sd)
+    m.load_state_dict(sd)
     data = train_data(pairs, g, device="cuda")
     loss, pos, neg = m(data, mode="train")
     assert loss.dim() == 0 and loss.dtype == torch.float32
@@ -745,7 +804,7 @@ def test_train_loss_forward_vs_reference_golden(synth_sd, monkeypatch, name, sin
     print(name, sinkhorn, got, [float(g["loss"]), float(g["pos"]), float(g["neg"])])
     np.testing.assert_allclose(got, [g["loss"], g["pos"], g["neg"]], atol=1e-4, rtol=0)
     m2 = GMatcher({"sinkhorn_iterations": 5}).eval()
-    m2.load_state_dict(synth_sd)
+    m2.load_state_dict(sd)
     with pytest.raises(KeyError):                     # like the reference: the loss weights have no default (gmatcher.py:383)
         m2(train_data(pairs, g, device="cuda"), mode="train")
 
@@ -798,15 +857,15 @@ def test_dense_keypoints_grow_the_graph_capacity(synth_sd):
     np.testing.assert_array_equal(out2["matches0"].cpu().numpy(), out["matches0"].cpu().numpy())
 
 
-@pytest.mark.parametrize("name", golden_names("trainloss_"))
-def test_train_loss_score_gradients_vs_reference_golden(synth_sd, name):
+@pytest.mark.parametrize("name", golden_names("trainloss_") + golden_names("binloss_"))
+def test_train_loss_score_gradients_vs_reference_golden(name):
     """First stage of the backward pass: d loss / d scores and d loss / d bin_score from gims_sinkhorn_backward
     (reverse mode through the unrolled Sinkhorn iterations) against the reference's own autograd."""
     g = load_golden(name)
     pairs = train_pairs(name, g)
     m = GMatcher({"sinkhorn_iterations": int(g["meta"][4]), "pos_loss_weight": float(g["pos_loss_weight"]),
                   "neg_loss_weight": float(g["neg_loss_weight"])}).eval()
-    m.load_state_dict(synth_sd)
+    m.load_state_dict(fixture_state_dict(g))
     out = m.loss_and_score_gradients(train_data(pairs, g, device="cuda"))
     np.testing.assert_allclose(float(out["loss"]), float(g["loss"]), atol=1e-4, rtol=0)
     ds = [d.cpu().numpy() for d in out["dscores"]]

@@ -127,3 +127,58 @@ def test_training_steps_with_the_fused_optimizer_track_torch_adam():
         losses.append(ls)
     assert losses[0][-1] < losses[0][0]
     assert np.allclose(losses[0], losses[1], rtol=1e-4, atol=1e-6), losses
+
+
+def test_eval_forward_after_weight_updates_uses_the_new_weights():
+    """GMatcher caches its packed weights, bin_score included (a host float), keyed on the parameters' version counters.  After each way
+    the weights change in place -- load_state_dict with another bin_score, bin_score.fill_ under no_grad, and a fused-Adam step taken after
+    an eval forward() that followed a training forward -- the next forward() equals that of a model freshly loaded with the same state."""
+    from gims_amd import GMatcher, synth
+    from gims_amd.optim import Adam
+    from tests.helpers import load_golden, pair_to_data, train_data, train_pairs
+    cfg = {"sinkhorn_iterations": 100, "match_threshold": 0.2, "attention_precision": "bf16x3", "pos_loss_weight": 0.45, "neg_loss_weight": 1.0}
+    pair = synth.make_pair(256, 1002)
+
+    def fresh(state):
+        f = GMatcher(cfg).eval()
+        f.load_state_dict(state)
+        return f.cuda()(pair_to_data(pair, 15, 2, 7, device="cuda"))
+
+    def same(out, ref, exact=True):
+        for k in ("matches0", "matches1"):
+            assert torch.equal(out[k], ref[k]), k
+        for k in ("matching_scores0", "matching_scores1"):
+            if exact:
+                assert torch.equal(out[k], ref[k]), k
+            else:          # matched rows; an unmatched near-tie row may flip its mutual check (score ~4e-3 vs 0) between two instances
+                sel = (out[k.replace("matching_scores", "matches")] >= 0)
+                assert sel.any() and float((out[k] - ref[k])[sel].abs().max()) < 1e-5, k
+
+    m = GMatcher(cfg).eval()
+    m.load_state_dict(synth.make_state_dict(123))
+    m.cuda()
+    with torch.no_grad():
+        base = m(pair_to_data(pair, 15, 2, 7, device="cuda"))
+        sd = synth.make_state_dict(123, bin_score=62.1052)          # about the median row maximum of this pair's scores
+        m.load_state_dict(sd)
+        out = m(pair_to_data(pair, 15, 2, 7, device="cuda"))
+        same(out, fresh(sd))
+        assert not torch.equal(out["matches0"], base["matches0"])
+        m.bin_score.fill_(75.4201)
+        out = m(pair_to_data(pair, 15, 2, 7, device="cuda"))
+        same(out, fresh(m.state_dict()))
+    m.load_state_dict(synth.make_state_dict(123))
+    name = "trainstep_n256_s1002_i100"
+    g = load_golden(name)
+    opt = Adam(m.parameters(), lr=1e-2)
+    m.train()
+    loss, _, _ = m(train_data(train_pairs(name, g), g, device="cuda"), mode="train")
+    loss.backward()
+    m.eval()
+    with torch.no_grad():
+        before = m(pair_to_data(pair, 15, 2, 7, device="cuda"))       # packs the weights as they are before the step
+    opt.step()
+    with torch.no_grad():
+        out = m(pair_to_data(pair, 15, 2, 7, device="cuda"))
+        same(out, fresh(m.state_dict()), exact=False)
+    assert not torch.equal(out["matches0"], before["matches0"])

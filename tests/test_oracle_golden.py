@@ -6,7 +6,7 @@ import torch
 
 from gims_amd import synth
 from oracle import gims_oracle as O
-from tests.helpers import check_score_gradients, golden_names, load_golden, pair_to_data, train_data, train_pairs
+from tests.helpers import alpha_pair, check_score_gradients, fixture_state_dict, golden_names, load_golden, pair_to_data, train_data, train_pairs
 
 torch.set_grad_enabled(False)
 
@@ -109,6 +109,28 @@ def test_e2e_unbalanced(name, synth_sd):
     assert (g["out/matches0"] < 0).any() and (g["out/matches1"] < 0).any()      # rows AND columns end in the dustbin
 
 
+@pytest.mark.parametrize("name", golden_names("bine2e_") + golden_names("seede2e_"))
+def test_e2e_alpha_and_weight_seeds(name):
+    """The oracle against the reference at dustbin logits chosen from each pair's own score matrix (-2, p10 / p50 / p90 of the row maxima,
+    above every score: bine2e_*) and with two more weight seeds at bin_score = 1 (seede2e_*): kept ids, matches, scores
+    (tools/gen_golden_alpha.py).  The fixture's matched fraction is what the generator recorded: none above the largest score, some below."""
+    g = load_golden(name)
+    rad, pct, ms, iters = [int(x) for x in g["meta"]]
+    sd = fixture_state_dict(g)
+    assert sd["bin_score"] == g["bin_score"] and sd["bin_score"].dtype == np.float32
+    data = pair_to_data(alpha_pair(g), rad, pct, ms)
+    out = O.gmatcher_forward(sd, data, {"sinkhorn_iterations": iters, "match_threshold": float(g["match_threshold"])})
+    np.testing.assert_array_equal(np.asarray(data["kept_kpts0_indices"][0]), g["out/kept0"])
+    np.testing.assert_array_equal(np.asarray(data["kept_kpts1_indices"][0]), g["out/kept1"])
+    np.testing.assert_array_equal(out["matches0"][0].numpy(), g["out/matches0"])
+    np.testing.assert_array_equal(out["matches1"][0].numpy(), g["out/matches1"])
+    np.testing.assert_allclose(out["matching_scores0"][0].numpy(), g["out/matching_scores0"], atol=5e-5)
+    np.testing.assert_allclose(out["matching_scores1"][0].numpy(), g["out/matching_scores1"], atol=5e-5)
+    frac = float((g["out/matches0"] >= 0).mean())
+    assert frac == float(g["matched_frac"])
+    assert (frac == 0.0) if name.endswith("_atop") else (frac > 0.0)
+
+
 @pytest.mark.parametrize("name", golden_names("full_"))
 def test_full_with_intermediates(name, synth_sd):
     g = load_golden(name)
@@ -152,21 +174,21 @@ def test_e2e_layernorm(name):
     np.testing.assert_allclose(out["matching_scores1"][0].numpy(), g["out/matching_scores1"], atol=5e-5)
 
 
-@pytest.mark.parametrize("name", golden_names("trainloss_"))
-def test_train_loss_forward_vs_reference(synth_sd, name):
+@pytest.mark.parametrize("name", golden_names("trainloss_") + golden_names("binloss_"))
+def test_train_loss_forward_vs_reference(name):
     """Forward value of forward_train's loss (gmatcher.py:309-386, module in eval mode): oracle == reference."""
     g = load_golden(name)
     pairs = train_pairs(name, g)
     data = train_data(pairs, g)
     cfg = {"sinkhorn_iterations": int(g["meta"][4]), "pos_loss_weight": float(g["pos_loss_weight"]), "neg_loss_weight": float(g["neg_loss_weight"])}
-    loss, pos, neg = O.gmatcher_forward(synth_sd, data, cfg, mode="train")
+    loss, pos, neg = O.gmatcher_forward(fixture_state_dict(g), data, cfg, mode="train")
     for b in range(len(pairs)):
         np.testing.assert_array_equal(np.asarray(data["kept_kpts0_indices"][b]), g[f"kept0_{b}"])
     np.testing.assert_allclose([float(loss), float(pos), float(neg)], [g["loss"], g["pos"], g["neg"]], atol=2e-5, rtol=1e-5)
 
 
-@pytest.mark.parametrize("name", [n for n in golden_names("trainloss_") if "n1024_s1000" not in n])
-def test_train_loss_score_gradients_vs_reference(synth_sd, name):
+@pytest.mark.parametrize("name", [n for n in golden_names("trainloss_") if "n1024_s1000" not in n] + golden_names("binloss_"))
+def test_train_loss_score_gradients_vs_reference(name):
     """d loss / d scores and d loss / d bin_score by autograd through the oracle's unrolled Sinkhorn == the reference's autograd."""
     g = load_golden(name)
     pairs = train_pairs(name, g)
@@ -174,6 +196,6 @@ def test_train_loss_score_gradients_vs_reference(synth_sd, name):
     cfg = {"sinkhorn_iterations": int(g["meta"][4]), "pos_loss_weight": float(g["pos_loss_weight"]), "neg_loss_weight": float(g["neg_loss_weight"])}
     st = {"grad_scores": True}
     with torch.enable_grad():
-        loss, _, _ = O.gmatcher_forward(synth_sd, data, cfg, stages=st, mode="train")
+        loss, _, _ = O.gmatcher_forward(fixture_state_dict(g), data, cfg, stages=st, mode="train")
         loss.backward()
     check_score_gradients(g, [st["scores_leaf"].grad[b].numpy() for b in range(len(pairs))], st["alpha_leaf"].grad, len(pairs), rtol=2e-3)

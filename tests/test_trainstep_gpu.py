@@ -8,7 +8,7 @@ import torch
 
 from gims_amd import GMatcher, synth
 from oracle import gims_oracle as O
-from tests.helpers import check_step_gradients, golden_names, load_golden, train_data, train_pairs
+from tests.helpers import check_step_gradients, fixture_state_dict, golden_names, load_golden, train_data, train_pairs
 
 pytestmark = pytest.mark.gpu
 
@@ -41,11 +41,12 @@ def _model(sd, g, precision="bf16x6", use_layernorm=False):
 
 
 @pytest.mark.parametrize("precision", ["bf16x6", "bf16x3"])
-@pytest.mark.parametrize("name", golden_names("trainstep_"))
+@pytest.mark.parametrize("name", golden_names("trainstep_") + golden_names("binstep_"))
 def test_train_step_vs_reference_golden(name, precision):
     g = load_golden(name)
     ln = name.startswith("trainstep_ln_")          # use_layernorm=True: the reference's LayerNorm in every MLP
-    sd = synth.make_state_dict(123, use_layernorm=ln)
+    # (binstep_*: bin_score at the median row maximum of the pair's score matrix, tools/gen_golden_alpha.py)
+    sd = synth.make_state_dict(123, use_layernorm=ln) if "bin_score" not in g else fixture_state_dict(g)
     m = _model(sd, g, precision, ln)
     data = train_data(train_pairs(name, g), g, device="cuda")
     m.zero_grad()

@@ -32,7 +32,7 @@ def sample_index(name: str, numel: int) -> np.ndarray:
     return np.sort(rng.choice(numel, SAMPLE, replace=False)).astype(np.int64)
 
 
-def one(name, sd, cfg, pairs, rad, pct, ms):
+def one(name, sd, cfg, pairs, rad, pct, ms, extra=None):
     model = G.RG.GMatcher(dict(cfg))
     model.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
     model.train()
@@ -66,6 +66,7 @@ def one(name, sd, cfg, pairs, rad, pct, ms):
     for s in "01":
         for b in range(len(pairs)):
             out[f"kept{s}_{b}"] = np.asarray(data[f"kept_kpts{s}_indices"][b], dtype=np.int64)
+    out.update(extra or {})
     G.save(name, **out)
     gn = np.sqrt(sum(float((p.grad.double() ** 2).sum()) for p in model.parameters() if p.grad is not None))
     print(f"  {name}: loss {float(loss):.6f} pos {float(pos):.6f} neg {float(neg):.6f}; {len(names)} gradients, global norm {gn:.4e}", flush=True)

@@ -35,7 +35,7 @@ def matches_of(b, gt_perm, n1):
     return np.concatenate([np.full((len(m), 1), b, np.int64), m], 1)
 
 
-def one(name, model, pairs, rad, pct, ms, iters):
+def one(name, model, pairs, rad, pct, ms, iters, extra=None):
     datas = [G.to_data(p, rad, pct, ms) for p in pairs]
     data = {k: (torch.cat([d[k] for d in datas]) if torch.is_tensor(datas[0][k]) else datas[0][k]) for k in datas[0]}
     data["image0"] = np.concatenate([p["image0"] for p in pairs])
@@ -75,7 +75,7 @@ def one(name, model, pairs, rad, pct, ms, iters):
     kept = {f"kept{s}_{b}": np.asarray(data[f"kept_kpts{s}_indices"][b], dtype=np.int64) for s in "01" for b in range(len(pairs))}
     G.save(name, matches=matches, loss=np.float64(loss), pos=np.float64(pos), neg=np.float64(neg),
            meta=np.asarray([pairs[0]["keypoints0"].shape[1], rad, pct, ms, iters, len(pairs)], dtype=np.int64),
-           pos_loss_weight=np.float64(WEIGHTS["pos_loss_weight"]), neg_loss_weight=np.float64(WEIGHTS["neg_loss_weight"]), **kept, **grads)
+           pos_loss_weight=np.float64(WEIGHTS["pos_loss_weight"]), neg_loss_weight=np.float64(WEIGHTS["neg_loss_weight"]), **kept, **grads, **(extra or {}))
     print(f"  loss {float(loss):.6f} pos {float(pos):.6f} neg {float(neg):.6f}; kept {[len(v) for v in kept.values()]}", flush=True)
 
 
