@@ -424,6 +424,64 @@ __device__ __forceinline__ void attention_peak_sample_wg(const uint16_t* __restr
   }
 }
 
+// ---------------------------------------------------------------------------------------------- exact row maxima of one wave's queries
+// The largest probability of 32 softmax rows, measured by ONE wave: lane (li, lh) holds query row `qr` (lanes li and li + 32 the same row) and
+// walks all keys in 32-key tiles like attention_peak_sample_wg -- S^T = K Q^T with the K fragments straight from global memory, an exact online
+// (maximum, sum), the two lane halves merged at the end.  The 8-wave kernel calls it for rows of fewer than 512 keys whose half-tile bound
+// reached 1/2: n_q x n_kv work that only the waves holding such a row pay.
+template <bool F16>
+__device__ __forceinline__ float attention_rowmax_wave(const uint16_t* __restrict__ qkv, int64_t ld, int q_col, int k_col, const gims_attn_problem pr,
+                                                       int head, float c, int qr) {
+  const int lane = threadIdx.x & 63, li = lane & 31, lh = lane >> 5;
+  bf16x8 qf[4];
+  {
+    const uint16_t* qp = qkv + (int64_t)(pr.q_off + qr) * ld + q_col + head * DH + 8 * lh;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) qf[s] = *(const bf16x8*)(qp + 16 * s);
+  }
+  const int n_tiles = (pr.n_kv + 31) / 32;
+  float m_run = -1e30f, l_run = 0.f;
+  constexpr int TB = 2;                                                   // tiles in flight
+  for (int t0 = 0; t0 < n_tiles; t0 += TB) {
+    bf16x8 kf[TB][4];
+#pragma unroll
+    for (int b = 0; b < TB; ++b) {
+      int kr = (t0 + b) * 32 + li;
+      kr = kr < pr.n_kv ? kr : pr.n_kv - 1;
+      const uint16_t* kp = qkv + (int64_t)(pr.kv_off + kr) * ld + k_col + head * DH + 8 * lh;
+#pragma unroll
+      for (int s = 0; s < 4; ++s) kf[b][s] = *(const bf16x8*)(kp + 16 * s);
+    }
+#pragma unroll
+    for (int b = 0; b < TB; ++b) {
+      const int t = t0 + b;
+      if (t >= n_tiles) break;                                            // wave-uniform
+      f32x16 sacc;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) sacc[r] = 0.f;
+#pragma unroll
+      for (int s = 0; s < 4; ++s) sacc = mfma_16b<F16>(kf[b][s], qf[s], sacc);
+      float tmax = -1e30f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int key = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        if (key >= pr.n_kv) sacc[r] = -1e30f;
+        tmax = fmaxf(tmax, sacc[r]);
+      }
+      const float m_new = fmaxf(m_run, tmax);
+      float sum = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) sum += __builtin_amdgcn_exp2f((sacc[r] - m_new) * c);
+      l_run = l_run * __builtin_amdgcn_exp2f((m_run - m_new) * c) + sum;
+      m_run = m_new;
+    }
+  }
+  const float m_o = __shfl_xor(m_run, 32, 64), l_o = __shfl_xor(l_run, 32, 64);
+  const float m = fmaxf(m_run, m_o);
+  const float l = l_run * __builtin_amdgcn_exp2f((m_run - m) * c) + l_o * __builtin_amdgcn_exp2f((m_o - m) * c);
+  return 1.f / l;
+}
+
 template <bool PROF, bool NOFMA, bool F16 = false>     // NOFMA: Q carries the softmax scale (c == 1): the optimistic pass is P = exp2(S), reference 0
 __global__ __launch_bounds__(512) void attention8_bf16_kernel(
     const uint16_t* __restrict__ qkv, int64_t ld, int q_col, int k_col, int v_col,
@@ -527,7 +585,8 @@ __global__ __launch_bounds__(512) void attention8_bf16_kernel(
   float m_run[QP], l_run[QP];
   // bf16 instance, measured launches: the largest share of a row's mass that one 32-key half tile (this lane's keys of a tile) has held -- an upper
   // bound of the row's largest probability at ONE v_max per query block and tile, so that a single sharply peaked row inside a diffuse layer
-  // cannot hide behind the 32-query sample (the guard of attention_precision='auto' looks at the head's largest row maximum)
+  // cannot hide behind the 32-query sample (the guard of attention_precision='auto' looks at the head's largest row maximum).  Reported as is for
+  // rows of >= 512 keys; for shorter rows it only decides which waves measure their rows exactly (after the epilogue)
   float hmass[QP];
 
   auto store_tile = [&](int buf) __attribute__((always_inline)) {
@@ -787,8 +846,11 @@ __global__ __launch_bounds__(512) void attention8_bf16_kernel(
   bool ran_exact = (exact_only & 1) != 0;
   if (!ran_exact) ran_exact = __syncthreads_or(pass(std::false_type{})) != 0;
   if (ran_exact) pass(std::true_type{});
+  // Rows of fewer than 512 keys: a half tile holds a large share of a merely SHORT row's mass, so the bound is only the trigger there -- a
+  // wave that holds a row whose bound reaches 1/2 measures its rows exactly once its output is stored (attention_rowmax_wave below)
+  bool short_rows = false;                       // wave-uniform
   if constexpr (!F16) {
-    if (stat != nullptr && (ran_exact || pr.n_kv >= 512)) {
+    if (stat != nullptr) {
       // rows whose bound reaches 1/2 (none in a diffuse layer: the block below is skipped by the whole wave); a workgroup that needed the exact
       // pass -- a row sum left f32's range: scores ~100 octaves apart -- reports 1
       unsigned fx = 0u;
@@ -801,9 +863,11 @@ __global__ __launch_bounds__(512) void attention8_bf16_kernel(
         if (row && frac >= 0.5f) { const unsigned f = (unsigned)(frac * 16777216.f + 0.5f); fx = fx > f ? fx : f; }
       }
       if (__ballot(fx != 0u) != 0ull) {
+        if (ran_exact || pr.n_kv >= 512) {
 #pragma unroll
-        for (int o2 = 32; o2 > 0; o2 >>= 1) { const unsigned other = __shfl_xor(fx, o2, 64); fx = fx > other ? fx : other; }
-        if (lane == 0) atomicMax(stat + 4 * head + 2, (unsigned long long)fx);
+          for (int o2 = 32; o2 > 0; o2 >>= 1) { const unsigned other = __shfl_xor(fx, o2, 64); fx = fx > other ? fx : other; }
+          if (lane == 0) atomicMax(stat + 4 * head + 2, (unsigned long long)fx);
+        } else short_rows = true;
       }
     }
   }
@@ -863,6 +927,22 @@ __global__ __launch_bounds__(512) void attention8_bf16_kernel(
             *(uint2*)(out_lo + grow * ld_split + spl_col(col)) = make_uint2(l01, l23);
           }
         }
+    }
+  }
+  if constexpr (!F16) {
+    if (short_rows) {                            // (the accumulators are dead here: the measurement has the register file to itself)
+      unsigned fx = 0u;
+#pragma unroll 1
+      for (int qi = 0; qi < QP; ++qi) {
+        const int qr = q0 + wave * QWV + qi * QW + li;
+        const float pmax = attention_rowmax_wave<F16>(qkv, ld, q_col, k_col, pr, head, c, qr < pr.n_q ? qr : pr.n_q - 1);
+        if (qr < pr.n_q && pmax >= 0.5f) { const unsigned f = (unsigned)(fminf(pmax, 1.f) * 16777216.f + 0.5f); fx = fx > f ? fx : f; }
+      }
+      if (__ballot(fx != 0u) != 0ull) {
+#pragma unroll
+        for (int o2 = 32; o2 > 0; o2 >>= 1) { const unsigned other = __shfl_xor(fx, o2, 64); fx = fx > other ? fx : other; }
+        if (lane == 0) atomicMax(stat + 4 * head + 2, (unsigned long long)fx);
+      }
     }
   }
   if (PROF && bid == 0 && wave == 0 && lane == 0) {      // spans of wave 0: prologue, tile loop, epilogue (shader cycles) and the whole kernel on the 100-MHz counter

@@ -115,7 +115,10 @@ class GMatcher(nn.Module):
         # peaked row inside a diffuse layer (an outlier keypoint: mean and tail fraction stay far under their thresholds, the reference golden
         # raree2e_*_g10 shows 6e-4 of score error on plain bf16 operands).  That redo is per batch: the layer is NOT moved up (one outlier does
         # not cost every later batch the faster tier); forward() repeats such a batch with the device-side guards on.  The figure is complete
-        # for every kernel (the 8-wave kernel bounds every row's maximum by its largest half-tile mass); 0 switches the criterion off.
+        # for every kernel and every row length: the running-maximum kernels report every row; the 8-wave kernel bounds every row's maximum by
+        # its largest half-tile mass, reports that bound for rows of >= 512 keys and, for shorter rows (where half a tile is a large share of a
+        # merely short row), has the waves whose bound reaches 1/2 measure their rows exactly (tests/test_attention_rowmax_gpu.py).  A batch
+        # counts once towards `attention_auto_rare_batches`, also when forward() repeats it.  0 switches the criterion off.
         # `attention_auto_rare_batches`: a layer whose rows did that on this many batches is no outlier any more -- redoing it at three times the
         # matrix work every batch costs more than the half tier's 1.2 x -- and IS moved up (0: never).
         'attention_precision': 'auto',
@@ -130,7 +133,7 @@ class GMatcher(nn.Module):
         # others 0.5 % slower, and with occasional 20-36 ms steps the tables never showed (GMatcher._replays)
         'launch_replay_rows': 0,
         'train_precision': 'bf16x6',      # products of the training step's forward (gims_amd/trainstep.py): 'bf16x6' (f32 class) | 'bf16x3'
-        'train_backward_precision': 'bf16x3',      # products of its reverse pass: 'bf16x3' (default) or 'f32'.  The pass is linear in its operands, but the
+        'train_backward_precision': 'bf16x3',      # products of its reverse pass: 'bf16x3' (default), 'bf16x6' or 'f32'.  The pass is linear in its operands, but the
                                                    # attention scores it recomputes carry 16 mantissa bits against the forward's exact-f32 lse: the error of
                                                    # the attention gradients grows with the logit magnitude, about 2.2e-6 |S| of the largest entry (6e-5 at
                                                    # |S| = 33, 6e-4 at 268: tests/test_train_kernels_gpu.py::test_train_attention_reverse_precision_at_large_logits);
@@ -355,7 +358,8 @@ class GMatcher(nn.Module):
             st = self.__dict__["_attn_auto"] = dict(gen=P["gen"], mode=[2] * L, calibrated=False, peak=np.zeros((L, self._heads)),
                                                     peak_max=np.zeros((L, self._heads)), tail=np.zeros((L, self._heads)),
                                                     range=np.zeros((L, 3)), switched=[], batches={}, redone=np.zeros(L, dtype=np.int64))
-        n_b = st["batches"][self._lane] = st["batches"].get(self._lane, -1) + 1
+        # (forward()'s repeat of a batch IS that batch: it is measured if the batch was -- the device-side guards it runs with read the statistic)
+        n_b = st["batches"][self._lane] = st["batches"].get(self._lane, -1) + (0 if self.__dict__.get("_attn_repeat", False) else 1)
         if st["calibrated"] and n_b % max(1, int(self.config['attention_monitor_period'])) != 0:
             return list(st["mode"]), None              # not a measured batch
         nbytes = L * (self._heads + 1) * 4 * 8
@@ -374,15 +378,20 @@ class GMatcher(nn.Module):
         slot[1].record()
         slot[2] = self._attn_auto["gen"]
 
-    def _attention_stats_consume(self, lane=None):
+    def _attention_stats_consume(self, lane=None, repeat=False):
         """Fold the read-back of `lane` (None: of every lane) into the per-layer decision.  Called by a lane right after the
         host synchronisation of its next batch's graph build -- its previous batch, read-back included, has finished by then,
         so WHEN a measurement takes effect does not depend on timing -- and after forward()'s final synchronisation.
         Decisions only ever move UP (bf16 -> f16 -> bf16x3) once the first measurement is in.  Returns the number of layers a SETTLED table
-        moved up by in this call (forward() repeats its batch then; match_pairs' batches were redone on the device already)."""
+        moved up by in this call (forward() repeats its batch then; match_pairs' batches were redone on the device already).
+        repeat: the read-back belongs to forward()'s repeat of a batch that was counted already -- its outlier rows are the same rows and do
+        not count towards `attention_auto_rare_batches` a second time.  st['rare_last'] speaks of the read-backs folded in by THIS call: a
+        call that finds none leaves it False (an unmeasured batch never inherits the verdict of an earlier one)."""
         st = self.__dict__.get("_attn_auto")
         H = self._heads
         moved = 0
+        if st is not None:
+            st["rare_last"] = False
         for ln, slot in list(self.__dict__.get("_attn_pending", {}).items()):
             if slot[1] is None or (lane is not None and ln != lane):
                 continue
@@ -406,8 +415,8 @@ class GMatcher(nn.Module):
             # repeat the batch with the guards on -- never a reason to move the layer up
             rmx = float(self.config['attention_auto_rowmax'])
             rare = (~hot) & (np.asarray(st["mode"]) == 0) & ((host[:, :, 2] / hip.ATTN_STAT_SCALE >= rmx).any(axis=1) if rmx > 0 else False)
-            st["rare"] = st.get("rare", np.zeros(len(hot), dtype=np.int64)) + rare
-            st["rare_last"] = bool(np.any(rare)) and st["calibrated"]
+            st["rare"] = st.get("rare", np.zeros(len(hot), dtype=np.int64)) + (0 if repeat else rare)
+            st["rare_last"] = st["rare_last"] or (bool(np.any(rare)) and st["calibrated"])
             nb = int(self.config['attention_auto_rare_batches'])
             if nb > 0 and st["calibrated"]:          # no outlier any more: such a layer goes to the half tier like a sharpened one
                 hot = hot | (rare & (st["rare"] >= nb))
@@ -1114,7 +1123,7 @@ class GMatcher(nn.Module):
             st[i:i + 1].copy_(uv[so:so + 1], non_blocking=True)
         torch.cuda.current_stream().synchronize()
         # 'auto' attention: the statistic of THIS batch is in (the first call's measurement decides the next call's kernels)
-        moved = self._attention_stats_consume(self._lane)
+        moved = self._attention_stats_consume(self._lane, repeat=self.__dict__.get("_attn_repeat", False))
         rare = bool(self.__dict__.get("_attn_auto", {}).get("rare_last")) and not self._device_guards
         if (moved or rare) and not last_attempt:
             return None
@@ -1136,7 +1145,11 @@ class GMatcher(nn.Module):
             # ... and so does every REPEAT: a repeat was asked for either by a layer that moved up (then the guards are idle) or by a sharply
             # peaked row inside a diffuse layer, which only the device-side redo answers (the layer is not moved up for one outlier)
             self._device_guards = attempt >= 1
-            done = self._forward_once(data, B, radius, percentile, min_size, attempt == 3)
+            self._attn_repeat = attempt >= 1      # the same batch again: measured like the first attempt, its outlier rows counted once
+            try:
+                done = self._forward_once(data, B, radius, percentile, min_size, attempt == 3)
+            finally:
+                self._attn_repeat = False
             if done is not None:
                 break
             self._attn_forward_repeats = getattr(self, "_attn_forward_repeats", 0) + 1

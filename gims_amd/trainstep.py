@@ -48,9 +48,20 @@ def _backward_precision(cfg):
     with a 3-pass reverse pass equal those of a 6-pass one to three digits (worst 1.0e-3 ... 1.7e-2, p95 8e-5 ... 4.7e-4 either way: what is
     left is the forward's ReLU flips)."""
     p = cfg.get('train_backward_precision', 'bf16x3')
-    if p not in ('bf16x6', 'bf16x3'):
-        raise ValueError("train_backward_precision must be 'bf16x6' or 'bf16x3'")
-    return hip.PREC_BF16X6 if p == 'bf16x6' else hip.PREC_BF16X3
+    if p not in _BACKWARD_PRECISIONS:
+        raise ValueError("train_backward_precision must be 'bf16x3', 'bf16x6' or 'f32'")
+    return hip.PREC_BF16X3 if p == 'bf16x3' else hip.PREC_BF16X6
+
+
+# 'f32': the setting for sharply peaked trained attention -- the attention reverse is asked for exact-f32 products by name; the GEMMs of the
+# reverse pass stay on six bf16 passes (f32 class, as under 'bf16x6')
+_BACKWARD_PRECISIONS = ('bf16x3', 'bf16x6', 'f32')
+
+
+def _attention_backward_kwargs(cfg):
+    """Keyword arguments of the reverse pass's hip.train_attention_backward calls: PREC_F32 by name for train_backward_precision='f32',
+    nothing otherwise (the kernel then follows the GEMM precision of the block it runs in)."""
+    return dict(precision=hip.PREC_F32) if cfg.get('train_backward_precision', 'bf16x3') == 'f32' else {}
 
 
 class _Step:
@@ -333,7 +344,7 @@ def _backward(model, S, w_pos: float, w_neg: float):
         aside(lambda dmsg=dmsg, pre=pre: put(pre + "attn.merge.bias", hip.colsum(dmsg)), dmsg)
         do = hip.gemm(dmsg, L["wm"].t())
         # attention of all images and heads (every image's rows are queries once and sources once per layer: dqkv is written exactly once)
-        dqkv = hip.train_attention_backward(L["qkv"], L["o"], L["lse"], do, S.attn_problems[L["cross"]], HEADS)
+        dqkv = hip.train_attention_backward(L["qkv"], L["o"], L["lse"], do, S.attn_problems[L["cross"]], HEADS, **_attention_backward_kwargs(cfg))
         gw = [torch.empty_like(P[pre + f"attn.proj.{j}.weight"]) for j in range(3)]
         gb = [torch.empty_like(P[pre + f"attn.proj.{j}.bias"]) for j in range(3)]
         gm = torch.empty_like(P[pre + "attn.merge.weight"])

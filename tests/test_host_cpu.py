@@ -304,8 +304,9 @@ def test_auto_attention_routes_on_the_tail_and_the_range():
     before = m.attention_report()["modes"]
     m.__dict__["_attn_pending"] = {0: [torch.from_numpy(raw), Ev(), 7]}
     assert m._attention_stats_consume() == 0
+    assert m._attn_auto["rare_last"] is True       # (speaks of the read-backs of THAT call: read before the report below consumes -- nothing -- again)
     rep = m.attention_report()
-    assert rep["modes"] == before and rep["rare"].tolist() == [0] * 7 + [1] + [0] * (L - 8) and m._attn_auto["rare_last"] is True
+    assert rep["modes"] == before and rep["rare"].tolist() == [0] * 7 + [1] + [0] * (L - 8)
     raw[7, 3, 2] = int(0.3 * 2 ** 24)
     m.__dict__["_attn_pending"] = {0: [torch.from_numpy(raw), Ev(), 7]}
     m._attention_stats_consume()
@@ -317,6 +318,59 @@ def test_auto_attention_routes_on_the_tail_and_the_range():
         moved = m._attention_stats_consume()
         assert m.attention_report()["rare"][7] == k and moved == (1 if k == 3 else 0)
     assert m.attention_report()["modes"][7] == "f16" and m.attention_report()["modes"][8] == "bf16"
+
+
+def test_auto_attention_counts_an_outlier_batch_once():
+    """forward() repeats a batch with an outlier row and reads that batch's statistic a second time: the repeat's read-back does not add to
+    `rare` (attention_auto_rare_batches counts BATCHES, as match_pairs does), and `rare_last` -- forward()'s reason to repeat -- is False after
+    any call that consumed no read-back (an unmeasured batch, attention_monitor_period > 1) instead of keeping an earlier batch's verdict."""
+    m = GMatcher({}).eval()
+    L, H = m.n_layers, 4
+    st = m.__dict__["_attn_auto"] = dict(gen=7, mode=[0] * L, calibrated=True, peak=np.zeros((L, H)), peak_max=np.zeros((L, H)),
+                                         tail=np.zeros((L, H)), range=np.zeros((L, 3)), switched=[], batches={}, redone=np.zeros(L, dtype=np.int64))
+
+    class Ev:
+        def synchronize(self):
+            pass
+
+    raw = np.zeros((L, H + 1, 4), dtype=np.int64)
+    raw[:, :H, 1] = 1000
+    raw[:, :H, 0] = int(0.01 * 1000 * 2 ** 24)
+    raw[:, H, :3] = np.asarray(np.full(3, 20.0), dtype=np.float32).view(np.uint32).astype(np.int64)
+    raw[7, 3, 2] = int(0.97 * 2 ** 24)
+
+    def feed(**kw):
+        m.__dict__["_attn_pending"] = {0: [torch.from_numpy(raw.copy()), Ev(), 7]}
+        return m._attention_stats_consume(0, **kw)
+
+    for batch in (1, 2):                                   # two outlier batches through forward(): attempt 0, then the repeat
+        assert feed() == 0 and st["rare_last"] is True and st["rare"][7] == batch
+        assert feed(repeat=True) == 0 and st["rare"][7] == batch and st["rare_last"] is True      # the repeat still sees the row (its guards answer it)
+        assert st["mode"][7] == 0
+    assert m._attention_stats_consume(0) == 0 and st["rare_last"] is False                          # nothing pending: an unmeasured batch
+    assert m._attention_stats_consume() == 0 and st["rare_last"] is False
+    assert feed() == 1 and st["rare"][7] == 3 and st["mode"][7] == 1                                # the third BATCH moves the layer up
+    m.__dict__["_attn_pending"] = {}
+    m._attention_stats_consume(0)
+    assert st["rare_last"] is False
+
+
+def test_train_backward_precision_takes_the_documented_values():
+    """config['train_backward_precision']: 'bf16x3' (default), 'bf16x6', 'f32' -- the GEMMs of the reverse pass run in three or six bf16 passes
+    ('f32' is the six-pass, f32-class form), the attention reverse is asked for exact-f32 products by name under 'f32' only; anything else raises."""
+    from gims_amd import trainstep
+    assert trainstep._backward_precision({}) == hip.PREC_BF16X3
+    assert trainstep._backward_precision({"train_backward_precision": "bf16x3"}) == hip.PREC_BF16X3
+    assert trainstep._backward_precision({"train_backward_precision": "bf16x6"}) == hip.PREC_BF16X6
+    assert trainstep._backward_precision({"train_backward_precision": "f32"}) == hip.PREC_BF16X6
+    assert trainstep._attention_backward_kwargs({"train_backward_precision": "f32"}) == {"precision": hip.PREC_F32}
+    for v in ("bf16x3", "bf16x6"):
+        assert trainstep._attention_backward_kwargs({"train_backward_precision": v}) == {}
+    assert trainstep._attention_backward_kwargs({}) == {}
+    for bad in ("fp32", "F32", "bf16", "", None, 0, "bf16x9"):
+        with pytest.raises(ValueError, match="train_backward_precision"):
+            trainstep._backward_precision({"train_backward_precision": bad})
+    assert GMatcher.default_config["train_backward_precision"] == "bf16x3"
 
 
 def test_graph_build_flag_words_decide_the_repeat():

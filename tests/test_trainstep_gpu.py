@@ -33,9 +33,9 @@ RTOL_WORST, RTOL_P95 = BARS["bf16x6"]
 LOSS_ATOL = 1e-4
 
 
-def _model(sd, g, precision="bf16x6", use_layernorm=False):
+def _model(sd, g, precision="bf16x6", use_layernorm=False, **config):
     m = GMatcher({"sinkhorn_iterations": int(g["meta"][4]), "pos_loss_weight": float(g["pos_loss_weight"]),
-                  "neg_loss_weight": float(g["neg_loss_weight"]), "train_precision": precision, "use_layernorm": use_layernorm})
+                  "neg_loss_weight": float(g["neg_loss_weight"]), "train_precision": precision, "use_layernorm": use_layernorm, **config})
     m.load_state_dict(sd)
     return m.cuda().train()
 
@@ -74,6 +74,51 @@ def test_train_step_vs_reference_golden(name, precision):
                 assert int(mine) == int(ref), k
             else:
                 np.testing.assert_allclose(mine, ref, rtol=1e-4 if precision == "bf16x6" else 1e-3, atol=1e-5, err_msg=k)
+
+
+@pytest.mark.parametrize("name", ["trainstep_n256_s1002_i100", "trainstep_n512_s1003_i20"])
+def test_train_step_with_f32_reverse_pass_vs_reference_golden(name):
+    """train_backward_precision='f32' (the documented setting for sharply peaked trained attention: the attention reverse on exact-f32 products,
+    the reverse GEMMs in six bf16 passes) is held to the loss and gradient bars of the default step (BARS['bf16x6'])."""
+    g = load_golden(name)
+    m = _model(synth.make_state_dict(123), g, "bf16x6", train_backward_precision="f32")
+    data = train_data(train_pairs(name, g), g, device="cuda")
+    m.zero_grad()
+    loss, pos, neg = m(data, mode="train")
+    loss.backward()
+    got = [float(loss.detach()), float(pos.detach()), float(neg.detach())]
+    np.testing.assert_allclose(got, [g["loss"], g["pos"], g["neg"]], atol=LOSS_ATOL, rtol=0)
+    grads = {k: p.grad.detach().cpu().numpy() for k, p in m.named_parameters() if p.grad is not None}
+    positions = min(int(g["meta"][5]) * len(g[f"kept{s}_0"]) for s in "01")
+    worst, where, p95 = check_step_gradients(g, grads, rtol=max(RTOL_WORST, 10.0 / positions), rtol_p95=RTOL_P95)
+    print(name, "f32 reverse pass: loss", got, "gradients: worst", worst, where, "p95", p95)
+
+
+@pytest.mark.parametrize("value", ["bf16x3", "bf16x6", "f32"])
+def test_train_backward_precision_reaches_the_attention_reverse(monkeypatch, value):
+    """What the reverse pass hands to hip.train_attention_backward: precision=PREC_F32 by name for 'f32', no precision argument for the other
+    two values (the kernel then follows the GEMM precision of the reverse pass: bf16x3 -> three-pass kernel, bf16x6 -> exact f32), 18 calls."""
+    from gims_amd import hip
+    name = "trainstep_n256_s1002_i100"
+    g = load_golden(name)
+    m = _model(synth.make_state_dict(123), g, "bf16x6", train_backward_precision=value)
+    seen = []
+    real = hip.train_attention_backward
+
+    def spy(*args, **kwargs):
+        seen.append((len(args), dict(kwargs), getattr(hip._TLS, "gemm_prec", None)))
+        return real(*args, **kwargs)
+    monkeypatch.setattr(hip, "train_attention_backward", spy)
+    data = train_data(train_pairs(name, g), g, device="cuda")
+    m.zero_grad()
+    loss, _, _ = m(data, mode="train")
+    loss.backward()
+    assert len(seen) == 18
+    for n_args, kwargs, gemm_prec in seen:
+        assert n_args == 6                                                     # (qkv, o, lse, d_o, problems, heads): precision is never positional
+        assert kwargs == ({"precision": hip.PREC_F32} if value == "f32" else {})
+        assert gemm_prec == (hip.PREC_BF16X3 if value == "bf16x3" else hip.PREC_BF16X6)
+    np.testing.assert_allclose(float(loss.detach()), g["loss"], atol=LOSS_ATOL, rtol=0)
 
 
 def test_train_step_vs_oracle_and_optimizer_step():
