@@ -71,6 +71,9 @@ struct AgcWs {
   int32_t* kept; int32_t* indptr; int32_t* indices; int32_t* info;
   int64_t krank;        // percentile rank k (agc.py:378-379)
   int n, d, nw, cap, max_edges_dir;
+  // the image's own graph parameters (gims_agc_params): min_size of the component removal, squared radius, inverse cell side of the keypoint grid
+  int min_size;
+  double r2, inv_side;
 };
 
 // per-image reset of the select state and counters (descriptors are already in device memory, see upload_table)
@@ -893,8 +896,9 @@ __device__ __forceinline__ uint32_t agc_cell_hash(int cx, int cy) {
   h ^= h >> 15;
   return h & (uint32_t)(AGC_NB - 1);
 }
-__global__ __launch_bounds__(1024) void agc_grid_kernel(const AgcWs* __restrict__ ws, double inv_side) {
+__global__ __launch_bounds__(1024) void agc_grid_kernel(const AgcWs* __restrict__ ws) {
   const AgcWs& w = ws[blockIdx.y];
+  const double inv_side = w.inv_side;
   extern __shared__ int cnt[];                  // [AGC_NB] counts, then running fill positions
   __shared__ int wsum[16];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, n = w.n;
@@ -933,8 +937,9 @@ __global__ __launch_bounds__(1024) void agc_grid_kernel(const AgcWs* __restrict_
 // the eight adjacent cells and takes the points j > i of exactly that cell (two cells may share a bucket: no pair twice) that pass the float64
 // test -- the same predicate on the same pairs as the all-pairs kernel below, which stays for degenerate radii.  A workgroup also clears the
 // adjacency rows of its points.  Candidates are staged in LDS (one global reservation per workgroup).
-__global__ __launch_bounds__(288) void agc_radius_grid_kernel(const AgcWs* __restrict__ ws, double r2, double inv_side) {
+__global__ __launch_bounds__(288) void agc_radius_grid_kernel(const AgcWs* __restrict__ ws) {
   const AgcWs& w = ws[blockIdx.y];
+  const double r2 = w.r2, inv_side = w.inv_side;
   const float* __restrict__ kpts = w.kpts;
   __shared__ uint32_t st[RAD_STAGE];
   __shared__ uint32_t nst, gbase;
@@ -1182,8 +1187,9 @@ __global__ __launch_bounds__(256) void agc_fill_kernel(const AgcWs* __restrict__
 // single workgroup; parent[n], count[n] in LDS -- or, GLOBAL (images of more than AGC_CC_LDS_N nodes), in the members / nnc arrays, which are free
 // until the linking step: every access to them is then a device-scope atomic or a volatile access (the workgroup's L1 is never trusted)
 template <bool GLOBAL>
-__global__ __launch_bounds__(1024) void agc_cc_kernel(const AgcWs* __restrict__ ws, int min_size) {
+__global__ __launch_bounds__(1024) void agc_cc_kernel(const AgcWs* __restrict__ ws) {
   const AgcWs& w = ws[blockIdx.y];
+  const int min_size = w.min_size;
   int32_t* __restrict__ kept = w.kept;
   int32_t* info = w.info;
   extern __shared__ int32_t sm[];
@@ -1571,10 +1577,19 @@ extern "C" int gims_agc_build(const gims_agc_image* images, int32_t n_images, do
   return gims_agc_build_ex(images, n_images, radius, percentile, min_size, 0, work, work_bytes, stream);
 }
 
+// one (radius, percentile, min_size) for every image: the per-image entry with the triple replicated
 extern "C" int gims_agc_build_ex(const gims_agc_image* images, int32_t n_images, double radius, double percentile,
                                  int32_t min_size, int32_t flags, void* work, size_t work_bytes, void* stream) {
-  using namespace gims;
   GIMS_CHECK_ARG(images && n_images > 0 && work, "gims_agc_build: null / empty arguments");
+  const gims_agc_params one = {radius, percentile, min_size, 0};
+  const std::vector<gims_agc_params> params((size_t)n_images, one);
+  return gims_agc_build_v(images, n_images, params.data(), flags, work, work_bytes, stream);
+}
+
+extern "C" int gims_agc_build_v(const gims_agc_image* images, int32_t n_images, const gims_agc_params* params, int32_t flags, void* work,
+                                size_t work_bytes, void* stream) {
+  using namespace gims;
+  GIMS_CHECK_ARG(images && n_images > 0 && work && params, "gims_agc_build: null / empty arguments");
   // GIMS_AGC_ROBUST=1 / GIMS_AGC_WINDOW_SHIFT=<x> (read per call: the tests switch flows and force a missed window)
   const bool robust = agc_takes_robust_flow(images, n_images, flags);
   const char* env_shift = getenv("GIMS_AGC_WINDOW_SHIFT");
@@ -1599,10 +1614,17 @@ extern "C" int gims_agc_build_ex(const gims_agc_image* images, int32_t n_images,
     w->info = im.info; w->max_edges_dir = im.max_edges_dir;
     // K2 rank: k = int(L * p / 100), clamped (agc.py:378-379)
     const int64_t L = (int64_t)im.n * (im.n - 1) / 2;
-    int64_t k = (int64_t)(((double)L * percentile) / 100.0);
+    int64_t k = (int64_t)(((double)L * params[i].percentile) / 100.0);
     if (k >= L) k = L - 1;
     if (k < 0) k = 0;
     w->krank = k;
+    // radius candidates go through a keypoint grid of cell side 1.001 |r|, never below 1e-3 (a larger cell only costs tests); an infinite radius
+    // puts every point into one cell (every pair is tested: what the predicate asks for), a NaN radius keeps no pair (agc.py:443: d2 <= r2 is False)
+    double side = fabs(params[i].radius) * 1.001;
+    if (!(side >= 1e-3)) side = 1e-3;
+    w->r2 = params[i].radius * params[i].radius;
+    w->inv_side = 1.0 / side;
+    w->min_size = params[i].min_size;
     maxn = im.n > maxn ? im.n : maxn;
     maxnw = w->nw > maxnw ? w->nw : maxnw;
   }
@@ -1643,13 +1665,10 @@ extern "C" int gims_agc_build_ex(const gims_agc_image* images, int32_t n_images,
       hipLaunchKernelGGL(agc_window_kernel, g1, dim3(256), 0, s, dws, window_test_shift);
       hipLaunchKernelGGL(agc_simw_kernel<SIM_COLLECT>, dim3(wgrid), dim3(256), SW_LDS_BYTES, s, dws, B);
     }
-    // radius candidates through the keypoint grid.  Cell side 1.001 |r|, never below 1e-3 (a larger cell only costs tests); an infinite radius
-    // puts every point into one cell (every pair is tested: what the predicate asks for), a NaN radius keeps no pair (agc.py:443: d2 <= r2 is False)
-    double side = fabs(radius) * 1.001;
-    if (!(side >= 1e-3)) side = 1e-3;
+    // radius candidates through each image's keypoint grid (cell side and squared radius: in its record)
     GIMS_LDS_ATTR((const void*)agc_grid_kernel, AGC_NB * 4);
-    hipLaunchKernelGGL(agc_grid_kernel, g1, dim3(1024), AGC_NB * 4, s, dws, 1.0 / side);
-    hipLaunchKernelGGL(agc_radius_grid_kernel, dim3(cdiv(maxn, 32), B), dim3(288), 0, s, dws, radius * radius, 1.0 / side);
+    hipLaunchKernelGGL(agc_grid_kernel, g1, dim3(1024), AGC_NB * 4, s, dws);
+    hipLaunchKernelGGL(agc_radius_grid_kernel, dim3(cdiv(maxn, 32), B), dim3(288), 0, s, dws);
     // the exact values of the listed entries and of the radius candidates, then the exact k-th among the former
     hipLaunchKernelGGL(agc_exact_kernel, dim3(8 * 4 * (device_cus() / 8)), dim3(256), 0, s, dws, B, robust ? 0 : 1);
     const int lgrid = 1024 / B < 4 ? 4 : (1024 / B > 64 ? 64 : 1024 / B);
@@ -1672,8 +1691,8 @@ extern "C" int gims_agc_build_ex(const gims_agc_image* images, int32_t n_images,
   hipLaunchKernelGGL(agc_scan_kernel, g1, dim3(1024), 0, s, dws, 0);
   hipLaunchKernelGGL(agc_fill_kernel, dim3(cdiv(maxn, 16), B), dim3(256), 0, s, dws, 0);
   // K5
-  if (maxn <= AGC_CC_LDS_N) hipLaunchKernelGGL(agc_cc_kernel<false>, g1, dim3(1024), (size_t)maxn * 8, s, dws, min_size);
-  else hipLaunchKernelGGL(agc_cc_kernel<true>, g1, dim3(1024), 0, s, dws, min_size);
+  if (maxn <= AGC_CC_LDS_N) hipLaunchKernelGGL(agc_cc_kernel<false>, g1, dim3(1024), (size_t)maxn * 8, s, dws);
+  else hipLaunchKernelGGL(agc_cc_kernel<true>, g1, dim3(1024), 0, s, dws);
   // K6: component sizes -> offsets; members, centroids, nearest component, links
   hipLaunchKernelGGL(agc_scan_kernel, g1, dim3(1024), 0, s, dws, 1);
   if (maxn <= 16384) hipLaunchKernelGGL(agc_members_kernel<4>, dim3(32, B), dim3(256), 0, s, dws);

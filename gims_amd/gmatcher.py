@@ -147,6 +147,12 @@ class GMatcher(nn.Module):
         # match_pairs can split a batch into independent sub-batches on separate HIP streams.  Measured on MI355X: no gain
         # (1840 vs 1874 pairs/s at 2x1024, 271 vs 267 at 2x4096) -- every stage already fills the chip -- so default 1.
         'streams': 1,
+        # GMatcher.sweep runs its settings in sub-batches of at most this many keypoint rows (both images of every entry counted; one
+        # entry at least): 65536 is the 8 pairs of 2 x 4096 the throughput numbers of match_pairs are quoted for -- larger sub-batches
+        # gain nothing there, and every entry holds its own activations and score matrix ...
+        'sweep_rows': 65536,
+        # ... and of at most this much graph-build workspace (hip.agc_workspace_bytes: one 32-bit word per keypoint pair of an image)
+        'sweep_workspace_mb': 4096,
     }
 
     def __init__(self, config):
@@ -519,11 +525,13 @@ class GMatcher(nn.Module):
         (2p, 2p+1) form pair p.  Every pair may keep a different number of keypoints (ragged batch)."""
         return self._run_rest(self._run_build(images, radius, percentile, min_size, delaunay=delaunay))
 
-    def _run_build(self, images, radius, percentile, min_size, robust=False, delaunay=False):
+    def _run_build(self, images, radius, percentile, min_size, robust=False, delaunay=False, each=None):
         """Phase 1: enqueue the adaptive graph construction (asynchronous; no host sync).  robust: the graph build histograms every
         similarity instead of predicting where the percentile lies (the repeat after a build reported a missed prediction).
         delaunay: D-GIMS -- the Delaunay triangulation of the keypoints instead (gims_delaunay_build: every keypoint kept; radius,
-        percentile and min_size have no effect); it fills the same kept / indptr / indices / info slots."""
+        percentile and min_size have no effect); it fills the same kept / indptr / indices / info slots.
+        each: one (radius, percentile, min_size, delaunay) per image instead of the four values above (match_pairs(per_pair_graph=True),
+        sweep): the adaptive images go through ONE agc_build_each call, the Delaunay images through ONE delaunay_build call."""
         cfg = self.config
         dev = images[0]["kp"].device
         D = cfg['descriptor_dim']
@@ -544,12 +552,26 @@ class GMatcher(nn.Module):
                 g["kept"], g["indptr"], g["indices"] = pool[o:o + n], pool[o + n:o + 2 * n + 1], pool[o + 2 * n + 4:o + (ec + 2) * n + 4]
                 o += (ec + 2) * n + 4
             info_all = torch.empty((len(images), 8), dtype=torch.int32, device=dev)
-            agc_imgs = hip.make_agc_images([dict(kpts=g["kp"], desc=g["de"], kept=g["kept"], indptr=g["indptr"],
-                                                 indices=g["indices"], info=info_all[i]) for i, g in enumerate(images)])
-            if delaunay:
+            slots = [dict(kpts=g["kp"], desc=g["de"], kept=g["kept"], indptr=g["indptr"], indices=g["indices"], info=info_all[i])
+                     for i, g in enumerate(images)]
+            aflags = hip.AGC_ROBUST if robust else 0        # (the default flow never stores the N x N half matrix: half the workspace)
+            if each is not None:
+                assert len(each) == len(images)
+                tri = [i for i, e in enumerate(each) if e[3]]
+                ada = [i for i, e in enumerate(each) if not e[3]]
+                if tri:
+                    tri_imgs = hip.make_agc_images([slots[i] for i in tri])
+                    hip.delaunay_build(tri_imgs, self._buf("delaunay", hip.delaunay_workspace_bytes(tri_imgs)))
+                if ada:
+                    ada_imgs = hip.make_agc_images([slots[i] for i in ada])
+                    hip.agc_build_each(ada_imgs, [each[i][:3] for i in ada], self._buf("agc", hip.agc_workspace_bytes(ada_imgs, aflags)),
+                                       flags=aflags)
+                delaunay = False
+            elif delaunay:
+                agc_imgs = hip.make_agc_images(slots)
                 hip.delaunay_build(agc_imgs, self._buf("delaunay", hip.delaunay_workspace_bytes(agc_imgs)))
             else:
-                aflags = hip.AGC_ROBUST if robust else 0        # (the default flow never stores the N x N half matrix: half the workspace)
+                agc_imgs = hip.make_agc_images(slots)
                 hip.agc_build(agc_imgs, radius, percentile, min_size, self._buf("agc", hip.agc_workspace_bytes(agc_imgs, aflags)), flags=aflags)
             # everything of the next stage that does not depend on the kept counts is prepared NOW, while the GPU builds the
             # graphs: after the host sync only two cumsums stand between the counts and the next launch
@@ -559,7 +581,7 @@ class GMatcher(nn.Module):
             # NHWC callers => (height, width) = (W, 3): the reference's quirk, kept verbatim.
             hw = np.asarray([[g["shape"][3], g["shape"][2]] for g in images], dtype=np.float32)   # size = [width, height]
             norm3 = np.concatenate([hw / np.float32(2), (hw.max(axis=1, keepdims=True) * np.float32(0.7))], axis=1).astype(np.float32)
-            norm3 = hip.upload(norm3, dev)
+            norm3_host, norm3 = norm3, hip.upload(norm3, dev)
             n_up = sum(ns)                                  # upper bounds: kept <= n, edges <= capacity * n
             bufs = dict(feat=torch.empty((n_up, D), dtype=torch.float32, device=dev),
                         kpts=torch.empty((n_up, 2), dtype=torch.float32, device=dev),
@@ -568,7 +590,7 @@ class GMatcher(nn.Module):
                         indptr=torch.empty((n_up + 1,), dtype=torch.int32, device=dev),
                         indices=torch.empty((ec * n_up + 1,), dtype=torch.int32, device=dev))
         return dict(images=images, info_all=info_all, pool=pool, ptab=ptab, norm3=norm3, bufs=bufs, params=(radius, percentile, min_size),
-                    robust=robust, delaunay=delaunay)
+                    robust=robust, delaunay=delaunay, each=each, norm3_host=norm3_host)
 
     _edge_cap = 64
 
@@ -614,7 +636,14 @@ class GMatcher(nn.Module):
         torch.cuda.current_stream().synchronize()
         infos = pin[:info_all.shape[0]].numpy().copy()
         self._sync_ms = 1e3 * (time.perf_counter() - ts0)
-        action = self._agc_retry(infos[:, 7], bool(ctx.get("robust")), bool(ctx.get("delaunay")))
+        each = ctx.get("each")
+        if each is None:
+            action = self._agc_retry(infos[:, 7], bool(ctx.get("robust")), bool(ctx.get("delaunay")))
+        else:       # per-image graph kinds: every image's flag word is read by the rules of its own build (the other kind's masked out)
+            tri = np.asarray([bool(e[3]) for e in each])
+            acts = [self._agc_retry(np.where(tri, infos[:, 7], 0), bool(ctx.get("robust")), True) if tri.any() else None,
+                    self._agc_retry(np.where(tri, 0, infos[:, 7]), bool(ctx.get("robust")), False)]
+            action = "robust" if "robust" in acts else ("grow" if "grow" in acts else None)
         if action == "robust":
             # the percentile window predicted from the similarity sample did not provably hold the threshold (gims_agc_build_ex): the
             # outputs of this build are void; the repeat histograms every similarity
@@ -635,8 +664,20 @@ class GMatcher(nn.Module):
             self._edge_cap = cap
             ctx["params"] = tuple(ctx["params"][:3]) + (bool(ctx.get("robust")),)      # a robust build stays robust when it is repeated for room
             return None
+        norm3 = ctx["norm3"]
         if (infos[:, 0] == 0).any():
-            raise ValueError("need at least one array to concatenate")               # np.vstack([]) in agc.py:701
+            if not ctx.get("skip_empty"):
+                raise ValueError("need at least one array to concatenate")               # np.vstack([]) in agc.py:701
+            # sweep: a pair with an image that keeps nothing leaves the batch here, before the compaction (the reference raises for that
+            # setting alone, and parameter_search.py records it as a row without matches)
+            gone = (infos[:, 0].reshape(-1, 2) == 0).any(axis=1)
+            ctx["dropped"] = np.nonzero(gone)[0].tolist()
+            keep = np.repeat(~gone, 2)
+            images = ctx["images"] = [g for g, k in zip(images, keep) if k]
+            infos, ctx["ptab"] = infos[keep], ctx["ptab"][keep]
+            if not images:
+                return dict(n_tot=0)
+            norm3 = hip.upload(ctx["norm3_host"][keep], dev)
 
         # ---- kept-keypoint compaction (gmatcher.py:244-249): rows of all images concatenated, one launch
         row_off = np.concatenate([[0], np.cumsum(infos[:, 0], dtype=np.int64)])
@@ -653,7 +694,7 @@ class GMatcher(nn.Module):
             g["n_kept"], g["n_edges"], g["info_host"] = int(inf[0]), int(inf[1]), inf
             g["rows"] = (ro, g["n_kept"])
         return dict(feat=feat, kpts_all=kpts_all, score_all=score_all, seg=seg, indptr_all=indptr_all, indices_all=indices_all,
-                    norm3=ctx["norm3"], n_tot=n_tot, e_tot=e_tot)
+                    norm3=norm3, n_tot=n_tot, e_tot=e_tot)
 
     @staticmethod
     def _finish_graphs(images, G):
@@ -693,7 +734,13 @@ class GMatcher(nn.Module):
         St = lambda name: GMatcher._Stage(self, name)   # noqa: E731
         G = self._gather(ctx)
         if G is None:
-            return self._run_rest(self._run_build(images, *ctx["params"], delaunay=bool(ctx.get("delaunay"))))
+            again = self._run_build(images, *ctx["params"], delaunay=bool(ctx.get("delaunay")), each=ctx.get("each"))
+            again["skip_empty"], again["repeats"] = ctx.get("skip_empty", False), ctx.get("repeats", 0) + 1
+            return self._run_rest(again)
+        images = ctx["images"]              # (a sweep's sub-batch may have lost the pairs that kept nothing)
+        if not images:
+            self._last = dict(items=[], pairs=[], images=[], dropped=ctx.get("dropped", []), repeats=ctx.get("repeats", 0), outputs=[])
+            return [], [], None
         feat, kpts_all, score_all, seg = G["feat"], G["kpts_all"], G["score_all"], G["seg"]
         indptr_all, indices_all, norm3, n_tot = G["indptr_all"], G["indices_all"], G["norm3"], G["n_tot"]
         # ---- GraphSAGE over the merged CSR of all images (gmatcher.py:145-162, 268-269)
@@ -948,7 +995,8 @@ class GMatcher(nn.Module):
         self._finish_graphs(images, G)
         self._last = dict(items=items, pairs=pairs, mdesc=mdesc, desc=desc, sage=sage, images=images,
                           flat=dict(matches0=m0_all, scores0=s0_all, n0=[n0 for (_, n0), _ in pairs], n1=[n1 for _, (_, n1) in pairs]),
-                          outputs=[m0_all, m1_all, s0_all, s1_all, uv_all, mdesc, feat, kpts_all, score_all, ctx["pool"]])
+                          outputs=[m0_all, m1_all, s0_all, s1_all, uv_all, mdesc, feat, kpts_all, score_all, ctx["pool"]],
+                          dropped=ctx.get("dropped", []), repeats=ctx.get("repeats", 0))
         return items, pairs, mdesc
 
     def _encoder_replay(self, P, feat, kpts_all, seg, indptr_all, indices_all, norm3, n_tot):
@@ -1208,11 +1256,15 @@ class GMatcher(nn.Module):
 
     # ------------------------------------------------------------------ ragged batch of independent pairs
     @torch.no_grad()
-    def match_pairs(self, datas: List[dict], **kwargs):
+    def match_pairs(self, datas: List[dict], *, per_pair_graph=False, **kwargs):
         """Throughput API: a list of single-pair dicts (each exactly what ``forward`` takes with B == 1) is
         matched in ONE batched pass even when every pair keeps a different number of keypoints (the reference's
         ``forward`` can only stack equal-sized pairs, gmatcher.py:244-249).  Each dict is mutated like ``forward``
-        does and a list of per-pair result dicts (same keys as ``forward``) is returned."""
+        does and a list of per-pair result dicts (same keys as ``forward``) is returned.
+
+        All pairs of a call share radius / percentile / min_size and ``delaunay`` (ValueError otherwise) unless
+        ``per_pair_graph=True``: then every dict's own values (defaults 25 / 7 / 8, False) are honoured inside the same single pass --
+        the graph build takes its parameters per image (gims_agc_build_v), the Delaunay pairs go through one Delaunay build."""
         tm0 = time.perf_counter()
         self._device_guards = True          # no host synchronisation at the end of this call: the 'auto' verdict is drawn on the device
         n_lanes = int(self.config.get('streams', 1))
@@ -1227,13 +1279,13 @@ class GMatcher(nn.Module):
                 raise ValueError("match_pairs takes single-pair dicts (B == 1)")
         d0 = datas[0]
         params = (d0.get('radius', 25), d0.get('percentile', 7), d0.get('min_size', 8))
-        for i, data in enumerate(datas):        # one graph-build launch serves the whole batch: its parameters are the batch's
+        for i, data in enumerate(() if per_pair_graph else datas):        # one graph-build launch serves the whole batch: its parameters are the batch's
             if (data.get('radius', 25), data.get('percentile', 7), data.get('min_size', 8)) != params:
                 raise ValueError(f"match_pairs: pair {i} asks for radius / percentile / min_size = "
                                  f"{(data.get('radius', 25), data.get('percentile', 7), data.get('min_size', 8))}, pair 0 for {params}; "
                                  "all pairs of one call share the adaptive-graph parameters (call match_pairs once per setting)")
         delaunay = bool(d0.get('delaunay', False))
-        for i, data in enumerate(datas):
+        for i, data in enumerate(() if per_pair_graph else datas):
             if bool(data.get('delaunay', False)) != delaunay:
                 raise ValueError(f"match_pairs: pair {i} asks for delaunay={bool(data.get('delaunay', False))}, pair 0 for delaunay={delaunay}; "
                                  "all pairs of one call share the graph construction (call match_pairs once per setting)")
@@ -1252,7 +1304,8 @@ class GMatcher(nn.Module):
                 self._lane = gi
                 raw = [(data['keypoints' + side][0], data['descriptors' + side][0], data['scores' + side][0], data['image' + side].shape)
                        for data in grp for side in ("0", "1")]
-                ctxs.append(self._run_build(self._ingest(raw), *params, delaunay=delaunay))
+                each = [self._graph_setting(data) for data in grp for _ in ("0", "1")] if per_pair_graph else None
+                ctxs.append(self._run_build(self._ingest(raw), *params, delaunay=delaunay, each=each))
         tm1 = time.perf_counter()
         outs, flats = [], []
         for gi, grp in enumerate(groups):
@@ -1293,3 +1346,91 @@ class GMatcher(nn.Module):
             self._timers.setdefault("_host_marks", []).append((None, None, (1e3 * (tm1 - tm0), 1e3 * (tm2 - tm1), 1e3 * (time.perf_counter() - tm2),
                                                                             getattr(self, "_sync_ms", 0.0))))
         return outs
+
+    @staticmethod
+    def _graph_setting(s):
+        """(radius, percentile, min_size, delaunay) of a data dict or of one entry of a sweep's grid (a triple, or a dict that may carry
+        ``delaunay``); the defaults are forward()'s."""
+        if isinstance(s, dict):
+            return (s.get('radius', 25), s.get('percentile', 7), s.get('min_size', 8), bool(s.get('delaunay', False)))
+        radius, percentile, min_size = s
+        return (radius, percentile, min_size, False)
+
+    # ------------------------------------------------------------------ one pair under a grid of graph parameters
+    @torch.no_grad()
+    def sweep(self, data, grid, *, rows=None, outputs="all"):
+        """One image pair matched under every graph setting of ``grid`` (what the reference's tools/parameter_search.py does with one
+        ``forward`` per setting).  ``data``: a single-pair dict as ``forward`` takes it (B == 1; not mutated).  ``grid``: an iterable of
+        ``(radius, percentile, min_size)`` triples or of dicts with those keys that may also carry ``delaunay``.
+
+        The two images are ingested ONCE; every setting is an entry of a batch whose images point at the same keypoint / descriptor /
+        score buffers, and the entries run like the pairs of ``match_pairs(per_pair_graph=True)``, in sub-batches of at most
+        ``rows`` keypoint rows (default ``config['sweep_rows']``) and ``config['sweep_workspace_mb']`` of graph-build workspace.  One
+        host synchronisation per sub-batch (the kept counts), none per setting.
+
+        Returns one record per setting, in grid order: ``radius, percentile, min_size, delaunay, kept0, kept1`` (host numbers),
+        ``n_matches`` (a 0-dim device tensor: ``(matches0 > -1).sum()``), ``error`` (None) and ``result``: the per-pair dict of
+        ``match_pairs`` plus ``kept_kpts0_indices`` / ``kept_kpts1_indices`` (device tensors; ``outputs='matches'`` leaves out keypoints,
+        descriptors and mdesc, which are 16 MB per setting at 2 x 4096).  A setting under which an image keeps nothing does not raise
+        (``forward`` and ``match_pairs`` do, like the reference): its record has ``error='ValueError: need at least one array to
+        concatenate'``, ``kept0 = kept1 = 0``, ``n_matches = 0`` and ``result=None``, the way parameter_search.py writes such a row."""
+        self._check_call(data, {})
+        if data['keypoints0'].shape[0] != 1:
+            raise ValueError("sweep takes one single-pair dict (B == 1)")
+        if outputs not in ("all", "matches"):
+            raise ValueError("outputs must be 'all' or 'matches'")
+        settings = [self._graph_setting(s) for s in grid]
+        if not settings:
+            return []
+        cfg = self.config
+        self._device_guards = True          # as in match_pairs: no host synchronisation at the end, the 'auto' verdict is drawn on the device
+        self._lanes_active, self._lane = 1, 0
+        records = [None] * len(settings)
+        stats = self.sweep_stats_last = dict(settings=len(settings), ingests=0, sub_batches=0, build_repeats=0)
+        with hip.pinned_stream():
+            base = self._ingest([(data['keypoints' + side][0], data['descriptors' + side][0], data['scores' + side][0], data['image' + side].shape)
+                                 for side in ("0", "1")])
+            stats["ingests"] += 1
+            dev = base[0]["kp"].device
+            n_rows = base[0]["kp"].shape[0] + base[1]["kp"].shape[0]
+            per = max(1, int(rows if rows is not None else cfg['sweep_rows']) // n_rows)
+            if min(g["kp"].shape[0] for g in base) >= 2 and not all(s[3] for s in settings):
+                # the workspace of one entry's two images (the slots are never written by this call: it only sizes)
+                z = torch.empty(8, dtype=torch.int32, device=dev)
+                one = hip.agc_workspace_bytes(hip.make_agc_images([dict(kpts=g["kp"], desc=g["de"], kept=z, indptr=z, indices=z, info=z) for g in base]), 0)
+                per = max(1, min(per, (int(cfg['sweep_workspace_mb']) << 20) // max(one, 1)))
+            for c0 in range(0, len(settings), per):
+                chunk = settings[c0:c0 + per]
+                images = [dict(kp=g["kp"], de=g["de"], sc=g["sc"], shape=g["shape"]) for _ in chunk for g in base]
+                ctx = self._run_build(images, None, None, None, each=[s for s in chunk for _ in (0, 1)])
+                ctx["skip_empty"] = True
+                items, pairs, mdesc = self._run_rest(ctx)
+                stats["sub_batches"] += 1
+                stats["build_repeats"] += self._last["repeats"]
+                images, dropped = self._last["images"], set(self._last["dropped"])
+                if items:       # matches per entry: one segmented count for the sub-batch
+                    m0_all = self._last["flat"]["matches0"]
+                    ends = np.cumsum(self._last["flat"]["n0"], dtype=np.int64)
+                    csum = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), (m0_all > -1).cumsum(0)])
+                    n_matches = csum[hip.upload(ends, dev)] - csum[hip.upload(ends - np.asarray(self._last["flat"]["n0"], dtype=np.int64), dev)]
+                p = 0
+                for j, (radius, percentile, min_size, delaunay) in enumerate(chunk):
+                    rec = dict(radius=radius, percentile=percentile, min_size=min_size, delaunay=delaunay, kept0=0, kept1=0, n_matches=0,
+                               error=None, result=None)
+                    records[c0 + j] = rec
+                    if j in dropped:
+                        rec["error"] = "ValueError: need at least one array to concatenate"
+                        continue
+                    g0, g1, it = images[2 * p], images[2 * p + 1], items[p]
+                    (o0, n0), (o1, n1) = pairs[p]
+                    rec.update(kept0=n0, kept1=n1, n_matches=n_matches[p])
+                    res = {'matches0': it["matches0"][None], 'matches1': it["matches1"][None],
+                           'matching_scores0': it["mscores0"][None], 'matching_scores1': it["mscores1"][None],
+                           'kept_kpts0_indices': [g0["kept"]], 'kept_kpts1_indices': [g1["kept"]]}
+                    if outputs == "all":
+                        res.update({'keypoints0': g0["graph"].ndata['point'][None], 'keypoints1': g1["graph"].ndata['point'][None],
+                                    'descriptors0': g0["graph"].ndata['feat'].t()[None], 'descriptors1': g1["graph"].ndata['feat'].t()[None],
+                                    'mdesc0': mdesc[o0:o0 + n0], 'mdesc1': mdesc[o1:o1 + n1]})
+                    rec["result"] = res
+                    p += 1
+        return records

@@ -82,6 +82,10 @@ class AgcImage(C.Structure):
                 ("info", C.c_void_p)]
 
 
+class AgcParams(C.Structure):
+    _fields_ = [("radius", C.c_double), ("percentile", C.c_double), ("min_size", C.c_int32), ("reserved", C.c_int32)]
+
+
 class PackImage(C.Structure):
     _fields_ = [("kpts", C.c_void_p), ("desc", C.c_void_p), ("ldd", C.c_int64), ("score", C.c_void_p),
                 ("kept", C.c_void_p), ("indptr", C.c_void_p), ("indices", C.c_void_p),
@@ -228,6 +232,7 @@ _SIGNATURES = {
     "gims_agc_max_keypoints": (C.c_int32, []),
     "gims_agc_build": (C.c_int, [C.POINTER(AgcImage), C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_void_p,
                                  C.c_size_t, C.c_void_p]),
+    "gims_agc_build_v": (C.c_int, [C.POINTER(AgcImage), C.c_int32, C.POINTER(AgcParams), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "gims_agc_build_ex": (C.c_int, [C.POINTER(AgcImage), C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_void_p,
                                     C.c_size_t, C.c_void_p]),
     "gims_delaunay_workspace_bytes": (C.c_size_t, [C.POINTER(AgcImage), C.c_int32]),
@@ -767,6 +772,16 @@ def agc_build(images, radius, percentile, min_size, work: torch.Tensor, flags=0)
     lib = load()
     _check(lib.gims_agc_build_ex(images, len(images), float(radius), float(percentile), int(min_size), int(flags), _p(work),
                                  work.numel() * work.element_size(), _stream()), "gims_agc_build_ex")
+
+
+def agc_build_each(images, params, work: torch.Tensor, flags=0):
+    """agc_build with each image's own parameters: params[i] = (radius, percentile, min_size) of images[i] (gims_agc_build_v)."""
+    params = list(params)
+    if len(params) != len(images):
+        raise ValueError(f"agc_build_each: {len(images)} images but {len(params)} parameter triples")
+    arr = (AgcParams * len(params))(*[AgcParams(float(r), float(t), int(m), 0) for r, t, m in params])
+    _check(load().gims_agc_build_v(images, len(images), arr, int(flags), _p(work), work.numel() * work.element_size(), _stream()),
+           "gims_agc_build_v")
 
 
 DT_INFO_DEGENERATE, DT_INFO_ASYMMETRIC = 4, 8     # bits of info[7] set by delaunay_build (bit 0: AGC_INFO_OVERFLOW, same meaning)

@@ -42,7 +42,8 @@ class Matching(torch.nn.Module):
         self.max_keypoints = config.get('max_keypoints', -1)
         self._front_end = _find_front_end(config)
 
-    def forward(self, data):
+    def _front(self, data):
+        """models/matching.py:17-26: the front end for the side(s) the caller gave no keypoints for; returns (pred, data) with the lists stacked."""
         pred = {}
         for side in ('0', '1'):                         # models/matching.py:17-24
             if 'keypoints' + side in data:
@@ -59,5 +60,15 @@ class Matching(torch.nn.Module):
         for k in data:
             if isinstance(data[k], (list, tuple)):
                 data[k] = torch.stack(data[k])
+        return pred, data
+
+    def forward(self, data):
+        pred, data = self._front(data)
         pred = {**pred, **self.gmodel(data)}
         return pred
+
+    def sweep(self, data, grid, **kwargs):
+        """The pair of ``data`` under every graph setting of ``grid``: the front end (detection, patches, descriptors) runs ONCE, then
+        ``GMatcher.sweep`` (see there for the grid, the keywords and the records returned).  ``data`` is not mutated."""
+        _, data = self._front(data)
+        return self.gmodel.sweep(data, grid, **kwargs)

@@ -357,6 +357,12 @@ int gims_agc_build(const gims_agc_image* h_images /* HOST array */, int32_t n_im
 #define GIMS_AGC_ROBUST 1
 int gims_agc_build_ex(const gims_agc_image* h_images /* HOST array */, int32_t n_images, double radius, double percentile,
                       int32_t min_size, int32_t flags, void* work, size_t work_bytes, void* stream);
+/* The same with each image's own (radius, percentile, min_size): h_params[i] belongs to h_images[i].  Still one launch per stage for the
+ * whole batch; same workspace functions, info[8], flags and flows.  The two entries above are this one with one triple replicated.
+ * `reserved` is not read (keep it 0). */
+typedef struct gims_agc_params { double radius, percentile; int32_t min_size, reserved; } gims_agc_params;
+int gims_agc_build_v(const gims_agc_image* h_images /* HOST array */, int32_t n_images, const gims_agc_params* h_params /* HOST [n_images] */,
+                     int32_t flags, void* work, size_t work_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Delaunay graph construction for a BATCH of images (D-GIMS: the reference's build_graph_from_keypoints_Delaunay, models/agc.py:718-751,
