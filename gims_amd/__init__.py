@@ -5,5 +5,6 @@ Kernels live in ``gims_amd/csrc`` (HIP, gfx950) behind the C ABI of ``include/gi
 """
 from .gmatcher import GMatcher  # noqa: F401
 from .matching import Matching  # noqa: F401
+from .baselines import mnn, nn_match_pairs, nndr  # noqa: F401
 
-__all__ = ["GMatcher", "Matching"]
+__all__ = ["GMatcher", "Matching", "nndr", "mnn", "nn_match_pairs"]

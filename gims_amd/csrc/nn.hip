@@ -1,0 +1,499 @@
+// Classical descriptor baselines on the device: nearest-neighbour distance ratio (NNDR) and mutual nearest neighbours (MNN).
+// replaces: calculate_nndr / calculate_mnn (eval_matches.py:13-67).  Semantics: include/gims_hip.h; design and error bound: DESIGN.md 4.11.
+//
+// A PROBLEM is one direction of one pair: queries X [nx][d] against the data base Y [ny][d] (A against B, and for MNN also B against A: the
+// same kernels through one problem table, one launch per stage for every direction of every pair).
+//   norms      float64 |row|^2 of every row, float32 copies for the candidate pass, the largest per matrix (integer max on the bits);
+//   candidate  exact-f32 MFMA (v_mfma_f32_32x32x2_f32) tiles of Y X^T.  Y is the ROW operand and X the COLUMN operand, so a lane owns one query
+//              (accumulator column) and its 16 registers of an MFMA tile are 16 data-base columns of that query: the 4 smallest approximate scores
+//              s^(i,j) = |y_j|^2 - 2 x_i.y_j per query stay in the lane's registers across the column tiles, no cross-lane work in the loop, and
+//              no tile of the product is ever stored.  Every (column split, wave column half, lane half) ends with its own list of 4: a query has
+//              4 * csplit lists, each over a disjoint column subset;
+//   refine     one wave per query: exact float64 distances of the candidates that can still be among the two nearest, then the certificate
+//              e2 < |x_i|^2 + T - eps_i  (T = the smallest of the lists' largest kept scores).  A query that fails goes on a device-side list;
+//   exhaustive the listed queries against all of Y with the same float64 distance routine (bit-identical to what refine would have written);
+//   finish     ratio, threshold, mutual test, matches / scores.
+#include "common.h"
+
+#include <math.h>
+#include <string.h>
+
+#include <vector>
+
+namespace gims {
+
+constexpr int NN_K = 4;                    // kept per list
+constexpr int NN_T = 128;                  // queries / data-base columns per workgroup tile
+constexpr int NN_BK = 32, NN_LD = NN_T + 1;
+constexpr int NN_MAXT = 8;                 // d <= 64 * NN_MAXT
+constexpr int NN_MAX_N = 32768;
+constexpr int NN_TARGET_WGS = 512;         // two workgroups per CU: small problems split their columns until the grid is about this large
+constexpr int NN_MAX_SPLIT = 8;
+
+struct NnProb {
+  const float* x; const float* y; int64_t ldx, ldy;
+  int32_t nx, ny, d, csplit;               // lists per query = 4 * csplit
+  int32_t tiles_per, item0, forced, reserved;
+  const double* xn; const float* ynf; const uint32_t* ymax_bits;
+  float* cs; int32_t* ci;                  // [nx][4 * csplit][NN_K] approximate score / column id (-1: empty slot, score +inf)
+  int32_t* nn1; int32_t* nn2; float* d1; float* d2;
+  int32_t* fb_rows; int32_t* fb_count;
+  float* debug;
+};
+
+struct NnPairDev {
+  const float* a; const float* b; int64_t lda, ldb;
+  int32_t n0, n1, d, mutual;
+  float threshold; int32_t forced;
+  double* an; double* bn; float* anf; float* bnf; uint32_t* amax; uint32_t* bmax;
+  const int32_t* nn1; const float* d1; const float* d2; const int32_t* cnn1;
+  float* ratio; uint8_t* match; int64_t* matches0; float* scores0; int64_t* matches1; int32_t* info;
+  const int32_t* fb_count0; const int32_t* fb_count1;
+};
+
+// The exact squared distance of include/gims_hip.h: lane l sums k = l, l + 64, ... (square rounded, then added), then the xor butterfly
+// 32, 16, 8, 4, 2, 1.  Every lane returns the same value (a + b == b + a).  y == nullptr: the squared norm of x.
+__device__ __forceinline__ double nn_exact_d2(const float (&xv)[NN_MAXT], const float* __restrict__ y, int d, int lane) {
+  double acc = 0.0;
+#pragma unroll
+  for (int t = 0; t < NN_MAXT; ++t) {
+    const int k = lane + 64 * t;
+    if (k < d) {
+      const double df = (double)xv[t] - (y ? (double)y[k] : 0.0);
+      acc = __dadd_rn(acc, __dmul_rn(df, df));
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc = __dadd_rn(acc, __shfl_xor(acc, o, 64));
+  return acc;
+}
+__device__ __forceinline__ void nn_load_row(float (&xv)[NN_MAXT], const float* __restrict__ x, int d, int lane) {
+#pragma unroll
+  for (int t = 0; t < NN_MAXT; ++t) {
+    const int k = lane + 64 * t;
+    xv[t] = k < d ? x[k] : 0.f;
+  }
+}
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ float f32_round_up(double v) {       // smallest float >= v (v >= 0)
+  float f = (float)v;
+  if ((double)f < v) f = __uint_as_float(__float_as_uint(f) + 1u);
+  return f;
+}
+
+// (S, j) ordered lexicographically: the two nearest so far.  NaN compares false everywhere and is never taken.
+struct NnBest { double e1, e2; int i1, i2; };
+__device__ __forceinline__ void nn_best_init(NnBest& b) { b.e1 = b.e2 = INFINITY; b.i1 = b.i2 = 0x7fffffff; }
+__device__ __forceinline__ void nn_best_update(NnBest& b, double e, int j) {
+  if (e < b.e1 || (e == b.e1 && j < b.i1)) { b.e2 = b.e1; b.i2 = b.i1; b.e1 = e; b.i1 = j; }
+  else if (e < b.e2 || (e == b.e2 && j < b.i2)) { b.e2 = e; b.i2 = j; }
+}
+__device__ __forceinline__ void nn_best_write(const NnProb& P, int i, const NnBest& b) {
+  P.nn1[i] = b.i1 == 0x7fffffff ? -1 : b.i1;
+  P.nn2[i] = b.i2 == 0x7fffffff ? -1 : b.i2;
+  P.d1[i] = (float)sqrt(b.e1);
+  P.d2[i] = (float)sqrt(b.e2);
+}
+
+// ---------------------------------------------------------------------------------------------- norms
+__global__ __launch_bounds__(256) void nn_norms_kernel(const NnPairDev* __restrict__ pairs) {
+  const NnPairDev& P = pairs[blockIdx.y];
+  const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= P.n0 + P.n1) return;
+  const bool isa = r < P.n0;
+  const int i = isa ? r : r - P.n0;
+  float xv[NN_MAXT];
+  nn_load_row(xv, isa ? P.a + (int64_t)i * P.lda : P.b + (int64_t)i * P.ldb, P.d, lane);
+  const double n2 = nn_exact_d2(xv, nullptr, P.d, lane);
+  if (lane == 0) {
+    (isa ? P.an : P.bn)[i] = n2;
+    (isa ? P.anf : P.bnf)[i] = (float)n2;
+    atomicMax(isa ? P.amax : P.bmax, __float_as_uint(f32_round_up(n2)));      // non-negative floats order like their bit patterns; NaN sorts above all
+    if (!isa && P.mutual) P.matches1[i] = -1;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- candidate pass
+#define NN_INSERT(IX, S, J)                                                                              \
+  do {                                                                                                   \
+    if ((S) < ls[IX][3]) {                                                                               \
+      float s_ = (S); int j_ = (J);                                                                      \
+      ls[IX][3] = s_; lj[IX][3] = j_;                                                                    \
+      _Pragma("unroll") for (int q_ = 3; q_ > 0; --q_) {                                                 \
+        if (ls[IX][q_] < ls[IX][q_ - 1]) {                                                               \
+          const float ts_ = ls[IX][q_]; ls[IX][q_] = ls[IX][q_ - 1]; ls[IX][q_ - 1] = ts_;               \
+          const int tj_ = lj[IX][q_]; lj[IX][q_] = lj[IX][q_ - 1]; lj[IX][q_ - 1] = tj_;                 \
+        }                                                                                                \
+      }                                                                                                  \
+    }                                                                                                    \
+  } while (0)
+
+__global__ __launch_bounds__(256, 2) void nn_candidate_kernel(const NnProb* __restrict__ probs, int np) {
+  __shared__ float Xs[NN_BK * NN_LD];
+  __shared__ float Ys[NN_BK * NN_LD];
+  __shared__ float Yn[2][NN_T];
+  const int bid = blockIdx.x;
+  int lo = 0, hi = np;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (probs[mid].item0 <= bid) lo = mid; else hi = mid;
+  }
+  const NnProb& P = probs[lo];
+  const int nx = P.nx, ny = P.ny, csplit = P.csplit, nk = P.d / NN_BK;
+  const int local = bid - P.item0, rb = local / csplit, sp = local - rb * csplit;
+  const int m0 = rb * NN_T;
+  const int tiles_total = (ny + NN_T - 1) / NN_T, t0 = sp * P.tiles_per;
+  const int ntl = min(tiles_total, t0 + P.tiles_per) - t0;             // >= 1: the host sizes csplit so that no split is empty
+  const float* __restrict__ x = P.x;
+  const float* __restrict__ y = P.y;
+  const float* __restrict__ ynf = P.ynf;
+  const int64_t ldx = P.ldx, ldy = P.ldy;
+
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int wy = wave >> 1, wx = wave & 1, li = lane & 31, lh = lane >> 5;
+
+  float ls[2][NN_K];
+  int lj[2][NN_K];
+#pragma unroll
+  for (int ix = 0; ix < 2; ++ix)
+#pragma unroll
+    for (int q = 0; q < NN_K; ++q) { ls[ix][q] = INFINITY; lj[ix][q] = -1; }
+
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+  float4 rx[4], ry[4];
+  float rn = INFINITY;
+  const int total = ntl * nk;
+  auto load_tile = [&](int step) {
+    const int tl = step / nk, kt = step - tl * nk, k = kt * NN_BK, c0 = (t0 + tl) * NN_T;
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+      const int f = t + 256 * it, row = f >> 3, kq = f & 7;
+      int xr = m0 + row; xr = xr < nx ? xr : nx - 1;
+      int yr = c0 + row; yr = yr < ny ? yr : ny - 1;
+      rx[it] = *(const float4*)(x + (int64_t)xr * ldx + k + 4 * kq);
+      ry[it] = *(const float4*)(y + (int64_t)yr * ldy + k + 4 * kq);
+    }
+    if (kt == 0 && t < NN_T) rn = c0 + t < ny ? ynf[c0 + t] : INFINITY;      // a column past the end scores +inf and is never kept
+  };
+  auto store_tile = [&](int step) {
+    const int tl = step / nk, kt = step - tl * nk;
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+      const int f = t + 256 * it, row = f >> 3, kq = f & 7;
+      float* a = Xs + (4 * kq) * NN_LD + row;
+      a[0] = rx[it].x; a[NN_LD] = rx[it].y; a[2 * NN_LD] = rx[it].z; a[3 * NN_LD] = rx[it].w;
+      float* b = Ys + (4 * kq) * NN_LD + row;
+      b[0] = ry[it].x; b[NN_LD] = ry[it].y; b[2 * NN_LD] = ry[it].z; b[3 * NN_LD] = ry[it].w;
+    }
+    if (kt == 0 && t < NN_T) Yn[tl & 1][t] = rn;
+  };
+
+  load_tile(0);
+  store_tile(0);
+  __syncthreads();
+  int step = 0;
+  for (int tl = 0; tl < ntl; ++tl) {
+    for (int kt = 0; kt < nk; ++kt, ++step) {
+      if (step + 1 < total) load_tile(step + 1);
+#pragma unroll
+      for (int s = 0; s < NN_BK / 2; ++s) {
+        const float* yp = Ys + (2 * s + lh) * NN_LD + wy * 64 + li;
+        const float* xp = Xs + (2 * s + lh) * NN_LD + wx * 64 + li;
+        const float y0 = yp[0], y1 = yp[32], x0 = xp[0], x1 = xp[32];
+        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(y0, x0, acc[0][0], 0, 0, 0);
+        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(y0, x1, acc[0][1], 0, 0, 0);
+        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(y1, x0, acc[1][0], 0, 0, 0);
+        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(y1, x1, acc[1][1], 0, 0, 0);
+      }
+      __syncthreads();
+      if (step + 1 < total) {
+        store_tile(step + 1);
+        __syncthreads();
+      }
+    }
+    // the tile's 64 x 64 block of this wave: accumulator row = data-base column, accumulator column (the lane) = query
+    const int c0 = (t0 + tl) * NN_T;
+    const float* yn = Yn[tl & 1];
+#pragma unroll
+    for (int iy = 0; iy < 2; ++iy)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int yl = wy * 64 + iy * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        const float ynv = yn[yl];
+        const float s0 = fmaf(-2.f, acc[iy][0][r], ynv), s1 = fmaf(-2.f, acc[iy][1][r], ynv);
+        NN_INSERT(0, s0, c0 + yl);
+        NN_INSERT(1, s1, c0 + yl);
+        acc[iy][0][r] = 0.f;
+        acc[iy][1][r] = 0.f;
+      }
+  }
+  const int nl = 4 * csplit, list = sp * 4 + wy * 2 + lh;
+#pragma unroll
+  for (int ix = 0; ix < 2; ++ix) {
+    const int row = m0 + wx * 64 + ix * 32 + li;
+    if (row < nx) {
+      const int64_t o = ((int64_t)row * nl + list) * NN_K;
+      *(float4*)(P.cs + o) = make_float4(ls[ix][0], ls[ix][1], ls[ix][2], ls[ix][3]);
+      *(int4*)(P.ci + o) = make_int4(lj[ix][0], lj[ix][1], lj[ix][2], lj[ix][3]);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- refine and certify
+// eps_i >= |s^ - s| for every column: u = 2^-24, gamma = d u / (1 - d u), B2 = max_j |y_j|^2 (rounded up),
+//   eps_i = 1.01 * (2 u B2 + 2 (gamma + u) sqrt(|x_i|^2 B2)) + 2^-40 (|x_i|^2 + B2)
+// the last term covers the float64 roundings of the exact distance and of the certificate itself.  Non-finite norms give NaN: never certified.
+__device__ __forceinline__ double nn_eps(double xn, double b2, int d) {
+  const double u = 5.9604644775390625e-08, g = d * u / (1.0 - d * u);
+  return 1.01 * (2.0 * u * b2 + 2.0 * (g + u) * sqrt(xn * b2)) + 9.094947017729282e-13 * (xn + b2);
+}
+
+__global__ __launch_bounds__(256) void nn_refine_kernel(const NnProb* __restrict__ probs) {
+  const NnProb& P = probs[blockIdx.y];
+  const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= P.nx) return;
+  float xv[NN_MAXT];
+  nn_load_row(xv, P.x + (int64_t)i * P.ldx, P.d, lane);
+  const double xn = P.xn[i];
+  const int nc = 4 * P.csplit * NN_K;
+  const float* __restrict__ cs = P.cs + (int64_t)i * nc;
+  const int32_t* __restrict__ ci = P.ci + (int64_t)i * nc;
+  // the two smallest approximate scores of the row, and T
+  float m1 = INFINITY, m2 = INFINITY, T = INFINITY;
+  for (int c0 = 0; c0 < nc; c0 += 64) {
+    const int c = c0 + lane;
+    const float s = c < nc ? cs[c] : INFINITY;
+    T = fminf(T, wave_min((c < nc && (c & (NN_K - 1)) == NN_K - 1) ? s : INFINITY));
+    const float a = wave_min(s);
+    const unsigned long long at = __ballot(s == a);
+    const int first = at ? __ffsll((long long)at) - 1 : 0;
+    const float b = wave_min(lane == first ? INFINITY : s);
+    m2 = fminf(fmaxf(m1, a), fminf(m2, b));
+    m1 = fminf(m1, a);
+  }
+  const double eps = nn_eps(xn, (double)__uint_as_float(*P.ymax_bits), P.d);
+  // a candidate whose approximate score exceeds the second smallest by more than 2 eps is strictly farther than two others: not evaluated
+  const bool dbg = P.debug != nullptr;
+  const double cut = dbg ? (double)INFINITY : (double)m2 + 2.0 * eps;
+  NnBest best;
+  nn_best_init(best);
+  double maxerr = 0.0;
+  float s_nn1 = __uint_as_float(0x7fc00000u);
+  for (int c0 = 0; c0 < nc; c0 += 64) {
+    const int c = c0 + lane;
+    const float s = c < nc ? cs[c] : INFINITY;
+    const int j = c < nc ? ci[c] : -1;
+    unsigned long long mask = __ballot(j >= 0 && (double)s <= cut);
+    while (mask) {
+      const int src = __ffsll((long long)mask) - 1;
+      mask &= mask - 1;
+      const int jj = __shfl(j, src, 64);
+      const double e = nn_exact_d2(xv, P.y + (int64_t)jj * P.ldy, P.d, lane);
+      const int before = best.i1;
+      nn_best_update(best, e, jj);
+      if (dbg) {
+        const float sj = __shfl(s, src, 64);
+        maxerr = fmax(maxerr, fabs((double)sj - (e - xn)));
+        if (best.i1 != before) s_nn1 = sj;
+      }
+    }
+  }
+  const bool certified = best.e2 < xn + (double)T - eps;
+  if (dbg && lane == 0) {
+    float* g = P.debug + 4 * (int64_t)i;
+    g[0] = f32_round_up(eps); g[1] = f32_round_up(maxerr); g[2] = s_nn1; g[3] = T;
+  }
+  if (lane == 0) {
+    if (certified) nn_best_write(P, i, best);
+    else P.fb_rows[atomicAdd(P.fb_count, 1)] = i;         // integer counter: the ORDER of the list varies, what is written per row does not
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- exhaustive fallback
+__global__ __launch_bounds__(256) void nn_exhaustive_kernel(const NnProb* __restrict__ probs) {
+  const NnProb& P = probs[blockIdx.y];
+  const int lane = threadIdx.x & 63, w = blockIdx.x * 4 + (threadIdx.x >> 6), nw = gridDim.x * 4;
+  const int cnt = P.forced ? P.nx : min(*P.fb_count, P.nx);
+  for (int r = w; r < cnt; r += nw) {
+    const int i = P.forced ? r : P.fb_rows[r];
+    float xv[NN_MAXT];
+    nn_load_row(xv, P.x + (int64_t)i * P.ldx, P.d, lane);
+    NnBest best;
+    nn_best_init(best);
+    for (int j = 0; j < P.ny; ++j) nn_best_update(best, nn_exact_d2(xv, P.y + (int64_t)j * P.ldy, P.d, lane), j);
+    if (lane == 0) nn_best_write(P, i, best);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- finish
+__global__ __launch_bounds__(256) void nn_finish_kernel(const NnPairDev* __restrict__ pairs) {
+  const NnPairDev& P = pairs[blockIdx.y];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i == 0) {
+    P.info[0] = P.forced ? P.n0 : *P.fb_count0;
+    P.info[1] = P.mutual ? (P.forced ? P.n1 : *P.fb_count1) : 0;
+    P.info[2] = 0; P.info[3] = 0;
+  }
+  if (i >= P.n0) return;
+  const float ratio = P.d1[i] / P.d2[i];
+  const int j = P.nn1[i];
+  bool m = ratio < P.threshold;
+  if (P.mutual) m = m && j >= 0 && P.cnn1[j] == i;
+  P.ratio[i] = ratio;
+  P.match[i] = m ? 1 : 0;
+  P.matches0[i] = m ? (int64_t)j : (int64_t)-1;
+  P.scores0[i] = m ? 1.f - ratio : 0.f;
+  if (m && P.mutual) P.matches1[j] = i;            // the mutual test makes j's partner unique
+}
+
+// ---------------------------------------------------------------------------------------------- host
+static inline size_t nn_al(size_t x) { return (x + 255) & ~(size_t)255; }
+
+static bool nn_pair_ok(const gims_nn_pair& p, int i, bool report) {
+  const char* why = nullptr;
+  if (p.d < 32 || p.d > 64 * NN_MAXT || p.d % 32 != 0) why = "d must be a multiple of 32 in [32, 512]";
+  else if (p.n0 < 1 || p.n1 < 2) why = "needs n0 >= 1 and n1 >= 2 (a second neighbour in B)";
+  else if (p.mutual && p.n0 < 2) why = "the mutual test needs n0 >= 2 (a second neighbour in A)";
+  else if (p.n0 > NN_MAX_N || p.n1 > NN_MAX_N) why = "more than 32768 rows";
+  else if (!p.a || !p.b || !p.nn1 || !p.nn2 || !p.d1 || !p.d2 || !p.ratio || !p.match || !p.matches0 || !p.scores0 || !p.info) why = "null pointer";
+  else if (p.mutual && !p.matches1) why = "null matches1 with mutual set";
+  else if (p.lda < p.d || p.ldb < p.d || p.lda % 4 != 0 || p.ldb % 4 != 0) why = "row pitch below d or not a multiple of 4";
+  else if (((uintptr_t)p.a | (uintptr_t)p.b) & 15) why = "a / b not 16-byte aligned";
+  if (why && report) set_error("gims_nn_match: pair %d (n0 = %d, n1 = %d, d = %d): %s", i, p.n0, p.n1, p.d, why);
+  return why == nullptr;
+}
+
+// Lays the workspace out (base may be null: sizes only).  Tables first, then the words that must start at zero, then per-pair arrays.
+static size_t nn_layout(const gims_nn_pair* pairs, int n_pairs, int flags, char* base, std::vector<NnProb>* probs, std::vector<NnPairDev>* pd,
+                        size_t* zero_off, size_t* zero_bytes, int* n_items) {
+  const bool forced = (flags & GIMS_NN_EXHAUSTIVE) != 0;
+  int np = 0;
+  int64_t rbs = 0;
+  for (int i = 0; i < n_pairs; ++i) {
+    np += pairs[i].mutual ? 2 : 1;
+    rbs += cdiv(pairs[i].n0, NN_T) + (pairs[i].mutual ? cdiv(pairs[i].n1, NN_T) : 0);
+  }
+  int want = (int)((NN_TARGET_WGS + rbs - 1) / rbs);
+  want = want < 1 ? 1 : (want > NN_MAX_SPLIT ? NN_MAX_SPLIT : want);
+  size_t off = nn_al(sizeof(NnProb) * (size_t)np) + nn_al(sizeof(NnPairDev) * (size_t)n_pairs);
+  *zero_off = off;
+  *zero_bytes = nn_al(16 * (size_t)n_pairs);
+  off += *zero_bytes;
+  int item = 0;
+  for (int i = 0; i < n_pairs; ++i) {
+    const gims_nn_pair& p = pairs[i];
+    uint32_t* z = (uint32_t*)(base + *zero_off) + 4 * (size_t)i;              // {amax bits, bmax bits, fb_count0, fb_count1}
+    NnPairDev D;
+    memset(&D, 0, sizeof(D));
+    D.a = p.a; D.b = p.b; D.lda = p.lda; D.ldb = p.ldb; D.n0 = p.n0; D.n1 = p.n1; D.d = p.d; D.mutual = p.mutual ? 1 : 0;
+    D.threshold = p.threshold; D.forced = forced;
+    D.an = (double*)(base + off); off += nn_al((size_t)p.n0 * 8);
+    D.bn = (double*)(base + off); off += nn_al((size_t)p.n1 * 8);
+    D.anf = (float*)(base + off); off += nn_al((size_t)p.n0 * 4);
+    D.bnf = (float*)(base + off); off += nn_al((size_t)p.n1 * 4);
+    D.amax = z; D.bmax = z + 1;
+    D.nn1 = p.nn1; D.d1 = p.d1; D.d2 = p.d2;
+    D.ratio = p.ratio; D.match = p.match; D.matches0 = p.matches0; D.scores0 = p.scores0; D.matches1 = p.matches1; D.info = p.info;
+    D.fb_count0 = (const int32_t*)(z + 2); D.fb_count1 = (const int32_t*)(z + 3);
+    for (int dir = 0; dir < (p.mutual ? 2 : 1); ++dir) {
+      NnProb Q;
+      memset(&Q, 0, sizeof(Q));
+      Q.x = dir ? p.b : p.a; Q.y = dir ? p.a : p.b; Q.ldx = dir ? p.ldb : p.lda; Q.ldy = dir ? p.lda : p.ldb;
+      Q.nx = dir ? p.n1 : p.n0; Q.ny = dir ? p.n0 : p.n1; Q.d = p.d;
+      const int tiles_total = cdiv(Q.ny, NN_T);
+      int cs = want < tiles_total ? want : tiles_total;
+      Q.tiles_per = cdiv(tiles_total, cs);
+      Q.csplit = cdiv(tiles_total, Q.tiles_per);                               // no empty split
+      Q.item0 = item; Q.forced = forced;
+      item += cdiv(Q.nx, NN_T) * Q.csplit;
+      Q.xn = dir ? D.bn : D.an; Q.ynf = dir ? D.anf : D.bnf; Q.ymax_bits = dir ? D.amax : D.bmax;
+      const size_t nc = (size_t)Q.nx * 4 * Q.csplit * NN_K;
+      if (!forced) {
+        Q.cs = (float*)(base + off); off += nn_al(nc * 4);
+        Q.ci = (int32_t*)(base + off); off += nn_al(nc * 4);
+      }
+      Q.fb_rows = (int32_t*)(base + off); off += nn_al((size_t)Q.nx * 4);
+      Q.fb_count = (int32_t*)(z + 2 + dir);
+      if (dir == 0) {
+        Q.nn1 = p.nn1; Q.nn2 = p.nn2; Q.d1 = p.d1; Q.d2 = p.d2; Q.debug = forced ? nullptr : p.debug;
+      } else {
+        Q.nn1 = p.cnn1 ? p.cnn1 : (int32_t*)(base + off);
+        if (!p.cnn1) off += nn_al((size_t)Q.nx * 4);
+        Q.nn2 = (int32_t*)(base + off); off += nn_al((size_t)Q.nx * 4);
+        Q.d1 = (float*)(base + off); off += nn_al((size_t)Q.nx * 4);
+        Q.d2 = (float*)(base + off); off += nn_al((size_t)Q.nx * 4);
+        D.cnn1 = Q.nn1;
+      }
+      if (probs) probs->push_back(Q);
+    }
+    if (pd) pd->push_back(D);
+  }
+  if (n_items) *n_items = item;
+  return off;
+}
+
+}  // namespace gims
+
+extern "C" size_t gims_nn_workspace_bytes(const gims_nn_pair* pairs, int32_t n_pairs, int32_t flags) {
+  using namespace gims;
+  if (!pairs || n_pairs <= 0 || (flags & ~GIMS_NN_EXHAUSTIVE)) return 0;
+  for (int i = 0; i < n_pairs; ++i)
+    if (!nn_pair_ok(pairs[i], i, false)) return 0;
+  size_t zo, zb;
+  return nn_layout(pairs, n_pairs, flags, nullptr, nullptr, nullptr, &zo, &zb, nullptr);
+}
+
+extern "C" int gims_nn_match(const gims_nn_pair* pairs, int32_t n_pairs, int32_t flags, void* work, size_t work_bytes, void* stream) {
+  using namespace gims;
+  GIMS_CHECK_ARG(pairs && n_pairs > 0, "gims_nn_match: null / empty pair array");
+  GIMS_CHECK_ARG((flags & ~GIMS_NN_EXHAUSTIVE) == 0, "gims_nn_match: unknown flag bits 0x%x", flags);
+  GIMS_CHECK_ARG((size_t)n_pairs * 2 * sizeof(NnProb) <= ((size_t)1 << 20), "gims_nn_match: %d pairs in one call (the descriptor table is limited to 1 MiB)", n_pairs);
+  for (int i = 0; i < n_pairs; ++i)
+    if (!nn_pair_ok(pairs[i], i, true)) return GIMS_EINVAL;
+  GIMS_CHECK_ARG(work && ((uintptr_t)work & 255) == 0, "gims_nn_match: null or misaligned workspace");
+  std::vector<NnProb> probs;
+  std::vector<NnPairDev> pd;
+  size_t zo = 0, zb = 0;
+  int n_items = 0;
+  const size_t need = nn_layout(pairs, n_pairs, flags, (char*)work, &probs, &pd, &zo, &zb, &n_items);
+  GIMS_CHECK_ARG(work_bytes >= need, "gims_nn_match: workspace too small (%zu bytes given, %zu needed)", work_bytes, need);
+  hipStream_t s = (hipStream_t)stream;
+  const int np = (int)probs.size();
+  NnProb* dprobs = (NnProb*)work;
+  NnPairDev* dpairs = (NnPairDev*)((char*)work + nn_al(sizeof(NnProb) * (size_t)np));
+  int rc = upload_table(probs.data(), sizeof(NnProb) * (size_t)np, dprobs, s);
+  if (rc != GIMS_OK) return rc;
+  rc = upload_table(pd.data(), sizeof(NnPairDev) * (size_t)n_pairs, dpairs, s);
+  if (rc != GIMS_OK) return rc;
+  GIMS_HIP(hipMemsetAsync((char*)work + zo, 0, zb, s));
+  int max_rows = 0, max_nx = 0, max_n0 = 0;
+  for (int i = 0; i < n_pairs; ++i) {
+    const int r = pairs[i].n0 + pairs[i].n1, m = pairs[i].mutual ? (pairs[i].n0 > pairs[i].n1 ? pairs[i].n0 : pairs[i].n1) : pairs[i].n0;
+    max_rows = r > max_rows ? r : max_rows;
+    max_nx = m > max_nx ? m : max_nx;
+    max_n0 = pairs[i].n0 > max_n0 ? pairs[i].n0 : max_n0;
+  }
+  const bool forced = (flags & GIMS_NN_EXHAUSTIVE) != 0;
+  hipLaunchKernelGGL(nn_norms_kernel, dim3(cdiv(max_rows, 4), n_pairs), dim3(256), 0, s, (const NnPairDev*)dpairs);
+  if (!forced) {
+    hipLaunchKernelGGL(nn_candidate_kernel, dim3(n_items), dim3(256), 0, s, (const NnProb*)dprobs, np);
+    hipLaunchKernelGGL(nn_refine_kernel, dim3(cdiv(max_nx, 4), np), dim3(256), 0, s, (const NnProb*)dprobs);
+  }
+  // the list of uncertified rows is only known on the device: a fixed grid of waves walks it (empty lists cost one load per wave)
+  const int gx = forced ? cdiv(max_nx, 4) : (cdiv(max_nx, 4) < 64 ? cdiv(max_nx, 4) : 64);
+  hipLaunchKernelGGL(nn_exhaustive_kernel, dim3(gx, np), dim3(256), 0, s, (const NnProb*)dprobs);
+  hipLaunchKernelGGL(nn_finish_kernel, dim3(cdiv(max_n0, 256), n_pairs), dim3(256), 0, s, (const NnPairDev*)dpairs);
+  GIMS_LAUNCH_CHECK();
+  return GIMS_OK;
+}

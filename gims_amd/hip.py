@@ -167,6 +167,14 @@ class LabelPair(C.Structure):
     _fields_ = [("kpts0", C.c_void_p), ("kpts1", C.c_void_p), ("n0", C.c_int32), ("n1", C.c_int32)]
 
 
+class NnPair(C.Structure):
+    _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("lda", C.c_int64), ("ldb", C.c_int64),
+                ("n0", C.c_int32), ("n1", C.c_int32), ("d", C.c_int32), ("mutual", C.c_int32), ("threshold", C.c_float), ("reserved", C.c_int32),
+                ("nn1", C.c_void_p), ("nn2", C.c_void_p), ("d1", C.c_void_p), ("d2", C.c_void_p), ("ratio", C.c_void_p), ("match", C.c_void_p),
+                ("matches0", C.c_void_p), ("scores0", C.c_void_p), ("cnn1", C.c_void_p), ("matches1", C.c_void_p), ("info", C.c_void_p),
+                ("debug", C.c_void_p)]
+
+
 _SIGNATURES = {
     "gims_abi_version": (C.c_int, []),
     "gims_last_error": (C.c_char_p, []),
@@ -304,6 +312,8 @@ _SIGNATURES = {
     "gims_adam_step": (C.c_int, [C.POINTER(AdamTensor), C.c_int32, C.POINTER(AdamGroup), C.c_int32, C.c_void_p]),
     "gims_ot_matrix": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
                                  C.c_void_p]),
+    "gims_nn_workspace_bytes": (C.c_size_t, [C.POINTER(NnPair), C.c_int32, C.c_int32]),
+    "gims_nn_match": (C.c_int, [C.POINTER(NnPair), C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -946,6 +956,49 @@ def eval_pairs(items, dist_thresh=3.0, n_iters=3, ransac_thresh=3.0, ransac_iter
     _check(lib.gims_eval_pairs(arr, len(items), float(dist_thresh), int(n_iters), float(ransac_thresh), int(ransac_iters),
                                int(seed) & 0xFFFFFFFFFFFFFFFF, _p(work), work.numel() * work.element_size(), _stream()),
            "gims_eval_pairs")
+    return work
+
+
+# ------------------------------------------------------------------------------------------------ descriptor baselines
+NN_EXHAUSTIVE = 1            # gims_nn_match flag: every row through the exhaustive float64 path
+NN_OUTPUTS = (("nn1", torch.int32), ("nn2", torch.int32), ("d1", torch.float32), ("d2", torch.float32), ("ratio", torch.float32),
+              ("match", torch.uint8), ("matches0", torch.int64), ("scores0", torch.float32))
+
+
+def nn_match(items, flags: int = 0, work=None):
+    """items: list of dicts with device tensors a [n0, d] / b [n1, d] (float32, rows contiguous), `mutual` (bool), `threshold`, and the output
+    tensors of include/gims_hip.h's gims_nn_pair: nn1, nn2 (int32), d1, d2, ratio (float32), match (uint8), matches0 (int64), scores0 (float32),
+    all [n0]; info int32 [4]; with `mutual` also matches1 int64 [n1] and optionally cnn1 int32 [n1]; optionally debug float32 [n0, 4].
+    One batched asynchronous call; returns the workspace (keep it alive until the stream has passed the call)."""
+    lib = load()
+    arr = (NnPair * len(items))()
+    for i, it in enumerate(items):
+        a, b = it["a"], it["b"]
+        if a.dtype != torch.float32 or b.dtype != torch.float32 or a.dim() != 2 or b.dim() != 2 or a.stride(1) != 1 or b.stride(1) != 1:
+            raise GimsHipError("nn_match: a / b must be float32 [n, d] with contiguous rows")
+        n0, n1 = int(a.shape[0]), int(b.shape[0])
+        for name, dt in NN_OUTPUTS:
+            if it[name].dtype != dt or it[name].numel() < n0 or not it[name].is_contiguous():
+                raise GimsHipError(f"nn_match: output {name} must be a contiguous {dt} tensor of n0 elements")
+        mutual = bool(it.get("mutual", False))
+        if mutual and (it["matches1"].dtype != torch.int64 or it["matches1"].numel() < n1):
+            raise GimsHipError("nn_match: matches1 must be int64 [n1]")
+        if it.get("cnn1") is not None and (it["cnn1"].dtype != torch.int32 or it["cnn1"].numel() < n1):
+            raise GimsHipError("nn_match: cnn1 must be int32 [n1]")
+        if it["info"].dtype != torch.int32 or it["info"].numel() < 4:
+            raise GimsHipError("nn_match: info must be int32 [4]")
+        if it.get("debug") is not None and (it["debug"].dtype != torch.float32 or it["debug"].numel() < 4 * n0):
+            raise GimsHipError("nn_match: debug must be float32 [n0, 4]")
+        lda, ldb = (a.stride(0) if n0 > 1 else a.shape[1]), (b.stride(0) if n1 > 1 else b.shape[1])      # a single row has no meaningful stride
+        arr[i] = NnPair(_p(a), _p(b), lda, ldb, n0, n1, int(a.shape[1]), int(mutual), float(it.get("threshold", 0.8)), 0,
+                        *[_p(it[name]) for name, _ in NN_OUTPUTS], _p(it.get("cnn1")) if mutual else None,
+                        _p(it["matches1"]) if mutual else None, _p(it["info"]), _p(it.get("debug")))
+    need = int(lib.gims_nn_workspace_bytes(arr, len(items), int(flags)))
+    if need == 0:           # bad arguments: let the call itself name them
+        _check(lib.gims_nn_match(arr, len(items), int(flags), None, 0, _stream()), "gims_nn_match")
+    if work is None or work.numel() * work.element_size() < need:
+        work = torch.empty(need, dtype=torch.uint8, device=items[0]["a"].device)
+    _check(lib.gims_nn_match(arr, len(items), int(flags), _p(work), work.numel() * work.element_size(), _stream()), "gims_nn_match")
     return work
 
 

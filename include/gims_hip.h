@@ -825,6 +825,49 @@ size_t gims_train_labels_workspace_bytes(const gims_label_pair* h_pairs /* HOST 
 int gims_train_labels(const gims_label_pair* h_pairs /* HOST array */, int32_t n_pairs, const float* homographies, float dist_thresh,
                       int32_t n_iters, int64_t* rows, int64_t* total, void* work, size_t work_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Classical descriptor baselines (gims_amd/csrc/nn.hip): the nearest-neighbour distance ratio test and its
+ * mutual-nearest variant, batched over pairs, nothing of size n0 x n1 stored.
+ * replaces: calculate_nndr / calculate_mnn (eval_matches.py:13-67: torch.cdist + a full torch.sort of every row).
+ * Semantics (fixed; tests/nn_ref.py restates them in NumPy):
+ *   inputs   A [n0][d], B [n1][d] float32, finite, row pitches lda / ldb (elements, multiples of 4; pointers 16-byte aligned);
+ *            d a multiple of 32 in [32, 512] (128 and 256 are the tested ones); 1 <= n0, 2 <= n1, both <= 32768 = gims_agc_max_keypoints;
+ *            mutual != 0 also needs n0 >= 2 (the reference indexes a second neighbour of every row of B).
+ *   distance d(i,j) = sqrt(S(i,j)),  S(i,j) = sum_k (double(a_ik) - double(b_jk))^2  in float64, in this fixed order: 64 partial sums,
+ *            partial sum l takes k = l, l + 64, l + 128, ... ascending (square rounded, then added: no fused multiply-add); the 64
+ *            partial sums are then combined by a butterfly: v_l <- v_l + v_(l xor 32), then xor 16, 8, 4, 2, 1.  This is the EXACT
+ *            distance; every decision is taken on it.  Distances are ordered by S (the float64 square root is monotone in it).
+ *   per row i of A: nn1[i], nn2[i] = the nearest and second-nearest row of B by exact distance, an exact tie goes to the LOWEST index;
+ *            d1, d2 = those distances, sqrt in float64 then rounded to float32; ratio[i] = d1 / d2 in float32 (IEEE: 0/0 = NaN, which
+ *            is no match); match[i] = ratio[i] < threshold (threshold as float32).
+ *   mutual:  for each row j of B, cnn1[j] = its exact nearest row of A (lowest index on ties);  match[i] &= (cnn1[nn1[i]] == i).
+ *   derived: matches0[i] = match ? nn1[i] : -1;  scores0[i] = match ? 1 - ratio[i] : 0;  mutual only: matches1[j] = the i matched to j, or -1.
+ * How: an exact-f32 MFMA pass keeps, per row and per column slice, the 4 smallest approximate scores |b_j|^2 - 2 a_i.b_j in registers;
+ * one wave per row re-evaluates the candidates exactly and CERTIFIES the row against an a-priori bound of the approximation error
+ * (every column that is no candidate is then strictly farther than nn2); a row that cannot be certified is re-solved exactly against
+ * all of B inside the same call.  Results are bit-identical whichever way a row went, and from run to run (no float atomics).
+ * info[4] = {rows of A re-solved exhaustively, rows of B re-solved exhaustively (mutual only), 0, 0}.
+ * debug (may be NULL; [n0][4] float32, test hook of the candidate pass): {eps_i (the bound, rounded up), max over ALL candidates of row i
+ * of |approximate - exact score| (rounded up), the approximate score the candidate pass gave column nn1[i] (NaN if nn1[i] was no
+ * candidate), T_i = the smallest of the per-list largest kept scores}; rows re-solved exhaustively included (their candidates are
+ * still measured).  Not written under GIMS_NN_EXHAUSTIVE.
+ * flags: GIMS_NN_EXHAUSTIVE sends every row through the exhaustive float64 path (tests, A/B runs).
+ * `work`: scratch of gims_nn_workspace_bytes(pairs, n_pairs, flags) bytes, 256-byte aligned.  Asynchronous; no host synchronisation.
+ */
+typedef struct gims_nn_pair {
+  const float* a; const float* b; int64_t lda, ldb;
+  int32_t n0, n1, d, mutual;
+  float threshold; int32_t reserved;
+  int32_t* nn1; int32_t* nn2; float* d1; float* d2; float* ratio; uint8_t* match;   /* [n0] */
+  int64_t* matches0; float* scores0;                                                /* [n0] */
+  int32_t* cnn1; int64_t* matches1;                                                 /* [n1]; read only when mutual; cnn1 may be NULL */
+  int32_t* info;                                                                    /* [4] */
+  float* debug;                                                                     /* [n0][4] or NULL */
+} gims_nn_pair;
+#define GIMS_NN_EXHAUSTIVE 1
+size_t gims_nn_workspace_bytes(const gims_nn_pair* h_pairs /* HOST array */, int32_t n_pairs, int32_t flags);   /* 0 on bad arguments */
+int gims_nn_match(const gims_nn_pair* h_pairs /* HOST array */, int32_t n_pairs, int32_t flags, void* work, size_t work_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
