@@ -7,7 +7,11 @@ stubbed by tools/_ref_stubs, none of the four functions calls it -- and stores t
 portable generator ``gims_amd.synth`` in ``tests/golden/eval_*.npz``.  Nothing from the reference's source is written.  (utils/common.py as a whole needs
 torchvision / matplotlib, which are not installed: its two functions are compiled from the file by name.)
 
-    python tools/gen_golden_eval.py
+    python tools/gen_golden_eval.py [gt] [metrics] [ties]        (no argument: everything)
+
+``ties`` runs ``torch_find_matches`` on the lattice inputs of tests/eval_cases.py, where every nearest-neighbour decision is a tie between
+equidistant points: ``tests/golden/eval_tie_*.npz`` hold the reference's index arrays after 6 iterations and the number of matches after
+1, 2, 3 and 6 (it appends iteration after iteration, so the result of k iterations is a prefix).
 """
 import os
 import sys
@@ -43,7 +47,7 @@ compute_pixel_error, pose_auc = _reference_functions("/root/reference/utils/comm
 OUT = os.path.join(ROOT, "tests", "golden")
 
 
-def main():
+def gt_pairs():
     # ---- GT matching on homography pairs: (n, seed, noise px, dist_thresh, n_iters)
     for n, seed, noise, thr, iters in [(300, 3000, 0.5, 3, 3), (1024, 3001, 0.5, 3, 3), (700, 3002, 1.5, 3, 1), (512, 3003, 2.5, 3, 3),
                                        (2048, 3004, 0.7, 3, 3)]:
@@ -57,6 +61,9 @@ def main():
                             noise=np.float64(noise), ma0=ma0.numpy(), ma1=ma1.numpy(), miss0=mi0.numpy(), miss1=mi1.numpy(),
                             warped=warped.numpy())
         print(f"eval_gt n={n} seed={seed}: {len(ma0)} GT matches, {len(mi0)} / {len(mi1)} unmatched")
+
+
+def metrics():
     # ---- pixel error and AUC on seeded numbers
     r = np.random.default_rng(7)
     a, b = r.normal(size=(4, 2)).astype(np.float32) * 50, r.normal(size=(4, 2)).astype(np.float32) * 50
@@ -67,5 +74,28 @@ def main():
     print("eval_metrics written")
 
 
+def ties():
+    # ---- GT matching where only the first-minimum rule decides: index arrays and the builder's arguments, nothing else
+    from tests import eval_cases as C
+    for fname, (case, shift) in C.TIE_GOLDENS.items():
+        (kp0, kp1, _, _, H, _, _), args = C.lattice_case(case, shift)
+        runs = {it: torch_find_matches(torch.from_numpy(kp0), torch.from_numpy(kp1), torch.from_numpy(H), dist_thresh=3, n_iters=it)
+                for it in C.TIE_ITERS}
+        ma0, ma1, mi0, mi1 = [t.numpy() for t in runs[max(C.TIE_ITERS)]]
+        for it, r in runs.items():                              # k iterations = a prefix of more iterations
+            assert np.array_equal(r[0].numpy(), ma0[:len(r[0])]) and np.array_equal(r[1].numpy(), ma1[:len(r[1])])
+        np.savez_compressed(os.path.join(OUT, fname + ".npz"), ma0=ma0, ma1=ma1, miss0=mi0, miss1=mi1,
+                            iters=np.array(C.TIE_ITERS), n_after=np.array([len(runs[it][0]) for it in C.TIE_ITERS]),
+                            lattice=np.array([args[k] for k in ("nx", "ny", "spacing", "n0", "n1", "seed")]),
+                            shift=np.array(C.LATTICE_SHIFTS[shift]))
+        print(f"{fname}: {[len(runs[it][0]) for it in C.TIE_ITERS]} GT matches after {list(C.TIE_ITERS)} iterations")
+
+
+def main(what):
+    for name, fn in (("gt", gt_pairs), ("metrics", metrics), ("ties", ties)):
+        if not what or name in what:
+            fn()
+
+
 if __name__ == "__main__":
-    main()
+    main(sys.argv[1:])
