@@ -338,6 +338,15 @@ extern "C" int gims_run_ops(const gims_op* ops, int32_t n_ops, void* stream) {
       else if (x.fn == GIMS_AUX_KENC_FIRST)
         rc = gims_kenc_first((const float*)x.p[0], (const float*)x.p[1], (const int32_t*)x.p[2], (const float*)x.p[3], (const float*)x.p[4],
                              (int32_t)x.i[0], (float*)x.p[5], x.i[1], stream);
+      else if (x.fn == GIMS_AUX_SAGE_MEAN)
+        rc = gims_sage_mean((const float*)x.p[0], x.i[0], (const int32_t*)x.p[1], (const int32_t*)x.p[2], (int32_t)x.i[1], (int32_t)x.i[2],
+                            (float*)x.p[3], x.i[3], stream);
+      else if (x.fn == GIMS_AUX_KENC_FIRST_LINEAR)
+        rc = gims_kenc_first_linear((const float*)x.p[0], (const float*)x.p[1], (const int32_t*)x.p[2], (const float*)x.p[3], (const float*)x.p[4],
+                                    (int32_t)x.i[0], (float*)x.p[5], x.i[1], stream);
+      else if (x.fn == GIMS_AUX_LAYERNORM_ACT)
+        rc = gims_layernorm_act((const float*)x.p[0], x.i[0], x.i[1], (int32_t)x.i[2], (const float*)x.p[1], (const float*)x.p[2], x.f[0], (int32_t)x.i[3],
+                                (float*)x.p[3], x.i[4], (uint16_t*)x.p[4], (uint16_t*)x.p[5], x.i[5], stream);
       else
         GIMS_CHECK_ARG(false, "gims_run_ops: op %d: unknown auxiliary function %d", i, x.fn);
     } else {

@@ -17,7 +17,6 @@ so that every linear layer is ONE launch for the whole batch.
 """
 from __future__ import annotations
 
-import contextlib
 import math
 import os
 import time
@@ -30,6 +29,7 @@ import torch.nn as nn
 from . import hip
 
 BN_EPS = 1e-5
+LN_EPS = 1e-6          # the reference's LayerNorm (gmatcher.py:74-85)
 
 
 class _Node(nn.Module):
@@ -468,7 +468,7 @@ class GMatcher(nn.Module):
         """Record a (start, end) HIP-event pair around every stage on the stream the kernels are launched on;
         read them back with ``stage_times_ms()`` after a synchronize.  The GNN layers keep running through the replayed
         launch table (the production path): the library records an event after each of its launches
-        (gims_run_ops_timed).  ``stepwise=True`` launches the layers one by one from Python instead."""
+        (gims_run_ops_timed).  ``stepwise=True`` issues the encoder and layer tables launch by launch instead (_issue)."""
         self._timers = {} if on else None
         self._stepwise = bool(stepwise)
 
@@ -741,222 +741,25 @@ class GMatcher(nn.Module):
         if not images:
             self._last = dict(items=[], pairs=[], images=[], dropped=ctx.get("dropped", []), repeats=ctx.get("repeats", 0), outputs=[])
             return [], [], None
-        feat, kpts_all, score_all, seg = G["feat"], G["kpts_all"], G["score_all"], G["seg"]
-        indptr_all, indices_all, norm3, n_tot = G["indptr_all"], G["indices_all"], G["norm3"], G["n_tot"]
-        # ---- GraphSAGE over the merged CSR of all images (gmatcher.py:145-162, 268-269)
-        x3 = P["x3"]
-        enc = None
-        if (x3 and not P["ln"] and self._replays("encoder", n_tot)
-                and D % 32 == 0 and P["kenc_w1"].shape[0] % 32 == 0):
-            # the encoder stage as ONE replayed call (the stepwise code below is its definition and its cross-check)
-            enc = self._encoder_replay(P, feat, kpts_all, seg, indptr_all, indices_all, norm3, n_tot)
-        with (St("sage") if enc is None else contextlib.nullcontext()):
-            h = feat
-            if enc is not None:
-                h = enc[0]
-            elif x3:
-                # split-bf16 operands for the LDS-DMA GEMM: h and mean(h) as SPL32 planes (the producing GEMM writes the
-                # planes of the next layer's h itself; the aggregation reads h in f32)
-                # (intermediates live in the per-lane arena: nothing of them is handed to the caller, and a dozen allocator calls per
-                # call are host time the single-pair path feels; `sage` itself -- kept in _last for the intermediates tests -- stays fresh)
-                h_spl = hip.split_spl32(h, out=self._act("sage_hs0", n_tot, 2 * h.shape[1], torch.bfloat16))
-                for i, e in enumerate(P["sage"]):
-                    agg_spl = hip.sage_mean_split(h, indptr_all, indices_all, self._act("sage_agg", n_tot, 2 * h.shape[1], torch.bfloat16))
-                    last = i == len(P["sage"]) - 1
-                    h_next = (torch.empty((n_tot, e["n"]), dtype=torch.float32, device=dev) if last
-                              else self._act("sage_h%d" % (i & 1), n_tot, e["n"], torch.float32))
-                    h_spl_next = None if last else self._act("sage_hs%d" % ((i + 1) & 1), n_tot, 2 * e["n"], torch.bfloat16)
-                    self._lin(e, h_spl, a1=agg_spl, act=hip.ACT_NONE if last else hip.ACT_RELU, out=h_next, out_split=h_spl_next)
-                    h, h_spl = h_next, h_spl_next
-            else:
-                for i, e in enumerate(P["sage"]):
-                    agg = torch.empty_like(h)
-                    hip.sage_mean(h, indptr_all, indices_all, agg)
-                    h = self._lin(e, h, a1=agg, act=hip.ACT_RELU if i < 2 else hip.ACT_NONE)
-            sage = h
-        # ---- keypoint encoder (gmatcher.py:26-33, 87-97) ; desc = sage + kenc (gmatcher.py:270-271)
-        with (St("kenc") if enc is None else contextlib.nullcontext()):
-            ln = P["ln"]
-            if enc is None:
-                x = self._act("kenc_x", n_tot, P["kenc_w1"].shape[0], torch.float32)
-                hip.kenc_first(kpts_all, norm3, seg, P["kenc_w1"], P["kenc_b1"], x, relu=not ln)
-                if ln:      # use_layernorm=True: conv -> LayerNorm -> ReLU (gmatcher.py:17-23), the norm as its own kernel
-                    hip.layernorm_act(x, *P["kenc_ln"][0], out=x)
-            dpl = self._act("dpl", n_tot, 2 * D, torch.bfloat16) if x3 else None     # split-bf16 (SPL32) copy of the residual stream
-            if enc is not None:
-                x = enc[1]
-            elif x3 and not ln:
-                xs = hip.split_spl32(x, out=self._act("kenc_xs0", n_tot, 2 * x.shape[1], torch.bfloat16))      # the hidden activations only ever exist as SPL32 planes
-                for i, e in enumerate(P["kenc"]):
-                    last = i == len(P["kenc"]) - 1
-                    if last:
-                        x = self._act("desc", n_tot, e["n"], torch.float32)
-                        self._lin(e, xs, residual=sage, out=x, out_split=dpl)
-                    else:
-                        nxt = self._act("kenc_xs%d" % ((i + 1) & 1), n_tot, 2 * e["n"], torch.bfloat16)
-                        self._lin(e, xs, act=hip.ACT_RELU, out_split=nxt)
-                        xs = nxt
-            else:
-                for i, e in enumerate(P["kenc"]):
-                    last = i == len(P["kenc"]) - 1
-                    x = self._lin(e, x, act=hip.ACT_NONE if (last or ln) else hip.ACT_RELU, residual=sage if last else None,
-                                  out=torch.empty((n_tot, e["n"]), dtype=torch.float32, device=dev),
-                                  out_split=dpl if (last and x3) else None)
-                    if ln and not last:
-                        hip.layernorm_act(x, *P["kenc_ln"][i + 1], out=x)
-            desc = x
+        feat, kpts_all, score_all, n_tot = G["feat"], G["kpts_all"], G["score_all"], G["n_tot"]
+        # ---- GraphSAGE over the merged CSR of all images (gmatcher.py:145-162, 268-269) and keypoint encoder (gmatcher.py:26-33, 87-97);
+        #      desc = sage + kenc (gmatcher.py:270-271)
+        sage, desc = self._encoder(P, G)
         # ---- attentional GNN (gmatcher.py:99-143): per layer QKV -> flash attention -> merge -> MLP -> residual
         pairs = [(images[2 * p]["rows"], images[2 * p + 1]["rows"]) for p in range(len(images) // 2)]
         # problem tables travel as kernel arguments (hip.upload): a pageable torch.tensor(..., device=) would block this
         # thread until the stream drains and stop the host from running ahead of the GPU
-        # (problem tables and layer activations live in per-lane arenas: stable addresses let the launch sequence be replayed)
+        # (problem tables and layer activations live in per-lane arenas: stable addresses let the launch tables be cached)
         spr = np.asarray([[o, n, o, n] for pr in pairs for (o, n) in pr], dtype=np.int32)
         cpr = np.asarray([q for (o0, n0), (o1, n1) in pairs for q in ((o0, n0, o1, n1), (o1, n1, o0, n0))], dtype=np.int32)
         # (ONE upload for both tables: a launch and ~15 us of host time less per call on the single-pair path)
         both = hip.upload(np.concatenate([spr, cpr]), dev, out=self._buf("attn_pr", spr.nbytes + cpr.nbytes + 32))
-        self_pr, cross_pr = both[:spr.shape[0]], both[spr.shape[0]:]
-        max_nq = max(g["n_kept"] for g in images)
-        if cfg['attention_precision'] not in ('auto', 'bf16', 'f16', 'bf16x3'):
-            raise ValueError("attention_precision must be 'auto', 'bf16', 'f16' or 'bf16x3'")
-        if cfg['attention_precision'] in ('f16', 'bf16x3') and not x3:
-            raise ValueError(f"attention_precision='{cfg['attention_precision']}' needs linear_precision='bf16x3' (the 3-pass Q/K/V projection)")
-        # per-layer choice of the attention kernel family (0 bf16, 1 half, 2 split-bf16) and, in 'auto' mode, the accumulator its
-        # statistic goes to
-        amode, stat = self._attention_modes(P, dev)
-        st_calibrated = bool(self.__dict__.get("_attn_auto", {}).get("calibrated"))
-        ax3 = [a == 2 for a in amode]
-        # bf16 / half attention: Q|K|V as one 16-bit buffer [rows][768] (a layer writes and reads it in its own format); x3 attention:
-        # the same three matrices as SPL32 hi/lo planes
-        qkv_b = self._act("qkv", n_tot, 3 * D, torch.bfloat16) if not all(ax3) else None
-        qkv_s = self._act("qkv6", n_tot, 6 * D, torch.bfloat16) if any(ax3) else None
-        qkv_of = lambda l: qkv_s if ax3[l] else qkv_b                                                       # noqa: E731
-        # the half tier rounds the THREE-pass projection (f32 class) to half in the epilogue; the bf16 tier multiplies hi planes only
-        # (a settled split-bf16 layer is the top tier: nothing left to decide, nothing measured; a half layer's operand range is reported by
-        # its projection's epilogue -- range_stat -- instead of a scan of the Q | K | V buffer, 25 us per layer at 2 x 4096 x 8)
-        stat_of = lambda l: None if (stat is None or (st_calibrated and amode[l] == 2)) else stat[l]       # noqa: E731
-        qkv_out_of = lambda l: (dict(out_split=qkv_s) if amode[l] == 2 else                                 # noqa: E731
-                                dict(out_bf16=qkv_b, flags=hip.LINEAR_OUT_F16, range_stat=None if stat_of(l) is None else stat[l][self._heads])
-                                if amode[l] == 1 else dict(out_bf16=qkv_b, flags=self._qkv_flags))
-        # the device-side verdict of 'auto' (see default_config): the guard of layer l's redo launches, None for a layer that needs none
-        # (match_pairs returns without a host synchronisation: its verdict is drawn on the device, by guarded launches; forward() ends in one and
-        # repeats the batch itself when the statistic it reads back there moved a layer up -- no extra launches on the latency path)
-        guarded = stat is not None and cfg['attention_precision'] == 'auto' and st_calibrated and self.__dict__.get("_device_guards", False)
-        if guarded and qkv_s is None:
-            qkv_s = self._act("qkv6", n_tot, 6 * D, torch.bfloat16)
-
-        def guard_of(l):
-            if not guarded or amode[l] == 2:
-                return None
-            if amode[l] == 0:
-                return hip.attn_guard(stat[l], hip.GUARD_PEAKED, self._heads, mean_thr=cfg['attention_auto_threshold'], tail_thr=cfg['attention_auto_tail'],
-                                      max_thr=cfg['attention_auto_rowmax'])
-            return hip.attn_guard(stat[l], hip.GUARD_RANGE, self._heads, range_limit=cfg['attention_f16_range'])
-        sfx = lambda l: ("", "_f16", "_x3")[amode[l]]      # stage-timer labels tell the attention kernels apart       # noqa: E731
-        if x3:
-            # all GEMM operands travel as split-bf16 SPL32 buffers written by the producing kernel's epilogue; only the
-            # residual stream `desc` also exists in f32
-            mpl, gpl, hpl = (self._act("mpl", n_tot, 2 * D, torch.bfloat16), self._act("gpl", n_tot, 2 * D, torch.bfloat16),
-                             self._act("hpl", n_tot, 4 * D, torch.bfloat16))
-            hid_ln = None
-            replay = not ln and all(L["mlp0_fused"] is not None for L in P["layers"]) and self._replays("layers", n_tot)
-            if replay:
-                # the 72 launches of the 18 layers as ONE call into the library (gims_run_ops): their arguments depend only on
-                # the buffer addresses and the batch geometry, which repeat from call to call in steady state
-                key = (P["gen"], n_tot, max_nq, dpl.data_ptr(), mpl.data_ptr(), hpl.data_ptr(), desc.data_ptr(),
-                       0 if qkv_b is None else qkv_b.data_ptr(), 0 if qkv_s is None else qkv_s.data_ptr(),
-                       0 if stat is None else stat.data_ptr(),
-                       (float(cfg['attention_auto_threshold']), float(cfg['attention_auto_tail']), float(cfg['attention_f16_range']),
-                        float(cfg['attention_auto_rowmax'])) if guarded else None,
-                       self_pr.data_ptr(), cross_pr.data_ptr(), self_pr.shape[0], cross_pr.shape[0], self._qkv_flags, tuple(amode))
-                cache = self.__dict__.setdefault("_ops_cache", {})
-                ops = cache.get(key)
-                if ops is None:
-                    def la(e, a0, **kw):
-                        return hip.op_linear(hip.linear_args(a0, e["w"], w_lo=e["w_lo"], bias=e["b"], precision=e["prec"], spl=e["spl"], **kw))
-                    lst = []
-                    for l, L in enumerate(P["layers"]):
-                        lst.append(la(L["qkv"], dpl, **qkv_out_of(l)))
-                        lst.append(hip.op_attention(qkv_of(l), cross_pr if L["cross"] else self_pr, max_nq, self._heads, None, 0, D, 2 * D,
-                                                    out_split=mpl, q_prescaled=True, x3=ax3[l], f16=amode[l] == 1, stat=stat_of(l), no_range=amode[l] == 1))
-                        gd = guard_of(l)
-                        if gd is not None:      # the redo of this layer at split-bf16, launched always, executed only when the guard fires
-                            lst.append(la(L["qkv"], dpl, out_split=qkv_s, guard=gd))
-                            lst.append(hip.op_attention(qkv_s, cross_pr if L["cross"] else self_pr, max_nq, self._heads, None, 0, D, 2 * D,
-                                                        out_split=mpl, q_prescaled=True, x3=True, guard=gd))
-                        lst.append(la(L["mlp0_fused"], dpl, a1=mpl, act=hip.ACT_RELU, out_split=hpl))
-                        lst.append(la(L["mlp1"], hpl, residual=desc, out=desc, out_split=dpl))
-                    if len(cache) > 8:
-                        cache.clear()
-                    # table, HIP graph, uses, and references to every tensor whose address is baked into the table
-                    ops = cache[key] = [hip.make_ops(lst), None, 0, (P, dpl, mpl, hpl, desc, qkv_b, qkv_s, stat, self_pr, cross_pr),
-                                        [lab for l, L in enumerate(P["layers"])
-                                         for lab in (("qkv" + sfx(l), ("attn_cross" if L["cross"] else "attn_self") + sfx(l))
-                                                     + (("guard", "guard") if guard_of(l) is not None else ()) + ("mlp", "mlp"))]]
-                # first use: plain replay (first-use initialisation inside the library); from the second use on a non-default
-                # stream, if GIMS_OPS_GRAPH=1: ONE graph launch
-                ops[2] += 1
-                if ops[1] is None and ops[2] >= 2 and self._use_graph and torch.cuda.current_stream().cuda_stream != 0:
-                    ops[1] = hip.OpsGraph(ops[0])
-                if self._timers is not None:
-                    pool = hip.EventPool(len(ops[0]) + 1)
-                    hip.run_ops_timed(ops[0], pool)
-                    self._timers.setdefault("_ops", []).append((pool, ops[4]))
-                elif ops[1] is not None:
-                    ops[1].launch()
-                else:
-                    hip.run_ops(ops[0])
-            for l, L in (() if replay else enumerate(P["layers"])):
-                with St("qkv" + sfx(l)):
-                    self._lin(L["qkv"], dpl, **qkv_out_of(l))
-                with St(("attn_cross" if L["cross"] else "attn_self") + sfx(l)):
-                    hip.attention(qkv_of(l), cross_pr if L["cross"] else self_pr, max_nq, self._heads, None, 0, D, 2 * D, out_split=mpl,
-                                  q_prescaled=True, x3=ax3[l], f16=amode[l] == 1, stat=stat_of(l), no_range=amode[l] == 1)
-                gd = guard_of(l)
-                if gd is not None:
-                    with St("guard"):
-                        self._lin(L["qkv"], dpl, out_split=qkv_s, guard=gd)
-                        hip.attention(qkv_s, cross_pr if L["cross"] else self_pr, max_nq, self._heads, None, 0, D, 2 * D, out_split=mpl,
-                                      q_prescaled=True, x3=True, guard=gd)
-                with St("mlp"):
-                    if ln:        # LayerNorm between the two MLP convs: hidden activations in f32, normalised + split by the norm kernel
-                        if hid_ln is None:
-                            hid_ln = torch.empty((n_tot, 2 * D), dtype=torch.float32, device=dev)
-                        if L["mlp0_fused"] is not None:
-                            self._lin(L["mlp0_fused"], dpl, a1=mpl, out=hid_ln)
-                        else:
-                            self._lin(L["merge"], mpl, out_split=gpl)
-                            self._lin(L["mlp0"], dpl, a1=gpl, out=hid_ln)
-                        hip.layernorm_act(hid_ln, *L["ln"], out_split=hpl)
-                    elif L["mlp0_fused"] is not None:
-                        self._lin(L["mlp0_fused"], dpl, a1=mpl, act=hip.ACT_RELU, out_split=hpl)
-                    else:
-                        self._lin(L["merge"], mpl, out_split=gpl)
-                        self._lin(L["mlp0"], dpl, a1=gpl, act=hip.ACT_RELU, out_split=hpl)
-                    self._lin(L["mlp1"], hpl, residual=desc, out=desc, out_split=dpl)   # desc += delta (gmatcher.py:142)
-        else:
-            msg = torch.empty((n_tot, D), dtype=torch.float32, device=dev)
-            mrg = torch.empty((n_tot, D), dtype=torch.float32, device=dev)
-            hid = torch.empty((n_tot, 2 * D), dtype=torch.float32, device=dev)
-            for L in P["layers"]:
-                with St("qkv"):
-                    self._lin(L["qkv"], desc, out_bf16=qkv_b)
-                with St("attn_cross" if L["cross"] else "attn_self"):
-                    hip.attention(qkv_b, cross_pr if L["cross"] else self_pr, max_nq, self._heads, msg, 0, D, 2 * D, q_prescaled=True)
-                with St("mlp"):
-                    act0 = hip.ACT_NONE if ln else hip.ACT_RELU
-                    if L["mlp0_fused"] is not None:
-                        self._lin(L["mlp0_fused"], desc, a1=msg, act=act0, out=hid)
-                    else:
-                        self._lin(L["merge"], msg, out=mrg)
-                        self._lin(L["mlp0"], desc, a1=mrg, act=act0, out=hid)
-                    if ln:
-                        hip.layernorm_act(hid, *L["ln"], out=hid)
-                    self._lin(L["mlp1"], hid, residual=desc, out=desc)          # desc += delta  (gmatcher.py:142)
+        stat = self._layers(P, desc, n_tot, max(g["n_kept"] for g in images), both[:spr.shape[0]], both[spr.shape[0]:])
         if stat is not None:
             self._attention_stats_enqueue(stat)
         # ---- final projection, score matrix, Sinkhorn, selection (gmatcher.py:273-294)
         with St("final_scores"):
-            mdesc = self._lin(P["final"], dpl) if x3 else self._lin(P["final"], desc)
+            mdesc = self._lin(P["final"], self._act("dpl", n_tot, 2 * D, torch.bfloat16) if P["x3"] else desc)
             items, largs = [], []
             tot0, tot1 = sum(n0 for (_, n0), _ in pairs), sum(n1 for _, (_, n1) in pairs)
             m0_all = torch.empty(tot0, dtype=torch.int64, device=dev)
@@ -999,95 +802,244 @@ class GMatcher(nn.Module):
                           dropped=ctx.get("dropped", []), repeats=ctx.get("repeats", 0))
         return items, pairs, mdesc
 
-    def _encoder_replay(self, P, feat, kpts_all, seg, indptr_all, indices_all, norm3, n_tot):
-        """GraphSAGE + keypoint encoder (the stepwise code in _run_rest, default precision, no LayerNorm) as ONE call into the library: 15 launches
-        recorded as a table of gims_op structs that is CACHED -- every intermediate lives in the per-lane arena, so its address does not change
-        from call to call -- and PATCHED per call with what does change: the row count and the six pointers of the batch (kept descriptors, CSR,
-        keypoints, image index per row, normalisation constants).  Between a batch's one host synchronisation and its layers the device waits
-        for the host: a dozen crossings of the ABI with their argument marshalling were most of that wait.
-        Returns (sage, desc); dpl (the SPL32 copy of desc) is self._act('dpl')."""
-        D = self.config['descriptor_dim']
+    # ------------------------------------------------------------------ encoder and layer stages: launch tables
+    # Each stage's launches are spelled ONCE, by its builder (_encoder_ops, _layer_ops), as a list of (stage-timer label, gims_op); the list is
+    # cached as a gims_run_ops table and _issue runs it -- in one call into the library, or launch by launch as slices of the same table.
+    @staticmethod
+    def _lin_op(e, a0, **kw):
+        """Linear layer `e` of the weight pack applied to a0, as an op of a launch table."""
+        return hip.op_linear(hip.linear_args(a0, e["w"], w_lo=e["w_lo"], bias=e["b"], precision=e["prec"], spl=e["spl"], **kw))
+
+    @staticmethod
+    def _norm_args(x, a2b2, rows, out=None, out_split=None):
+        """hip.op_aux arguments of LayerNorm + ReLU over the channels of x[:rows] (use_layernorm=True: conv -> LayerNorm -> ReLU, gmatcher.py:17-23)."""
+        return (hip.AUX_LAYERNORM_ACT, [x, a2b2[0], a2b2[1], out, out_split, None if out_split is None else out_split.data_ptr() + 64],
+                [x.stride(0), rows, x.shape[1], hip.ACT_RELU, 0 if out is None else out.stride(0), 0 if out_split is None else out_split.stride(0)],
+                [LN_EPS])
+
+    @staticmethod
+    def _table(lst, keep, *extra):
+        """Cache entry of the launch sequence lst = [(label, gims_op)], a list: [0] the table, [1] its HIP graph (GIMS_OPS_GRAPH=1), [2] the number
+        of times it was issued in ONE call, [3] `keep`, references to every tensor whose address is baked into the table, [4] its labels, [5] the
+        maximal runs of equal consecutive labels as [label, start, count] (the stage brackets of launch-by-launch issue), then `extra`."""
+        runs = []
+        for k, (lab, _) in enumerate(lst):
+            if runs and runs[-1][0] == lab:
+                runs[-1][2] += 1
+            else:
+                runs.append([lab, k, 1])
+        return [hip.make_ops([o for _, o in lst]), None, 0, keep, [lab for lab, _ in lst], runs, *extra]
+
+    def _issue(self, part, ent, n_tot):
+        """Run the cached table `ent` of `part` ("encoder" | "layers").  Where _replays says so, in one call: gims_run_ops; for the layers
+        under stage timers gims_run_ops_timed (an event after every op), under GIMS_OPS_GRAPH=1 on a non-default stream ONE graph launch from
+        the second use on (the first initialises inside the library).  Otherwise launch by launch: one gims_run_ops call per run of equal
+        labels, inside that label's stage bracket -- the same ops in the same order, so the results are bit-equal by construction.  The
+        replayed encoder under stage timers is issued that way too (two brackets: an event after each of its ops -- and their creation -- sat
+        in the host-bound stretch behind the synchronisation and cost a timed 1024 x 32 step 3 %)."""
+        ops, labels, runs = ent[0], ent[4], ent[5]
+        if self._replays(part, n_tot) and (part == "layers" or self._timers is None):
+            ent[2] += 1
+            if (part == "layers" and ent[1] is None and ent[2] >= 2 and self._use_graph
+                    and torch.cuda.current_stream().cuda_stream != 0):        # (the encoder table is patched per call: never a graph)
+                ent[1] = hip.OpsGraph(ops)
+            if self._timers is not None:
+                pool = hip.EventPool(len(ops) + 1)
+                hip.run_ops_timed(ops, pool)
+                self._timers.setdefault("_ops", []).append((pool, labels))
+            elif ent[1] is not None:
+                ent[1].launch()
+            else:
+                hip.run_ops(ops)
+            return
+        for label, start, count in runs:
+            with GMatcher._Stage(self, label):
+                hip.run_ops(ops, start, count)
+
+    def _encoder(self, P, G):
+        """GraphSAGE + keypoint encoder of the batch gathered in G.  Every intermediate lives in the per-lane arena, so its address does not
+        change from call to call: the table is CACHED and PATCHED per call with what does change -- the row count and the six pointers of the
+        batch (kept descriptors, CSR, keypoints, image index per row, normalisation constants), at the slots the builder recorded.  Between a
+        batch's one host synchronisation and its layers the device waits for the host: on a cache hit no gims_op is built or copied
+        (DESIGN.md 4.5).  Returns (sage, desc); with linear_precision='bf16x3' dpl, the SPL32 copy of desc, is self._act('dpl')."""
+        D, n_tot = self.config['descriptor_dim'], G["n_tot"]
         bf, f32 = torch.bfloat16, torch.float32
-        c1 = P["kenc_w1"].shape[0]
+        x3, spl = P["x3"], P["x3"] and not P["ln"]            # spl: the keypoint encoder's hidden activations exist as SPL32 planes only
         A = lambda name, cols, dt: self._act(name, n_tot, cols, dt)                     # noqa: E731
-        dims = [D] + [e["n"] for e in P["sage"]]                                         # 256, 128, 128, 256
-        wmax = max(dims)                                                                 # (one width per arena buffer: the widest layer that uses it)
-        hs = [A("sage_hs0", 2 * wmax, bf), A("sage_hs1", 2 * wmax, bf)]
-        agg = A("sage_agg", 2 * wmax, bf)
-        hf = [A("sage_h0", wmax, f32), A("sage_h1", wmax, f32)]
-        sage = A("sage_out", dims[-1], f32)
-        kd = [c1] + [e["n"] for e in P["kenc"]]                                          # 32, 64, 128, 256, 256
-        xk = A("kenc_x", c1, f32)
-        xs = [A("kenc_xs0", 2 * max(kd), bf), A("kenc_xs1", 2 * max(kd), bf)]
-        desc, dpl = A("desc", kd[-1], f32), A("dpl", 2 * D, bf)
-        key = (P["gen"],) + tuple(t.data_ptr() for t in (hs[0], hs[1], agg, hf[0], hf[1], sage, xk, xs[0], xs[1], desc, dpl))
+        c1 = P["kenc_w1"].shape[0]
+        wmax = max([D] + [e["n"] for e in P["sage"]])                                    # (one width per arena buffer: the widest layer that uses it)
+        kmax = max([c1] + [e["n"] for e in P["kenc"]])
+        b = dict(hf0=A("sage_h0", wmax, f32), hf1=A("sage_h1", wmax, f32), sage=A("sage_out", P["sage"][-1]["n"], f32),
+                 agg=A("sage_agg", 2 * wmax, bf) if x3 else A("sage_agg", wmax, f32), xk=A("kenc_x", c1, f32), desc=A("desc", P["kenc"][-1]["n"], f32))
+        if x3:
+            b.update(hs0=A("sage_hs0", 2 * wmax, bf), hs1=A("sage_hs1", 2 * wmax, bf), dpl=A("dpl", 2 * D, bf))
+        if spl:
+            b.update(xs0=A("kenc_xs0", 2 * kmax, bf), xs1=A("kenc_xs1", 2 * kmax, bf))
+        else:
+            b.update(xf0=A("kenc_xf0", kmax, f32), xf1=A("kenc_xf1", kmax, f32))
+        batch = dict(n=n_tot, feat=G["feat"].data_ptr(), ldf=G["feat"].stride(0), indptr=G["indptr_all"].data_ptr(), indices=G["indices_all"].data_ptr(),
+                     kpts=G["kpts_all"].data_ptr(), norm3=G["norm3"].data_ptr(), seg=G["seg"].data_ptr())
+        key = (P["gen"],) + tuple(t.data_ptr() for t in b.values())
         cache = self.__dict__.setdefault("_enc_cache", {})
         ent = cache.get(key)
         if ent is None:
-            V = lambda t, cols: t[:, :cols]                                              # noqa: E731  (a view of the arena slice with the layer's width)
-            lst, labels = [], []
-
-            def la(e, a0, **kw):
-                return hip.op_linear(hip.linear_args(a0, e["w"], w_lo=e["w_lo"], bias=e["b"], precision=e["prec"], spl=e["spl"], **kw))
-            # GraphSAGE: h as SPL32 planes, then per layer mean(h) as planes and the GEMM on [h | mean(h)]
-            lst.append(hip.op_aux(hip.AUX_SPLIT_SPL32, [feat, hs[0]], [feat.stride(0), hs[0].stride(0), n_tot, dims[0]])); labels.append("sage")
-            h, hspl = feat, V(hs[0], 2 * dims[0])
-            mean_ops = []
-            for i, e in enumerate(P["sage"]):
-                last = i == len(P["sage"]) - 1
-                aggv = V(agg, 2 * dims[i])
-                mean_ops.append(len(lst))
-                lst.append(hip.op_aux(hip.AUX_SAGE_MEAN_SPLIT, [h, indptr_all, indices_all, aggv], [h.stride(0), n_tot, dims[i], agg.stride(0)])); labels.append("sage")
-                h_next = sage if last else V(hf[i & 1], dims[i + 1])
-                hs_next = None if last else V(hs[(i + 1) & 1], 2 * dims[i + 1])
-                lst.append(la(e, hspl, a1=aggv, act=hip.ACT_NONE if last else hip.ACT_RELU, out=h_next, out_split=hs_next)); labels.append("sage")
-                h, hspl = h_next, hs_next
-            # keypoint encoder: first layer on normalised coordinates, then the MLP on SPL32 planes; the last layer adds `sage` and writes desc + dpl
-            k_first = len(lst)
-            lst.append(hip.op_aux(hip.AUX_KENC_FIRST, [kpts_all, norm3, seg, P["kenc_w1"], P["kenc_b1"], xk], [c1, n_tot])); labels.append("kenc")
-            lst.append(hip.op_aux(hip.AUX_SPLIT_SPL32, [xk, xs[0]], [xk.stride(0), xs[0].stride(0), n_tot, c1])); labels.append("kenc")
-            cur = V(xs[0], 2 * c1)
-            for i, e in enumerate(P["kenc"]):
-                last = i == len(P["kenc"]) - 1
-                if last:
-                    lst.append(la(e, cur, residual=sage, out=desc, out_split=dpl))
-                else:
-                    nxt = V(xs[(i + 1) & 1], 2 * e["n"])
-                    lst.append(la(e, cur, act=hip.ACT_RELU, out_split=nxt))
-                    cur = nxt
-                labels.append("kenc")
             if len(cache) > 4:
                 cache.clear()
-            ent = cache[key] = dict(ops=hip.make_ops(lst), labels=labels, mean_ops=mean_ops, k_first=k_first, keep=(P, hs, agg, hf, sage, xk, xs, desc, dpl))
-        ops = ent["ops"]
-        # ---- per-call patches: row counts, and the pointers that belong to this batch
-        for o in ops:
-            if o.kind == 0:
-                o.u.lin.m = n_tot
-            elif o.u.aux.fn == hip.AUX_SPLIT_SPL32:
-                o.u.aux.i[2] = n_tot
+            lst, slots = self._encoder_ops(P, b, G["feat"], batch)
+            ent = cache[key] = self._table(lst, (P, b), slots)
+        ops = ent[0]
+        for k, field, j, what in ent[6]:
+            if j is None:
+                setattr(ops[k].u.lin, field, batch[what])
             else:
-                o.u.aux.i[1] = n_tot
-        ops[0].u.aux.p[0] = feat.data_ptr()
-        ops[0].u.aux.i[0] = feat.stride(0)
-        for j, k in enumerate(ent["mean_ops"]):
-            if j == 0:
-                ops[k].u.aux.p[0] = feat.data_ptr()
-                ops[k].u.aux.i[0] = feat.stride(0)
-            ops[k].u.aux.p[1] = indptr_all.data_ptr()
-            ops[k].u.aux.p[2] = indices_all.data_ptr()
-        kf = ops[ent["k_first"]].u.aux
-        kf.p[0], kf.p[1], kf.p[2] = kpts_all.data_ptr(), norm3.data_ptr(), seg.data_ptr()
-        if self._timers is not None:
-            # stage timers: ONE event pair per stage (an event after each of the 15 ops -- and their creation -- sat in the host-bound stretch behind
-            # the synchronisation and cost a timed 1024 x 32 step 3 %)
-            with GMatcher._Stage(self, "sage"):
-                hip.run_ops(ops, 0, ent["k_first"])
-            with GMatcher._Stage(self, "kenc"):
-                hip.run_ops(ops, ent["k_first"], len(ops) - ent["k_first"])
-        else:
-            hip.run_ops(ops)
-        return sage, desc
+                getattr(ops[k].u.aux, field)[j] = batch[what]
+        self._issue("encoder", ent, n_tot)
+        return b["sage"], b["desc"]
+
+    def _encoder_ops(self, P, b, feat, batch):
+        """The launches of GraphSAGE (label 'sage') and the keypoint encoder ('kenc') on the arena buffers b, for the configuration of pack P:
+        [(label, gims_op)], and the slots _encoder patches per call as (op, field, index | None, name in `batch`) -- an argument given here by its
+        name in `batch` is such a slot."""
+        x3, ln, spl = P["x3"], P["ln"], P["x3"] and not P["ln"]
+        lst, slots = [], []
+        V = lambda t, cols: t[:, :cols]                                              # noqa: E731  (a view of the arena buffer with the layer's width)
+
+        def aux(label, fn, ptrs, ints, floats=()):
+            for field, args in (("p", ptrs), ("i", ints)):
+                slots.extend((len(lst), field, j, a) for j, a in enumerate(args) if isinstance(a, str))
+            lst.append((label, hip.op_aux(fn, [batch[a] if isinstance(a, str) else a for a in ptrs],
+                                          [batch[a] if isinstance(a, str) else a for a in ints], floats)))
+
+        def lin(label, e, a0, **kw):
+            slots.append((len(lst), "m", None, "n"))
+            if a0 is feat:
+                slots.extend([(len(lst), "a0", None, "feat"), (len(lst), "lda0", None, "ldf")])
+            lst.append((label, self._lin_op(e, a0, **kw)))
+        # GraphSAGE, per layer mean(h) over the neighbours and the GEMM on [h | mean(h)].  bf16x3: both operands as SPL32 planes (the producing
+        # GEMM writes the planes of the next layer's h itself; the aggregation reads h in f32); f32: both in f32
+        dims = [feat.shape[1]] + [e["n"] for e in P["sage"]]                           # 256, 128, 128, 256
+        h, ldh, hop = "feat", "ldf", feat
+        if x3:
+            aux("sage", hip.AUX_SPLIT_SPL32, ["feat", b["hs0"]], ["ldf", b["hs0"].stride(0), "n", dims[0]])
+            hop = V(b["hs0"], 2 * dims[0])
+        for i, e in enumerate(P["sage"]):
+            last = i == len(P["sage"]) - 1
+            aggv = V(b["agg"], (2 if x3 else 1) * dims[i])
+            aux("sage", hip.AUX_SAGE_MEAN_SPLIT if x3 else hip.AUX_SAGE_MEAN, [h, "indptr", "indices", aggv], [ldh, "n", dims[i], aggv.stride(0)])
+            h = b["sage"] if last else V(b["hf%d" % (i & 1)], dims[i + 1])
+            hs = V(b["hs%d" % ((i + 1) & 1)], 2 * dims[i + 1]) if x3 and not last else None
+            lin("sage", e, hop, a1=aggv, act=hip.ACT_NONE if last else hip.ACT_RELU, out=h, out_split=hs)
+            ldh, hop = h.stride(0), hs if x3 else h
+        # keypoint encoder: first layer on normalised coordinates, then the MLP (LayerNorm variant: conv -> norm kernel -> ReLU); the last layer
+        # adds `sage` and writes desc (+ dpl)
+        c1, xk = b["xk"].shape[1], b["xk"]
+        aux("kenc", hip.AUX_KENC_FIRST_LINEAR if ln else hip.AUX_KENC_FIRST, ["kpts", "norm3", "seg", P["kenc_w1"], P["kenc_b1"], xk], [c1, "n"])
+        if ln:
+            aux("kenc", *self._norm_args(xk, P["kenc_ln"][0], "n", out=xk))
+        cur = xk
+        if spl:
+            aux("kenc", hip.AUX_SPLIT_SPL32, [xk, b["xs0"]], [xk.stride(0), b["xs0"].stride(0), "n", c1])
+            cur = V(b["xs0"], 2 * c1)
+        for i, e in enumerate(P["kenc"]):
+            if i == len(P["kenc"]) - 1:
+                lin("kenc", e, cur, residual=b["sage"], out=b["desc"], out_split=b.get("dpl"))
+            elif spl:
+                cur, prev = V(b["xs%d" % ((i + 1) & 1)], 2 * e["n"]), cur
+                lin("kenc", e, prev, act=hip.ACT_RELU, out_split=cur)
+            else:
+                cur, prev = V(b["xf%d" % (i & 1)], e["n"]), cur
+                lin("kenc", e, prev, act=hip.ACT_NONE if ln else hip.ACT_RELU, out=cur)
+                if ln:
+                    aux("kenc", *self._norm_args(cur, P["kenc_ln"][i + 1], "n", out=cur))
+        return lst, slots
+
+    def _layers(self, P, desc, n_tot, max_nq, self_pr, cross_pr):
+        """The 18 attentional layers on the residual stream desc (and its SPL32 copy self._act('dpl')): their launches depend only on the buffer
+        addresses, the batch geometry and the per-layer attention tiers, which repeat from call to call in steady state -- one cached table per
+        such key.  Returns the accumulator the attention statistic of this batch went to (None: nothing was measured)."""
+        cfg, D = self.config, self.config['descriptor_dim']
+        x3 = P["x3"]
+        if cfg['attention_precision'] not in ('auto', 'bf16', 'f16', 'bf16x3'):
+            raise ValueError("attention_precision must be 'auto', 'bf16', 'f16' or 'bf16x3'")
+        if cfg['attention_precision'] in ('f16', 'bf16x3') and not x3:
+            raise ValueError(f"attention_precision='{cfg['attention_precision']}' needs linear_precision='bf16x3' (the 3-pass Q/K/V projection)")
+        # per-layer choice of the attention kernel family (0 bf16, 1 half, 2 split-bf16) and, in 'auto' mode, the accumulator its
+        # statistic goes to
+        amode, stat = self._attention_modes(P, desc.device)
+        calibrated = bool(self.__dict__.get("_attn_auto", {}).get("calibrated"))
+        # the device-side verdict of 'auto' (see default_config): guarded redo launches behind every bf16 / half attention launch
+        # (match_pairs returns without a host synchronisation: its verdict is drawn on the device, by guarded launches; forward() ends in one and
+        # repeats the batch itself when the statistic it reads back there moved a layer up -- no extra launches on the latency path)
+        guarded = stat is not None and cfg['attention_precision'] == 'auto' and calibrated and self.__dict__.get("_device_guards", False)
+        bf, f32 = torch.bfloat16, torch.float32
+        A = lambda name, cols, dt: self._act(name, n_tot, cols, dt)                     # noqa: E731
+        # bf16x3: all GEMM operands travel as split-bf16 SPL32 buffers written by the producing kernel's epilogue; only the residual stream `desc`
+        # also exists in f32 (dpl: its SPL32 copy) -- and, with LayerNorm, the hidden activations in front of the norm kernel.  f32: all in f32.
+        # msg: attention output, mrg: merged message (fuse_merge=False), hid: MLP hidden layer as the second conv reads it
+        b = dict(desc=desc, src=A("dpl", 2 * D, bf) if x3 else desc, stat=stat, self_pr=self_pr, cross_pr=cross_pr,
+                 msg=A("mpl", 2 * D, bf) if x3 else A("msg", D, f32), mrg=A("gpl", 2 * D, bf) if x3 else A("mrg", D, f32),
+                 hid=A("hpl", 4 * D, bf) if x3 else A("hid", 2 * D, f32), hid_ln=A("hid_ln", 2 * D, f32) if (x3 and P["ln"]) else None,
+                 # bf16 / half attention: Q|K|V as one 16-bit buffer [rows][768] (a layer writes and reads it in its own format); x3 attention (and the
+                 # guarded redo): the same three matrices as SPL32 hi/lo planes
+                 qkv_b=A("qkv", 3 * D, bf) if not all(a == 2 for a in amode) else None,
+                 qkv_s=A("qkv6", 6 * D, bf) if (guarded or any(a == 2 for a in amode)) else None)
+        key = (P["gen"], n_tot, max_nq) + tuple(0 if t is None else t.data_ptr() for t in b.values()) + (
+            (float(cfg['attention_auto_threshold']), float(cfg['attention_auto_tail']), float(cfg['attention_f16_range']),
+             float(cfg['attention_auto_rowmax'])) if guarded else None,
+            self_pr.shape[0], cross_pr.shape[0], self._qkv_flags, tuple(amode))
+        cache = self.__dict__.setdefault("_ops_cache", {})
+        ent = cache.get(key)
+        if ent is None:
+            if len(cache) > 8:
+                cache.clear()
+            ent = cache[key] = self._table(self._layer_ops(P, b, n_tot, max_nq, amode, calibrated, guarded), (P, b))
+        self._issue("layers", ent, n_tot)
+        return stat
+
+    def _layer_ops(self, P, b, n_tot, max_nq, amode, calibrated, guarded):
+        """The launches of the attentional layers on the buffers b (see _layers) as [(label, gims_op)]: per layer the Q/K/V projection ('qkv'),
+        the attention ('attn_self' | 'attn_cross'; both with a suffix that names the tier), for a guarded layer the two redo launches ('guard'),
+        and the MLP with the residual update ('mlp': two launches, three with fuse_merge=False, one more with LayerNorm)."""
+        cfg, D, H = self.config, self.config['descriptor_dim'], self._heads
+        x3, ln, stat = P["x3"], P["ln"], b["stat"]
+        desc, src, msg, mrg, hid, qkv_b, qkv_s = b["desc"], b["src"], b["msg"], b["mrg"], b["hid"], b["qkv_b"], b["qkv_s"]
+        to = (lambda t: dict(out_split=t)) if x3 else (lambda t: dict(out=t))           # where a GEMM's result goes: SPL32 planes | f32
+        lst = []
+        for l, L in enumerate(P["layers"]):
+            pr = b["cross_pr"] if L["cross"] else b["self_pr"]
+            sfx = ("", "_f16", "_x3")[amode[l]]                  # stage-timer labels tell the attention kernels apart
+            # (a settled split-bf16 layer is the top tier: nothing left to decide, nothing measured)
+            st = None if (stat is None or (calibrated and amode[l] == 2)) else stat[l]
+            # the half tier rounds the THREE-pass projection (f32 class) to half in the epilogue -- which also reports the operand range
+            # (range_stat) instead of a scan of the Q | K | V buffer, 25 us per layer at 2 x 4096 x 8; the bf16 tier multiplies hi planes only
+            if amode[l] == 2:
+                qkv, qkv_out = qkv_s, dict(out_split=qkv_s)
+            elif amode[l] == 1:
+                qkv, qkv_out = qkv_b, dict(out_bf16=qkv_b, flags=hip.LINEAR_OUT_F16, range_stat=None if st is None else stat[l][H])
+            else:
+                qkv, qkv_out = qkv_b, (dict(out_bf16=qkv_b, flags=self._qkv_flags) if x3 else dict(out_bf16=qkv_b))
+            lst.append(("qkv" + sfx, self._lin_op(L["qkv"], src, **qkv_out)))
+            lst.append((("attn_cross" if L["cross"] else "attn_self") + sfx,
+                        hip.op_attention(qkv, pr, max_nq, H, None if x3 else msg, 0, D, 2 * D, out_split=msg if x3 else None, q_prescaled=True,
+                                         x3=amode[l] == 2, f16=amode[l] == 1, stat=st, no_range=amode[l] == 1)))
+            if guarded and amode[l] != 2:      # the redo of this layer at split-bf16, launched always, executed only when the guard fires
+                gd = (hip.attn_guard(stat[l], hip.GUARD_PEAKED, H, mean_thr=cfg['attention_auto_threshold'], tail_thr=cfg['attention_auto_tail'],
+                                     max_thr=cfg['attention_auto_rowmax']) if amode[l] == 0
+                      else hip.attn_guard(stat[l], hip.GUARD_RANGE, H, range_limit=cfg['attention_f16_range']))
+                lst.append(("guard", self._lin_op(L["qkv"], src, out_split=qkv_s, guard=gd)))
+                lst.append(("guard", hip.op_attention(qkv_s, pr, max_nq, H, None, 0, D, 2 * D, out_split=msg, q_prescaled=True, x3=True, guard=gd)))
+            m, e0 = msg, L["mlp0_fused"]
+            if e0 is None:                     # fuse_merge=False: the reference's operation order
+                lst.append(("mlp", self._lin_op(L["merge"], msg, **to(mrg))))
+                m, e0 = mrg, L["mlp0"]
+            if ln:                             # LayerNorm between the two MLP convs: hidden activations in f32, normalised (+ split) by the norm kernel
+                hf = b["hid_ln"] if x3 else hid
+                lst.append(("mlp", self._lin_op(e0, src, a1=m, out=hf)))
+                lst.append(("mlp", hip.op_aux(*self._norm_args(hf, L["ln"], n_tot, **to(hid)))))
+            else:
+                lst.append(("mlp", self._lin_op(e0, src, a1=m, act=hip.ACT_RELU, **to(hid))))
+            lst.append(("mlp", self._lin_op(L["mlp1"], hid, residual=desc, out=desc, **(dict(out_split=src) if x3 else {}))))   # desc += delta (gmatcher.py:142)
+        return lst
 
     def _ingest(self, raw):
         """raw: list of (kp (N,2), desc (D,N) channel-major, scores (N,), image shape).  ONE launch transposes the whole

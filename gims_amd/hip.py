@@ -61,11 +61,12 @@ class AttnArgs(C.Structure):
 
 
 class AuxArgs(C.Structure):
-    """gims_aux_args: one of the small encoder-stage kernels as an op of gims_run_ops (fn = AUX_*; p / i in the entry point's argument order)."""
-    _fields_ = [("fn", C.c_int32), ("reserved", C.c_int32), ("p", C.c_void_p * 6), ("i", C.c_int64 * 4)]
+    """gims_aux_args: one of the small kernels as an op of gims_run_ops (fn = AUX_*; p / i / f: the entry point's pointer, integer and
+    floating-point arguments, each in declaration order)."""
+    _fields_ = [("fn", C.c_int32), ("reserved", C.c_int32), ("p", C.c_void_p * 6), ("i", C.c_int64 * 6), ("f", C.c_float * 2)]
 
 
-AUX_SPLIT_SPL32, AUX_SAGE_MEAN_SPLIT, AUX_KENC_FIRST = 0, 1, 2
+AUX_SPLIT_SPL32, AUX_SAGE_MEAN_SPLIT, AUX_KENC_FIRST, AUX_SAGE_MEAN, AUX_KENC_FIRST_LINEAR, AUX_LAYERNORM_ACT = range(6)
 
 
 class _OpU(C.Union):
@@ -537,6 +538,9 @@ def _attn_flags(q_prescaled, x3, f16, no_range=False):
 
 def op_attention(qkv, problems, max_n_q, n_heads, out=None, q_col=0, k_col=256, v_col=512, out_split=None, q_prescaled=False, x3=False,
                  stat=None, f16=False, guard=None, no_range=False) -> Op:
+    assert qkv.dtype == torch.bfloat16 and problems.dtype == torch.int32 and problems.is_cuda
+    if stat is not None:
+        assert stat.dtype == torch.int64 and stat.is_contiguous() and stat.numel() >= 4 * (n_heads + 1) and stat.is_cuda
     o = Op()
     o.kind = 1
     o.u.att = AttnArgs(_p(qkv), qkv.stride(0), q_col, k_col, v_col, _p(problems), problems.shape[0], max_n_q, n_heads, _p(out),
@@ -546,8 +550,9 @@ def op_attention(qkv, problems, max_n_q, n_heads, out=None, q_col=0, k_col=256, 
     return o
 
 
-def op_aux(fn: int, ptrs, ints) -> Op:
-    """One small encoder-stage kernel as an op (include/gims_hip.h GIMS_OP_AUX): ptrs = tensors or raw addresses (None -> NULL), ints = integers."""
+def op_aux(fn: int, ptrs, ints, floats=()) -> Op:
+    """One small kernel as an op (include/gims_hip.h GIMS_OP_AUX): ptrs = tensors or raw addresses (None -> NULL), ints = integers,
+    floats = the entry point's floating-point arguments."""
     o = Op()
     o.kind = 2
     o.u.aux.fn = int(fn)
@@ -555,6 +560,8 @@ def op_aux(fn: int, ptrs, ints) -> Op:
         o.u.aux.p[k] = t if (t is None or isinstance(t, int)) else t.data_ptr()
     for k, v in enumerate(ints):
         o.u.aux.i[k] = int(v)
+    for k, v in enumerate(floats):
+        o.u.aux.f[k] = float(v)
     return o
 
 
@@ -663,20 +670,9 @@ def attention(qkv: torch.Tensor, problems: torch.Tensor, max_n_q: int, n_heads: 
     f16: the 16-bit values of qkv are IEEE half, not bf16 (GIMS_ATTN_F16; the tensor's dtype stays torch.bfloat16: raw storage).
     stat: int64 [n_heads + 1, 4] accumulator of the softmax peakedness and the operand range (gims_attention_stat; zero it before the
     first use)."""
-    lib = load()
-    assert qkv.dtype == torch.bfloat16 and problems.dtype == torch.int32 and problems.is_cuda
-    if stat is not None:
-        assert stat.dtype == torch.int64 and stat.is_contiguous() and stat.numel() >= 4 * (n_heads + 1) and stat.is_cuda
-    if guard is not None:       # guarded launch (x3 only): a no-op unless the guard's statistic asks for the redo
-        op = op_attention(qkv, problems, max_n_q, n_heads, out, q_col, k_col, v_col, out_split, q_prescaled, x3, stat, f16, guard, no_range)
-        _check(lib.gims_attention_ex(C.byref(op.u.att), _stream()), "gims_attention_ex")
-        return out if out is not None else out_split
-    _check(lib.gims_attention_stat(_p(qkv), qkv.stride(0), q_col, k_col, v_col, _p(problems), problems.shape[0],
-                                   max_n_q, n_heads, _p(out), out.stride(0) if out is not None else 0, _p(out_split),
-                                   (out_split.data_ptr() + 64) if out_split is not None else None,
-                                   out_split.stride(0) if out_split is not None else 0,
-                                   _attn_flags(q_prescaled, x3, f16, no_range), _p(stat), _stream()),
-           "gims_attention")
+    # (guard: an x3 launch that is a no-op unless the guard's statistic asks for the redo)
+    op = op_attention(qkv, problems, max_n_q, n_heads, out, q_col, k_col, v_col, out_split, q_prescaled, x3, stat, f16, guard, no_range)
+    _check(load().gims_attention_ex(C.byref(op.u.att), _stream()), "gims_attention_ex")
     return out if out is not None else out_split
 
 

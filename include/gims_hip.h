@@ -239,12 +239,21 @@ typedef struct gims_attn_args {
  * pointer and integer arguments in declaration order:
  *   GIMS_AUX_SPLIT_SPL32      gims_split_spl32     p = {src, dst}                              i = {lds, ldd, rows, k}
  *   GIMS_AUX_SAGE_MEAN_SPLIT  gims_sage_mean_split p = {h, indptr, indices, out_spl}           i = {ldh, n, c, ld_spl}
- *   GIMS_AUX_KENC_FIRST       gims_kenc_first      p = {kpts, norm3, seg_of_row, w1, b1, out}  i = {c1, n} */
+ *   GIMS_AUX_KENC_FIRST       gims_kenc_first      p = {kpts, norm3, seg_of_row, w1, b1, out}  i = {c1, n}
+ * and the small kernels of the linear_precision='f32' and use_layernorm=True variants of both stages:
+ *   GIMS_AUX_SAGE_MEAN          gims_sage_mean          p = {h, indptr, indices, out}               i = {ldh, n, c, ldo}
+ *   GIMS_AUX_KENC_FIRST_LINEAR  gims_kenc_first_linear  p, i as GIMS_AUX_KENC_FIRST
+ *   GIMS_AUX_LAYERNORM_ACT      gims_layernorm_act      p = {x, a2, b2, out, out_hi, out_lo}        i = {ldx, rows, c, act, ldo, ld_split}  f = {eps}
+ * f holds the floating-point arguments in declaration order (eps is a float in the entry point and travels as one: no conversion on the way).
+ * The struct grew from i[4] to i[6] + f[2] inside the union, whose size gims_linear_args sets: sizeof(gims_op) and every earlier offset are unchanged. */
 #define GIMS_OP_AUX 2
 #define GIMS_AUX_SPLIT_SPL32 0
 #define GIMS_AUX_SAGE_MEAN_SPLIT 1
 #define GIMS_AUX_KENC_FIRST 2
-typedef struct gims_aux_args { int32_t fn, reserved; const void* p[6]; int64_t i[4]; } gims_aux_args;
+#define GIMS_AUX_SAGE_MEAN 3
+#define GIMS_AUX_KENC_FIRST_LINEAR 4
+#define GIMS_AUX_LAYERNORM_ACT 5
+typedef struct gims_aux_args { int32_t fn, reserved; const void* p[6]; int64_t i[6]; float f[2]; } gims_aux_args;
 typedef struct gims_op { int32_t kind; int32_t reserved; union { gims_linear_args lin; gims_attn_args att; gims_aux_args aux; } u; } gims_op;
 int gims_run_ops(const gims_op* ops /* HOST */, int32_t n_ops, void* stream);
 /* The same replay with a HIP event recorded on `stream` before the first op and after every op: events is a HOST array of
