@@ -6,5 +6,6 @@ Kernels live in ``gims_amd/csrc`` (HIP, gfx950) behind the C ABI of ``include/gi
 from .gmatcher import GMatcher  # noqa: F401
 from .matching import Matching  # noqa: F401
 from .baselines import mnn, nn_match_pairs, nndr  # noqa: F401
+from .augment import ColorAug, ColorAugPlan  # noqa: F401
 
-__all__ = ["GMatcher", "Matching", "nndr", "mnn", "nn_match_pairs"]
+__all__ = ["GMatcher", "Matching", "nndr", "mnn", "nn_match_pairs", "ColorAug", "ColorAugPlan"]

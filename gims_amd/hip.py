@@ -176,6 +176,12 @@ class NnPair(C.Structure):
                 ("debug", C.c_void_p)]
 
 
+class AugPlan(C.Structure):
+    """gims_aug_plan (include/gims_hip.h): one image's colour augmentation."""
+    _fields_ = [("lut", C.c_uint8 * 256), ("kernel", C.c_float * 49), ("use_lut", C.c_int32), ("ksize", C.c_int32), ("sigma", C.c_float),
+                ("key", C.c_uint64)]
+
+
 _SIGNATURES = {
     "gims_abi_version": (C.c_int, []),
     "gims_last_error": (C.c_char_p, []),
@@ -315,6 +321,9 @@ _SIGNATURES = {
                                  C.c_void_p]),
     "gims_nn_workspace_bytes": (C.c_size_t, [C.POINTER(NnPair), C.c_int32, C.c_int32]),
     "gims_nn_match": (C.c_int, [C.POINTER(NnPair), C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gims_color_aug_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "gims_color_aug": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(AugPlan), C.c_void_p, C.c_void_p, C.c_size_t,
+                                 C.c_void_p]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -1627,6 +1636,27 @@ def resize(images: torch.Tensor, dsize, interpolation=INTER_LINEAR, out=None):
     assert res.shape == (B, dh, dw, c) and res.dtype == torch.uint8 and res.is_contiguous()
     _check(load().gims_resize(_p(t), B, H, W, c, _p(res), dh, dw, int(interpolation), _stream()), "gims_resize")
     return res if images.dim() == 4 else res.squeeze(-1)
+
+
+def color_aug(images: torch.Tensor, plans, out=None):
+    """gims_color_aug: every image of a device uint8 batch [n, h, w, c] (or [n, h, w]) under its own plan (a ctypes array of n AugPlan, or
+    a sequence of them) into a separate tensor of the same shape; one launch for the batch, asynchronous on the current stream.  The
+    library checks the arguments (channels, kernel sizes, blur with noise, out overlapping images) and raises GimsHipError."""
+    if not torch.is_tensor(images) or not images.is_cuda or images.dtype != torch.uint8 or images.dim() not in (3, 4):
+        raise ValueError("color_aug takes device uint8 [n, h, w, c] or [n, h, w] images")
+    t = images.contiguous()
+    n, h, w = t.shape[:3]
+    c = t.shape[3] if t.dim() == 4 else 1
+    if len(plans) != n:
+        raise ValueError(f"color_aug: {len(plans)} plans for {n} images")
+    arr = plans if isinstance(plans, C.Array) else (AugPlan * max(n, 1))(*plans)
+    res = out if out is not None else torch.empty_like(t)
+    assert res.shape == t.shape and res.dtype == torch.uint8 and res.is_cuda and res.is_contiguous()
+    lib = load()
+    need = int(lib.gims_color_aug_workspace_bytes(n))
+    work = torch.empty(max(need, 16), dtype=torch.uint8, device=t.device)
+    _check(lib.gims_color_aug(_p(t), n, h, w, c, arr, _p(res), _p(work), need, _stream()), "gims_color_aug")
+    return res
 
 
 def train_labels(kpts0, kpts1, homographies: torch.Tensor, dist_thresh=3.0, n_iters=1):

@@ -5,7 +5,9 @@ The reference builds every training batch from a COCO image (utils/dataset.py:40
 per pair into the ``match_indexes`` rows the loss reads.  Here the random draws stay NumPy (the same ``np.random`` call sequence,
 so a seeded run draws the reference's matrices), and every pixel and label is computed by HIP kernels: ``warp_perspective`` /
 ``resize`` (csrc/warp.hip, OpenCV 4.x's scalar arithmetic restated) and ``training_labels`` (csrc/eval.hip).  The pixels never
-reach the host.  Not restated: the albumentations colour augmentation (``apply_color_aug``) and image decoding (``cv2.imread``).
+reach the host.  The albumentations colour augmentation (``apply_color_aug``) is restated as this library's own specification
+(``augment.ColorAug``, csrc/augment.hip: documented behaviour, its own random draws, parity with albumentations itself unpinned) and is
+applied by ``training_pair(..., color_aug=ColorAug(...))``.  Not restated: image decoding (``cv2.imread``).
 """
 from __future__ import annotations
 
@@ -166,9 +168,12 @@ def _aug_homography(shape, aug):
                                aug['shear_angle'], aug['rotation_angle'], aug['scale'], aug['translation'])
 
 
-def training_pair(img, dataset_params, device=None):
-    """COCO_loader.__getitem__ (utils/dataset.py:40-66) from a decoded image, without the colour augmentation: (original, warped)
-    uint8 images of image_height x image_width on the device and the scaled homography (float32 NumPy 3x3)."""
+def training_pair(img, dataset_params, device=None, color_aug=None):
+    """COCO_loader.__getitem__ (utils/dataset.py:40-66) from a decoded image: (original, warped) uint8 images of image_height x
+    image_width on the device and the scaled homography (float32 NumPy 3x3).  color_aug: an ``augment.ColorAug``; after the resize it
+    draws a plan for the original, then one for the warped image (the reference's order, utils/dataset.py:37), and augments both in one
+    launch; the homography is untouched.  None (the default) augments nothing and draws nothing, whatever ``apply_color_aug`` in
+    dataset_params says."""
     cfg = dataset_params
     th, tw = cfg['image_height'], cfg['image_width']
     image = _one(img, device)
@@ -181,6 +186,9 @@ def training_pair(img, dataset_params, device=None):
     warped = warp_perspective(image, hm, (w, h))
     if resize_both:
         pair = resize(torch.stack([image, warped]), (tw, th), INTER_AREA)
+        image, warped = pair[0], pair[1]
+    if color_aug is not None:
+        pair = color_aug.apply(pair if resize_both else torch.stack([image, warped]), [color_aug.draw(), color_aug.draw()])
         image, warped = pair[0], pair[1]
     return image, warped, scale_homography(hm, h, w, th, tw).astype(np.float32)
 

@@ -877,6 +877,50 @@ typedef struct gims_nn_pair {
 size_t gims_nn_workspace_bytes(const gims_nn_pair* h_pairs /* HOST array */, int32_t n_pairs, int32_t flags);   /* 0 on bad arguments */
 int gims_nn_match(const gims_nn_pair* h_pairs /* HOST array */, int32_t n_pairs, int32_t flags, void* work, size_t work_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Colour augmentation of the training images (gims_amd/csrc/augment.hip): brightness / contrast, motion blur and
+ * Gaussian noise for a batch of uint8 [n][h][w][c] images, c = 1 or 3, into a SEPARATE output of the same shape, one augmentation launch
+ * for the batch (after the upload of the plans, below), every image under its own plan.
+ * replaces: the albumentations Compose of utils/dataset.py:23-29 (RandomBrightness / RandomContrast, MotionBlur / GaussNoise).  This is
+ * the build's OWN, fully specified restatement of the documented behaviour of those transforms (like the RANSAC above): neither
+ * albumentations nor OpenCV is available to pin it to, and their random streams could not be reproduced anyway.  tests/aug_ref.py
+ * restates the specification in NumPy; the device equals it bit for bit.
+ * A plan has up to three parts, applied in this order:
+ *   (a) LUT (use_lut != 0): p = lut[src].  Applied on the fly to every source pixel that (b) or (c) reads; alone, dst = lut[src].
+ *   (b) motion blur (ksize 3, 5 or 7; 0: none): cv2.filter2D(img, -1, K) restated.  K = kernel[0 .. ksize*ksize), row-major.
+ *       Correlation (K is not flipped), anchor at the centre r = ksize / 2:  out(y, x, ch) = sum over (i, j) of K[i][j] * p(Y(y + i - r),
+ *       X(x + j - r), ch) with the border BORDER_REFLECT_101 by OpenCV's borderInterpolate loop: for len == 1 the index is 0, otherwise
+ *       repeat { q = -q if q < 0;  q = 2 * (len - 1) - q if q >= len } until 0 <= q < len (an image narrower than r bounces several
+ *       times).  Arithmetic per pixel and channel: acc = 0.f, then acc = fmaf(K[i][j], (float)p, acc) for every tap with K[i][j] != 0
+ *       in row-major tap order (i outer, j inner); out = saturate_cast<uchar>(acc): round half to even, then clamp to [0, 255].
+ *   (c) Gaussian noise (sigma > 0; <= 0: none): v = fmaf(sigma, z, (float)p);  out = (uint8)trunc(min(max(v, 0), 255)) -- truncation,
+ *       what np.clip(...).astype(uint8) does.  Every channel of every pixel has its own z, from a counter-based generator (no state, the
+ *       same result under any launch geometry): e = (y * w + x) * c + ch, the element's index inside its image;
+ *         s0 = key ^ (e * 0x9E3779B97F4A7C15)  (uint64, wrapping);  s1 = splitmix64(s0), s2 = splitmix64(s1), s3 = splitmix64(s2) with
+ *         splitmix64(x): x += 0x9E3779B97F4A7C15; x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9; x = (x ^ (x >> 27)) * 0x94D049BB133111EB;
+ *         return x ^ (x >> 31)  (the function of the RANSAC sampler above, chained the same way);
+ *         S = the sum of the twelve 16-bit lanes of s1, s2, s3 (0 .. 786420);  z = (float)(S - 393210) / 65536.f.
+ *       Integer arithmetic and two exact float32 operations: z is the same on every machine.  Unit variance to 2e-10 (1 - 2^-32), excess
+ *       kurtosis -0.1, support +-6.
+ *   (b) and (c) never occur in one plan (the reference's OneOf picks one); a plan with none of the three copies the image.
+ * plans: HOST array of n plans, copied into `work` on the stream through kernel arguments (like gims_label_pair / gims_eval_pair tables):
+ *   one small upload launch per 8 plans ahead of the one augmentation launch.  A batch whose plans are all empty is one device copy.
+ * work: device scratch of gims_color_aug_workspace_bytes(n) bytes, 16-byte aligned.  Asynchronous; no host synchronisation.
+ * sigma: noise is on when sigma > 0; a NaN sigma therefore means no noise (the comparison is false), like any sigma <= 0.
+ * GIMS_EINVAL: c not 1 or 3, ksize not in {0, 3, 5, 7}, blur and noise in one plan, sigma = +infinity, dst overlapping src (the blur reads
+ * neighbours), h * w * c >= 2^31, n > 65535 (the batch is the grid's y dimension), a missing, misaligned or too small workspace.
+ * n == 0 is GIMS_OK and touches nothing. */
+typedef struct gims_aug_plan {
+  uint8_t lut[256];
+  float kernel[49];            /* ksize x ksize, row-major, in the first ksize * ksize entries */
+  int32_t use_lut, ksize;      /* ksize 0: no blur */
+  float sigma;                 /* <= 0: no noise */
+  uint64_t key;                /* noise key of this image (offset 464; the struct is 472 bytes with no padding) */
+} gims_aug_plan;
+size_t gims_color_aug_workspace_bytes(int32_t n);
+int gims_color_aug(const uint8_t* src, int32_t n, int32_t h, int32_t w, int32_t c, const gims_aug_plan* plans /* HOST array */, uint8_t* dst,
+                   void* work, size_t work_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
