@@ -1487,64 +1487,60 @@ __global__ __launch_bounds__(256) void agc_kept_deg_kernel(const AgcWs* __restri
   if (u >= w.info[0]) w.degk[u] = 0;
 }
 
-static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-
 // The scratch CSR of the pre-removal graph gets the capacity the caller gives the final one (gims_agc_image::max_edges_dir,
 // at least 64 directed edges per node): a caller that sees the overflow flag repeats the build with larger output buffers.
 constexpr int AGC_MIN_CAP_PER_NODE = 64;
 
-static size_t agc_layout(int n, int d, int max_edges_dir, bool with_s16, char* base, AgcWs* w) {
+// One image's part of the workspace (sizing: L on a null base, w a scratch record)
+static void agc_layout(int n, int d, int max_edges_dir, bool with_s16, WsLayout& L, AgcWs& w) {
   const int nw = (n + 63) / 64, lds16 = (n + 7) & ~7;
   const int cap = max_edges_dir > n * AGC_MIN_CAP_PER_NODE ? max_edges_dir : n * AGC_MIN_CAP_PER_NODE;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off += al256(bytes); return base ? base + o : (char*)nullptr; };
-  char* p;
   // descriptors: [n][d] f32 followed by [n][d] half
-  p = take((size_t)n * d * 6);
-  if (w) { w->dnf = (float*)p; w->dn16 = (uint16_t*)(p + (size_t)n * d * 4); }
+  char* dn = L.take<char>((size_t)n * d * 6);
+  w.dnf = (float*)dn;
+  w.dn16 = dn ? (uint16_t*)(dn + (size_t)n * d * 4) : nullptr;
   // approximate similarities in half [n][lds16] (robust flow only: the window flow never stores them), the radius candidates and their keys, and the
   // band list (one u32 per pair of the strict upper triangle at most)
   const size_t list_cap = (size_t)n * (n - 1) / 2 + 64;
-  const size_t s16_bytes = with_s16 ? al256((size_t)n * lds16 * 2) : 0, cl_bytes = al256((size_t)cap * 4);
-  p = take(s16_bytes + 2 * cl_bytes + list_cap * 4);
-  if (w) {
-    w->S16 = with_s16 ? (uint16_t*)p : nullptr;
-    w->clist = (uint32_t*)(p + s16_bytes);
-    w->ckey = (uint32_t*)(p + s16_bytes + cl_bytes);
-    w->list = (uint32_t*)(p + s16_bytes + 2 * cl_bytes);
-    w->list_cap = (uint32_t)list_cap;
-    w->clist_cap = (uint32_t)cap;
-    w->lds16 = lds16;
-  }
-  p = take((size_t)(AGC_NB + 1) * 4); if (w) w->cellptr = (int32_t*)p;
-  p = take((size_t)n * 4); if (w) w->cellidx = (int32_t*)p;
-  p = take((size_t)n * nw * 8); if (w) w->bits = (uint64_t*)p;
-  p = take(4096 * 4); if (w) w->hist = (uint32_t*)p;
-  p = take(16); if (w) w->sel = (uint32_t*)p;
-  p = take(16); if (w) w->band = (uint32_t*)p;
-  p = take((size_t)n * 4); if (w) w->deg = (int32_t*)p;
-  p = take((size_t)n * 4); if (w) w->nn = (int32_t*)p;
-  p = take((size_t)n * 4); if (w) w->label = (int32_t*)p;
-  p = take((size_t)n * 4); if (w) w->alive = (int32_t*)p;
-  p = take((size_t)n * 4); if (w) w->newid = (int32_t*)p;
-  p = take((size_t)n * 4); if (w) w->crank = (int32_t*)p;
-  p = take((size_t)(n + 1) * 4); if (w) w->coff = (int32_t*)p;
-  p = take((size_t)n * 4); if (w) w->members = (int32_t*)p;
-  p = take((size_t)n * 4); if (w) w->nnc = (int32_t*)p;
-  p = take((size_t)n * 8); if (w) w->link = (int32_t*)p;
-  p = take((size_t)n * 16); if (w) w->cent = (double*)p;
-  p = take((size_t)(n + 1) * 4); if (w) w->ptr0 = (int32_t*)p;
-  p = take((size_t)cap * 4); if (w) w->idx0 = (int32_t*)p;
-  p = take((size_t)cap * 4); if (w) w->esrc = (int32_t*)p;
-  p = take(64); if (w) w->counters = (int32_t*)p;
-  p = take((size_t)(n + 1) * 4); if (w) w->coff2 = (int32_t*)p;
-  p = take((size_t)n * 4); if (w) w->degk = (int32_t*)p;
-  if (w) { w->n = n; w->d = d; w->nw = nw; w->cap = cap; }
-  return off;
+  w.S16 = with_s16 ? L.take<uint16_t>((size_t)n * lds16) : nullptr;
+  w.clist = L.take<uint32_t>(cap);
+  w.ckey = L.take<uint32_t>(cap);
+  w.list = L.take<uint32_t>(list_cap);
+  w.list_cap = (uint32_t)list_cap;
+  w.clist_cap = (uint32_t)cap;
+  w.lds16 = lds16;
+  w.cellptr = L.take<int32_t>(AGC_NB + 1);
+  w.cellidx = L.take<int32_t>(n);
+  w.bits = L.take<uint64_t>((size_t)n * nw);
+  w.hist = L.take<uint32_t>(4096);
+  w.sel = L.take<uint32_t>(4);
+  w.band = L.take<uint32_t>(4);
+  w.deg = L.take<int32_t>(n);
+  w.nn = L.take<int32_t>(n);
+  w.label = L.take<int32_t>(n);
+  w.alive = L.take<int32_t>(n);
+  w.newid = L.take<int32_t>(n);
+  w.crank = L.take<int32_t>(n);
+  w.coff = L.take<int32_t>(n + 1);
+  w.members = L.take<int32_t>(n);
+  w.nnc = L.take<int32_t>(n);
+  w.link = L.take<int32_t>((size_t)n * 2);
+  w.cent = L.take<double>((size_t)n * 2);
+  w.ptr0 = L.take<int32_t>(n + 1);
+  w.idx0 = L.take<int32_t>(cap);
+  w.esrc = L.take<int32_t>(cap);
+  w.counters = L.take<int32_t>(16);
+  w.coff2 = L.take<int32_t>(n + 1);
+  w.degk = L.take<int32_t>(n);
+  w.n = n; w.d = d; w.nw = nw; w.cap = cap;
 }
 
-static size_t agc_batch_header(int n_images) { return al256(sizeof(AgcWs) * (size_t)n_images); }
+// The whole workspace: the AgcWs table, then image after image.  recs == nullptr: sizing only.
+static void agc_batch_layout(const gims_agc_image* images, int n_images, bool robust, WsLayout& L, AgcWs* recs) {
+  L.take<AgcWs>(n_images);
+  AgcWs scratch;
+  for (int i = 0; i < n_images; ++i) agc_layout(images[i].n, images[i].d, images[i].max_edges_dir, robust, L, recs ? recs[i] : scratch);
+}
 
 }  // namespace gims
 
@@ -1561,9 +1557,9 @@ extern "C" size_t gims_agc_workspace_bytes_ex(const gims_agc_image* images, int3
   using namespace gims;
   if (!images || n_images <= 0) return 0;
   const bool robust = agc_takes_robust_flow(images, n_images, flags);
-  size_t b = agc_batch_header(n_images);
-  for (int i = 0; i < n_images; ++i) b += agc_layout(images[i].n, images[i].d, images[i].max_edges_dir, robust, nullptr, nullptr);
-  return b;
+  WsLayout L(nullptr);
+  agc_batch_layout(images, n_images, robust, L, nullptr);
+  return L.bytes();
 }
 
 extern "C" size_t gims_agc_workspace_bytes(const gims_agc_image* images, int32_t n_images) {
@@ -1594,22 +1590,24 @@ extern "C" int gims_agc_build_v(const gims_agc_image* images, int32_t n_images, 
   const bool robust = agc_takes_robust_flow(images, n_images, flags);
   const char* env_shift = getenv("GIMS_AGC_WINDOW_SHIFT");
   const float window_test_shift = env_shift ? (float)atof(env_shift) : 0.f;
-  GIMS_CHECK_ARG(work_bytes >= gims_agc_workspace_bytes_ex(images, n_images, robust ? GIMS_AGC_ROBUST : 0),
-                 "gims_agc_build: workspace too small (%zu bytes; gims_agc_workspace_bytes_ex asks for %zu for the %s flow)", work_bytes,
-                 gims_agc_workspace_bytes_ex(images, n_images, robust ? GIMS_AGC_ROBUST : 0), robust ? "robust" : "window");
-  hipStream_t s = (hipStream_t)stream;
-  AgcWs* dws = (AgcWs*)work;
-  char* base = (char*)work + agc_batch_header(n_images);
-  int maxn = 0, maxnw = 0;
-  std::vector<AgcWs> hws(n_images);
   for (int i = 0; i < n_images; ++i) {
     const gims_agc_image& im = images[i];
     GIMS_CHECK_ARG(im.kpts && im.desc && im.kept && im.indptr && im.indices && im.info, "gims_agc_build: image %d has a null pointer", i);
     GIMS_CHECK_ARG(im.n >= 2 && im.n <= AGC_MAX_N, "gims_agc_build: image %d: n=%d out of range [2, %d] (gims_agc_max_keypoints)", i, im.n, AGC_MAX_N);
     static_assert(AGC_MAX_N <= (1 << AGC_PK_SHIFT), "the band list packs a pair as i << 16 | j");
     GIMS_CHECK_ARG(im.d > 0 && (im.d % 32) == 0 && (im.ldd % 4) == 0, "gims_agc_build: image %d: d=%d must be a multiple of 32 (ldd %% 4 == 0)", i, im.d);
+  }
+  std::vector<AgcWs> hws(n_images);
+  WsLayout lay(work);
+  agc_batch_layout(images, n_images, robust, lay, hws.data());
+  GIMS_CHECK_ARG(work_bytes >= lay.bytes(), "gims_agc_build: workspace too small (%zu bytes; gims_agc_workspace_bytes_ex asks for %zu for the %s flow)", work_bytes,
+                 lay.bytes(), robust ? "robust" : "window");
+  hipStream_t s = (hipStream_t)stream;
+  AgcWs* dws = (AgcWs*)work;
+  int maxn = 0, maxnw = 0;
+  for (int i = 0; i < n_images; ++i) {
+    const gims_agc_image& im = images[i];
     AgcWs* w = &hws[i];
-    base += agc_layout(im.n, im.d, im.max_edges_dir, robust, base, w);
     w->kpts = im.kpts; w->desc = im.desc; w->ldd = im.ldd; w->kept = im.kept; w->indptr = im.indptr; w->indices = im.indices;
     w->info = im.info; w->max_edges_dir = im.max_edges_dir;
     // K2 rank: k = int(L * p / 100), clamped (agc.py:378-379)

@@ -130,6 +130,18 @@ __device__ __forceinline__ bool attn_guard_fires(const gims_attn_guard& g) {
 }
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+
+// Caller-allocated scratch workspaces.  Every region starts on a 256-byte boundary.  Each workspace has ONE layout routine that walks a
+// WsLayout through its takes; the size query runs it on a null base (take returns nullptr, bytes() is the answer) and the launch runs the
+// same routine on the caller's buffer, then compares bytes() with the size it was given before anything is enqueued.
+static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+struct WsLayout {
+  char* base;          // nullptr: sizing only
+  size_t off = 0;
+  explicit WsLayout(void* b) : base((char*)b) {}
+  template <typename T> T* take(size_t count) { const size_t o = off; off += al256(sizeof(T) * count); return base ? (T*)(base + o) : nullptr; }
+  size_t bytes() const { return off; }     // the total so far: also the offset of the next take
+};
 // GIMS_GUARD_WALK=0: guarded launches take the full grid instead of one dispatch round of workgroups that walk the tiles (read per call: the
 // cross-check of tests/test_hip_kernels.py::test_guarded_launches_that_walk_their_tiles switches it)
 static inline bool guard_walk_enabled() { const char* e = getenv("GIMS_GUARD_WALK"); return !(e && atoi(e) == 0); }

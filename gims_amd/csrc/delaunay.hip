@@ -456,38 +456,38 @@ __global__ void dt_info_kernel(const DtWs* __restrict__ wss) {
   for (int i = 0; i < 8; ++i) w.info[i] = v[i];
 }
 
-static inline size_t dt_al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-static size_t dt_layout(int n, char* base, DtWs* w) {
+// One image's part of the workspace (sizing: L on a null base, w a scratch record)
+static void dt_layout(int n, WsLayout& L, DtWs& w) {
   const int T = n / 2 > 1 ? n / 2 : 1, ncap = 3 * T + 2;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += dt_al256(bytes); return base ? base + o : (char*)nullptr; };
-  char* p;
-  p = take((size_t)(ncap + 1) * 4); if (w) w->cstart = (int32_t*)p;
-  p = take((size_t)ncap * 4); if (w) w->ccnt = (int32_t*)p;
-  p = take((size_t)ncap * 4); if (w) w->cfill = (int32_t*)p;
-  p = take((size_t)n * 4); if (w) w->csort = (int32_t*)p;
-  p = take((size_t)n * 4); if (w) w->cid = (int32_t*)p;
-  p = take((size_t)n * 8); if (w) w->cpt = (float2*)p;
-  p = take((size_t)n * 4); if (w) w->deg = (int32_t*)p;
-  p = take((size_t)n * 4); if (w) w->fb = (int32_t*)p;
-  p = take((size_t)n * 4); if (w) w->fbmark = (int32_t*)p;
-  p = take(64); if (w) w->cnt = (int32_t*)p;
-  p = take(sizeof(DtGrid)); if (w) w->grid = (DtGrid*)p;
-  if (w) { w->n = n; w->ncell_cap = ncap; w->pad = 0; }
-  return off;
+  w.cstart = L.take<int32_t>(ncap + 1);
+  w.ccnt = L.take<int32_t>(ncap);
+  w.cfill = L.take<int32_t>(ncap);
+  w.csort = L.take<int32_t>(n);
+  w.cid = L.take<int32_t>(n);
+  w.cpt = L.take<float2>(n);
+  w.deg = L.take<int32_t>(n);
+  w.fb = L.take<int32_t>(n);
+  w.fbmark = L.take<int32_t>(n);
+  w.cnt = L.take<int32_t>(16);
+  w.grid = L.take<DtGrid>(1);
+  w.n = n; w.ncell_cap = ncap; w.pad = 0;
 }
 
-static size_t dt_batch_header(int n_images) { return dt_al256(sizeof(DtWs) * (size_t)n_images); }
+// The whole workspace: the DtWs table, then image after image.  recs == nullptr: sizing only.
+static void dt_batch_layout(const gims_agc_image* images, int n_images, WsLayout& L, DtWs* recs) {
+  L.take<DtWs>(n_images);
+  DtWs scratch;
+  for (int i = 0; i < n_images; ++i) dt_layout(images[i].n > 0 ? images[i].n : 0, L, recs ? recs[i] : scratch);
+}
 
 }  // namespace gims
 
 extern "C" size_t gims_delaunay_workspace_bytes(const gims_agc_image* images, int32_t n_images) {
   using namespace gims;
   if (!images || n_images <= 0) return 0;
-  size_t b = dt_batch_header(n_images);
-  for (int i = 0; i < n_images; ++i) b += dt_layout(images[i].n > 0 ? images[i].n : 0, nullptr, nullptr);
-  return b;
+  WsLayout L(nullptr);
+  dt_batch_layout(images, n_images, L, nullptr);
+  return L.bytes();
 }
 
 extern "C" int gims_delaunay_build(const gims_agc_image* images, int32_t n_images, void* work, size_t work_bytes, void* stream) {
@@ -500,18 +500,17 @@ extern "C" int gims_delaunay_build(const gims_agc_image* images, int32_t n_image
                    DT_MAX_N);
     GIMS_CHECK_ARG(im.max_edges_dir >= 0, "gims_delaunay_build: image %d: max_edges_dir=%d < 0", i, im.max_edges_dir);
   }
-  const size_t need = gims_delaunay_workspace_bytes(images, n_images);
-  GIMS_CHECK_ARG(work_bytes >= need, "gims_delaunay_build: workspace too small (%zu bytes; gims_delaunay_workspace_bytes asks for %zu)", work_bytes,
-                 need);
+  std::vector<DtWs> hws(n_images);
+  WsLayout L(work);
+  dt_batch_layout(images, n_images, L, hws.data());
+  GIMS_CHECK_ARG(work_bytes >= L.bytes(), "gims_delaunay_build: workspace too small (%zu bytes; gims_delaunay_workspace_bytes asks for %zu)", work_bytes,
+                 L.bytes());
   hipStream_t s = (hipStream_t)stream;
   DtWs* dws = (DtWs*)work;
-  char* base = (char*)work + dt_batch_header(n_images);
   int maxn = 0;
-  std::vector<DtWs> hws(n_images);
   for (int i = 0; i < n_images; ++i) {
     const gims_agc_image& im = images[i];
     DtWs* w = &hws[i];
-    base += dt_layout(im.n, base, w);
     w->kpts = im.kpts; w->kept = im.kept; w->indptr = im.indptr; w->indices = im.indices; w->info = im.info;
     w->max_edges_dir = im.max_edges_dir;
     maxn = im.n > maxn ? im.n : maxn;

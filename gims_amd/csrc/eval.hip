@@ -419,19 +419,43 @@ __global__ __launch_bounds__(1024) void eval_ransac_finish_kernel(const EvalDev*
   }
 }
 
-static inline size_t al256e(size_t x) { return (x + 255) & ~(size_t)255; }
-static size_t eval_pair_bytes(const gims_eval_pair& p, int iters) {
-  return al256e((size_t)p.n0 * 8) + 5 * al256e((size_t)p.n0 * 4) + 3 * al256e((size_t)p.n1 * 4) + al256e((size_t)iters * 4) + 256;
+// The workspace of gims_eval_pairs: the EvalDev table, then per pair the GT-matching arrays and the RANSAC counters.  recs == nullptr: sizing only.
+static void eval_layout(const gims_eval_pair* pairs, int n_pairs, int ransac_iters, WsLayout& L, EvalDev* recs) {
+  L.take<EvalDev>(n_pairs);
+  for (int i = 0; i < n_pairs; ++i) {
+    const gims_eval_pair& p = pairs[i];
+    EvalDev d;
+    memset(&d, 0, sizeof(d));
+    d.proj = L.take<float>((size_t)p.n0 * 2);
+    d.alive0 = L.take<int32_t>(p.n0);
+    d.min1 = L.take<int32_t>(p.n0);
+    d.midx = L.take<int32_t>(p.n0);
+    L.take<int32_t>(p.n0); L.take<int32_t>(p.n0);      // reserved: two n0 arrays no kernel uses (kept so that the size query is unchanged)
+    d.alive1 = L.take<int32_t>(p.n1);
+    d.min2 = L.take<int32_t>(p.n1);
+    d.gt1 = L.take<int32_t>(p.n1);
+    d.hypcount = L.take<int32_t>(ransac_iters);
+    d.nvalid = L.take<int32_t>(64);
+    if (!recs) continue;
+    d.kp0 = p.kpts0; d.kp1 = p.kpts1; d.matches0 = p.matches0; d.mscores0 = p.mscores0;
+    d.n0 = p.n0; d.n1 = p.n1; d.height = p.height; d.width = p.width;
+    memcpy(d.hgt, p.h_gt, sizeof(d.hgt));
+    d.gt0 = p.gt0; d.inlier = p.inlier; d.record = p.record; d.hom = p.homographies;
+    recs[i] = d;
+  }
 }
+
+// The GT-matching launches shared with gims_train_labels (defined below, behind the label kernels)
+static void eval_gt_matching(const EvalDev* dev, int n_pairs, int maxn0, int maxn1, float dist_thresh, int n_iters, int32_t* const* itr, hipStream_t s);
 
 }  // namespace gims
 
 extern "C" size_t gims_eval_workspace_bytes(const gims_eval_pair* pairs, int32_t n_pairs, int32_t ransac_iters) {
   using namespace gims;
   if (!pairs || n_pairs <= 0 || ransac_iters < 0) return 0;
-  size_t b = al256e(sizeof(EvalDev) * (size_t)n_pairs);
-  for (int i = 0; i < n_pairs; ++i) b += eval_pair_bytes(pairs[i], ransac_iters);
-  return b;
+  WsLayout L(nullptr);
+  eval_layout(pairs, n_pairs, ransac_iters, L, nullptr);
+  return L.bytes();
 }
 
 extern "C" int gims_eval_pairs(const gims_eval_pair* pairs, int32_t n_pairs, float dist_thresh, int32_t n_iters, float ransac_thresh,
@@ -439,45 +463,23 @@ extern "C" int gims_eval_pairs(const gims_eval_pair* pairs, int32_t n_pairs, flo
   using namespace gims;
   GIMS_CHECK_ARG(pairs && n_pairs > 0 && work, "gims_eval_pairs: null / empty arguments");
   GIMS_CHECK_ARG(n_iters >= 0 && ransac_iters >= 0 && ransac_iters <= (1 << 20), "gims_eval_pairs: bad iteration counts");
-  GIMS_CHECK_ARG(work_bytes >= gims_eval_workspace_bytes(pairs, n_pairs, ransac_iters), "gims_eval_pairs: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  std::vector<EvalDev> h(n_pairs);
-  char* base = (char*)work;
-  size_t off = al256e(sizeof(EvalDev) * (size_t)n_pairs);
   int maxn0 = 0, maxn1 = 0;
   for (int i = 0; i < n_pairs; ++i) {
     const gims_eval_pair& p = pairs[i];
     GIMS_CHECK_ARG(p.n0 > 0 && p.n1 > 0 && p.kpts0 && p.kpts1 && p.matches0 && p.mscores0 && p.gt0 && p.inlier && p.record && p.homographies,
                    "gims_eval_pairs: pair %d has an empty shape or a null pointer", i);
-    EvalDev d;
-    d.kp0 = p.kpts0; d.kp1 = p.kpts1; d.matches0 = p.matches0; d.mscores0 = p.mscores0;
-    d.n0 = p.n0; d.n1 = p.n1; d.height = p.height; d.width = p.width;
-    memcpy(d.hgt, p.h_gt, sizeof(d.hgt));
-    d.gt0 = p.gt0; d.inlier = p.inlier; d.record = p.record; d.hom = p.homographies;
-    d.proj = (float*)(base + off); off += al256e((size_t)p.n0 * 8);
-    d.alive0 = (int32_t*)(base + off); off += al256e((size_t)p.n0 * 4);
-    d.min1 = (int32_t*)(base + off); off += al256e((size_t)p.n0 * 4);
-    d.midx = (int32_t*)(base + off); off += al256e((size_t)p.n0 * 4);
-    off += 2 * al256e((size_t)p.n0 * 4);       // spare
-    d.alive1 = (int32_t*)(base + off); off += al256e((size_t)p.n1 * 4);
-    d.min2 = (int32_t*)(base + off); off += al256e((size_t)p.n1 * 4);
-    d.gt1 = (int32_t*)(base + off); off += al256e((size_t)p.n1 * 4);
-    d.hypcount = (int32_t*)(base + off); off += al256e((size_t)ransac_iters * 4);
-    d.nvalid = (int32_t*)(base + off); off += 256;
-    h[i] = d;
     maxn0 = p.n0 > maxn0 ? p.n0 : maxn0;
     maxn1 = p.n1 > maxn1 ? p.n1 : maxn1;
   }
+  std::vector<EvalDev> h(n_pairs);
+  WsLayout L(work);
+  eval_layout(pairs, n_pairs, ransac_iters, L, h.data());
+  GIMS_CHECK_ARG(work_bytes >= L.bytes(), "gims_eval_pairs: workspace too small (%zu < %zu)", work_bytes, L.bytes());
+  hipStream_t s = (hipStream_t)stream;
   int rc = upload_table(h.data(), sizeof(EvalDev) * (size_t)n_pairs, work, s);
   if (rc != GIMS_OK) return rc;
   const EvalDev* dev = (const EvalDev*)work;
-  const int mx = maxn0 > maxn1 ? maxn0 : maxn1;
-  hipLaunchKernelGGL(eval_warp_kernel, dim3(cdiv(mx, 256), n_pairs), dim3(256), 0, s, dev);
-  for (int it = 0; it < n_iters; ++it) {
-    hipLaunchKernelGGL(eval_argmin_kernel<true>, dim3(cdiv(maxn0, 4), n_pairs), dim3(256), 0, s, dev);
-    hipLaunchKernelGGL(eval_argmin_kernel<false>, dim3(cdiv(maxn1, 4), n_pairs), dim3(256), 0, s, dev);
-    hipLaunchKernelGGL(eval_mutual_kernel, dim3(cdiv(maxn1, 256), n_pairs), dim3(256), 0, s, dev, dist_thresh);
-  }
+  eval_gt_matching(dev, n_pairs, maxn0, maxn1, dist_thresh, n_iters, nullptr, s);
   hipLaunchKernelGGL(eval_counts_kernel, dim3(n_pairs), dim3(1024), 0, s, dev);
   const double t2 = (double)ransac_thresh * (double)ransac_thresh;
   if (ransac_iters > 0) hipLaunchKernelGGL(eval_ransac_kernel, dim3(cdiv(ransac_iters, 4), n_pairs), dim3(256), 0, s, dev, seed, ransac_iters, t2);
@@ -571,8 +573,47 @@ __global__ __launch_bounds__(1024) void lab_rows_kernel(const EvalDev* __restric
   }
 }
 
-static size_t label_pair_bytes(const gims_label_pair& p) {
-  return al256e((size_t)p.n0 * 8) + 3 * al256e((size_t)p.n0 * 4) + al256e((size_t)p.n0) + 4 * al256e((size_t)p.n1 * 4);
+// The GT-matching launches shared by gims_eval_pairs and gims_train_labels: the warp, then n_iters rounds of the two arg-min sweeps and the
+// mutual test; the labels path passes the table of its per-pair iteration arrays (itr) and gets lab_iter_kernel after every round.
+static void eval_gt_matching(const EvalDev* dev, int n_pairs, int maxn0, int maxn1, float dist_thresh, int n_iters, int32_t* const* itr, hipStream_t s) {
+  const int mx = maxn0 > maxn1 ? maxn0 : maxn1;
+  hipLaunchKernelGGL(eval_warp_kernel, dim3(cdiv(mx, 256), n_pairs), dim3(256), 0, s, dev);
+  for (int it = 0; it < n_iters; ++it) {
+    hipLaunchKernelGGL(eval_argmin_kernel<true>, dim3(cdiv(maxn0, 4), n_pairs), dim3(256), 0, s, dev);
+    hipLaunchKernelGGL(eval_argmin_kernel<false>, dim3(cdiv(maxn1, 4), n_pairs), dim3(256), 0, s, dev);
+    hipLaunchKernelGGL(eval_mutual_kernel, dim3(cdiv(maxn1, 256), n_pairs), dim3(256), 0, s, dev, dist_thresh);
+    if (itr) hipLaunchKernelGGL(lab_iter_kernel, dim3(cdiv(maxn1, 256), n_pairs), dim3(256), 0, s, dev, itr, it);
+  }
+}
+
+// The workspace of gims_train_labels: the EvalDev table, the table of iteration-array pointers, the row counts, the per-pair iteration
+// arrays back to back (one block: the setup kernel initialises them in one sweep), then per pair the GT-matching arrays.  recs == nullptr: sizing only.
+struct LabWs { int32_t* const* ditr; int32_t* counts; int32_t* itr_all; int64_t n1_total; };
+static LabWs label_layout(const gims_label_pair* pairs, int n_pairs, WsLayout& L, EvalDev* recs, int32_t** itr) {
+  LabWs w{};
+  L.take<EvalDev>(n_pairs);
+  w.ditr = L.take<int32_t*>(n_pairs);
+  w.counts = L.take<int32_t>(n_pairs);
+  for (int i = 0; i < n_pairs; ++i) w.n1_total += (int64_t)(al256((size_t)pairs[i].n1 * 4) / 4);
+  w.itr_all = L.take<int32_t>((size_t)w.n1_total);
+  int64_t itr_off = 0;
+  for (int i = 0; i < n_pairs; ++i) {
+    const gims_label_pair& p = pairs[i];
+    EvalDev d;
+    memset(&d, 0, sizeof(d));
+    d.proj = L.take<float>((size_t)p.n0 * 2);
+    d.alive0 = L.take<int32_t>(p.n0);
+    d.min1 = L.take<int32_t>(p.n0);
+    d.gt0 = L.take<int32_t>(p.n0);
+    d.inlier = L.take<uint8_t>(p.n0);
+    d.alive1 = L.take<int32_t>(p.n1);
+    d.min2 = L.take<int32_t>(p.n1);
+    d.gt1 = L.take<int32_t>(p.n1);
+    d.kp0 = p.kpts0; d.kp1 = p.kpts1; d.n0 = p.n0; d.n1 = p.n1;
+    if (recs) { recs[i] = d; itr[i] = w.itr_all + itr_off; }
+    itr_off += (int64_t)(al256((size_t)p.n1 * 4) / 4);
+  }
+  return w;
 }
 
 }  // namespace gims
@@ -580,9 +621,9 @@ static size_t label_pair_bytes(const gims_label_pair& p) {
 extern "C" size_t gims_train_labels_workspace_bytes(const gims_label_pair* pairs, int32_t n_pairs) {
   using namespace gims;
   if (!pairs || n_pairs <= 0) return 0;
-  size_t b = al256e(sizeof(EvalDev) * (size_t)n_pairs) + al256e(sizeof(int32_t*) * (size_t)n_pairs) + al256e(4 * (size_t)n_pairs);
-  for (int i = 0; i < n_pairs; ++i) b += label_pair_bytes(pairs[i]);
-  return b;
+  WsLayout L(nullptr);
+  label_layout(pairs, n_pairs, L, nullptr, nullptr);
+  return L.bytes();
 }
 
 extern "C" int gims_train_labels(const gims_label_pair* pairs, int32_t n_pairs, const float* homographies, float dist_thresh, int32_t n_iters,
@@ -590,60 +631,28 @@ extern "C" int gims_train_labels(const gims_label_pair* pairs, int32_t n_pairs, 
   using namespace gims;
   GIMS_CHECK_ARG(pairs && n_pairs > 0 && n_pairs <= 65535 && homographies && rows && total && work, "gims_train_labels: null / empty arguments");
   GIMS_CHECK_ARG(n_iters >= 0 && n_iters <= 64, "gims_train_labels: bad iteration count");
-  GIMS_CHECK_ARG(work_bytes >= gims_train_labels_workspace_bytes(pairs, n_pairs), "gims_train_labels: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  std::vector<EvalDev> h(n_pairs);
-  std::vector<int32_t*> hitr(n_pairs);
-  char* base = (char*)work;
-  size_t off = al256e(sizeof(EvalDev) * (size_t)n_pairs);
-  int32_t* const* ditr = (int32_t* const*)(base + off);
-  off += al256e(sizeof(int32_t*) * (size_t)n_pairs);
-  int32_t* counts = (int32_t*)(base + off);
-  off += al256e(4 * (size_t)n_pairs);
-  // the per-pair iteration arrays sit back to back so that the setup kernel initialises them in one sweep
-  int64_t n1_total = 0;
-  for (int i = 0; i < n_pairs; ++i) n1_total += al256e((size_t)pairs[i].n1 * 4) / 4;
-  int32_t* itr_all = (int32_t*)(base + off);
-  off += (size_t)n1_total * 4;
-  int64_t itr_off = 0;
   int maxn0 = 0, maxn1 = 0;
   for (int i = 0; i < n_pairs; ++i) {
     const gims_label_pair& p = pairs[i];
     GIMS_CHECK_ARG(p.n0 > 0 && p.n1 > 0 && p.kpts0 && p.kpts1, "gims_train_labels: pair %d has an empty shape or a null pointer", i);
-    EvalDev d;
-    memset(&d, 0, sizeof(d));
-    d.kp0 = p.kpts0; d.kp1 = p.kpts1;
-    d.n0 = p.n0; d.n1 = p.n1;
-    d.proj = (float*)(base + off); off += al256e((size_t)p.n0 * 8);
-    d.alive0 = (int32_t*)(base + off); off += al256e((size_t)p.n0 * 4);
-    d.min1 = (int32_t*)(base + off); off += al256e((size_t)p.n0 * 4);
-    d.gt0 = (int32_t*)(base + off); off += al256e((size_t)p.n0 * 4);
-    d.inlier = (uint8_t*)(base + off); off += al256e((size_t)p.n0);
-    d.alive1 = (int32_t*)(base + off); off += al256e((size_t)p.n1 * 4);
-    d.min2 = (int32_t*)(base + off); off += al256e((size_t)p.n1 * 4);
-    d.gt1 = (int32_t*)(base + off); off += al256e((size_t)p.n1 * 4);
-    hitr[i] = itr_all + itr_off;
-    itr_off += al256e((size_t)p.n1 * 4) / 4;
-    h[i] = d;
     maxn0 = p.n0 > maxn0 ? p.n0 : maxn0;
     maxn1 = p.n1 > maxn1 ? p.n1 : maxn1;
   }
+  std::vector<EvalDev> h(n_pairs);
+  std::vector<int32_t*> hitr(n_pairs);
+  WsLayout L(work);
+  const LabWs w = label_layout(pairs, n_pairs, L, h.data(), hitr.data());
+  GIMS_CHECK_ARG(work_bytes >= L.bytes(), "gims_train_labels: workspace too small (%zu < %zu)", work_bytes, L.bytes());
+  hipStream_t s = (hipStream_t)stream;
   int rc = upload_table(h.data(), sizeof(EvalDev) * (size_t)n_pairs, work, s);
   if (rc != GIMS_OK) return rc;
-  rc = upload_table(hitr.data(), sizeof(int32_t*) * (size_t)n_pairs, (void*)ditr, s);
+  rc = upload_table(hitr.data(), sizeof(int32_t*) * (size_t)n_pairs, (void*)w.ditr, s);
   if (rc != GIMS_OK) return rc;
   EvalDev* dev = (EvalDev*)work;
-  hipLaunchKernelGGL(lab_setup_kernel, dim3(n_pairs), dim3(64), 0, s, dev, homographies, itr_all, n1_total);
-  const int mx = maxn0 > maxn1 ? maxn0 : maxn1;
-  hipLaunchKernelGGL(eval_warp_kernel, dim3(cdiv(mx, 256), n_pairs), dim3(256), 0, s, (const EvalDev*)dev);
-  for (int it = 0; it < n_iters; ++it) {
-    hipLaunchKernelGGL(eval_argmin_kernel<true>, dim3(cdiv(maxn0, 4), n_pairs), dim3(256), 0, s, (const EvalDev*)dev);
-    hipLaunchKernelGGL(eval_argmin_kernel<false>, dim3(cdiv(maxn1, 4), n_pairs), dim3(256), 0, s, (const EvalDev*)dev);
-    hipLaunchKernelGGL(eval_mutual_kernel, dim3(cdiv(maxn1, 256), n_pairs), dim3(256), 0, s, (const EvalDev*)dev, dist_thresh);
-    hipLaunchKernelGGL(lab_iter_kernel, dim3(cdiv(maxn1, 256), n_pairs), dim3(256), 0, s, (const EvalDev*)dev, ditr, it);
-  }
-  hipLaunchKernelGGL(lab_rows_kernel<0>, dim3(n_pairs), dim3(1024), 0, s, (const EvalDev*)dev, ditr, n_iters, counts, rows, total);
-  hipLaunchKernelGGL(lab_rows_kernel<1>, dim3(n_pairs), dim3(1024), 0, s, (const EvalDev*)dev, ditr, n_iters, counts, rows, total);
+  hipLaunchKernelGGL(lab_setup_kernel, dim3(n_pairs), dim3(64), 0, s, dev, homographies, w.itr_all, w.n1_total);
+  eval_gt_matching(dev, n_pairs, maxn0, maxn1, dist_thresh, n_iters, w.ditr, s);
+  hipLaunchKernelGGL(lab_rows_kernel<0>, dim3(n_pairs), dim3(1024), 0, s, (const EvalDev*)dev, w.ditr, n_iters, w.counts, rows, total);
+  hipLaunchKernelGGL(lab_rows_kernel<1>, dim3(n_pairs), dim3(1024), 0, s, (const EvalDev*)dev, w.ditr, n_iters, w.counts, rows, total);
   GIMS_LAUNCH_CHECK();
   return GIMS_OK;
 }

@@ -358,8 +358,6 @@ __global__ __launch_bounds__(256) void nn_finish_kernel(const NnPairDev* __restr
 }
 
 // ---------------------------------------------------------------------------------------------- host
-static inline size_t nn_al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static bool nn_pair_ok(const gims_nn_pair& p, int i, bool report) {
   const char* why = nullptr;
   if (p.d < 32 || p.d > 64 * NN_MAXT || p.d % 32 != 0) why = "d must be a multiple of 32 in [32, 512]";
@@ -374,9 +372,10 @@ static bool nn_pair_ok(const gims_nn_pair& p, int i, bool report) {
   return why == nullptr;
 }
 
-// Lays the workspace out (base may be null: sizes only).  Tables first, then the words that must start at zero, then per-pair arrays.
-static size_t nn_layout(const gims_nn_pair* pairs, int n_pairs, int flags, char* base, std::vector<NnProb>* probs, std::vector<NnPairDev>* pd,
-                        size_t* zero_off, size_t* zero_bytes, int* n_items) {
+// The workspace: the two descriptor tables, then the words that must start at zero (four per pair), then per-pair arrays.  probs / pd null
+// (with L on a null base): sizing only.
+struct NnWs { NnProb* dprobs; NnPairDev* dpairs; uint32_t* zero; size_t zero_bytes; int n_items; };
+static NnWs nn_layout(const gims_nn_pair* pairs, int n_pairs, int flags, WsLayout& L, std::vector<NnProb>* probs, std::vector<NnPairDev>* pd) {
   const bool forced = (flags & GIMS_NN_EXHAUSTIVE) != 0;
   int np = 0;
   int64_t rbs = 0;
@@ -386,26 +385,25 @@ static size_t nn_layout(const gims_nn_pair* pairs, int n_pairs, int flags, char*
   }
   int want = (int)((NN_TARGET_WGS + rbs - 1) / rbs);
   want = want < 1 ? 1 : (want > NN_MAX_SPLIT ? NN_MAX_SPLIT : want);
-  size_t off = nn_al(sizeof(NnProb) * (size_t)np) + nn_al(sizeof(NnPairDev) * (size_t)n_pairs);
-  *zero_off = off;
-  *zero_bytes = nn_al(16 * (size_t)n_pairs);
-  off += *zero_bytes;
-  int item = 0;
+  NnWs w{};
+  w.dprobs = L.take<NnProb>(np);
+  w.dpairs = L.take<NnPairDev>(n_pairs);
+  w.zero = L.take<uint32_t>(4 * (size_t)n_pairs);
+  w.zero_bytes = al256(16 * (size_t)n_pairs);
   for (int i = 0; i < n_pairs; ++i) {
     const gims_nn_pair& p = pairs[i];
-    uint32_t* z = (uint32_t*)(base + *zero_off) + 4 * (size_t)i;              // {amax bits, bmax bits, fb_count0, fb_count1}
+    uint32_t* z = w.zero ? w.zero + 4 * (size_t)i : nullptr;                  // {amax bits, bmax bits, fb_count0, fb_count1}
     NnPairDev D;
     memset(&D, 0, sizeof(D));
     D.a = p.a; D.b = p.b; D.lda = p.lda; D.ldb = p.ldb; D.n0 = p.n0; D.n1 = p.n1; D.d = p.d; D.mutual = p.mutual ? 1 : 0;
     D.threshold = p.threshold; D.forced = forced;
-    D.an = (double*)(base + off); off += nn_al((size_t)p.n0 * 8);
-    D.bn = (double*)(base + off); off += nn_al((size_t)p.n1 * 8);
-    D.anf = (float*)(base + off); off += nn_al((size_t)p.n0 * 4);
-    D.bnf = (float*)(base + off); off += nn_al((size_t)p.n1 * 4);
-    D.amax = z; D.bmax = z + 1;
+    D.an = L.take<double>(p.n0);
+    D.bn = L.take<double>(p.n1);
+    D.anf = L.take<float>(p.n0);
+    D.bnf = L.take<float>(p.n1);
     D.nn1 = p.nn1; D.d1 = p.d1; D.d2 = p.d2;
     D.ratio = p.ratio; D.match = p.match; D.matches0 = p.matches0; D.scores0 = p.scores0; D.matches1 = p.matches1; D.info = p.info;
-    D.fb_count0 = (const int32_t*)(z + 2); D.fb_count1 = (const int32_t*)(z + 3);
+    if (z) { D.amax = z; D.bmax = z + 1; D.fb_count0 = (const int32_t*)(z + 2); D.fb_count1 = (const int32_t*)(z + 3); }
     for (int dir = 0; dir < (p.mutual ? 2 : 1); ++dir) {
       NnProb Q;
       memset(&Q, 0, sizeof(Q));
@@ -415,32 +413,30 @@ static size_t nn_layout(const gims_nn_pair* pairs, int n_pairs, int flags, char*
       int cs = want < tiles_total ? want : tiles_total;
       Q.tiles_per = cdiv(tiles_total, cs);
       Q.csplit = cdiv(tiles_total, Q.tiles_per);                               // no empty split
-      Q.item0 = item; Q.forced = forced;
-      item += cdiv(Q.nx, NN_T) * Q.csplit;
+      Q.item0 = w.n_items; Q.forced = forced;
+      w.n_items += cdiv(Q.nx, NN_T) * Q.csplit;
       Q.xn = dir ? D.bn : D.an; Q.ynf = dir ? D.anf : D.bnf; Q.ymax_bits = dir ? D.amax : D.bmax;
       const size_t nc = (size_t)Q.nx * 4 * Q.csplit * NN_K;
       if (!forced) {
-        Q.cs = (float*)(base + off); off += nn_al(nc * 4);
-        Q.ci = (int32_t*)(base + off); off += nn_al(nc * 4);
+        Q.cs = L.take<float>(nc);
+        Q.ci = L.take<int32_t>(nc);
       }
-      Q.fb_rows = (int32_t*)(base + off); off += nn_al((size_t)Q.nx * 4);
-      Q.fb_count = (int32_t*)(z + 2 + dir);
+      Q.fb_rows = L.take<int32_t>(Q.nx);
+      Q.fb_count = z ? (int32_t*)(z + 2 + dir) : nullptr;
       if (dir == 0) {
         Q.nn1 = p.nn1; Q.nn2 = p.nn2; Q.d1 = p.d1; Q.d2 = p.d2; Q.debug = forced ? nullptr : p.debug;
       } else {
-        Q.nn1 = p.cnn1 ? p.cnn1 : (int32_t*)(base + off);
-        if (!p.cnn1) off += nn_al((size_t)Q.nx * 4);
-        Q.nn2 = (int32_t*)(base + off); off += nn_al((size_t)Q.nx * 4);
-        Q.d1 = (float*)(base + off); off += nn_al((size_t)Q.nx * 4);
-        Q.d2 = (float*)(base + off); off += nn_al((size_t)Q.nx * 4);
+        Q.nn1 = p.cnn1 ? p.cnn1 : L.take<int32_t>(Q.nx);
+        Q.nn2 = L.take<int32_t>(Q.nx);
+        Q.d1 = L.take<float>(Q.nx);
+        Q.d2 = L.take<float>(Q.nx);
         D.cnn1 = Q.nn1;
       }
       if (probs) probs->push_back(Q);
     }
     if (pd) pd->push_back(D);
   }
-  if (n_items) *n_items = item;
-  return off;
+  return w;
 }
 
 }  // namespace gims
@@ -450,8 +446,9 @@ extern "C" size_t gims_nn_workspace_bytes(const gims_nn_pair* pairs, int32_t n_p
   if (!pairs || n_pairs <= 0 || (flags & ~GIMS_NN_EXHAUSTIVE)) return 0;
   for (int i = 0; i < n_pairs; ++i)
     if (!nn_pair_ok(pairs[i], i, false)) return 0;
-  size_t zo, zb;
-  return nn_layout(pairs, n_pairs, flags, nullptr, nullptr, nullptr, &zo, &zb, nullptr);
+  WsLayout L(nullptr);
+  nn_layout(pairs, n_pairs, flags, L, nullptr, nullptr);
+  return L.bytes();
 }
 
 extern "C" int gims_nn_match(const gims_nn_pair* pairs, int32_t n_pairs, int32_t flags, void* work, size_t work_bytes, void* stream) {
@@ -464,19 +461,18 @@ extern "C" int gims_nn_match(const gims_nn_pair* pairs, int32_t n_pairs, int32_t
   GIMS_CHECK_ARG(work && ((uintptr_t)work & 255) == 0, "gims_nn_match: null or misaligned workspace");
   std::vector<NnProb> probs;
   std::vector<NnPairDev> pd;
-  size_t zo = 0, zb = 0;
-  int n_items = 0;
-  const size_t need = nn_layout(pairs, n_pairs, flags, (char*)work, &probs, &pd, &zo, &zb, &n_items);
-  GIMS_CHECK_ARG(work_bytes >= need, "gims_nn_match: workspace too small (%zu bytes given, %zu needed)", work_bytes, need);
+  WsLayout L(work);
+  const NnWs w = nn_layout(pairs, n_pairs, flags, L, &probs, &pd);
+  GIMS_CHECK_ARG(work_bytes >= L.bytes(), "gims_nn_match: workspace too small (%zu bytes given, %zu needed)", work_bytes, L.bytes());
   hipStream_t s = (hipStream_t)stream;
-  const int np = (int)probs.size();
-  NnProb* dprobs = (NnProb*)work;
-  NnPairDev* dpairs = (NnPairDev*)((char*)work + nn_al(sizeof(NnProb) * (size_t)np));
+  const int np = (int)probs.size(), n_items = w.n_items;
+  NnProb* dprobs = w.dprobs;
+  NnPairDev* dpairs = w.dpairs;
   int rc = upload_table(probs.data(), sizeof(NnProb) * (size_t)np, dprobs, s);
   if (rc != GIMS_OK) return rc;
   rc = upload_table(pd.data(), sizeof(NnPairDev) * (size_t)n_pairs, dpairs, s);
   if (rc != GIMS_OK) return rc;
-  GIMS_HIP(hipMemsetAsync((char*)work + zo, 0, zb, s));
+  GIMS_HIP(hipMemsetAsync(w.zero, 0, w.zero_bytes, s));
   int max_rows = 0, max_nx = 0, max_n0 = 0;
   for (int i = 0; i < n_pairs; ++i) {
     const int r = pairs[i].n0 + pairs[i].n1, m = pairs[i].mutual ? (pairs[i].n0 > pairs[i].n1 ? pairs[i].n0 : pairs[i].n1) : pairs[i].n0;

@@ -1111,7 +1111,6 @@ static int ot_cus() {
   if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, current_device()) != hipSuccess) n = 0;
   return n;
 }
-static thread_local bool tl_streamed_only = false;   // set for the duration of a *_ex call with GIMS_OT_STREAMED
 
 // Give-up bookkeeping, per device: a device counter of re-solved problems (bumped by the rescue kernels), mirrored into pinned host
 // memory by an asynchronous copy at the end of every on-chip call; the copy of call k is looked at by call k + 1.
@@ -1137,17 +1136,15 @@ static OtRescueState* ot_rescue_state() {
 
 // The on-chip kernel (2-D decomposition, sinkhorn2d.hip) is used whenever every problem has a geometry (n, m <= 4096) and the device has
 // the 256 CUs its workgroups need; GIMS_OT_RESIDENT=0 / GIMS_OT_STREAMED select the streamed kernels.
-static OtR2Plan ot_res2_choose(const gims_ot_problem* pr, int np, int iters) {
+static OtR2Plan ot_res2_choose(const gims_ot_problem* pr, int np, int iters, int flags) {
   OtR2Plan none{};
-  if (tl_streamed_only || !ot_env("GIMS_OT_RESIDENT", 1) || iters < 1 || ot_cus() < 256) return none;
+  if ((flags & GIMS_OT_STREAMED) || !ot_env("GIMS_OT_RESIDENT", 1) || iters < 1 || ot_cus() < 256) return none;
   // (no size gate: measured down to one problem of 128^2 the 2-D kernel's ~5.5 us per iteration beats the two launches per
   // iteration of the streamed kernels -- 0.60 vs 0.75 ms per 100 iterations)
   std::vector<OtR2Host> h(np);
   for (int i = 0; i < np; ++i) { h[i] = OtR2Host{}; h[i].n = pr[i].n; h[i].m = pr[i].m; }
   return ot_res2_plan(h.data(), np, iters);
 }
-
-static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 static void ot_launch_shape(const gims_ot_problem* pr, int np, int& threads, int& cpt, int& maxn, int& maxm) {
   maxn = 0; maxm = 0;
@@ -1168,100 +1165,96 @@ static int ot_G(int n, int np, int threads, int cpt) {
   int g = (n + rows - 1) / rows;
   return g < cap ? g : cap;
 }
-static size_t ot_problem_bytes(const gims_ot_problem& q, int G) {
-  size_t b = 0;
-  b += al256((size_t)G * (q.m + 1) * 4);          // partial
-  b += al256((size_t)G * q.m * 4) * 2;            // cbest val/idx
-  b += al256((size_t)q.n * 4) * 2;                // max0/idx0
-  b += al256((size_t)q.m * 4) * 2;                // max1/idx1
-  return b;
+static void ot_fill_common(const gims_ot_problem& q, float& norm, float& log_mu_bin, float& log_nu_bin) {
+  const float ms = (float)q.n, ns = (float)q.m;            // gmatcher.py:53 (m rows, n cols there)
+  norm = -logf(ms + ns);
+  log_mu_bin = logf(ns) + norm;                            // gmatcher.py:63
+  log_nu_bin = logf(ms) + norm;                            // gmatcher.py:64
 }
 
-}  // namespace gims
-
-extern "C" size_t gims_sinkhorn_workspace_bytes(const gims_ot_problem* pr, int32_t np) {
-  using namespace gims;
-  if (!pr || np <= 0) return 0;
-  int threads, cpt, maxn, maxm;
-  ot_launch_shape(pr, np, threads, cpt, maxn, maxm);
-  size_t b = al256(sizeof(OtDev) * (size_t)np);
-  for (int i = 0; i < np; ++i) b += ot_problem_bytes(pr[i], ot_G(pr[i].n, np, threads, cpt));
-  return b + al256(ot_res2_choose(pr, np, 1).bytes);    // on-chip-path buffers (0 when that path is off or does not fit)
+// The workspace of gims_sinkhorn_match and gims_sinkhorn_history (which leaves the selection buffers and the on-chip region unused): the OtDev
+// table, the buffers of the streamed kernels problem by problem, then the region of the on-chip kernel (0 bytes when that path is off or does
+// not fit).  recs == nullptr: sizing only (nothing of a problem but n and m is looked at); otherwise the records are filled, hist left null.
+struct OtWs { int threads, cpt, maxn, maxm, maxG; OtR2Plan plan2; char* onchip; };
+static OtWs ot_layout(const gims_ot_problem* pr, int np, int flags, WsLayout& L, OtDev* recs) {
+  OtWs w{};
+  ot_launch_shape(pr, np, w.threads, w.cpt, w.maxn, w.maxm);
+  L.take<OtDev>(np);
+  for (int i = 0; i < np; ++i) {
+    const gims_ot_problem& q = pr[i];
+    OtDev d{};
+    d.G = ot_G(q.n, np, w.threads, w.cpt);
+    w.maxG = d.G > w.maxG ? d.G : w.maxG;
+    d.partial = L.take<float>((size_t)d.G * (q.m + 1));
+    d.cbest_val = L.take<float>((size_t)d.G * q.m);
+    d.cbest_idx = L.take<int>((size_t)d.G * q.m);
+    d.max0 = L.take<float>(q.n);
+    d.idx0 = L.take<int>(q.n);
+    d.max1 = L.take<float>(q.m);
+    d.idx1 = L.take<int>(q.m);
+    if (!recs) continue;
+    d.z = q.scores; d.ld = q.ld; d.n = q.n; d.m = q.m;
+    d.u = q.uv; d.v = q.uv + q.n + 1; d.status = q.uv + q.n + 1 + q.m + 1;
+    d.matches0 = q.matches0; d.matches1 = q.matches1; d.mscores0 = q.mscores0; d.mscores1 = q.mscores1;
+    ot_fill_common(q, d.norm, d.log_mu_bin, d.log_nu_bin);
+    recs[i] = d;
+  }
+  w.plan2 = ot_res2_choose(pr, np, 1, flags);      // (the plan of one iteration is the plan of any number: the size does not depend on the count)
+  w.onchip = L.take<char>(w.plan2.bytes);
+  return w;
 }
 
-extern "C" int gims_sinkhorn_plan(const gims_ot_problem* pr, int32_t np, int32_t iters) {
-  using namespace gims;
+// one iteration of the streamed kernels: the row sweep (instance by column quads per thread), then the column reduction, which also writes
+// u and v into slot hist_slot of the history (-1: none)
+static void ot_streamed_iteration(const OtWs& w, const OtDev* dp, int np, float alpha, int rescue, int hist_slot, hipStream_t s) {
+  const dim3 gi(w.maxG, np), gc(cdiv(w.maxm + 1, 64), np), bt(w.threads);
+  if (w.cpt == 1) hipLaunchKernelGGL((ot_iter_kernel<1, 8>), gi, bt, 0, s, dp, alpha, rescue);
+  else if (w.cpt == 2) hipLaunchKernelGGL((ot_iter_kernel<2, 4>), gi, bt, 0, s, dp, alpha, rescue);
+  else if (w.cpt <= 4) hipLaunchKernelGGL((ot_iter_kernel<4, 2>), gi, bt, 0, s, dp, alpha, rescue);
+  else hipLaunchKernelGGL((ot_iter_kernel<8, 1>), gi, bt, 0, s, dp, alpha, rescue);      // 16 384 < m <= 32 768 (round 5: the graph build's limit)
+  hipLaunchKernelGGL(ot_colreduce_kernel, gc, dim3(1024), 0, s, dp, hist_slot, rescue);
+}
+
+static int ot_plan(const gims_ot_problem* pr, int np, int iters, int flags) {
   if (!pr || np <= 0) return 0;
-  const OtR2Plan p2 = ot_res2_choose(pr, np, iters);
+  const OtR2Plan p2 = ot_res2_choose(pr, np, iters, flags);
   return p2.ok ? p2.ngroups : 0;
 }
 
-extern "C" int gims_sinkhorn_match(const gims_ot_problem* pr, int32_t np, float alpha, int32_t iters,
-                                   float match_threshold, void* work, size_t work_bytes, void* stream) {
-  using namespace gims;
+static int ot_match(const gims_ot_problem* pr, int np, float alpha, int iters, float match_threshold, void* work, size_t work_bytes, int flags,
+                    hipStream_t s) {
   GIMS_CHECK_ARG(pr && np > 0 && work, "gims_sinkhorn_match: null / empty arguments");
   GIMS_CHECK_ARG(iters >= 0, "gims_sinkhorn_match: iters < 0");
-  GIMS_CHECK_ARG(work_bytes >= gims_sinkhorn_workspace_bytes(pr, np), "gims_sinkhorn_match: workspace too small (%zu < %zu)",
-                 work_bytes, gims_sinkhorn_workspace_bytes(pr, np));
-  hipStream_t s = (hipStream_t)stream;
-  int threads, cpt, maxn, maxm;
-  ot_launch_shape(pr, np, threads, cpt, maxn, maxm);
-  GIMS_CHECK_ARG(cpt <= 8, "gims_sinkhorn_match: m=%d too large (max 32768 columns: a thread of the streamed kernels owns at most 8 column quads)", maxm);
-  std::vector<OtDev> hprob(np);
-  char* base = (char*)work;
-  size_t off = al256(sizeof(OtDev) * (size_t)np);
-  int maxG = 0;
   for (int i = 0; i < np; ++i) {
     const gims_ot_problem& q = pr[i];
     GIMS_CHECK_ARG(q.n > 0 && q.m > 0 && q.scores && q.uv && q.matches0 && q.matches1 && q.mscores0 && q.mscores1,
                    "gims_sinkhorn_match: problem %d has empty shape or null pointer", i);
     GIMS_CHECK_ARG((q.ld % 4) == 0 && (((uintptr_t)q.scores) & 15) == 0, "gims_sinkhorn_match: scores must be 16-byte aligned with ld %% 4 == 0");
-    OtDev d{};
-    d.z = q.scores; d.ld = q.ld; d.n = q.n; d.m = q.m;
-    d.u = q.uv; d.v = q.uv + q.n + 1; d.status = q.uv + q.n + 1 + q.m + 1;
-    d.G = ot_G(q.n, np, threads, cpt);
-    maxG = d.G > maxG ? d.G : maxG;
-    d.partial = (float*)(base + off); off += al256((size_t)d.G * (q.m + 1) * 4);
-    d.cbest_val = (float*)(base + off); off += al256((size_t)d.G * q.m * 4);
-    d.cbest_idx = (int*)(base + off); off += al256((size_t)d.G * q.m * 4);
-    d.max0 = (float*)(base + off); off += al256((size_t)q.n * 4);
-    d.idx0 = (int*)(base + off); off += al256((size_t)q.n * 4);
-    d.max1 = (float*)(base + off); off += al256((size_t)q.m * 4);
-    d.idx1 = (int*)(base + off); off += al256((size_t)q.m * 4);
-    d.matches0 = q.matches0; d.matches1 = q.matches1; d.mscores0 = q.mscores0; d.mscores1 = q.mscores1;
-    const float ms = (float)q.n, ns = (float)q.m;            // gmatcher.py:53 (m rows, n cols there)
-    d.norm = -logf(ms + ns);
-    d.log_mu_bin = logf(ns) + d.norm;                        // gmatcher.py:63
-    d.log_nu_bin = logf(ms) + d.norm;                        // gmatcher.py:64
-    hprob[i] = d;
   }
+  std::vector<OtDev> hprob(np);
+  WsLayout L(work);
+  const OtWs w = ot_layout(pr, np, flags, L, hprob.data());
+  GIMS_CHECK_ARG(work_bytes >= L.bytes(), "gims_sinkhorn_match: workspace too small (%zu < %zu)", work_bytes, L.bytes());
+  GIMS_CHECK_ARG(w.cpt <= 8, "gims_sinkhorn_match: m=%d too large (max 32768 columns: a thread of the streamed kernels owns at most 8 column quads)", w.maxm);
+  const int threads = w.threads, cpt = w.cpt, maxn = w.maxn, maxm = w.maxm;
   {
     const int rc = upload_table(hprob.data(), sizeof(OtDev) * (size_t)np, work, s);   // by kernel arguments: no sync
     if (rc != GIMS_OK) return rc;
   }
   const OtDev* dp = (const OtDev*)work;
-  const OtR2Plan plan2 = ot_res2_choose(pr, np, iters);
+  const bool onchip = w.plan2.ok && iters >= 1;
   // the 2-D on-chip kernel forms the start potentials itself (GIMS_OT_R2_INIT=0: the separate sweep, for cross-checks)
-  const int init_inside = plan2.ok && ot_env("GIMS_OT_R2_INIT", 1) ? 1 : 0;
+  const int init_inside = onchip && ot_env("GIMS_OT_R2_INIT", 1) ? 1 : 0;
   if (init_inside) hipLaunchKernelGGL(ot_status0_kernel, dim3(cdiv(np, 256)), dim3(256), 0, s, dp, np);
   else hipLaunchKernelGGL(ot_init_kernel, dim3(cdiv(maxn, 4), np), dim3(256), 0, s, dp, alpha, iters == 0 ? 1 : 0, 0);
-  dim3 gi(maxG, np), gc(cdiv(maxm + 1, 64), np);
-  auto streamed_iterations = [&](int rescue) {
-    for (int it = 0; it < iters; ++it) {
-      if (cpt == 1) hipLaunchKernelGGL((ot_iter_kernel<1, 8>), gi, dim3(threads), 0, s, dp, alpha, rescue);
-      else if (cpt == 2) hipLaunchKernelGGL((ot_iter_kernel<2, 4>), gi, dim3(threads), 0, s, dp, alpha, rescue);
-      else if (cpt <= 4) hipLaunchKernelGGL((ot_iter_kernel<4, 2>), gi, dim3(threads), 0, s, dp, alpha, rescue);
-      else hipLaunchKernelGGL((ot_iter_kernel<8, 1>), gi, dim3(threads), 0, s, dp, alpha, rescue);      // 16 384 < m <= 32 768 (round 5: the graph build's limit)
-      hipLaunchKernelGGL(ot_colreduce_kernel, gc, dim3(1024), 0, s, dp, -1, rescue);
-    }
-  };
-  if (plan2.ok) {     // whole iteration loop on chip, 2-D decomposition (sinkhorn2d.hip)
+  const dim3 gi(w.maxG, np);
+  if (onchip) {     // whole iteration loop on chip, 2-D decomposition (sinkhorn2d.hip)
     std::vector<OtR2Host> h2(np);
     for (int i = 0; i < np; ++i) {
       const OtDev& d = hprob[i];
       h2[i] = OtR2Host{d.z, d.ld, d.n, d.m, d.u, d.v, d.status, d.norm, d.log_mu_bin, d.log_nu_bin};
     }
-    const int rc = ot_res2_run(plan2, h2.data(), np, alpha, iters, init_inside, base + off, s);
+    const int rc = ot_res2_run(w.plan2, h2.data(), np, alpha, iters, init_inside, w.onchip, s);
     if (rc != GIMS_OK) return rc;
     const int force_fail = ot_env("GIMS_OT_FORCE_FAIL", 0);       // test hook: pretend every on-chip solve timed out
     if (force_fail) hipLaunchKernelGGL(ot_poison_kernel, dim3(np), dim3(256), 0, s, dp);
@@ -1279,7 +1272,7 @@ extern "C" int gims_sinkhorn_match(const gims_ot_problem* pr, int32_t np, float 
     if (marginal) {
       hipLaunchKernelGGL(ot_rescue_begin_kernel, dim3(cdiv(np, 256)), dim3(256), 0, s, dp, np, rs->d_count);
       hipLaunchKernelGGL(ot_init_kernel, dim3(cdiv(maxn, 4), np), dim3(256), 0, s, dp, alpha, 0, 1);
-      streamed_iterations(1);
+      for (int it = 0; it < iters; ++it) ot_streamed_iteration(w, dp, np, alpha, 1, -1, s);
       hipLaunchKernelGGL(ot_rescue_end_kernel, dim3(cdiv(np, 256)), dim3(256), 0, s, dp, np);
     }
     // last resort (and the only rescue while the device is not marginal): an empty launch unless a status word still reads 2
@@ -1289,7 +1282,7 @@ extern "C" int gims_sinkhorn_match(const gims_ot_problem* pr, int32_t np, float 
       GIMS_HIP(hipEventRecord(rs->ev, s));
     }
   } else {
-    streamed_iterations(0);
+    for (int it = 0; it < iters; ++it) ot_streamed_iteration(w, dp, np, alpha, 0, -1, s);
   }
   if (cpt == 1) hipLaunchKernelGGL(ot_select_kernel<1>, gi, dim3(threads), 0, s, dp);
   else if (cpt == 2) hipLaunchKernelGGL((ot_select_kernel<2, 4>), gi, dim3(threads), 0, s, dp);      // (four-row slabs: eight staged 364 B of the row pieces in scratch)
@@ -1303,6 +1296,28 @@ extern "C" int gims_sinkhorn_match(const gims_ot_problem* pr, int32_t np, float 
   return GIMS_OK;
 }
 
+}  // namespace gims
+
+extern "C" size_t gims_sinkhorn_workspace_bytes(const gims_ot_problem* pr, int32_t np) {
+  using namespace gims;
+  if (!pr || np <= 0) return 0;
+  WsLayout L(nullptr);
+  ot_layout(pr, np, 0, L, nullptr);
+  return L.bytes();
+}
+
+extern "C" int gims_sinkhorn_plan(const gims_ot_problem* pr, int32_t np, int32_t iters) { return gims::ot_plan(pr, np, iters, 0); }
+extern "C" int gims_sinkhorn_plan_ex(const gims_ot_problem* pr, int32_t np, int32_t iters, int32_t flags) { return gims::ot_plan(pr, np, iters, flags); }
+
+extern "C" int gims_sinkhorn_match(const gims_ot_problem* pr, int32_t np, float alpha, int32_t iters,
+                                   float match_threshold, void* work, size_t work_bytes, void* stream) {
+  return gims::ot_match(pr, np, alpha, iters, match_threshold, work, work_bytes, 0, (hipStream_t)stream);
+}
+extern "C" int gims_sinkhorn_match_ex(const gims_ot_problem* pr, int32_t np, float alpha, int32_t iters, float match_threshold, void* work,
+                                      size_t work_bytes, int32_t flags, void* stream) {
+  return gims::ot_match(pr, np, alpha, iters, match_threshold, work, work_bytes, flags, (hipStream_t)stream);
+}
+
 extern "C" int64_t gims_sinkhorn_rescues(void) {
   using namespace gims;
   OtRescueState* rs = ot_rescue_state();
@@ -1312,21 +1327,6 @@ extern "C" int64_t gims_sinkhorn_rescues(void) {
     return -1;
   }
   return n;
-}
-
-extern "C" int gims_sinkhorn_plan_ex(const gims_ot_problem* pr, int32_t np, int32_t iters, int32_t flags) {
-  gims::tl_streamed_only = (flags & GIMS_OT_STREAMED) != 0;
-  const int k = gims_sinkhorn_plan(pr, np, iters);
-  gims::tl_streamed_only = false;
-  return k;
-}
-
-extern "C" int gims_sinkhorn_match_ex(const gims_ot_problem* pr, int32_t np, float alpha, int32_t iters, float match_threshold, void* work,
-                                      size_t work_bytes, int32_t flags, void* stream) {
-  gims::tl_streamed_only = (flags & GIMS_OT_STREAMED) != 0;
-  const int rc = gims_sinkhorn_match(pr, np, alpha, iters, match_threshold, work, work_bytes, stream);
-  gims::tl_streamed_only = false;
-  return rc;
 }
 
 extern "C" int gims_ot_matrix(const float* scores, int64_t ld, int32_t n, int32_t m, float alpha, const float* uv,
@@ -1352,16 +1352,6 @@ extern "C" int gims_train_loss(const gims_loss_pair* dev_pairs, int32_t n_pairs,
 }
 
 // ---- recorded forward solve + backward sweep (forward_train gradients w.r.t. scores and bin_score)
-namespace gims {
-static int ot_fill_common(const gims_ot_problem& q, float& norm, float& log_mu_bin, float& log_nu_bin) {
-  const float ms = (float)q.n, ns = (float)q.m;
-  norm = -logf(ms + ns);
-  log_mu_bin = logf(ns) + norm;
-  log_nu_bin = logf(ms) + norm;
-  return 0;
-}
-}  // namespace gims
-
 extern "C" size_t gims_sinkhorn_history_floats(int32_t n, int32_t m, int32_t iters) {
   return (size_t)(iters + 1) * (size_t)(n + m + 2);
 }
@@ -1370,31 +1360,18 @@ extern "C" int gims_sinkhorn_history(const gims_ot_problem* pr, int32_t np, floa
                                      size_t work_bytes, void* stream) {
   using namespace gims;
   GIMS_CHECK_ARG(pr && np > 0 && work && h_hist && iters >= 1, "gims_sinkhorn_history: null / empty arguments");
-  GIMS_CHECK_ARG(work_bytes >= gims_sinkhorn_workspace_bytes(pr, np), "gims_sinkhorn_history: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  int threads, cpt, maxn, maxm;
-  ot_launch_shape(pr, np, threads, cpt, maxn, maxm);
-  GIMS_CHECK_ARG(cpt <= 4, "gims_sinkhorn_history: m=%d too large (max 16384)", maxm);
-  std::vector<OtDev> hprob(np);
-  char* base = (char*)work;
-  size_t off = al256(sizeof(OtDev) * (size_t)np);
-  int maxG = 0;
   for (int i = 0; i < np; ++i) {
     const gims_ot_problem& q = pr[i];
     GIMS_CHECK_ARG(q.n > 0 && q.m > 0 && q.scores && q.uv && h_hist[i], "gims_sinkhorn_history: problem %d has empty shape or null pointer", i);
     GIMS_CHECK_ARG((q.ld % 4) == 0 && (((uintptr_t)q.scores) & 15) == 0, "gims_sinkhorn_history: scores must be 16-byte aligned with ld %% 4 == 0");
-    OtDev d{};
-    d.z = q.scores; d.ld = q.ld; d.n = q.n; d.m = q.m;
-    d.u = q.uv; d.v = q.uv + q.n + 1; d.status = q.uv + q.n + 1 + q.m + 1;
-    d.G = ot_G(q.n, np, threads, cpt);
-    maxG = d.G > maxG ? d.G : maxG;
-    d.partial = (float*)(base + off); off += al256((size_t)d.G * (q.m + 1) * 4);
-    d.cbest_val = nullptr; d.cbest_idx = nullptr; d.max0 = nullptr; d.idx0 = nullptr; d.max1 = nullptr; d.idx1 = nullptr;
-    d.matches0 = nullptr; d.matches1 = nullptr; d.mscores0 = nullptr; d.mscores1 = nullptr;
-    ot_fill_common(q, d.norm, d.log_mu_bin, d.log_nu_bin);
-    d.hist = h_hist[i];
-    hprob[i] = d;
   }
+  std::vector<OtDev> hprob(np);
+  WsLayout L(work);
+  const OtWs w = ot_layout(pr, np, 0, L, hprob.data());      // the layout of gims_sinkhorn_match: the caller sized the buffer with its query
+  GIMS_CHECK_ARG(work_bytes >= L.bytes(), "gims_sinkhorn_history: workspace too small (%zu < %zu)", work_bytes, L.bytes());
+  GIMS_CHECK_ARG(w.cpt <= 4, "gims_sinkhorn_history: m=%d too large (max 16384)", w.maxm);
+  for (int i = 0; i < np; ++i) hprob[i].hist = h_hist[i];
+  hipStream_t s = (hipStream_t)stream;
   const int rc = upload_table(hprob.data(), sizeof(OtDev) * (size_t)np, work, s);
   if (rc != GIMS_OK) return rc;
   const OtDev* dp = (const OtDev*)work;
@@ -1402,71 +1379,68 @@ extern "C" int gims_sinkhorn_history(const gims_ot_problem* pr, int32_t np, floa
   // and took it out again: its potentials are consistent with the K it ROUNDED at the last derivation, the reverse sweep recomputes
   // exp(Z + u_k + v_k-1) afresh, and that 1e-5 inconsistency per iteration is amplified by the cancellation in d loss / d bin_score:
   // 7.9e-2 on the 2 x 2048 fixture against a bar of 2e-2; every other gradient was unaffected.)
-  hipLaunchKernelGGL(ot_init_kernel, dim3(cdiv(maxn, 4), np), dim3(256), 0, s, dp, alpha, 0, 0);
-  dim3 gi(maxG, np), gc(cdiv(maxm + 1, 64), np);
-  for (int it = 0; it < iters; ++it) {        // the streamed kernels, one iteration at a time
-    if (cpt == 1) hipLaunchKernelGGL((ot_iter_kernel<1, 8>), gi, dim3(threads), 0, s, dp, alpha, 0);
-    else if (cpt == 2) hipLaunchKernelGGL((ot_iter_kernel<2, 4>), gi, dim3(threads), 0, s, dp, alpha, 0);
-    else hipLaunchKernelGGL((ot_iter_kernel<4, 2>), gi, dim3(threads), 0, s, dp, alpha, 0);
-    hipLaunchKernelGGL(ot_colreduce_kernel, gc, dim3(1024), 0, s, dp, it + 1, 0);      // writes u, v of this iteration into the history itself
-  }
+  hipLaunchKernelGGL(ot_init_kernel, dim3(cdiv(w.maxn, 4), np), dim3(256), 0, s, dp, alpha, 0, 0);
+  // the streamed kernels, one iteration at a time; the column reduction writes u, v of this iteration into the history itself
+  for (int it = 0; it < iters; ++it) ot_streamed_iteration(w, dp, np, alpha, 0, it + 1, s);
   GIMS_LAUNCH_CHECK();
   return GIMS_OK;
 }
 
-// low-rank sweep buffers of one problem: gu_rec, gv_rec, P, Q, T (sized for OT_BWD_MAX_ITERS iterations: the workspace query does
-// not know the iteration count; more iterations fall back to the in-place sweep)
+namespace gims {
+// The workspace of gims_sinkhorn_backward: the OtBwd table, then per problem the sweep vectors and the low-rank sweep's gu_rec, gv_rec, P, Q, T.
+// The low-rank buffers always have the capacity of OT_BWD_MAX_ITERS iterations (the workspace query does not know the iteration count; a
+// shorter solve uses their front, a longer one falls back to the in-place sweep and leaves them alone).  recs == nullptr: sizing only.
 constexpr int OT_BWD_MAX_ITERS = 128;
-static size_t ot_bwd_lowrank_bytes(int n, int m, int iters) {
-  const size_t ldt = ((size_t)m + 1 + 3) & ~(size_t)3;
-  return gims::al256((size_t)(iters + 1) * (n + 1) * 4) + gims::al256((size_t)(iters + 1) * (m + 1) * 4) + gims::al256((size_t)(n + 1) * 2 * iters * 4) +
-         gims::al256((size_t)(m + 1) * 2 * iters * 4) + gims::al256((size_t)(n + 1) * ldt * 4);
+static void ot_bwd_layout(const gims_ot_problem* pr, int np, WsLayout& L, OtBwd* recs) {
+  constexpr size_t cap = OT_BWD_MAX_ITERS;
+  L.take<OtBwd>(np);
+  for (int i = 0; i < np; ++i) {
+    const size_t n1 = (size_t)pr[i].n + 1, m1 = (size_t)pr[i].m + 1, ldt = (m1 + 3) & ~(size_t)3;
+    OtBwd b{};
+    b.gu = L.take<float>(n1);
+    b.gv = L.take<float>(m1);
+    b.gv2 = L.take<float>(m1);
+    b.colpart = L.take<float>((size_t)((pr[i].n + BW_ROWS) / BW_ROWS) * m1);
+    b.gu_rec = L.take<float>((cap + 1) * n1);
+    b.gv_rec = L.take<float>((cap + 1) * m1);
+    b.fp = L.take<float>(n1 * 2 * cap);
+    b.fq = L.take<float>(m1 * 2 * cap);
+    b.tmat = L.take<float>(n1 * ldt);
+    b.ldt = (int64_t)ldt;
+    if (recs) recs[i] = b;
+  }
 }
+}  // namespace gims
 
 extern "C" size_t gims_sinkhorn_backward_workspace_bytes(const gims_ot_problem* pr, int32_t np) {
   using namespace gims;
   if (!pr || np <= 0) return 0;
-  size_t b = al256(sizeof(OtBwd) * (size_t)np);
-  for (int i = 0; i < np; ++i)
-    b += al256((size_t)(pr[i].n + 1) * 4) + 2 * al256((size_t)(pr[i].m + 1) * 4) + al256((size_t)((pr[i].n + BW_ROWS) / BW_ROWS) * (size_t)(pr[i].m + 1) * 4) +
-         ot_bwd_lowrank_bytes(pr[i].n, pr[i].m, OT_BWD_MAX_ITERS);
-  return b;
+  WsLayout L(nullptr);
+  ot_bwd_layout(pr, np, L, nullptr);
+  return L.bytes();
 }
 
 extern "C" int gims_sinkhorn_backward(const gims_ot_problem* pr, int32_t np, float alpha, int32_t iters, const float* const* h_hist,
                                       float* const* h_dz, float* dalpha /* device [np] */, void* work, size_t work_bytes, void* stream) {
   using namespace gims;
   GIMS_CHECK_ARG(pr && np > 0 && h_hist && h_dz && dalpha && work && iters >= 1, "gims_sinkhorn_backward: null / empty arguments");
-  GIMS_CHECK_ARG(work_bytes >= gims_sinkhorn_backward_workspace_bytes(pr, np), "gims_sinkhorn_backward: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
+  for (int i = 0; i < np; ++i)
+    GIMS_CHECK_ARG(pr[i].n > 0 && pr[i].m > 0 && pr[i].scores && h_hist[i] && h_dz[i], "gims_sinkhorn_backward: problem %d has empty shape or null pointer", i);
   std::vector<OtBwd> hp(np);
-  char* base = (char*)work;
-  size_t off = al256(sizeof(OtBwd) * (size_t)np);
+  WsLayout L(work);
+  ot_bwd_layout(pr, np, L, hp.data());
+  GIMS_CHECK_ARG(work_bytes >= L.bytes(), "gims_sinkhorn_backward: workspace too small (%zu < %zu)", work_bytes, L.bytes());
+  hipStream_t s = (hipStream_t)stream;
   int maxn = 0, maxm = 0;
   for (int i = 0; i < np; ++i) {
     const gims_ot_problem& q = pr[i];
-    GIMS_CHECK_ARG(q.n > 0 && q.m > 0 && q.scores && h_hist[i] && h_dz[i], "gims_sinkhorn_backward: problem %d has empty shape or null pointer", i);
-    OtBwd b{};
+    OtBwd& b = hp[i];
     b.z = q.scores; b.ld = q.ld; b.n = q.n; b.m = q.m;
     b.hist = h_hist[i]; b.hstride = q.n + q.m + 2;
     b.dz = h_dz[i];
-    b.gu = (float*)(base + off); off += al256((size_t)(q.n + 1) * 4);
-    b.gv = (float*)(base + off); off += al256((size_t)(q.m + 1) * 4);
-    b.gv2 = (float*)(base + off); off += al256((size_t)(q.m + 1) * 4);
-    b.colpart = (float*)(base + off); off += al256((size_t)((q.n + BW_ROWS) / BW_ROWS) * (size_t)(q.m + 1) * 4);
-    {
-      const int it = iters <= OT_BWD_MAX_ITERS ? iters : 0;          // 0: the low-rank buffers are not used
-      b.iters = iters;
-      b.ldt = ((int64_t)q.m + 1 + 3) & ~(int64_t)3;
-      b.gu_rec = (float*)(base + off); off += al256((size_t)(it + 1) * (q.n + 1) * 4);
-      b.gv_rec = (float*)(base + off); off += al256((size_t)(it + 1) * (q.m + 1) * 4);
-      b.fp = (float*)(base + off); off += al256((size_t)(q.n + 1) * 2 * it * 4);
-      b.fq = (float*)(base + off); off += al256((size_t)(q.m + 1) * 2 * it * 4);
-      b.tmat = (float*)(base + off); off += al256((size_t)(q.n + 1) * b.ldt * 4);
-    }
+    b.iters = iters;
     b.dalpha = dalpha + i;
     ot_fill_common(q, b.norm, b.log_mu_bin, b.log_nu_bin);
-    hp[i] = b;
     maxn = q.n > maxn ? q.n : maxn; maxm = q.m > maxm ? q.m : maxm;
   }
   const int rc = upload_table(hp.data(), sizeof(OtBwd) * (size_t)np, work, s);

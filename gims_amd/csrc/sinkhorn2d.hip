@@ -836,7 +836,6 @@ static int r2_env(const char* name, int dflt) {
   const char* s = getenv(name);
   return s ? atoi(s) : dflt;
 }
-static inline size_t r2_al(size_t x) { return (x + 255) & ~(size_t)255; }
 static inline int r2_up4(int x) { return (x + 3) & ~3; }
 
 // Geometry classes.  The decomposition of a problem -- nx row groups x nc column blocks, hence every summation order inside the solve -- is a
@@ -863,6 +862,41 @@ static inline int r2_class_key(const OtR2Host& h) {
   return r2_geom(h.n, h.m, nx, nc) ? nx * 64 + nc : -1;
 }
 
+// The workspace of one geometry class; recs == nullptr (with a null base): sizing only.  plan_class sizes with it, run_class carves with it.
+struct R2Ws { OtR2Dev* dprob; int* dplace; size_t ex0, ex1, rf1; };     // [ex0, ex1): exchange buffers (start as 0xFF); [ex1, rf1): flags (start as 0)
+static R2Ws r2_layout(const OtR2Plan& P, const OtR2Host* pr, int np, WsLayout& L, OtR2Dev* recs) {
+  R2Ws w{};
+  w.dprob = L.take<OtR2Dev>(np);
+  w.dplace = L.take<int>(64);
+  w.ex0 = L.bytes();
+  for (int i = 0; i < np; ++i) {
+    const int rb = cdiv(pr[i].n, P.nx), rbf = r2_up4(cdiv(rb + 1, P.nc)), rbs = P.nc * rbf;
+    float* rpart = L.take<float>((size_t)P.nx * P.nc * rbs);
+    float* fbuf = L.take<float>((size_t)P.nx * 2 * rbs);
+    float* cpart = L.take<float>((size_t)2 * P.nx * P.nc * R2_CSEG);
+    float* mpart = L.take<float>((size_t)P.nx * P.nc * rbs);
+    if (!recs) continue;
+    const OtR2Host& d = pr[i];
+    OtR2Dev q{};
+    q.z = d.z; q.ld = d.ld; q.n = d.n; q.m = d.m; q.u = d.u; q.v = d.v; q.status = d.status;
+    q.norm = d.norm; q.log_mu_bin = d.log_mu_bin; q.log_nu_bin = d.log_nu_bin;
+    q.mu = (float)exp((double)d.norm); q.mu_bin = (float)exp((double)d.log_mu_bin); q.nu_bin = (float)exp((double)d.log_nu_bin);
+    q.nx = P.nx; q.nc = P.nc; q.rb = rb; q.cb = r2_up4(cdiv(d.m, P.nc)); q.rbf = rbf; q.rbs = rbs;
+    q.rpart = rpart; q.fbuf = fbuf; q.cpart = cpart; q.mpart = mpart;
+    q.placement = w.dplace;
+    recs[i] = q;
+  }
+  w.ex1 = L.bytes();
+  // the re-derivation flags of all problems (behind the exchange buffers): a fixed capacity -- the caller's workspace query does not know the iteration count
+  for (int i = 0; i < np; ++i) {
+    int* rflag = L.take<int>(R2_FLAG_ITERS + 8);
+    if (recs) recs[i].rflag = rflag;
+  }
+  w.rf1 = L.bytes();
+  L.take<OtR2Block>((size_t)512 * P.ngroups);      // reserved: the per-group block table the kernel no longer reads (kept so that the size query is unchanged)
+  return w;
+}
+
 static OtR2Plan plan_class(const OtR2Host* pr, int np, int iters) {
   OtR2Plan P{};
   if (iters < 1 || np < 1) return P;
@@ -879,15 +913,13 @@ static OtR2Plan plan_class(const OtR2Host* pr, int np, int iters) {
   P.ppg = P.ppg < np ? P.ppg : np;
   P.ngroups = cdiv(np, P.ppg);
   if (P.ngroups > 64) return P;
-  size_t b = r2_al(sizeof(OtR2Dev) * (size_t)np) + (size_t)P.ngroups * r2_al(sizeof(OtR2Block) * 512) + 256;
   for (int i = 0; i < np; ++i) {
     const int rb = cdiv(pr[i].n, nx);
-    const int rbf = r2_up4(cdiv(rb + 1, nc)), rbs = nc * rbf;
-    if (rbf > R2_FOLD || rb > r2_rbmax() || r2_up4(cdiv(pr[i].m, nc)) > 128) return P;
-    b += 2 * r2_al((size_t)nx * nc * rbs * 4) + r2_al((size_t)nx * 2 * rbs * 4) + r2_al((size_t)2 * nx * nc * R2_CSEG * 4);
-    b += r2_al((size_t)(R2_FLAG_ITERS + 8) * 4);                       // rflag: a fixed capacity -- the caller's workspace query does not know the iteration count
+    if (r2_up4(cdiv(rb + 1, nc)) > R2_FOLD || rb > r2_rbmax() || r2_up4(cdiv(pr[i].m, nc)) > 128) return P;
   }
-  P.bytes = b;
+  WsLayout L(nullptr);
+  r2_layout(P, pr, np, L, nullptr);
+  P.bytes = L.bytes();
   P.ok = true;
   return P;
 }
@@ -918,7 +950,7 @@ OtR2Plan ot_res2_plan(const OtR2Host* pr, int np, int iters) {
     P.nc = c.nc > P.nc ? c.nc : P.nc;
     P.ppg = c.ppg > P.ppg ? c.ppg : P.ppg;
     P.ngroups += c.ngroups;
-    P.bytes += r2_al(c.bytes);
+    P.bytes += al256(c.bytes);
   }
   return P;
 }
@@ -946,50 +978,27 @@ static R2State* r2_state(const void* kernel, int threads, int blocks, size_t lds
 }
 
 int ot_res2_run(const OtR2Plan&, const OtR2Host* hp, int np, float alpha, int iters, int init_inside, char* base, hipStream_t s) {
-  size_t off = 0;
+  WsLayout L(base);
   for (const std::vector<int>& cls : r2_classes(hp, np)) {
     std::vector<OtR2Host> sub;
     for (int i : cls) sub.push_back(hp[i]);
     const OtR2Plan c = plan_class(sub.data(), (int)sub.size(), iters);
     if (!c.ok) { set_error("ot_res2_run: a geometry class has no plan"); return GIMS_EINVAL; }
-    const int rc = run_class(c, sub.data(), (int)sub.size(), alpha, iters, init_inside, base + off, s);
+    const int rc = run_class(c, sub.data(), (int)sub.size(), alpha, iters, init_inside, L.take<char>(c.bytes), s);
     if (rc != GIMS_OK) return rc;
-    off += r2_al(c.bytes);
   }
   return GIMS_OK;
 }
 
 static int run_class(const OtR2Plan& P, const OtR2Host* hp, int np, float alpha, int iters, int init_inside, char* base, hipStream_t s) {
-  size_t off = 0;
-  OtR2Dev* dprob = (OtR2Dev*)(base + off); off += r2_al(sizeof(OtR2Dev) * (size_t)np);
-  int* dplace = (int*)(base + off); off += 256;
   std::vector<OtR2Dev> hd(np);
-  const size_t ex0 = off;
-  for (int i = 0; i < np; ++i) {
-    const OtR2Host& d = hp[i];
-    OtR2Dev q{};
-    q.z = d.z; q.ld = d.ld; q.n = d.n; q.m = d.m; q.u = d.u; q.v = d.v; q.status = d.status;
-    q.norm = d.norm; q.log_mu_bin = d.log_mu_bin; q.log_nu_bin = d.log_nu_bin;
-    q.mu = (float)exp((double)d.norm); q.mu_bin = (float)exp((double)d.log_mu_bin); q.nu_bin = (float)exp((double)d.log_nu_bin);
-    q.nx = P.nx; q.nc = P.nc;
-    q.rb = cdiv(d.n, P.nx);
-    q.cb = r2_up4(cdiv(d.m, P.nc));
-    q.rbf = r2_up4(cdiv(q.rb + 1, P.nc));
-    q.rbs = P.nc * q.rbf;
-    q.rpart = (float*)(base + off); off += r2_al((size_t)P.nx * P.nc * q.rbs * 4);
-    q.fbuf = (float*)(base + off); off += r2_al((size_t)P.nx * 2 * q.rbs * 4);
-    q.cpart = (float*)(base + off); off += r2_al((size_t)2 * P.nx * P.nc * R2_CSEG * 4);
-    q.mpart = (float*)(base + off); off += r2_al((size_t)P.nx * P.nc * q.rbs * 4);
-    q.placement = dplace;
-    hd[i] = q;
-  }
+  WsLayout L(base);
+  const R2Ws w = r2_layout(P, hp, np, L, hd.data());
+  OtR2Dev* const dprob = w.dprob;
+  int* const dplace = w.dplace;
   // exchange buffers start with every sign bit set: iteration 0 waits for sign 0
-  GIMS_HIP(hipMemsetAsync(base + ex0, 0xFF, off - ex0, s));
-  {   // the re-derivation flags of all problems, zeroed (behind the exchange buffers)
-    const size_t rf0 = off, rfb = r2_al((size_t)(R2_FLAG_ITERS + 8) * 4);
-    for (int i = 0; i < np; ++i) { hd[i].rflag = (int*)(base + off); off += rfb; }
-    GIMS_HIP(hipMemsetAsync(base + rf0, 0, off - rf0, s));
-  }
+  GIMS_HIP(hipMemsetAsync(base + w.ex0, 0xFF, w.ex1 - w.ex0, s));
+  GIMS_HIP(hipMemsetAsync(base + w.ex1, 0, w.rf1 - w.ex1, s));
   GIMS_HIP(hipMemsetAsync(dplace, 0, 256, s));
   int rc = upload_table(hd.data(), sizeof(OtR2Dev) * (size_t)np, dprob, s);
   if (rc != GIMS_OK) return rc;

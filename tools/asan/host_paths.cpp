@@ -9,7 +9,17 @@
 #include <string.h>
 #include <vector>
 
+#include <hip/hip_runtime.h>
+
 #include "../../include/gims_hip.h"
+
+namespace gims {   // the internal interface of sinkhorn2d.hip as csrc/common.h declares it: the on-chip Sinkhorn layout is chosen only on a
+// device with 256 compute units, so its carving mode is reached here directly
+struct OtR2Host { const float* z; int64_t ld; int n, m; float* u; float* v; float* status; float norm, log_mu_bin, log_nu_bin; };
+struct OtR2Plan { bool ok; int nx, nc, ppg, ngroups; size_t bytes; };
+OtR2Plan ot_res2_plan(const OtR2Host* pr, int np, int iters);
+int ot_res2_run(const OtR2Plan& P, const OtR2Host* hp, int np, float alpha, int iters, int init_inside, char* base, hipStream_t s);
+}  // namespace gims
 
 static int checks = 0;
 #define EXPECT(cond) do { ++checks; if (!(cond)) { fprintf(stderr, "FAILED %s:%d: %s  (last error: %s)\n", __FILE__, __LINE__, #cond, gims_last_error()); exit(1); } } while (0)
@@ -238,6 +248,86 @@ int main() {
     const int rc0 = gims_patch_affine(nullptr, nullptr, 0, nullptr, nullptr, nullptr);
     EXPECT(rc0 == GIMS_OK || rc0 == GIMS_EINVAL);
     EXPECT(gims_patch_affine(nullptr, nullptr, 5, nullptr, nullptr, nullptr) == GIMS_EINVAL);
+  }
+  {   // ---- workspace layouts (csrc/common.h: WsLayout): every layout routine in sizing mode (the queries, over ragged lists on and around a
+      // 256-byte boundary) and in carving mode (the entry points with fake non-null pointers and an adequate work_bytes: every pointer is
+      // computed, then the call fails cleanly in the runtime -- no device here), and the refusal of a workspace one byte short
+    const int shp[5][2] = {{1, 2}, {63, 65}, {64, 64}, {257, 4097}, {700, 650}};
+    char* const work = (char*)0x10000000;
+    auto fake = [](uintptr_t v) { return (void*)v; };
+    auto carved = [](int rc) { return rc == GIMS_EHIP || rc == GIMS_OK; };
+    std::vector<gims_ot_problem> ot(5);
+    std::vector<gims_eval_pair> ev(5);
+    std::vector<gims_label_pair> lb(5);
+    std::vector<gims_nn_pair> nn(5);
+    std::vector<gims_agc_image> gi(5);
+    std::vector<gims_agc_params> gp(5);
+    std::vector<float*> hist(5, (float*)fake(0x70000)), dz(5, (float*)fake(0x80000));
+    for (int i = 0; i < 5; ++i) {
+      const int a = shp[i][0], b = shp[i][1];
+      memset(&ot[i], 0, sizeof(ot[i])); memset(&ev[i], 0, sizeof(ev[i])); memset(&nn[i], 0, sizeof(nn[i])); memset(&gi[i], 0, sizeof(gi[i]));
+      ot[i].scores = (const float*)fake(0x1000); ot[i].ld = (b + 3) / 4 * 4; ot[i].n = a; ot[i].m = b;
+      ot[i].matches0 = (int64_t*)fake(0x2000); ot[i].matches1 = (int64_t*)fake(0x3000); ot[i].mscores0 = (float*)fake(0x4000);
+      ot[i].mscores1 = (float*)fake(0x5000); ot[i].uv = (float*)fake(0x6000);
+      ev[i].kpts0 = (const float*)fake(0x1000); ev[i].kpts1 = (const float*)fake(0x2000); ev[i].matches0 = (const int64_t*)fake(0x3000);
+      ev[i].mscores0 = (const float*)fake(0x4000); ev[i].n0 = a; ev[i].n1 = b; ev[i].height = 480; ev[i].width = 640;
+      ev[i].gt0 = (int32_t*)fake(0x5000); ev[i].inlier = (uint8_t*)fake(0x6000); ev[i].record = (float*)fake(0x7000); ev[i].homographies = (float*)fake(0x8000);
+      lb[i].kpts0 = (const float*)fake(0x1000); lb[i].kpts1 = (const float*)fake(0x2000); lb[i].n0 = a; lb[i].n1 = b;
+      nn[i].a = (const float*)fake(0x1000); nn[i].b = (const float*)fake(0x2000); nn[i].lda = nn[i].ldb = 64; nn[i].n0 = a + 1; nn[i].n1 = b; nn[i].d = 64;
+      nn[i].mutual = i & 1; nn[i].threshold = 0.8f;
+      nn[i].nn1 = nn[i].nn2 = (int32_t*)fake(0x3000); nn[i].d1 = nn[i].d2 = nn[i].ratio = nn[i].scores0 = (float*)fake(0x4000);
+      nn[i].match = (uint8_t*)fake(0x5000); nn[i].matches0 = nn[i].matches1 = (int64_t*)fake(0x6000); nn[i].info = (int32_t*)fake(0x7000);
+      gi[i].kpts = (const float*)fake(0x1000); gi[i].desc = (const float*)fake(0x2000); gi[i].ldd = 128; gi[i].n = a + 1; gi[i].d = 128;
+      gi[i].kept = (int32_t*)fake(0x3000); gi[i].indptr = (int32_t*)fake(0x4000); gi[i].indices = (int32_t*)fake(0x5000); gi[i].max_edges_dir = 64 * (a + 1) + 7;
+      gi[i].info = (int32_t*)fake(0x6000);
+      gp[i].radius = 15.0; gp[i].percentile = 2.0; gp[i].min_size = 7; gp[i].reserved = 0;
+    }
+    size_t need;
+    for (int it : {0, 1, 65, 3000}) {
+      EXPECT((need = gims_eval_workspace_bytes(ev.data(), 5, it)) > 0 && need % 256 == 0);
+      EXPECT(carved(gims_eval_pairs(ev.data(), 5, 3.f, 3, 3.f, it, 1, work, need, nullptr)));
+      EXPECT(gims_eval_pairs(ev.data(), 5, 3.f, 3, 3.f, it, 1, work, need - 1, nullptr) == GIMS_EINVAL && strstr(gims_last_error(), "gims_eval_pairs"));
+    }
+    EXPECT((need = gims_train_labels_workspace_bytes(lb.data(), 5)) > 0 && need % 256 == 0);
+    EXPECT(carved(gims_train_labels(lb.data(), 5, (const float*)fake(0x7000), 3.f, 3, (int64_t*)fake(0x8000), (int64_t*)fake(0x9000), work, need, nullptr)));
+    EXPECT(gims_train_labels(lb.data(), 5, (const float*)fake(0x7000), 3.f, 3, (int64_t*)fake(0x8000), (int64_t*)fake(0x9000), work, need - 1, nullptr) == GIMS_EINVAL &&
+           strstr(gims_last_error(), "gims_train_labels"));
+    for (int np : {1, 5}) {
+      EXPECT((need = gims_sinkhorn_workspace_bytes(ot.data(), np)) > 0 && need % 256 == 0);
+      EXPECT(carved(gims_sinkhorn_match(ot.data(), np, 1.f, 10, 0.2f, work, need, nullptr)));
+      EXPECT(carved(gims_sinkhorn_match_ex(ot.data(), np, 1.f, 10, 0.2f, work, need, GIMS_OT_STREAMED, nullptr)));
+      EXPECT(gims_sinkhorn_match(ot.data(), np, 1.f, 10, 0.2f, work, need - 1, nullptr) == GIMS_EINVAL && strstr(gims_last_error(), "gims_sinkhorn_match"));
+      EXPECT(carved(gims_sinkhorn_history(ot.data(), np, 1.f, 3, hist.data(), work, need, nullptr)));
+      EXPECT(gims_sinkhorn_history(ot.data(), np, 1.f, 3, hist.data(), work, need - 1, nullptr) == GIMS_EINVAL && strstr(gims_last_error(), "gims_sinkhorn_history"));
+      EXPECT((need = gims_sinkhorn_backward_workspace_bytes(ot.data(), np)) > 0 && need % 256 == 0);
+      for (int it : {3, 128, 129}) EXPECT(carved(gims_sinkhorn_backward(ot.data(), np, 1.f, it, hist.data(), dz.data(), (float*)fake(0x9000), work, need, nullptr)));
+      EXPECT(gims_sinkhorn_backward(ot.data(), np, 1.f, 3, hist.data(), dz.data(), (float*)fake(0x9000), work, need - 1, nullptr) == GIMS_EINVAL &&
+             strstr(gims_last_error(), "gims_sinkhorn_backward"));
+    }
+    {   // the on-chip Sinkhorn layout: several geometry classes in one list (sizing), then the carve of every class
+      std::vector<gims::OtR2Host> h2;
+      for (int i = 0; i < 5; ++i) {
+        if (ot[i].m > 4096) continue;
+        h2.push_back(gims::OtR2Host{ot[i].scores, ot[i].ld, ot[i].n, ot[i].m, ot[i].uv, ot[i].uv, ot[i].uv, -1.f, -1.f, -1.f});
+      }
+      h2.push_back(gims::OtR2Host{ot[0].scores, 2000, 2000, 1990, ot[0].uv, ot[0].uv, ot[0].uv, -1.f, -1.f, -1.f});
+      const gims::OtR2Plan plan = gims::ot_res2_plan(h2.data(), (int)h2.size(), 10);
+      EXPECT(plan.ok && plan.ngroups >= 3 && plan.bytes > 0 && plan.bytes % 256 == 0);
+      EXPECT(gims::ot_res2_run(plan, h2.data(), (int)h2.size(), 1.f, 10, 1, work, nullptr) == GIMS_EHIP);
+    }
+    for (int flags : {0, (int)GIMS_AGC_ROBUST}) {
+      EXPECT((need = gims_agc_workspace_bytes_ex(gi.data(), 5, flags)) > 0 && need % 256 == 0);
+      EXPECT(carved(gims_agc_build_v(gi.data(), 5, gp.data(), flags, work, need, nullptr)));
+      EXPECT(gims_agc_build_v(gi.data(), 5, gp.data(), flags, work, need - 1, nullptr) == GIMS_EINVAL && strstr(gims_last_error(), "gims_agc_build"));
+    }
+    EXPECT((need = gims_delaunay_workspace_bytes(gi.data(), 5)) > 0 && need % 256 == 0);
+    EXPECT(carved(gims_delaunay_build(gi.data(), 5, work, need, nullptr)));
+    EXPECT(gims_delaunay_build(gi.data(), 5, work, need - 1, nullptr) == GIMS_EINVAL && strstr(gims_last_error(), "gims_delaunay_build"));
+    for (int flags : {0, (int)GIMS_NN_EXHAUSTIVE}) {
+      EXPECT((need = gims_nn_workspace_bytes(nn.data(), 5, flags)) > 0 && need % 256 == 0);
+      EXPECT(carved(gims_nn_match(nn.data(), 5, flags, work, need, nullptr)));
+      EXPECT(gims_nn_match(nn.data(), 5, flags, work, need - 1, nullptr) == GIMS_EINVAL && strstr(gims_last_error(), "gims_nn_match"));
+    }
   }
   // ---- a call that reaches the HIP runtime: no device in this container -> a clean GIMS_EHIP / error string, no crash
   char host_table[64] = {0};
