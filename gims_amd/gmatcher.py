@@ -218,14 +218,24 @@ class GMatcher(nn.Module):
         self.__dict__.pop("_plist", None)
         self.__dict__.pop("_train_params", None)
         self.__dict__.pop("_train_buffers", None)
+        self.__dict__.pop("_fstate", None)
         return super().load_state_dict(sd, strict=strict, **kw)
 
     def _apply(self, fn, *a, **kw):          # .to() / .cuda() / .half() replace the parameter tensors
         self.__dict__.pop("_plist", None)
         self.__dict__.pop("_train_params", None)
         self.__dict__.pop("_train_buffers", None)
+        self.__dict__.pop("_fstate", None)
         self._pack = None
         return super()._apply(fn, *a, **kw)
+
+    def _float_state(self):
+        """The floating entries of state_dict() -- parameters and BatchNorm running statistics, the tensors themselves -- in its order:
+        what optim.ModelEMA averages.  Cached like _plist (walking the module tree per training step is host time)."""
+        fs = self.__dict__.get("_fstate")
+        if fs is None:
+            fs = self.__dict__["_fstate"] = [v for v in self.state_dict(keep_vars=True).values() if v.dtype.is_floating_point]
+        return fs
 
     # ------------------------------------------------------------------ weight packing
     def _packed(self, device):

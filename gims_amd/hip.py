@@ -158,6 +158,19 @@ class AdamGroup(C.Structure):
                 ("step", C.c_int64)]
 
 
+class SgdTensor(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("momentum_buffer", C.c_void_p), ("n", C.c_int64), ("group", C.c_int32), ("first", C.c_int32)]
+
+
+class SgdGroup(C.Structure):
+    _fields_ = [("lr", C.c_double), ("momentum", C.c_double), ("dampening", C.c_double), ("weight_decay", C.c_double), ("nesterov", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class EmaTensor(C.Structure):
+    _fields_ = [("ema", C.c_void_p), ("model", C.c_void_p), ("n", C.c_int64)]
+
+
 class EvalPair(C.Structure):
     _fields_ = [("kpts0", C.c_void_p), ("kpts1", C.c_void_p), ("matches0", C.c_void_p), ("mscores0", C.c_void_p),
                 ("n0", C.c_int32), ("n1", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("h_gt", C.c_float * 9),
@@ -317,6 +330,8 @@ _SIGNATURES = {
     "gims_sage_mean_transposed": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "gims_normalize_keypoints": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "gims_adam_step": (C.c_int, [C.POINTER(AdamTensor), C.c_int32, C.POINTER(AdamGroup), C.c_int32, C.c_void_p]),
+    "gims_sgd_step": (C.c_int, [C.POINTER(SgdTensor), C.c_int32, C.POINTER(SgdGroup), C.c_int32, C.c_void_p]),
+    "gims_ema_update": (C.c_int, [C.POINTER(EmaTensor), C.c_int32, C.c_double, C.c_void_p]),
     "gims_ot_matrix": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
                                  C.c_void_p]),
     "gims_nn_workspace_bytes": (C.c_size_t, [C.POINTER(NnPair), C.c_int32, C.c_int32]),
@@ -1590,6 +1605,31 @@ def adam_step(table, groups):
         gt[i].lr, gt[i].beta1, gt[i].beta2, gt[i].eps, gt[i].weight_decay, gt[i].step = (float(g["lr"]), float(g["beta1"]), float(g["beta2"]), float(g["eps"]),
                                                                                       float(g["weight_decay"]), int(g["step"]))
     _check(load().gims_adam_step(table.ctypes.data_as(C.POINTER(AdamTensor)), len(table), gt, len(groups), _stream()), "gims_adam_step")
+
+
+SGD_TENSOR_DTYPE = [("param", "<u8"), ("grad", "<u8"), ("momentum_buffer", "<u8"), ("n", "<i8"), ("group", "<i4"), ("first", "<i4")]
+EMA_TENSOR_DTYPE = [("ema", "<u8"), ("model", "<u8"), ("n", "<i8")]
+
+
+def sgd_step(table, groups):
+    """One fused SGD step (gims_sgd_step).  table: C-contiguous NumPy structured array of dtype SGD_TENSOR_DTYPE (= gims_sgd_tensor: device
+    pointers of contiguous float32 tensors, element count, group index, first = the momentum buffer holds nothing yet); groups: 1 to 8
+    dicts with lr, momentum, dampening, weight_decay, nesterov."""
+    import numpy as np
+    assert table.dtype == np.dtype(SGD_TENSOR_DTYPE) and table.flags["C_CONTIGUOUS"] and table.dtype.itemsize == C.sizeof(SgdTensor)
+    gt = (SgdGroup * max(len(groups), 1))()
+    for i, g in enumerate(groups):
+        gt[i].lr, gt[i].momentum, gt[i].dampening, gt[i].weight_decay, gt[i].nesterov = (float(g["lr"]), float(g["momentum"]), float(g["dampening"]),
+                                                                                         float(g["weight_decay"]), int(bool(g["nesterov"])))
+    _check(load().gims_sgd_step(table.ctypes.data_as(C.POINTER(SgdTensor)), len(table), gt, len(groups), _stream()), "gims_sgd_step")
+
+
+def ema_update(table, decay):
+    """ema = ema * decay + (1 - decay) * model over a table of tensors (gims_ema_update).  table: C-contiguous NumPy structured array of
+    dtype EMA_TENSOR_DTYPE (= gims_ema_tensor: device pointers of contiguous float32 tensors and their element count)."""
+    import numpy as np
+    assert table.dtype == np.dtype(EMA_TENSOR_DTYPE) and table.flags["C_CONTIGUOUS"] and table.dtype.itemsize == C.sizeof(EmaTensor)
+    _check(load().gims_ema_update(table.ctypes.data_as(C.POINTER(EmaTensor)), len(table), float(decay), _stream()), "gims_ema_update")
 
 
 # ------------------------------------------------------------------------------------------------ training data from images (DESIGN.md 4.9)

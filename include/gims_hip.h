@@ -779,6 +779,18 @@ int gims_normalize_keypoints(const float* kpts, const float* norm3, const int32_
 typedef struct gims_adam_tensor { float* param; const float* grad; float* exp_avg; float* exp_avg_sq; int64_t n; int32_t group; int32_t reserved; } gims_adam_tensor;
 typedef struct gims_adam_group { double lr, beta1, beta2, eps, weight_decay; int64_t step; } gims_adam_group;
 int gims_adam_step(const gims_adam_tensor* tensors, int32_t count, const gims_adam_group* groups, int32_t n_groups /* <= 8 */, void* stream);
+/* The same for opt_type: sgd (train.py:55 builds optim.SGD(pg0, lr, momentum=0.9, nesterov=True)): torch's _single_tensor_sgd (maximize =
+ * False) in float32, every `x + alpha * y` one fused multiply-add, the scalars (-lr, 1 - dampening) formed in double and rounded once.
+ * first != 0: this tensor's momentum buffer holds nothing yet -- it is written (buf = g + wd * p), never read.  momentum_buffer may be
+ * null only in a group whose momentum is 0.  Both calls check their arguments before any HIP call; count == 0 returns GIMS_OK. */
+typedef struct gims_sgd_tensor { float* param; const float* grad; float* momentum_buffer; int64_t n; int32_t group; int32_t first; } gims_sgd_tensor;
+typedef struct gims_sgd_group { double lr, momentum, dampening, weight_decay; int32_t nesterov; int32_t reserved; } gims_sgd_group;
+int gims_sgd_step(const gims_sgd_tensor* tensors, int32_t count, const gims_sgd_group* groups, int32_t n_groups /* 1..8 */, void* stream);
+/* ModelEMA.update (utils/common.py:1005-1015: `v *= d; v += (1 - d) * msd[k]` per floating state-dict entry) over a HOST table:
+ * ema = fadd(fmul(ema, (float)decay), fmul((float)(1.0 - decay), model)), three separately rounded operations as torch's two statements
+ * are; ~count/80 launches.  decay in [0, 1]; ema and model of one entry must be different tensors. */
+typedef struct gims_ema_tensor { float* ema; const float* model; int64_t n; } gims_ema_tensor;
+int gims_ema_update(const gims_ema_tensor* tensors, int32_t count, double decay, void* stream);
 
 /* ---- SIFT keypoint detection (gims_amd/csrc/sift.hip): OpenCV 4.x SIFT_create(0, 3, 0.001, 80, 1.6).detect,
  * restated for uint8 BGR [n][h][w][3] or gray [n][h][w][1] images of one size, every image of a batch in the same launches.

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Training-step throughput of the HIP path: model.train(); loss = model(data, mode='train')[0];
-loss.backward(); optimizer.step() on one synthetic pair of 2 x N keypoints (the reference trains with batch_size 1 and
+loss.backward(); optimizer.step() (and, with --ema, ema.update(model): train.py:141) on one synthetic pair of 2 x N keypoints (the reference trains with batch_size 1 and
 max_keypoints 2048: configs/coco_config.yaml, train.py:107), next to the oracle's CPU training step on the same input.
 
-    python tools/train_bench.py [--keypoints 2048] [--steps 10] [--no-cpu]
+    python tools/train_bench.py [--keypoints 2048] [--steps 10] [--no-cpu] [--optimizer fused|torch|sgd|torch-sgd] [--ema none|fused|torch]
 """
 import argparse
 import json
@@ -16,7 +16,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gims_amd import GMatcher, synth  # noqa: E402
-from gims_amd.optim import Adam as FusedAdam  # noqa: E402
+from gims_amd.optim import SGD as FusedSGD, Adam as FusedAdam, ModelEMA  # noqa: E402
 from tools.gen_pairs import matches_of  # noqa: E402
 
 
@@ -29,14 +29,36 @@ def batch(n, seed, device):
     return d
 
 
-def measure(keypoints=2048, steps=10, warmup=2, precision="bf16x6", with_cpu=True, optimizer="fused"):
+OPTIMIZERS = {"fused": "Adam (gims_amd.optim.Adam, fused)", "torch": "Adam (torch.optim.Adam)",
+              "sgd": "SGD, momentum 0.9, nesterov (gims_amd.optim.SGD, fused)", "torch-sgd": "SGD, momentum 0.9, nesterov (torch.optim.SGD)"}
+EMAS = {"none": "", "fused": " + EMA update (gims_amd.optim.ModelEMA, fused)", "torch": " + EMA update (the reference's per-entry torch loop)"}
+
+
+def _torch_ema_update(ema, model):
+    """ModelEMA.update as the reference has it (utils/common.py:1005-1015): three torch operations per floating state-dict entry."""
+    with torch.no_grad():
+        ema.updates += 1
+        d = ema.decay(ema.updates)
+        msd = model.state_dict()
+        for k, v in ema.ema.state_dict().items():
+            if v.dtype.is_floating_point:
+                v *= d
+                v += (1. - d) * msd[k].detach()
+
+
+def measure(keypoints=2048, steps=10, warmup=2, precision="bf16x6", with_cpu=True, optimizer="fused", ema="none"):
     """The JSON block of one measurement (also embedded in bench.py's line as `train_step`)."""
     cfg = {"sinkhorn_iterations": 100, "pos_loss_weight": 0.45, "neg_loss_weight": 1.0, "train_precision": precision}
     sd = synth.make_state_dict(123)
     m = GMatcher(cfg)
     m.load_state_dict(sd)
     m = m.cuda().train()
-    opt = (torch.optim.Adam if optimizer == "torch" else FusedAdam)(m.parameters(), lr=1e-4)      # train.py:53
+    if optimizer in ("fused", "torch"):
+        opt = (torch.optim.Adam if optimizer == "torch" else FusedAdam)(m.parameters(), lr=1e-4)      # train.py:53
+    else:
+        opt = (torch.optim.SGD if optimizer == "torch-sgd" else FusedSGD)(m.parameters(), lr=1e-4, momentum=0.9, nesterov=True)      # train.py:55
+    avg = ModelEMA(m) if ema != "none" else None                           # train.py:60-62
+    ema_update = {"none": lambda: None, "fused": lambda: avg.update(m), "torch": lambda: _torch_ema_update(avg, m)}[ema]
     fw, bw, st, losses = [], [], [], []
     with torch.enable_grad():
         # the timed region is the reference's own "Mtime" (train.py:135-139: t3 = time_synchronized(); forward; backward; optimizer.step();
@@ -51,6 +73,7 @@ def measure(keypoints=2048, steps=10, warmup=2, precision="bf16x6", with_cpu=Tru
             loss.backward()
             opt.step()
             opt.zero_grad()
+            ema_update()                                 # train.py:141 (behind the reference's t4; inside the timed region here when asked for)
             lv = float(loss.detach())                    # (the synchronisation)
             t3 = time.perf_counter()
             if i >= warmup:
@@ -73,7 +96,9 @@ def measure(keypoints=2048, steps=10, warmup=2, precision="bf16x6", with_cpu=Tru
            "ms_per_step": 1e3 * float(np.median(st)), "forward_ms": 1e3 * float(np.median(fw)), "backward_ms": 1e3 * float(np.median(bw)),
            "phase_note": "forward_ms / backward_ms: separate steps with a synchronisation behind each phase (their sum exceeds ms_per_step)", "steps": steps, "loss_first_last": [losses[0], losses[-1]],
            "dtype": "split-%s MFMA products, f32 everything else" % precision, "data": "synthetic",
-           "config": {"workload": "1 pair/step of 2x%d synthetic keypoints, 18 layers, 100 Sinkhorn iterations, train() mode forward + backward + Adam (%s)" % (keypoints, "gims_amd.optim.Adam, fused" if optimizer != "torch" else "torch.optim.Adam"), "optimizer": optimizer}}
+           "config": {"workload": "1 pair/step of 2x%d synthetic keypoints, 18 layers, 100 Sinkhorn iterations, train() mode forward + backward + %s%s" % (keypoints, OPTIMIZERS[optimizer], EMAS[ema]), "optimizer": optimizer}}
+    if ema != "none":
+        out["config"]["ema"] = ema
     if with_cpu:
         from oracle import gims_oracle as O
         cores = min(os.cpu_count() or 1, 16)            # more threads than that make torch's CPU autograd crawl on many-core hosts
@@ -93,9 +118,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--precision", default="bf16x6", choices=["bf16x6", "bf16x3"])
-    ap.add_argument("--optimizer", default="fused", choices=["fused", "torch"], help="gims_amd.optim.Adam (one fused multi-tensor launch sequence) or torch.optim.Adam")
+    ap.add_argument("--optimizer", default="fused", choices=list(OPTIMIZERS), help="gims_amd.optim.Adam / SGD (one fused multi-tensor launch sequence) or torch.optim.Adam / SGD")
+    ap.add_argument("--ema", default="none", choices=list(EMAS), help="also keep EMA weights (train.py:141) inside the timed region: gims_amd.optim.ModelEMA or the reference's torch loop")
     a = ap.parse_args()
-    print(json.dumps(measure(a.keypoints, a.steps, a.warmup, a.precision, not a.no_cpu, a.optimizer)))
+    print(json.dumps(measure(a.keypoints, a.steps, a.warmup, a.precision, not a.no_cpu, a.optimizer, a.ema)))
 
 
 if __name__ == "__main__":
