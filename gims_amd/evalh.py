@@ -21,11 +21,16 @@ RECORD_FIELDS = hip.EVAL_FIELDS          # columns of the per-pair record (float
 
 
 def evaluate_pairs(datas: Sequence[dict], outs: Sequence[dict], h_gts: Sequence[np.ndarray], dist_thresh: float = 3, n_iters: int = 3,
-                   ransac_thresh: float = 3.0, ransac_iters: int = 3000, seed: int = 0) -> dict:
+                   ransac_thresh: float = 3.0, ransac_iters: int = 3000, seed: int = 0, lo_iters: int = 0) -> dict:
     """datas: the dicts ``match_pairs`` / ``forward`` mutated (kept keypoints, image shapes); outs: the per-pair results;
     h_gts: 3x3 ground-truth homographies mapping image 0 to image 1.  Returns device tensors:
     records [P, 16] float32 (RECORD_FIELDS in the first columns), gt0 / inlier (lists of per-pair tensors),
-    homographies [P, 2, 3, 3] float32 (4-point, RANSAC).  Asynchronous on the current stream."""
+    homographies [P, 2, 3, 3] float32 (4-point, RANSAC).  Asynchronous on the current stream.
+
+    ``lo_iters=0`` (default): the RANSAC of ``gims_eval_pairs``, best hypothesis and one refit.  ``lo_iters > 0``: ``n_inliers``,
+    ``err_ransac``, ``ransac_ok``, the RANSAC homography and ``inlier`` come from the locally optimised estimator of
+    ``gims_amd.verify`` (``gims_verify_pairs`` with ``h_gt`` as its reference, same threshold, hypotheses and seed); everything else
+    is unchanged."""
     P = len(outs)
     dev = outs[0]["matches0"].device
     records = torch.zeros((P, 16), dtype=torch.float32, device=dev)
@@ -47,7 +52,17 @@ def evaluate_pairs(datas: Sequence[dict], outs: Sequence[dict], h_gts: Sequence[
                           h_gt=H, height=height, width=width, gt0=g, inlier=m, record=records[p], homographies=homs[p]))
         gts.append(g)
         inl.append(m)
-    keep = hip.eval_pairs(items, dist_thresh, n_iters, ransac_thresh, ransac_iters, seed)
+    if lo_iters > 0:
+        keep = hip.eval_pairs(items, dist_thresh, n_iters, ransac_thresh, 0, seed)
+        vrec = torch.zeros((P, 8), dtype=torch.float32, device=dev)
+        vitems = [dict(kpts0=it["kpts0"], kpts1=it["kpts1"], matches0=it["matches0"].contiguous(), h_ref=it["h_gt"], height=it["height"],
+                       width=it["width"], inlier=it["inlier"], record=vrec[p], homography=homs[p, 9:]) for p, it in enumerate(items)]
+        keep = (keep, hip.verify_pairs(vitems, ransac_thresh, ransac_iters, lo_iters, seed), vitems)
+        vcol, col = hip.VERIFY_FIELDS.index, RECORD_FIELDS.index
+        for dst, src in (("n_inliers", "n_inliers"), ("err_ransac", "err_corner"), ("ransac_ok", "ok")):
+            records[:, col(dst)] = vrec[:, vcol(src)]
+    else:
+        keep = hip.eval_pairs(items, dist_thresh, n_iters, ransac_thresh, ransac_iters, seed)
     return dict(records=records, homographies=homs.view(P, 2, 3, 3), gt0=gts, inlier=inl, _keep=(keep, items))
 
 

@@ -1320,7 +1320,7 @@ class GMatcher(nn.Module):
 
     # ------------------------------------------------------------------ one pair under a grid of graph parameters
     @torch.no_grad()
-    def sweep(self, data, grid, *, rows=None, outputs="all"):
+    def sweep(self, data, grid, *, rows=None, outputs="all", verify=None):
         """One image pair matched under every graph setting of ``grid`` (what the reference's tools/parameter_search.py does with one
         ``forward`` per setting).  ``data``: a single-pair dict as ``forward`` takes it (B == 1; not mutated).  ``grid``: an iterable of
         ``(radius, percentile, min_size)`` triples or of dicts with those keys that may also carry ``delaunay``.
@@ -1335,7 +1335,14 @@ class GMatcher(nn.Module):
         ``match_pairs`` plus ``kept_kpts0_indices`` / ``kept_kpts1_indices`` (device tensors; ``outputs='matches'`` leaves out keypoints,
         descriptors and mdesc, which are 16 MB per setting at 2 x 4096).  A setting under which an image keeps nothing does not raise
         (``forward`` and ``match_pairs`` do, like the reference): its record has ``error='ValueError: need at least one array to
-        concatenate'``, ``kept0 = kept1 = 0``, ``n_matches = 0`` and ``result=None``, the way parameter_search.py writes such a row."""
+        concatenate'``, ``kept0 = kept1 = 0``, ``n_matches = 0`` and ``result=None``, the way parameter_search.py writes such a row.
+
+        ``verify``: None, or a dict with any of ``thresh``, ``iters``, ``lo_iters``, ``seed`` (the keywords of ``gims_amd.verify.verify_pairs``).
+        When given, every record also carries ``correct_matches`` (a 0-dim device tensor: the inliers of the verified homography, the
+        quantity parameter_search.py:161-165 records), ``homography`` [3, 3] and ``inlier`` [kept0] uint8 -- one ``verify_pairs`` call per
+        sub-batch, no extra host synchronisation; ``0 / None / None`` on a record with ``error``."""
+        if verify is not None and (not isinstance(verify, dict) or set(verify) - {"thresh", "iters", "lo_iters", "seed"}):
+            raise ValueError("verify must be None or a dict with keys among thresh, iters, lo_iters, seed")
         self._check_call(data, {})
         if data['keypoints0'].shape[0] != 1:
             raise ValueError("sweep takes one single-pair dict (B == 1)")
@@ -1376,9 +1383,12 @@ class GMatcher(nn.Module):
                     csum = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), (m0_all > -1).cumsum(0)])
                     n_matches = csum[hip.upload(ends, dev)] - csum[hip.upload(ends - np.asarray(self._last["flat"]["n0"], dtype=np.int64), dev)]
                 p = 0
+                live = []
                 for j, (radius, percentile, min_size, delaunay) in enumerate(chunk):
                     rec = dict(radius=radius, percentile=percentile, min_size=min_size, delaunay=delaunay, kept0=0, kept1=0, n_matches=0,
                                error=None, result=None)
+                    if verify is not None:
+                        rec.update(correct_matches=0, homography=None, inlier=None)
                     records[c0 + j] = rec
                     if j in dropped:
                         rec["error"] = "ValueError: need at least one array to concatenate"
@@ -1394,5 +1404,13 @@ class GMatcher(nn.Module):
                                     'descriptors0': g0["graph"].ndata['feat'].t()[None], 'descriptors1': g1["graph"].ndata['feat'].t()[None],
                                     'mdesc0': mdesc[o0:o0 + n0], 'mdesc1': mdesc[o1:o1 + n1]})
                     rec["result"] = res
+                    live.append((rec, g0["graph"].ndata['point'][None], g1["graph"].ndata['point'][None]))
                     p += 1
+                if verify is not None and live:
+                    from .verify import verify_pairs
+                    v = verify_pairs([dict(keypoints0=k0, keypoints1=k1) for _, k0, k1 in live],
+                                     [{'matches0': r["result"]['matches0']} for r, _, _ in live], **verify)
+                    col = hip.VERIFY_FIELDS.index("n_inliers")
+                    for q, (rec, _, _) in enumerate(live):
+                        rec.update(correct_matches=v["records"][q, col], homography=v["homographies"][q], inlier=v["inlier"][q])
         return records

@@ -177,6 +177,13 @@ class EvalPair(C.Structure):
                 ("gt0", C.c_void_p), ("inlier", C.c_void_p), ("record", C.c_void_p), ("homographies", C.c_void_p)]
 
 
+class VerifySet(C.Structure):
+    """gims_verify_set (include/gims_hip.h): one set of correspondences for gims_verify_pairs."""
+    _fields_ = [("kpts0", C.c_void_p), ("kpts1", C.c_void_p), ("matches0", C.c_void_p),
+                ("n0", C.c_int32), ("n1", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("has_ref", C.c_int32), ("reserved", C.c_int32),
+                ("h_ref", C.c_float * 9), ("inlier", C.c_void_p), ("record", C.c_void_p), ("homography", C.c_void_p)]
+
+
 class LabelPair(C.Structure):
     _fields_ = [("kpts0", C.c_void_p), ("kpts1", C.c_void_p), ("n0", C.c_int32), ("n1", C.c_int32)]
 
@@ -282,6 +289,8 @@ _SIGNATURES = {
     "gims_eval_workspace_bytes": (C.c_size_t, [C.POINTER(EvalPair), C.c_int32, C.c_int32]),
     "gims_eval_pairs": (C.c_int, [C.POINTER(EvalPair), C.c_int32, C.c_float, C.c_int32, C.c_float, C.c_int32, C.c_uint64,
                                   C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gims_verify_workspace_bytes": (C.c_size_t, [C.POINTER(VerifySet), C.c_int32, C.c_int32]),
+    "gims_verify_pairs": (C.c_int, [C.POINTER(VerifySet), C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p]),
     "gims_pyramid_layout": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_size_t),
                                       C.POINTER(C.c_size_t)]),
     "gims_pyramid_build": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -976,6 +985,41 @@ def eval_pairs(items, dist_thresh=3.0, n_iters=3, ransac_thresh=3.0, ransac_iter
     _check(lib.gims_eval_pairs(arr, len(items), float(dist_thresh), int(n_iters), float(ransac_thresh), int(ransac_iters),
                                int(seed) & 0xFFFFFFFFFFFFFFFF, _p(work), work.numel() * work.element_size(), _stream()),
            "gims_eval_pairs")
+    return work
+
+
+# ------------------------------------------------------------------------------------------------ geometric verification
+VERIFY_FIELDS = ("n_valid", "ok", "n_inliers", "best_hyp", "best_hyp_inliers", "lo_rounds", "err_corner")
+
+
+def verify_pairs(items, thresh=3.0, iters=3000, lo_iters=8, seed=0, work=None):
+    """items: list of dicts with device tensors kpts0 [n0,2] f32, kpts1 [n1,2] f32, matches0 [n0] int64 or None (identity pairing, n0 == n1),
+    optionally h_ref (3x3 array-like) with height / width, and outputs inlier [n0] uint8, record [8] f32 (VERIFY_FIELDS), homography [9] f32.
+    One batched asynchronous call; returns the workspace (keep it alive until the stream has passed the call).  See include/gims_hip.h."""
+    import numpy as np
+    lib = load()
+    arr = (VerifySet * len(items))()
+    for i, it in enumerate(items):
+        k0, k1, m0 = it["kpts0"], it["kpts1"], it.get("matches0")
+        for k in (k0, k1):
+            if k.dtype != torch.float32 or not k.is_contiguous() or k.dim() != 2 or k.shape[1] != 2 or not k.is_cuda:
+                raise GimsHipError("verify_pairs: kpts0 / kpts1 must be contiguous float32 [n, 2] device tensors")
+        n0, n1 = int(k0.shape[0]), int(k1.shape[0])
+        if m0 is not None and (m0.dtype != torch.int64 or m0.numel() != n0 or not m0.is_contiguous()):
+            raise GimsHipError("verify_pairs: matches0 must be a contiguous int64 tensor of n0 elements")
+        if it["inlier"].dtype != torch.uint8 or it["inlier"].numel() < n0 or it["record"].dtype != torch.float32 or it["record"].numel() < 8 \
+                or it["homography"].dtype != torch.float32 or it["homography"].numel() < 9:
+            raise GimsHipError("verify_pairs: outputs are inlier uint8 [n0], record float32 [8], homography float32 [9]")
+        h_ref = it.get("h_ref")
+        h = np.asarray(h_ref, dtype=np.float32).reshape(9) if h_ref is not None else np.zeros(9, dtype=np.float32)
+        arr[i] = VerifySet(_p(k0) if n0 else None, _p(k1) if n1 else None, _p(m0), n0, n1, int(it.get("height", 0)), int(it.get("width", 0)),
+                           int(h_ref is not None), 0, (C.c_float * 9)(*h.tolist()), _p(it["inlier"]) if n0 else None, _p(it["record"]),
+                           _p(it["homography"]))
+    need = int(lib.gims_verify_workspace_bytes(arr, len(items), int(iters)))
+    if work is None or work.numel() * work.element_size() < need:
+        work = torch.empty(max(need, 256), dtype=torch.uint8, device=items[0]["record"].device)
+    _check(lib.gims_verify_pairs(arr, len(items), float(thresh), int(iters), int(lo_iters), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(work),
+                                 work.numel() * work.element_size(), _stream()), "gims_verify_pairs")
     return work
 
 

@@ -69,6 +69,7 @@ class Matching(torch.nn.Module):
 
     def sweep(self, data, grid, **kwargs):
         """The pair of ``data`` under every graph setting of ``grid``: the front end (detection, patches, descriptors) runs ONCE, then
-        ``GMatcher.sweep`` (see there for the grid, the keywords and the records returned).  ``data`` is not mutated."""
+        ``GMatcher.sweep`` (see there for the grid, the keywords -- ``rows``, ``outputs``, ``verify`` -- and the records returned).  ``data``
+        is not mutated."""
         _, data = self._front(data)
         return self.gmodel.sweep(data, grid, **kwargs)

@@ -516,6 +516,52 @@ size_t gims_eval_workspace_bytes(const gims_eval_pair* h_pairs, int32_t n_pairs,
 int gims_eval_pairs(const gims_eval_pair* h_pairs /* HOST array */, int32_t n_pairs, float dist_thresh, int32_t n_iters,
                     float ransac_thresh, int32_t ransac_iters, uint64_t seed, void* work, size_t work_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Geometric verification without a ground truth -- batched over sets of correspondences, everything stays on the device.
+ * replaces: cv2.findHomography(points0, points1, cv2.RANSAC | cv2.USAC_DEFAULT) and the count of its mask (`correct_matches`) in
+ *   eval_homography.py:191, eval_matches.py:71,164 and tools/parameter_search.py:161.  Parity with OpenCV is unpinned as for
+ *   gims_eval_pairs: the estimator is this build's own; its SPECIFICATION is this comment (restated in tests/verify_ref.py).
+ * Inputs per set: kpts0 [n0][2], kpts1 [n1][2] float32; matches0 [n0] int64, or NULL = the identity pairing i <-> i (needs n0 == n1).
+ *   The K correspondences are the rows with -1 < matches0[i] < n1, in ascending i.  Optionally h_ref / height / width (has_ref != 0) for
+ *   the corner-error column.
+ * Stage 1 (exactly stage 1 of gims_eval_pairs above, float64): hypotheses h = 0 .. iters-1 from the same sampler, the exact 4-point
+ *   model (h22 = 1), score = #correspondences with forward reprojection error^2 <= thresh^2; a hypothesis without a finite model
+ *   scores -1; best = highest score, lowest h among equals.
+ * Stage 2, lo_iters == 0: the single unguarded least-squares refit of gims_eval_pairs on the inliers of the best hypothesis (raw
+ *   coordinates) and the final mask under it -- the same inputs give the same model as there.
+ * Stage 2, lo_iters >= 1 (local optimisation, float64): H_0 = the best 4-point model, I_0 its inliers.  For l = 1 .. lo_iters:
+ *     stop if |I_{l-1}| < 4;
+ *     T0, T1 = similarity normalisations of the two point sets of I_{l-1}: centroid to the origin, scale sqrt(2) / (mean distance to the
+ *       centroid), scale 1 if that mean is 0;
+ *     Hn = solution of the 8 x 8 normal equations (h22 = 1) over the normalised inliers, by the same elimination; stop if it fails or is
+ *       not finite;
+ *     H' = T1^-1 Hn T0, divided by H'[8]; stop if H'[8] is 0 or anything is not finite;
+ *     I' = inliers of H';  if |I'| < |I_{l-1}|: stop and keep H_{l-1};  otherwise accept (H_l, I_l) = (H', I') and stop if I' == I_{l-1}.
+ *   The inlier count never decreases; lo_iters is a cap (the default 8 is not a tuned value).
+ * Outputs per set: homography [9] float32 row-major, inlier [n0] uint8 (0 on rows without a correspondence), record float[8]
+ *   (GIMS_VERIFY_* below).  K < 4, iters == 0 or no hypothesis with a model: ok = 0, err_corner = -1, n_valid = K, zeros elsewhere.
+ * GIMS_EINVAL: n_sets > 65535 (the sets are the grid's y dimension), iters > 2^20, lo_iters > 1024, a negative or non-finite thresh, a
+ *   workspace smaller than gims_verify_workspace_bytes (checked before anything is enqueued).  Asynchronous; no host synchronisation.
+ */
+typedef struct gims_verify_set {
+  const float* kpts0; const float* kpts1;   /* [n0][2], [n1][2] */
+  const int64_t* matches0;                  /* [n0], or NULL: identity pairing */
+  int32_t n0, n1, height, width;            /* image 0 size for the corner error (read with has_ref only) */
+  int32_t has_ref, reserved;
+  float h_ref[9];                           /* reference homography, row-major (read with has_ref only) */
+  uint8_t* inlier; float* record; float* homography;
+} gims_verify_set;
+#define GIMS_VERIFY_NVALID 0            /* K */
+#define GIMS_VERIFY_OK 1
+#define GIMS_VERIFY_NINLIERS 2          /* under the returned model: the reference's `correct_matches` */
+#define GIMS_VERIFY_BEST_HYP 3
+#define GIMS_VERIFY_BEST_HYP_INLIERS 4  /* the score of the best hypothesis = |I_0| */
+#define GIMS_VERIFY_LO_ROUNDS 5         /* accepted rounds of the local optimisation */
+#define GIMS_VERIFY_ERR_CORNER 6        /* mean corner distance to h_ref (as GIMS_EVAL_ERR_RANSAC), -1 without h_ref or model */
+size_t gims_verify_workspace_bytes(const gims_verify_set* h_sets, int32_t n_sets, int32_t iters);
+int gims_verify_pairs(const gims_verify_set* h_sets /* HOST array */, int32_t n_sets, float thresh, int32_t iters, int32_t lo_iters,
+                      uint64_t seed, void* work, size_t work_bytes, void* stream);
+
 /* Rebuild the full (n+1)x(m+1) OT matrix Z + u + v - norm (gmatcher.py:47,68) -- for forward_train and tests. */
 int gims_ot_matrix(const float* scores, int64_t ld, int32_t n, int32_t m, float alpha, const float* uv,
                    float* out /* [(n+1)][(m+1)] */, void* stream);

@@ -14,9 +14,11 @@ Output: ``<output>/record.txt`` with one line per setting in the reference's for
 
 * ``total_matches`` = len(matches0), the number of kept keypoints of image 0, as the reference writes it (parameter_search.py:162-165);
   a setting under which an image keeps nothing gives ``[r, t, m, 0, 0, time]``, as there.
-* ``correct_matches`` = the inlier count of THIS LIBRARY's RANSAC homography (gims_eval_pairs on the sweep's outputs, one batched call), NOT
-  of OpenCV's ``cv2.findHomography(..., cv2.USAC_DEFAULT)`` as in the reference: the two estimators differ, so these counts are comparable
-  among themselves and not with a record.txt of the reference (parity unpinned).
+* ``correct_matches`` = the inlier count of THIS LIBRARY's RANSAC homography (``sweep(verify=...)``: gims_verify_pairs on the sweep's outputs,
+  one batched call per sub-batch), NOT of OpenCV's ``cv2.findHomography(..., cv2.USAC_DEFAULT)`` as in the reference: the two estimators
+  differ, so these counts are comparable among themselves and not with a record.txt of the reference (parity unpinned).  The estimator
+  (include/gims_hip.h): 3000 hypotheses, 3 px, best 4-point model, then ``--lo-iters`` rounds of local optimisation.  ``--lo-iters 0``
+  (default) is one plain refit, the estimator of gims_eval_pairs, which this tool used before: its counts stay what they were.
 * ``time`` = the wall time of the whole sweep divided by the number of settings (the settings are not timed one by one: they run together).
   The file's first line, a comment, says so.
 """
@@ -29,7 +31,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from gims_amd import GMatcher, evalh, synth  # noqa: E402
+from gims_amd import GMatcher, synth  # noqa: E402
 
 
 def str_to_range(s):
@@ -49,6 +51,7 @@ def parse_args(argv=None):
     ap.add_argument("--synth", default="1024,2001,800,600", help="N,SEED[,W,H] of a synthetic pair")
     ap.add_argument("--pair", default=None, help="torch-saved dict of keypoint tensors (overrides --synth)")
     ap.add_argument("--rows", type=int, default=None, help="keypoint rows per sub-batch (default: config['sweep_rows'])")
+    ap.add_argument("--lo-iters", type=int, default=0, help="rounds of local optimisation of the RANSAC homography (0: one plain refit)")
     return ap.parse_args(argv)
 
 
@@ -91,22 +94,17 @@ def main(argv=None):
     data = load_pair(args, device)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    recs = model.sweep(data, grid, rows=args.rows)
+    recs = model.sweep(data, grid, rows=args.rows, outputs="matches", verify=dict(thresh=3.0, iters=3000, lo_iters=args.lo_iters, seed=0))
     live = [r for r in recs if r["error"] is None]
-    inliers = {}
-    if live:
-        # RANSAC inliers of every setting in ONE batched call; the ground-truth homography only feeds the error columns, which are not used here
-        ev = evalh.evaluate_pairs([dict(r["result"], image0=data["image0"]) for r in live], [r["result"] for r in live],
-                                  [np.eye(3, dtype=np.float32)] * len(live))
-        col = evalh.RECORD_FIELDS.index("n_inliers")
-        inliers = dict(zip(map(id, live), ev["records"][:, col].cpu().numpy().tolist()))
+    counts = torch.stack([r["correct_matches"] for r in live]).cpu().numpy().tolist() if live else []       # one read for the whole grid
+    inliers = dict(zip(map(id, live), counts))
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     os.makedirs(args.output, exist_ok=True)
     path = os.path.join(args.output, "record.txt")
     with open(path, "w") as f:
         f.write(f"# [r, t, m, correct_matches, total_matches, time]; time = sweep wall time {dt:.3f} s / {len(grid)} settings (RANSAC included); "
-                "correct_matches = inliers of gims_eval_pairs' RANSAC, not OpenCV USAC_DEFAULT\n")
+                f"correct_matches = inliers of gims_verify_pairs' RANSAC (lo_iters={args.lo_iters}), not OpenCV USAC_DEFAULT\n")
         f.write("\n".join(records_to_lines(recs, [inliers.get(id(r), 0) for r in recs], dt / len(grid))) + "\n")
     st = model.sweep_stats_last
     print(f"{len(grid)} settings in {dt:.3f} s ({len(grid) / dt:.1f} settings/s), {st['sub_batches']} sub-batches, "
