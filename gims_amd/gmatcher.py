@@ -27,6 +27,7 @@ import torch
 import torch.nn as nn
 
 from . import hip
+from .attention_tiers import MODE_NAMES, AttentionTiers
 
 BN_EPS = 1e-5
 LN_EPS = 1e-6          # the reference's LayerNorm (gmatcher.py:74-85)
@@ -214,18 +215,13 @@ class GMatcher(nn.Module):
                 k = k[:-len("bias")] + "fc_self.bias"
             sd[k] = v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))
         self._pack = None
-        self.__dict__.pop("_ops_cache", None)
-        self.__dict__.pop("_plist", None)
-        self.__dict__.pop("_train_params", None)
-        self.__dict__.pop("_train_buffers", None)
-        self.__dict__.pop("_fstate", None)
+        for k in ("_ops_cache", "_plist", "_train_params", "_train_buffers", "_fstate"):
+            self.__dict__.pop(k, None)
         return super().load_state_dict(sd, strict=strict, **kw)
 
     def _apply(self, fn, *a, **kw):          # .to() / .cuda() / .half() replace the parameter tensors
-        self.__dict__.pop("_plist", None)
-        self.__dict__.pop("_train_params", None)
-        self.__dict__.pop("_train_buffers", None)
-        self.__dict__.pop("_fstate", None)
+        for k in ("_plist", "_train_params", "_train_buffers", "_fstate"):
+            self.__dict__.pop(k, None)
         self._pack = None
         return super()._apply(fn, *a, **kw)
 
@@ -347,11 +343,6 @@ class GMatcher(nn.Module):
     def _lin(e, a0, **kw):
         return hip.linear(a0, e["w"], w_lo=e["w_lo"], bias=e["b"], precision=e["prec"], spl=e["spl"], **kw)
 
-    @staticmethod
-    def _spl(rows, cols, dev):
-        """SPL32 split-bf16 activation buffer for a logical [rows, cols] matrix (see include/gims_hip.h)."""
-        return torch.empty((rows, 2 * cols), dtype=torch.bfloat16, device=dev)
-
     def _act(self, name, rows, cols, dtype):
         """Layer activation that never leaves this object ([rows, cols] of dtype): a view of a per-lane arena, so its
         address is the same from call to call and the recorded launch sequence of the GNN layers can be replayed."""
@@ -359,32 +350,28 @@ class GMatcher(nn.Module):
         return self._buf("act_" + name, nbytes)[:nbytes].view(dtype).view(rows, cols)
 
     # ------------------------------------------------------------------ attention_precision='auto'
-    _MODE_NAMES = ('bf16', 'f16', 'bf16x3')
+    _tiers = None          # the AttentionTiers of the current weight pack (None before the first 'auto' batch)
 
-    def _attention_modes(self, P, dev):
+    def _attention_modes(self, P, repeat):
         """Per layer the attention kernel family -- 0: bf16 operands, 1: IEEE half (GIMS_ATTN_F16), 2: split-bf16 pairs
         (GIMS_ATTN_X3) -- and the device accumulator [layers][heads + 1][4] int64 the kernels report the softmax peakedness and the
-        operand range into (None when nothing is measured)."""
+        operand range into (None when nothing is measured).  repeat: forward()'s repeat of a batch that was counted already."""
         mode, L = self.config['attention_precision'], self.n_layers
         if mode != 'auto' or not P["x3"]:          # (linear_precision='f32' has no split Q/K/V planes: 'auto' means bf16 there)
-            return [self._MODE_NAMES.index(mode) if mode in self._MODE_NAMES and P["x3"] else 0] * L, None
+            return [MODE_NAMES.index(mode) if mode in MODE_NAMES and P["x3"] else 0] * L, None
         self._attention_stats_consume(self._lane)
-        st = self.__dict__.get("_attn_auto")
-        if st is None or st["gen"] != P["gen"]:      # new weights: measure every layer at the accurate precision first
-            st = self.__dict__["_attn_auto"] = dict(gen=P["gen"], mode=[2] * L, calibrated=False, peak=np.zeros((L, self._heads)),
-                                                    peak_max=np.zeros((L, self._heads)), tail=np.zeros((L, self._heads)),
-                                                    range=np.zeros((L, 3)), switched=[], batches={}, redone=np.zeros(L, dtype=np.int64))
-        # (forward()'s repeat of a batch IS that batch: it is measured if the batch was -- the device-side guards it runs with read the statistic)
-        n_b = st["batches"][self._lane] = st["batches"].get(self._lane, -1) + (0 if self.__dict__.get("_attn_repeat", False) else 1)
-        if st["calibrated"] and n_b % max(1, int(self.config['attention_monitor_period'])) != 0:
-            return list(st["mode"]), None              # not a measured batch
+        tiers = self._tiers
+        if tiers is None or tiers.gen != P["gen"]:      # new weights: measure every layer at the accurate precision first
+            tiers = self._tiers = AttentionTiers(L, self._heads, P["gen"], self.config)
+        if not tiers.measured(self._lane, repeat):
+            return list(tiers.mode), None
         nbytes = L * (self._heads + 1) * 4 * 8
         stat = self._buf("attn_stat", nbytes)[:nbytes].view(torch.int64).view(L, self._heads + 1, 4)
-        stat.zero_()
-        return list(st["mode"]), stat
+        return list(tiers.mode), stat.zero_()
 
     def _attention_stats_enqueue(self, stat):
-        """Asynchronous read-back of this batch's statistics (consumed behind the next host synchronisation of this lane)."""
+        """Asynchronous read-back of this batch's statistics (consumed behind the next host synchronisation of this lane) into the lane's
+        slot: [pinned buffer, event behind the copy (None once consumed), generation of the tier table the batch ran on]."""
         pend = self.__dict__.setdefault("_attn_pending", {})
         slot = pend.get(self._lane)
         if slot is None or slot[0].numel() != stat.numel():
@@ -392,86 +379,42 @@ class GMatcher(nn.Module):
         slot[0].copy_(stat, non_blocking=True)
         slot[1] = torch.cuda.Event()
         slot[1].record()
-        slot[2] = self._attn_auto["gen"]
+        slot[2] = self._tiers.gen
 
     def _attention_stats_consume(self, lane=None, repeat=False):
-        """Fold the read-back of `lane` (None: of every lane) into the per-layer decision.  Called by a lane right after the
-        host synchronisation of its next batch's graph build -- its previous batch, read-back included, has finished by then,
-        so WHEN a measurement takes effect does not depend on timing -- and after forward()'s final synchronisation.
-        Decisions only ever move UP (bf16 -> f16 -> bf16x3) once the first measurement is in.  Returns the number of layers a SETTLED table
-        moved up by in this call (forward() repeats its batch then; match_pairs' batches were redone on the device already).
-        repeat: the read-back belongs to forward()'s repeat of a batch that was counted already -- its outlier rows are the same rows and do
-        not count towards `attention_auto_rare_batches` a second time.  st['rare_last'] speaks of the read-backs folded in by THIS call: a
-        call that finds none leaves it False (an unmeasured batch never inherits the verdict of an earlier one)."""
-        st = self.__dict__.get("_attn_auto")
-        H = self._heads
-        moved = 0
-        if st is not None:
-            st["rare_last"] = False
+        """Fold the finished read-back of `lane` (None: of every lane) into the tier table (AttentionTiers.fold; `repeat` as there); a
+        read-back of an older generation of the weights is dropped.  Called by a lane right after the host synchronisation of its next
+        batch's graph build -- its previous batch, read-back included, has finished by then, so WHEN a measurement takes effect does not
+        depend on timing -- and after forward()'s final synchronisation.  Returns the number of layers a SETTLED table moved up by in this
+        call (forward() repeats its batch then; match_pairs' batches were redone on the device already)."""
+        tiers, moved = self._tiers, 0
+        if tiers is not None:
+            tiers.begin()
         for ln, slot in list(self.__dict__.get("_attn_pending", {}).items()):
             if slot[1] is None or (lane is not None and ln != lane):
                 continue
             slot[1].synchronize()
             raw, slot[1] = slot[0].numpy().copy(), None
-            if st is None or slot[2] != st["gen"]:
-                continue
-            host = raw[:, :H, :].astype(np.float64)
-            cnt = host[:, :, 1]
-            seen = cnt > 0
-            mean = np.where(seen, host[:, :, 0] / np.maximum(cnt, 1.0) / hip.ATTN_STAT_SCALE, 0.0)
-            tail = np.where(seen, host[:, :, 3] / np.maximum(cnt, 1.0), 0.0)
-            rng = raw[:, H, :3].astype(np.uint32).view(np.float32).astype(np.float64)       # max |Q|, |K|, |V| as stored
-            st["peak"] = np.where(seen, mean, st["peak"])
-            st["tail"] = np.where(seen, tail, st["tail"])
-            st["peak_max"] = np.maximum(st["peak_max"], np.where(seen, host[:, :, 2] / hip.ATTN_STAT_SCALE, 0.0))
-            st["range"] = np.maximum(st["range"], np.where(np.isfinite(rng), rng, np.inf))
-            st["redone"] += (raw[:, H, 3] != 0)          # layers the device redid at split-bf16 inside that batch (guarded launches)
-            hot = (mean > float(self.config['attention_auto_threshold'])).any(axis=1) | (tail > float(self.config['attention_auto_tail'])).any(axis=1)
-            # a single sharply peaked row inside a diffuse bf16 layer: redone on the device by the guard (match_pairs), a reason for forward() to
-            # repeat the batch with the guards on -- never a reason to move the layer up
-            rmx = float(self.config['attention_auto_rowmax'])
-            rare = (~hot) & (np.asarray(st["mode"]) == 0) & ((host[:, :, 2] / hip.ATTN_STAT_SCALE >= rmx).any(axis=1) if rmx > 0 else False)
-            st["rare"] = st.get("rare", np.zeros(len(hot), dtype=np.int64)) + (0 if repeat else rare)
-            st["rare_last"] = st["rare_last"] or (bool(np.any(rare)) and st["calibrated"])
-            nb = int(self.config['attention_auto_rare_batches'])
-            if nb > 0 and st["calibrated"]:          # no outlier any more: such a layer goes to the half tier like a sharpened one
-                hot = hot | (rare & (st["rare"] >= nb))
-            wide = (st["range"] > float(self.config['attention_f16_range'])).any(axis=1)
-            want = np.where(hot, np.where(wide, 2, 1), 0)
-            if not st["calibrated"]:
-                if seen.all():
-                    st["mode"] = [int(w) for w in want]
-                    st["calibrated"] = True
-            else:
-                for l in np.nonzero(want > np.asarray(st["mode"]))[0]:
-                    st["mode"][l] = int(want[l])
-                    st["switched"].append(int(l))
-                    moved += 1
+            if tiers is not None and slot[2] == tiers.gen:
+                moved += tiers.fold(raw, repeat)
         return moved
 
     def _keep_attention_tiers(self, device):
         """TEST HOOK: carry the settled per-layer tier table over a change of the weights (which normally starts a new calibration), so that a
         test can hand a model whose layers all sit on plain bf16 a batch whose attention is peaked -- the situation the device-side redo exists
         for (a trained model meeting an input that sharpens a layer)."""
-        st = self.__dict__.get("_attn_auto")
-        assert st is not None and st["calibrated"], "settle the model first"
+        assert self._tiers is not None and self._tiers.calibrated, "settle the model first"
         device = torch.device(device)
         if device.type == "cuda" and device.index is None:        # (the pack is keyed by the full device name the batches arrive on)
             device = torch.device("cuda", torch.cuda.current_device())
-        st["gen"] = self._packed(device)["gen"]
+        self._tiers.rebind(self._packed(device)["gen"])
 
     def attention_report(self):
         """What 'auto' decided: per layer 'bf16' / 'f16' / 'bf16x3', the last measured peakedness (mean row maximum) and tail
         fraction (row maximum above 1/2) per (layer, head), max |Q|, |K|, |V| per layer, layers moved up after the first measurement.
         None before the first batch or with a fixed attention_precision."""
         self._attention_stats_consume()
-        st = self.__dict__.get("_attn_auto")
-        if st is None:
-            return None
-        return dict(modes=[self._MODE_NAMES[v] for v in st["mode"]], calibrated=st["calibrated"], peak=st["peak"].copy(),
-                    peak_max=st["peak_max"].copy(), tail=st["tail"].copy(), range=st["range"].copy(), switched=list(st["switched"]),
-                    redone=st["redone"].copy(), rare=st.get("rare", np.zeros(len(st["mode"]), dtype=np.int64)).copy(),
-                    threshold=float(self.config['attention_auto_threshold']), tail_threshold=float(self.config['attention_auto_tail']))
+        return None if self._tiers is None else self._tiers.report()
 
     # ------------------------------------------------------------------ stage timing (HIP events on the launch stream)
     def enable_timing(self, on: bool = True, stepwise: bool = False):
@@ -530,13 +473,12 @@ class GMatcher(nn.Module):
     _lane = 0
 
     # ------------------------------------------------------------------ ragged core: 2P images -> P pair results
-    def _run(self, images, radius, percentile, min_size, delaunay=False):
-        """images: list of dicts {kp (N,2) f32, de (N,D) f32 point-major, sc (N,), shape}; consecutive entries
-        (2p, 2p+1) form pair p.  Every pair may keep a different number of keypoints (ragged batch)."""
-        return self._run_rest(self._run_build(images, radius, percentile, min_size, delaunay=delaunay))
-
     def _run_build(self, images, radius, percentile, min_size, robust=False, delaunay=False, each=None):
-        """Phase 1: enqueue the adaptive graph construction (asynchronous; no host sync).  robust: the graph build histograms every
+        """Phase 1: enqueue the adaptive graph construction (asynchronous; no host sync).  images: list of dicts {kp (N,2) f32, de (N,D) f32
+        point-major, sc (N,), shape}; consecutive entries (2p, 2p+1) form pair p.  Every pair may keep a different number of keypoints
+        (ragged batch).  Returns the context of the call, which _run_rest takes: the caller adds its mode to it -- `guards` (device-side
+        redo launches behind the 'auto' attention tiers), `repeat` (forward()'s repeat of a batch that was counted already), `streamed`
+        (other stream lanes run next to this one), `skip_empty` (sweep); each False where it is absent.  robust: the graph build histograms every
         similarity instead of predicting where the percentile lies (the repeat after a build reported a missed prediction).
         delaunay: D-GIMS -- the Delaunay triangulation of the keypoints instead (gims_delaunay_build: every keypoint kept; radius,
         percentile and min_size have no effect); it fills the same kept / indptr / indices / info slots.
@@ -635,7 +577,6 @@ class GMatcher(nn.Module):
         cfg = self.config
         dev = images[0]["kp"].device
         D = cfg['descriptor_dim']
-        St = lambda name: GMatcher._Stage(self, name)   # noqa: E731
         ts0 = time.perf_counter()
         # the one host sync of the build: into a pinned staging buffer (a pageable .cpu() goes through the runtime's own
         # pin / copy / unpin path and costs ~0.1 ms more per call, which a single pair through forward() feels)
@@ -693,7 +634,7 @@ class GMatcher(nn.Module):
         row_off = np.concatenate([[0], np.cumsum(infos[:, 0], dtype=np.int64)])
         e_off = np.concatenate([[0], np.cumsum(infos[:, 1], dtype=np.int64)])
         n_tot, e_tot = int(row_off[-1]), int(e_off[-1])
-        with St("gather"):
+        with GMatcher._Stage(self, "gather"):
             ptab, b = ctx["ptab"], ctx["bufs"]
             ptab["n_kept"], ptab["n_edges"], ptab["row_off"], ptab["edge_off"] = infos[:, 0], infos[:, 1], row_off[:-1], e_off[:-1]
             feat, kpts_all, score_all, seg = b["feat"][:n_tot], b["kpts"][:n_tot], b["score"][:n_tot], b["seg"][:n_tot]
@@ -735,22 +676,30 @@ class GMatcher(nn.Module):
         return os.environ.get("GIMS_REPLAY") == "1" or rows <= 0 or n_tot <= rows
 
     def _run_rest(self, ctx):
-        """Phase 2: read the kept counts (the one host sync), then enqueue everything else."""
+        """Phase 2: read the kept counts (the one host sync; a build that asks for it is repeated), then enqueue everything else.  Returns the
+        results of the batch: items (per pair the score matrix, matches and potentials), pairs (their row ranges), mdesc, desc, sage,
+        images, flat, outputs (every device buffer of the batch), status_offs (where in outputs[4] each pair's Sinkhorn status word lies),
+        dropped (sweep: the pairs that kept nothing) and repeats (of the graph build)."""
+        G = self._gather(ctx)
+        if G is None:
+            again = self._run_build(ctx["images"], *ctx["params"], delaunay=bool(ctx.get("delaunay")), each=ctx.get("each"))
+            again.update({k: ctx[k] for k in ("guards", "repeat", "streamed", "skip_empty") if k in ctx}, repeats=ctx.get("repeats", 0) + 1)
+            return self._run_rest(again)
+        # (a sweep's sub-batch may have lost the pairs that kept nothing, all of them even)
+        # self._last: a reference to the most recent result, for sinkhorn_status(), the probes under tools/ and the tests -- valid until the
+        # next call on the same lane
+        res = self._last = self._run_batch(ctx, G) if ctx["images"] else dict(items=[], pairs=[], mdesc=None, images=[], outputs=[], status_offs=np.zeros(0, dtype=np.int64))
+        res.update(dropped=ctx.get("dropped", []), repeats=ctx.get("repeats", 0))
+        return res
+
+    def _run_batch(self, ctx, G):
+        """_run_rest for the batch gathered in G: encoder, layers, scores, Sinkhorn and selection, all enqueued without a host sync."""
         images = ctx["images"]
         cfg = self.config
         dev = images[0]["kp"].device
         P = self._packed(dev)
         D = cfg['descriptor_dim']
         St = lambda name: GMatcher._Stage(self, name)   # noqa: E731
-        G = self._gather(ctx)
-        if G is None:
-            again = self._run_build(images, *ctx["params"], delaunay=bool(ctx.get("delaunay")), each=ctx.get("each"))
-            again["skip_empty"], again["repeats"] = ctx.get("skip_empty", False), ctx.get("repeats", 0) + 1
-            return self._run_rest(again)
-        images = ctx["images"]              # (a sweep's sub-batch may have lost the pairs that kept nothing)
-        if not images:
-            self._last = dict(items=[], pairs=[], images=[], dropped=ctx.get("dropped", []), repeats=ctx.get("repeats", 0), outputs=[])
-            return [], [], None
         feat, kpts_all, score_all, n_tot = G["feat"], G["kpts_all"], G["score_all"], G["n_tot"]
         # ---- GraphSAGE over the merged CSR of all images (gmatcher.py:145-162, 268-269) and keypoint encoder (gmatcher.py:26-33, 87-97);
         #      desc = sage + kenc (gmatcher.py:270-271)
@@ -764,7 +713,7 @@ class GMatcher(nn.Module):
         cpr = np.asarray([q for (o0, n0), (o1, n1) in pairs for q in ((o0, n0, o1, n1), (o1, n1, o0, n0))], dtype=np.int32)
         # (ONE upload for both tables: a launch and ~15 us of host time less per call on the single-pair path)
         both = hip.upload(np.concatenate([spr, cpr]), dev, out=self._buf("attn_pr", spr.nbytes + cpr.nbytes + 32))
-        stat = self._layers(P, desc, n_tot, max(g["n_kept"] for g in images), both[:spr.shape[0]], both[spr.shape[0]:])
+        stat = self._layers(P, desc, n_tot, max(g["n_kept"] for g in images), both[:spr.shape[0]], both[spr.shape[0]:], bool(ctx.get("guards")), bool(ctx.get("repeat")))
         if stat is not None:
             self._attention_stats_enqueue(stat)
         # ---- final projection, score matrix, Sinkhorn, selection (gmatcher.py:273-294)
@@ -794,23 +743,18 @@ class GMatcher(nn.Module):
         with St("sinkhorn"):
             probs = hip.make_ot_problems(items)
             work = self._buf("ot", hip.sinkhorn_workspace_bytes(probs))
-            # stream lanes run concurrently, and the on-chip Sinkhorn kernels need every CU of the device to themselves: next to
-            # another lane's kernels they cannot get their workgroups co-resident, give up and fall to the slow rescue -- so a
-            # model with streams > 1 plans the streamed kernels up front
-            otf = hip.OT_STREAMED if self.__dict__.get("_lanes_active", 1) > 1 else 0
+            otf = hip.OT_STREAMED if ctx.get("streamed") else 0
             self.sinkhorn_plan_last = hip.sinkhorn_plan(probs, cfg['sinkhorn_iterations'], otf)   # 0 streamed / k resident launches
             # (a resident solve that gives up -- status 2: its 256 workgroups were not co-resident, e.g. next to another
             # process's kernels -- is re-solved inside this call by a dependency-free kernel before the selection runs, so the
             # matches of THIS batch are valid when the call returns; see ot_rescue_kernel.  The status words stay readable:
             # `sinkhorn_status()` after a synchronise.)
             hip.sinkhorn_match(probs, P["alpha"], cfg['sinkhorn_iterations'], cfg['match_threshold'], work, otf)
-            self._status_offs = np.cumsum([it["n"] + it["m"] + 3 for it in items]) - 1
+            status_offs = np.cumsum([it["n"] + it["m"] + 3 for it in items]) - 1
         self._finish_graphs(images, G)
-        self._last = dict(items=items, pairs=pairs, mdesc=mdesc, desc=desc, sage=sage, images=images,
-                          flat=dict(matches0=m0_all, scores0=s0_all, n0=[n0 for (_, n0), _ in pairs], n1=[n1 for _, (_, n1) in pairs]),
-                          outputs=[m0_all, m1_all, s0_all, s1_all, uv_all, mdesc, feat, kpts_all, score_all, ctx["pool"]],
-                          dropped=ctx.get("dropped", []), repeats=ctx.get("repeats", 0))
-        return items, pairs, mdesc
+        return dict(items=items, pairs=pairs, mdesc=mdesc, desc=desc, sage=sage, images=images,
+                    flat=dict(matches0=m0_all, scores0=s0_all, n0=[n0 for (_, n0), _ in pairs], n1=[n1 for _, (_, n1) in pairs]),
+                    outputs=[m0_all, m1_all, s0_all, s1_all, uv_all, mdesc, feat, kpts_all, score_all, ctx["pool"]], status_offs=status_offs)
 
     # ------------------------------------------------------------------ encoder and layer stages: launch tables
     # Each stage's launches are spelled ONCE, by its builder (_encoder_ops, _layer_ops), as a list of (stage-timer label, gims_op); the list is
@@ -963,10 +907,11 @@ class GMatcher(nn.Module):
                     aux("kenc", *self._norm_args(cur, P["kenc_ln"][i + 1], "n", out=cur))
         return lst, slots
 
-    def _layers(self, P, desc, n_tot, max_nq, self_pr, cross_pr):
+    def _layers(self, P, desc, n_tot, max_nq, self_pr, cross_pr, guards, repeat):
         """The 18 attentional layers on the residual stream desc (and its SPL32 copy self._act('dpl')): their launches depend only on the buffer
         addresses, the batch geometry and the per-layer attention tiers, which repeat from call to call in steady state -- one cached table per
-        such key.  Returns the accumulator the attention statistic of this batch went to (None: nothing was measured)."""
+        such key.  guards, repeat: the mode of the call (_run_build).  Returns the accumulator the attention statistic of this batch went to (None:
+        nothing was measured)."""
         cfg, D = self.config, self.config['descriptor_dim']
         x3 = P["x3"]
         if cfg['attention_precision'] not in ('auto', 'bf16', 'f16', 'bf16x3'):
@@ -975,12 +920,12 @@ class GMatcher(nn.Module):
             raise ValueError(f"attention_precision='{cfg['attention_precision']}' needs linear_precision='bf16x3' (the 3-pass Q/K/V projection)")
         # per-layer choice of the attention kernel family (0 bf16, 1 half, 2 split-bf16) and, in 'auto' mode, the accumulator its
         # statistic goes to
-        amode, stat = self._attention_modes(P, desc.device)
-        calibrated = bool(self.__dict__.get("_attn_auto", {}).get("calibrated"))
+        amode, stat = self._attention_modes(P, repeat)
+        calibrated = self._tiers is not None and self._tiers.calibrated
         # the device-side verdict of 'auto' (see default_config): guarded redo launches behind every bf16 / half attention launch
         # (match_pairs returns without a host synchronisation: its verdict is drawn on the device, by guarded launches; forward() ends in one and
         # repeats the batch itself when the statistic it reads back there moved a layer up -- no extra launches on the latency path)
-        guarded = stat is not None and cfg['attention_precision'] == 'auto' and calibrated and self.__dict__.get("_device_guards", False)
+        guarded = stat is not None and cfg['attention_precision'] == 'auto' and calibrated and guards
         bf, f32 = torch.bfloat16, torch.float32
         A = lambda name, cols, dt: self._act(name, n_tot, cols, dt)                     # noqa: E731
         # bf16x3: all GEMM operands travel as split-bf16 SPL32 buffers written by the producing kernel's epilogue; only the residual stream `desc`
@@ -1080,8 +1025,8 @@ class GMatcher(nn.Module):
     def sinkhorn_status(self):
         """Status word of every pair of the LAST batch of this lane (0 ok, 1 a marginal left the finite range -> that pair's
         matches are all -1); synchronises.  Status 2 (on-chip solve gave up) never survives a call: it is rescued inside."""
-        uv = self._last["outputs"][4]
-        return uv[torch.from_numpy(self._status_offs).to(uv.device)].cpu().numpy()
+        uv, offs = self._last["outputs"][4], self._last["status_offs"]
+        return uv[torch.from_numpy(offs).to(uv.device)].cpu().numpy()
 
     def _check_call(self, data, kwargs):
         if data.get('delaunay', False) and kwargs.get('mode', 'test') == "train":
@@ -1108,12 +1053,17 @@ class GMatcher(nn.Module):
         with hip.pinned_stream():                 # one stream lookup for the ~150 launches of a call
             return self._forward_eval(data, **kwargs)
 
-    def _forward_once(self, data, B, radius, percentile, min_size, last_attempt):
-        """One pass of forward()'s batch up to its host synchronisation.  None: the statistic this batch produced moved a layer of a SETTLED
-        'auto' table up -- the batch ran that layer on operands that did not suffice and the caller repeats it on the new table."""
+    def _forward_once(self, data, B, radius, percentile, min_size, guards, last_attempt):
+        """One pass of forward()'s batch up to its host synchronisation; guards: a repeat of the batch, run with the device-side guards.
+        Returns the batch's results (_run_rest) and the pinned views of its kept-index lists, or None: the statistic this batch produced
+        moved a layer of a SETTLED 'auto' table up -- the batch ran that layer on operands that did not suffice and the caller repeats it on
+        the new table."""
         images = self._ingest([(data['keypoints' + side][b], data['descriptors' + side][b], data['scores' + side][b],
                                 data['image' + side].shape) for b in range(B) for side in ("0", "1")])
-        items, pairs, mdesc = self._run(images, radius, percentile, min_size, delaunay=bool(data.get('delaunay', False)))
+        ctx = self._run_build(images, radius, percentile, min_size, delaunay=bool(data.get('delaunay', False)))
+        ctx.update(guards=guards, repeat=guards)      # the same batch again: measured like the first attempt, its outlier rows counted once
+        res = self._run_rest(ctx)
+        items = res["items"]
         # what the host needs back -- the kept-index lists the reference returns as Python lists, and the Sinkhorn status words --
         # travels in asynchronous copies into one pinned buffer behind ONE stream synchronisation (three blocking read-backs cost
         # ~0.1 ms of a 5 ms single-pair call)
@@ -1127,53 +1077,53 @@ class GMatcher(nn.Module):
             v.copy_(g["kept"], non_blocking=True)
             views.append(v)
             o += g["n_kept"]
-        uv = self._last["outputs"][4]
+        uv = res["outputs"][4]
         st = pin[o:o + len(items)].view(torch.float32)
-        for i, so in enumerate(self._status_offs.tolist()):        # (an index tensor would be a pageable upload in the middle of the stream)
+        for i, so in enumerate(res["status_offs"].tolist()):        # (an index tensor would be a pageable upload in the middle of the stream)
             st[i:i + 1].copy_(uv[so:so + 1], non_blocking=True)
         torch.cuda.current_stream().synchronize()
         # 'auto' attention: the statistic of THIS batch is in (the first call's measurement decides the next call's kernels)
-        moved = self._attention_stats_consume(self._lane, repeat=self.__dict__.get("_attn_repeat", False))
-        rare = bool(self.__dict__.get("_attn_auto", {}).get("rare_last")) and not self._device_guards
+        moved = self._attention_stats_consume(self._lane, repeat=guards)
+        rare = self._tiers is not None and self._tiers.rare_last and not guards
         if (moved or rare) and not last_attempt:
             return None
         if (st.numpy() == 2.0).any():        # cannot happen (rescued inside gims_sinkhorn_match); never return silently wrong
             raise hip.GimsHipError("the Sinkhorn solve of this batch gave up and was not rescued")
-        return images, items, pairs, mdesc, views
+        return res, views
 
-    @torch.no_grad()
-    def _forward_eval(self, data, **kwargs):
+    def _forward_batch(self, data):
+        """forward()'s batch: run it (twice where the 'auto' attention tiers ask for it), mutate `data` as the reference does, return its results."""
         radius, percentile, min_size = data.get('radius', 25), data.get('percentile', 7), data.get('min_size', 8)
         B = data['keypoints0'].shape[0]
         # forward() ends in a host synchronisation, so its 'auto' verdict is drawn THERE (no guarded launches on the latency path): a batch
         # whose statistic moves a settled layer up is repeated on the new table before anything is returned.  Tiers only move up, twice per
         # layer at most: the loop is short and a repeat is rare (a layer sharpening for the first time).
-        done = None
         for attempt in range(4):
             # the LAST attempt cannot be repeated: it runs with the device-side guards (like match_pairs), so a layer whose statistic moves up
             # once more inside it is redone at f32-class accuracy on the device -- no batch is ever returned from an under-precision tier
             # ... and so does every REPEAT: a repeat was asked for either by a layer that moved up (then the guards are idle) or by a sharply
             # peaked row inside a diffuse layer, which only the device-side redo answers (the layer is not moved up for one outlier)
-            self._device_guards = attempt >= 1
-            self._attn_repeat = attempt >= 1      # the same batch again: measured like the first attempt, its outlier rows counted once
-            try:
-                done = self._forward_once(data, B, radius, percentile, min_size, attempt == 3)
-            finally:
-                self._attn_repeat = False
+            done = self._forward_once(data, B, radius, percentile, min_size, attempt >= 1, attempt == 3)
             if done is not None:
                 break
             self._attn_forward_repeats = getattr(self, "_attn_forward_repeats", 0) + 1
-        images, items, pairs, mdesc, views = done
+        res, views = done
         # the reference's in-place dict mutation (gmatcher.py:244-252); torch.stack raises for ragged B>1, as there
         for s, side in enumerate(("0", "1")):
-            gs = [images[2 * b + s]["graph"] for b in range(B)]
+            gs = [res["images"][2 * b + s]["graph"] for b in range(B)]
             data['keypoints' + side] = _stack([h.ndata['point'] for h in gs])
             data['descriptors' + side] = _stack([h.ndata['feat'] for h in gs]).permute(0, 2, 1)
             data['scores' + side] = _stack([h.ndata['score'] for h in gs])
             data['kept_kpts%s_indices' % side] = [views[2 * b + s].tolist() for b in range(B)]
             data['graph' + side] = gs
+        return res
+
+    @torch.no_grad()
+    def _forward_eval(self, data, **kwargs):
+        res = self._forward_batch(data)
+        items, pairs, mdesc = res["items"], res["pairs"], res["mdesc"]
         if kwargs.get('mode', 'test') == "train":        # gmatcher.py:254
-            return self._forward_train(data, images, items)
+            return self._forward_train(data, res["images"], items)
         md0 = _stack([mdesc[o0:o0 + n0] for (o0, n0), _ in pairs])
         md1 = _stack([mdesc[o1:o1 + n1] for _, (o1, n1) in pairs])
         return {
@@ -1210,8 +1160,9 @@ class GMatcher(nn.Module):
         ``{'loss', 'pos_loss', 'neg_loss', 'dscores': [per pair, (n_kept0, n_kept1)], 'dbin_score'}``.  A diagnostic of the
         Sinkhorn reverse sweep for a module in eval() mode; the complete backward pass (final projection, attention layers,
         encoders, GraphSAGE) is the training step of gims_amd/trainstep.py (``model.train(); model(data, mode='train')``)."""
-        loss, pos, neg = self._forward_eval(data, mode="train")
-        items = self._last["items"]
+        res = self._forward_batch(data)
+        items = res["items"]
+        loss, pos, neg = self._forward_train(data, res["images"], items)
         dscores, dalpha = hip.sinkhorn_score_gradients(items, self._packed(items[0]["scores"].device)["alpha"], self.config['sinkhorn_iterations'],
                                                        self.config['pos_loss_weight'], self.config['neg_loss_weight'], hip.train_loss.last)
         return {"loss": loss, "pos_loss": pos, "neg_loss": neg, "dscores": dscores, "dbin_score": dalpha}
@@ -1228,11 +1179,9 @@ class GMatcher(nn.Module):
         ``per_pair_graph=True``: then every dict's own values (defaults 25 / 7 / 8, False) are honoured inside the same single pass --
         the graph build takes its parameters per image (gims_agc_build_v), the Delaunay pairs go through one Delaunay build."""
         tm0 = time.perf_counter()
-        self._device_guards = True          # no host synchronisation at the end of this call: the 'auto' verdict is drawn on the device
         n_lanes = int(self.config.get('streams', 1))
         if n_lanes < 2 or len(datas) < 2 * n_lanes:
             n_lanes = 1
-        self._lanes_active = n_lanes
         cuts = [round(i * len(datas) / n_lanes) for i in range(n_lanes + 1)]
         groups = [datas[cuts[i]:cuts[i + 1]] for i in range(n_lanes)]
         for data in datas:
@@ -1260,43 +1209,48 @@ class GMatcher(nn.Module):
                 L.wait_stream(cur)
         else:
             lanes = [cur]
-        ctxs = []
-        for gi, grp in enumerate(groups):
-            with torch.cuda.stream(lanes[gi]), hip.pinned_stream():
-                self._lane = gi
-                raw = [(data['keypoints' + side][0], data['descriptors' + side][0], data['scores' + side][0], data['image' + side].shape)
-                       for data in grp for side in ("0", "1")]
-                each = [self._graph_setting(data) for data in grp for _ in ("0", "1")] if per_pair_graph else None
-                ctxs.append(self._run_build(self._ingest(raw), *params, delaunay=delaunay, each=each))
-        tm1 = time.perf_counter()
-        outs, flats = [], []
-        for gi, grp in enumerate(groups):
-            with torch.cuda.stream(lanes[gi]), hip.pinned_stream():
-                self._lane = gi
-                items, pairs, mdesc = self._run_rest(ctxs[gi])
-                images = ctxs[gi]["images"]
-                flats.append(self._last["flat"])
-                if n_lanes > 1:
-                    for t_ in self._last["outputs"]:
-                        t_.record_stream(cur)
-                for p, (data, it) in enumerate(zip(grp, items)):
-                    for s, side in enumerate(("0", "1")):
-                        g = images[2 * p + s]["graph"]
-                        data['keypoints' + side] = g.ndata['point'][None]
-                        data['descriptors' + side] = g.ndata['feat'].t()[None]
-                        data['scores' + side] = g.ndata['score'][None]
-                        data['kept_kpts%s_indices' % side] = [images[2 * p + s]["kept"]]      # device tensor (no host sync here)
-                        data['graph' + side] = [g]
-                    (o0, n0), (o1, n1) = pairs[p]
-                    outs.append({
-                        'keypoints0': data['keypoints0'], 'keypoints1': data['keypoints1'],
-                        'descriptors0': data['descriptors0'], 'descriptors1': data['descriptors1'],
-                        'matches0': it["matches0"][None], 'matches1': it["matches1"][None],
-                        'matching_scores0': it["mscores0"][None], 'matching_scores1': it["mscores1"][None],
-                        'mdesc0': mdesc[o0:o0 + n0], 'mdesc1': mdesc[o1:o1 + n1],
-                    })
-        self._lane = 0
-        self._lanes_active = 1
+        try:
+            ctxs = []
+            for gi, grp in enumerate(groups):
+                with torch.cuda.stream(lanes[gi]), hip.pinned_stream():
+                    self._lane = gi
+                    raw = [(data['keypoints' + side][0], data['descriptors' + side][0], data['scores' + side][0], data['image' + side].shape)
+                           for data in grp for side in ("0", "1")]
+                    each = [self._graph_setting(data) for data in grp for _ in ("0", "1")] if per_pair_graph else None
+                    ctxs.append(self._run_build(self._ingest(raw), *params, delaunay=delaunay, each=each))
+                    # no host synchronisation at the end of this call: the 'auto' verdict is drawn on the device.  Stream lanes run concurrently,
+                    # and the on-chip Sinkhorn kernels need every CU of the device to themselves: next to another lane's kernels they cannot get
+                    # their workgroups co-resident, give up and fall to the slow rescue -- so such a call plans the streamed kernels up front
+                    ctxs[gi].update(guards=True, streamed=n_lanes > 1)
+            tm1 = time.perf_counter()
+            outs, flats = [], []
+            for gi, grp in enumerate(groups):
+                with torch.cuda.stream(lanes[gi]), hip.pinned_stream():
+                    self._lane = gi
+                    res = self._run_rest(ctxs[gi])
+                    items, pairs, mdesc, images = res["items"], res["pairs"], res["mdesc"], res["images"]
+                    flats.append(res["flat"])
+                    if n_lanes > 1:
+                        for t_ in res["outputs"]:
+                            t_.record_stream(cur)
+                    for p, (data, it) in enumerate(zip(grp, items)):
+                        for s, side in enumerate(("0", "1")):
+                            g = images[2 * p + s]["graph"]
+                            data['keypoints' + side] = g.ndata['point'][None]
+                            data['descriptors' + side] = g.ndata['feat'].t()[None]
+                            data['scores' + side] = g.ndata['score'][None]
+                            data['kept_kpts%s_indices' % side] = [images[2 * p + s]["kept"]]      # device tensor (no host sync here)
+                            data['graph' + side] = [g]
+                        (o0, n0), (o1, n1) = pairs[p]
+                        outs.append({
+                            'keypoints0': data['keypoints0'], 'keypoints1': data['keypoints1'],
+                            'descriptors0': data['descriptors0'], 'descriptors1': data['descriptors1'],
+                            'matches0': it["matches0"][None], 'matches1': it["matches1"][None],
+                            'matching_scores0': it["mscores0"][None], 'matching_scores1': it["mscores1"][None],
+                            'mdesc0': mdesc[o0:o0 + n0], 'mdesc1': mdesc[o1:o1 + n1],
+                        })
+        finally:
+            self._lane = 0          # (_buf hands out the scratch arena of the current lane)
         if n_lanes > 1:
             for L in lanes:
                 cur.wait_stream(L)
@@ -1352,8 +1306,6 @@ class GMatcher(nn.Module):
         if not settings:
             return []
         cfg = self.config
-        self._device_guards = True          # as in match_pairs: no host synchronisation at the end, the 'auto' verdict is drawn on the device
-        self._lanes_active, self._lane = 1, 0
         records = [None] * len(settings)
         stats = self.sweep_stats_last = dict(settings=len(settings), ingests=0, sub_batches=0, build_repeats=0)
         with hip.pinned_stream():
@@ -1372,16 +1324,17 @@ class GMatcher(nn.Module):
                 chunk = settings[c0:c0 + per]
                 images = [dict(kp=g["kp"], de=g["de"], sc=g["sc"], shape=g["shape"]) for _ in chunk for g in base]
                 ctx = self._run_build(images, None, None, None, each=[s for s in chunk for _ in (0, 1)])
-                ctx["skip_empty"] = True
-                items, pairs, mdesc = self._run_rest(ctx)
+                ctx.update(skip_empty=True, guards=True)      # as in match_pairs: no host synchronisation at the end, the 'auto' verdict is drawn on the device
+                out = self._run_rest(ctx)
+                items, pairs, mdesc = out["items"], out["pairs"], out["mdesc"]
                 stats["sub_batches"] += 1
-                stats["build_repeats"] += self._last["repeats"]
-                images, dropped = self._last["images"], set(self._last["dropped"])
+                stats["build_repeats"] += out["repeats"]
+                images, dropped = out["images"], set(out["dropped"])
                 if items:       # matches per entry: one segmented count for the sub-batch
-                    m0_all = self._last["flat"]["matches0"]
-                    ends = np.cumsum(self._last["flat"]["n0"], dtype=np.int64)
+                    m0_all = out["flat"]["matches0"]
+                    ends = np.cumsum(out["flat"]["n0"], dtype=np.int64)
                     csum = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), (m0_all > -1).cumsum(0)])
-                    n_matches = csum[hip.upload(ends, dev)] - csum[hip.upload(ends - np.asarray(self._last["flat"]["n0"], dtype=np.int64), dev)]
+                    n_matches = csum[hip.upload(ends, dev)] - csum[hip.upload(ends - np.asarray(out["flat"]["n0"], dtype=np.int64), dev)]
                 p = 0
                 live = []
                 for j, (radius, percentile, min_size, delaunay) in enumerate(chunk):

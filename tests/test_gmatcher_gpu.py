@@ -742,6 +742,25 @@ def test_two_stream_lanes_equal_single_stream(synth_sd, monkeypatch):
         np.testing.assert_allclose(a["matching_scores0"].cpu().numpy(), b["matching_scores0"].cpu().numpy(), atol=2e-5)   # on-chip vs streamed solve
 
 
+def test_a_match_pairs_call_that_raises_leaves_no_mode_behind(synth_sd):
+    """The mode of a call (stream lanes, device-side guards) travels with the call: a two-lane match_pairs that raises -- here in its argument
+    check, before any launch -- leaves nothing on the model.  The next forward() plans the on-chip Sinkhorn and returns what a fresh
+    single-stream model returns, bit for bit (a lane count that outlived the failed call made every later forward() plan the streamed kernels)."""
+    m = GMatcher({"streams": 2}).eval()
+    m.load_state_dict(synth_sd)
+    datas = [pair_to_data(synth.make_pair(256, seed), 15, 2, 7, device="cuda") for seed in (1002, 1003, 1004, 1005)]
+    datas[2] = {k: torch.cat([v, v]) if torch.is_tensor(v) else v for k, v in datas[2].items()}        # B == 2
+    with pytest.raises(ValueError, match="match_pairs takes single-pair dicts"):
+        m.match_pairs(datas)
+    fresh = GMatcher({}).eval()
+    fresh.load_state_dict(synth_sd)
+    pair = synth.make_pair(256, 1002)
+    out, ref = m(pair_to_data(pair, 15, 2, 7, device="cuda")), fresh(pair_to_data(pair, 15, 2, 7, device="cuda"))
+    assert m.sinkhorn_plan_last == fresh.sinkhorn_plan_last and m._lane == 0, (m.sinkhorn_plan_last, fresh.sinkhorn_plan_last, m._lane)
+    for k in ("matches0", "matches1", "matching_scores0", "matching_scores1"):
+        np.testing.assert_array_equal(out[k].cpu().numpy(), ref[k].cpu().numpy())
+
+
 def test_replayed_layers_equal_stepwise(synth_sd):
     """The 18 GNN layers replayed through gims_run_ops (one ABI crossing, argument table cached across calls) give exactly
     what the launch-by-launch path gives (the one that runs when stage timers are on)."""

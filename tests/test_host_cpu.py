@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from gims_amd import GMatcher, Matching, hip, synth
+from gims_amd.attention_tiers import AttentionTiers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -255,14 +256,8 @@ def test_auto_attention_routes_on_the_tail_and_the_range():
     """The decision rule of 'auto' on hand-made statistics (no GPU work: the folding of a read-back into per-layer modes):
     a head with 5 % one-hot rows among diffuse ones has a small MEAN row maximum (0.05) but a tail fraction of 0.05 -> half;
     operands beyond `attention_f16_range` -> split-bf16; layers only move up."""
-    m = GMatcher({}).eval()
-    L, H = m.n_layers, 4
-    st = m.__dict__["_attn_auto"] = dict(gen=7, mode=[2] * L, calibrated=False, peak=np.zeros((L, H)), peak_max=np.zeros((L, H)),
-                                         tail=np.zeros((L, H)), range=np.zeros((L, 3)), switched=[], batches={}, redone=np.zeros(L, dtype=np.int64))
-
-    class Ev:
-        def synchronize(self):
-            pass
+    L, H = len(GMatcher.default_config['transformer_layers']), 4
+    t = AttentionTiers(L, H, 7, dict(GMatcher.default_config))
 
     def feed(mean, tail, rng):
         raw = np.zeros((L, H + 1, 4), dtype=np.int64)
@@ -270,9 +265,8 @@ def test_auto_attention_routes_on_the_tail_and_the_range():
         raw[:, :H, 0] = np.round(np.asarray(mean) * 1000 * 2 ** 24).astype(np.int64)
         raw[:, :H, 3] = np.round(np.asarray(tail) * 1000).astype(np.int64)
         raw[:, H, :3] = np.asarray(rng, dtype=np.float32).view(np.uint32).astype(np.int64)
-        m.__dict__["_attn_pending"] = {0: [torch.from_numpy(raw), Ev(), 7]}
-        m._attention_stats_consume()
-        return m.attention_report()["modes"]
+        t.fold(raw)
+        return t.report()["modes"]
 
     mean, tail, rng = np.full((L, H), 0.01), np.zeros((L, H)), np.full((L, 3), 20.0)
     mean[1, 2] = 0.3                     # plainly peaked head
@@ -286,12 +280,12 @@ def test_auto_attention_routes_on_the_tail_and_the_range():
     rng3 = np.full((L, 3), 20.0); rng3[1, 2] = 4.0e4      # ... and a half layer whose operands grow goes up
     mean3 = mean2.copy(); mean3[1, 2] = 0.3
     modes3 = feed(mean3, np.zeros((L, H)), rng3)
-    assert modes3[1] == "bf16x3" and m.attention_report()["switched"] == [1]
+    assert modes3[1] == "bf16x3" and t.report()["switched"] == [1]
     # the device's record of a redo (stat[H][3], set by a guarded attention launch that fired) is counted per layer
     raw = np.zeros((L, H + 1, 4), dtype=np.int64)
     raw[5, H, 3] = 1
-    m.__dict__["_attn_pending"] = {0: [torch.from_numpy(raw), Ev(), 7]}
-    assert m.attention_report()["redone"].tolist() == [0] * 5 + [1] + [0] * (L - 6)
+    t.fold(raw)
+    assert t.report()["redone"].tolist() == [0] * 5 + [1] + [0] * (L - 6)
     # round 6: ONE sharply peaked row inside a diffuse bf16 layer (the head's largest row maximum reaches attention_auto_rowmax = 0.5 while mean
     # and tail stay under their thresholds) is recorded as `rare` and makes forward() repeat the batch with the device-side guards -- the layer is
     # NOT moved up; the same maximum on a layer that is not on the bf16 tier means nothing
@@ -301,33 +295,61 @@ def test_auto_attention_routes_on_the_tail_and_the_range():
     raw[:, H, :3] = np.asarray(np.full(3, 20.0), dtype=np.float32).view(np.uint32).astype(np.int64)
     raw[7, 3, 2] = int(0.97 * 2 ** 24)      # layer 7 (bf16 tier): a row at 0.97
     raw[1, 0, 2] = int(0.99 * 2 ** 24)      # layer 1 (split-bf16 by now): irrelevant
-    before = m.attention_report()["modes"]
-    m.__dict__["_attn_pending"] = {0: [torch.from_numpy(raw), Ev(), 7]}
-    assert m._attention_stats_consume() == 0
-    assert m._attn_auto["rare_last"] is True       # (speaks of the read-backs of THAT call: read before the report below consumes -- nothing -- again)
-    rep = m.attention_report()
+    before = t.report()["modes"]
+    t.begin()
+    assert t.fold(raw) == 0
+    assert t.rare_last is True       # (speaks of the read-backs folded in since begin())
+    rep = t.report()
     assert rep["modes"] == before and rep["rare"].tolist() == [0] * 7 + [1] + [0] * (L - 8)
     raw[7, 3, 2] = int(0.3 * 2 ** 24)
-    m.__dict__["_attn_pending"] = {0: [torch.from_numpy(raw), Ev(), 7]}
-    m._attention_stats_consume()
-    assert m._attn_auto["rare_last"] is False and m.attention_report()["rare"].sum() == 1
+    t.begin()
+    t.fold(raw)
+    assert t.rare_last is False and t.report()["rare"].sum() == 1
     # ... but a layer that does it on attention_auto_rare_batches (3) batches is no outlier: it moves to the half tier (cheaper than a redo per batch)
     raw[7, 3, 2] = int(0.9 * 2 ** 24)
     for k in (2, 3):
-        m.__dict__["_attn_pending"] = {0: [torch.from_numpy(raw), Ev(), 7]}
-        moved = m._attention_stats_consume()
-        assert m.attention_report()["rare"][7] == k and moved == (1 if k == 3 else 0)
-    assert m.attention_report()["modes"][7] == "f16" and m.attention_report()["modes"][8] == "bf16"
+        t.begin()
+        moved = t.fold(raw)
+        assert t.report()["rare"][7] == k and moved == (1 if k == 3 else 0)
+    assert t.report()["modes"][7] == "f16" and t.report()["modes"][8] == "bf16"
 
 
 def test_auto_attention_counts_an_outlier_batch_once():
     """forward() repeats a batch with an outlier row and reads that batch's statistic a second time: the repeat's read-back does not add to
     `rare` (attention_auto_rare_batches counts BATCHES, as match_pairs does), and `rare_last` -- forward()'s reason to repeat -- is False after
     any call that consumed no read-back (an unmeasured batch, attention_monitor_period > 1) instead of keeping an earlier batch's verdict."""
+    L, H = len(GMatcher.default_config['transformer_layers']), 4
+    t = AttentionTiers(L, H, 7, dict(GMatcher.default_config))
+    t.mode, t.calibrated = [0] * L, True
+
+    raw = np.zeros((L, H + 1, 4), dtype=np.int64)
+    raw[:, :H, 1] = 1000
+    raw[:, :H, 0] = int(0.01 * 1000 * 2 ** 24)
+    raw[:, H, :3] = np.asarray(np.full(3, 20.0), dtype=np.float32).view(np.uint32).astype(np.int64)
+    raw[7, 3, 2] = int(0.97 * 2 ** 24)
+
+    def feed(**kw):          # one consume call that finds one read-back
+        t.begin()
+        return t.fold(raw.copy(), **kw)
+
+    for batch in (1, 2):                                   # two outlier batches through forward(): attempt 0, then the repeat
+        assert feed() == 0 and t.rare_last is True and t.rare[7] == batch
+        assert feed(repeat=True) == 0 and t.rare[7] == batch and t.rare_last is True      # the repeat still sees the row (its guards answer it)
+        assert t.mode[7] == 0
+    t.begin()                                              # nothing pending: an unmeasured batch
+    assert t.rare_last is False
+    assert feed() == 1 and t.rare[7] == 3 and t.mode[7] == 1                                # the third BATCH moves the layer up
+    t.begin()
+    assert t.rare_last is False
+
+
+def test_attention_stats_consume_folds_its_own_generation_only():
+    """GMatcher._attention_stats_consume hands a lane's finished read-back to the tier table when the batch ran on that table's generation of
+    the weights, drops it when it did not (weights replaced in between), and empties the slot either way."""
     m = GMatcher({}).eval()
     L, H = m.n_layers, 4
-    st = m.__dict__["_attn_auto"] = dict(gen=7, mode=[0] * L, calibrated=True, peak=np.zeros((L, H)), peak_max=np.zeros((L, H)),
-                                         tail=np.zeros((L, H)), range=np.zeros((L, 3)), switched=[], batches={}, redone=np.zeros(L, dtype=np.int64))
+    t = m._tiers = AttentionTiers(L, H, 7, m.config)
+    t.mode, t.calibrated = [0] * L, True
 
     class Ev:
         def synchronize(self):
@@ -337,22 +359,31 @@ def test_auto_attention_counts_an_outlier_batch_once():
     raw[:, :H, 1] = 1000
     raw[:, :H, 0] = int(0.01 * 1000 * 2 ** 24)
     raw[:, H, :3] = np.asarray(np.full(3, 20.0), dtype=np.float32).view(np.uint32).astype(np.int64)
-    raw[7, 3, 2] = int(0.97 * 2 ** 24)
+    raw[2, 1, 0] = int(0.3 * 1000 * 2 ** 24)       # layer 2: a peaked head (-> half)
+    raw[7, 3, 2] = int(0.97 * 2 ** 24)             # layer 7: one outlier row
+    slot = [torch.from_numpy(raw.copy()), Ev(), 6]      # a batch of the previous weights
+    m.__dict__["_attn_pending"] = {0: slot}
+    assert m._attention_stats_consume(0) == 0 and slot[1] is None
+    assert t.mode == [0] * L and t.rare.tolist() == [0] * L and t.rare_last is False and not t.peak.any()
+    slot[1], slot[2] = Ev(), 7
+    assert m._attention_stats_consume(1) == 0 and slot[1] is not None       # another lane's consume leaves it pending
+    assert m._attention_stats_consume(0) == 1 and slot[1] is None
+    assert t.mode == [0, 0, 1] + [0] * (L - 3) and t.rare[7] == 1 and t.rare_last is True and t.switched == [2]
+    assert m._attention_stats_consume(0) == 0 and t.rare_last is False and t.rare[7] == 1       # the slot is empty: nothing is folded twice
+    assert m.attention_report()["modes"][2] == "f16"
 
-    def feed(**kw):
-        m.__dict__["_attn_pending"] = {0: [torch.from_numpy(raw.copy()), Ev(), 7]}
-        return m._attention_stats_consume(0, **kw)
 
-    for batch in (1, 2):                                   # two outlier batches through forward(): attempt 0, then the repeat
-        assert feed() == 0 and st["rare_last"] is True and st["rare"][7] == batch
-        assert feed(repeat=True) == 0 and st["rare"][7] == batch and st["rare_last"] is True      # the repeat still sees the row (its guards answer it)
-        assert st["mode"][7] == 0
-    assert m._attention_stats_consume(0) == 0 and st["rare_last"] is False                          # nothing pending: an unmeasured batch
-    assert m._attention_stats_consume() == 0 and st["rare_last"] is False
-    assert feed() == 1 and st["rare"][7] == 3 and st["mode"][7] == 1                                # the third BATCH moves the layer up
-    m.__dict__["_attn_pending"] = {}
-    m._attention_stats_consume(0)
-    assert st["rare_last"] is False
+def test_attention_tiers_constructor_creates_every_field():
+    """A fresh table reports every key GMatcher.attention_report() documents, in the shapes they keep (`rare` used to appear with the first fold)."""
+    L, H = len(GMatcher.default_config['transformer_layers']), 4
+    rep = AttentionTiers(L, H, 1, dict(GMatcher.default_config)).report()
+    assert set(rep) == {"modes", "calibrated", "peak", "peak_max", "tail", "range", "switched", "redone", "rare", "threshold", "tail_threshold"}
+    assert rep["modes"] == ["bf16x3"] * L and rep["calibrated"] is False and rep["switched"] == []
+    assert rep["peak"].shape == rep["peak_max"].shape == rep["tail"].shape == (L, H) and rep["range"].shape == (L, 3)
+    assert rep["rare"].shape == rep["redone"].shape == (L,) and rep["rare"].dtype == rep["redone"].dtype == np.int64
+    assert not rep["rare"].any() and not rep["redone"].any()
+    assert (rep["threshold"], rep["tail_threshold"]) == (0.08, 0.02)
+    assert GMatcher({}).attention_report() is None
 
 
 def test_train_backward_precision_takes_the_documented_values():
