@@ -9,347 +9,69 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
+import threading
 
+import numpy as np
 import torch
+
+from . import _abi
+from ._abi import GimsHipError
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgims_hip.so")
 
-PREC_F32, PREC_BF16X3, PREC_BF16X6 = 0, 1, 2
-LINEAR_UPPER = 1
-LINEAR_HI_ONLY = 2
-LINEAR_CONV3 = 8
-LINEAR_OUT_F16 = 16      # out_bf16 receives IEEE half (saturated) instead of bf16
-ACT_NONE, ACT_RELU = 0, 1
+ABI = _abi.parse()          # include/gims_hip.h as ctypes: every struct, prototype and `#define GIMS_X <int>` below comes from it
+_K = ABI.constants
+EXPORTS = tuple(ABI.signatures)
+ABI_VERSION = _K["GIMS_ABI_VERSION"]
+GIMS_OK, GIMS_EINVAL, GIMS_EHIP, GIMS_ENUMERIC = _K["GIMS_OK"], _K["GIMS_EINVAL"], _K["GIMS_EHIP"], _K["GIMS_ENUMERIC"]
 
+PREC_F32, PREC_BF16X3, PREC_BF16X6 = _K["GIMS_PREC_F32"], _K["GIMS_PREC_BF16X3"], _K["GIMS_PREC_BF16X6"]
+LINEAR_UPPER = _K["GIMS_LINEAR_UPPER"]
+LINEAR_HI_ONLY = _K["GIMS_LINEAR_HI_ONLY"]
+LINEAR_CONV3 = _K["GIMS_LINEAR_CONV3"]
+LINEAR_OUT_F16 = _K["GIMS_LINEAR_OUT_F16"]      # out_bf16 receives IEEE half (saturated) instead of bf16
+ACT_NONE, ACT_RELU = _K["GIMS_ACT_NONE"], _K["GIMS_ACT_RELU"]
 
-class GimsHipError(RuntimeError):
-    pass
+# The structs of the header under their Python names; every pointer member is a c_void_p (an address, or None).
+AttnGuard = ABI.structs["gims_attn_guard"]      # a launch that only runs when the statistic of the launch before it asks for the redo
+LinearArgs = ABI.structs["gims_linear_args"]
+AttnArgs = ABI.structs["gims_attn_args"]
+AuxArgs = ABI.structs["gims_aux_args"]          # one of the small kernels as an op of gims_run_ops (fn = AUX_*; p / i / f: its arguments)
+Op = ABI.structs["gims_op"]
+AgcImage = ABI.structs["gims_agc_image"]
+AgcParams = ABI.structs["gims_agc_params"]
+PackImage = ABI.structs["gims_pack_image"]
+IngestImage = ABI.structs["gims_ingest_image"]
+OtProblem = ABI.structs["gims_ot_problem"]
+PyrLevel = ABI.structs["gims_pyr_level"]
+SiftInfo = ABI.structs["gims_sift_info"]        # what gims_sift_layout reports for one image size
+LossPair = ABI.structs["gims_loss_pair"]
+Gemm = ABI.structs["gims_gemm"]
+TrainAttnProblem = ABI.structs["gims_train_attn_problem"]
+TrainAttnArgs = ABI.structs["gims_train_attn_args"]
+Segments = ABI.structs["gims_segments"]
+AdamTensor = ABI.structs["gims_adam_tensor"]
+AdamGroup = ABI.structs["gims_adam_group"]
+SgdTensor = ABI.structs["gims_sgd_tensor"]
+SgdGroup = ABI.structs["gims_sgd_group"]
+EmaTensor = ABI.structs["gims_ema_tensor"]
+EvalPair = ABI.structs["gims_eval_pair"]
+VerifySet = ABI.structs["gims_verify_set"]      # one set of correspondences for gims_verify_pairs
+LabelPair = ABI.structs["gims_label_pair"]
+NnPair = ABI.structs["gims_nn_pair"]
+AugPlan = ABI.structs["gims_aug_plan"]          # one image's colour augmentation
 
-
-class AttnGuard(C.Structure):
-    """gims_attn_guard (include/gims_hip.h): a launch that only runs when the statistic of the launch before it asks for the redo."""
-    _fields_ = [("stat", C.c_void_p), ("mean_thr", C.c_double), ("tail_thr", C.c_double), ("range_limit", C.c_double),
-                ("n_heads", C.c_int32), ("kind", C.c_int32), ("max_thr", C.c_double)]
-
-
-GUARD_PEAKED, GUARD_RANGE = 1, 2
+GUARD_PEAKED, GUARD_RANGE = _K["GIMS_GUARD_PEAKED"], _K["GIMS_GUARD_RANGE"]
+AUX_SPLIT_SPL32, AUX_SAGE_MEAN_SPLIT, AUX_KENC_FIRST = _K["GIMS_AUX_SPLIT_SPL32"], _K["GIMS_AUX_SAGE_MEAN_SPLIT"], _K["GIMS_AUX_KENC_FIRST"]
+AUX_SAGE_MEAN, AUX_KENC_FIRST_LINEAR, AUX_LAYERNORM_ACT = _K["GIMS_AUX_SAGE_MEAN"], _K["GIMS_AUX_KENC_FIRST_LINEAR"], _K["GIMS_AUX_LAYERNORM_ACT"]
+SIFT_MAX_OCTAVES, SIFT_MAX_RADIUS, SIFT_SLOTS = _K["GIMS_SIFT_MAX_OCTAVES"], _K["GIMS_SIFT_MAX_RADIUS"], _K["GIMS_SIFT_SLOTS"]
 
 
 def attn_guard(stat, kind, n_heads, mean_thr=0.0, tail_thr=0.0, range_limit=0.0, max_thr=0.0) -> AttnGuard:
     assert stat.dtype == torch.int64 and stat.is_cuda and stat.is_contiguous() and stat.numel() >= 4 * (n_heads + 1)
     return AttnGuard(stat.data_ptr(), float(mean_thr), float(tail_thr), float(range_limit), int(n_heads), int(kind), float(max_thr))
 
-
-class LinearArgs(C.Structure):
-    _fields_ = [("a0", C.c_void_p), ("lda0", C.c_int64), ("a1", C.c_void_p), ("lda1", C.c_int64),
-                ("w", C.c_void_p), ("w_lo", C.c_void_p), ("ldw", C.c_int64), ("bias", C.c_void_p),
-                ("residual", C.c_void_p), ("out_f32", C.c_void_p), ("ldc", C.c_int64),
-                ("out_bf16", C.c_void_p), ("ldc_bf16", C.c_int64), ("m", C.c_int32), ("n", C.c_int32),
-                ("k", C.c_int32), ("k0", C.c_int32), ("act", C.c_int32), ("precision", C.c_int32),
-                ("scale", C.c_float), ("a0_lo", C.c_void_p), ("a1_lo", C.c_void_p), ("out_hi", C.c_void_p),
-                ("out_lo", C.c_void_p), ("ld_split", C.c_int64), ("flags", C.c_int32),
-                ("conv_h", C.c_int32), ("conv_w", C.c_int32), ("conv_stride", C.c_int32), ("conv_reserved", C.c_int32),
-                ("guard", AttnGuard), ("range_stat", C.c_void_p)]
-
-
-class AttnArgs(C.Structure):
-    _fields_ = [("qkv", C.c_void_p), ("ld", C.c_int64), ("q_col", C.c_int32), ("k_col", C.c_int32), ("v_col", C.c_int32),
-                ("problems", C.c_void_p), ("n_problems", C.c_int32), ("max_n_q", C.c_int32), ("n_heads", C.c_int32),
-                ("out", C.c_void_p), ("ld_out", C.c_int64), ("out_hi", C.c_void_p), ("out_lo", C.c_void_p),
-                ("ld_split", C.c_int64), ("flags", C.c_int32), ("stat", C.c_void_p), ("guard", AttnGuard)]
-
-
-class AuxArgs(C.Structure):
-    """gims_aux_args: one of the small kernels as an op of gims_run_ops (fn = AUX_*; p / i / f: the entry point's pointer, integer and
-    floating-point arguments, each in declaration order)."""
-    _fields_ = [("fn", C.c_int32), ("reserved", C.c_int32), ("p", C.c_void_p * 6), ("i", C.c_int64 * 6), ("f", C.c_float * 2)]
-
-
-AUX_SPLIT_SPL32, AUX_SAGE_MEAN_SPLIT, AUX_KENC_FIRST, AUX_SAGE_MEAN, AUX_KENC_FIRST_LINEAR, AUX_LAYERNORM_ACT = range(6)
-
-
-class _OpU(C.Union):
-    _fields_ = [("lin", LinearArgs), ("att", AttnArgs), ("aux", AuxArgs)]
-
-
-class Op(C.Structure):
-    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("u", _OpU)]
-
-
-class AgcImage(C.Structure):
-    _fields_ = [("kpts", C.c_void_p), ("desc", C.c_void_p), ("ldd", C.c_int64), ("n", C.c_int32), ("d", C.c_int32),
-                ("kept", C.c_void_p), ("indptr", C.c_void_p), ("indices", C.c_void_p), ("max_edges_dir", C.c_int32),
-                ("info", C.c_void_p)]
-
-
-class AgcParams(C.Structure):
-    _fields_ = [("radius", C.c_double), ("percentile", C.c_double), ("min_size", C.c_int32), ("reserved", C.c_int32)]
-
-
-class PackImage(C.Structure):
-    _fields_ = [("kpts", C.c_void_p), ("desc", C.c_void_p), ("ldd", C.c_int64), ("score", C.c_void_p),
-                ("kept", C.c_void_p), ("indptr", C.c_void_p), ("indices", C.c_void_p),
-                ("n_kept", C.c_int32), ("n_edges", C.c_int32), ("row_off", C.c_int32), ("edge_off", C.c_int32)]
-
-
-class IngestImage(C.Structure):
-    _fields_ = [("kpts", C.c_void_p), ("desc", C.c_void_p), ("ldd", C.c_int64), ("score", C.c_void_p), ("n", C.c_int32),
-                ("row_off", C.c_int32)]
-
-
-class OtProblem(C.Structure):
-    _fields_ = [("scores", C.c_void_p), ("ld", C.c_int64), ("n", C.c_int32), ("m", C.c_int32),
-                ("matches0", C.c_void_p), ("matches1", C.c_void_p), ("mscores0", C.c_void_p),
-                ("mscores1", C.c_void_p), ("uv", C.c_void_p)]
-
-
-class PyrLevel(C.Structure):
-    _fields_ = [("offset", C.c_int64), ("h", C.c_int32), ("w", C.c_int32)]
-
-
-SIFT_MAX_OCTAVES, SIFT_MAX_RADIUS, SIFT_SLOTS = 16, 16, 18
-
-
-class SiftInfo(C.Structure):
-    """gims_sift_info (include/gims_hip.h): what gims_sift_layout reports for one image size."""
-    _fields_ = [("h", C.c_int32), ("w", C.c_int32), ("n_octaves", C.c_int32), ("reserved", C.c_int32),
-                ("image_floats", C.c_int64), ("scratch_floats", C.c_int64),
-                ("oct_h", C.c_int32 * SIFT_MAX_OCTAVES), ("oct_w", C.c_int32 * SIFT_MAX_OCTAVES),
-                ("gauss_offset", C.c_int64 * SIFT_MAX_OCTAVES), ("dog_offset", C.c_int64 * SIFT_MAX_OCTAVES),
-                ("sigma", C.c_double * 6), ("ksize", C.c_int32 * 6), ("kernel", (C.c_float * (SIFT_MAX_RADIUS + 1)) * 6)]
-
-
-class LossPair(C.Structure):
-    _fields_ = [("scores", C.c_void_p), ("ld", C.c_int64), ("n", C.c_int32), ("m", C.c_int32), ("uv", C.c_void_p),
-                ("kept0", C.c_void_p), ("kept1", C.c_void_p)]
-
-
-class Gemm(C.Structure):
-    _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("c", C.c_void_p), ("bias", C.c_void_p), ("residual", C.c_void_p),
-                ("lda", C.c_int64), ("ldb", C.c_int64), ("ldc", C.c_int64), ("ldr", C.c_int64),
-                ("sa", C.c_int64), ("sb", C.c_int64), ("sc", C.c_int64), ("sr", C.c_int64),
-                ("m", C.c_int32), ("n", C.c_int32), ("k", C.c_int32), ("batch", C.c_int32),
-                ("ta", C.c_int32), ("tb", C.c_int32), ("act", C.c_int32), ("flags", C.c_int32),
-                ("alpha", C.c_float), ("beta", C.c_float), ("work", C.c_void_p), ("work_floats", C.c_int64), ("splits", C.c_int32), ("precision", C.c_int32)]
-
-
-class TrainAttnProblem(C.Structure):
-    _fields_ = [("q_off", C.c_int32), ("nq", C.c_int32), ("k_off", C.c_int32), ("nk", C.c_int32)]
-
-
-class TrainAttnArgs(C.Structure):
-    _fields_ = [("qkv", C.c_void_p), ("ld", C.c_int64), ("rows", C.c_int64), ("d", C.c_int32), ("heads", C.c_int32), ("scale", C.c_float),
-                ("n_problems", C.c_int32), ("problems", C.POINTER(TrainAttnProblem)), ("o", C.c_void_p), ("ldo", C.c_int64), ("lse", C.c_void_p),
-                ("d_o", C.c_void_p), ("lddo", C.c_int64), ("d_qkv", C.c_void_p), ("lddq", C.c_int64), ("work", C.c_void_p), ("work_floats", C.c_size_t), ("reverse_precision", C.c_int32)]
-
-
-class Segments(C.Structure):
-    _fields_ = [("n", C.c_int32), ("off", C.c_int32 * 8), ("rows", C.c_int32 * 8)]
-
-
-class AdamTensor(C.Structure):
-    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("n", C.c_int64),
-                ("group", C.c_int32), ("reserved", C.c_int32)]
-
-
-class AdamGroup(C.Structure):
-    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
-                ("step", C.c_int64)]
-
-
-class SgdTensor(C.Structure):
-    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("momentum_buffer", C.c_void_p), ("n", C.c_int64), ("group", C.c_int32), ("first", C.c_int32)]
-
-
-class SgdGroup(C.Structure):
-    _fields_ = [("lr", C.c_double), ("momentum", C.c_double), ("dampening", C.c_double), ("weight_decay", C.c_double), ("nesterov", C.c_int32),
-                ("reserved", C.c_int32)]
-
-
-class EmaTensor(C.Structure):
-    _fields_ = [("ema", C.c_void_p), ("model", C.c_void_p), ("n", C.c_int64)]
-
-
-class EvalPair(C.Structure):
-    _fields_ = [("kpts0", C.c_void_p), ("kpts1", C.c_void_p), ("matches0", C.c_void_p), ("mscores0", C.c_void_p),
-                ("n0", C.c_int32), ("n1", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("h_gt", C.c_float * 9),
-                ("gt0", C.c_void_p), ("inlier", C.c_void_p), ("record", C.c_void_p), ("homographies", C.c_void_p)]
-
-
-class VerifySet(C.Structure):
-    """gims_verify_set (include/gims_hip.h): one set of correspondences for gims_verify_pairs."""
-    _fields_ = [("kpts0", C.c_void_p), ("kpts1", C.c_void_p), ("matches0", C.c_void_p),
-                ("n0", C.c_int32), ("n1", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("has_ref", C.c_int32), ("reserved", C.c_int32),
-                ("h_ref", C.c_float * 9), ("inlier", C.c_void_p), ("record", C.c_void_p), ("homography", C.c_void_p)]
-
-
-class LabelPair(C.Structure):
-    _fields_ = [("kpts0", C.c_void_p), ("kpts1", C.c_void_p), ("n0", C.c_int32), ("n1", C.c_int32)]
-
-
-class NnPair(C.Structure):
-    _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("lda", C.c_int64), ("ldb", C.c_int64),
-                ("n0", C.c_int32), ("n1", C.c_int32), ("d", C.c_int32), ("mutual", C.c_int32), ("threshold", C.c_float), ("reserved", C.c_int32),
-                ("nn1", C.c_void_p), ("nn2", C.c_void_p), ("d1", C.c_void_p), ("d2", C.c_void_p), ("ratio", C.c_void_p), ("match", C.c_void_p),
-                ("matches0", C.c_void_p), ("scores0", C.c_void_p), ("cnn1", C.c_void_p), ("matches1", C.c_void_p), ("info", C.c_void_p),
-                ("debug", C.c_void_p)]
-
-
-class AugPlan(C.Structure):
-    """gims_aug_plan (include/gims_hip.h): one image's colour augmentation."""
-    _fields_ = [("lut", C.c_uint8 * 256), ("kernel", C.c_float * 49), ("use_lut", C.c_int32), ("ksize", C.c_int32), ("sigma", C.c_float),
-                ("key", C.c_uint64)]
-
-
-_SIGNATURES = {
-    "gims_abi_version": (C.c_int, []),
-    "gims_last_error": (C.c_char_p, []),
-    "gims_stream_sync": (C.c_int, [C.c_void_p]),
-    "gims_upload_table": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    "gims_linear": (C.c_int, [C.POINTER(LinearArgs), C.c_void_p]),
-    "gims_linear_put": (C.c_int, [C.POINTER(LinearArgs), C.c_void_p, C.c_void_p]),
-    "gims_linear_put_many": (C.c_int, [C.POINTER(LinearArgs), C.c_int32, C.c_void_p, C.c_void_p]),
-    "gims_linear_batch": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
-    "gims_split_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "gims_ch_frn_stats": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
-    "gims_ch_pool_hw": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "gims_ch_frn_from_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
-    "gims_ch_gates": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 11),
-    "gims_ch_apply": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 7 + [C.c_int64, C.c_void_p]),
-    "gims_ch_im2col3": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
-    "gims_ch_dwconv3": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_float,
-                                  C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "gims_ch_gate_pw_pw": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 8),
-    "gims_ch_input_block": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "gims_ch_frn_block": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "gims_ch_conv_block": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                     C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "gims_ch_conv_block_first": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "gims_ch_sandglass": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "gims_ch_l2norm": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
-    "gims_ch_relu6": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
-    "gims_run_ops": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
-    "gims_run_ops_timed": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
-    "gims_events_create": (C.c_int, [C.c_int32, C.c_void_p]),
-    "gims_events_record": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "gims_events_elapsed": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
-    "gims_events_destroy": (C.c_int, [C.c_void_p, C.c_int32]),
-    "gims_ops_graph_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]),
-    "gims_ops_graph_launch": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "gims_ops_graph_destroy": (C.c_int, [C.c_void_p]),
-    "gims_split_spl3": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]),
-    "gims_split_spl32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]),
-    "gims_attention": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
-                                 C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
-                                 C.c_int32, C.c_void_p]),
-    "gims_attention_ex": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "gims_attention_stat": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
-                                      C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
-                                      C.c_int32, C.c_void_p, C.c_void_p]),
-    "gims_kenc_first": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-                                  C.c_void_p, C.c_int64, C.c_void_p]),
-    "gims_kenc_first_linear": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-                                         C.c_void_p, C.c_int64, C.c_void_p]),
-    "gims_layernorm_act": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_int32,
-                                     C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "gims_sage_mean": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
-                                 C.c_void_p, C.c_int64, C.c_void_p]),
-    "gims_sage_mean_split": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
-                                 C.c_void_p, C.c_int64, C.c_void_p]),
-    "gims_pair_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
-    "gims_gather_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
-                                   C.c_int64, C.c_void_p]),
-    "gims_agc_workspace_bytes": (C.c_size_t, [C.POINTER(AgcImage), C.c_int32]),
-    "gims_agc_workspace_bytes_ex": (C.c_size_t, [C.POINTER(AgcImage), C.c_int32, C.c_int32]),
-    "gims_agc_max_keypoints": (C.c_int32, []),
-    "gims_agc_build": (C.c_int, [C.POINTER(AgcImage), C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_void_p,
-                                 C.c_size_t, C.c_void_p]),
-    "gims_agc_build_v": (C.c_int, [C.POINTER(AgcImage), C.c_int32, C.POINTER(AgcParams), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "gims_agc_build_ex": (C.c_int, [C.POINTER(AgcImage), C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_void_p,
-                                    C.c_size_t, C.c_void_p]),
-    "gims_delaunay_workspace_bytes": (C.c_size_t, [C.POINTER(AgcImage), C.c_int32]),
-    "gims_delaunay_build": (C.c_int, [C.POINTER(AgcImage), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "gims_ingest_images": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
-                                     C.c_void_p, C.c_void_p]),
-    "gims_pack_graphs": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
-                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
-                                   C.c_void_p]),
-    "gims_sinkhorn_workspace_bytes": (C.c_size_t, [C.POINTER(OtProblem), C.c_int32]),
-    "gims_sinkhorn_plan": (C.c_int, [C.POINTER(OtProblem), C.c_int32, C.c_int32]),
-    "gims_sinkhorn_match": (C.c_int, [C.POINTER(OtProblem), C.c_int32, C.c_float, C.c_int32, C.c_float,
-                                      C.c_void_p, C.c_size_t, C.c_void_p]),
-    "gims_sinkhorn_plan_ex": (C.c_int, [C.POINTER(OtProblem), C.c_int32, C.c_int32, C.c_int32]),
-    "gims_sinkhorn_rescues": (C.c_int64, []),
-    "gims_attention_launch_counts": (C.c_int, [C.POINTER(C.c_uint64), C.c_int32, C.c_int32]),
-    "gims_sinkhorn_match_ex": (C.c_int, [C.POINTER(OtProblem), C.c_int32, C.c_float, C.c_int32, C.c_float,
-                                         C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
-    "gims_eval_workspace_bytes": (C.c_size_t, [C.POINTER(EvalPair), C.c_int32, C.c_int32]),
-    "gims_eval_pairs": (C.c_int, [C.POINTER(EvalPair), C.c_int32, C.c_float, C.c_int32, C.c_float, C.c_int32, C.c_uint64,
-                                  C.c_void_p, C.c_size_t, C.c_void_p]),
-    "gims_verify_workspace_bytes": (C.c_size_t, [C.POINTER(VerifySet), C.c_int32, C.c_int32]),
-    "gims_verify_pairs": (C.c_int, [C.POINTER(VerifySet), C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "gims_pyramid_layout": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_size_t),
-                                      C.POINTER(C.c_size_t)]),
-    "gims_pyramid_build": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "gims_patch_extract": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "gims_patch_affine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "gims_sift_layout": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(SiftInfo)]),
-    "gims_sift_pyramid": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "gims_sift_detect": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "gims_sift_compact": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "gims_warp_invert": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
-    "gims_warp_perspective": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
-                                        C.c_void_p, C.c_void_p]),
-    "gims_resize": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
-    "gims_train_labels_workspace_bytes": (C.c_size_t, [C.POINTER(LabelPair), C.c_int32]),
-    "gims_train_labels": (C.c_int, [C.POINTER(LabelPair), C.c_int32, C.c_void_p, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_size_t, C.c_void_p]),
-    "gims_sinkhorn_history_floats": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
-    "gims_sinkhorn_history": (C.c_int, [C.POINTER(OtProblem), C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "gims_sinkhorn_backward_workspace_bytes": (C.c_size_t, [C.POINTER(OtProblem), C.c_int32]),
-    "gims_sinkhorn_backward": (C.c_int, [C.POINTER(OtProblem), C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                         C.c_void_p]),
-    "gims_train_loss_grad": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
-    "gims_train_loss": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
-                                  C.c_void_p, C.c_void_p]),
-    "gims_gemm_f32": (C.c_int, [C.POINTER(Gemm), C.c_void_p]),
-    "gims_batchnorm_workspace_floats": (C.c_size_t, [C.POINTER(Segments), C.c_int32]),
-    "gims_batchnorm_train_forward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(Segments), C.c_void_p, C.c_void_p, C.c_float, C.c_float,
-                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
-    "gims_batchnorm_train_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(Segments), C.c_void_p, C.c_void_p,
-                                                C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "gims_layernorm_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_int32,
-                                          C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "gims_softmax_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_void_p]),
-    "gims_softmax_rows_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_void_p]),
-    "gims_train_attention_workspace_floats": (C.c_size_t, [C.c_int64, C.c_int32]),
-    "gims_train_attention_forward": (C.c_int, [C.POINTER(TrainAttnArgs), C.c_void_p]),
-    "gims_train_attention_backward": (C.c_int, [C.POINTER(TrainAttnArgs), C.c_void_p]),
-    "gims_colsum_workspace_floats": (C.c_size_t, [C.c_int64, C.c_int32]),
-    "gims_colsum": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "gims_elementwise": (C.c_int, [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_float,
-                                   C.c_void_p]),
-    "gims_permute3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_int64] * 6 + [C.c_int32, C.c_void_p]),
-    "gims_head_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
-    "gims_sage_mean_transposed": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
-    "gims_normalize_keypoints": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    "gims_adam_step": (C.c_int, [C.POINTER(AdamTensor), C.c_int32, C.POINTER(AdamGroup), C.c_int32, C.c_void_p]),
-    "gims_sgd_step": (C.c_int, [C.POINTER(SgdTensor), C.c_int32, C.POINTER(SgdGroup), C.c_int32, C.c_void_p]),
-    "gims_ema_update": (C.c_int, [C.POINTER(EmaTensor), C.c_int32, C.c_double, C.c_void_p]),
-    "gims_ot_matrix": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
-                                 C.c_void_p]),
-    "gims_nn_workspace_bytes": (C.c_size_t, [C.POINTER(NnPair), C.c_int32, C.c_int32]),
-    "gims_nn_match": (C.c_int, [C.POINTER(NnPair), C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "gims_color_aug_workspace_bytes": (C.c_size_t, [C.c_int32]),
-    "gims_color_aug": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(AugPlan), C.c_void_p, C.c_void_p, C.c_size_t,
-                                 C.c_void_p]),
-}
-EXPORTS = tuple(_SIGNATURES)
 
 _lib = None
 
@@ -364,7 +86,7 @@ def load(path: str | None = None):
         raise GimsHipError(f"{p} is missing: build it with `python -m gims_amd.build` "
                            "(hipcc --offload-arch=gfx950); there is no CPU fallback")
     lib = C.CDLL(p)
-    for name, (res, args) in _SIGNATURES.items():
+    for name, (res, args) in ABI.signatures.items():
         fn = getattr(lib, name)           # AttributeError if the .so does not export a declared symbol
         fn.restype, fn.argtypes = res, args
     if lib.gims_abi_version() != ABI_VERSION:
@@ -374,17 +96,12 @@ def load(path: str | None = None):
     return lib
 
 
-GIMS_OK, GIMS_EINVAL, GIMS_EHIP, GIMS_ENUMERIC = 0, -1, -2, -3          # include/gims_hip.h
-ABI_VERSION = 2                     # GIMS_ABI_VERSION of the header these ctypes mirrors were written against
-
 
 def _check(rc: int, what: str):
     if rc != 0:
         msg = load().gims_last_error()
         raise GimsHipError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
 
-
-import threading  # noqa: E402
 
 _TLS = threading.local()    # per thread: .pin = the raw hipStream_t pinned by pinned_stream(), .gemm_prec = gemm()'s default precision
 
@@ -441,7 +158,6 @@ def upload(arr, device="cuda", out=None) -> torch.Tensor:
     """Small host table (numpy array) -> device tensor, asynchronously and in stream order (gims_upload_table): the
     bytes ride in kernel arguments, so unlike ``torch.tensor(..., device=...)`` / ``.to(device)`` from pageable memory
     the calling thread never waits for the stream to drain."""
-    import numpy as np
     a = np.ascontiguousarray(arr)
     dt = _NP2TORCH[a.dtype.name]
     nbytes = a.nbytes
@@ -687,9 +403,9 @@ def split_bf16(x: torch.Tensor):
 ATTN_Q_SCALE = 0.125 * 1.4426950408889634      # log2(e) / sqrt(64): what q_prescaled=True expects folded into Q
 
 
-ATTN_X3 = 2
-ATTN_NO_RANGE = 8   # a measured launch leaves the range row alone (the projection reported it: linear_args(range_stat=...))
-ATTN_F16 = 4        # qkv holds IEEE half (gims_linear with LINEAR_OUT_F16); v_mfma_f32_32x32x16_f16 kernels
+ATTN_X3 = _K["GIMS_ATTN_X3"]
+ATTN_NO_RANGE = _K["GIMS_ATTN_NO_RANGE"]   # a measured launch leaves the range row alone (the projection reported it: linear_args(range_stat=...))
+ATTN_F16 = _K["GIMS_ATTN_F16"]        # qkv holds IEEE half (gims_linear with LINEAR_OUT_F16); v_mfma_f32_32x32x16_f16 kernels
 
 
 ATTN_STAT_SCALE = float(1 << 24)       # fixed point of the row maxima in gims_attention_stat's accumulator
@@ -801,7 +517,7 @@ def agc_workspace_bytes(images, flags=None) -> int:
     return int(load().gims_agc_workspace_bytes_ex(images, len(images), int(flags)))
 
 
-AGC_ROBUST = 1               # gims_agc_build_ex flags (include/gims_hip.h)
+AGC_ROBUST = _K["GIMS_AGC_ROBUST"]               # gims_agc_build_ex flags
 AGC_INFO_OVERFLOW, AGC_INFO_WINDOW_MISSED = 1, 2     # bits of info[7]
 
 
@@ -823,7 +539,7 @@ def agc_build_each(images, params, work: torch.Tensor, flags=0):
            "gims_agc_build_v")
 
 
-DT_INFO_DEGENERATE, DT_INFO_ASYMMETRIC = 4, 8     # bits of info[7] set by delaunay_build (bit 0: AGC_INFO_OVERFLOW, same meaning)
+DT_INFO_DEGENERATE, DT_INFO_ASYMMETRIC = _K["GIMS_DT_INFO_DEGENERATE"], _K["GIMS_DT_INFO_ASYMMETRIC"]     # bits of info[7] set by delaunay_build (bit 0: AGC_INFO_OVERFLOW, same meaning)
 
 
 def delaunay_workspace_bytes(images) -> int:
@@ -860,19 +576,12 @@ def ingest_images(items, d, desc_out, kpts_out, score_out):
     return dev_arr
 
 
-PACK_DTYPE = None
+PACK_DTYPE = np.dtype(PackImage)
 
 
 def pack_table(images_ptrs):
-    """numpy structured array mirroring gims_pack_image (one record per image) with the pointer columns filled;
+    """numpy structured array of gims_pack_image records (one per image) with the pointer columns filled;
     the count/offset columns are filled after the graph build's host sync (vectorised: no per-image Python work then)."""
-    import numpy as np
-    global PACK_DTYPE
-    if PACK_DTYPE is None:
-        PACK_DTYPE = np.dtype([("kpts", "<u8"), ("desc", "<u8"), ("ldd", "<i8"), ("score", "<u8"), ("kept", "<u8"),
-                               ("indptr", "<u8"), ("indices", "<u8"), ("n_kept", "<i4"), ("n_edges", "<i4"),
-                               ("row_off", "<i4"), ("edge_off", "<i4")])
-        assert PACK_DTYPE.itemsize == C.sizeof(PackImage)
     t = np.zeros(len(images_ptrs), dtype=PACK_DTYPE)
     for i, r in enumerate(images_ptrs):
         t[i] = r + (0, 0, 0, 0)
@@ -918,7 +627,7 @@ def sinkhorn_workspace_bytes(problems) -> int:
     return int(load().gims_sinkhorn_workspace_bytes(problems, len(problems)))
 
 
-OT_STREAMED = 1      # flag of sinkhorn_plan / sinkhorn_match: never an on-chip kernel (concurrent streams on one GPU)
+OT_STREAMED = _K["GIMS_OT_STREAMED"]      # flag of sinkhorn_plan / sinkhorn_match: never an on-chip kernel (concurrent streams on one GPU)
 
 
 def sinkhorn_plan(problems, iters: int, flags: int = 0) -> int:
@@ -967,7 +676,6 @@ def eval_pairs(items, dist_thresh=3.0, n_iters=3, ransac_thresh=3.0, ransac_iter
     """items: list of dicts with device tensors kpts0 [n0,2] f32, kpts1 [n1,2] f32, matches0 [n0] int64, mscores0 [n0] f32,
     h_gt (3x3 array-like), height, width, and outputs gt0 [n0] int32, inlier [n0] uint8, record [16] f32,
     homographies [18] f32.  One batched asynchronous call; see include/gims_hip.h."""
-    import numpy as np
     lib = load()
     arr = (EvalPair * len(items))()
     for i, it in enumerate(items):
@@ -996,7 +704,6 @@ def verify_pairs(items, thresh=3.0, iters=3000, lo_iters=8, seed=0, work=None):
     """items: list of dicts with device tensors kpts0 [n0,2] f32, kpts1 [n1,2] f32, matches0 [n0] int64 or None (identity pairing, n0 == n1),
     optionally h_ref (3x3 array-like) with height / width, and outputs inlier [n0] uint8, record [8] f32 (VERIFY_FIELDS), homography [9] f32.
     One batched asynchronous call; returns the workspace (keep it alive until the stream has passed the call).  See include/gims_hip.h."""
-    import numpy as np
     lib = load()
     arr = (VerifySet * len(items))()
     for i, it in enumerate(items):
@@ -1024,7 +731,7 @@ def verify_pairs(items, thresh=3.0, iters=3000, lo_iters=8, seed=0, work=None):
 
 
 # ------------------------------------------------------------------------------------------------ descriptor baselines
-NN_EXHAUSTIVE = 1            # gims_nn_match flag: every row through the exhaustive float64 path
+NN_EXHAUSTIVE = _K["GIMS_NN_EXHAUSTIVE"]            # gims_nn_match flag: every row through the exhaustive float64 path
 NN_OUTPUTS = (("nn1", torch.int32), ("nn2", torch.int32), ("d1", torch.float32), ("d2", torch.float32), ("ratio", torch.float32),
               ("match", torch.uint8), ("matches0", torch.int64), ("scores0", torch.float32))
 
@@ -1190,7 +897,6 @@ def train_loss(items, kept0, kept1, gt: torch.Tensor, alpha: float, pos_weight: 
     """forward_train's loss from the solved potentials (gims_train_loss).  items: the per-pair dicts given to make_ot_problems
     (scores, n, m, uv); kept0 / kept1: per pair the int32 device tensors of kept original ids; gt: [K, 3] int64 device tensor
     (b, i0, i1).  Returns (out3 f32 [3] = loss, pos, neg; per-row loss vector [K])."""
-    import numpy as np
     dev = gt.device
     assert gt.dtype == torch.int64 and gt.is_contiguous() and (gt.numel() == 0 or gt.shape[1] == 3)
     B = len(items)
@@ -1234,7 +940,6 @@ def sinkhorn_score_gradients(items, alpha: float, iters: int, pos_weight: float,
         hists = sinkhorn_history(items, alpha, iters)
     hp = (C.c_void_p * len(items))(*[h.data_ptr() for h in hists])
     dzs = [torch.zeros((it["n"] + 1, it["m"] + 1), dtype=torch.float32, device=dev) for it in items]
-    import numpy as np
     dz_tab = upload(np.asarray([d.data_ptr() for d in dzs], dtype=np.int64), dev)
     st = loss_state
     _check(lib.gims_train_loss_grad(_p(st["table"]), st["B"], _p(st["gt"]), st["K"], float(alpha), _p(st["tag"]), float(pos_weight), float(neg_weight),
@@ -1258,7 +963,6 @@ def pyramid_layout(h: int, w: int, c: int = 3):
 
 def pyramid_build(img: torch.Tensor):
     """img uint8 [H, W, 3] on the device -> (pyramid buffer uint8, ctypes level table, device level table)."""
-    import numpy as np
     assert img.dtype == torch.uint8 and img.is_cuda and img.dim() == 3 and img.is_contiguous()
     h, w, c = img.shape
     levels, pb, sb = pyramid_layout(h, w, c)
@@ -1378,7 +1082,7 @@ def patch_affine(kp4: torch.Tensor, kp_octave: torch.Tensor):
 
 
 # ------------------------------------------------------------------------------------------------ training step
-EW_SCALE, EW_ADD, EW_RELU_MASK, EW_RELU, EW_ACC = 0, 1, 2, 3, 4
+EW_SCALE, EW_ADD, EW_RELU_MASK, EW_RELU, EW_ACC = (_K["GIMS_EW_" + k] for k in ("SCALE", "ADD", "RELU_MASK", "RELU", "ACC"))
 
 
 def _operand(x: torch.Tensor):
@@ -1520,7 +1224,7 @@ def train_attn_problems(problems):
     return arr, len(problems)
 
 
-TRAIN_ATTN_REVERSE_F32, TRAIN_ATTN_REVERSE_BF16X3 = 0, 1
+TRAIN_ATTN_REVERSE_F32, TRAIN_ATTN_REVERSE_BF16X3 = _K["GIMS_TRAIN_ATTN_REVERSE_F32"], _K["GIMS_TRAIN_ATTN_REVERSE_BF16X3"]
 
 
 def _train_attn_args(qkv, problems, heads, o, lse, d_o=None, d_qkv=None, reverse_precision=1):
@@ -1534,7 +1238,7 @@ def _train_attn_args(qkv, problems, heads, o, lse, d_o=None, d_qkv=None, reverse
             _colsum_retired.append(w)                 # (see colsum: a launch on a non-torch stream may still read the outgrown buffer)
         w = _tattn_work[key] = torch.empty(need, dtype=torch.float32, device=qkv.device)
     arr, n = problems if isinstance(problems, tuple) else train_attn_problems(problems)
-    g = TrainAttnArgs(qkv.data_ptr(), qkv.stride(0), rows, d, heads, 1.0 / math.sqrt(d // heads), n, arr, o.data_ptr(), o.stride(0), lse.data_ptr(),
+    g = TrainAttnArgs(qkv.data_ptr(), qkv.stride(0), rows, d, heads, 1.0 / math.sqrt(d // heads), n, C.addressof(arr), o.data_ptr(), o.stride(0), lse.data_ptr(),
                       _p(d_o), d_o.stride(0) if d_o is not None else 0, _p(d_qkv), d_qkv.stride(0) if d_qkv is not None else 0, w.data_ptr(), w.numel(),
                       int(reverse_precision))
     return g, arr
@@ -1635,49 +1339,46 @@ def head_pack(proj_w, proj_b, merge_w, wqkv, bqkv, wm, heads: int, to_params: bo
     _check(load().gims_head_pack(pw, pb, _p(merge_w), _p(wqkv), _p(bqkv), _p(wm), merge_w.shape[0], int(heads), int(to_params), _stream()), "gims_head_pack")
 
 
-ADAM_TENSOR_DTYPE = [("param", "<u8"), ("grad", "<u8"), ("exp_avg", "<u8"), ("exp_avg_sq", "<u8"), ("n", "<i8"), ("group", "<i4"), ("reserved", "<i4")]
+ADAM_TENSOR_DTYPE = np.dtype(AdamTensor)
 
 
 def adam_step(table, groups):
     """One fused Adam step (gims_adam_step).  table: C-contiguous NumPy structured array of dtype ADAM_TENSOR_DTYPE (= gims_adam_tensor:
     device pointers of contiguous float32 tensors, element count, group index); groups: at most 8 dicts with lr, beta1, beta2, eps,
     weight_decay, step (1-based, after the increment)."""
-    import numpy as np
-    assert table.dtype == np.dtype(ADAM_TENSOR_DTYPE) and table.flags["C_CONTIGUOUS"] and table.dtype.itemsize == C.sizeof(AdamTensor)
+    assert table.dtype == ADAM_TENSOR_DTYPE and table.flags["C_CONTIGUOUS"]
     gt = (AdamGroup * max(len(groups), 1))()
     for i, g in enumerate(groups):
         gt[i].lr, gt[i].beta1, gt[i].beta2, gt[i].eps, gt[i].weight_decay, gt[i].step = (float(g["lr"]), float(g["beta1"]), float(g["beta2"]), float(g["eps"]),
                                                                                       float(g["weight_decay"]), int(g["step"]))
-    _check(load().gims_adam_step(table.ctypes.data_as(C.POINTER(AdamTensor)), len(table), gt, len(groups), _stream()), "gims_adam_step")
+    _check(load().gims_adam_step(table.ctypes.data, len(table), gt, len(groups), _stream()), "gims_adam_step")
 
 
-SGD_TENSOR_DTYPE = [("param", "<u8"), ("grad", "<u8"), ("momentum_buffer", "<u8"), ("n", "<i8"), ("group", "<i4"), ("first", "<i4")]
-EMA_TENSOR_DTYPE = [("ema", "<u8"), ("model", "<u8"), ("n", "<i8")]
+SGD_TENSOR_DTYPE = np.dtype(SgdTensor)
+EMA_TENSOR_DTYPE = np.dtype(EmaTensor)
 
 
 def sgd_step(table, groups):
     """One fused SGD step (gims_sgd_step).  table: C-contiguous NumPy structured array of dtype SGD_TENSOR_DTYPE (= gims_sgd_tensor: device
     pointers of contiguous float32 tensors, element count, group index, first = the momentum buffer holds nothing yet); groups: 1 to 8
     dicts with lr, momentum, dampening, weight_decay, nesterov."""
-    import numpy as np
-    assert table.dtype == np.dtype(SGD_TENSOR_DTYPE) and table.flags["C_CONTIGUOUS"] and table.dtype.itemsize == C.sizeof(SgdTensor)
+    assert table.dtype == SGD_TENSOR_DTYPE and table.flags["C_CONTIGUOUS"]
     gt = (SgdGroup * max(len(groups), 1))()
     for i, g in enumerate(groups):
         gt[i].lr, gt[i].momentum, gt[i].dampening, gt[i].weight_decay, gt[i].nesterov = (float(g["lr"]), float(g["momentum"]), float(g["dampening"]),
                                                                                          float(g["weight_decay"]), int(bool(g["nesterov"])))
-    _check(load().gims_sgd_step(table.ctypes.data_as(C.POINTER(SgdTensor)), len(table), gt, len(groups), _stream()), "gims_sgd_step")
+    _check(load().gims_sgd_step(table.ctypes.data, len(table), gt, len(groups), _stream()), "gims_sgd_step")
 
 
 def ema_update(table, decay):
     """ema = ema * decay + (1 - decay) * model over a table of tensors (gims_ema_update).  table: C-contiguous NumPy structured array of
     dtype EMA_TENSOR_DTYPE (= gims_ema_tensor: device pointers of contiguous float32 tensors and their element count)."""
-    import numpy as np
-    assert table.dtype == np.dtype(EMA_TENSOR_DTYPE) and table.flags["C_CONTIGUOUS"] and table.dtype.itemsize == C.sizeof(EmaTensor)
-    _check(load().gims_ema_update(table.ctypes.data_as(C.POINTER(EmaTensor)), len(table), float(decay), _stream()), "gims_ema_update")
+    assert table.dtype == EMA_TENSOR_DTYPE and table.flags["C_CONTIGUOUS"]
+    _check(load().gims_ema_update(table.ctypes.data, len(table), float(decay), _stream()), "gims_ema_update")
 
 
 # ------------------------------------------------------------------------------------------------ training data from images (DESIGN.md 4.9)
-INTER_LINEAR, INTER_AREA = 1, 3          # cv2's values (GIMS_INTER_* in include/gims_hip.h)
+INTER_LINEAR, INTER_AREA = _K["GIMS_INTER_LINEAR"], _K["GIMS_INTER_AREA"]          # cv2's values
 
 
 def _image_batch(images: torch.Tensor):
@@ -1689,7 +1390,6 @@ def _image_batch(images: torch.Tensor):
 
 def warp_invert(m):
     """cv::invert(M, DECOMP_LU) of float64 [n, 3, 3] matrices on the host (gims_warp_invert): what warp_perspective samples through."""
-    import numpy as np
     a = np.ascontiguousarray(np.asarray(m, dtype=np.float64).reshape(-1, 9))
     out = np.empty_like(a)
     _check(load().gims_warp_invert(a.ctypes.data, len(a), out.ctypes.data), "gims_warp_invert")
@@ -1699,7 +1399,6 @@ def warp_invert(m):
 def warp_perspective(images: torch.Tensor, ms, dsize, out=None):
     """cv2.warpPerspective(img, M, dsize) (INTER_LINEAR, BORDER_CONSTANT 0) for a batch: images uint8 [B, H, W(, 3)] on the device,
     ms float64-convertible [B, 3, 3] (host), dsize (w, h) -> uint8 [B, h, w(, 3)] on the device.  One launch for the batch."""
-    import numpy as np
     t = _image_batch(images)
     B, H, W, c = t.shape
     dw, dh = int(dsize[0]), int(dsize[1])

@@ -21,34 +21,106 @@ def test_library_exports_every_declared_symbol():
     declared = set(re.findall(r"\b(gims_[a-z0-9_]+)\s*\(", hdr))
     assert len(declared) >= 20
     assert declared == set(hip.EXPORTS), declared ^ set(hip.EXPORTS)
+    assert len(hip.EXPORTS) == 110 and len(hip.ABI.structs) == 28          # at this commit: a parser that drops a declaration fails here
     lib = ctypes.CDLL(hip.LIB_PATH)
     for name in declared:
         assert hasattr(lib, name), name
     assert hip.load().gims_abi_version() == hip.ABI_VERSION == 2
 
 
-def test_struct_layouts_match_header(tmp_path):
-    """Sizes and field offsets of the ctypes mirrors against what a C compiler makes of include/gims_hip.h (gcc, LP64)."""
+def _gcc(tmp_path, code, run=True):
+    """Compile C code that includes the header (gcc, LP64); run=True: link, run it and return its "key value" output lines as a dict."""
     import subprocess
-    pairs = [("gims_linear_args", hip.LinearArgs, ["a0", "w", "bias", "out_f32", "m", "act", "scale", "a0_lo", "out_hi", "ld_split", "flags", "conv_h", "guard", "range_stat"]),
-             ("gims_attn_guard", hip.AttnGuard, ["stat", "mean_thr", "range_limit", "n_heads", "kind", "max_thr"]),
-             ("gims_attn_args", hip.AttnArgs, ["qkv", "q_col", "problems", "n_heads", "out", "ld_split", "flags", "stat", "guard"]),
-             ("gims_train_attn_problem", hip.TrainAttnProblem, ["nk"]),
-             ("gims_train_attn_args", hip.TrainAttnArgs, ["qkv", "rows", "d", "scale", "problems", "o", "lse", "d_o", "d_qkv", "work", "work_floats", "reverse_precision"]),
-             ("gims_ot_problem", hip.OtProblem, []), ("gims_agc_image", hip.AgcImage, ["kept", "max_edges_dir", "info"]),
-             ("gims_pack_image", hip.PackImage, []), ("gims_ingest_image", hip.IngestImage, []), ("gims_op", hip.Op, ["u"]),
-             ("gims_aux_args", hip.AuxArgs, ["fn", "p", "i", "f"])]
-    body = "".join('printf("%s %%zu\\n", sizeof(%s));\n' % (c, c) + "".join('printf("%s.%s %%zu\\n", offsetof(%s, %s));\n' % (c, f, c, f) for f in fs)
-                   for c, _, fs in pairs)
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "gims_hip.h"\nint main(void) {\n' + body + "return 0; }\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = dict(line.split() for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    for c, py, fs in pairs:
-        assert int(got[c]) == ctypes.sizeof(py), (c, got[c], ctypes.sizeof(py))
-        for f in fs:
-            assert int(got[f"{c}.{f}"]) == getattr(py, f).offset, (c, f)
+    src, exe = tmp_path / "abi.c", tmp_path / "abi"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "gims_hip.h"\n' + code)
+    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)] + ([] if run else ["-c"]), check=True)
+    if run:
+        return dict(line.rsplit(" ", 1) for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+
+
+def _layout(c_name, cls, path="", base=0):
+    """{C expression: value} of the offset and the size of every field of a ctypes class; the members of a union by their member path."""
+    out = {}
+    for f, t in cls._fields_:
+        d = getattr(cls, f)
+        out[f"offsetof({c_name}, {path}{f})"] = base + d.offset
+        out[f"sizeof((({c_name}*)0)->{path}{f})"] = d.size
+        if issubclass(t, ctypes.Union):
+            out.update(_layout(c_name, t, f"{path}{f}.", base + d.offset))
+    return out
+
+
+def _check_layouts(tmp_path, structs):
+    """sizeof of every struct in {C name: ctypes class}, and offset and size of every field, against a gcc-compiled program."""
+    want = {}
+    for c_name, cls in structs.items():
+        want[f"sizeof({c_name})"] = ctypes.sizeof(cls)
+        want.update(_layout(c_name, cls))
+    got = _gcc(tmp_path, "int main(void) {\n" + "".join('printf("%s %%zu\\n", (size_t)%s);\n' % (e, e) for e in want) + "return 0; }\n")
+    assert {e: int(v) for e, v in got.items()} == want
+    return want
+
+
+def test_struct_layouts_match_header(tmp_path):
+    """Size of every struct the binding derives from include/gims_hip.h, and offset and size of every field, against what a C compiler
+    makes of the header (gcc, LP64)."""
+    want = _check_layouts(tmp_path, hip.ABI.structs)
+    assert "offsetof(gims_op, u.aux)" in want and "sizeof(((gims_sift_info*)0)->kernel)" in want
+
+
+def test_optimizer_table_layouts_match_header(tmp_path):
+    """The SGD / EMA table structs against the header (same harness), and the NumPy dtypes the optimizers build their tables with
+    against those structs."""
+    _check_layouts(tmp_path, {c: hip.ABI.structs[c] for c in ("gims_sgd_tensor", "gims_sgd_group", "gims_ema_tensor", "gims_adam_tensor")})
+    for py, dt in ((hip.AdamTensor, hip.ADAM_TENSOR_DTYPE), (hip.SgdTensor, hip.SGD_TENSOR_DTYPE), (hip.EmaTensor, hip.EMA_TENSOR_DTYPE)):
+        d = np.dtype(dt)
+        assert d.itemsize == ctypes.sizeof(py) and list(d.names) == [f[0] for f in py._fields_]
+        assert [d.fields[n][1] for n in d.names] == [getattr(py, n).offset for n in d.names]
+    assert ctypes.sizeof(hip.SgdTensor) == 40 and ctypes.sizeof(hip.SgdGroup) == 40 and ctypes.sizeof(hip.EmaTensor) == 24
+    assert hip.load().gims_abi_version() == 2
+
+
+def test_prototypes_and_scalar_types_match_the_compiler(tmp_path):
+    """Every prototype the binding read from the header, rebuilt from the parsed type text, is the type gcc gives the function; every C
+    scalar has the size and the signedness of the ctypes type it is mapped to."""
+    from gims_amd import _abi
+    assert set(hip.ABI.c_types) == set(hip.ABI.signatures) == set(hip.EXPORTS)
+    code = ""
+    for name, (ret, args) in hip.ABI.c_types.items():
+        assert len(args) == len(hip.ABI.signatures[name][1])
+        code += '_Static_assert(__builtin_types_compatible_p(__typeof__(&%s), %s (*)(%s)), "%s");\n' % (name, ret, ", ".join(args) or "void", name)
+    for c, py in _abi.SCALARS.items():
+        code += '_Static_assert(sizeof(%s) == %d, "sizeof(%s)");\n' % (c, ctypes.sizeof(py), c)
+        code += '_Static_assert(((%s)-1 < 0) == %d, "signedness of %s");\n' % (c, py(-1).value < 0, c)
+    _gcc(tmp_path, code, run=False)
+
+
+def test_constants_equal_the_header():
+    """Every `#define GIMS_X <integer>` of the header that the binding has a name for (hip.X, or hip.GIMS_X for the error codes)."""
+    checked = 0
+    for name, value in hip.ABI.constants.items():
+        for py in (name, name[len("GIMS_"):]):
+            if hasattr(hip, py) and name != "GIMS_ATTN_KERNEL_KINDS":
+                assert getattr(hip, py) == value and isinstance(getattr(hip, py), int), name
+                checked += 1
+    assert checked >= 42                                                     # the names the binding had when the mirrors were hand-written
+    assert len(hip.ATTN_KERNEL_KINDS) == hip.ABI.constants["GIMS_ATTN_KERNEL_KINDS"] == 6
+
+
+def test_header_parser_rejects_what_it_cannot_read():
+    """An unknown type, a missing ';': the parser raises and names the text, never skips."""
+    from gims_amd import _abi
+    good = "#define GIMS_N 4\ntypedef struct gims_t { int32_t a, b[GIMS_N + 1]; const float* p; } gims_t;\nint gims_f(const gims_t* t, void* stream);\n"
+    abi = _abi.parse_text(good)
+    assert ctypes.sizeof(abi.structs["gims_t"]) == 32 and abi.signatures["gims_f"] == (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p])
+    for bad, named in (("int gims_g(wchar_t x);\n", "wchar_t"), ("int gims_g(const wchar_t* x);\n", "wchar_t"), ("int gims_g(int32_t a)\nint gims_h(void);\n", "gims_g(int32_t a)"),
+                       ("typedef struct gims_u { unsigned long a; } gims_u;\n", "unsigned long a"), ("typedef struct gims_u { int32_t a; int32_t b } gims_u;\n", "int32_t b"),
+                       ("typedef struct gims_u { int32_t a; } gims_u\n", "typedef struct gims_u"), ("#define GIMS_S \"text\"\n", "text"),
+                       ("int gims_g(int32_t);\n", "gims_g")):
+        with pytest.raises(hip.GimsHipError, match="line [34]: .*" + re.escape(named)):
+            _abi.parse_text(good + bad)
+    with pytest.raises(hip.GimsHipError, match="nowhere.h"):
+        _abi.parse("/nowhere.h")
 
 
 def test_pyramid_layout_equals_the_reference_schedule(golden_dir):
@@ -201,7 +273,7 @@ def test_adam_table_layout_and_cpu_refusal():
     from gims_amd import hip
     from gims_amd.optim import Adam
     assert C.sizeof(hip.AdamTensor) == 48 == np.dtype(hip.ADAM_TENSOR_DTYPE).itemsize
-    assert [f[0] for f in hip.AdamTensor._fields_] == [f[0] for f in hip.ADAM_TENSOR_DTYPE]
+    assert [f[0] for f in hip.AdamTensor._fields_] == list(np.dtype(hip.ADAM_TENSOR_DTYPE).names)
     assert C.sizeof(hip.AdamGroup) == 48
     p = [torch.nn.Parameter(torch.zeros(4))]
     with pytest.raises(NotImplementedError):

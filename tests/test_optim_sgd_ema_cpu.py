@@ -1,42 +1,15 @@
 """gims_amd.optim.SGD / ModelEMA / param_groups and their entry points gims_sgd_step / gims_ema_update (csrc/optim.hip) as far as they
-can be checked without a GPU: table layouts against the header, argument rejection before any HIP call, the parameter-group rule of
-train.py:42-51, the constructors, and the checkpoint layout train.py:155-160 writes."""
-import ctypes as C
+can be checked without a GPU: argument rejection before any HIP call, the parameter-group rule of train.py:42-51, the constructors, and
+the checkpoint layout train.py:155-160 writes.  (The table layouts are checked in test_host_cpu.py, on the harness every struct of the header shares.)"""
 import math
-import os
-import subprocess
 
-import numpy as np
 import pytest
 import torch
 
 from gims_amd import GMatcher, hip
 from gims_amd.optim import SGD, ModelEMA, param_groups
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL, OK = -1, 0
-
-
-def test_table_layouts_match_header(tmp_path):
-    """Sizes and field offsets of the three ctypes mirrors and the NumPy dtypes against what gcc makes of include/gims_hip.h."""
-    pairs = [("gims_sgd_tensor", hip.SgdTensor, hip.SGD_TENSOR_DTYPE), ("gims_sgd_group", hip.SgdGroup, None), ("gims_ema_tensor", hip.EmaTensor, hip.EMA_TENSOR_DTYPE)]
-    body = "".join('printf("%s %%zu\\n", sizeof(%s));\n' % (c, c) + "".join('printf("%s.%s %%zu\\n", offsetof(%s, %s));\n' % (c, f[0], c, f[0]) for f in py._fields_)
-                   for c, py, _ in pairs)
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "gims_hip.h"\nint main(void) {\n' + body + "return 0; }\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = dict(line.split() for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    for c, py, dt in pairs:
-        assert int(got[c]) == C.sizeof(py), (c, got[c], C.sizeof(py))
-        for f in py._fields_:
-            assert int(got[f"{c}.{f[0]}"]) == getattr(py, f[0]).offset, (c, f[0])
-        if dt is not None:
-            d = np.dtype(dt)
-            assert d.itemsize == C.sizeof(py) and list(d.names) == [f[0] for f in py._fields_]
-            assert [d.fields[n][1] for n in d.names] == [getattr(py, n).offset for n in d.names]
-    assert C.sizeof(hip.SgdTensor) == 40 and C.sizeof(hip.SgdGroup) == 40 and C.sizeof(hip.EmaTensor) == 24
-    assert hip.load().gims_abi_version() == 2
 
 
 def _sgd(tensors, groups, count=None, n_groups=None):
