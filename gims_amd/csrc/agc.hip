@@ -1547,8 +1547,7 @@ static void agc_batch_layout(const gims_agc_image* images, int n_images, bool ro
 // which flow a call takes: the robust one when asked for (flag or GIMS_AGC_ROBUST=1) or when an image's descriptor width does not fit the
 // window kernels (they keep a tile row's whole K in registers); only that flow stores the half similarity matrix
 static bool agc_takes_robust_flow(const gims_agc_image* images, int n_images, int flags) {
-  const char* env_robust = getenv("GIMS_AGC_ROBUST");          // read per call: the tests switch flows
-  bool robust = (flags & GIMS_AGC_ROBUST) != 0 || (env_robust && atoi(env_robust) != 0);
+  bool robust = (flags & GIMS_AGC_ROBUST) != 0 || gims::env_int("GIMS_AGC_ROBUST", 0) != 0;          // read per call: the tests switch flows
   for (int i = 0; i < n_images; ++i) robust = robust || images[i].d % gims::SW_KC != 0 || images[i].d > gims::SW_KMAX;
   return robust;
 }

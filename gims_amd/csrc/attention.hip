@@ -1720,83 +1720,121 @@ static int attention_range_launch(const uint16_t* qkv, int64_t ld, int q_col, in
 static std::atomic<uint64_t> g_launch_counts[GIMS_ATTN_KERNEL_KINDS];
 static inline void count_launch(int kind) { g_launch_counts[kind].fetch_add(1, std::memory_order_relaxed); }
 
-// launch of the one-pass 16-bit kernels (F16 = false: bf16 operands, true: IEEE half), by launch shape
-template <bool F16>
-static int attention_16b_launch(const uint16_t* qkv, int64_t ld, int q_col, int k_col, int v_col, const gims_attn_problem* problems, int n_groups, int max_n_q,
-                                int n_heads, float* out, int64_t ld_out, uint16_t* out_hi, uint16_t* out_lo, int64_t ld_split, bool prescaled, float c,
-                                unsigned long long* stat, hipStream_t stream) {
-  int force = 0;
-  { const char* e = getenv("GIMS_ATTN_QP"); force = e ? atoi(e) : 0; }
-  const int blocks2 = 8 * cdiv(n_groups, 8) * cdiv(max_n_q, 2 * QB);
-  const bool two = force == 2 || (force != 1 && blocks2 >= 512);
-  const int n_qt8 = cdiv(max_n_q, 512);
-  const bool eight = force == 8 || (force == 0 && 8 * cdiv(n_groups, 8) * n_qt8 >= 256);   // 8-wave workgroups of 512 queries
-  // a small launch (one pair through forward()): split the keys of every query block over two wave groups (GIMS_ATTN_QP=3: always)
-  const bool split = force == 3 || (force == 0 && !eight && !two && 8 * cdiv(n_groups, 8) * cdiv(max_n_q, QB) <= 512 && max_n_q >= 512);
-  if (split) {
-    GIMS_LDS_ATTR((const void*)attention_split_kernel<2, F16>, SPLIT_LDS_BYTES<2>);
-    GIMS_LDS_ATTR((const void*)attention_split_kernel<4, F16>, SPLIT_LDS_BYTES<4>);
-    const int n_qt = cdiv(max_n_q, QB);
-    const int wgs = 8 * cdiv(n_groups, 8) * n_qt;
-    int ns_env = 0;                                  // read per call: the tests switch between the two variants
-    { const char* e = getenv("GIMS_ATTN_SPLIT"); ns_env = e ? atoi(e) : 0; }
-    // four key parts (sixteen waves) when the launch is at most one workgroup per CU and the keys are many
-    const bool four = ns_env == 4 || (ns_env != 2 && wgs <= 256 && max_n_q >= 2048);
-    count_launch(GIMS_ATTN_KERNEL_SPLIT);
-    if (four)
-      hipLaunchKernelGGL((attention_split_kernel<4, F16>), dim3(wgs), dim3(1024), SPLIT_LDS_BYTES<4>, stream, qkv, ld, q_col, k_col, v_col, problems,
-                         n_groups, n_heads, n_qt, out, ld_out, out_hi, out_lo, ld_split, c, stat);
-    else
-      hipLaunchKernelGGL((attention_split_kernel<2, F16>), dim3(wgs), dim3(512), SPLIT_LDS_BYTES<2>, stream, qkv, ld, q_col, k_col, v_col, problems,
-                         n_groups, n_heads, n_qt, out, ld_out, out_hi, out_lo, ld_split, c, stat);
-  } else if (eight) {
-    count_launch(F16 ? GIMS_ATTN_KERNEL_WAVE8_F16 : GIMS_ATTN_KERNEL_WAVE8);
-    int exact_only = 0;                         // GIMS_ATTN_EXACT=1: running-maximum softmax only (no optimistic pass)
-    { const char* e = getenv("GIMS_ATTN_EXACT"); exact_only = e ? atoi(e) : 0; }
-    static int prof = -1;
-    if (prof < 0) { const char* e = getenv("GIMS_ATTN_PROF"); prof = e ? atoi(e) : 0; }
-    if (prof) {                                 // diagnostics only: synchronous, prints the phase anatomy of workgroup 0
-      unsigned long long* dprof = (unsigned long long*)device_once("attention8_prof", 24 * sizeof(unsigned long long), nullptr);
-      GIMS_CHECK_ARG(dprof, "gims_attention: no profile buffer");
-      if (prescaled)
-        hipLaunchKernelGGL((attention8_bf16_kernel<true, true, F16>), dim3(8 * cdiv(n_groups, 8) * n_qt8), dim3(512), 0, stream, qkv, ld,
-                           q_col, k_col, v_col, problems, n_groups, n_heads, n_qt8, out, ld_out, out_hi, out_lo, ld_split, dprof, exact_only, c, nullptr, 0);
-      else
-        hipLaunchKernelGGL((attention8_bf16_kernel<true, false, F16>), dim3(8 * cdiv(n_groups, 8) * n_qt8), dim3(512), 0, stream, qkv, ld,
-                           q_col, k_col, v_col, problems, n_groups, n_heads, n_qt8, out, ld_out, out_hi, out_lo, ld_split, dprof, exact_only, c, nullptr, 0);
-      GIMS_HIP(hipStreamSynchronize(stream));
-      unsigned long long h[24];
-      GIMS_HIP(hipMemcpy(h, dprof, sizeof(h), hipMemcpyDeviceToHost));
-      fprintf(stderr, "[attention8 wave 0 of workgroup 0] prologue %llu, tile loop %llu, epilogue %llu shader cycles; %.1f us on the 100-MHz counter -> %.2f GHz\n",
-              h[20], h[21], h[22], h[23] / 100.0, (double)(h[20] + h[21] + h[22]) / (h[23] / 100.0) * 1e-3);
-      for (int g = 0; g < 2; ++g)
-        fprintf(stderr, "[attention8 wave %d] cycles over the whole tile loop: QK %llu, softmax0 %llu, softmax1 %llu, PV %llu, store_tile %llu, "
-                "load_tile %llu, barrier wait %llu\n", 4 * g, h[g * 10 + 0], h[g * 10 + 2], h[g * 10 + 4], h[g * 10 + 8], h[g * 10 + 9], h[g * 10 + 6],
-                h[g * 10 + 7]);
-    } else {
-      // the optimistic 8-wave kernel tracks no maximum: measured launches carry 8 * ceil(n_groups / 8) extra workgroups in front that measure
-      // a sample of the rows (attention_peak_sample_wg)
-      const int n_sample = stat ? 8 * cdiv(n_groups, 8) : 0;
-      if (prescaled)
-        hipLaunchKernelGGL((attention8_bf16_kernel<false, true, F16>), dim3(n_sample + 8 * cdiv(n_groups, 8) * n_qt8), dim3(512), 0, stream, qkv, ld,
-                           q_col, k_col, v_col, problems, n_groups, n_heads, n_qt8, out, ld_out, out_hi, out_lo, ld_split, nullptr, exact_only, c, stat, n_sample);
-      else
-        hipLaunchKernelGGL((attention8_bf16_kernel<false, false, F16>), dim3(n_sample + 8 * cdiv(n_groups, 8) * n_qt8), dim3(512), 0, stream, qkv, ld,
-                           q_col, k_col, v_col, problems, n_groups, n_heads, n_qt8, out, ld_out, out_hi, out_lo, ld_split, nullptr, exact_only, c, stat, n_sample);
-    }
-  } else if (two) {
-    count_launch(GIMS_ATTN_KERNEL_WAVE4);
-    const int n_qt = cdiv(max_n_q, 2 * QB);
-    hipLaunchKernelGGL((attention_bf16_kernel<2, F16>), dim3(8 * cdiv(n_groups, 8) * n_qt), dim3(256), 0, stream, qkv, ld,
-                       q_col, k_col, v_col, problems, n_groups, n_heads, n_qt, out, ld_out, out_hi, out_lo, ld_split, c, stat);
-  } else {
-    count_launch(GIMS_ATTN_KERNEL_WAVE4);
-    const int n_qt = cdiv(max_n_q, QB);
-    hipLaunchKernelGGL((attention_bf16_kernel<1, F16>), dim3(8 * cdiv(n_groups, 8) * n_qt), dim3(256), 0, stream, qkv, ld,
-                       q_col, k_col, v_col, problems, n_groups, n_heads, n_qt, out, ld_out, out_hi, out_lo, ld_split, c, stat);
-  }
+// What every attention kernel takes in front of its own arguments, and the launch shape; filled once by gims_attention_ex after validation.
+struct AttnPrefix {
+  const uint16_t* qkv; int64_t ld; int q_col, k_col, v_col; const gims_attn_problem* problems; int n_groups, n_heads;
+  float* out; int64_t ld_out; uint16_t* out_hi; uint16_t* out_lo; int64_t ld_split;
+  int max_n_q, groups8;      // groups8: (problem, head) groups padded to the 8 XCDs, 8 * ceil(n_groups / 8)
+  hipStream_t stream;
+};
+// One launch: the prefix (n_qt = query tiles per group, by the instance's queries per workgroup) in front of the family's own tail -- c, stat
+// for the 4-wave and split kernels; prof, exact_only, c, stat, n_sample for the 8-wave kernel; c, stat, guard, n_blocks for the X3 kernels.
+// The LDS attribute is set here, for the kernel that is launched.
+template <typename K, typename... Tail>
+static int attn_launch(K kernel, const AttnPrefix& p, int n_qt, int grid, int block, int lds, Tail... tail) {
+  if (lds) GIMS_LDS_ATTR((const void*)kernel, lds);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, p.stream, p.qkv, p.ld, p.q_col, p.k_col, p.v_col, p.problems, p.n_groups, p.n_heads, n_qt,
+                     p.out, p.ld_out, p.out_hi, p.out_lo, p.ld_split, tail...);
   GIMS_LAUNCH_CHECK();
   return GIMS_OK;
+}
+
+// Which one-pass 16-bit instance a launch takes, by launch shape; force = GIMS_ATTN_QP, ns_env = GIMS_ATTN_SPLIT (0: not set).
+enum class Attn16 { SPLIT2, SPLIT4, WAVE8, WAVE4_QP2, WAVE4_QP1 };
+static Attn16 attn16_choose(int groups8, int max_n_q, int force, int ns_env) {
+  // 64 queries per wave (K/V fragments and barriers shared by two query blocks) when that still fills the chip
+  const bool two = force == 2 || (force != 1 && groups8 * cdiv(max_n_q, 2 * QB) >= 512);
+  const bool eight = force == 8 || (force == 0 && groups8 * cdiv(max_n_q, 512) >= 256);   // 8-wave workgroups of 512 queries
+  // a small launch (one pair through forward()): split the keys of every query block over two wave groups (GIMS_ATTN_QP=3: always)
+  const int wgs = groups8 * cdiv(max_n_q, QB);
+  const bool split = force == 3 || (force == 0 && !eight && !two && wgs <= 512 && max_n_q >= 512);
+  // four key parts (sixteen waves) when the launch is at most one workgroup per CU and the keys are many
+  if (split) return ns_env == 4 || (ns_env != 2 && wgs <= 256 && max_n_q >= 2048) ? Attn16::SPLIT4 : Attn16::SPLIT2;
+  if (eight) return Attn16::WAVE8;
+  // QP 2 is reachable only by override (GIMS_ATTN_QP=2 or a value with no meaning of its own): unforced, `two` implies `eight`, tested first
+  return two ? Attn16::WAVE4_QP2 : Attn16::WAVE4_QP1;
+}
+
+// Which X3 instance; wide_env = GIMS_ATTN_X3W (-1: not set, 0 / 2 force), round = the workgroups of one dispatch round (two per CU),
+// walk = a guarded launch with GIMS_GUARD_WALK on.
+enum class AttnX3 { NARROW, WIDE, WIDE_WALK };
+static AttnX3 attn_x3_choose(int groups8, int max_n_q, int wide_env, int round, bool walk) {
+  const int n_blocks = groups8 * cdiv(max_n_q, 2 * QB);
+  const bool wide = wide_env < 0 ? n_blocks >= 512 : wide_env != 0;
+  if (!wide) return AttnX3::NARROW;
+  // guarded launches: one dispatch round of workgroups (two per CU), a strided walk over the tiles when the guard fires
+  return walk && n_blocks > round ? AttnX3::WIDE_WALK : AttnX3::WIDE;
+}
+
+template <bool PROF, bool F16>
+static int attention8_launch(const AttnPrefix& p, bool prescaled, unsigned long long* dprof, int exact_only, float c, unsigned long long* stat, int n_sample) {
+  const int n_qt = cdiv(p.max_n_q, 512), grid = n_sample + p.groups8 * n_qt;
+  return prescaled ? attn_launch(attention8_bf16_kernel<PROF, true, F16>, p, n_qt, grid, 512, 0, dprof, exact_only, c, stat, n_sample)
+                   : attn_launch(attention8_bf16_kernel<PROF, false, F16>, p, n_qt, grid, 512, 0, dprof, exact_only, c, stat, n_sample);
+}
+
+// launch of the one-pass 16-bit kernels (F16 = false: bf16 operands, true: IEEE half), by launch shape
+template <bool F16>
+static int attention_16b_launch(const AttnPrefix& p, bool prescaled, float c, unsigned long long* stat) {
+  // (environment read per call, not cached: the tests switch kernels and the two split variants with it)
+  const Attn16 kind = attn16_choose(p.groups8, p.max_n_q, env_int("GIMS_ATTN_QP", 0), env_int("GIMS_ATTN_SPLIT", 0));
+  const int n_qt = cdiv(p.max_n_q, QB), n_qt2 = cdiv(p.max_n_q, 2 * QB);
+  switch (kind) {
+    case Attn16::SPLIT4:
+      count_launch(GIMS_ATTN_KERNEL_SPLIT);
+      return attn_launch(attention_split_kernel<4, F16>, p, n_qt, p.groups8 * n_qt, 1024, SPLIT_LDS_BYTES<4>, c, stat);
+    case Attn16::SPLIT2:
+      count_launch(GIMS_ATTN_KERNEL_SPLIT);
+      return attn_launch(attention_split_kernel<2, F16>, p, n_qt, p.groups8 * n_qt, 512, SPLIT_LDS_BYTES<2>, c, stat);
+    case Attn16::WAVE4_QP2:
+      count_launch(GIMS_ATTN_KERNEL_WAVE4);
+      return attn_launch(attention_bf16_kernel<2, F16>, p, n_qt2, p.groups8 * n_qt2, 256, 0, c, stat);
+    case Attn16::WAVE4_QP1:
+      count_launch(GIMS_ATTN_KERNEL_WAVE4);
+      return attn_launch(attention_bf16_kernel<1, F16>, p, n_qt, p.groups8 * n_qt, 256, 0, c, stat);
+    case Attn16::WAVE8: break;
+  }
+  count_launch(F16 ? GIMS_ATTN_KERNEL_WAVE8_F16 : GIMS_ATTN_KERNEL_WAVE8);
+  const int exact_only = env_int("GIMS_ATTN_EXACT", 0);      // GIMS_ATTN_EXACT=1: running-maximum softmax only (no optimistic pass)
+  static const int prof = env_int("GIMS_ATTN_PROF", 0);
+  if (!prof) {
+    // the optimistic 8-wave kernel tracks no maximum: measured launches carry 8 * ceil(n_groups / 8) extra workgroups in front that measure
+    // a sample of the rows (attention_peak_sample_wg)
+    return attention8_launch<false, F16>(p, prescaled, nullptr, exact_only, c, stat, stat ? p.groups8 : 0);
+  }
+  // diagnostics only: synchronous, prints the phase anatomy of workgroup 0
+  unsigned long long* dprof = (unsigned long long*)device_once("attention8_prof", 24 * sizeof(unsigned long long), nullptr);
+  GIMS_CHECK_ARG(dprof, "gims_attention: no profile buffer");
+  const int rc = attention8_launch<true, F16>(p, prescaled, dprof, exact_only, c, nullptr, 0);
+  if (rc != GIMS_OK) return rc;
+  GIMS_HIP(hipStreamSynchronize(p.stream));
+  unsigned long long h[24];
+  GIMS_HIP(hipMemcpy(h, dprof, sizeof(h), hipMemcpyDeviceToHost));
+  fprintf(stderr, "[attention8 wave 0 of workgroup 0] prologue %llu, tile loop %llu, epilogue %llu shader cycles; %.1f us on the 100-MHz counter -> %.2f GHz\n",
+          h[20], h[21], h[22], h[23] / 100.0, (double)(h[20] + h[21] + h[22]) / (h[23] / 100.0) * 1e-3);
+  for (int g = 0; g < 2; ++g)
+    fprintf(stderr, "[attention8 wave %d] cycles over the whole tile loop: QK %llu, softmax0 %llu, softmax1 %llu, PV %llu, store_tile %llu, "
+            "load_tile %llu, barrier wait %llu\n", 4 * g, h[g * 10 + 0], h[g * 10 + 2], h[g * 10 + 4], h[g * 10 + 8], h[g * 10 + 9], h[g * 10 + 6],
+            h[g * 10 + 7]);
+  return GIMS_OK;
+}
+
+// launch of the split-bf16 (X3) kernels: operands from the SPL32 Q/K/V buffer, three MFMAs per product
+static int attention_x3_launch(const AttnPrefix& p, float c, unsigned long long* stat, const gims_attn_guard& guard) {
+  // wide form (64 queries per wave in a pair that shares every K / V fragment; 256-query workgroups, two per CU) when they fill the chip, else
+  // the 32-query-per-wave kernel; GIMS_ATTN_X3W=0/2 forces.  Measured with K and V staged by LDS-DMA (32-query / wide; a 128-query-per-wave
+  // form with the whole register file, QP = 4, was third everywhere -- 912 / 730 / 867 us at 16 x 4096 keys -- and left the library in round 6):
+  // 32 x 2048 460 / 398, 40 x 1500 298 / 274, 64 x 1022 206 / 197, 8 x 700 26 / 41.
+  const int round = 2 * (device_cus() & ~7);
+  const AttnX3 kind = attn_x3_choose(p.groups8, p.max_n_q, env_int("GIMS_ATTN_X3W", -1), round, guard.stat && guard_walk_enabled());
+  count_launch(guard.stat ? GIMS_ATTN_KERNEL_X3_GUARDED : GIMS_ATTN_KERNEL_X3);
+  if (kind == AttnX3::NARROW) {      // (a guarded launch of more than one round always walks here)
+    const int n_qt = cdiv(p.max_n_q, QB), n_blocks = p.groups8 * n_qt;
+    return attn_launch(attention_x3_kernel, p, n_qt, guard.stat && n_blocks > round ? round : n_blocks, 256, X3_LDS_BYTES, c, stat, guard, n_blocks);
+  }
+  const int n_qt = cdiv(p.max_n_q, 2 * QB), n_blocks = p.groups8 * n_qt;
+  if (kind == AttnX3::WIDE_WALK) return attn_launch(attention_x3w_kernel<2, true>, p, n_qt, round, 256, X3W_LDS_BYTES, c, stat, guard, n_blocks);
+  return attn_launch(attention_x3w_kernel<2, false>, p, n_qt, n_blocks, 256, X3W_LDS_BYTES, c, stat, guard, n_blocks);
 }
 }  // namespace gims
 
@@ -1853,54 +1891,19 @@ extern "C" int gims_attention_ex(const gims_attn_args* args, void* stream) {
   GIMS_CHECK_ARG((ld_out % 4) == 0, "gims_attention: ld_out must be a multiple of 4");
   GIMS_CHECK_ARG(ld <= 16384, "gims_attention: qkv pitch %lld too large (32-bit tile offsets)", (long long)ld);
   const int n_groups = n_heads * n_problems;
+  const AttnPrefix p = {qkv, ld, q_col, k_col, v_col, problems, n_groups, n_heads, out, ld_out, out_hi, out_lo, ld_split, max_n_q, 8 * cdiv(n_groups, 8), (hipStream_t)stream};
   const bool prescaled = (flags & GIMS_ATTN_Q_PRESCALED) != 0;
   const float c = prescaled ? 1.f : 0.125f * 1.4426950408889634f;      // 1/sqrt(64) * log2(e)
-  // 64 queries per wave (K/V fragments and barriers shared by two query blocks) when that still fills the chip
-  // (environment read per call, not cached: the tests switch kernels with it)
   const bool f16 = (flags & GIMS_ATTN_F16) != 0;
   GIMS_CHECK_ARG(!(f16 && (flags & GIMS_ATTN_X3)), "gims_attention: GIMS_ATTN_F16 and GIMS_ATTN_X3 exclude each other");
   if (stat && (flags & (GIMS_ATTN_X3 | GIMS_ATTN_F16)) && !(flags & GIMS_ATTN_NO_RANGE)) {   // range of the operands as stored (measured launches of the half / calibration tiers: bf16 has f32's range)
-    const int rc = attention_range_launch(qkv, ld, q_col, k_col, v_col, problems, n_problems, n_heads, (flags & GIMS_ATTN_X3) ? 2 : (f16 ? 1 : 0), stat,
-                                          (hipStream_t)stream);
+    const int rc = attention_range_launch(qkv, ld, q_col, k_col, v_col, problems, n_problems, n_heads, (flags & GIMS_ATTN_X3) ? 2 : (f16 ? 1 : 0), stat, p.stream);
     if (rc != GIMS_OK) return rc;
   }
-  if (flags & GIMS_ATTN_X3) {                  // split-bf16 operands from the SPL32 Q/K/V buffer, three MFMAs per product
+  if (flags & GIMS_ATTN_X3) {
     GIMS_CHECK_ARG((q_col % 32) == 0 && (k_col % 32) == 0 && (v_col % 32) == 0 && (ld % 64) == 0,
                    "gims_attention: GIMS_ATTN_X3 takes logical column offsets that are multiples of 32 and an SPL32 pitch (multiple of 64)");
-    GIMS_LDS_ATTR((const void*)attention_x3_kernel, X3_LDS_BYTES);
-    // wide form (64 queries per wave in a pair that shares every K / V fragment; 256-query workgroups, two per CU) when they fill the chip, else
-    // the 32-query-per-wave kernel; GIMS_ATTN_X3W=0/2 forces.  Measured with K and V staged by LDS-DMA (32-query / wide; a 128-query-per-wave
-    // form with the whole register file, QP = 4, was third everywhere -- 912 / 730 / 867 us at 16 x 4096 keys -- and left the library in round 6):
-    // 32 x 2048 460 / 398, 40 x 1500 298 / 274, 64 x 1022 206 / 197, 8 x 700 26 / 41.
-    int wide = -1;
-    { const char* e = getenv("GIMS_ATTN_X3W"); if (e) wide = atoi(e); }
-    if (wide < 0) wide = 8 * cdiv(n_groups, 8) * cdiv(max_n_q, 2 * QB) >= 512 ? 2 : 0;
-    count_launch(guard.stat ? GIMS_ATTN_KERNEL_X3_GUARDED : GIMS_ATTN_KERNEL_X3);
-    if (wide) {
-      GIMS_LDS_ATTR((const void*)(attention_x3w_kernel<2, false>), X3W_LDS_BYTES);
-      GIMS_LDS_ATTR((const void*)(attention_x3w_kernel<2, true>), X3W_LDS_BYTES);
-      const int n_qtw = cdiv(max_n_q, 2 * QB);
-      // guarded launches: one dispatch round of workgroups (two per CU), a strided walk over the tiles when the guard fires
-      const int n_blocks = 8 * cdiv(n_groups, 8) * n_qtw, round = 2 * (device_cus() & ~7);
-      if (guard.stat && n_blocks > round && guard_walk_enabled())
-        hipLaunchKernelGGL((attention_x3w_kernel<2, true>), dim3(round), dim3(256), X3W_LDS_BYTES, (hipStream_t)stream, qkv, ld,
-                           q_col, k_col, v_col, problems, n_groups, n_heads, n_qtw, out, ld_out, out_hi, out_lo, ld_split, c, stat, guard, n_blocks);
-      else
-        hipLaunchKernelGGL((attention_x3w_kernel<2, false>), dim3(n_blocks), dim3(256), X3W_LDS_BYTES, (hipStream_t)stream, qkv, ld,
-                           q_col, k_col, v_col, problems, n_groups, n_heads, n_qtw, out, ld_out, out_hi, out_lo, ld_split, c, stat, guard, n_blocks);
-      GIMS_LAUNCH_CHECK();
-      return GIMS_OK;
-    }
-    const int n_qt = cdiv(max_n_q, QB);
-    const int n_blocks = 8 * cdiv(n_groups, 8) * n_qt, round = 2 * (device_cus() & ~7);
-    hipLaunchKernelGGL(attention_x3_kernel, dim3(guard.stat && n_blocks > round ? round : n_blocks), dim3(256), X3_LDS_BYTES, (hipStream_t)stream, qkv, ld,
-                       q_col, k_col, v_col, problems, n_groups, n_heads, n_qt, out, ld_out, out_hi, out_lo, ld_split, c, stat, guard, n_blocks);
-    GIMS_LAUNCH_CHECK();
-    return GIMS_OK;
+    return attention_x3_launch(p, c, stat, guard);
   }
-  return f16 ? attention_16b_launch<true>(qkv, ld, q_col, k_col, v_col, problems, n_groups, max_n_q, n_heads, out, ld_out, out_hi, out_lo, ld_split, prescaled, c,
-                                          stat, (hipStream_t)stream)
-             : attention_16b_launch<false>(qkv, ld, q_col, k_col, v_col, problems, n_groups, max_n_q, n_heads, out, ld_out, out_hi, out_lo, ld_split, prescaled, c,
-                                           stat, (hipStream_t)stream);
+  return f16 ? attention_16b_launch<true>(p, prescaled, c, stat) : attention_16b_launch<false>(p, prescaled, c, stat);
 }
-

@@ -1454,7 +1454,7 @@ static int conv_block_launch(const uint16_t* x, int64_t ldx, int64_t patches, co
     GIMS_CHECK_ARG(dprof, "gims_ch_conv_block: no profile buffer");
     first.prof = dprof;
   }
-  static const int stagger = getenv("GIMS_CH_STAGGER") ? atoi(getenv("GIMS_CH_STAGGER")) : 8000;
+  static const int stagger = env_int("GIMS_CH_STAGGER", 8000);
   first.stagger = stagger;
   // (FRN_FLOATS * 4 <= LDS_BYTES by construction; the staged gate weights sit behind the FRN arrays)
   const int lds_bytes = G.w1 ? PP * Geo::FRN_FLOATS * 4 + Geo::GATE_BYTES : Geo::LDS_BYTES;
@@ -1480,7 +1480,7 @@ static int conv_block_half_launch(const uint16_t* x, int64_t ldx, int64_t patche
   using namespace gims;
   using Geo = HalfGeom<CIN, COUT, STRIDE>;
   GIMS_LDS_ATTR((const void*)ch_conv_block_half_kernel<CIN, COUT, STRIDE>, Geo::LDS_BYTES);
-  static const int stagger = getenv("GIMS_CH_STAGGER") ? atoi(getenv("GIMS_CH_STAGGER")) : 8000;
+  static const int stagger = env_int("GIMS_CH_STAGGER", 8000);
   static const bool prof_on = getenv("GIMS_CH_PROF") != nullptr;      // diagnostics: cycle stamps of one workgroup per launch (synchronous)
   unsigned long long* dprof = nullptr;
   if (prof_on) {
@@ -1488,7 +1488,7 @@ static int conv_block_half_launch(const uint16_t* x, int64_t ldx, int64_t patche
     GIMS_CHECK_ARG(dprof, "gims_ch_conv_block: no profile buffer");
   }
   // GIMS_CH_HALF_LDS=<bytes>: pad the dynamic LDS (diagnostics: > 80 KB leaves ONE workgroup per CU -- what the co-residency is worth)
-  static const int pad = getenv("GIMS_CH_HALF_LDS") ? atoi(getenv("GIMS_CH_HALF_LDS")) : 0;
+  static const int pad = env_int("GIMS_CH_HALF_LDS", 0);
   const int lds = pad > Geo::LDS_BYTES ? pad : Geo::LDS_BYTES;
   if (pad) GIMS_LDS_ATTR((const void*)ch_conv_block_half_kernel<CIN, COUT, STRIDE>, lds);
   hipLaunchKernelGGL((ch_conv_block_half_kernel<CIN, COUT, STRIDE>), dim3((unsigned)patches), dim3(512), lds, st, x, ldx, w, bias, fw, fb, eps, G, tau, y,
@@ -1504,8 +1504,7 @@ static int conv_block_half_launch(const uint16_t* x, int64_t ldx, int64_t patche
   return GIMS_OK;
 }
 static bool ch_half() {
-  const char* e = getenv("GIMS_CH_HALF");         // read per call: the tests compare the two forms
-  return !e || atoi(e) != 0;
+  return env_int("GIMS_CH_HALF", 1) != 0;         // read per call: the tests compare the two forms
 }
 
 extern "C" int gims_ch_conv_block_first(const float* patches, int64_t n, const float* frn0_weight, const float* frn0_bias, float eps0, const float* tau0,
@@ -1573,11 +1572,11 @@ extern "C" int gims_ch_sandglass(const float* x, int64_t patches, int32_t hw, in
     GIMS_CHECK_ARG(dprof, "gims_ch_sandglass: no profile buffer");
     W.prof = dprof;
   }
-  static const int stagger = getenv("GIMS_CH_STAGGER") ? atoi(getenv("GIMS_CH_STAGGER")) : 8000;
+  static const int stagger = env_int("GIMS_CH_STAGGER", 8000);
   W.stagger = stagger;
   W.first_wave = 256 * (int)((160 * 1024) / lds);
   // 32x32x32: one 1024-thread workgroup per CU, persistent over the patches (806 -> 691 us per 8192 patches); 16x16x64: one workgroup per patch
-  static const int persist = getenv("GIMS_CH_PERSIST") ? atoi(getenv("GIMS_CH_PERSIST")) : 1;
+  static const int persist = env_int("GIMS_CH_PERSIST", 1);
   const unsigned grid = (unsigned)(c == 32 && persist && patches > 256 ? 256 : patches);
   if (c == 32) hipLaunchKernelGGL((ch_sandglass_kernel<32, 32, SG_NT>), dim3(grid), dim3(SG_NT), lds, (hipStream_t)stream, x, W, out_split, ld_split, (int)patches);
   else hipLaunchKernelGGL((ch_sandglass_kernel<64, 16, SG_NT>), dim3(grid), dim3(SG_NT), lds, (hipStream_t)stream, x, W, out_split, ld_split, (int)patches);

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include "../../include/gims_hip.h"
 
@@ -142,9 +143,12 @@ struct WsLayout {
   template <typename T> T* take(size_t count) { const size_t o = off; off += al256(sizeof(T) * count); return base ? (T*)(base + o) : nullptr; }
   size_t bytes() const { return off; }     // the total so far: also the offset of the next take
 };
+// An integer knob from the environment: its value, or dflt when the variable is not set.  Every call reads the environment: a knob that is
+// fixed for the process is held as `static const int x = env_int(...)` by its user; one that the tests switch is read per call.
+static inline int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 // GIMS_GUARD_WALK=0: guarded launches take the full grid instead of one dispatch round of workgroups that walk the tiles (read per call: the
 // cross-check of tests/test_hip_kernels.py::test_guarded_launches_that_walk_their_tiles switches it)
-static inline bool guard_walk_enabled() { const char* e = getenv("GIMS_GUARD_WALK"); return !(e && atoi(e) == 0); }
+static inline bool guard_walk_enabled() { return env_int("GIMS_GUARD_WALK", 1) != 0; }
 
 // Host descriptor table -> device memory through KERNEL ARGUMENTS (chunks of <= 3968 bytes per launch): asynchronous on
 // the stream, no staging buffer whose lifetime would need a synchronisation, no pageable-memory pinning by the runtime.

@@ -698,11 +698,39 @@ static int linear_validate(const gims_linear_args* a) {
   return GIMS_OK;
 }
 
-static int x3_attr() {
+// The register-staged bf16x3 kernels (one problem / a batch of them) share one geometry: 256 threads, four operand planes of LDS.
+template <typename K, typename A>
+static int x3_launch(K kernel, dim3 grid, const A& args, hipStream_t s) {
   using namespace gims;
-  const int lds = 4 * X3_PLANE * (int)sizeof(uint16_t);
-  GIMS_LDS_ATTR((const void*)linear_bf16x3_kernel, lds);
-  GIMS_LDS_ATTR((const void*)linear_bf16x3_batch_kernel, lds);
+  constexpr int lds = 4 * X3_PLANE * (int)sizeof(uint16_t);
+  GIMS_LDS_ATTR((const void*)kernel, lds);
+  hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, args);
+  GIMS_LAUNCH_CHECK();
+  return GIMS_OK;
+}
+
+// Output tiles of a pre-split launch in the XCD-aware order: the rows of tiles are padded to the 8 XCDs.
+template <int TM, int TN>
+static int x3p_tiles(const gims_linear_args& a) { return 8 * gims::cdiv(gims::cdiv(a.m, TM), 8) * gims::cdiv(a.n, TN); }
+
+// One launch of a pre-split instance.  LDS size, block and grid all follow from the instance's own parameters, and the attribute is set for
+// the kernel that is launched.  WALK: one dispatch round of workgroups that walk the tiles (linear_x3p_guarded_kernel).
+template <int TM, int TN, int WM, int WN, int S, int HI_ONLY = 0, bool WALK = false>
+static int x3p_launch(const gims_linear_args& a, hipStream_t s) {
+  using namespace gims;
+  using T = X3P<TM, TN, WM, WN, S, HI_ONLY == 1>;
+  constexpr int block = 64 * WM * WN, lds = T::LDS_BYTES;
+  static_assert(T::WAVES * 64 == block && block <= 1024, "one wave per (WM, WN) slot of the tile");
+  static_assert(T::MI * WM * 32 == TM && T::NI * WN * 32 == TN, "the waves' 32x32 MFMA tiles cover the workgroup tile");
+  const int n_tiles = x3p_tiles<TM, TN>(a);
+  if constexpr (WALK) {
+    GIMS_LDS_ATTR((const void*)linear_x3p_guarded_kernel<TM, TN, WM, WN, S, HI_ONLY>, lds);
+    hipLaunchKernelGGL((linear_x3p_guarded_kernel<TM, TN, WM, WN, S, HI_ONLY>), dim3(device_cus() & ~7), dim3(block), lds, s, a, n_tiles);
+  } else {
+    GIMS_LDS_ATTR((const void*)linear_x3p_kernel<TM, TN, WM, WN, S, HI_ONLY>, lds);
+    hipLaunchKernelGGL((linear_x3p_kernel<TM, TN, WM, WN, S, HI_ONLY>), dim3(n_tiles), dim3(block), lds, s, a);
+  }
+  GIMS_LAUNCH_CHECK();
   return GIMS_OK;
 }
 
@@ -712,103 +740,57 @@ extern "C" int gims_linear(const gims_linear_args* a, void* stream) {
   if (rc != GIMS_OK) return rc;
   GIMS_CHECK_ARG(a->precision != GIMS_PREC_BF16X6, "gims_linear: GIMS_PREC_BF16X6 runs through gims_linear_put_many + gims_linear_batch");
   hipStream_t s = (hipStream_t)stream;
-  dim3 grid(cdiv(a->n, BN), cdiv(a->m, BM));
-  if (a->a0_lo) {
-    // tile geometry: 256x256 (half the operand bytes per MFMA) when that still gives ~one workgroup per CU,
-    // else 128x128.  GIMS_X3P_TILE=128|256 forces one (A/B).
-    using TS = X3P<128, 128, 2, 2, 2>;
-    using TL = X3P<256, 256, 4, 2, 2>;
-    static const int force = [] { const char* e = getenv("GIMS_X3P_TILE"); return e ? atoi(e) : 0; }();
-    // one-pass (Q/K/V) GEMMs: 0 = 256 x 256 tiles like the others; 2 / 3 = 256 x 128 tiles with that many ring stages (default 3)
-    static const int qkv_tile = [] { const char* e = getenv("GIMS_X3P_QKV"); return e ? atoi(e) : 3; }();
-    static const int small_tiles = [] { const char* e = getenv("GIMS_X3P_SMALL"); return e ? atoi(e) : 128; }();      // 128 x 128 tiles at or below which a launch takes 64 x 64 ones (GIMS_X3P_SMALL=0: never)
-    const int big_blocks = cdiv(a->m, 256) * cdiv(a->n, 256);
-    // the 256-wide tile only when it is not half empty (n = 64 / 128 layers of the keypoint encoder and GraphSAGE)
-    const bool big = force == 256 || (force != 128 && big_blocks >= 192 && (a->n % 256 == 0 || a->n > 512));
-    if (big && (a->flags & GIMS_LINEAR_HI_ONLY) && qkv_tile > 0) {
-      // one-pass GEMMs with a short K (the Q/K/V projection: K = 256, 8 stages) are all prologue and epilogue: 256 x 128
-      // tiles with 64 accumulator registers per wave let TWO workgroups share a CU, one's epilogue under the other's loads
-      using TQ2 = X3P<256, 128, 4, 2, 2, true>;
-      using TQ3 = X3P<256, 128, 4, 2, 3, true>;
-      GIMS_LDS_ATTR((const void*)linear_x3p_kernel<256, 128, 4, 2, 2, 1>, (int)TQ2::LDS_BYTES);
-      GIMS_LDS_ATTR((const void*)linear_x3p_kernel<256, 128, 4, 2, 3, 1>, (int)TQ3::LDS_BYTES);
-      const dim3 g(8 * cdiv(cdiv(a->m, 256), 8) * cdiv(a->n, 128));
-      if (qkv_tile == 2) { constexpr size_t lds = TQ2::LDS_BYTES; hipLaunchKernelGGL((linear_x3p_kernel<256, 128, 4, 2, 2, 1>), g, dim3(512), lds, s, *a); }
-      else { constexpr size_t lds = TQ3::LDS_BYTES; hipLaunchKernelGGL((linear_x3p_kernel<256, 128, 4, 2, 3, 1>), g, dim3(512), lds, s, *a); }
-    } else if (big) {
-      using TLH = X3P<256, 256, 4, 2, 4, true>;
-      constexpr size_t lds = TL::LDS_BYTES, lds_h = TLH::LDS_BYTES;
-      GIMS_LDS_ATTR((const void*)linear_x3p_kernel<256, 256, 4, 2, 4, 1>, (int)lds_h);
-      GIMS_LDS_ATTR((const void*)linear_x3p_kernel<256, 256, 4, 2, 2, 2>, (int)lds);
-      GIMS_LDS_ATTR((const void*)linear_x3p_kernel<256, 256, 4, 2, 2>, (int)lds);
-      const dim3 g(8 * cdiv(cdiv(a->m, 256), 8) * cdiv(a->n, 256));
-      if (a->flags & GIMS_LINEAR_HI_ONLY) hipLaunchKernelGGL((linear_x3p_kernel<256, 256, 4, 2, 4, 1>), g, dim3(512), lds_h, s, *a);
-      else if (a->guard.stat && (int)g.x > device_cus() && guard_walk_enabled()) {      // guarded: one round of workgroups (see linear_x3p_guarded_kernel)
-        GIMS_LDS_ATTR((const void*)linear_x3p_guarded_kernel<256, 256, 4, 2, 2>, (int)lds);
-        hipLaunchKernelGGL((linear_x3p_guarded_kernel<256, 256, 4, 2, 2>), dim3(device_cus() & ~7), dim3(512), lds, s, *a, (int)g.x);
-      } else hipLaunchKernelGGL((linear_x3p_kernel<256, 256, 4, 2, 2>), g, dim3(512), lds, s, *a);
-    } else if (a->flags & GIMS_LINEAR_CONV3) {
-      using T32 = X3P<128, 32, 4, 1, 2>;
-      using T64 = X3P<128, 64, 2, 2, 2>;
-      GIMS_LDS_ATTR((const void*)linear_x3p_kernel<128, 32, 4, 1, 2, 4>, (int)T32::LDS_BYTES);
-      GIMS_LDS_ATTR((const void*)linear_x3p_kernel<128, 64, 2, 2, 2, 4>, (int)T64::LDS_BYTES);
-      GIMS_LDS_ATTR((const void*)linear_x3p_kernel<128, 128, 2, 2, 2, 4>, (int)TS::LDS_BYTES);
-      const int mt = 8 * cdiv(cdiv(a->m, 128), 8);
-      if (a->n <= 32) { constexpr size_t lds = T32::LDS_BYTES; hipLaunchKernelGGL((linear_x3p_kernel<128, 32, 4, 1, 2, 4>), dim3(mt * cdiv(a->n, 32)), dim3(256), lds, s, *a); }
-      else if (a->n <= 64) { constexpr size_t lds = T64::LDS_BYTES; hipLaunchKernelGGL((linear_x3p_kernel<128, 64, 2, 2, 2, 4>), dim3(mt * cdiv(a->n, 64)), dim3(256), lds, s, *a); }
-      else { constexpr size_t lds = TS::LDS_BYTES; hipLaunchKernelGGL((linear_x3p_kernel<128, 128, 2, 2, 2, 4>), dim3(mt * cdiv(a->n, 128)), dim3(256), lds, s, *a); }
-    } else if (a->n <= 64 && !(a->flags & GIMS_LINEAR_HI_ONLY) && force == 0) {
-      // narrow outputs (the 32- and 64-channel convolutions of the descriptor network, millions of rows): 128 x 32 / 128 x 64
-      // tiles instead of wasting three quarters / half of a 128-wide one
-      using T32 = X3P<128, 32, 4, 1, 2>;
-      using T64 = X3P<128, 64, 2, 2, 2>;
-      GIMS_LDS_ATTR((const void*)linear_x3p_kernel<128, 32, 4, 1, 2>, (int)T32::LDS_BYTES);
-      GIMS_LDS_ATTR((const void*)linear_x3p_kernel<128, 64, 2, 2, 2>, (int)T64::LDS_BYTES);
-      if (a->n <= 32) {
-        constexpr size_t lds = T32::LDS_BYTES;
-        hipLaunchKernelGGL((linear_x3p_kernel<128, 32, 4, 1, 2>), dim3(8 * cdiv(cdiv(a->m, 128), 8) * cdiv(a->n, 32)), dim3(256), lds, s, *a);
-      } else {
-        constexpr size_t lds = T64::LDS_BYTES;
-        hipLaunchKernelGGL((linear_x3p_kernel<128, 64, 2, 2, 2>), dim3(8 * cdiv(cdiv(a->m, 128), 8) * cdiv(a->n, 64)), dim3(256), lds, s, *a);
-      }
-    } else if (force == 64 || (force == 0 && cdiv(a->m, 128) * cdiv(a->n, 128) <= small_tiles)) {
-      // launches that leave most of the chip idle at 128 x 128 (one pair through forward(): 32 ... 96 tiles at 2 x 1024 keypoints): 64 x 64 tiles
-      // on four waves -- four times the workgroups, the same K order per output element (bit-identical), and what a launch costs there is
-      // the latency of its K loop, not its matrix work
-      using T6 = X3P<64, 64, 2, 2, 3>;
-      using T6H = X3P<64, 64, 2, 2, 4, true>;
-      GIMS_LDS_ATTR((const void*)linear_x3p_kernel<64, 64, 2, 2, 3>, (int)T6::LDS_BYTES);
-      GIMS_LDS_ATTR((const void*)linear_x3p_kernel<64, 64, 2, 2, 4, 1>, (int)T6H::LDS_BYTES);
-      const dim3 g(8 * cdiv(cdiv(a->m, 64), 8) * cdiv(a->n, 64));
-      if (a->flags & GIMS_LINEAR_HI_ONLY) { constexpr size_t lds = T6H::LDS_BYTES; hipLaunchKernelGGL((linear_x3p_kernel<64, 64, 2, 2, 4, 1>), g, dim3(256), lds, s, *a); }
-      else { constexpr size_t lds = T6::LDS_BYTES; hipLaunchKernelGGL((linear_x3p_kernel<64, 64, 2, 2, 3>), g, dim3(256), lds, s, *a); }
-    } else {
-      using TSH = X3P<128, 128, 2, 2, 4, true>;
-      constexpr size_t lds = TS::LDS_BYTES, lds_h = TSH::LDS_BYTES;
-      GIMS_LDS_ATTR((const void*)linear_x3p_kernel<128, 128, 2, 2, 4, 1>, (int)lds_h);
-      GIMS_LDS_ATTR((const void*)linear_x3p_kernel<128, 128, 2, 2, 2, 2>, (int)lds);
-      GIMS_LDS_ATTR((const void*)linear_x3p_kernel<128, 128, 2, 2, 2>, (int)lds);
-      const dim3 g(8 * cdiv(cdiv(a->m, 128), 8) * cdiv(a->n, 128));
-      if (a->flags & GIMS_LINEAR_HI_ONLY) hipLaunchKernelGGL((linear_x3p_kernel<128, 128, 2, 2, 4, 1>), g, dim3(256), lds_h, s, *a);
-      else if (force == 128 || cdiv(a->m, 128) * cdiv(a->n, 128) > 256)      // more than one tile per CU (or GIMS_X3P_TILE=128): the 4-wave tile, two workgroups per CU
-        hipLaunchKernelGGL((linear_x3p_kernel<128, 128, 2, 2, 2>), g, dim3(256), lds, s, *a);
-      else {
-        // small launches are latency-bound (one tile per CU, ~1 us per K step at one wave per SIMD): the same 128 x 128 tile on
-        // EIGHT waves (two per SIMD, 64 x 32 ... per wave) hides the LDS and MFMA-chain latencies: 23 -> 18 us at 8192 rows,
-        // 21 -> 15 us at 2048 rows (tools/gemm_probe.py); same K order per output element: bit-identical results
-        GIMS_LDS_ATTR((const void*)linear_x3p_kernel<128, 128, 4, 2, 2>, (int)X3P<128, 128, 4, 2, 2>::LDS_BYTES);
-        constexpr size_t lds8 = X3P<128, 128, 4, 2, 2>::LDS_BYTES;
-        hipLaunchKernelGGL((linear_x3p_kernel<128, 128, 4, 2, 2>), g, dim3(512), lds8, s, *a);
-      }
-    }
-  } else if (a->precision == GIMS_PREC_F32) {
+  const dim3 grid(cdiv(a->n, BN), cdiv(a->m, BM));
+  if (!a->a0_lo) {
+    if (a->precision == GIMS_PREC_BF16X3) return x3_launch(linear_bf16x3_kernel, grid, *a, s);
     hipLaunchKernelGGL(linear_f32_kernel, grid, dim3(256), 0, s, *a);
-  } else {
-    if ((rc = x3_attr()) != GIMS_OK) return rc;
-    hipLaunchKernelGGL(linear_bf16x3_kernel, grid, dim3(256), 4 * X3_PLANE * sizeof(uint16_t), s, *a);
+    GIMS_LAUNCH_CHECK();
+    return GIMS_OK;
   }
-  GIMS_LAUNCH_CHECK();
-  return GIMS_OK;
+  // pre-split operands: which instance, by shape.  Tile geometry: 256x256 (half the operand bytes per MFMA) when that still gives ~one
+  // workgroup per CU, else 128x128.  GIMS_X3P_TILE=128|256 forces one (A/B).
+  static const int force = env_int("GIMS_X3P_TILE", 0);
+  // one-pass (Q/K/V) GEMMs: 0 = 256 x 256 tiles like the others; 2 / 3 = 256 x 128 tiles with that many ring stages (default 3)
+  static const int qkv_tile = env_int("GIMS_X3P_QKV", 3);
+  static const int small_tiles = env_int("GIMS_X3P_SMALL", 128);      // 128 x 128 tiles at or below which a launch takes 64 x 64 ones (GIMS_X3P_SMALL=0: never)
+  const bool hi_only = (a->flags & GIMS_LINEAR_HI_ONLY) != 0;
+  const int big_blocks = cdiv(a->m, 256) * cdiv(a->n, 256), tiles128 = cdiv(a->m, 128) * cdiv(a->n, 128);
+  // the 256-wide tile only when it is not half empty (n = 64 / 128 layers of the keypoint encoder and GraphSAGE)
+  const bool big = force == 256 || (force != 128 && big_blocks >= 192 && (a->n % 256 == 0 || a->n > 512));
+  if (big && hi_only && qkv_tile > 0) {
+    // one-pass GEMMs with a short K (the Q/K/V projection: K = 256, 8 stages) are all prologue and epilogue: 256 x 128
+    // tiles with 64 accumulator registers per wave let TWO workgroups share a CU, one's epilogue under the other's loads
+    return qkv_tile == 2 ? x3p_launch<256, 128, 4, 2, 2, 1>(*a, s) : x3p_launch<256, 128, 4, 2, 3, 1>(*a, s);
+  }
+  if (big) {
+    if (hi_only) return x3p_launch<256, 256, 4, 2, 4, 1>(*a, s);
+    if (a->guard.stat && x3p_tiles<256, 256>(*a) > device_cus() && guard_walk_enabled())      // guarded: one round of workgroups (see linear_x3p_guarded_kernel)
+      return x3p_launch<256, 256, 4, 2, 2, 0, true>(*a, s);
+    return x3p_launch<256, 256, 4, 2, 2>(*a, s);
+  }
+  if (a->flags & GIMS_LINEAR_CONV3) {
+    if (a->n <= 32) return x3p_launch<128, 32, 4, 1, 2, 4>(*a, s);
+    if (a->n <= 64) return x3p_launch<128, 64, 2, 2, 2, 4>(*a, s);
+    return x3p_launch<128, 128, 2, 2, 2, 4>(*a, s);
+  }
+  if (a->n <= 64 && !hi_only && force == 0) {
+    // narrow outputs (the 32- and 64-channel convolutions of the descriptor network, millions of rows): 128 x 32 / 128 x 64
+    // tiles instead of wasting three quarters / half of a 128-wide one
+    return a->n <= 32 ? x3p_launch<128, 32, 4, 1, 2>(*a, s) : x3p_launch<128, 64, 2, 2, 2>(*a, s);
+  }
+  if (force == 64 || (force == 0 && tiles128 <= small_tiles)) {
+    // launches that leave most of the chip idle at 128 x 128 (one pair through forward(): 32 ... 96 tiles at 2 x 1024 keypoints): 64 x 64 tiles
+    // on four waves -- four times the workgroups, the same K order per output element (bit-identical), and what a launch costs there is
+    // the latency of its K loop, not its matrix work
+    return hi_only ? x3p_launch<64, 64, 2, 2, 4, 1>(*a, s) : x3p_launch<64, 64, 2, 2, 3>(*a, s);
+  }
+  if (hi_only) return x3p_launch<128, 128, 2, 2, 4, 1>(*a, s);
+  if (force == 128 || tiles128 > 256)      // more than one tile per CU (or GIMS_X3P_TILE=128): the 4-wave tile, two workgroups per CU
+    return x3p_launch<128, 128, 2, 2, 2>(*a, s);
+  // small launches are latency-bound (one tile per CU, ~1 us per K step at one wave per SIMD): the same 128 x 128 tile on
+  // EIGHT waves (two per SIMD, 64 x 32 ... per wave) hides the LDS and MFMA-chain latencies: 23 -> 18 us at 8192 rows,
+  // 21 -> 15 us at 2048 rows (tools/gemm_probe.py); same K order per output element: bit-identical results
+  return x3p_launch<128, 128, 4, 2, 2>(*a, s);
 }
 
 extern "C" int gims_linear_put(const gims_linear_args* a, gims_linear_args* dev_dst, void* stream) {
@@ -843,9 +825,7 @@ extern "C" int gims_linear_batch(const gims_linear_args* dev_args, int32_t count
   } else if (precision == GIMS_PREC_F32) {
     hipLaunchKernelGGL(linear_f32_batch_kernel, grid, dim3(256), 0, s, dev_args);
   } else if (precision == GIMS_PREC_BF16X3) {
-    int rc = x3_attr();
-    if (rc != GIMS_OK) return rc;
-    hipLaunchKernelGGL(linear_bf16x3_batch_kernel, grid, dim3(256), 4 * X3_PLANE * sizeof(uint16_t), s, dev_args);
+    return x3_launch(linear_bf16x3_batch_kernel, grid, dev_args, s);
   } else {
     GIMS_CHECK_ARG(false, "gims_linear_batch: unknown precision %d", precision);
   }

@@ -1102,10 +1102,6 @@ __global__ void ot_rescue_end_kernel(const OtDev* __restrict__ probs, int np) {
 }
 
 // ---- host side of the on-chip path
-static int ot_env(const char* name, int dflt) {
-  const char* s = getenv(name);
-  return s ? atoi(s) : dflt;
-}
 static int ot_cus() {
   int n = 0;
   if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, current_device()) != hipSuccess) n = 0;
@@ -1138,12 +1134,32 @@ static OtRescueState* ot_rescue_state() {
 // the 256 CUs its workgroups need; GIMS_OT_RESIDENT=0 / GIMS_OT_STREAMED select the streamed kernels.
 static OtR2Plan ot_res2_choose(const gims_ot_problem* pr, int np, int iters, int flags) {
   OtR2Plan none{};
-  if ((flags & GIMS_OT_STREAMED) || !ot_env("GIMS_OT_RESIDENT", 1) || iters < 1 || ot_cus() < 256) return none;
+  if ((flags & GIMS_OT_STREAMED) || !env_int("GIMS_OT_RESIDENT", 1) || iters < 1 || ot_cus() < 256) return none;
   // (no size gate: measured down to one problem of 128^2 the 2-D kernel's ~5.5 us per iteration beats the two launches per
   // iteration of the streamed kernels -- 0.60 vs 0.75 ms per 100 iterations)
   std::vector<OtR2Host> h(np);
   for (int i = 0; i < np; ++i) { h[i] = OtR2Host{}; h[i].n = pr[i].n; h[i].m = pr[i].m; }
   return ot_res2_plan(h.data(), np, iters);
+}
+
+// The instances of the streamed kernels by column quads per thread: ot_iter_kernel<CPT, R> sweeps slabs of R rows, ot_select_kernel<CPT, RS>
+// of RS rows.  f is called with the constants of the instance that serves cpt (the launches check cpt <= 8 first; sizing may ask beyond it).
+template <int CPT_, int R_, int RS_> struct OtInst { static constexpr int CPT = CPT_, R = R_, RS = RS_; };
+template <typename F>
+static auto ot_instance(int cpt, F&& f) {
+  if (cpt == 1) return f(OtInst<1, OT_R, OT_R>{});
+  if (cpt == 2) return f(OtInst<2, 4, 4>{});      // (select: four-row slabs: eight staged 364 B of the row pieces in scratch)
+  // (select: two rows per slab for the 4- and 8-quad instances: with eight, the two slabs' worth of staged rows are 256-512 registers per lane: 1.1 KB of scratch)
+  if (cpt <= 4) return f(OtInst<4, 2, 2>{});
+  return f(OtInst<8, 1, 2>{});                    // 16 384 < m <= 32 768 (round 5: the graph build's limit)
+}
+// The register-resident sweeps of the backward pass by column pieces per thread (cpt <= 9)
+template <typename F>
+static void ot_bwd_instance(int cpt, F&& f) {
+  if (cpt <= 1) f(std::integral_constant<int, 1>{});
+  else if (cpt <= 3) f(std::integral_constant<int, 3>{});
+  else if (cpt <= 5) f(std::integral_constant<int, 5>{});
+  else f(std::integral_constant<int, 9>{});
 }
 
 static void ot_launch_shape(const gims_ot_problem* pr, int np, int& threads, int& cpt, int& maxn, int& maxm) {
@@ -1158,7 +1174,7 @@ static void ot_launch_shape(const gims_ot_problem* pr, int np, int& threads, int
 // workgroups per problem.  Large workgroups (one resident per CU) run persistent-style: ~256 in total, each
 // walking several slabs with the prefetch above; small workgroups want ~4 per CU for latency hiding.
 static int ot_G(int n, int np, int threads, int cpt) {
-  const int rows = cpt > 4 ? 1 : (cpt >= 3 ? 2 : (cpt == 2 ? 4 : OT_R));   // rows per slab of ot_iter_kernel<CPT, R>
+  const int rows = ot_instance(cpt, [](auto inst) { return decltype(inst)::R; });   // rows per slab of ot_iter_kernel<CPT, R>
   const int total = threads >= 1024 ? 256 : (threads >= 512 ? 512 : 1024);
   int cap = total / (np > 0 ? np : 1);
   if (cap < 4) cap = 4;
@@ -1208,10 +1224,7 @@ static OtWs ot_layout(const gims_ot_problem* pr, int np, int flags, WsLayout& L,
 // u and v into slot hist_slot of the history (-1: none)
 static void ot_streamed_iteration(const OtWs& w, const OtDev* dp, int np, float alpha, int rescue, int hist_slot, hipStream_t s) {
   const dim3 gi(w.maxG, np), gc(cdiv(w.maxm + 1, 64), np), bt(w.threads);
-  if (w.cpt == 1) hipLaunchKernelGGL((ot_iter_kernel<1, 8>), gi, bt, 0, s, dp, alpha, rescue);
-  else if (w.cpt == 2) hipLaunchKernelGGL((ot_iter_kernel<2, 4>), gi, bt, 0, s, dp, alpha, rescue);
-  else if (w.cpt <= 4) hipLaunchKernelGGL((ot_iter_kernel<4, 2>), gi, bt, 0, s, dp, alpha, rescue);
-  else hipLaunchKernelGGL((ot_iter_kernel<8, 1>), gi, bt, 0, s, dp, alpha, rescue);      // 16 384 < m <= 32 768 (round 5: the graph build's limit)
+  ot_instance(w.cpt, [&](auto inst) { using I = decltype(inst); hipLaunchKernelGGL((ot_iter_kernel<I::CPT, I::R>), gi, bt, 0, s, dp, alpha, rescue); });
   hipLaunchKernelGGL(ot_colreduce_kernel, gc, dim3(1024), 0, s, dp, hist_slot, rescue);
 }
 
@@ -1244,7 +1257,7 @@ static int ot_match(const gims_ot_problem* pr, int np, float alpha, int iters, f
   const OtDev* dp = (const OtDev*)work;
   const bool onchip = w.plan2.ok && iters >= 1;
   // the 2-D on-chip kernel forms the start potentials itself (GIMS_OT_R2_INIT=0: the separate sweep, for cross-checks)
-  const int init_inside = onchip && ot_env("GIMS_OT_R2_INIT", 1) ? 1 : 0;
+  const int init_inside = onchip && env_int("GIMS_OT_R2_INIT", 1) ? 1 : 0;
   if (init_inside) hipLaunchKernelGGL(ot_status0_kernel, dim3(cdiv(np, 256)), dim3(256), 0, s, dp, np);
   else hipLaunchKernelGGL(ot_init_kernel, dim3(cdiv(maxn, 4), np), dim3(256), 0, s, dp, alpha, iters == 0 ? 1 : 0, 0);
   const dim3 gi(w.maxG, np);
@@ -1256,12 +1269,12 @@ static int ot_match(const gims_ot_problem* pr, int np, float alpha, int iters, f
     }
     const int rc = ot_res2_run(w.plan2, h2.data(), np, alpha, iters, init_inside, w.onchip, s);
     if (rc != GIMS_OK) return rc;
-    const int force_fail = ot_env("GIMS_OT_FORCE_FAIL", 0);       // test hook: pretend every on-chip solve timed out
+    const int force_fail = env_int("GIMS_OT_FORCE_FAIL", 0);       // test hook: pretend every on-chip solve timed out
     if (force_fail) hipLaunchKernelGGL(ot_poison_kernel, dim3(np), dim3(256), 0, s, dp);
     // Problems whose on-chip solve gave up (status 2) are re-solved here, before the selection kernels read u and v.
     OtRescueState* rs = ot_rescue_state();
     if (!rs) { set_error("gims_sinkhorn_match: no rescue state on this device"); return GIMS_EHIP; }
-    const int mode = ot_env("GIMS_OT_RESCUE", -1);                // 0: one-workgroup kernel only, 1: streamed always, default: streamed while marginal
+    const int mode = env_int("GIMS_OT_RESCUE", -1);                // 0: one-workgroup kernel only, 1: streamed always, default: streamed while marginal
     bool marginal;
     {
       std::lock_guard<std::mutex> lock(g_rescue_mu);
@@ -1284,11 +1297,7 @@ static int ot_match(const gims_ot_problem* pr, int np, float alpha, int iters, f
   } else {
     for (int it = 0; it < iters; ++it) ot_streamed_iteration(w, dp, np, alpha, 0, -1, s);
   }
-  if (cpt == 1) hipLaunchKernelGGL(ot_select_kernel<1>, gi, dim3(threads), 0, s, dp);
-  else if (cpt == 2) hipLaunchKernelGGL((ot_select_kernel<2, 4>), gi, dim3(threads), 0, s, dp);      // (four-row slabs: eight staged 364 B of the row pieces in scratch)
-  // (two rows per slab for the 4- and 8-quad instances: with eight, the two slabs' worth of staged rows are 256-512 registers per lane: 1.1 KB of scratch)
-  else if (cpt <= 4) hipLaunchKernelGGL((ot_select_kernel<4, 2>), gi, dim3(threads), 0, s, dp);
-  else hipLaunchKernelGGL((ot_select_kernel<8, 2>), gi, dim3(threads), 0, s, dp);
+  ot_instance(cpt, [&](auto inst) { using I = decltype(inst); hipLaunchKernelGGL((ot_select_kernel<I::CPT, I::RS>), gi, dim3(threads), 0, s, dp); });
   hipLaunchKernelGGL(ot_colbest_kernel, dim3(cdiv(maxm, 32), np), dim3(256), 0, s, dp);
   const int mx = maxn > maxm ? maxn : maxm;
   hipLaunchKernelGGL(ot_mutual_kernel, dim3(cdiv(mx, 256), np), dim3(256), 0, s, dp, match_threshold);
@@ -1447,7 +1456,7 @@ extern "C" int gims_sinkhorn_backward(const gims_ot_problem* pr, int32_t np, flo
   if (rc != GIMS_OK) return rc;
   const OtBwd* dp = (const OtBwd*)work;
   const int mx = maxn > maxm ? maxn : maxm;
-  if (iters <= OT_BWD_MAX_ITERS && cdiv(maxm + 1, 512) <= 9 && !ot_env("GIMS_OT_BWD_INPLACE", 0)) {
+  if (iters <= OT_BWD_MAX_ITERS && cdiv(maxm + 1, 512) <= 9 && !env_int("GIMS_OT_BWD_INPLACE", 0)) {
     // low-rank form: reductions only per iteration, one K = 2 iters product at the end
     const dim3 gs(cdiv(maxn + 1, BW_ROWS), np), gc(cdiv(maxm + 1, 16), np);
     const int cpt = cdiv(maxm + 1, 512);
@@ -1455,10 +1464,7 @@ extern "C" int gims_sinkhorn_backward(const gims_ot_problem* pr, int32_t np, flo
     hipLaunchKernelGGL(ot_bwd_colsum_rec_kernel, gc, dim3(1024), 0, s, dp, 1.f, iters);
     for (int k = iters; k >= 1; --k) {
       const int first = k == iters ? 1 : 0;
-      if (cpt <= 1) hipLaunchKernelGGL((ot_bwd_reduce_kernel<1>), gs, dim3(512), 0, s, dp, alpha, k, first);
-      else if (cpt <= 3) hipLaunchKernelGGL((ot_bwd_reduce_kernel<3>), gs, dim3(512), 0, s, dp, alpha, k, first);
-      else if (cpt <= 5) hipLaunchKernelGGL((ot_bwd_reduce_kernel<5>), gs, dim3(512), 0, s, dp, alpha, k, first);
-      else hipLaunchKernelGGL((ot_bwd_reduce_kernel<9>), gs, dim3(512), 0, s, dp, alpha, k, first);
+      ot_bwd_instance(cpt, [&](auto n) { hipLaunchKernelGGL((ot_bwd_reduce_kernel<decltype(n)::value>), gs, dim3(512), 0, s, dp, alpha, k, first); });
       hipLaunchKernelGGL(ot_bwd_colsum_rec_kernel, gc, dim3(1024), 0, s, dp, -1.f, k - 1);
     }
     const int64_t fmax = (int64_t)(maxn + 1 + maxm + 1) * iters;
@@ -1482,10 +1488,7 @@ extern "C" int gims_sinkhorn_backward(const gims_ot_problem* pr, int32_t np, flo
     hipLaunchKernelGGL(ot_bwd_colsum_kernel, gc, dim3(256), 0, s, dp, 1.f);
     for (int k = iters; k >= 1; --k) {
       const int first = k == iters ? 1 : 0;
-      if (cpt <= 1) hipLaunchKernelGGL((ot_bwd_fused_reg_kernel<1>), gs, dim3(512), 0, s, dp, alpha, k, first);
-      else if (cpt <= 3) hipLaunchKernelGGL((ot_bwd_fused_reg_kernel<3>), gs, dim3(512), 0, s, dp, alpha, k, first);
-      else if (cpt <= 5) hipLaunchKernelGGL((ot_bwd_fused_reg_kernel<5>), gs, dim3(512), 0, s, dp, alpha, k, first);
-      else if (cpt <= 9) hipLaunchKernelGGL((ot_bwd_fused_reg_kernel<9>), gs, dim3(512), 0, s, dp, alpha, k, first);
+      if (cpt <= 9) ot_bwd_instance(cpt, [&](auto n) { hipLaunchKernelGGL((ot_bwd_fused_reg_kernel<decltype(n)::value>), gs, dim3(512), 0, s, dp, alpha, k, first); });
       else hipLaunchKernelGGL((ot_bwd_fused_kernel<false>), gs, dim3(256), 0, s, dp, alpha, k, first);
       hipLaunchKernelGGL(ot_bwd_colsum_kernel, gc, dim3(256), 0, s, dp, -1.f);
     }

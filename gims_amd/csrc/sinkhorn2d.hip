@@ -832,10 +832,6 @@ __global__ __launch_bounds__(R2_NT, 1) void ot_res2_kernel(OtR2Args a) {
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static int r2_env(const char* name, int dflt) {
-  const char* s = getenv(name);
-  return s ? atoi(s) : dflt;
-}
 static inline int r2_up4(int x) { return (x + 3) & ~3; }
 
 // Geometry classes.  The decomposition of a problem -- nx row groups x nc column blocks, hence every summation order inside the solve -- is a
@@ -971,7 +967,7 @@ static R2State* r2_state(const void* kernel, int threads, int blocks, size_t lds
   const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds);
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
   st.resident_ok = (e == hipSuccess && per_cu * cus >= blocks) ? 1 : 0;
-  st.wt_local = r2_env("GIMS_OT_R2_WT", 0) ? 1 : 0;
+  st.wt_local = env_int("GIMS_OT_R2_WT", 0) ? 1 : 0;
   st.h_place = (volatile int*)pinned_once("ot_res2_place", 256);
   if (!st.h_place || hipEventCreateWithFlags(&st.place_ev, hipEventDisableTiming) != hipSuccess) return nullptr;
   return &states.emplace(dev, st).first->second;
@@ -1018,9 +1014,9 @@ static int run_class(const OtR2Plan& P, const OtR2Host* hp, int np, float alpha,
   if (*st->h_place) st->wt_local = 1;
   const int wt_local = st->wt_local;
   // GIMS_OT_REFRESH: k > 0 = a derivation every k iterations (rounds 2-4: 50); 0 (default) = adaptive, see the header; -1 = the final one only
-  int refresh = r2_env("GIMS_OT_REFRESH", 0);
+  int refresh = env_int("GIMS_OT_REFRESH", 0);
   if (refresh == 0 && iters > R2_FLAG_ITERS) refresh = 50;       // more iterations than flags: the fixed period of rounds 2-4
-  const int prof = r2_env("GIMS_OT_PROF", 0);
+  const int prof = env_int("GIMS_OT_PROF", 0);
   for (int gi = 0; gi < P.ngroups; ++gi) {
     const int p0 = gi * P.ppg, p1 = (p0 + P.ppg < np) ? p0 + P.ppg : np;
     // (unit (problem q, row group xr) -> XCD unit % 8, slot unit / 8 of that XCD's workgroups: computed in the kernel from p0, pcount, nx, nc)
@@ -1045,7 +1041,7 @@ static int run_class(const OtR2Plan& P, const OtR2Host* hp, int np, float alpha,
       GIMS_LAUNCH_CHECK();
     }
   }
-  if (r2_env("GIMS_OT_R2_DEBUG", 0)) {          // diagnostics (synchronous): which bounded wait ran out, by site number in source order
+  if (env_int("GIMS_OT_R2_DEBUG", 0)) {          // diagnostics (synchronous): which bounded wait ran out, by site number in source order
     int h[4] = {0, 0, 0, 0};
     GIMS_HIP(hipStreamSynchronize(s));
     GIMS_HIP(hipMemcpy(h, dplace, sizeof(h), hipMemcpyDeviceToHost));

@@ -816,8 +816,8 @@ static int ta_splits(const gims_train_attn_args* g, bool over_keys) {
     min_tiles = std::min(min_tiles, cdiv(over_keys ? p.nk : p.nq, 32));
   }
   int s = (int)std::min<int64_t>(TA_MAX_SPLITS, std::max<int64_t>(1, (2048 + waves - 1) / std::max<int64_t>(waves, 1)));
-  const char* e = getenv("GIMS_TRAIN_ATTN_SPLITS");
-  if (e && atoi(e) >= 1) s = std::min(atoi(e), TA_MAX_SPLITS);
+  const int forced = env_int("GIMS_TRAIN_ATTN_SPLITS", 0);
+  if (forced >= 1) s = std::min(forced, TA_MAX_SPLITS);
   return std::max(1, std::min(s, min_tiles));
 }
 

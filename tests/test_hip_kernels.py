@@ -3,6 +3,8 @@
 Checker = the CPU oracle (oracle/gims_oracle.py) / plain float64 NumPy on the same seeded inputs.
 Integer / index outputs must be bit-exact; floating-point tolerances are stated next to each check.
 """
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -725,6 +727,31 @@ def test_attention_optimistic_overflow_falls_back(hip, monkeypatch, kernel, pres
     assert np.isfinite(o).all()
     assert np.abs(o - ref).max() < 1.5e-2
     np.testing.assert_allclose(o[:40, :64], np.broadcast_to(f[700, 512:576], (40, 64)), atol=5e-3)   # one-hot rows: V[700]
+
+
+@pytest.mark.parametrize("x3,problems,n,family", [
+    (False, 1, 256, "wave4"),        # too few queries to split their keys
+    (False, 1, 1024, "split"), (False, 1, 2048, "split"),      # two / four key parts
+    (False, 16, 1024, "split"),      # 512 query blocks: the last launch that splits ...
+    (False, 17, 1024, "wave4"),      # ... 576: the first that does not, and not yet enough for the 8-wave kernel
+    (False, 32, 512, "split"),       # the fewest queries that split, at the most query blocks
+    (False, 32, 1024, "wave8"),      # 256 workgroups of 512 queries: fills the chip
+    (True, 4, 1024, "x3"), (True, 32, 1024, "x3"),      # narrow (64 wide workgroups) / wide (512)
+])
+def test_attention_kernel_family_by_launch_shape(hip, monkeypatch, x3, problems, n, family):
+    """Which kernel family an UNFORCED attention launch takes is a function of its shape alone (4 heads, `problems` self-attention problems of n
+    keypoints): one launch, counted by the library under the expected family and under no other."""
+    for name in [k for k in os.environ if k.startswith("GIMS_ATTN_")]:
+        monkeypatch.delenv(name)
+    rows, H = problems * n, 4
+    qkv = (torch.randn((rows, 1536 if x3 else 768), dtype=torch.float32, device="cuda") * 0.5).to(torch.bfloat16)
+    pr = torch.tensor([(i * n, n, i * n, n) for i in range(problems)], dtype=torch.int32, device="cuda")
+    out = torch.empty((rows, 256), dtype=torch.float32, device="cuda")
+    hip.attention_launch_counts(reset=True)
+    hip.attention(qkv, pr, n, H, out, x3=x3)
+    counts = {k: v for k, v in hip.attention_launch_counts().items() if v}
+    assert counts == {family: 1}
+    assert torch.isfinite(out).all()
 
 
 # --------------------------------------------------------------------------------------------- sinkhorn + selection
