@@ -24,8 +24,7 @@ class GimsHipError(RuntimeError):
 
 
 _DECL = re.compile(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*\1\s*;"               # 1, 2: typedef struct x { body } x;
-                   r"|struct\s+(\w+)\s*;"                                         # 3: forward declaration
-                   r"|([\w\s*]+?)\b(gims_\w+)\s*\(([^(){};]*)\)\s*;", re.S)       # 4, 5, 6: ret gims_x(args);
+                   r"|([\w\s*]+?)\b(gims_\w+)\s*\(([^(){};]*)\)\s*;", re.S)       # 3, 4, 5: ret gims_x(args);
 _MEMBER = re.compile(r"((?:const\s+)?(?:struct\s+)?\w+)\b(.*)", re.S)            # type, declarators
 _DECLARATOR = re.compile(r"([\s*]*)(\w+)\s*((?:\[[^\]]+\]\s*)*)")                 # stars, name, [dims]
 _INT_EXPR = re.compile(r"[\w\s()+\-*|<]+")
@@ -41,7 +40,6 @@ def parse(header_path: str = HEADER_PATH) -> Abi:
 
 def parse_text(text: str) -> Abi:
     abi = Abi({}, {}, {}, {})
-    tags = set()                                                                   # forward-declared structs: pointers to them are fine
 
     def fail(what, where):
         raise GimsHipError(f"gims_hip.h, line {text.count(chr(10), 0, where) + 1}: {what}")
@@ -57,7 +55,7 @@ def parse_text(text: str) -> Abi:
     def ctype(c_text, where, ret=False):
         base = re.sub(r"\b(const|struct)\b|\*", " ", c_text).strip()
         if "*" in c_text:
-            if base not in SCALARS and base not in abi.structs and base not in tags and base not in ("void", "char"):
+            if base not in SCALARS and base not in abi.structs and base not in ("void", "char"):
                 fail(f"pointer to unknown type {c_text!r}", where)
             return C.c_char_p if ret and base == "char" else C.c_void_p
         if base not in SCALARS and base not in abi.structs:
@@ -99,14 +97,12 @@ def parse_text(text: str) -> Abi:
             fail(f"cannot parse the declaration {text[pos:].split(chr(10))[0].strip()!r} (unknown form, or a missing ';')", pos)
         if m[1]:
             abi.structs[m[1]] = type(m[1], (C.Structure,), {"_fields_": fields(m[1], m[2], m.start(2))})
-        elif m[3]:
-            tags.add(m[3])
         else:
-            args = [] if m[6].strip() == "void" else [re.fullmatch(r"(.*?)\s*\b(\w+)", a.strip(), re.S) for a in m[6].split(",")]
+            args = [] if m[5].strip() == "void" else [re.fullmatch(r"(.*?)\s*\b(\w+)", a.strip(), re.S) for a in m[5].split(",")]
             if not all(a and a[1] for a in args):
-                fail(f"cannot parse the arguments of {m[5]}: {' '.join(m[6].split())!r}", pos)
+                fail(f"cannot parse the arguments of {m[4]}: {' '.join(m[5].split())!r}", pos)
             c_args = [" ".join(a[1].split()) for a in args]
-            abi.c_types[m[5]] = (" ".join(m[4].split()), c_args)
-            abi.signatures[m[5]] = (ctype(m[4], pos, ret=True), [ctype(a, pos) for a in c_args])
+            abi.c_types[m[4]] = (" ".join(m[3].split()), c_args)
+            abi.signatures[m[4]] = (ctype(m[3], pos, ret=True), [ctype(a, pos) for a in c_args])
         pos = _SPACE.match(text, m.end()).end()
     return abi

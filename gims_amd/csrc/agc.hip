@@ -1552,7 +1552,7 @@ static bool agc_takes_robust_flow(const gims_agc_image* images, int n_images, in
   return robust;
 }
 
-extern "C" size_t gims_agc_workspace_bytes_ex(const gims_agc_image* images, int32_t n_images, int32_t flags) {
+extern "C" size_t gims_agc_workspace_bytes(const gims_agc_image* images, int32_t n_images, int32_t flags) {
   using namespace gims;
   if (!images || n_images <= 0) return 0;
   const bool robust = agc_takes_robust_flow(images, n_images, flags);
@@ -1561,30 +1561,15 @@ extern "C" size_t gims_agc_workspace_bytes_ex(const gims_agc_image* images, int3
   return L.bytes();
 }
 
-extern "C" size_t gims_agc_workspace_bytes(const gims_agc_image* images, int32_t n_images) {
-  return gims_agc_workspace_bytes_ex(images, n_images, GIMS_AGC_ROBUST);        // enough for either flow
-}
-
 extern "C" int32_t gims_agc_max_keypoints(void) { return gims::AGC_MAX_N; }
 
-extern "C" int gims_agc_build(const gims_agc_image* images, int32_t n_images, double radius, double percentile,
-                              int32_t min_size, void* work, size_t work_bytes, void* stream) {
-  return gims_agc_build_ex(images, n_images, radius, percentile, min_size, 0, work, work_bytes, stream);
-}
-
-// one (radius, percentile, min_size) for every image: the per-image entry with the triple replicated
-extern "C" int gims_agc_build_ex(const gims_agc_image* images, int32_t n_images, double radius, double percentile,
-                                 int32_t min_size, int32_t flags, void* work, size_t work_bytes, void* stream) {
-  GIMS_CHECK_ARG(images && n_images > 0 && work, "gims_agc_build: null / empty arguments");
-  const gims_agc_params one = {radius, percentile, min_size, 0};
-  const std::vector<gims_agc_params> params((size_t)n_images, one);
-  return gims_agc_build_v(images, n_images, params.data(), flags, work, work_bytes, stream);
-}
-
-extern "C" int gims_agc_build_v(const gims_agc_image* images, int32_t n_images, const gims_agc_params* params, int32_t flags, void* work,
-                                size_t work_bytes, void* stream) {
+// n_params == 1: one (radius, percentile, min_size) for every image; n_params == n_images: params[i] belongs to images[i]
+extern "C" int gims_agc_build(const gims_agc_image* images, int32_t n_images, const gims_agc_params* params, int32_t n_params, int32_t flags,
+                              void* work, size_t work_bytes, void* stream) {
   using namespace gims;
-  GIMS_CHECK_ARG(images && n_images > 0 && work && params, "gims_agc_build: null / empty arguments");
+  GIMS_CHECK_ARG(images && n_images > 0 && work, "gims_agc_build: null / empty arguments");
+  GIMS_CHECK_ARG(params && (n_params == 1 || n_params == n_images), "gims_agc_build: h_params is null or n_params=%d is neither 1 nor n_images=%d",
+                 n_params, n_images);
   // GIMS_AGC_ROBUST=1 / GIMS_AGC_WINDOW_SHIFT=<x> (read per call: the tests switch flows and force a missed window)
   const bool robust = agc_takes_robust_flow(images, n_images, flags);
   const char* env_shift = getenv("GIMS_AGC_WINDOW_SHIFT");
@@ -1599,7 +1584,7 @@ extern "C" int gims_agc_build_v(const gims_agc_image* images, int32_t n_images, 
   std::vector<AgcWs> hws(n_images);
   WsLayout lay(work);
   agc_batch_layout(images, n_images, robust, lay, hws.data());
-  GIMS_CHECK_ARG(work_bytes >= lay.bytes(), "gims_agc_build: workspace too small (%zu bytes; gims_agc_workspace_bytes_ex asks for %zu for the %s flow)", work_bytes,
+  GIMS_CHECK_ARG(work_bytes >= lay.bytes(), "gims_agc_build: workspace too small (%zu bytes; gims_agc_workspace_bytes asks for %zu for the %s flow)", work_bytes,
                  lay.bytes(), robust ? "robust" : "window");
   hipStream_t s = (hipStream_t)stream;
   AgcWs* dws = (AgcWs*)work;
@@ -1609,19 +1594,20 @@ extern "C" int gims_agc_build_v(const gims_agc_image* images, int32_t n_images, 
     AgcWs* w = &hws[i];
     w->kpts = im.kpts; w->desc = im.desc; w->ldd = im.ldd; w->kept = im.kept; w->indptr = im.indptr; w->indices = im.indices;
     w->info = im.info; w->max_edges_dir = im.max_edges_dir;
+    const gims_agc_params& pm = params[n_params == 1 ? 0 : i];
     // K2 rank: k = int(L * p / 100), clamped (agc.py:378-379)
     const int64_t L = (int64_t)im.n * (im.n - 1) / 2;
-    int64_t k = (int64_t)(((double)L * params[i].percentile) / 100.0);
+    int64_t k = (int64_t)(((double)L * pm.percentile) / 100.0);
     if (k >= L) k = L - 1;
     if (k < 0) k = 0;
     w->krank = k;
     // radius candidates go through a keypoint grid of cell side 1.001 |r|, never below 1e-3 (a larger cell only costs tests); an infinite radius
     // puts every point into one cell (every pair is tested: what the predicate asks for), a NaN radius keeps no pair (agc.py:443: d2 <= r2 is False)
-    double side = fabs(params[i].radius) * 1.001;
+    double side = fabs(pm.radius) * 1.001;
     if (!(side >= 1e-3)) side = 1e-3;
-    w->r2 = params[i].radius * params[i].radius;
+    w->r2 = pm.radius * pm.radius;
     w->inv_side = 1.0 / side;
-    w->min_size = params[i].min_size;
+    w->min_size = pm.min_size;
     maxn = im.n > maxn ? im.n : maxn;
     maxnw = w->nw > maxnw ? w->nw : maxnw;
   }

@@ -1720,7 +1720,7 @@ static int attention_range_launch(const uint16_t* qkv, int64_t ld, int q_col, in
 static std::atomic<uint64_t> g_launch_counts[GIMS_ATTN_KERNEL_KINDS];
 static inline void count_launch(int kind) { g_launch_counts[kind].fetch_add(1, std::memory_order_relaxed); }
 
-// What every attention kernel takes in front of its own arguments, and the launch shape; filled once by gims_attention_ex after validation.
+// What every attention kernel takes in front of its own arguments, and the launch shape; filled once by gims_attention after validation.
 struct AttnPrefix {
   const uint16_t* qkv; int64_t ld; int q_col, k_col, v_col; const gims_attn_problem* problems; int n_groups, n_heads;
   float* out; int64_t ld_out; uint16_t* out_hi; uint16_t* out_lo; int64_t ld_split;
@@ -1846,26 +1846,8 @@ extern "C" int gims_attention_launch_counts(uint64_t* counts, int32_t n, int32_t
   return GIMS_OK;
 }
 
-extern "C" int gims_attention(const uint16_t* qkv, int64_t ld, int32_t q_col, int32_t k_col, int32_t v_col,
-                              const gims_attn_problem* problems, int32_t n_problems, int32_t max_n_q,
-                              int32_t n_heads, float* out, int64_t ld_out, uint16_t* out_hi, uint16_t* out_lo,
-                              int64_t ld_split, int32_t flags, void* stream) {
-  return gims_attention_stat(qkv, ld, q_col, k_col, v_col, problems, n_problems, max_n_q, n_heads, out, ld_out, out_hi, out_lo, ld_split, flags,
-                             nullptr, stream);
-}
-
-extern "C" int gims_attention_stat(const uint16_t* qkv, int64_t ld, int32_t q_col, int32_t k_col, int32_t v_col,
-                                   const gims_attn_problem* problems, int32_t n_problems, int32_t max_n_q,
-                                   int32_t n_heads, float* out, int64_t ld_out, uint16_t* out_hi, uint16_t* out_lo,
-                                   int64_t ld_split, int32_t flags, uint64_t* stat_u64, void* stream) {
-  gims_attn_args a = {};
-  a.qkv = qkv; a.ld = ld; a.q_col = q_col; a.k_col = k_col; a.v_col = v_col; a.problems = problems; a.n_problems = n_problems; a.max_n_q = max_n_q;
-  a.n_heads = n_heads; a.out = out; a.ld_out = ld_out; a.out_hi = out_hi; a.out_lo = out_lo; a.ld_split = ld_split; a.flags = flags; a.stat = stat_u64;
-  return gims_attention_ex(&a, stream);
-}
-
-extern "C" int gims_attention_ex(const gims_attn_args* args, void* stream) {
-  GIMS_CHECK_ARG(args, "gims_attention_ex: null arguments");
+extern "C" int gims_attention(const gims_attn_args* args, void* stream) {
+  GIMS_CHECK_ARG(args, "gims_attention: null arguments");
   const uint16_t* qkv = args->qkv;
   const int64_t ld = args->ld, ld_out = args->ld_out, ld_split = args->ld_split;
   const int32_t q_col = args->q_col, k_col = args->k_col, v_col = args->v_col, n_problems = args->n_problems, max_n_q = args->max_n_q, n_heads = args->n_heads,
@@ -1878,9 +1860,9 @@ extern "C" int gims_attention_ex(const gims_attn_args* args, void* stream) {
   const gims_attn_guard guard = args->guard;
   GIMS_CHECK_ARG(!guard.stat || ((flags & GIMS_ATTN_X3) && !stat_u64 && (guard.kind == GIMS_GUARD_PEAKED || guard.kind == GIMS_GUARD_RANGE) &&
                                  guard.n_heads > 0 && guard.n_heads <= 15 && (((uintptr_t)guard.stat) & 7) == 0),
-                 "gims_attention_ex: a guard goes with GIMS_ATTN_X3, without a statistic of its own, kind GIMS_GUARD_*, 8-byte aligned stat");
+                 "gims_attention: a guard goes with GIMS_ATTN_X3, without a statistic of its own, kind GIMS_GUARD_*, 8-byte aligned stat");
   using namespace gims;
-  GIMS_CHECK_ARG((((uintptr_t)stat_u64) & 7) == 0, "gims_attention_stat: stat must be 8-byte aligned");
+  GIMS_CHECK_ARG((((uintptr_t)stat_u64) & 7) == 0, "gims_attention: stat must be 8-byte aligned");
   unsigned long long* stat = (unsigned long long*)stat_u64;
   GIMS_CHECK_ARG(qkv && problems && (out || out_hi), "gims_attention: null pointer");
   GIMS_CHECK_ARG((out_hi == nullptr) == (out_lo == nullptr) && (ld_split % 8) == 0 && (((uintptr_t)out_hi | (uintptr_t)out_lo) & 15) == 0,

@@ -1312,15 +1312,6 @@ __global__ __launch_bounds__(256) void ch_l2norm_kernel(const float* __restrict_
   for (int j = 0; j < 4; ++j) { const int k = lane + 64 * j; if (k < c) y[row * c + k] = v[j] * inv; }
 }
 
-// elementwise clamp to [0, 6] (ReLU6 after a pointwise GEMM) and  y = a + b
-__global__ __launch_bounds__(256) void ch_relu6_kernel(float* __restrict__ x, int64_t total) {
-  const int64_t i4 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-  if (i4 >= total) return;
-  float4 v = *(float4*)(x + i4);
-  v.x = fminf(fmaxf(v.x, 0.f), 6.f); v.y = fminf(fmaxf(v.y, 0.f), 6.f); v.z = fminf(fmaxf(v.z, 0.f), 6.f); v.w = fminf(fmaxf(v.w, 0.f), 6.f);
-  *(float4*)(x + i4) = v;
-}
-
 }  // namespace gims
 
 using namespace gims;
@@ -1594,13 +1585,6 @@ extern "C" int gims_ch_sandglass(const float* x, int64_t patches, int32_t hw, in
 extern "C" int gims_ch_l2norm(const float* x, int64_t rows, int32_t c, float eps, float* y, void* stream) {
   GIMS_CHECK_ARG(x && y && rows > 0 && c > 0 && c <= 256, "gims_ch_l2norm: bad arguments (c <= 256)");
   hipLaunchKernelGGL(ch_l2norm_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, rows, c, eps, y);
-  GIMS_LAUNCH_CHECK();
-  return GIMS_OK;
-}
-
-extern "C" int gims_ch_relu6(float* x, int64_t total, void* stream) {
-  GIMS_CHECK_ARG(x && total > 0 && (total % 4) == 0, "gims_ch_relu6: bad arguments (total %% 4 == 0)");
-  hipLaunchKernelGGL(ch_relu6_kernel, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, total);
   GIMS_LAUNCH_CHECK();
   return GIMS_OK;
 }

@@ -607,8 +607,6 @@ __global__ __launch_bounds__(64 * WM * WN) void linear_x3p_guarded_kernel(gims_l
   }
 }
 
-__global__ void put_linear_args_kernel(gims_linear_args a, gims_linear_args* __restrict__ dst) { *dst = a; }
-
 // ------------------------------------------------------------------------------------------ split kernel
 __global__ void split_bf16_kernel(const float* __restrict__ src, uint16_t* __restrict__ hi,
                                   uint16_t* __restrict__ lo, int64_t n) {
@@ -791,16 +789,6 @@ extern "C" int gims_linear(const gims_linear_args* a, void* stream) {
   // EIGHT waves (two per SIMD, 64 x 32 ... per wave) hides the LDS and MFMA-chain latencies: 23 -> 18 us at 8192 rows,
   // 21 -> 15 us at 2048 rows (tools/gemm_probe.py); same K order per output element: bit-identical results
   return x3p_launch<128, 128, 4, 2, 2>(*a, s);
-}
-
-extern "C" int gims_linear_put(const gims_linear_args* a, gims_linear_args* dev_dst, void* stream) {
-  using namespace gims;
-  int rc = linear_validate(a);
-  if (rc != GIMS_OK) return rc;
-  GIMS_CHECK_ARG(dev_dst != nullptr, "gims_linear_put: null destination");
-  hipLaunchKernelGGL(put_linear_args_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, *a, dev_dst);
-  GIMS_LAUNCH_CHECK();
-  return GIMS_OK;
 }
 
 extern "C" int gims_linear_put_many(const gims_linear_args* h_args, int32_t count, gims_linear_args* dev_dst, void* stream) {

@@ -327,7 +327,7 @@ extern "C" int gims_run_ops(const gims_op* ops, int32_t n_ops, void* stream) {
     if (ops[i].kind == GIMS_OP_LINEAR) {
       rc = gims_linear(&ops[i].u.lin, stream);
     } else if (ops[i].kind == GIMS_OP_ATTENTION) {
-      rc = gims_attention_ex(&ops[i].u.att, stream);
+      rc = gims_attention(&ops[i].u.att, stream);
     } else if (ops[i].kind == GIMS_OP_AUX) {
       const gims_aux_args& x = ops[i].u.aux;
       if (x.fn == GIMS_AUX_SPLIT_SPL32)
@@ -386,13 +386,6 @@ extern "C" int gims_events_create(int32_t n, void** events_out) {
   return GIMS_OK;
 }
 
-extern "C" int gims_events_record(void* event, void* stream) {
-  using namespace gims;
-  GIMS_CHECK_ARG(event, "gims_events_record: null event");
-  GIMS_HIP(hipEventRecord((hipEvent_t)event, (hipStream_t)stream));
-  return GIMS_OK;
-}
-
 // ms_out[i] = time between events[i] and events[i+1], i < n - 1; every event must have completed (synchronise first).
 extern "C" int gims_events_elapsed(void* const* events, int32_t n, float* ms_out) {
   using namespace gims;
@@ -442,11 +435,6 @@ extern "C" int gims_ops_graph_destroy(void* graph_exec) {
 
 extern "C" int gims_abi_version(void) { return GIMS_ABI_VERSION; }
 extern "C" const char* gims_last_error(void) { return gims::g_err; }
-extern "C" int gims_stream_sync(void* stream) {
-  using namespace gims;
-  GIMS_HIP(hipStreamSynchronize((hipStream_t)stream));
-  return GIMS_OK;
-}
 
 extern "C" int gims_kenc_first(const float* kpts, const float* norm3, const int32_t* seg_of_row, const float* w1,
                                const float* b1, int32_t c1, float* out, int64_t n, void* stream) {

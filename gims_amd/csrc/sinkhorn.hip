@@ -1228,14 +1228,19 @@ static void ot_streamed_iteration(const OtWs& w, const OtDev* dp, int np, float 
   hipLaunchKernelGGL(ot_colreduce_kernel, gc, dim3(1024), 0, s, dp, hist_slot, rescue);
 }
 
-static int ot_plan(const gims_ot_problem* pr, int np, int iters, int flags) {
+}  // namespace gims
+
+extern "C" int gims_sinkhorn_plan(const gims_ot_problem* pr, int32_t np, int32_t iters, int32_t flags) {
+  using namespace gims;
   if (!pr || np <= 0) return 0;
   const OtR2Plan p2 = ot_res2_choose(pr, np, iters, flags);
   return p2.ok ? p2.ngroups : 0;
 }
 
-static int ot_match(const gims_ot_problem* pr, int np, float alpha, int iters, float match_threshold, void* work, size_t work_bytes, int flags,
-                    hipStream_t s) {
+extern "C" int gims_sinkhorn_match(const gims_ot_problem* pr, int32_t np, float alpha, int32_t iters, float match_threshold, void* work,
+                                   size_t work_bytes, int32_t flags, void* stream) {
+  using namespace gims;
+  hipStream_t s = (hipStream_t)stream;
   GIMS_CHECK_ARG(pr && np > 0 && work, "gims_sinkhorn_match: null / empty arguments");
   GIMS_CHECK_ARG(iters >= 0, "gims_sinkhorn_match: iters < 0");
   for (int i = 0; i < np; ++i) {
@@ -1305,26 +1310,12 @@ static int ot_match(const gims_ot_problem* pr, int np, float alpha, int iters, f
   return GIMS_OK;
 }
 
-}  // namespace gims
-
 extern "C" size_t gims_sinkhorn_workspace_bytes(const gims_ot_problem* pr, int32_t np) {
   using namespace gims;
   if (!pr || np <= 0) return 0;
   WsLayout L(nullptr);
   ot_layout(pr, np, 0, L, nullptr);
   return L.bytes();
-}
-
-extern "C" int gims_sinkhorn_plan(const gims_ot_problem* pr, int32_t np, int32_t iters) { return gims::ot_plan(pr, np, iters, 0); }
-extern "C" int gims_sinkhorn_plan_ex(const gims_ot_problem* pr, int32_t np, int32_t iters, int32_t flags) { return gims::ot_plan(pr, np, iters, flags); }
-
-extern "C" int gims_sinkhorn_match(const gims_ot_problem* pr, int32_t np, float alpha, int32_t iters,
-                                   float match_threshold, void* work, size_t work_bytes, void* stream) {
-  return gims::ot_match(pr, np, alpha, iters, match_threshold, work, work_bytes, 0, (hipStream_t)stream);
-}
-extern "C" int gims_sinkhorn_match_ex(const gims_ot_problem* pr, int32_t np, float alpha, int32_t iters, float match_threshold, void* work,
-                                      size_t work_bytes, int32_t flags, void* stream) {
-  return gims::ot_match(pr, np, alpha, iters, match_threshold, work, work_bytes, flags, (hipStream_t)stream);
 }
 
 extern "C" int64_t gims_sinkhorn_rescues(void) {

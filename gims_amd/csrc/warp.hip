@@ -239,13 +239,6 @@ static void invert3(const double* S, double* D) {
 
 }  // namespace gims
 
-extern "C" int gims_warp_invert(const double* m, int32_t n, double* minv) {
-  using namespace gims;
-  GIMS_CHECK_ARG(m && minv && n > 0, "gims_warp_invert: null / empty arguments");
-  for (int i = 0; i < n; ++i) invert3(m + 9 * i, minv + 9 * i);
-  return GIMS_OK;
-}
-
 extern "C" int gims_warp_perspective(const uint8_t* src, int32_t n, int32_t sh, int32_t sw, int32_t c, const double* m, uint8_t* dst, int32_t dh,
                                      int32_t dw, double* work, void* stream) {
   using namespace gims;

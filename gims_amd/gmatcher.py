@@ -99,7 +99,7 @@ class GMatcher(nn.Module):
         # (v_mfma_f32_32x32x16_f16: same rate, 2^-12 instead of 2^-9 per operand; Q/K/V from the 3-pass projection, rounded to half in
         # its epilogue) -- holds the bar on the sharply peaked 'peaked' goldens (mean row maximum ~0.8) where bf16 does not.
         # 'bf16x3': Q, K, V and P as split-bf16 pairs, three MFMAs per product (GIMS_ATTN_X3): f32 class, no range limit.
-        # 'auto' (default) picks PER LAYER from what the kernels measure about that layer (gims_attention_stat): per head the mean
+        # 'auto' (default) picks PER LAYER from what the kernels measure about that layer (the stat accumulator of gims_attention): per head the mean
         # over the queries of max_k P[q, k] and the fraction of queries whose maximum exceeds 1/2 (the tail: a head with a few
         # one-hot rows among diffuse ones), and max |Q|, |K|, |V| as stored.  The first batch after the weights change runs every
         # layer at 'bf16x3' and measures; from then on a layer runs in plain bf16 while every head stays below
@@ -596,7 +596,7 @@ class GMatcher(nn.Module):
                     self._agc_retry(np.where(tri, 0, infos[:, 7]), bool(ctx.get("robust")), False)]
             action = "robust" if "robust" in acts else ("grow" if "grow" in acts else None)
         if action == "robust":
-            # the percentile window predicted from the similarity sample did not provably hold the threshold (gims_agc_build_ex): the
+            # the percentile window predicted from the similarity sample did not provably hold the threshold (gims_agc_build): the
             # outputs of this build are void; the repeat histograms every similarity
             ctx["params"] = tuple(ctx["params"][:3]) + (True,)
             self._agc_window_misses = getattr(self, "_agc_window_misses", 0) + 1
@@ -1177,7 +1177,7 @@ class GMatcher(nn.Module):
 
         All pairs of a call share radius / percentile / min_size and ``delaunay`` (ValueError otherwise) unless
         ``per_pair_graph=True``: then every dict's own values (defaults 25 / 7 / 8, False) are honoured inside the same single pass --
-        the graph build takes its parameters per image (gims_agc_build_v), the Delaunay pairs go through one Delaunay build."""
+        the graph build takes its parameters per image (gims_agc_build with one gims_agc_params each), the Delaunay pairs go through one Delaunay build."""
         tm0 = time.perf_counter()
         n_lanes = int(self.config.get('streams', 1))
         if n_lanes < 2 or len(datas) < 2 * n_lanes:

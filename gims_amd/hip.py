@@ -408,7 +408,7 @@ ATTN_NO_RANGE = _K["GIMS_ATTN_NO_RANGE"]   # a measured launch leaves the range 
 ATTN_F16 = _K["GIMS_ATTN_F16"]        # qkv holds IEEE half (gims_linear with LINEAR_OUT_F16); v_mfma_f32_32x32x16_f16 kernels
 
 
-ATTN_STAT_SCALE = float(1 << 24)       # fixed point of the row maxima in gims_attention_stat's accumulator
+ATTN_STAT_SCALE = float(1 << 24)       # fixed point of the row maxima in gims_attention's stat accumulator
 
 
 def attention(qkv: torch.Tensor, problems: torch.Tensor, max_n_q: int, n_heads: int, out=None,
@@ -417,11 +417,11 @@ def attention(qkv: torch.Tensor, problems: torch.Tensor, max_n_q: int, n_heads: 
     and/or out_split = SPL32 bf16 buffer [rows, >= 512].  q_prescaled: Q already carries ATTN_Q_SCALE.
     x3: qkv is the SPL32 split-bf16 buffer [rows, >= 1536] of the 3-pass projection (GIMS_ATTN_X3).
     f16: the 16-bit values of qkv are IEEE half, not bf16 (GIMS_ATTN_F16; the tensor's dtype stays torch.bfloat16: raw storage).
-    stat: int64 [n_heads + 1, 4] accumulator of the softmax peakedness and the operand range (gims_attention_stat; zero it before the
+    stat: int64 [n_heads + 1, 4] accumulator of the softmax peakedness and the operand range (gims_attn_args.stat; zero it before the
     first use)."""
     # (guard: an x3 launch that is a no-op unless the guard's statistic asks for the redo)
     op = op_attention(qkv, problems, max_n_q, n_heads, out, q_col, k_col, v_col, out_split, q_prescaled, x3, stat, f16, guard, no_range)
-    _check(load().gims_attention_ex(C.byref(op.u.att), _stream()), "gims_attention_ex")
+    _check(load().gims_attention(C.byref(op.u.att), _stream()), "gims_attention")
     return out if out is not None else out_split
 
 
@@ -512,31 +512,29 @@ def agc_workspace_bytes(images, flags=None) -> int:
     if nmax > agc_max_keypoints():
         raise GimsHipError(f"adaptive graph: an image has {nmax} keypoints, more than the library's limit of {agc_max_keypoints()} per image "
                            "(gims_agc_max_keypoints; the reference has none) -- reduce max_keypoints or split the image")
-    if flags is None:
-        return int(load().gims_agc_workspace_bytes(images, len(images)))
-    return int(load().gims_agc_workspace_bytes_ex(images, len(images), int(flags)))
+    return int(load().gims_agc_workspace_bytes(images, len(images), AGC_ROBUST if flags is None else int(flags)))
 
 
-AGC_ROBUST = _K["GIMS_AGC_ROBUST"]               # gims_agc_build_ex flags
+AGC_ROBUST = _K["GIMS_AGC_ROBUST"]               # gims_agc_build flags
 AGC_INFO_OVERFLOW, AGC_INFO_WINDOW_MISSED = 1, 2     # bits of info[7]
 
 
 def agc_build(images, radius, percentile, min_size, work: torch.Tensor, flags=0):
     """Asynchronous adaptive-graph build for a batch of images; see include/gims_hip.h.  An image whose info[7] has AGC_INFO_WINDOW_MISSED
     set after the call must be rebuilt with flags=AGC_ROBUST."""
-    lib = load()
-    _check(lib.gims_agc_build_ex(images, len(images), float(radius), float(percentile), int(min_size), int(flags), _p(work),
-                                 work.numel() * work.element_size(), _stream()), "gims_agc_build_ex")
+    one = AgcParams(float(radius), float(percentile), int(min_size), 0)
+    _check(load().gims_agc_build(images, len(images), C.byref(one), 1, int(flags), _p(work), work.numel() * work.element_size(), _stream()),
+           "gims_agc_build")
 
 
 def agc_build_each(images, params, work: torch.Tensor, flags=0):
-    """agc_build with each image's own parameters: params[i] = (radius, percentile, min_size) of images[i] (gims_agc_build_v)."""
+    """agc_build with each image's own parameters: params[i] = (radius, percentile, min_size) of images[i]."""
     params = list(params)
     if len(params) != len(images):
         raise ValueError(f"agc_build_each: {len(images)} images but {len(params)} parameter triples")
     arr = (AgcParams * len(params))(*[AgcParams(float(r), float(t), int(m), 0) for r, t, m in params])
-    _check(load().gims_agc_build_v(images, len(images), arr, int(flags), _p(work), work.numel() * work.element_size(), _stream()),
-           "gims_agc_build_v")
+    _check(load().gims_agc_build(images, len(images), arr, len(params), int(flags), _p(work), work.numel() * work.element_size(), _stream()),
+           "gims_agc_build")
 
 
 DT_INFO_DEGENERATE, DT_INFO_ASYMMETRIC = _K["GIMS_DT_INFO_DEGENERATE"], _K["GIMS_DT_INFO_ASYMMETRIC"]     # bits of info[7] set by delaunay_build (bit 0: AGC_INFO_OVERFLOW, same meaning)
@@ -589,7 +587,7 @@ def pack_table(images_ptrs):
 
 
 def pack_graphs_table(table, d, feat, kpts_out, score_out, seg, indptr_out, indices_out, n_rows, n_edges):
-    """pack_graphs with the descriptor table given as the numpy array of pack_table()."""
+    """One launch for the batch (gims_pack_graphs); table: the descriptor records as the numpy array of pack_table()."""
     lib = load()
     nbytes = table.nbytes
     dev_arr = torch.empty(((nbytes + 15) // 16 * 16 + 16,), dtype=torch.uint8, device=feat.device)
@@ -598,18 +596,6 @@ def pack_graphs_table(table, d, feat, kpts_out, score_out, seg, indptr_out, indi
     _check(lib.gims_pack_graphs(_p(dev_arr), len(table), int(table["n_kept"].max()), max(int(table["n_edges"].max()), 1), d,
                                 _p(feat), feat.stride(0), _p(kpts_out), _p(score_out), _p(seg), _p(indptr_out),
                                 _p(indices_out), n_rows, n_edges, st), "gims_pack_graphs")
-    return dev_arr
-
-
-def pack_graphs(pack_items, d, feat, kpts_out, score_out, seg, indptr_out, indices_out, n_rows, n_edges):
-    """pack_items: list of PackImage (host); uploaded as kernel arguments, then one launch for the batch."""
-    lib = load()
-    arr = (PackImage * len(pack_items))(*pack_items)
-    dev_arr = _upload_structs(arr, feat.device)
-    _check(lib.gims_pack_graphs(_p(dev_arr), len(pack_items), max(p.n_kept for p in pack_items),
-                                max(max(p.n_edges for p in pack_items), 1), d, _p(feat), feat.stride(0), _p(kpts_out),
-                                _p(score_out), _p(seg), _p(indptr_out), _p(indices_out), n_rows, n_edges, _stream()),
-           "gims_pack_graphs")
     return dev_arr
 
 
@@ -632,7 +618,7 @@ OT_STREAMED = _K["GIMS_OT_STREAMED"]      # flag of sinkhorn_plan / sinkhorn_mat
 
 def sinkhorn_plan(problems, iters: int, flags: int = 0) -> int:
     """0: streamed kernels (one launch per iteration); k > 0: on-chip resident kernel in k launches."""
-    return int(load().gims_sinkhorn_plan_ex(problems, len(problems), int(iters), int(flags)))
+    return int(load().gims_sinkhorn_plan(problems, len(problems), int(iters), int(flags)))
 
 
 ATTN_KERNEL_KINDS = ("wave4", "split", "wave8", "wave8_f16", "x3", "x3_guarded")
@@ -655,8 +641,8 @@ def sinkhorn_rescues() -> int:
 
 def sinkhorn_match(problems, alpha: float, iters: int, match_threshold: float, work: torch.Tensor, flags: int = 0):
     lib = load()
-    _check(lib.gims_sinkhorn_match_ex(problems, len(problems), float(alpha), int(iters), float(match_threshold), _p(work),
-                                      work.numel() * work.element_size(), int(flags), _stream()), "gims_sinkhorn_match")
+    _check(lib.gims_sinkhorn_match(problems, len(problems), float(alpha), int(iters), float(match_threshold), _p(work),
+                                   work.numel() * work.element_size(), int(flags), _stream()), "gims_sinkhorn_match")
 
 
 def ot_matrix(scores, n, m, alpha, uv):
@@ -886,11 +872,6 @@ def ch_l2norm(x, eps, y):
     rows, c = x.shape
     _check(load().gims_ch_l2norm(_p(_dev(x, torch.float32)), rows, c, float(eps), _p(y), _stream()), "gims_ch_l2norm")
     return y
-
-
-def ch_relu6(x):
-    _check(load().gims_ch_relu6(_p(_dev(x, torch.float32)), x.numel(), _stream()), "gims_ch_relu6")
-    return x
 
 
 def train_loss(items, kept0, kept1, gt: torch.Tensor, alpha: float, pos_weight: float, neg_weight: float):
@@ -1386,14 +1367,6 @@ def _image_batch(images: torch.Tensor):
         raise ValueError("image warps take device uint8 [B, H, W, 3] or [B, H, W] images")
     t = images.contiguous()
     return t if t.dim() == 4 else t.unsqueeze(-1)
-
-
-def warp_invert(m):
-    """cv::invert(M, DECOMP_LU) of float64 [n, 3, 3] matrices on the host (gims_warp_invert): what warp_perspective samples through."""
-    a = np.ascontiguousarray(np.asarray(m, dtype=np.float64).reshape(-1, 9))
-    out = np.empty_like(a)
-    _check(load().gims_warp_invert(a.ctypes.data, len(a), out.ctypes.data), "gims_warp_invert")
-    return out.reshape(-1, 3, 3)
 
 
 def warp_perspective(images: torch.Tensor, ms, dsize, out=None):

@@ -9,7 +9,7 @@
  * Conventions
  *   - every pointer is a DEVICE pointer owned by the caller unless its name starts with h_ (host);
  *   - every call enqueues work on `stream` (a hipStream_t passed as void*) and returns immediately,
- *     except the two calls documented as synchronising;
+ *     except the calls documented as synchronising;
  *   - return value: 0 on success, a negative GIMS_E* code on failure (never throws across the ABI);
  *     gims_last_error() returns a thread-local message for the last failure;
  *   - activations are POINT-MAJOR: row = keypoint, column = channel (the reference is channel-major
@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GIMS_ABI_VERSION 2   /* 2 (round 6): gims_attn_guard grew `max_thr` (so did gims_linear_args / gims_attn_args, which embed it); + gims_attention_launch_counts, gims_agc_workspace_bytes_ex */
+#define GIMS_ABI_VERSION 3   /* 3: one entry point per operation (the positional / flag-less / scalar spellings of 2 and its entry points without a caller are gone); no struct changed */
 
 #define GIMS_OK 0
 #define GIMS_EINVAL (-1)   /* bad argument (shape / alignment / null pointer) */
@@ -35,8 +35,6 @@ extern "C" {
 
 int gims_abi_version(void);
 const char* gims_last_error(void);
-/* Blocks until `stream` is idle (hipStreamSynchronize). */
-int gims_stream_sync(void* stream);
 /* Copies a small host table (descriptor arrays, offsets, <= 1 MiB) to device memory IN STREAM ORDER without touching the
  * copy engines: the bytes travel as kernel arguments (chunks of 3968 B).  Unlike a pageable hipMemcpy this never blocks
  * the submitting thread on the stream and never pins pages, so the host can keep running ahead of the GPU.  `dev` must be
@@ -68,17 +66,17 @@ int gims_upload_table(const void* host, int64_t bytes, void* dev, void* stream);
 /* Device-side guard of a launch (attention_precision='auto' of the host shell: a layer that ran on cheap operands is REDONE at f32-class accuracy
  * inside the same batch when the statistic of the cheap launch says the operands did not suffice -- no host round trip, so the results of a
  * batch never leave with the cheap tier's error).  A launch whose args carry a guard with stat != NULL is a no-op unless the guard FIRES; every
- * workgroup evaluates it at entry from `stat`, the accumulator a preceding gims_attention_stat launch of the same stream filled:
+ * workgroup evaluates it at entry from `stat`, the accumulator a preceding measured gims_attention launch (gims_attn_args.stat) of the same stream filled:
  *   GIMS_GUARD_PEAKED: some head's mean row maximum (stat[h][0] / stat[h][1] / 2^24) exceeds mean_thr, or its share of rows with a maximum above
  *                      1/2 (stat[h][3] / stat[h][1]) exceeds tail_thr, or -- max_thr > 0 -- its LARGEST row maximum (stat[h][2] / 2^24) reaches
- *                      max_thr: a single sharply peaked row inside a diffuse layer (round 6)        (guards a plain-bf16 attention layer);
+ *                      max_thr: a single sharply peaked row inside a diffuse layer                  (guards a plain-bf16 attention layer);
  *   GIMS_GUARD_RANGE : max |Q|, |K| or |V| as stored (stat[n_heads][0..2]) exceeds range_limit, or is not finite   (guards an IEEE-half layer).
  * A guarded gims_attention launch that fires stores 1 into stat[n_heads][3] (the host's record that the layer was redone).  The comparisons
  * are done in float64 exactly as written here, so a host that reads `stat` back reaches the same verdict.  stat == NULL: unconditional. */
 #define GIMS_GUARD_PEAKED 1
 #define GIMS_GUARD_RANGE 2
 typedef struct gims_attn_guard {
-  uint64_t* stat;                        /* [n_heads + 1][4], see gims_attention_stat; NULL = no guard */
+  uint64_t* stat;                        /* [n_heads + 1][4], see gims_attn_args.stat; NULL = no guard */
   double mean_thr, tail_thr, range_limit;
   int32_t n_heads, kind;                 /* GIMS_GUARD_* */
   double max_thr;                        /* GIMS_GUARD_PEAKED: 0 = the largest row maximum is not looked at */
@@ -115,7 +113,7 @@ typedef struct gims_linear_args {
   gims_attn_guard guard;               /* pre-split operands (a0_lo != NULL) only: the launch is a no-op unless the guard fires; zero = always run */
   /* pre-split operands with GIMS_LINEAR_OUT_F16 only: the launch also reports max |value| of what it stores into out_bf16, per block of
    * 256 output columns (Q | K | V of the projection in front of a GIMS_ATTN_F16 launch): range_stat[b] = max(range_stat[b], float bits of
-   * the maximum) for column block b = col / 256 < 3, by integer atomics on the f32 bit patterns -- the range row of gims_attention_stat's
+   * the maximum) for column block b = col / 256 < 3, by integer atomics on the f32 bit patterns -- the range row of gims_attn_args.stat's
    * accumulator (pass stat + 4 * n_heads), measured where the values are produced instead of by a scan of the buffer.  NULL: not measured. */
   uint64_t* range_stat;
 } gims_linear_args;
@@ -132,10 +130,9 @@ typedef struct gims_linear_args {
 
 int gims_linear(const gims_linear_args* args, void* stream);
 /* Many independent problems in ONE launch (ragged batch: per-pair score matrices, per-image similarity
- * matrices).  gims_linear_put validates one descriptor and stores it into device memory (by-value kernel
- * argument: no host staging copy, no synchronisation); gims_linear_batch launches all `count` problems,
+ * matrices).  gims_linear_put_many validates `count` descriptors and stores them into device memory (as kernel
+ * arguments: no host staging copy, no synchronisation); gims_linear_batch launches all `count` problems,
  * grid sized for the largest (max_m x max_n).  All problems of a batch share `precision`. */
-int gims_linear_put(const gims_linear_args* args, gims_linear_args* dev_dst, void* stream);
 int gims_linear_put_many(const gims_linear_args* h_args /* HOST array */, int32_t count, gims_linear_args* dev_dst, void* stream);
 int gims_linear_batch(const gims_linear_args* dev_args, int32_t count, int32_t max_m, int32_t max_n,
                       int32_t precision, void* stream);
@@ -170,36 +167,37 @@ int gims_split_spl32(const float* src, int64_t lds, uint16_t* dst, int64_t ldd, 
 /* GIMS_ATTN_F16: qkv holds IEEE half instead of bf16 (same layout; written by gims_linear with GIMS_LINEAR_OUT_F16 from the 3-pass
  * projection) and the kernels multiply on v_mfma_f32_32x32x16_f16 -- the bf16 kernels' structure and rate with three more mantissa
  * bits (2^-12 instead of 2^-9 relative per operand), P rounded to half with a row reference that keeps it below 2^15.  For
- * peaked softmaxes, where bf16 operands miss the reference's 1e-4 score bar; |Q|, |K|, |V| must stay below 65504 (the statistic of
- * gims_attention_stat reports them).  Not together with GIMS_ATTN_X3. */
+ * peaked softmaxes, where bf16 operands miss the reference's 1e-4 score bar; |Q|, |K|, |V| must stay below 65504 (the range row of
+ * `stat` reports them).  Not together with GIMS_ATTN_X3. */
 #define GIMS_ATTN_F16 4
 /* GIMS_ATTN_NO_RANGE: a measured launch (stat != NULL) leaves the range row of the accumulator alone -- the projection in front of it reported it
  * (gims_linear_args.range_stat), or the caller has no use for it */
 #define GIMS_ATTN_NO_RANGE 8
 typedef struct gims_attn_problem { int32_t q_off, n_q, kv_off, n_kv; } gims_attn_problem;
 
-int gims_attention(const uint16_t* qkv, int64_t ld, int32_t q_col, int32_t k_col, int32_t v_col,
-                   const gims_attn_problem* problems /* device */, int32_t n_problems, int32_t max_n_q,
-                   int32_t n_heads, float* out /* may be NULL */, int64_t ld_out,
-                   uint16_t* out_hi /* may be NULL */, uint16_t* out_lo, int64_t ld_split, int32_t flags, void* stream);
-/* The same launch, additionally reporting how PEAKED the softmax rows were -- the quantity that decides whether plain bf16
- * operands keep the reference's 1e-4 score bar (models/gmatcher.py:35-39 computes the softmax in f32): stat is a device array
+/* stat (may be NULL): the launch additionally reports how PEAKED the softmax rows were -- the quantity that decides whether plain bf16
+ * operands keep the reference's 1e-4 score bar (models/gmatcher.py:35-39 computes the softmax in f32): a device array
  * [n_heads + 1][4] of uint64.  Rows 0 .. n_heads-1: {sum over the reported queries of max_k P[q,k] in 2^-24 fixed point, number of
  * reported queries, largest row maximum (same fixed point), number of reported queries with a row maximum above 1/2}; row n_heads:
  * {bit patterns of max|Q|, max|K|, max|V| as stored (f32), unused} over the rows the launch touches -- the range guard of
  * GIMS_ATTN_F16, filled by GIMS_ATTN_F16 and GIMS_ATTN_X3 launches only (bf16 operands have f32's range).  ACCUMULATED with integer atomics (zero it first; order-independent).
- * The "largest row maximum" of a head is COMPLETE for every kernel (round 6): the 8-wave bf16 kernel, whose other figures come from the sample,
+ * The "largest row maximum" of a head is COMPLETE for every kernel: the 8-wave bf16 kernel, whose other figures come from the sample,
  * adds for EVERY query an upper bound of its row maximum whenever that bound reaches 1/2 -- the largest share of the row's mass that fell into
  * one 32-key half tile (problems of at least 512 keys; a workgroup that had to repeat its tiles in the exact pass reports 1) -- so a single
  * sharply peaked row cannot hide behind the sample.
  * The running-maximum kernels (GIMS_ATTN_X3, the 4-wave and split-key bf16 kernels) report every query as a by-product; the
  * 8-wave bf16 kernel tracks no maximum, so for launches it serves a second, small kernel measures 32 evenly spaced queries of
- * every (problem, head) against all keys (a few microseconds).  stat == NULL: exactly gims_attention. */
-int gims_attention_stat(const uint16_t* qkv, int64_t ld, int32_t q_col, int32_t k_col, int32_t v_col,
-                        const gims_attn_problem* problems /* device */, int32_t n_problems, int32_t max_n_q,
-                        int32_t n_heads, float* out /* may be NULL */, int64_t ld_out,
-                        uint16_t* out_hi /* may be NULL */, uint16_t* out_lo, int64_t ld_split, int32_t flags,
-                        uint64_t* stat /* device, may be NULL */, void* stream);
+ * every (problem, head) against all keys (a few microseconds).
+ * guard: see gims_attn_guard; GIMS_ATTN_X3 launches without a `stat` of their own only. */
+typedef struct gims_attn_args {
+  const uint16_t* qkv; int64_t ld; int32_t q_col, k_col, v_col;
+  const gims_attn_problem* problems /* device */; int32_t n_problems, max_n_q, n_heads;
+  float* out /* may be NULL */; int64_t ld_out; uint16_t* out_hi /* may be NULL */; uint16_t* out_lo; int64_t ld_split;
+  int32_t flags;                       /* GIMS_ATTN_* */
+  uint64_t* stat;                      /* the peakedness accumulator, or NULL */
+  gims_attn_guard guard;               /* no-op unless the guard fires; zero = always run */
+} gims_attn_args;
+int gims_attention(const gims_attn_args* args, void* stream);
 
 /* Which kernel served the attention launches of this process so far (host-side counters, one per kernel family; thread-safe):
  * counts[k] for k < min(n, GIMS_ATTN_KERNEL_KINDS), the rest zero; reset != 0 clears them afterwards.  The launcher picks a kernel
@@ -214,26 +212,15 @@ int gims_attention_stat(const uint16_t* qkv, int64_t ld, int32_t q_col, int32_t 
 #define GIMS_ATTN_KERNEL_KINDS 6
 int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t reset);
 
-/* gims_attention_stat with its arguments in a struct, plus the guard (see gims_attn_guard): what an op of gims_run_ops executes. */
-struct gims_attn_args;
-int gims_attention_ex(const struct gims_attn_args* args, void* stream);
-
 /* ------------------------------------------------------------------------------------------------
  * A recorded sequence of launches replayed by ONE call: the 18 layers of AttentionalGNN.forward (gmatcher.py:127-143) are
  * 72 launches whose arguments only change when the batch geometry does, and a caller in an interpreted language pays for
  * every crossing of the ABI.  ops: HOST array; each op is exactly one gims_linear, gims_attention or (GIMS_OP_AUX) small-kernel call, in order, on
  * `stream`.  Stops at (and returns) the first error.
  */
-typedef struct gims_attn_args {
-  const uint16_t* qkv; int64_t ld; int32_t q_col, k_col, v_col;
-  const gims_attn_problem* problems; int32_t n_problems, max_n_q, n_heads;
-  float* out; int64_t ld_out; uint16_t* out_hi; uint16_t* out_lo; int64_t ld_split; int32_t flags;
-  uint64_t* stat;                      /* gims_attention_stat's peakedness accumulator, or NULL */
-  gims_attn_guard guard;               /* GIMS_ATTN_X3 launches only: no-op unless the guard fires; zero = always run */
-} gims_attn_args;
 #define GIMS_OP_LINEAR 0
 #define GIMS_OP_ATTENTION 1
-/* GIMS_OP_AUX (round 6): the small kernels of the encoder stage in front of the layers (GraphSAGE, gmatcher.py:145-162, 268-269; keypoint encoder,
+/* GIMS_OP_AUX: the small kernels of the encoder stage in front of the layers (GraphSAGE, gmatcher.py:145-162, 268-269; keypoint encoder,
  * gmatcher.py:87-97, 270-271), so that that stage replays from a table like the layers do -- between the one host synchronisation of a batch and
  * the layers the device waits for the host, and a dozen calls across the ABI were most of that wait.  fn selects the entry point, p / i are its
  * pointer and integer arguments in declaration order:
@@ -244,8 +231,7 @@ typedef struct gims_attn_args {
  *   GIMS_AUX_SAGE_MEAN          gims_sage_mean          p = {h, indptr, indices, out}               i = {ldh, n, c, ldo}
  *   GIMS_AUX_KENC_FIRST_LINEAR  gims_kenc_first_linear  p, i as GIMS_AUX_KENC_FIRST
  *   GIMS_AUX_LAYERNORM_ACT      gims_layernorm_act      p = {x, a2, b2, out, out_hi, out_lo}        i = {ldx, rows, c, act, ldo, ld_split}  f = {eps}
- * f holds the floating-point arguments in declaration order (eps is a float in the entry point and travels as one: no conversion on the way).
- * The struct grew from i[4] to i[6] + f[2] inside the union, whose size gims_linear_args sets: sizeof(gims_op) and every earlier offset are unchanged. */
+ * f holds the floating-point arguments in declaration order (eps is a float in the entry point and travels as one: no conversion on the way). */
 #define GIMS_OP_AUX 2
 #define GIMS_AUX_SPLIT_SPL32 0
 #define GIMS_AUX_SAGE_MEAN_SPLIT 1
@@ -262,7 +248,6 @@ int gims_run_ops(const gims_op* ops /* HOST */, int32_t n_ops, void* stream);
  * stream the kernels run on.  (Instrumentation of this build; the reference prints wall-clock stage times, gmatcher.py:226-243.) */
 int gims_run_ops_timed(const gims_op* ops /* HOST */, int32_t n_ops, void* stream, void* const* events /* HOST, n_ops + 1 */);
 int gims_events_create(int32_t n, void** events_out /* HOST array of n handles */);
-int gims_events_record(void* event, void* stream);
 int gims_events_elapsed(void* const* events /* HOST */, int32_t n, float* h_ms_out /* HOST, n - 1 */);
 int gims_events_destroy(void* const* events /* HOST */, int32_t n);
 /* The same sequence as a HIP graph: gims_ops_graph_create captures the launches of `ops` on `stream` (nothing executes),
@@ -331,13 +316,13 @@ int gims_gather_rows(const float* src, int64_t lds, const int32_t* idx, int32_t 
  * (first n_kept entries: sorted original ids), indptr[n+1] (first n_kept+1 valid), indices[max_edges_dir]
  * in kept-relabelled ids, info[8] = {n_kept, n_dir_edges, n_coarse_edges, n_iso_added,
  * n_components_after_removal, n_link_added, threshold bits (f32), flags: bit 0 = an edge / candidate buffer overflowed (repeat with a larger
- * max_edges_dir), bit 1 = see gims_agc_build_ex}.
- * `work` is scratch of at least gims_agc_workspace_bytes(images, n_images) bytes.
+ * max_edges_dir), bit 1 = the percentile window did not hold, see below}.
+ * `work` is scratch of at least gims_agc_workspace_bytes(images, n_images, flags) bytes.
  * LIMIT: 2 <= n <= gims_agc_max_keypoints() = 32768 keypoints per image (GIMS_EINVAL above it; the reference -- NumPy / SciPy -- has no
  * limit and publishes runs with up to 21 163 kept keypoints, tools/files/rgbd1/record.txt:635).  What bounds it: a pair of node ids is one
  * packed 32-bit word (i << 16 | j), the sequential isolated-node walk keeps its ordered list in LDS (135 KB of 160 KB at 32768), and the
  * workspace reserves one word per pair of the strict upper triangle (n^2 * 2 bytes: 0.9 GB per image at 21 163, 2.1 GB at 32768) -- and
- * the ROBUST flow as much again for the half similarity matrix it stores (gims_agc_workspace_bytes_ex: 1.8 GB / 4.3 GB).  Images
+ * the ROBUST flow as much again for the half similarity matrix it stores (gims_agc_workspace_bytes with GIMS_AGC_ROBUST: 1.8 GB / 4.3 GB).  Images
  * above 16384 keypoints run the component search in global memory instead of LDS (same labels).
  * Exact-distance ties in the two sequential fix-ups resolve to the lowest node index.
  * Asynchronous; read info[] after synchronising the stream.
@@ -347,15 +332,7 @@ typedef struct gims_agc_image {
   int32_t* kept; int32_t* indptr; int32_t* indices; int32_t max_edges_dir; int32_t* info;
 } gims_agc_image;
 
-size_t gims_agc_workspace_bytes(const gims_agc_image* h_images /* HOST array */, int32_t n_images);   /* enough for either flow of gims_agc_build_ex */
-/* Scratch bytes of gims_agc_build_ex(..., flags, ...): the default (window) flow never stores the N x N half similarity matrix, which is half of
- * the robust flow's workspace -- a batch of README-size images (15 k keypoints) asks for 0.5 GB per image instead of 0.9.  A call whose
- * images force the robust flow (d % 64 != 0 or d > 256; GIMS_AGC_ROBUST=1 in the environment) is sized for it whatever the flags say. */
-size_t gims_agc_workspace_bytes_ex(const gims_agc_image* h_images /* HOST array */, int32_t n_images, int32_t flags);
-int32_t gims_agc_max_keypoints(void);
-int gims_agc_build(const gims_agc_image* h_images /* HOST array */, int32_t n_images, double radius, double percentile,
-                   int32_t min_size, void* work, size_t work_bytes, void* stream);
-/* The same with flags.  The percentile threshold is exact in both flows (the k-th smallest of the similarities as the library evaluates
+/* flags of the two calls below.  The percentile threshold is exact in both flows (the k-th smallest of the similarities as the library evaluates
  * them: float64 dot products of the normalised f32 rows, rounded once); they differ in how the entries that can decide it are found.
  * Default: a sample of one-pass half-precision similarities predicts a window of values that holds rank k, one pass over all N^2/2 of
  * them counts what lies below the window and lists what lies inside it, and only the listed entries (and the radius candidates) are
@@ -364,14 +341,17 @@ int gims_agc_build(const gims_agc_image* h_images /* HOST array */, int32_t n_im
  * GIMS_AGC_ROBUST, which histograms every entry instead of predicting (about 0.2 ms more per 16 images of 4096).  Images of at most 1536
  * keypoints are "sampled" in full and never report bit 1. */
 #define GIMS_AGC_ROBUST 1
-int gims_agc_build_ex(const gims_agc_image* h_images /* HOST array */, int32_t n_images, double radius, double percentile,
-                      int32_t min_size, int32_t flags, void* work, size_t work_bytes, void* stream);
-/* The same with each image's own (radius, percentile, min_size): h_params[i] belongs to h_images[i].  Still one launch per stage for the
- * whole batch; same workspace functions, info[8], flags and flows.  The two entries above are this one with one triple replicated.
- * `reserved` is not read (keep it 0). */
+/* Scratch bytes of gims_agc_build(..., flags, ...): the default (window) flow never stores the N x N half similarity matrix, which is half of
+ * the robust flow's workspace -- a batch of README-size images (15 k keypoints) asks for 0.5 GB per image instead of 0.9.  A call whose
+ * images force the robust flow (d % 64 != 0 or d > 256; GIMS_AGC_ROBUST=1 in the environment) is sized for it whatever the flags say.
+ * flags = GIMS_AGC_ROBUST is enough for either flow. */
+size_t gims_agc_workspace_bytes(const gims_agc_image* h_images /* HOST array */, int32_t n_images, int32_t flags);
+int32_t gims_agc_max_keypoints(void);
+/* The graph parameters: n_params == 1, one (radius, percentile, min_size) for the whole batch, or n_params == n_images, h_params[i] belongs
+ * to h_images[i] (still one launch per stage for the whole batch); any other n_params is GIMS_EINVAL.  `reserved` is not read (keep it 0). */
 typedef struct gims_agc_params { double radius, percentile; int32_t min_size, reserved; } gims_agc_params;
-int gims_agc_build_v(const gims_agc_image* h_images /* HOST array */, int32_t n_images, const gims_agc_params* h_params /* HOST [n_images] */,
-                     int32_t flags, void* work, size_t work_bytes, void* stream);
+int gims_agc_build(const gims_agc_image* h_images /* HOST array */, int32_t n_images, const gims_agc_params* h_params /* HOST [n_params] */,
+                   int32_t n_params, int32_t flags, void* work, size_t work_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Delaunay graph construction for a BATCH of images (D-GIMS: the reference's build_graph_from_keypoints_Delaunay, models/agc.py:718-751,
@@ -444,10 +424,9 @@ int gims_pack_graphs(const gims_pack_image* dev_images /* DEVICE array */, int32
  *                no HBM traffic inside the loop.  Used when the matrices fit on chip (n, m <= 4096, about 134 MB of
  *                matrix per launch) and are large enough to pay (>= 6 M entries); GIMS_OT_RESIDENT=0 / 2 in the
  *                environment forces streamed / resident.  gims_sinkhorn_plan() tells which one a call will take.
- *                Two on-chip kernels exist: the 2-D decomposition of csrc/sinkhorn2d.hip (default: a problem is cut into row
+ *                The on-chip kernel is the 2-D decomposition of csrc/sinkhorn2d.hip (a problem is cut into row
  *                groups, one per XCD, times 128-column blocks, one per CU; the row-sum exchange stays inside the XCD's L2, only
- *                a 0.5-KB column edge crosses XCDs; start potentials formed in the kernel) and the 1-D row-slab kernel of
- *                csrc/sinkhorn.hip (GIMS_OT_RES2=0; the cross-check).
+ *                a 0.5-KB column edge crosses XCDs; start potentials formed in the kernel).
  */
 typedef struct gims_ot_problem {
   const float* scores; int64_t ld; int32_t n, m;
@@ -456,18 +435,15 @@ typedef struct gims_ot_problem {
 } gims_ot_problem;
 
 size_t gims_sinkhorn_workspace_bytes(const gims_ot_problem* h_problems, int32_t n_problems);
-/* 0: the call will run streamed; k > 0: resident, in k launches.  (Query only; no reference counterpart.) */
-int gims_sinkhorn_plan(const gims_ot_problem* h_problems, int32_t n_problems, int32_t iters);
-int gims_sinkhorn_match(const gims_ot_problem* h_problems /* HOST array */, int32_t n_problems, float alpha,
-                        int32_t iters, float match_threshold, void* work, size_t work_bytes, void* stream);
-/* The same two calls with flags.  GIMS_OT_STREAMED: never take an on-chip kernel -- they occupy every CU of the device for the
+/* flags of the two calls below.  GIMS_OT_STREAMED: never take an on-chip kernel -- they occupy every CU of the device for the
  * whole solve and wait on each other across workgroups, so a caller that runs several streams (or processes) on one GPU
  * concurrently must use the streamed kernels: next to another stream's kernels an on-chip solve cannot get its 256 workgroups
  * resident, gives up and is re-solved by the slow rescue path. */
 #define GIMS_OT_STREAMED 1
-int gims_sinkhorn_plan_ex(const gims_ot_problem* h_problems, int32_t n_problems, int32_t iters, int32_t flags);
-int gims_sinkhorn_match_ex(const gims_ot_problem* h_problems /* HOST array */, int32_t n_problems, float alpha,
-                           int32_t iters, float match_threshold, void* work, size_t work_bytes, int32_t flags, void* stream);
+/* 0: the call will run streamed; k > 0: resident, in k launches.  (Query only; no reference counterpart.) */
+int gims_sinkhorn_plan(const gims_ot_problem* h_problems, int32_t n_problems, int32_t iters, int32_t flags);
+int gims_sinkhorn_match(const gims_ot_problem* h_problems /* HOST array */, int32_t n_problems, float alpha,
+                        int32_t iters, float match_threshold, void* work, size_t work_bytes, int32_t flags, void* stream);
 
 /* Diagnostics: how many on-chip solves gave up and were re-solved by a rescue path on the CURRENT device since the process started
  * (synchronises the device; -1 on error).  A given-up solve is re-solved inside the same call -- by the streamed kernels when a
@@ -615,7 +591,6 @@ int gims_train_loss_grad(const gims_loss_pair* dev_pairs, int32_t n_pairs, const
  *   gims_ch_dwconv3:   depthwise 3x3 (pad 1) with wt [9][c], bias [c] (BatchNorm folded), optional ReLU6, optional
  *                      y += res_scale * res                                                            (172-180, 207, 220-233)
  *   gims_ch_l2norm:    y = x / sqrt(sum_c x^2 + eps) per row                                           (desc_l2norm, 9-21)
- *   gims_ch_relu6:     in-place clamp to [0, 6]
  */
 int gims_ch_frn_stats(const float* x, int64_t patches, int32_t hw, int32_t c, const float* weight, float eps, float* scale, void* stream);
 int gims_ch_pool_hw(const float* x, int64_t patches, int32_t h, int32_t w, int32_t c, const float* s, const float* b, float* ph, float* pw,
@@ -667,7 +642,6 @@ int gims_ch_conv_block_first(const float* patches, int64_t n, const float* frn0_
                              const uint16_t* w_packed, const float* bias, const float* frn_weight, const float* frn_bias, float eps,
                              const float* const* gate_w, const float* tau, float* y, uint16_t* y_split, int64_t ld_split, void* stream);
 int gims_ch_l2norm(const float* x, int64_t rows, int32_t c, float eps, float* y, void* stream);
-int gims_ch_relu6(float* x, int64_t total, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Patch extraction: the front-end stage between keypoint detection and CAR-HyNet,
@@ -871,9 +845,8 @@ int gims_sift_compact(const int64_t* perm, int64_t n, int32_t n_images, int32_t 
                       void* stream);
 
 /* ---- Training data from images (gims_amd/csrc/warp.hip, eval.hip): the reference's COCO_loader / train.py data path.
- * gims_warp_invert (host only): cv::invert(M, DECOMP_LU) of n row-major float64 3x3 matrices (determinant / cofactor path; singular -> 0).
  * gims_warp_perspective: cv2.warpPerspective(src, M, (dw, dh)), INTER_LINEAR, BORDER_CONSTANT 0, for uint8 [n][sh][sw][c] -> [n][dh][dw][c],
- *   c = 1 or 3; m: HOST float64 [n][9] forward matrices (inverted here like the line above); work: device, >= 72 * n bytes, 16-aligned.
+ *   c = 1 or 3; m: HOST float64 [n][9] forward matrices (inverted here like cv::invert(M, DECOMP_LU): determinant / cofactor path; singular -> 0); work: device, >= 72 * n bytes, 16-aligned.
  * gims_resize: cv2.resize(src, (dw, dh), interpolation) for GIMS_INTER_LINEAR / GIMS_INTER_AREA, same layout (OpenCV's path choice:
  *   copy, area-fast, general area, linear with area-mode coefficients).
  * gims_train_labels: torch_find_matches(kpts0, kpts1, H, dist_thresh, n_iters) for n_pairs pairs and the match_indexes rows of
@@ -883,7 +856,6 @@ int gims_sift_compact(const int64_t* perm, int64_t n, int32_t n_images, int32_t 
 #define GIMS_INTER_LINEAR 1
 #define GIMS_INTER_AREA 3
 typedef struct gims_label_pair { const float* kpts0; const float* kpts1; int32_t n0, n1; } gims_label_pair;
-int gims_warp_invert(const double* m /* HOST */, int32_t n, double* minv /* HOST */);
 int gims_warp_perspective(const uint8_t* src, int32_t n, int32_t sh, int32_t sw, int32_t c, const double* m /* HOST */, uint8_t* dst, int32_t dh,
                           int32_t dw, double* work, void* stream);
 int gims_resize(const uint8_t* src, int32_t n, int32_t sh, int32_t sw, int32_t c, uint8_t* dst, int32_t dh, int32_t dw, int32_t interpolation,

@@ -517,7 +517,7 @@ def test_guarded_launches_that_walk_their_tiles(hip, monkeypatch, fires):
 @pytest.mark.parametrize("kernel", ["4wave", "4wave2", "8", "split", "split4", "x3", "x3w2", "4wave2_f16", "8_f16", "split_f16"])
 @pytest.mark.parametrize("sharp", [1.0, 4.0])
 def test_attention_peak_statistic(hip, monkeypatch, kernel, sharp):
-    """gims_attention_stat: per head, sum / count / maximum of the softmax row maxima (2^-24 fixed point), what
+    """gims_attention with a stat accumulator: per head, sum / count / maximum of the softmax row maxima (2^-24 fixed point), what
     attention_precision='auto' decides from -- against the float64 softmax of the same bf16 operands.  The running-maximum
     kernels report every query; launches served by the 8-wave kernel are measured by the sampling kernel (32 evenly spaced
     queries of every (problem, head) against all keys)."""
@@ -1289,7 +1289,7 @@ def test_agc_window_at_the_ends_of_the_distribution(hip, monkeypatch, pct):
 @pytest.mark.parametrize("n", [700, 4100])
 def test_agc_missed_window_is_reported(hip, monkeypatch, n):
     """The default graph build PREDICTS the window of approximate similarities that holds the percentile threshold and verifies the prediction on
-    the device (gims_agc_build_ex).  GIMS_AGC_WINDOW_SHIFT moves the predicted window away from the threshold: the build must say so (bit 1 of
+    the device (gims_agc_build).  GIMS_AGC_WINDOW_SHIFT moves the predicted window away from the threshold: the build must say so (bit 1 of
     info[7]) -- for a sampled image (4100 rows: every 8th row) and for one that is histogrammed in full (700) -- and the robust repeat, which
     is what gims_amd.GMatcher does on that bit, gives what the undisturbed default flow gives."""
     r = _rng(29)

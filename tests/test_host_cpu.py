@@ -21,11 +21,20 @@ def test_library_exports_every_declared_symbol():
     declared = set(re.findall(r"\b(gims_[a-z0-9_]+)\s*\(", hdr))
     assert len(declared) >= 20
     assert declared == set(hip.EXPORTS), declared ^ set(hip.EXPORTS)
-    assert len(hip.EXPORTS) == 110 and len(hip.ABI.structs) == 28          # at this commit: a parser that drops a declaration fails here
+    assert len(hip.EXPORTS) == 98 and len(hip.ABI.structs) == 28          # at this commit: a parser that drops a declaration fails here
     lib = ctypes.CDLL(hip.LIB_PATH)
     for name in declared:
         assert hasattr(lib, name), name
-    assert hip.load().gims_abi_version() == hip.ABI_VERSION == 2
+    assert hip.load().gims_abi_version() == hip.ABI_VERSION == 3
+
+
+def test_library_defines_no_entry_point_the_header_does_not_declare():
+    """The unmangled dynamic symbols of the library that start with gims_ are exactly the header's prototypes: an entry point left behind
+    without a declaration (a forwarder, an old spelling) fails here."""
+    import subprocess
+    nm = subprocess.run(["nm", "-D", "--defined-only", hip.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    defined = {line.split()[-1] for line in nm.splitlines() if line.split() and line.split()[-1].startswith("gims_")}
+    assert defined == set(hip.ABI.signatures), defined ^ set(hip.ABI.signatures)
 
 
 def _gcc(tmp_path, code, run=True):
@@ -77,7 +86,7 @@ def test_optimizer_table_layouts_match_header(tmp_path):
         assert d.itemsize == ctypes.sizeof(py) and list(d.names) == [f[0] for f in py._fields_]
         assert [d.fields[n][1] for n in d.names] == [getattr(py, n).offset for n in d.names]
     assert ctypes.sizeof(hip.SgdTensor) == 40 and ctypes.sizeof(hip.SgdGroup) == 40 and ctypes.sizeof(hip.EmaTensor) == 24
-    assert hip.load().gims_abi_version() == 2
+    assert hip.load().gims_abi_version() == 3
 
 
 def test_prototypes_and_scalar_types_match_the_compiler(tmp_path):
@@ -261,6 +270,19 @@ def test_training_entry_points_validate_arguments_without_a_gpu():
     assert lib.gims_head_pack(None, None, None, None, None, None, 256, 4, 0, None) == -1
     assert lib.gims_permute3(None, None, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, None) == -1
     assert lib.gims_sinkhorn_history_floats(10, 12, 5) == 6 * 24
+
+
+def test_agc_build_takes_one_parameter_triple_or_one_per_image():
+    """gims_agc_build refuses an n_params that is neither 1 nor n_images, and a null h_params, with GIMS_EINVAL and a message that names
+    n_params -- before any HIP call (fake pointers, never dereferenced)."""
+    import ctypes as C
+    lib = hip.load()
+    images = (hip.AgcImage * 5)(*[hip.AgcImage(0x10000, 0x20000, 256, n, 256, 0x30000, 0x40000, 0x50000, 64 * n, 0x60000) for n in (100, 200, 300, 400, 500)])
+    params = (hip.AgcParams * 6)(*[hip.AgcParams(15.0, 2.0, 7, 0)] * 6)
+    need = lib.gims_agc_workspace_bytes(images, 5, hip.AGC_ROBUST)
+    for h_params, n_params in ((params, 0), (params, 2), (params, 6), (None, 5), (None, 1)):
+        assert lib.gims_agc_build(images, 5, h_params, n_params, 0, 0x100000, need, None) == hip.GIMS_EINVAL
+        assert b"gims_agc_build" in lib.gims_last_error() and b"n_params" in lib.gims_last_error()
 
 
 def test_adam_table_layout_and_cpu_refusal():

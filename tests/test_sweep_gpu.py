@@ -1,4 +1,4 @@
-"""Per-image graph parameters on the GPU: gims_agc_build_v against the reference's graphs with every image's own triple, the scalar entry
+"""Per-image graph parameters on the GPU: gims_agc_build with n_params == n_images against the reference's graphs with every image's own triple, the scalar entry
 points against it bit for bit, match_pairs(per_pair_graph=True) on a batch of mixed settings and graph kinds, and GMatcher.sweep over the
 stored grids of tests/golden/sweep_* (tools/gen_golden_sweep.py), against forward() per setting, and across sub-batch sizes."""
 import math

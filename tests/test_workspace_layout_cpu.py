@@ -79,8 +79,8 @@ def queries(lib):
         out["sinkhorn/each"] = [int(lib.gims_sinkhorn_workspace_bytes(fake_ot([s]), 1)) for s in SHAPES]
     out["sinkhorn_backward"] = int(lib.gims_sinkhorn_backward_workspace_bytes(fake_ot(SHAPES), k))
     with _env(GIMS_AGC_ROBUST="0"):
-        out["agc/window"] = int(lib.gims_agc_workspace_bytes_ex(fake_images(GRAPH_N), len(GRAPH_N), 0))
-        out["agc/robust"] = int(lib.gims_agc_workspace_bytes_ex(fake_images(GRAPH_N), len(GRAPH_N), hip.AGC_ROBUST))
+        out["agc/window"] = int(lib.gims_agc_workspace_bytes(fake_images(GRAPH_N), len(GRAPH_N), 0))
+        out["agc/robust"] = int(lib.gims_agc_workspace_bytes(fake_images(GRAPH_N), len(GRAPH_N), hip.AGC_ROBUST))
     out["delaunay"] = int(lib.gims_delaunay_workspace_bytes(fake_images(GRAPH_N), len(GRAPH_N)))
     for name, mutual, flags in (("plain", 0, 0), ("mutual", 1, 0), ("exhaustive", 0, hip.NN_EXHAUSTIVE), ("mutual+exhaustive", 1, hip.NN_EXHAUSTIVE)):
         out[f"nn/{name}"] = int(lib.gims_nn_workspace_bytes(fake_nn(NN_SHAPES, mutual), len(NN_SHAPES), flags))
@@ -112,7 +112,7 @@ def _short_labels(lib, short):
 def _short_match(lib, short):
     arr = fake_ot(SHAPES)
     need = int(lib.gims_sinkhorn_workspace_bytes(arr, len(SHAPES)))
-    return need, lib.gims_sinkhorn_match(arr, len(SHAPES), 1.0, 10, 0.2, WORK, need - short, None)
+    return need, lib.gims_sinkhorn_match(arr, len(SHAPES), 1.0, 10, 0.2, WORK, need - short, 0, None)
 
 
 def _short_history(lib, short):
@@ -132,8 +132,8 @@ def _short_backward(lib, short):
 def _short_agc(lib, short):
     arr = fake_images(GRAPH_N)
     params = (hip.AgcParams * len(GRAPH_N))(*[hip.AgcParams(15.0, 2.0, 7, 0)] * len(GRAPH_N))
-    need = int(lib.gims_agc_workspace_bytes_ex(arr, len(GRAPH_N), 0))
-    return need, lib.gims_agc_build_v(arr, len(GRAPH_N), params, 0, WORK, need - short, None)
+    need = int(lib.gims_agc_workspace_bytes(arr, len(GRAPH_N), 0))
+    return need, lib.gims_agc_build(arr, len(GRAPH_N), params, len(GRAPH_N), 0, WORK, need - short, None)
 
 
 def _short_delaunay(lib, short):
@@ -147,7 +147,7 @@ def _short_delaunay(lib, short):
     (_short_history, "gims_sinkhorn_history"), (_short_backward, "gims_sinkhorn_backward"), (_short_agc, "gims_agc_build"),
     (_short_delaunay, "gims_delaunay_build")])
 def test_a_workspace_one_byte_short_is_refused_before_any_device_call(call, name):
-    """(gims_agc_build_v reports under the name its callers always saw: gims_agc_build.)  The message carries both byte counts."""
+    """The message carries both byte counts."""
     lib = hip.load()
     with _env(GIMS_OT_RESIDENT="0", GIMS_AGC_ROBUST="0"):
         need, rc = call(lib, 1)

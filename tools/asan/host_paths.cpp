@@ -35,64 +35,65 @@ int main() {
   }
   EXPECT(gims_sinkhorn_workspace_bytes(pr.data(), (int)pr.size()) > 0);
   EXPECT(gims_sinkhorn_workspace_bytes(nullptr, 3) == 0);
-  EXPECT(gims_sinkhorn_plan(pr.data(), (int)pr.size(), 100) >= 0);
+  EXPECT(gims_sinkhorn_plan(pr.data(), (int)pr.size(), 100, 0) >= 0);
   for (int n : {1, 31, 1024, 4096, 5000, 16384}) {
     gims_ot_problem q; memset(&q, 0, sizeof(q)); q.n = n; q.m = n; q.ld = (n + 3) / 4 * 4;
     EXPECT(gims_sinkhorn_workspace_bytes(&q, 1) > 0);
-    EXPECT(gims_sinkhorn_plan(&q, 1, 100) >= 0);
+    EXPECT(gims_sinkhorn_plan(&q, 1, 100, 0) >= 0);
   }
-  EXPECT(gims_sinkhorn_match(nullptr, 1, 1.f, 10, 0.2f, nullptr, 0, nullptr) == GIMS_EINVAL);
-  EXPECT(gims_sinkhorn_match(pr.data(), (int)pr.size(), 1.f, -1, 0.2f, (void*)0x1000, 1 << 20, nullptr) == GIMS_EINVAL);
+  EXPECT(gims_sinkhorn_match(nullptr, 1, 1.f, 10, 0.2f, nullptr, 0, 0, nullptr) == GIMS_EINVAL);
+  EXPECT(gims_sinkhorn_match(pr.data(), (int)pr.size(), 1.f, -1, 0.2f, (void*)0x1000, 1 << 20, 0, nullptr) == GIMS_EINVAL);
   EXPECT(strlen(gims_last_error()) > 0);
   // ---- adaptive graph: workspace arithmetic, validation
   std::vector<gims_agc_image> im(5);
   for (size_t i = 0; i < im.size(); ++i) { memset(&im[i], 0, sizeof(im[i])); im[i].n = 100 + 900 * (int)i; im[i].d = 256; im[i].ldd = 256; im[i].max_edges_dir = 64 * im[i].n; }
-  EXPECT(gims_agc_workspace_bytes(im.data(), (int)im.size()) > 0);
-  EXPECT(gims_agc_build(nullptr, 0, 15.0, 2.0, 7, nullptr, 0, nullptr) != GIMS_OK);
-  {   // rounds 4-5: gims_agc_build_ex (flags), the keypoint limit by name, workspace arithmetic at the largest published size and at the limit
+  EXPECT(gims_agc_workspace_bytes(im.data(), (int)im.size(), GIMS_AGC_ROBUST) > 0);
+  const gims_agc_params one = {15.0, 2.0, 7, 0};
+  EXPECT(gims_agc_build(nullptr, 0, &one, 1, 0, nullptr, 0, nullptr) != GIMS_OK);
+  {   // flags, the keypoint limit by name, workspace arithmetic at the largest published size and at the limit
     EXPECT(gims_agc_max_keypoints() == 32768);
-    EXPECT(gims_agc_build_ex(nullptr, 0, 15.0, 2.0, 7, GIMS_AGC_ROBUST, nullptr, 0, nullptr) != GIMS_OK);
+    EXPECT(gims_agc_build(nullptr, 0, &one, 1, GIMS_AGC_ROBUST, nullptr, 0, nullptr) != GIMS_OK);
     gims_agc_image big; memset(&big, 0, sizeof(big));
     big.d = 256; big.ldd = 256;
     for (int n : {2, 16384, 16385, 21163, 32768}) {
       big.n = n; big.max_edges_dir = 64 * n;
-      const size_t wb = gims_agc_workspace_bytes(&big, 1);
+      const size_t wb = gims_agc_workspace_bytes(&big, 1, GIMS_AGC_ROBUST);
       EXPECT(wb > (size_t)n * (size_t)(n - 1) * 2);                                   // one word per pair of the strict upper triangle is in there
     }
     big.n = 32769; big.max_edges_dir = 64;                                             // over the limit: refused with the limit in the message
     big.kpts = (const float*)0x1000; big.desc = (const float*)0x2000; big.kept = (int32_t*)0x3000; big.indptr = (int32_t*)0x4000;
     big.indices = (int32_t*)0x5000; big.info = (int32_t*)0x6000;
-    EXPECT(gims_agc_build_ex(&big, 1, 15.0, 2.0, 7, 0, (void*)0x7000, (size_t)1 << 40, nullptr) == GIMS_EINVAL);
+    EXPECT(gims_agc_build(&big, 1, &one, 1, 0, (void*)0x7000, (size_t)1 << 40, nullptr) == GIMS_EINVAL);
     EXPECT(strstr(gims_last_error(), "32768") != nullptr);
     big.n = 100; big.d = 48;                                                           // descriptor width not a multiple of 32
-    EXPECT(gims_agc_build_ex(&big, 1, 15.0, 2.0, 7, 0, (void*)0x7000, (size_t)1 << 40, nullptr) == GIMS_EINVAL);
+    EXPECT(gims_agc_build(&big, 1, &one, 1, 0, (void*)0x7000, (size_t)1 << 40, nullptr) == GIMS_EINVAL);
     big.d = 256;                                                                       // a workspace that is too small
-    EXPECT(gims_agc_build_ex(&big, 1, 15.0, 2.0, 7, GIMS_AGC_ROBUST, (void*)0x7000, 64, nullptr) == GIMS_EINVAL);
-    // round 6: per-flow workspace sizes -- the default flow does not hold the half N x N matrix; a descriptor width that forces the robust flow
+    EXPECT(gims_agc_build(&big, 1, &one, 1, GIMS_AGC_ROBUST, (void*)0x7000, 64, nullptr) == GIMS_EINVAL);
+    // per-flow workspace sizes -- the default flow does not hold the half N x N matrix; a descriptor width that forces the robust flow
     // is sized for it whatever the flags say; a workspace sized for the default flow is refused by a robust build
     for (int n : {1000, 21163}) {
       big.n = n; big.d = 256; big.max_edges_dir = 64 * n;
-      const size_t w0 = gims_agc_workspace_bytes_ex(&big, 1, 0), w1 = gims_agc_workspace_bytes_ex(&big, 1, GIMS_AGC_ROBUST);
-      EXPECT(w1 == gims_agc_workspace_bytes(&big, 1) && w1 >= w0 + (size_t)n * (size_t)n * 2 && w0 > (size_t)n * (size_t)(n - 1) * 2);
+      const size_t w0 = gims_agc_workspace_bytes(&big, 1, 0), w1 = gims_agc_workspace_bytes(&big, 1, GIMS_AGC_ROBUST);
+      EXPECT(w1 >= w0 + (size_t)n * (size_t)n * 2 && w0 > (size_t)n * (size_t)(n - 1) * 2);      // the flags argument decides the half N x N matrix
     }
     big.n = 1000; big.d = 96; big.max_edges_dir = 64000;
-    EXPECT(gims_agc_workspace_bytes_ex(&big, 1, 0) == gims_agc_workspace_bytes_ex(&big, 1, GIMS_AGC_ROBUST));
+    EXPECT(gims_agc_workspace_bytes(&big, 1, 0) == gims_agc_workspace_bytes(&big, 1, GIMS_AGC_ROBUST));
     big.d = 256;
-    EXPECT(gims_agc_build_ex(&big, 1, 15.0, 2.0, 7, GIMS_AGC_ROBUST, (void*)0x7000, gims_agc_workspace_bytes_ex(&big, 1, 0), nullptr) == GIMS_EINVAL);
-    EXPECT(gims_agc_workspace_bytes_ex(nullptr, 0, 0) == 0);
+    EXPECT(gims_agc_build(&big, 1, &one, 1, GIMS_AGC_ROBUST, (void*)0x7000, gims_agc_workspace_bytes(&big, 1, 0), nullptr) == GIMS_EINVAL);
+    EXPECT(gims_agc_workspace_bytes(nullptr, 0, 0) == 0);
   }
-  {   // round 5: guarded launches (gims_attn_guard) -- validation only
+  {   // guarded launches (gims_attn_guard) -- validation only
     gims_attn_args aa; memset(&aa, 0, sizeof(aa));
-    EXPECT(gims_attention_ex(nullptr, nullptr) == GIMS_EINVAL);
-    EXPECT(gims_attention_ex(&aa, nullptr) == GIMS_EINVAL);
+    EXPECT(gims_attention(nullptr, nullptr) == GIMS_EINVAL);
+    EXPECT(gims_attention(&aa, nullptr) == GIMS_EINVAL);
     aa.qkv = (const uint16_t*)0x1000; aa.ld = 1536; aa.k_col = 256; aa.v_col = 512; aa.problems = (const gims_attn_problem*)0x2000; aa.n_problems = 1;
     aa.max_n_q = 64; aa.n_heads = 4; aa.out = (float*)0x3000; aa.ld_out = 256;
     aa.guard.stat = (uint64_t*)0x4000; aa.guard.kind = GIMS_GUARD_PEAKED; aa.guard.n_heads = 4;
-    EXPECT(gims_attention_ex(&aa, nullptr) == GIMS_EINVAL);                            // a guard without GIMS_ATTN_X3
+    EXPECT(gims_attention(&aa, nullptr) == GIMS_EINVAL);                            // a guard without GIMS_ATTN_X3
     aa.flags = GIMS_ATTN_X3; aa.guard.kind = 7;
-    EXPECT(gims_attention_ex(&aa, nullptr) == GIMS_EINVAL);                            // unknown guard kind
+    EXPECT(gims_attention(&aa, nullptr) == GIMS_EINVAL);                            // unknown guard kind
     aa.guard.kind = GIMS_GUARD_RANGE; aa.guard.n_heads = 16;
-    EXPECT(gims_attention_ex(&aa, nullptr) == GIMS_EINVAL);                            // more heads than one wave evaluates
+    EXPECT(gims_attention(&aa, nullptr) == GIMS_EINVAL);                            // more heads than one wave evaluates
     gims_linear_args lg; memset(&lg, 0, sizeof(lg));
     lg.a0 = (const float*)0x1000; lg.w = (const void*)0x2000; lg.out_f32 = (float*)0x3000; lg.m = lg.n = lg.k = lg.k0 = 64; lg.lda0 = lg.ldw = lg.ldc = 64;
     lg.guard.stat = (uint64_t*)0x4000; lg.guard.kind = GIMS_GUARD_PEAKED; lg.guard.n_heads = 4;
@@ -165,11 +166,7 @@ int main() {
   EXPECT(gims_linear(&la, nullptr) != GIMS_OK);
   EXPECT(gims_linear(nullptr, nullptr) != GIMS_OK);
   EXPECT(gims_linear_batch(nullptr, 0, 0, 0, GIMS_PREC_F32, nullptr) != GIMS_OK);
-  EXPECT(gims_attention(nullptr, 0, 0, 0, 0, nullptr, 0, 0, 0, nullptr, 0, nullptr, nullptr, 0, 0, nullptr) == GIMS_EINVAL);
-  EXPECT(gims_attention_stat(nullptr, 0, 0, 0, 0, nullptr, 0, 0, 0, nullptr, 0, nullptr, nullptr, 0, 0, nullptr, nullptr) == GIMS_EINVAL);
-  EXPECT(gims_attention_stat((const uint16_t*)0x1000, 768, 0, 256, 512, (const gims_attn_problem*)0x2000, 1, 64, 4, (float*)0x3000, 256, nullptr, nullptr, 0, 0,
-                             (uint64_t*)0x4004, nullptr) == GIMS_EINVAL);      // misaligned statistics accumulator
-  {   // round 6: the launch counters (host-side state only)
+  {   // the launch counters (host-side state only)
     uint64_t cnt[8] = {9, 9, 9, 9, 9, 9, 9, 9};
     EXPECT(gims_attention_launch_counts(cnt, 8, 1) == GIMS_OK && cnt[GIMS_ATTN_KERNEL_KINDS] == 0 && cnt[7] == 0);
     EXPECT(gims_attention_launch_counts(cnt, 3, 0) == GIMS_OK && cnt[0] == 0 && cnt[2] == 0);
@@ -178,12 +175,14 @@ int main() {
     aa.qkv = (const uint16_t*)0x1000; aa.ld = 1536; aa.k_col = 256; aa.v_col = 512; aa.problems = (const gims_attn_problem*)0x2000; aa.n_problems = 1;
     aa.max_n_q = 64; aa.n_heads = 4; aa.out = (float*)0x3000; aa.ld_out = 256; aa.guard.stat = (uint64_t*)0x4000; aa.guard.kind = GIMS_GUARD_PEAKED;
     aa.guard.n_heads = 4; aa.guard.max_thr = 0.5;
-    EXPECT(gims_attention_ex(&aa, nullptr) == GIMS_EINVAL);
+    EXPECT(gims_attention(&aa, nullptr) == GIMS_EINVAL);
+    memset(&aa.guard, 0, sizeof(aa.guard)); aa.ld = 768; aa.stat = (uint64_t*)0x4004;
+    EXPECT(gims_attention(&aa, nullptr) == GIMS_EINVAL && strstr(gims_last_error(), "stat"));      // misaligned statistics accumulator
   }
   EXPECT(gims_patch_affine(nullptr, nullptr, 3, nullptr, nullptr, nullptr) == GIMS_EINVAL);
   EXPECT(gims_patch_affine(nullptr, nullptr, 0, nullptr, nullptr, nullptr) == GIMS_OK);          // nothing to do
-  EXPECT(gims_sinkhorn_plan_ex(pr.data(), (int)pr.size(), 100, GIMS_OT_STREAMED) == 0);           // streamed on request, whatever the sizes
-  EXPECT(gims_sinkhorn_match_ex(nullptr, 0, 1.f, 10, 0.2f, nullptr, 0, GIMS_OT_STREAMED, nullptr) == GIMS_EINVAL);
+  EXPECT(gims_sinkhorn_plan(pr.data(), (int)pr.size(), 100, GIMS_OT_STREAMED) == 0);           // streamed on request, whatever the sizes
+  EXPECT(gims_sinkhorn_match(nullptr, 0, 1.f, 10, 0.2f, nullptr, 0, GIMS_OT_STREAMED, nullptr) == GIMS_EINVAL);
   EXPECT(gims_train_loss(nullptr, 0, nullptr, 0, 1.f, 0.45f, 1.f, nullptr, nullptr, nullptr, nullptr) == GIMS_EINVAL);
   EXPECT(gims_ingest_images(nullptr, 0, 0, 0, nullptr, 0, nullptr, nullptr, nullptr) == GIMS_EINVAL);
   EXPECT(gims_pack_graphs(nullptr, 0, 0, 0, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr) == GIMS_EINVAL);
@@ -294,9 +293,8 @@ int main() {
            strstr(gims_last_error(), "gims_train_labels"));
     for (int np : {1, 5}) {
       EXPECT((need = gims_sinkhorn_workspace_bytes(ot.data(), np)) > 0 && need % 256 == 0);
-      EXPECT(carved(gims_sinkhorn_match(ot.data(), np, 1.f, 10, 0.2f, work, need, nullptr)));
-      EXPECT(carved(gims_sinkhorn_match_ex(ot.data(), np, 1.f, 10, 0.2f, work, need, GIMS_OT_STREAMED, nullptr)));
-      EXPECT(gims_sinkhorn_match(ot.data(), np, 1.f, 10, 0.2f, work, need - 1, nullptr) == GIMS_EINVAL && strstr(gims_last_error(), "gims_sinkhorn_match"));
+      for (int flags : {0, (int)GIMS_OT_STREAMED}) EXPECT(carved(gims_sinkhorn_match(ot.data(), np, 1.f, 10, 0.2f, work, need, flags, nullptr)));
+      EXPECT(gims_sinkhorn_match(ot.data(), np, 1.f, 10, 0.2f, work, need - 1, 0, nullptr) == GIMS_EINVAL && strstr(gims_last_error(), "gims_sinkhorn_match"));
       EXPECT(carved(gims_sinkhorn_history(ot.data(), np, 1.f, 3, hist.data(), work, need, nullptr)));
       EXPECT(gims_sinkhorn_history(ot.data(), np, 1.f, 3, hist.data(), work, need - 1, nullptr) == GIMS_EINVAL && strstr(gims_last_error(), "gims_sinkhorn_history"));
       EXPECT((need = gims_sinkhorn_backward_workspace_bytes(ot.data(), np)) > 0 && need % 256 == 0);
@@ -316,10 +314,12 @@ int main() {
       EXPECT(gims::ot_res2_run(plan, h2.data(), (int)h2.size(), 1.f, 10, 1, work, nullptr) == GIMS_EHIP);
     }
     for (int flags : {0, (int)GIMS_AGC_ROBUST}) {
-      EXPECT((need = gims_agc_workspace_bytes_ex(gi.data(), 5, flags)) > 0 && need % 256 == 0);
-      EXPECT(carved(gims_agc_build_v(gi.data(), 5, gp.data(), flags, work, need, nullptr)));
-      EXPECT(gims_agc_build_v(gi.data(), 5, gp.data(), flags, work, need - 1, nullptr) == GIMS_EINVAL && strstr(gims_last_error(), "gims_agc_build"));
+      EXPECT((need = gims_agc_workspace_bytes(gi.data(), 5, flags)) > 0 && need % 256 == 0);
+      for (int n_params : {1, 5}) EXPECT(carved(gims_agc_build(gi.data(), 5, gp.data(), n_params, flags, work, need, nullptr)));
+      EXPECT(gims_agc_build(gi.data(), 5, gp.data(), 5, flags, work, need - 1, nullptr) == GIMS_EINVAL && strstr(gims_last_error(), "gims_agc_build"));
     }
+    for (int n_params : {0, 2, 6}) EXPECT(gims_agc_build(gi.data(), 5, gp.data(), n_params, 0, work, need, nullptr) == GIMS_EINVAL && strstr(gims_last_error(), "n_params"));
+    EXPECT(gims_agc_build(gi.data(), 5, nullptr, 5, 0, work, need, nullptr) == GIMS_EINVAL && strstr(gims_last_error(), "n_params"));
     EXPECT((need = gims_delaunay_workspace_bytes(gi.data(), 5)) > 0 && need % 256 == 0);
     EXPECT(carved(gims_delaunay_build(gi.data(), 5, work, need, nullptr)));
     EXPECT(gims_delaunay_build(gi.data(), 5, work, need - 1, nullptr) == GIMS_EINVAL && strstr(gims_last_error(), "gims_delaunay_build"));
