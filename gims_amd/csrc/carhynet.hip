@@ -1,113 +1,15 @@
-// CAR-HyNet patch descriptor: the layers of /root/reference/carhynet/models.py:311-399 that are not
-// plain GEMMs.  Activations are NHWC f32 in HBM ([patch][y][x][channel]: a pixel's channels are contiguous, so a 3x3
-// convolution is im2col + the split-bf16 GEMM of linear.hip with output rows = pixels, and the GEMM's output IS the next
-// NHWC activation).  First version of this row: correct and parity-checked; the kernels below are simple streaming kernels
-// (one thread per output element or per (pixel, channel quad)), HBM-bound by design, not yet fused.
+// CAR-HyNet patch descriptor: the layers of /root/reference/carhynet/models.py:311-399 in front of the 8x8 convolution
+// (which is a plain split-bf16 GEMM of linear.hip on the flattened activation), and the final normalisation.  One workgroup per patch (or
+// half patch): the activation of a patch lives in LDS from the first read to the last write of a block, and leaves either as NHWC f32
+// ([patch][y][x][channel], what gims_ch_sandglass reads) or as SPL32 split-bf16 pixel rows (the operand of the next convolution).
 //
-//   gims_ch_frn_stats     FRN's per-(patch, channel) scale  weight * rsqrt(mean over H x W of x^2 + |eps|)        models.py:67-82
-//   gims_ch_pool_hw       CoordAtt's two average pools (over W and over H), optionally of the FRN output    models.py:141-143
-//   gims_ch_gates         CoordAtt's shared 1x1 conv + BN + h_swish and the two 1x1 convs + sigmoid         models.py:144-151
-//   gims_ch_apply         y = max((x * s + b) * a_w * a_h, tau): FRN scale, CoordAtt gates, TLU in one pass models.py:78-84,152,107
-//   gims_ch_im2col3       3x3 patches (pad 1, stride 1 or 2) written as SPL32 split-bf16 GEMM operand rows
-//   gims_ch_dwconv3       depthwise 3x3 + folded BatchNorm (+ReLU6 on input / output, + residual)          models.py:172-180, 207, 220-223
-//   gims_ch_gate_pw_pw    SandGlass middle in one pass: CoordAtt gates applied, 1x1 C->16 (+BN), 1x1 16->C (+BN, ReLU6)  models.py:152, 208-218
-//   gims_ch_input_block   FRN(3) + TLU(3) on the raw patches and the first convolution's split-bf16 operand rows, one workgroup per patch  models.py:316-317
-//   gims_ch_frn_block     FRN (+ CoordAtt) + TLU of one layer, one workgroup per patch: one read, one write of the activation   models.py:57-108, 139-153
-//   gims_ch_sandglass     the whole SandGlass block + outer residual, one workgroup per patch, activation resident in LDS  models.py:182-235
-//   gims_ch_l2norm        x / sqrt(sum x^2 + 1e-10) per row                                                 models.py:9-21
+//   gims_ch_conv_block_first  FRN(3) + TLU(3) on the raw patches, conv 3->32, FRN + CoordAtt + TLU (layer 1)                     models.py:315-322
+//   gims_ch_conv_block        3x3 convolution as an implicit GEMM on the matrix cores + FRN (+ CoordAtt) + TLU (layers 2-6)      models.py:324-355, 57-108, 139-153
+//   gims_ch_sandglass         the whole SandGlass block + outer residual, activation resident in LDS                            models.py:182-235
+//   gims_ch_l2norm            x / sqrt(sum x^2 + 1e-10) per row                                                                 models.py:9-21
 #include "common.h"
 
 namespace gims {
-
-// one workgroup per (patch, 32-channel group): 256 threads = 8 pixel lanes x 32 channels
-__global__ __launch_bounds__(256) void ch_frn_stats_kernel(const float* __restrict__ x, int hw, int c, const float* __restrict__ wgt, float eps,
-                                                           float* __restrict__ scale) {
-  __shared__ float red[8][32];
-  const int p = blockIdx.x, cg = blockIdx.y, cl = threadIdx.x & 31, pl = threadIdx.x >> 5;
-  const int ch = cg * 32 + cl;
-  float s = 0.f;
-  if (ch < c) {
-    const float* xp = x + (int64_t)p * hw * c + ch;
-    for (int i = pl; i < hw; i += 8) { const float v = xp[(int64_t)i * c]; s = fmaf(v, v, s); }
-  }
-  red[pl][cl] = s;
-  __syncthreads();
-  if (pl == 0 && ch < c) {
-    float t = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) t += red[j][cl];
-    scale[(int64_t)p * c + ch] = wgt[ch] * rsqrtf(t / (float)hw + eps);      // x * rsqrt(nu2 + |eps|) * weight (models.py:67-82)
-  }
-}
-
-// pooled means over W (ph[p][y][c]) and over H (pw[p][x][c]) of  x * s[p][c] + b[c]  (s, b may be null: identity).
-// One thread per output element: blockIdx.y = 0 -> ph (sum over x), 1 -> pw (sum over y); consecutive threads = consecutive
-// channels, so every load of the 32-step loop is a contiguous line across the wave.  The patch is read twice (once per
-// direction), from L2 the second time.
-__global__ __launch_bounds__(256) void ch_pool_hw_kernel(const float* __restrict__ x, int64_t patches, int h, int w, int c, const float* __restrict__ s,
-                                                         const float* __restrict__ b, float* __restrict__ ph, float* __restrict__ pw,
-                                                         float* __restrict__ rowsq) {
-  const bool over_x = blockIdx.y == 0;
-  const int n_line = over_x ? h : w, n_sum = over_x ? w : h;
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= patches * n_line * c) return;
-  const int ch = (int)(i % c);
-  const int line = (int)((i / c) % n_line);
-  const int64_t p = i / ((int64_t)c * n_line);
-  const float* xp = x + (p * h * w + (over_x ? (int64_t)line * w : line)) * c + ch;
-  const int64_t step = over_x ? c : (int64_t)w * c;
-  float t = 0.f, q = 0.f;
-  for (int k = 0; k < n_sum; ++k) { const float v = xp[k * step]; t += v; q = fmaf(v, v, q); }
-  t /= (float)n_sum;
-  if (s) t = fmaf(t, s[p * c + ch], b ? b[ch] : 0.f);      // the mean of an affine map is the affine map of the mean
-  (over_x ? ph : pw)[i] = t;
-  if (rowsq && over_x) rowsq[i] = q;                        // per-row sums of squares: FRN's statistics from the same pass
-}
-
-// FRN scale from the per-row sums of squares of gims_ch_pool_hw: scale[p][c] = weight[c] * rsqrt(sum_y rowsq[p][y][c] / (h w) + eps)
-__global__ __launch_bounds__(256) void ch_frn_from_rows_kernel(const float* __restrict__ rowsq, int64_t patches, int h, int w, int c, const float* __restrict__ wgt,
-                                                               float eps, float* __restrict__ scale) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= patches * c) return;
-  const int ch = (int)(i % c);
-  const int64_t p = i / c;
-  float t = 0.f;
-  for (int y = 0; y < h; ++y) t += rowsq[(p * h + y) * c + ch];
-  scale[i] = wgt[ch] * rsqrtf(t / (float)(h * w) + eps);
-}
-
-// CoordAtt gates for one patch per workgroup: rows r = 0..h-1 from ph, h..h+w-1 from pw (optionally the pools of the RAW
-// activation, mapped through FRN's per-(patch, channel) affine  v * s[p][k] + b[k]  on the way in).
-//   mid[r][m] = h_swish(bn(conv1(row r)))  (8 channels; BatchNorm folded into w1 / b1 by the caller)
-//   a_h[y][ch] = sigmoid(conv_h(mid[y])),  a_w[x][ch] = sigmoid(conv_w(mid[h + x]))
-__global__ __launch_bounds__(256) void ch_gates_kernel(const float* __restrict__ ph, const float* __restrict__ pw, int h, int w, int c,
-                                                       const float* __restrict__ w1, const float* __restrict__ b1,      // [8][c], [8]
-                                                       const float* __restrict__ wh, const float* __restrict__ bh,      // [c][8], [c]
-                                                       const float* __restrict__ ww, const float* __restrict__ bw,
-                                                       const float* __restrict__ fs, const float* __restrict__ fb,
-                                                       float* __restrict__ ah, float* __restrict__ aw) {
-  __shared__ float mid[64][8];
-  const int p = blockIdx.x, t = threadIdx.x, rows = h + w;
-  for (int i = t; i < rows * 8; i += 256) {
-    const int r = i >> 3, m = i & 7;
-    const float* src = r < h ? ph + ((int64_t)p * h + r) * c : pw + ((int64_t)p * w + (r - h)) * c;
-    float acc = b1[m];
-    for (int k = 0; k < c; ++k) acc = fmaf(fs ? fmaf(src[k], fs[(int64_t)p * c + k], fb[k]) : src[k], w1[m * c + k], acc);
-    mid[r][m] = acc * (fminf(fmaxf(acc + 3.f, 0.f), 6.f) / 6.f);
-  }
-  __syncthreads();
-  for (int i = t; i < rows * c; i += 256) {
-    const int r = i / c, ch = i - r * c;
-    const bool is_h = r < h;
-    const float* wt = (is_h ? wh : ww) + ch * 8;
-    float acc = (is_h ? bh : bw)[ch];
-#pragma unroll
-    for (int m = 0; m < 8; ++m) acc = fmaf(mid[r][m], wt[m], acc);
-    const float g = 1.f / (1.f + __expf(-acc));
-    if (is_h) ah[((int64_t)p * h + r) * c + ch] = g;
-    else aw[((int64_t)p * w + (r - h)) * c + ch] = g;
-  }
-}
 
 // four consecutive channels of one pixel as split-bf16 (SPL32: hi at o, lo at o + 32)
 __device__ __forceinline__ void store_split4(uint16_t* o, const float (&v)[4]) {
@@ -118,205 +20,16 @@ __device__ __forceinline__ void store_split4(uint16_t* o, const float (&v)[4]) {
   *(uint2*)(o + 32) = make_uint2(l01, l23);
 }
 
-// y[p][y][x][ch] = max((x * s[p][ch] + b[ch]) * ah[p][y][ch] * aw[p][x][ch], tau[ch]);  any of s/b, ah/aw, tau may be null.
-// Output as f32 NHWC (y) and / or as SPL32 split-bf16 pixel rows (ysp, pitch ldsp): the operand of the next convolution.
-__global__ __launch_bounds__(256) void ch_apply_kernel(const float* __restrict__ x, int64_t total, int h, int w, int c, const float* __restrict__ s,
-                                                       const float* __restrict__ b, const float* __restrict__ ah, const float* __restrict__ aw,
-                                                       const float* __restrict__ tau, float* __restrict__ y, uint16_t* __restrict__ ysp, int64_t ldsp) {
-  const int64_t i4 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-  if (i4 >= total) return;
-  const int ch = (int)(i4 % c);
-  const int64_t pix = i4 / c;
-  const int xx = (int)(pix % w), yy = (int)((pix / w) % h);
-  const int64_t p = pix / ((int64_t)w * h);
-  float4 v = *(const float4*)(x + i4);
-  float r[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    float t = r[j];
-    if (s) t = fmaf(t, s[p * c + ch + j], b ? b[ch + j] : 0.f);
-    if (ah) t = t * aw[(p * w + xx) * c + ch + j] * ah[(p * h + yy) * c + ch + j];
-    if (tau) t = fmaxf(t, tau[ch + j]);
-    r[j] = t;
-  }
-  if (y) *(float4*)(y + i4) = make_float4(r[0], r[1], r[2], r[3]);
-  if (ysp) store_split4(ysp + pix * ldsp + spl_col(ch), r);
-}
-
-// 3x3 neighbourhoods (pad 1) of an NHWC activation as rows of a split-bf16 (SPL32) GEMM operand:
-// out row = output pixel (p, yo, xo), logical column k = (ky * 3 + kx) * c + ch, K = 9 c zero-padded to kpad (multiple of 32).
-__global__ __launch_bounds__(256) void ch_im2col3_kernel(const float* __restrict__ x, int64_t rows, int h, int w, int c, int stride, int ho, int wo,
-                                                         int kpad, uint16_t* __restrict__ out, int64_t ld) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int kq = kpad / 4;                                   // column quads per row
-  if (i >= rows * kq) return;
-  const int64_t row = i / kq;
-  const int k = (int)(i - row * kq) * 4;
-  const int xo = (int)(row % wo), yo = (int)((row / wo) % ho);
-  const int64_t p = row / ((int64_t)wo * ho);
-  float v[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int kk = k + j;
-    float t = 0.f;
-    if (kk < 9 * c) {
-      const int tap = kk / c, ch = kk - tap * c;
-      const int yy = yo * stride + tap / 3 - 1, xx = xo * stride + tap % 3 - 1;
-      if (yy >= 0 && yy < h && xx >= 0 && xx < w) t = x[((p * h + yy) * w + xx) * c + ch];
-    }
-    v[j] = t;
-  }
-  const uint32_t h01 = pack_bf2(v[0], v[1]), h23 = pack_bf2(v[2], v[3]);
-  const uint32_t l01 = pack_bf2(v[0] - __uint_as_float(h01 << 16), v[1] - __uint_as_float(h01 & 0xffff0000u));
-  const uint32_t l23 = pack_bf2(v[2] - __uint_as_float(h23 << 16), v[3] - __uint_as_float(h23 & 0xffff0000u));
-  uint16_t* o = out + row * ld + spl_col(k);
-  *(uint2*)o = make_uint2(h01, h23);
-  *(uint2*)(o + 32) = make_uint2(l01, l23);
-}
-
-// depthwise 3x3 (pad 1, stride 1) with BatchNorm folded into wt [9][c] / bias [c]; optional ReLU6 on the output;
-// optional residual: y = res_scale * res + conv.
-__global__ __launch_bounds__(256) void ch_dwconv3_kernel(const float* __restrict__ x, int64_t total, int h, int w, int c, const float* __restrict__ wt,
-                                                         const float* __restrict__ bias, int relu6_out, const float* __restrict__ res, float res_scale,
-                                                         float* __restrict__ y, uint16_t* __restrict__ ysp, int64_t ldsp) {
-  const int64_t i4 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-  if (i4 >= total) return;
-  const int ch = (int)(i4 % c);
-  const int64_t pix = i4 / c;
-  const int xx = (int)(pix % w), yy = (int)((pix / w) % h);
-  const int64_t p = pix / ((int64_t)w * h);
-  float acc[4] = {bias[ch], bias[ch + 1], bias[ch + 2], bias[ch + 3]};
-#pragma unroll
-  for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-    for (int kx = 0; kx < 3; ++kx) {
-      const int y2 = yy + ky - 1, x2 = xx + kx - 1;
-      if (y2 < 0 || y2 >= h || x2 < 0 || x2 >= w) continue;
-      const float4 v = *(const float4*)(x + ((p * h + y2) * w + x2) * c + ch);
-      const float4 k4 = *(const float4*)(wt + (ky * 3 + kx) * c + ch);
-      acc[0] = fmaf(v.x, k4.x, acc[0]); acc[1] = fmaf(v.y, k4.y, acc[1]); acc[2] = fmaf(v.z, k4.z, acc[2]); acc[3] = fmaf(v.w, k4.w, acc[3]);
-    }
-  if (relu6_out) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[j] = fminf(fmaxf(acc[j], 0.f), 6.f);
-  }
-  if (res) {
-    const float4 r = *(const float4*)(res + i4);
-    acc[0] = fmaf(r.x, res_scale, acc[0]); acc[1] = fmaf(r.y, res_scale, acc[1]); acc[2] = fmaf(r.z, res_scale, acc[2]); acc[3] = fmaf(r.w, res_scale, acc[3]);
-  }
-  if (y) *(float4*)(y + i4) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-  if (ysp) store_split4(ysp + pix * ldsp + spl_col(ch), acc);
-}
-
-// SandGlass middle, one thread per pixel: z = ReLU6(W1 (W0 (x * a_w * a_h) + b0) + b1) with C -> 16 -> C channels (C = 32 or 64),
-// BatchNorm folded into W0/b0 and W1/b1 (models.py:208-218: CoordAtt output, pw-linear + BN, pw + BN + ReLU6).  The weights
-// (<= 2 x 64 x 16 floats) sit in LDS; x, a_h, a_w are read as float4.
-template <int C>
-__global__ __launch_bounds__(256) void ch_gate_pw_pw_kernel(const float* __restrict__ x, int64_t pixels, int h, int w, const float* __restrict__ ah,
-                                                            const float* __restrict__ aw, const float* __restrict__ w0, const float* __restrict__ b0,
-                                                            const float* __restrict__ w1, const float* __restrict__ b1, float* __restrict__ z) {
-  __shared__ float s0[16 * C], s1[C * 16], sb0[16], sb1[C];
-  for (int i = threadIdx.x; i < 16 * C; i += 256) { s0[i] = w0[i]; s1[i] = w1[i]; }
-  if (threadIdx.x < 16) sb0[threadIdx.x] = b0[threadIdx.x];
-  if (threadIdx.x < C) sb1[threadIdx.x] = b1[threadIdx.x];
-  __syncthreads();
-  const int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (pix >= pixels) return;
-  const int xx = (int)(pix % w), yy = (int)((pix / w) % h);
-  const int64_t p = pix / ((int64_t)w * h);
-  const float* xr = x + pix * C;
-  const float* hr = ah + (p * h + yy) * C;
-  const float* wr = aw + (p * w + xx) * C;
-  float hid[16];
-#pragma unroll
-  for (int m = 0; m < 16; ++m) hid[m] = sb0[m];
-#pragma unroll
-  for (int k = 0; k < C; k += 4) {
-    const float4 v = *(const float4*)(xr + k), g1 = *(const float4*)(hr + k), g2 = *(const float4*)(wr + k);
-    const float t[4] = {v.x * g2.x * g1.x, v.y * g2.y * g1.y, v.z * g2.z * g1.z, v.w * g2.w * g1.w};      // x * a_w * a_h (models.py:152)
-#pragma unroll
-    for (int m = 0; m < 16; ++m)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) hid[m] = fmaf(t[j], s0[m * C + k + j], hid[m]);
-  }
-#pragma unroll
-  for (int o = 0; o < C; o += 4) {
-    float r[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float acc = sb1[o + j];
-#pragma unroll
-      for (int m = 0; m < 16; ++m) acc = fmaf(hid[m], s1[(o + j) * 16 + m], acc);
-      r[j] = fminf(fmaxf(acc, 0.f), 6.f);
-    }
-    *(float4*)(z + pix * C + o) = make_float4(r[0], r[1], r[2], r[3]);
-  }
-}
-
-// ---------------------------------------------------------------------------------------------- input block
-// One workgroup per patch: FRN(3) + TLU(3) on the 32x32x3 input (models.py:316-317) and the 3x3 neighbourhoods of the result
-// written straight as the split-bf16 operand rows of the first convolution (K = 9 taps x 4 channels -- the 4th is zero --
-// padded to 64): 16 lanes write one 256-byte row, so a wave-wide store covers 1 KiB of consecutive bytes.
-__global__ __launch_bounds__(256) void ch_input_block_kernel(const float* __restrict__ patches, const float* __restrict__ fw, const float* __restrict__ fb,
-                                                             float eps, const float* __restrict__ tau, uint16_t* __restrict__ out, int64_t ldo) {
-  __shared__ float yb[1024 * 4];
-  __shared__ float red[64][4];
-  __shared__ float sc[4];
-  const int t = threadIdx.x;
-  const float* pp = patches + (int64_t)blockIdx.x * 1024 * 3;
-  float q[3] = {0.f, 0.f, 0.f};
-  for (int pix = t; pix < 1024; pix += 256) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { const float v = pp[pix * 3 + c]; yb[pix * 4 + c] = v; q[c] = fmaf(v, v, q[c]); }
-    yb[pix * 4 + 3] = 0.f;
-  }
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) q[c] += __shfl_xor(q[c], o, 64);
-  }
-  if ((t & 63) == 0) { red[t >> 6][0] = q[0]; red[t >> 6][1] = q[1]; red[t >> 6][2] = q[2]; }
-  __syncthreads();
-  if (t < 3) sc[t] = fw[t] * rsqrtf((red[0][t] + red[1][t] + red[2][t] + red[3][t]) / 1024.f + eps);
-  __syncthreads();
-  for (int i = t; i < 1024 * 3; i += 256) {
-    const int pix = i / 3, c = i - 3 * pix;
-    yb[pix * 4 + c] = fmaxf(fmaf(yb[pix * 4 + c], sc[c], fb[c]), tau[c]);
-  }
-  __syncthreads();
-  // rows: pixel = 16 * it + (t >> 4); lane part q16 = t & 15 writes elements [8 q16, 8 q16 + 8) of the 128-element SPL32 row
-  const int q16 = t & 15, blk = q16 >> 3, pos = (8 * q16) & 63, lo = pos >= 32, k0 = 32 * blk + (pos & 31);
-  for (int it = 0; it < 64; ++it) {
-    const int pix = 16 * it + (t >> 4), yy = pix >> 5, xx = pix & 31;
-    float v[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int k = k0 + e, tap = k >> 2, c = k & 3;
-      const int y2 = yy + tap / 3 - 1, x2 = xx + tap % 3 - 1;
-      v[e] = (tap < 9 && y2 >= 0 && y2 < 32 && x2 >= 0 && x2 < 32) ? yb[(y2 * 32 + x2) * 4 + c] : 0.f;
-    }
-    uint32_t w[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const uint32_t h = pack_bf2(v[2 * e], v[2 * e + 1]);
-      w[e] = lo ? pack_bf2(v[2 * e] - __uint_as_float(h << 16), v[2 * e + 1] - __uint_as_float(h & 0xffff0000u)) : h;
-    }
-    *(uint4*)(out + ((int64_t)blockIdx.x * 1024 + pix) * ldo + 8 * q16) = make_uint4(w[0], w[1], w[2], w[3]);
-  }
-}
-
-// ---------------------------------------------------------------------------------------------- fused FRN (+CoordAtt) + TLU block
-// One workgroup per patch: the raw convolution output [HW*HW][C] is read ONCE into LDS, FRN's statistic, CoordAtt's pools and
-// gates are computed from the LDS copy, and  y = max((x s + b) a_w a_h, tau)  leaves as f32 and / or split-bf16 pixel rows:
-// 8 bytes of HBM traffic per element instead of 12 (plain FRN layers) or 20 (FRN + CoordAtt layers: statistics pass, two
-// pooling sweeps, apply pass).  models.py:57-85 (FRN), 139-153 (CoordAtt), 107-108 (TLU).
+// ---------------------------------------------------------------------------------------------- FRN (+CoordAtt) + TLU on an LDS-resident patch
+// The raw convolution output [HW*HW][C] of a patch sits in LDS; FRN's statistic, CoordAtt's pools and gates are computed from that copy,
+// and  y = max((x s + b) a_w a_h, tau)  leaves as f32 and / or split-bf16 pixel rows.  models.py:57-85 (FRN), 139-153 (CoordAtt), 107-108 (TLU).
 // position of channel c of pixel p inside the LDS image [NPIX][C] of frn_block_body
 __device__ __forceinline__ int frn_slot(int p, int c, int C) { return p * C + ((((c >> 2) ^ (p & 7)) << 2) | (c & 3)); }
 
 struct ChGateW { const float* w1; const float* b1; const float* wh; const float* bh; const float* ww; const float* bw; };   // null w1: no CoordAtt
 
-// body shared by ch_frn_block_kernel and ch_conv_block_kernel: the raw convolution output of ONE patch is in LDS (xb [NPIX][C],
-// followed by the scratch arrays); pbase = index of the patch's first pixel row in the outputs
+// the second half of ch_conv_block_kernel: the raw convolution output of ONE patch is in LDS (xb [NPIX][C], followed by the scratch
+// arrays); pbase = index of the patch's first pixel row in the outputs
 template <int C, int HW, int NT>
 __device__ __forceinline__ void frn_block_body(float* lds, const float* __restrict__ fw, const float* __restrict__ fb, float eps, const ChGateW& g,
                                                const float* __restrict__ tau, float* __restrict__ y, uint16_t* __restrict__ ysp, int64_t ldsp, int64_t pbase,
@@ -421,34 +134,14 @@ __device__ __forceinline__ void frn_block_body(float* lds, const float* __restri
   stamp(6);
 }
 
-template <int C, int HW, int NT>
-__global__ __launch_bounds__(NT) void ch_frn_block_kernel(const float* __restrict__ x, const float* __restrict__ fw, const float* __restrict__ fb, float eps,
-                                                           ChGateW g, const float* __restrict__ tau, float* __restrict__ y, uint16_t* __restrict__ ysp,
-                                                           int64_t ldsp) {
-  constexpr int NPIX = HW * HW, QPP = C / 4, NQ = NPIX * QPP / NT;
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int t = threadIdx.x;
-  const int64_t pbase = (int64_t)blockIdx.x * NPIX;
-  const float* xp = x + pbase * C;
-  {   // bulk load: NQ independent, fully coalesced 16-byte loads per thread
-    float4 v[NQ];
-#pragma unroll
-    for (int j = 0; j < NQ; ++j) v[j] = *(const float4*)(xp + (int64_t)(t + NT * j) * 4);
-#pragma unroll
-    for (int j = 0; j < NQ; ++j) { const int i = t + NT * j; *(float4*)(lds + frn_slot(i / QPP, 4 * (i % QPP), C)) = v[j]; }
-  }
-  __syncthreads();
-  frn_block_body<C, HW, NT>(lds, fw, fb, eps, g, tau, y, ysp, ldsp, pbase);
-}
-
 // ---------------------------------------------------------------------------------------------- fused 3x3 convolution + FRN (+CoordAtt) + TLU
 // One workgroup (8 waves) per patch.  The split-bf16 input activation of the patch ([HIN*HIN][2 CIN] SPL32 pixel rows) is
 // read ONCE into LDS with a one-pixel zero border, and the 3x3 convolution runs there as an implicit GEMM on the matrix
 // cores: rows = output pixels, K = 9 taps x CIN channels, three bf16 MFMAs per product (hi*hi + hi*lo + lo*hi, like the
-// GEMMs it replaces).  A tap is a shifted view of the LDS image -- where the gather-mode GEMM (GIMS_LINEAR_CONV3) DMA-ed every
+// GEMMs it replaces).  A tap is a shifted view of the LDS image -- where a gather-mode GEMM would fetch every
 // pixel row nine times from L2.  The weights come pre-packed in MFMA fragment order (one contiguous KiB per fragment),
 // straight from L1 / L2 into registers, one K step ahead.  The accumulators (+ bias) then go to LDS over the dead input image
-// and the FRN (+ CoordAtt) + TLU block runs on them as in ch_frn_block_kernel: the raw convolution output never reaches HBM.
+// and the FRN (+ CoordAtt) + TLU block runs on them (frn_block_body): the raw convolution output never reaches HBM.
 // 16-byte chunks of a pixel record are XOR-swizzled by the pixel index so that the fragment reads of 16 consecutive pixels
 // hit distinct banks.
 template <int CIN, int COUT, int HIN, int STRIDE, int PP = 1>
@@ -1315,121 +1008,6 @@ __global__ __launch_bounds__(256) void ch_l2norm_kernel(const float* __restrict_
 }  // namespace gims
 
 using namespace gims;
-
-extern "C" int gims_ch_frn_stats(const float* x, int64_t patches, int32_t hw, int32_t c, const float* weight, float eps, float* scale, void* stream) {
-  GIMS_CHECK_ARG(x && weight && scale && patches > 0 && hw > 0 && c > 0 && eps >= 0.f, "gims_ch_frn_stats: bad arguments");
-  hipLaunchKernelGGL(ch_frn_stats_kernel, dim3((unsigned)patches, (c + 31) / 32), dim3(256), 0, (hipStream_t)stream, x, hw, c, weight, eps, scale);
-  GIMS_LAUNCH_CHECK();
-  return GIMS_OK;
-}
-
-extern "C" int gims_ch_pool_hw(const float* x, int64_t patches, int32_t h, int32_t w, int32_t c, const float* s, const float* b, float* ph, float* pw,
-                               float* rowsq, void* stream) {
-  GIMS_CHECK_ARG(x && ph && pw && patches > 0 && h > 0 && w > 0 && c > 0, "gims_ch_pool_hw: bad arguments");
-  const int64_t n = patches * (h > w ? h : w) * c;
-  hipLaunchKernelGGL(ch_pool_hw_kernel, dim3((unsigned)((n + 255) / 256), 2), dim3(256), 0, (hipStream_t)stream, x, patches, h, w, c, s, b, ph, pw, rowsq);
-  GIMS_LAUNCH_CHECK();
-  return GIMS_OK;
-}
-
-extern "C" int gims_ch_frn_from_rows(const float* rowsq, int64_t patches, int32_t h, int32_t w, int32_t c, const float* weight, float eps, float* scale,
-                                     void* stream) {
-  GIMS_CHECK_ARG(rowsq && weight && scale && patches > 0 && h > 0 && w > 0 && c > 0 && eps >= 0.f, "gims_ch_frn_from_rows: bad arguments");
-  hipLaunchKernelGGL(ch_frn_from_rows_kernel, dim3((unsigned)((patches * c + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rowsq, patches, h, w, c, weight,
-                     eps, scale);
-  GIMS_LAUNCH_CHECK();
-  return GIMS_OK;
-}
-
-extern "C" int gims_ch_gates(const float* ph, const float* pw, int64_t patches, int32_t h, int32_t w, int32_t c, const float* w1, const float* b1,
-                             const float* wh, const float* bh, const float* ww, const float* bw, const float* frn_scale, const float* frn_bias,
-                             float* ah, float* aw, void* stream) {
-  GIMS_CHECK_ARG(ph && pw && w1 && b1 && wh && bh && ww && bw && ah && aw && patches > 0 && h + w <= 64 && ((frn_scale == nullptr) == (frn_bias == nullptr)),
-                 "gims_ch_gates: bad arguments (h + w <= 64)");
-  hipLaunchKernelGGL(ch_gates_kernel, dim3((unsigned)patches), dim3(256), 0, (hipStream_t)stream, ph, pw, h, w, c, w1, b1, wh, bh, ww, bw, frn_scale, frn_bias,
-                     ah, aw);
-  GIMS_LAUNCH_CHECK();
-  return GIMS_OK;
-}
-
-extern "C" int gims_ch_apply(const float* x, int64_t patches, int32_t h, int32_t w, int32_t c, const float* s, const float* b, const float* ah,
-                             const float* aw, const float* tau, float* y, uint16_t* y_split, int64_t ld_split, void* stream) {
-  GIMS_CHECK_ARG(x && (y || y_split) && patches > 0 && (c % 4) == 0 && ((ah == nullptr) == (aw == nullptr)), "gims_ch_apply: bad arguments (c %% 4 == 0)");
-  GIMS_CHECK_ARG(!y_split || ((c % 32) == 0 && ld_split >= 2 * (int64_t)c && (ld_split % 4) == 0), "gims_ch_apply: split output needs c %% 32 == 0, pitch >= 2c");
-  const int64_t total = patches * h * w * c;
-  hipLaunchKernelGGL(ch_apply_kernel, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, total, h, w, c, s, b, ah, aw, tau, y,
-                     y_split, ld_split);
-  GIMS_LAUNCH_CHECK();
-  return GIMS_OK;
-}
-
-extern "C" int gims_ch_im2col3(const float* x, int64_t patches, int32_t h, int32_t w, int32_t c, int32_t stride, uint16_t* out, int64_t ld,
-                               int32_t kpad, void* stream) {
-  GIMS_CHECK_ARG(x && out && patches > 0 && (stride == 1 || stride == 2) && (kpad % 32) == 0 && kpad >= 9 * c && ld >= 2 * (int64_t)kpad && (ld % 64) == 0,
-                 "gims_ch_im2col3: bad arguments (kpad %% 32 == 0, kpad >= 9c, ld >= 2 kpad, ld %% 64 == 0)");
-  const int ho = (h - 1) / stride + 1, wo = (w - 1) / stride + 1;
-  const int64_t rows = patches * ho * wo, n = rows * (kpad / 4);
-  hipLaunchKernelGGL(ch_im2col3_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, rows, h, w, c, stride, ho, wo, kpad, out, ld);
-  GIMS_LAUNCH_CHECK();
-  return GIMS_OK;
-}
-
-extern "C" int gims_ch_dwconv3(const float* x, int64_t patches, int32_t h, int32_t w, int32_t c, const float* wt, const float* bias, int32_t relu6_out,
-                               const float* res, float res_scale, float* y, uint16_t* y_split, int64_t ld_split, void* stream) {
-  GIMS_CHECK_ARG(x && (y || y_split) && wt && bias && patches > 0 && (c % 4) == 0, "gims_ch_dwconv3: bad arguments (c %% 4 == 0)");
-  GIMS_CHECK_ARG(!y_split || ((c % 32) == 0 && ld_split >= 2 * (int64_t)c && (ld_split % 4) == 0), "gims_ch_dwconv3: split output needs c %% 32 == 0, pitch >= 2c");
-  const int64_t total = patches * h * w * c;
-  hipLaunchKernelGGL(ch_dwconv3_kernel, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, total, h, w, c, wt, bias, relu6_out, res,
-                     res_scale, y, y_split, ld_split);
-  GIMS_LAUNCH_CHECK();
-  return GIMS_OK;
-}
-
-extern "C" int gims_ch_gate_pw_pw(const float* x, int64_t patches, int32_t h, int32_t w, int32_t c, const float* ah, const float* aw, const float* w0,
-                                  const float* b0, const float* w1, const float* b1, float* z, void* stream) {
-  GIMS_CHECK_ARG(x && ah && aw && w0 && b0 && w1 && b1 && z && patches > 0 && (c == 32 || c == 64), "gims_ch_gate_pw_pw: bad arguments (c = 32 or 64, hidden 16)");
-  const int64_t pixels = patches * h * w;
-  const dim3 grid((unsigned)((pixels + 255) / 256));
-  if (c == 32) hipLaunchKernelGGL(ch_gate_pw_pw_kernel<32>, grid, dim3(256), 0, (hipStream_t)stream, x, pixels, h, w, ah, aw, w0, b0, w1, b1, z);
-  else hipLaunchKernelGGL(ch_gate_pw_pw_kernel<64>, grid, dim3(256), 0, (hipStream_t)stream, x, pixels, h, w, ah, aw, w0, b0, w1, b1, z);
-  GIMS_LAUNCH_CHECK();
-  return GIMS_OK;
-}
-
-extern "C" int gims_ch_input_block(const float* patches, int64_t n, const float* frn_weight, const float* frn_bias, float eps, const float* tau,
-                                   uint16_t* out, int64_t ld, void* stream) {
-  GIMS_CHECK_ARG(patches && frn_weight && frn_bias && tau && out && n > 0 && eps >= 0.f && ld >= 128 && (ld % 64) == 0 && (((uintptr_t)out) & 15) == 0,
-                 "gims_ch_input_block: bad arguments (SPL32 rows of K = 64: pitch >= 128, %% 64 == 0)");
-  hipLaunchKernelGGL(ch_input_block_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, patches, frn_weight, frn_bias, eps, tau, out, ld);
-  GIMS_LAUNCH_CHECK();
-  return GIMS_OK;
-}
-
-extern "C" int gims_ch_frn_block(const float* x, int64_t patches, int32_t hw, int32_t c, const float* frn_weight, const float* frn_bias, float eps,
-                                 const float* const* gate_w /* 6 device pointers (w1, b1, wh, bh, ww, bw) or NULL: no CoordAtt */, const float* tau,
-                                 float* y, uint16_t* y_split, int64_t ld_split, void* stream) {
-  GIMS_CHECK_ARG(x && frn_weight && frn_bias && tau && (y || y_split) && patches > 0 && eps >= 0.f &&
-                     ((c == 32 && hw == 32) || (c == 64 && hw == 16) || (c == 128 && hw == 8)),
-                 "gims_ch_frn_block: bad arguments (32x32x32, 16x16x64 or 8x8x128 activations)");
-  GIMS_CHECK_ARG(!y_split || (ld_split >= 2 * (int64_t)c && (ld_split % 4) == 0), "gims_ch_frn_block: split output pitch >= 2c");
-  ChGateW G = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  if (gate_w) {
-    for (int i = 0; i < 6; ++i) GIMS_CHECK_ARG(gate_w[i] != nullptr, "gims_ch_frn_block: gate weight pointer %d is null", i);
-    G = ChGateW{gate_w[0], gate_w[1], gate_w[2], gate_w[3], gate_w[4], gate_w[5]};
-  }
-  constexpr int FRN_NT = 1024;
-  const size_t lds = ((size_t)hw * hw * c + (FRN_NT / c) * (size_t)c + c + 2 * (size_t)hw * c + 16 * (size_t)hw) * sizeof(float);
-  GIMS_LDS_ATTR((const void*)ch_frn_block_kernel<32, 32, FRN_NT>, 160 * 1024);
-  GIMS_LDS_ATTR((const void*)ch_frn_block_kernel<64, 16, FRN_NT>, 160 * 1024);
-  GIMS_LDS_ATTR((const void*)ch_frn_block_kernel<128, 8, FRN_NT>, 160 * 1024);
-  const dim3 grid((unsigned)patches);
-  hipStream_t st = (hipStream_t)stream;
-  if (c == 32) hipLaunchKernelGGL((ch_frn_block_kernel<32, 32, FRN_NT>), grid, dim3(FRN_NT), lds, st, x, frn_weight, frn_bias, eps, G, tau, y, y_split, ld_split);
-  else if (c == 64) hipLaunchKernelGGL((ch_frn_block_kernel<64, 16, FRN_NT>), grid, dim3(FRN_NT), lds, st, x, frn_weight, frn_bias, eps, G, tau, y, y_split, ld_split);
-  else hipLaunchKernelGGL((ch_frn_block_kernel<128, 8, FRN_NT>), grid, dim3(FRN_NT), lds, st, x, frn_weight, frn_bias, eps, G, tau, y, y_split, ld_split);
-  GIMS_LAUNCH_CHECK();
-  return GIMS_OK;
-}
 
 constexpr int CH_PP5 = 1, CH_PP6 = 2;      // patches per workgroup of the 16x16x64 -> 8x8x128 layer (two measured slower: 357 -> 374 us) and of the 8x8x128 layer (537 -> 505 us per 8192 patches)
 template <int CIN, int COUT, int HIN, int STRIDE, bool FIRST = false, int PP = 1>

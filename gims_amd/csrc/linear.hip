@@ -305,12 +305,12 @@ struct X3P {
   __device__ static __forceinline__ int off(int row, int chunk) { return row * ROWE + ((chunk ^ swz(row)) << 3); }
 };
 
-// HI_ONLY: 1 = GIMS_LINEAR_HI_ONLY (one MFMA pass, hi planes), 4 = GIMS_LINEAR_CONV3 (all three passes; the A rows are gathered from the 3x3 neighbourhood of an NHWC activation)
+// HI_ONLY: GIMS_LINEAR_HI_ONLY (one MFMA pass, hi planes)
 // The body of one output tile (`bid` = the tile's slot in the XCD-aware order).  linear_x3p_kernel runs it once per workgroup; the
 // persistent form below walks a strided list of tiles.
-template <int TM, int TN, int WM, int WN, int S, int HI_ONLY>
+template <int TM, int TN, int WM, int WN, int S, bool HI_ONLY>
 __device__ __forceinline__ void linear_x3p_tile(const gims_linear_args& p, const int bid) {
-  using T = X3P<TM, TN, WM, WN, S, HI_ONLY == 1>;
+  using T = X3P<TM, TN, WM, WN, S, HI_ONLY>;
   constexpr int BK = T::BK;
   extern __shared__ __attribute__((aligned(16))) uint16_t smem[];
   const int t = threadIdx.x, lane = t & 63;
@@ -323,10 +323,10 @@ __device__ __forceinline__ void linear_x3p_tile(const gims_linear_args& p, const
   const int xcd = bid & 7, slot = bid >> 3;
   const int m0 = ((slot / nt_n) * 8 + xcd) * TM, n0 = (slot % nt_n) * TN;
   if (m0 >= p.m) return;
-  // probe (tools/gemm_probe.py): flag 0x1000 starts the workgroups of the odd slots conv_reserved x 3.4 us late, so that the
+  // probe (tools/gemm_probe.py): flag 0x1000 starts the workgroups of the odd slots probe_delay x 3.4 us late, so that the
   // HBM-bound epilogues of one half of the CUs fall into the L2-bound K loops of the other half
   if ((p.flags & 0x1000) && (slot & 1))
-    for (int d = 0; d < p.conv_reserved; ++d) __builtin_amdgcn_s_sleep(127);
+    for (int d = 0; d < p.probe_delay; ++d) __builtin_amdgcn_s_sleep(127);
   const int li = lane & 31, lh = lane >> 5;
   // diagnostic bits (tools/gemm_probe.py only): 0x100 = no main loop, 0x200 = no epilogue memory traffic, 0x400 / 0x800 / 0x2000 below
   const int nk = (p.flags & 0x100) ? 0 : p.k / BK;
@@ -335,21 +335,6 @@ __device__ __forceinline__ void linear_x3p_tile(const gims_linear_args& p, const
   const int p0 = wave * T::PIECES;
   constexpr int CPR = T::ROWE / 8;                         // 16-byte chunks per stage row (8, or 4 for the hi-only rows)
   const int drow = lane / CPR, dpos = lane % CPR;
-  // conv mode: this lane's A rows are output pixels; their input coordinates are fixed over the K loop
-  constexpr bool CONV = HI_ONLY == 4;
-  int cy[T::PIECES], cx[T::PIECES];
-  int64_t cb[T::PIECES];
-  const int cC = CONV ? p.k / 9 : 1;
-  if (CONV) {
-    const int wo = (p.conv_w - 1) / p.conv_stride + 1, ho = (p.conv_h - 1) / p.conv_stride + 1;
-#pragma unroll
-    for (int i = 0; i < T::PIECES; ++i) {
-      int gr = m0 + T::RPP * (p0 + i) + drow;
-      gr = gr < p.m - 1 ? gr : p.m - 1;
-      const int t2 = gr / wo, xo = gr - t2 * wo, pi = t2 / ho, yo = t2 - pi * ho;
-      cy[i] = yo * p.conv_stride; cx[i] = xo * p.conv_stride; cb[i] = (int64_t)pi * p.conv_h * p.conv_w;
-    }
-  }
   // Loop-invariant part of every DMA source address: the byte offset of this lane's 16-byte chunk inside the tile's row
   // panel (rows clamped to the last valid one), one per K segment.  The K-dependent part is a wave-uniform base pointer
   // (scalar ALU), so issuing a stage costs no vector ALU work -- VALU issue of one wave stalls the MFMAs of its SIMD mate,
@@ -378,14 +363,6 @@ __device__ __forceinline__ void linear_x3p_tile(const gims_linear_args& p, const
       const int pp = p0 + i;                               // wave-uniform
       const bool is_a = pp < T::PA;
       const char* g = (is_a ? ab : wb) + (second ? voff1[i] : voff0[i]);
-      if (CONV && is_a) {                                  // tap (ky, kx) and channel block of this K step; zeros outside the image
-        const int row = T::RPP * pp + drow;
-        const int tap = k / cC, c0 = k - tap * cC;
-        const int y = cy[i] + tap / 3 - 1, x = cx[i] + tap % 3 - 1;
-        const bool inb = y >= 0 && y < p.conv_h && x >= 0 && x < p.conv_w;
-        g = (const char*)(inb ? (const uint16_t*)p.a0 + (cb[i] + (int64_t)y * p.conv_w + x) * p.lda0 + 2 * c0 + 8 * (dpos ^ T::swz(row))
-                              : (const uint16_t*)p.a1 + 8 * dpos);
-      }
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
                                        (__attribute__((address_space(3))) void*)(dst + i * 512), 16, 0, 0);
     }
@@ -417,8 +394,8 @@ __device__ __forceinline__ void linear_x3p_tile(const gims_linear_args& p, const
     // order, so the waits count down): reads of K step 0 -> its lo*hi and hi*lo products -> reads of step 1 -> hi*hi of
     // step 0 -> step 1.  Left alone the compiler emits read-a-few / wait-for-ALL / multiply-a-few, eight exposed LDS round
     // trips per stage; more than 15 reads in flight cannot be counted by lgkmcnt either, hence two groups.
-    constexpr bool LO = HI_ONLY != 1;
-    const bool lo_pass = HI_ONLY == 0 || HI_ONLY == 4;
+    constexpr bool LO = !HI_ONLY;
+    const bool lo_pass = !HI_ONLY;
     bf16x8 ah[2][T::MI], al[2][T::MI], wh[2][T::NI], wl[2][T::NI];
     auto rd = [&](int s) __attribute__((always_inline)) {
 #pragma unroll
@@ -589,7 +566,7 @@ __device__ __forceinline__ void linear_x3p_tile(const gims_linear_args& p, const
   }
 }
 
-template <int TM, int TN, int WM, int WN, int S, int HI_ONLY = 0>
+template <int TM, int TN, int WM, int WN, int S, bool HI_ONLY = false>
 __global__ __launch_bounds__(64 * WM * WN) void linear_x3p_kernel(gims_linear_args p) {
   if (p.guard.stat && !attn_guard_fires(p.guard)) return;      // guarded launch (uniform for the grid): nothing to redo
   linear_x3p_tile<TM, TN, WM, WN, S, HI_ONLY>(p, (int)blockIdx.x);
@@ -598,7 +575,7 @@ __global__ __launch_bounds__(64 * WM * WN) void linear_x3p_kernel(gims_linear_ar
 // not fire used to dispatch every workgroup of the full grid -- 1536 workgroups with 128 KB of LDS each, six rounds per CU, 7 us -- just to
 // have them all return.  Here ONE round of workgroups is dispatched (gridDim.x <= CUs); a launch that fires walks its tiles with that stride
 // (same tile -> XCD mapping: the stride is a multiple of 8; same arithmetic per tile: bit-identical to the unguarded launch).
-template <int TM, int TN, int WM, int WN, int S, int HI_ONLY = 0>
+template <int TM, int TN, int WM, int WN, int S, bool HI_ONLY = false>
 __global__ __launch_bounds__(64 * WM * WN) void linear_x3p_guarded_kernel(gims_linear_args p, int n_tiles) {
   if (p.guard.stat && !attn_guard_fires(p.guard)) return;
   for (int bid = (int)blockIdx.x; bid < n_tiles; bid += (int)gridDim.x) {
@@ -661,17 +638,11 @@ static int linear_validate(const gims_linear_args* a) {
                    "gims_linear(bf16x6): plain scaled product only");
     return GIMS_OK;
   }
-  if (a->flags & GIMS_LINEAR_CONV3) {
-    GIMS_CHECK_ARG(a->a0_lo && a->a1 && a->k0 == a->k && (a->k % 9) == 0 && ((a->k / 9) % 32) == 0 && a->conv_h > 0 && a->conv_w > 0 &&
-                       (a->conv_stride == 1 || a->conv_stride == 2) &&
-                       (a->m % (((a->conv_h - 1) / a->conv_stride + 1) * ((a->conv_w - 1) / a->conv_stride + 1))) == 0,
-                   "gims_linear(conv3): pre-split NHWC input with C %% 32 == 0, k = 9 C, a1 = 128 zero bytes, m = patches * Ho * Wo");
-  }
   if (a->a0_lo) {   // pre-split activations: bf16 hi/lo planes, LDS-DMA kernel
     GIMS_CHECK_ARG(a->precision == GIMS_PREC_BF16X3 && a->w_lo, "gims_linear: pre-split A needs GIMS_PREC_BF16X3 and w_lo");
     GIMS_CHECK_ARG(a->k0 == a->k || a->a1_lo, "gims_linear: second A segment needs its lo plane");
     GIMS_CHECK_ARG((a->k % 32) == 0 && (a->k0 % 32) == 0, "gims_linear(pre-split): K=%d k0=%d must be multiples of 32", a->k, a->k0);
-    GIMS_CHECK_ARG((a->lda0 % 64) == 0 && (a->lda1 % 64) == 0 && (a->ldw % 64) == 0 && a->lda0 >= 2 * ((a->flags & GIMS_LINEAR_CONV3) ? a->k / 9 : a->k0) && a->ldw >= 2 * a->k,
+    GIMS_CHECK_ARG((a->lda0 % 64) == 0 && (a->lda1 % 64) == 0 && (a->ldw % 64) == 0 && a->lda0 >= 2 * a->k0 && a->ldw >= 2 * a->k,
                    "gims_linear(pre-split): SPL32 operands have row pitch >= 2*K, a multiple of 64 elements");
     GIMS_CHECK_ARG((((uintptr_t)a->a0 | (uintptr_t)a->w | (uintptr_t)a->a1) & 127) == 0, "gims_linear(pre-split): SPL32 operands must be 128-byte aligned");
     GIMS_CHECK_ARG(a->lda0 < (1 << 22) && a->lda1 < (1 << 22) && a->ldw < (1 << 22), "gims_linear(pre-split): row pitch too large (32-bit tile-relative offsets)");
@@ -713,10 +684,10 @@ static int x3p_tiles(const gims_linear_args& a) { return 8 * gims::cdiv(gims::cd
 
 // One launch of a pre-split instance.  LDS size, block and grid all follow from the instance's own parameters, and the attribute is set for
 // the kernel that is launched.  WALK: one dispatch round of workgroups that walk the tiles (linear_x3p_guarded_kernel).
-template <int TM, int TN, int WM, int WN, int S, int HI_ONLY = 0, bool WALK = false>
+template <int TM, int TN, int WM, int WN, int S, bool HI_ONLY = false, bool WALK = false>
 static int x3p_launch(const gims_linear_args& a, hipStream_t s) {
   using namespace gims;
-  using T = X3P<TM, TN, WM, WN, S, HI_ONLY == 1>;
+  using T = X3P<TM, TN, WM, WN, S, HI_ONLY>;
   constexpr int block = 64 * WM * WN, lds = T::LDS_BYTES;
   static_assert(T::WAVES * 64 == block && block <= 1024, "one wave per (WM, WN) slot of the tile");
   static_assert(T::MI * WM * 32 == TM && T::NI * WN * 32 == TN, "the waves' 32x32 MFMA tiles cover the workgroup tile");
@@ -758,21 +729,16 @@ extern "C" int gims_linear(const gims_linear_args* a, void* stream) {
   if (big && hi_only && qkv_tile > 0) {
     // one-pass GEMMs with a short K (the Q/K/V projection: K = 256, 8 stages) are all prologue and epilogue: 256 x 128
     // tiles with 64 accumulator registers per wave let TWO workgroups share a CU, one's epilogue under the other's loads
-    return qkv_tile == 2 ? x3p_launch<256, 128, 4, 2, 2, 1>(*a, s) : x3p_launch<256, 128, 4, 2, 3, 1>(*a, s);
+    return qkv_tile == 2 ? x3p_launch<256, 128, 4, 2, 2, true>(*a, s) : x3p_launch<256, 128, 4, 2, 3, true>(*a, s);
   }
   if (big) {
-    if (hi_only) return x3p_launch<256, 256, 4, 2, 4, 1>(*a, s);
+    if (hi_only) return x3p_launch<256, 256, 4, 2, 4, true>(*a, s);
     if (a->guard.stat && x3p_tiles<256, 256>(*a) > device_cus() && guard_walk_enabled())      // guarded: one round of workgroups (see linear_x3p_guarded_kernel)
-      return x3p_launch<256, 256, 4, 2, 2, 0, true>(*a, s);
+      return x3p_launch<256, 256, 4, 2, 2, false, true>(*a, s);
     return x3p_launch<256, 256, 4, 2, 2>(*a, s);
   }
-  if (a->flags & GIMS_LINEAR_CONV3) {
-    if (a->n <= 32) return x3p_launch<128, 32, 4, 1, 2, 4>(*a, s);
-    if (a->n <= 64) return x3p_launch<128, 64, 2, 2, 2, 4>(*a, s);
-    return x3p_launch<128, 128, 2, 2, 2, 4>(*a, s);
-  }
   if (a->n <= 64 && !hi_only && force == 0) {
-    // narrow outputs (the 32- and 64-channel convolutions of the descriptor network, millions of rows): 128 x 32 / 128 x 64
+    // narrow outputs (the 32- and 64-wide layers of the keypoint encoder): 128 x 32 / 128 x 64
     // tiles instead of wasting three quarters / half of a 128-wide one
     return a->n <= 32 ? x3p_launch<128, 32, 4, 1, 2>(*a, s) : x3p_launch<128, 64, 2, 2, 2>(*a, s);
   }
@@ -780,9 +746,9 @@ extern "C" int gims_linear(const gims_linear_args* a, void* stream) {
     // launches that leave most of the chip idle at 128 x 128 (one pair through forward(): 32 ... 96 tiles at 2 x 1024 keypoints): 64 x 64 tiles
     // on four waves -- four times the workgroups, the same K order per output element (bit-identical), and what a launch costs there is
     // the latency of its K loop, not its matrix work
-    return hi_only ? x3p_launch<64, 64, 2, 2, 4, 1>(*a, s) : x3p_launch<64, 64, 2, 2, 3>(*a, s);
+    return hi_only ? x3p_launch<64, 64, 2, 2, 4, true>(*a, s) : x3p_launch<64, 64, 2, 2, 3>(*a, s);
   }
-  if (hi_only) return x3p_launch<128, 128, 2, 2, 4, 1>(*a, s);
+  if (hi_only) return x3p_launch<128, 128, 2, 2, 4, true>(*a, s);
   if (force == 128 || tiles128 > 256)      // more than one tile per CU (or GIMS_X3P_TILE=128): the 4-wave tile, two workgroups per CU
     return x3p_launch<128, 128, 2, 2, 2>(*a, s);
   // small launches are latency-bound (one tile per CU, ~1 us per K step at one wave per SIMD): the same 128 x 128 tile on

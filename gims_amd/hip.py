@@ -29,7 +29,6 @@ GIMS_OK, GIMS_EINVAL, GIMS_EHIP, GIMS_ENUMERIC = _K["GIMS_OK"], _K["GIMS_EINVAL"
 PREC_F32, PREC_BF16X3, PREC_BF16X6 = _K["GIMS_PREC_F32"], _K["GIMS_PREC_BF16X3"], _K["GIMS_PREC_BF16X6"]
 LINEAR_UPPER = _K["GIMS_LINEAR_UPPER"]
 LINEAR_HI_ONLY = _K["GIMS_LINEAR_HI_ONLY"]
-LINEAR_CONV3 = _K["GIMS_LINEAR_CONV3"]
 LINEAR_OUT_F16 = _K["GIMS_LINEAR_OUT_F16"]      # out_bf16 receives IEEE half (saturated) instead of bf16
 ACT_NONE, ACT_RELU = _K["GIMS_ACT_NONE"], _K["GIMS_ACT_RELU"]
 
@@ -180,23 +179,12 @@ def _dev(t: torch.Tensor, dtype=None):
 
 
 def linear_args(a0, w, *, bias=None, a1=None, w_lo=None, residual=None, out=None, out_bf16=None, act=ACT_NONE,
-                precision=PREC_F32, scale=1.0, n=None, spl=False, out_split=None, flags=0, conv=None, m=None, guard=None, range_stat=None):
+                precision=PREC_F32, scale=1.0, n=None, spl=False, out_split=None, flags=0, guard=None, range_stat=None):
     """Build the C struct.
     spl=False: a0/a1 f32 [m,k*]; w f32 [n,K] (PREC_F32) or bf16 hi plane with w_lo (PREC_BF16X3).
     spl=True : a0/a1/w are SPL32 bf16 buffers [rows, 2*k] (see include/gims_hip.h), precision BF16X3.
     out_split: SPL32 bf16 buffer [m, >= 2n] receiving the result split into hi/lo."""
-    m = a0.shape[0] if m is None else m
-    if conv is not None:
-        # 3x3 convolution read straight from an SPL32 NHWC activation: a0 = pixel rows [n*h*w, 2C], a1 = 128 zero bytes,
-        # w = SPL32 [n_out, 2*9C], conv = (h, w, stride), m = output pixels
-        assert spl and precision == PREC_BF16X3 and a1 is not None and m is not None
-        k0 = k = w.shape[1] // 2
-        assert k % 9 == 0 and a0.shape[1] == 2 * (k // 9)
-        a0_lo, a1_lo, w_lo = a0[:, 32:], None, w[:, 32:]
-        args = LinearArgs(_p(a0), a0.stride(0), _p(a1), 0, _p(w), _p(w_lo), w.stride(0), _p(bias), None, _p(out),
-                          out.stride(0) if out is not None else 0, None, 0, m, w.shape[0] if n is None else n, k, k0, act, precision, float(scale),
-                          _p(a0_lo), None, None, None, 0, int(flags) | LINEAR_CONV3, int(conv[0]), int(conv[1]), int(conv[2]), 0)
-        return args
+    m = a0.shape[0]
     if precision == PREC_BF16X6:
         # a0 / w are SPL3 bf16 buffers [rows, 3k] (split_spl3); plain f32 output only
         assert a0.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and a1 is None and not spl
@@ -235,8 +223,8 @@ def _linear_struct(p_a0, lda0, p_a1, lda1, p_w, p_w_lo, w, bias, residual, out, 
                       out.stride(0) if out is not None else 0, _p(out_bf16),
                       out_bf16.stride(0) if out_bf16 is not None else 0, m, n, k, k0, act, precision, float(scale),
                       p_a0_lo, p_a1_lo, _p(out_split), (out_split.data_ptr() + 64) if out_split is not None else None,
-                      out_split.stride(0) if out_split is not None else 0, int(flags), 0, 0, 0, 0,
-                      guard if guard is not None else AttnGuard(), _p(range_stat))
+                      out_split.stride(0) if out_split is not None else 0, int(flags),
+                      guard=guard if guard is not None else AttnGuard(), range_stat=_p(range_stat))
 
 
 def linear_batch(arg_list, dev_args: torch.Tensor, precision=PREC_F32):
@@ -760,75 +748,6 @@ def nn_match(items, flags: int = 0, work=None):
 
 
 # ------------------------------------------------------------------------------------------------ CAR-HyNet ops (NHWC f32)
-def ch_frn_stats(x, weight, eps, scale):
-    n, h, w, c = x.shape
-    _check(load().gims_ch_frn_stats(_p(_dev(x, torch.float32)), n, h * w, c, _p(weight), float(eps), _p(scale), _stream()), "gims_ch_frn_stats")
-    return scale
-
-
-def ch_pool_hw(x, s, b, ph, pw, rowsq=None):
-    n, h, w, c = x.shape
-    _check(load().gims_ch_pool_hw(_p(_dev(x, torch.float32)), n, h, w, c, _p(s), _p(b), _p(ph), _p(pw), _p(rowsq), _stream()), "gims_ch_pool_hw")
-
-
-def ch_frn_from_rows(rowsq, w, weight, eps, scale):
-    n, h, c = rowsq.shape
-    _check(load().gims_ch_frn_from_rows(_p(rowsq), n, h, w, c, _p(weight), float(eps), _p(scale), _stream()), "gims_ch_frn_from_rows")
-    return scale
-
-
-def ch_gates(ph, pw, g, ah, aw, frn_scale=None, frn_bias=None):
-    n, h, c = ph.shape
-    w = pw.shape[1]
-    _check(load().gims_ch_gates(_p(ph), _p(pw), n, h, w, c, _p(g["w1"]), _p(g["b1"]), _p(g["wh"]), _p(g["bh"]), _p(g["ww"]), _p(g["bw"]),
-                                _p(frn_scale), _p(frn_bias), _p(ah), _p(aw), _stream()), "gims_ch_gates")
-
-
-def ch_apply(x, s, b, ah, aw, tau, y=None, y_split=None):
-    """y: f32 NHWC and / or y_split: SPL32 bf16 [n*h*w, >= 2c] pixel rows (the operand layout of the next convolution)."""
-    n, h, w, c = x.shape
-    _check(load().gims_ch_apply(_p(_dev(x, torch.float32)), n, h, w, c, _p(s), _p(b), _p(ah), _p(aw), _p(tau), _p(y), _p(y_split),
-                                y_split.stride(0) if y_split is not None else 0, _stream()), "gims_ch_apply")
-    return y if y is not None else y_split
-
-
-def ch_im2col3(x, stride, out, kpad):
-    n, h, w, c = x.shape
-    _check(load().gims_ch_im2col3(_p(_dev(x, torch.float32)), n, h, w, c, stride, _p(out), out.stride(0), kpad, _stream()), "gims_ch_im2col3")
-    return out
-
-
-def ch_dwconv3(x, wt, bias, y=None, relu6_out=False, res=None, res_scale=1.0, y_split=None):
-    n, h, w, c = x.shape
-    _check(load().gims_ch_dwconv3(_p(_dev(x, torch.float32)), n, h, w, c, _p(wt), _p(bias), 1 if relu6_out else 0, _p(res), float(res_scale),
-                                  _p(y), _p(y_split), y_split.stride(0) if y_split is not None else 0, _stream()), "gims_ch_dwconv3")
-    return y if y is not None else y_split
-
-
-def ch_gate_pw_pw(x, ah, aw, S, z):
-    n, h, w, c = x.shape
-    _check(load().gims_ch_gate_pw_pw(_p(_dev(x, torch.float32)), n, h, w, c, _p(ah), _p(aw), _p(S["w0"]), _p(S["b0"]), _p(S["w1"]), _p(S["b1"]),
-                                     _p(z), _stream()), "gims_ch_gate_pw_pw")
-    return z
-
-
-def ch_input_block(patches, F, tau, out):
-    """patches [n, 32, 32, 3] f32 -> FRN + TLU -> SPL32 im2col rows [n*1024, >= 128] of the first convolution."""
-    n = patches.shape[0]
-    _check(load().gims_ch_input_block(_p(_dev(patches, torch.float32)), n, _p(F["w"]), _p(F["b"]), float(F["eps"]), _p(tau), _p(out), out.stride(0),
-                                      _stream()), "gims_ch_input_block")
-    return out
-
-
-def ch_frn_block(x, F, tau, G=None, y=None, y_split=None):
-    """FRN (+ CoordAtt gates G) + TLU of one layer, one pass over the activation; F: dict(w, b, eps), G: dict(w1, b1, wh, bh, ww, bw)."""
-    n, h, w, c = x.shape
-    arr = (C.c_void_p * 6)(*[G[k].data_ptr() for k in ("w1", "b1", "wh", "bh", "ww", "bw")]) if G is not None else None
-    _check(load().gims_ch_frn_block(_p(_dev(x, torch.float32)), n, h, c, _p(F["w"]), _p(F["b"]), float(F["eps"]), arr, _p(tau), _p(y), _p(y_split),
-                                    y_split.stride(0) if y_split is not None else 0, _stream()), "gims_ch_frn_block")
-    return y if y is not None else y_split
-
-
 def pack_conv3_fragments(w: torch.Tensor) -> torch.Tensor:
     """[cout][cin][3][3] float64/float32 (CPU) -> the bf16 fragment layout of gims_ch_conv_block:
     [step = (ky*3+kx) * cin/16 + ks][nb][plane hi|lo][lane = lh*32 + li][8]."""
@@ -841,21 +760,25 @@ def pack_conv3_fragments(w: torch.Tensor) -> torch.Tensor:
     return torch.stack([hi, lo], dim=2).contiguous()                                   # [step][nb][plane][lane][8]
 
 
+def _gate_table(G):
+    """CoordAtt gate weights G = dict(w1, b1, wh, bh, ww, bw) as the host array of six device pointers of gims_ch_conv_block*; None: no gates."""
+    return (C.c_void_p * 6)(*[G[k].data_ptr() for k in ("w1", "b1", "wh", "bh", "ww", "bw")]) if G is not None else None
+
+
 def ch_conv_block(xs, n, hin, cin, cout, stride, L, F, tau, G=None, y=None, y_split=None):
     """Fused 3x3 convolution + FRN (+ CoordAtt gates G) + TLU, one workgroup per patch (gims_ch_conv_block).
     xs: SPL32 pixel rows [n*hin*hin, >= 2 cin]; L: dict(wp=packed fragments on the device, b=bias)."""
-    arr = (C.c_void_p * 6)(*[G[k].data_ptr() for k in ("w1", "b1", "wh", "bh", "ww", "bw")]) if G is not None else None
-    _check(load().gims_ch_conv_block(_p(xs), xs.stride(0), n, hin, cin, cout, stride, _p(L["wp"]), _p(L["b"]), _p(F["w"]), _p(F["b"]), float(F["eps"]), arr,
+    _check(load().gims_ch_conv_block(_p(xs), xs.stride(0), n, hin, cin, cout, stride, _p(L["wp"]), _p(L["b"]), _p(F["w"]), _p(F["b"]), float(F["eps"]), _gate_table(G),
                                      _p(tau), _p(y), _p(y_split), y_split.stride(0) if y_split is not None else 0, _stream()), "gims_ch_conv_block")
     return y if y is not None else y_split
 
 
 def ch_conv_block_first(patches, F0, tau0, L, F, tau, G, y_split):
-    """Layer 1 in one kernel: patches [n, 32, 32, 3] f32 -> FRN(3) + TLU(3) -> conv 3->32 -> FRN + CoordAtt + TLU -> SPL32 rows."""
+    """Layer 1 in one kernel: patches [n, 32, 32, 3] f32 -> FRN(3) + TLU(3) -> conv 3->32 -> FRN + CoordAtt + TLU -> SPL32 rows.
+    L: dict(wp=fragments of the weights with the input channels zero-padded to 16, b=bias)."""
     n = patches.shape[0]
-    arr = (C.c_void_p * 6)(*[G[k].data_ptr() for k in ("w1", "b1", "wh", "bh", "ww", "bw")]) if G is not None else None
-    _check(load().gims_ch_conv_block_first(_p(_dev(patches, torch.float32)), n, _p(F0["w"]), _p(F0["b"]), float(F0["eps"]), _p(tau0), _p(L["wp16"]), _p(L["b"]),
-                                           _p(F["w"]), _p(F["b"]), float(F["eps"]), arr, _p(tau), None, _p(y_split), y_split.stride(0), _stream()),
+    _check(load().gims_ch_conv_block_first(_p(_dev(patches, torch.float32)), n, _p(F0["w"]), _p(F0["b"]), float(F0["eps"]), _p(tau0), _p(L["wp"]), _p(L["b"]),
+                                           _p(F["w"]), _p(F["b"]), float(F["eps"]), _gate_table(G), _p(tau), None, _p(y_split), y_split.stride(0), _stream()),
            "gims_ch_conv_block_first")
     return y_split
 

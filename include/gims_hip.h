@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GIMS_ABI_VERSION 3   /* 3: one entry point per operation (the positional / flag-less / scalar spellings of 2 and its entry points without a caller are gone); no struct changed */
+#define GIMS_ABI_VERSION 4   /* 4: the superseded CAR-HyNet entry points and the 3x3-convolution gather mode of gims_linear are gone; gims_linear_args keeps its size, conv_* became reserved0 / probe_delay */
 
 #define GIMS_OK 0
 #define GIMS_EINVAL (-1)   /* bad argument (shape / alignment / null pointer) */
@@ -104,12 +104,8 @@ typedef struct gims_linear_args {
   uint16_t* out_hi; uint16_t* out_lo; int64_t ld_split;
   /* GIMS_LINEAR_UPPER: symmetric product (A == W): skip output tiles that lie entirely below the diagonal */
   int32_t flags;
-  /* GIMS_LINEAR_CONV3 (pre-split operands only): the GEMM is a 3x3 convolution (pad 1) over an NHWC activation held in
-   * the SPL32 layout -- a0 = [patches * conv_h * conv_w][2C] with pitch lda0, C % 32 == 0, k = 9 C, W columns ordered
-   * (ky*3+kx)*C + c.  Output row r is output pixel (patch, yo, xo) of the [(conv_h-1)/stride+1] x [(conv_w-1)/stride+1]
-   * grid, and K block (tap, c0..c0+31) of its operand row is read straight from input pixel
-   * (yo*stride + ky - 1, xo*stride + kx - 1), or from the 128 zero bytes at a1 when that lies outside: no im2col buffer. */
-  int32_t conv_h, conv_w, conv_stride, conv_reserved;
+  int32_t reserved0[3];                /* must be 0 (they keep guard / range_stat at their kernel-argument offsets) */
+  int32_t probe_delay;                 /* tools/gemm_probe.py only (diagnostic flag 0x1000); 0 otherwise */
   gims_attn_guard guard;               /* pre-split operands (a0_lo != NULL) only: the launch is a no-op unless the guard fires; zero = always run */
   /* pre-split operands with GIMS_LINEAR_OUT_F16 only: the launch also reports max |value| of what it stores into out_bf16, per block of
    * 256 output columns (Q | K | V of the projection in front of a GIMS_ATTN_F16 launch): range_stat[b] = max(range_stat[b], float bits of
@@ -123,7 +119,7 @@ typedef struct gims_linear_args {
 #define GIMS_LINEAR_HI_ONLY 2
   /* (flag value 4 was GIMS_LINEAR_A1_HI_ONLY until round 5: the hi-planes-only product for the second A segment -- the attention message in MLP0 --
    * measured +1.5 % pairs/s at 6.4e-5 of the 1e-4 score bar and was removed) */
-#define GIMS_LINEAR_CONV3 8
+  /* (flag value 8 was a 3x3-convolution gather mode until ABI 3; gims_ch_conv_block superseded it) */
   /* GIMS_LINEAR_OUT_F16: out_bf16 receives IEEE half instead of bf16 (round to nearest even, saturated to +-65504 so that no
    * infinity is ever stored) -- the Q/K/V projection in front of the GIMS_ATTN_F16 attention kernels */
 #define GIMS_LINEAR_OUT_F16 16
@@ -579,46 +575,15 @@ int gims_train_loss_grad(const gims_loss_pair* dev_pairs, int32_t n_pairs, const
                          float pos_weight, float neg_weight, float* const* dev_dz_ptrs /* DEVICE array */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * CAR-HyNet patch descriptor: the non-GEMM layers of carhynet/models.py:311-399.  Activations are NHWC
- * f32 ([patch][y][x][channel]); the 3x3 and 8x8 convolutions are gims_ch_im2col3 / a reshape + gims_linear (split-bf16x3),
- * the 1x1 convolutions gims_linear directly.  BatchNorm (eval) is folded into weights / biases by the caller.
- *   gims_ch_frn_stats: scale[p][c] = weight[c] * rsqrt(mean over the hw pixels of x^2 + eps)          (FRN, models.py:67-82)
- *   gims_ch_pool_hw:   ph[p][y][c] = mean_x(x*s+b), pw[p][x][c] = mean_y(x*s+b); s [p][c], b [c] may be NULL  (CoordAtt 141-143)
- *   gims_ch_gates:     CoordAtt's conv1(+BN folded)+h_swish over the h+w pooled rows, then conv_h / conv_w + sigmoid (144-151);
- *                      w1 [8][c], b1 [8], wh / ww [c][8], bh / bw [c];  h + w <= 64
- *   gims_ch_apply:     y = max((x*s[p][c] + b[c]) * ah[p][y][c] * aw[p][x][c], tau[c]); s/b, ah/aw, tau each optional (78-84,152,107)
- *   gims_ch_im2col3:   3x3 neighbourhoods (pad 1, stride 1|2) as SPL32 rows: column (ky*3+kx)*c + ch, zero-padded to kpad
- *   gims_ch_dwconv3:   depthwise 3x3 (pad 1) with wt [9][c], bias [c] (BatchNorm folded), optional ReLU6, optional
- *                      y += res_scale * res                                                            (172-180, 207, 220-233)
- *   gims_ch_l2norm:    y = x / sqrt(sum_c x^2 + eps) per row                                           (desc_l2norm, 9-21)
+ * CAR-HyNet patch descriptor: carhynet/models.py:311-399 in five entry points.  Every block runs as one workgroup per
+ * patch with the patch's activation resident in LDS; between blocks an activation is either NHWC f32 ([patch][y][x][channel]) or SPL32
+ * split-bf16 pixel rows (the operand layout of the next convolution).  BatchNorm (eval) is folded into weights / biases by the caller.
+ *   gims_ch_conv_block_first: layer 1     -- FRN(3) + TLU(3), 3x3 convolution 3 -> 32, FRN + CoordAtt + TLU         (models.py:315-322)
+ *   gims_ch_conv_block:       layers 2..6 -- 3x3 convolution (stride 1 | 2), FRN (+ CoordAtt) + TLU                 (324-355)
+ *   gims_ch_sandglass:        x + SandGlass(x) behind layers 2 and 4                                                (182-235, 383-389)
+ *   (layer 7, the 8x8 convolution, is gims_linear (split-bf16x3) on the flattened [patch][8*8*128] SPL32 rows of layer 6)
+ *   gims_ch_l2norm:           y = x / sqrt(sum_c x^2 + eps) per row                                                 (desc_l2norm, 9-21)
  */
-int gims_ch_frn_stats(const float* x, int64_t patches, int32_t hw, int32_t c, const float* weight, float eps, float* scale, void* stream);
-int gims_ch_pool_hw(const float* x, int64_t patches, int32_t h, int32_t w, int32_t c, const float* s, const float* b, float* ph, float* pw,
-                    float* rowsq /* [p][y][c] sums of x^2 over x, may be NULL */, void* stream);
-/* FRN scale from those row sums (one pass over the activation serves the statistics and both pools) */
-int gims_ch_frn_from_rows(const float* rowsq, int64_t patches, int32_t h, int32_t w, int32_t c, const float* weight, float eps, float* scale, void* stream);
-int gims_ch_gates(const float* ph, const float* pw, int64_t patches, int32_t h, int32_t w, int32_t c, const float* w1, const float* b1,
-                  const float* wh, const float* bh, const float* ww, const float* bw,
-                  const float* frn_scale /* [p][c] */, const float* frn_bias /* [c]; both NULL: the pools are used as they are */, float* ah, float* aw,
-                  void* stream);
-int gims_ch_apply(const float* x, int64_t patches, int32_t h, int32_t w, int32_t c, const float* s, const float* b, const float* ah, const float* aw,
-                  const float* tau, float* y /* may be NULL */, uint16_t* y_split /* SPL32 pixel rows, may be NULL */, int64_t ld_split, void* stream);
-int gims_ch_im2col3(const float* x, int64_t patches, int32_t h, int32_t w, int32_t c, int32_t stride, uint16_t* out, int64_t ld, int32_t kpad, void* stream);
-int gims_ch_dwconv3(const float* x, int64_t patches, int32_t h, int32_t w, int32_t c, const float* wt, const float* bias, int32_t relu6_out,
-                    const float* res, float res_scale, float* y /* may be NULL */, uint16_t* y_split /* may be NULL */, int64_t ld_split, void* stream);
-/* SandGlass middle in one pass per pixel: z = ReLU6(w1 (w0 (x * a_w * a_h) + b0) + b1); w0 [16][c], w1 [c][16] (BatchNorm folded), c = 32 | 64 */
-int gims_ch_gate_pw_pw(const float* x, int64_t patches, int32_t h, int32_t w, int32_t c, const float* ah, const float* aw, const float* w0,
-                       const float* b0, const float* w1, const float* b1, float* z, void* stream);
-/* Input stage (models.py:316-317): patches [n][32][32][3] f32 -> FRN(3) + TLU(3) -> the 3x3 neighbourhoods as SPL32 rows
- * [n*1024][pitch ld >= 128] for the first convolution's GEMM: column (ky*3+kx)*4 + c, K = 36 zero-padded to 64 (channel 3 is zero). */
-int gims_ch_input_block(const float* patches, int64_t n, const float* frn_weight /* [>=3] */, const float* frn_bias, float eps, const float* tau,
-                        uint16_t* out, int64_t ld, void* stream);
-/* FRN (+ CoordAtt) + TLU of one layer in one pass over the activation (32x32x32, 16x16x64 or 8x8x128), one workgroup per patch with
- * the raw convolution output resident in LDS: y = max((x s + b) a_w a_h, tau), s = frn_weight * rsqrt(mean x^2 + eps) per (patch,
- * channel), gates as in gims_ch_gates (gate_w: HOST array of 6 device pointers w1 [8][c] (+BN folded), b1, wh [c][8], bh, ww, bw; NULL: no
- * CoordAtt).  Output f32 NHWC and / or SPL32 split-bf16 pixel rows. */
-int gims_ch_frn_block(const float* x, int64_t patches, int32_t hw, int32_t c, const float* frn_weight, const float* frn_bias, float eps,
-                      const float* const* gate_w, const float* tau, float* y, uint16_t* y_split, int64_t ld_split, void* stream);
 /* x + SandGlass(x) (models.py:182-235 with the outer residual of 383-389: 2x + conv stack) for 32x32x32 or 16x16x64 activations,
  * one workgroup per patch with the activation resident in LDS; w: HOST array of 14 device pointers (BatchNorm folded):
  * dw0 [9][c], dw0 bias [c], CoordAtt w1 [8][c], b1 [8], wh [c][8], bh [c], ww [c][8], bw [c], pw0 [16][c], pw0 bias [16],
@@ -627,8 +592,11 @@ int gims_ch_sandglass(const float* x, int64_t patches, int32_t hw, int32_t c, co
 /* 3x3 convolution (pad 1, stride 1 | 2) + bias + FRN (+ CoordAtt) + TLU of one CAR-HyNet layer in ONE kernel, one workgroup per patch
  * (models.py:325-360: layer2 .. layer6).  x_split: the layer's input as SPL32 split-bf16 pixel rows [patches * hin * hin][pitch ldx >= 2 cin];
  * it is read once into LDS (zero border) and the convolution runs there as an implicit GEMM on the matrix cores (split-bf16x3: hi*hi +
- * hi*lo + lo*hi, like gims_linear); the raw output never leaves the chip: FRN statistic, CoordAtt gates (gate_w as in gims_ch_frn_block,
- * NULL: none) and TLU are applied to the accumulators and the result leaves as f32 NHWC (y) and / or SPL32 pixel rows (y_split).
+ * hi*lo + lo*hi, like gims_linear); the raw output never leaves the chip:  y = max((x s + b) a_w a_h, tau)  with the FRN scale
+ * s = frn_weight * rsqrt(mean x^2 + eps) per (patch, channel) and CoordAtt's gates a_h [y][c], a_w [x][c] (models.py:139-153: conv1 + h_swish
+ * over the h + w pooled rows of the FRN output, then conv_h / conv_w + sigmoid) is applied to the accumulators, and the result leaves as f32
+ * NHWC (y) and / or SPL32 pixel rows (y_split).  gate_w: HOST array of 6 device pointers w1 [8][c] (BatchNorm folded), b1 [8], wh [c][8],
+ * bh [c], ww [c][8], bw [c]; NULL: no CoordAtt.
  * w_packed: the weights [cout][cin][3][3] in MFMA fragment order, bf16: [step = (ky*3+kx) * cin/16 + ks][nb = cout/32][plane hi|lo][lane 64][8]
  * with lane = lh*32 + li holding out channel nb*32 + li, input channels 16 ks + 8 lh + (0..7) of tap (ky, kx).
  * Geometries: (hin, cin, cout, stride) = (32,32,32,1), (32,32,64,2), (16,64,64,1), (16,64,128,2), (8,128,128,1). */
@@ -637,7 +605,7 @@ int gims_ch_conv_block(const uint16_t* x_split, int64_t ldx, int64_t patches, in
                        const float* const* gate_w, const float* tau, float* y, uint16_t* y_split, int64_t ld_split, void* stream);
 /* The FIRST layer the same way (models.py:316-323): patches [n][32][32][3] f32 -> FRN(3) + TLU(3) -> 3x3 convolution 3 -> 32 (weights packed like
  * above with the input channels zero-padded to 16) -> FRN(32) + CoordAtt + TLU, one workgroup per patch, nothing but the patch read and the result
- * written.  Replaces gims_ch_input_block + gims_linear + gims_ch_frn_block for this layer. */
+ * written; gate_w as above. */
 int gims_ch_conv_block_first(const float* patches, int64_t n, const float* frn0_weight, const float* frn0_bias, float eps0, const float* tau0,
                              const uint16_t* w_packed, const float* bias, const float* frn_weight, const float* frn_bias, float eps,
                              const float* const* gate_w, const float* tau, float* y, uint16_t* y_split, int64_t ld_split, void* stream);

@@ -55,7 +55,7 @@ def main():
         for fl in [0, 0x200, 0x100, 0x200 | 0x400, 0x200 | 0x800] + variants + [0x200 | 0x400 | 0x2000, 0x200 | 0x2000]:
             a = mk()
             a.flags |= fl & ~0xff
-            a.conv_reserved = fl & 0xff
+            a.probe_delay = fl & 0xff
             for _ in range(10):
                 lib.gims_linear(C.byref(a), st)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
