@@ -7,6 +7,8 @@
 //   hypotheses  one workgroup per VF_HB hypotheses: VF_HB lanes solve a model each into LDS, then every thread scores one correspondence per
 //               tile (one coalesced 16-byte load) against all VF_HB models (LDS broadcast reads), counters in registers;
 //   finish      one workgroup per set: best hypothesis, stage 2, mask, record, corner error.
+// A set may ask for the fundamental-matrix model instead (gims_verify_set.model): the same three launches, the model a per-set branch that
+// is uniform over the workgroup.  The homography branch is the code it was before the second model existed.
 #include "common.h"
 #include "eval_geom.h"
 
@@ -19,7 +21,7 @@ namespace gims {
 
 struct VerifyDev {
   const float* kp0; const float* kp1; const int64_t* matches0;
-  int n0, n1, height, width, has_ref;
+  int n0, n1, height, width, has_ref, model;
   float href[9];
   uint8_t* inlier; float* record; float* hom;
   // workspace
@@ -33,6 +35,8 @@ struct VerifyDev {
 enum { VF_NVALID = 0, VF_OK = 1, VF_NINLIERS = 2, VF_BEST_HYP = 3, VF_BEST_HYP_INLIERS = 4, VF_LO_ROUNDS = 5, VF_ERR_CORNER = 6, VF_RESERVED = 7 };
 
 constexpr int VF_HB = 16;          // hypotheses per workgroup of the scoring kernel
+constexpr int VF_ACC = 45;         // widest row of per-wave partial sums: the 45 sums of the fundamental refit (the homography's uses 44)
+constexpr int VF_JACOBI_SWEEPS = 12;
 
 // ---------------------------------------------------------------------------------------------- gather
 // one workgroup per set: ascending list of the correspondences (chunks of 1024 rows, inclusive scan in LDS, as eval_counts_kernel does it);
@@ -86,6 +90,181 @@ __device__ bool homography4_dense(const float4* __restrict__ corr, const int (&i
   return fin;
 }
 
+// ---------------------------------------------------------------------------------------------- fundamental matrix: the minimal model
+// eight distinct indices from the stream of ransac_sample (eval_geom.h): its four, then four more
+__device__ void ransac_sample8(uint64_t seed, int hyp, int k, int (&idx)[8]) {
+  uint64_t state = seed ^ ((uint64_t)hyp * 0xD1342543DE82EF95ull);
+  int n = 0;
+  while (n < 8) {
+    state = splitmix(state);
+    const int c = (int)(state % (uint64_t)k);
+    bool dup = false;
+    for (int q = 0; q < n; ++q) dup = dup || idx[q] == c;
+    if (!dup) idx[n++] = c;
+  }
+}
+
+// inlier(F, x, y, u, v) of the specification: squared Sampson distance <= thresh^2, without the division
+__device__ __forceinline__ bool sampson_in(const double (&F)[9], double x, double y, double u, double v, double t2) {
+  const double a0 = F[0] * x + F[1] * y + F[2], a1 = F[3] * x + F[4] * y + F[5], a2 = F[6] * x + F[7] * y + F[8];
+  const double g0 = F[0] * u + F[3] * v + F[6], g1 = F[1] * u + F[4] * v + F[7];
+  const double e = u * a0 + v * a1 + a2, den = a0 * a0 + a1 * a1 + g0 * g0 + g1 * g1;
+  return den > 0.0 && e * e <= t2 * den;
+}
+
+// unit(F): false when the norm is 0 or anything is not finite
+__device__ bool vf_unit(double (&F)[9]) {
+  double n2 = 0.0;
+  for (int c = 0; c < 9; ++c) n2 += F[c] * F[c];
+  const double n = sqrt(n2);
+  if (!(n > 0.0) || !isfinite(n)) return false;
+  bool fin = true;
+  for (int c = 0; c < 9; ++c) { F[c] = F[c] / n; fin = fin && isfinite(F[c]); }
+  return fin;
+}
+
+// denormalise: F = T1^T Fn T0 for the similarities (centroid, scale) of the two images
+__device__ void vf_denormalise(const double (&Fn)[9], double cx, double cy, double s0, double cu, double cv, double s1, double (&F)[9]) {
+  double M[9];
+  for (int r = 0; r < 3; ++r) {
+    M[3 * r] = Fn[3 * r] * s0;
+    M[3 * r + 1] = Fn[3 * r + 1] * s0;
+    M[3 * r + 2] = Fn[3 * r + 2] - s0 * (Fn[3 * r] * cx + Fn[3 * r + 1] * cy);
+  }
+  for (int c = 0; c < 3; ++c) {
+    F[c] = s1 * M[c];
+    F[3 + c] = s1 * M[3 + c];
+    F[6 + c] = M[6 + c] - s1 * (cu * M[c] + cv * M[3 + c]);
+  }
+}
+
+// null vector of the 8 x 9 system by Gauss-Jordan elimination with complete pivoting; the column without a pivot is the free variable.
+// The array is indexed by the pivot search, so it lives in LDS: entry (r, c) at A[(9 r + c) ld]
+__device__ bool vf_null8x9(double* A, int ld, double (&f)[9]) {
+  unsigned rused = 0u, cused = 0u, prow = 0u, pcol = 0u;      // prow, pcol: four bits per elimination step
+#pragma unroll 1
+  for (int s = 0; s < 8; ++s) {
+    int pr = -1, pc = -1;
+    double best = 0.0;
+#pragma unroll 1
+    for (int r = 0; r < 8; ++r) {
+      if ((rused >> r) & 1u) continue;
+      for (int c = 0; c < 9; ++c) {
+        if ((cused >> c) & 1u) continue;
+        const double a = fabs(A[(9 * r + c) * ld]);
+        if (a > best) { best = a; pr = r; pc = c; }
+      }
+    }
+    if (pr < 0 || !isfinite(best)) return false;
+    rused |= 1u << pr;
+    cused |= 1u << pc;
+    prow |= (unsigned)pr << (4 * s);
+    pcol |= (unsigned)pc << (4 * s);
+    const double piv = A[(9 * pr + pc) * ld];
+#pragma unroll 1
+    for (int r = 0; r < 8; ++r) {
+      if (r == pr) continue;
+      const double m = A[(9 * r + pc) * ld] / piv;
+      for (int c = 0; c < 9; ++c) A[(9 * r + c) * ld] -= m * A[(9 * pr + c) * ld];
+    }
+  }
+  const int fc = __ffs((int)(~cused & 0x1ffu)) - 1;          // eight of nine bits are set: 0 <= fc <= 8
+  bool fin = true;
+#pragma unroll
+  for (int c = 0; c < 9; ++c) f[c] = 1.0;                    // the free variable keeps this value
+  for (int s = 0; s < 8; ++s) {
+    const int pr = (prow >> (4 * s)) & 15, pc = (pcol >> (4 * s)) & 15;
+    const double val = -A[(9 * pr + fc) * ld] / A[(9 * pr + pc) * ld];
+    fin = fin && isfinite(val);
+#pragma unroll
+    for (int c = 0; c < 9; ++c) f[c] = c == pc ? val : f[c];
+  }
+  return fin;
+}
+
+// F_h of the specification through eight correspondences of the dense array; A: 72 doubles of LDS at stride ld (vf_null8x9)
+__device__ bool fundamental8_dense(const float4* __restrict__ corr, const int (&idx)[8], double* A, int ld, double (&F)[9]) {
+  double cx = 0.0, cy = 0.0, cu = 0.0, cv = 0.0;
+#pragma unroll 1
+  for (int k = 0; k < 8; ++k) {
+    const float4 c = corr[idx[k]];
+    cx += (double)c.x; cy += (double)c.y; cu += (double)c.z; cv += (double)c.w;
+  }
+  cx = cx / 8.0; cy = cy / 8.0; cu = cu / 8.0; cv = cv / 8.0;
+  double m0 = 0.0, m1 = 0.0;
+#pragma unroll 1
+  for (int k = 0; k < 8; ++k) {
+    const float4 c = corr[idx[k]];
+    const double px = c.x, py = c.y, pu = c.z, pv = c.w;
+    m0 += sqrt((px - cx) * (px - cx) + (py - cy) * (py - cy));
+    m1 += sqrt((pu - cu) * (pu - cu) + (pv - cv) * (pv - cv));
+  }
+  m0 = m0 / 8.0; m1 = m1 / 8.0;
+  const double s0 = m0 == 0.0 ? 1.0 : sqrt(2.0) / m0, s1 = m1 == 0.0 ? 1.0 : sqrt(2.0) / m1;
+#pragma unroll 1
+  for (int k = 0; k < 8; ++k) {
+    const float4 c = corr[idx[k]];
+    const double x = ((double)c.x - cx) * s0, y = ((double)c.y - cy) * s0, u = ((double)c.z - cu) * s1, v = ((double)c.w - cv) * s1;
+    const double row[9] = {u * x, u * y, u, v * x, v * y, v, x, y, 1.0};
+#pragma unroll
+    for (int q = 0; q < 9; ++q) A[(9 * k + q) * ld] = row[q];
+  }
+  double fn[9];
+  if (!vf_null8x9(A, ld, fn)) return false;
+  vf_denormalise(fn, cx, cy, s0, cu, cv, s1, F);
+  return vf_unit(F);
+}
+
+// the hypotheses kernel's body for a set with the fundamental model: as the homography's below, eight points per model, Sampson scoring
+__device__ void vf_hyp_fundamental(const VerifyDev& e, int K, int h0, uint64_t seed, int iters, double t2, double (*s_H)[10], int* s_ok,
+                                   int (*s_cnt)[VF_HB]) {
+  __shared__ double s_A[72][VF_HB];                       // the elimination arrays of the VF_HB solving lanes, lane-minor
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  if (K < 8) {                                             // the same for every thread of the workgroup
+    if (t < VF_HB && h0 + t < iters) e.hypcount[h0 + t] = -1;
+    return;
+  }
+  if (t < VF_HB) {
+    double F[9];
+    bool ok = false;
+    if (h0 + t < iters) {
+      int idx[8];
+      ransac_sample8(seed, h0 + t, K, idx);
+      ok = fundamental8_dense(e.corr, idx, &s_A[0][t], VF_HB, F);
+    }
+    for (int c = 0; c < 9; ++c) s_H[t][c] = ok ? F[c] : 0.0;
+    s_ok[t] = ok ? 1 : 0;
+  }
+  __syncthreads();
+  int cnt[VF_HB];
+#pragma unroll
+  for (int b = 0; b < VF_HB; ++b) cnt[b] = 0;
+  for (int p0 = 0; p0 < K; p0 += 256) {                  // K is the same for the whole workgroup
+    const int p = p0 + t;
+    const bool have = p < K;
+    const float4 c = e.corr[have ? p : 0];
+    const double x = c.x, y = c.y, u = c.z, v = c.w;
+#pragma unroll
+    for (int b = 0; b < VF_HB; ++b) {
+      double F[9];
+#pragma unroll
+      for (int q = 0; q < 9; ++q) F[q] = s_H[b][q];
+      cnt[b] += have && sampson_in(F, x, y, u, v, t2) ? 1 : 0;
+    }
+    __syncthreads();                                       // keeps the models in LDS, as in the homography's loop
+  }
+#pragma unroll
+  for (int b = 0; b < VF_HB; ++b) {
+    int s = cnt[b];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (lane == 0) s_cnt[wave][b] = s;
+  }
+  __syncthreads();
+  if (t < VF_HB && h0 + t < iters)
+    e.hypcount[h0 + t] = s_ok[t] ? s_cnt[0][t] + s_cnt[1][t] + s_cnt[2][t] + s_cnt[3][t] : -1;
+}
+
 // ---------------------------------------------------------------------------------------------- hypotheses
 // one workgroup per VF_HB hypotheses of one set.  The first VF_HB lanes solve one model each (their elimination array is indexed by the
 // pivot search and lives in scratch); the scoring loop keeps VF_HB counters in registers and reads the models at wave-uniform LDS addresses.
@@ -97,6 +276,10 @@ __global__ __launch_bounds__(256) void verify_hyp_kernel(const VerifyDev* __rest
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int K = e.nvalid[0];
   const int h0 = blockIdx.x * VF_HB;
+  if (e.model == GIMS_VERIFY_MODEL_FUNDAMENTAL) {           // per set: the same for every thread of the workgroup
+    vf_hyp_fundamental(e, K, h0, seed, iters, t2, s_H, s_ok, s_cnt);
+    return;
+  }
   if (K < 4) {                                             // the same for every thread of the workgroup
     if (t < VF_HB && h0 + t < iters) e.hypcount[h0 + t] = -1;
     return;
@@ -148,7 +331,7 @@ __global__ __launch_bounds__(256) void verify_hyp_kernel(const VerifyDev* __rest
 // the per-thread sums of a sweep over the correspondences, reduced across each wave into one LDS row per wave; after the caller's barrier
 // thread 0 adds the 16 rows in wave order (vf_total)
 template <int N>
-__device__ __forceinline__ void vf_partials(const double (&acc)[N], double (*s_acc)[44]) {
+__device__ __forceinline__ void vf_partials(const double (&acc)[N], double (*s_acc)[VF_ACC]) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int c = 0; c < N; ++c) {
     double s = acc[c];
@@ -156,7 +339,7 @@ __device__ __forceinline__ void vf_partials(const double (&acc)[N], double (*s_a
     if (lane == 0) s_acc[wave][c] = s;
   }
 }
-__device__ __forceinline__ double vf_total(const double (*s_acc)[44], int c) {
+__device__ __forceinline__ double vf_total(const double (*s_acc)[VF_ACC], int c) {
   double s = 0.0;
   for (int w = 0; w < 16; ++w) s += s_acc[w][c];
   return s;
@@ -170,7 +353,7 @@ __device__ __forceinline__ void vf_normal_add(double (&acc)[44], double x, doubl
   for (int a = 0; a < 8; ++a) acc[36 + a] += r0[a] * u + r1[a] * v;
 }
 // thread 0: the reduced normal equations -> solve8; true and h[0..7] when the solve succeeds with finite entries
-__device__ bool vf_normal_solve(const double (*s_acc)[44], double (&h)[8]) {
+__device__ bool vf_normal_solve(const double (*s_acc)[VF_ACC], double (&h)[8]) {
   double A[8][9];
   int q = 0;
   for (int a = 0; a < 8; ++a)
@@ -186,6 +369,261 @@ __device__ bool vf_normal_solve(const double (*s_acc)[44], double (&h)[8]) {
   return fin;
 }
 
+// ---------------------------------------------------------------------------------------------- fundamental matrix: refit and rank 2
+// jacobi(S) of the specification on an n x n symmetric matrix held in LDS (leading dimension 9): the eigenvector of the smallest
+// eigenvalue.  One thread; S is destroyed, V receives all eigenvectors.
+__device__ void vf_jacobi(double (*S)[9], double (*V)[9], int n, double* vec) {
+  for (int r = 0; r < n; ++r)
+    for (int c = 0; c < n; ++c) V[r][c] = r == c ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < VF_JACOBI_SWEEPS; ++sweep)
+    for (int p = 0; p < n - 1; ++p)
+      for (int q = p + 1; q < n; ++q) {
+        const double apq = S[p][q];
+        if (apq == 0.0) continue;
+        const double d = S[q][q] - S[p][p], b = 2.0 * apq;
+        const double tn = (d >= 0.0 ? b : -b) / (fabs(d) + hypot(d, b));
+        const double cs = 1.0 / sqrt(tn * tn + 1.0), sn = tn * cs;
+        for (int k = 0; k < n; ++k) {
+          const double akp = S[k][p], akq = S[k][q];
+          S[k][p] = cs * akp - sn * akq;
+          S[k][q] = sn * akp + cs * akq;
+        }
+        for (int k = 0; k < n; ++k) {
+          const double apk = S[p][k], aqk = S[q][k];
+          S[p][k] = cs * apk - sn * aqk;
+          S[q][k] = sn * apk + cs * aqk;
+        }
+        S[p][q] = 0.0;
+        S[q][p] = 0.0;
+        for (int k = 0; k < n; ++k) {
+          const double vkp = V[k][p], vkq = V[k][q];
+          V[k][p] = cs * vkp - sn * vkq;
+          V[k][q] = sn * vkp + cs * vkq;
+        }
+      }
+  int m = 0;
+  for (int k = 1; k < n; ++k)
+    if (S[k][k] < S[m][m]) m = k;
+  for (int k = 0; k < n; ++k) vec[k] = V[k][m];
+}
+
+// rank2(F) of the specification (one thread; S, V: the LDS of vf_jacobi)
+__device__ void vf_rank2(double (&F)[9], double (*S)[9], double (*V)[9]) {
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) S[i][j] = F[i] * F[j] + F[3 + i] * F[3 + j] + F[6 + i] * F[6 + j];
+  double v[3];
+  vf_jacobi(S, V, 3, v);
+  double G[9];
+  for (int r = 0; r < 3; ++r) {
+    const double fv = F[3 * r] * v[0] + F[3 * r + 1] * v[1] + F[3 * r + 2] * v[2];
+    for (int c = 0; c < 3; ++c) G[3 * r + c] = F[3 * r + c] - fv * v[c];
+  }
+  if (vf_unit(G))
+    for (int c = 0; c < 9; ++c) F[c] = G[c];
+}
+
+// the 45 sums a_i a_j (i <= j) that one normalised correspondence adds
+__device__ __forceinline__ void vf_epipolar_add(double (&acc)[45], double x, double y, double u, double v) {
+  const double a[9] = {u * x, u * y, u, v * x, v * y, v, x, y, 1.0};
+  int q = 0;
+  for (int i = 0; i < 9; ++i)
+    for (int j = i; j < 9; ++j) acc[q++] += a[i] * a[j];
+}
+
+// the finish kernel's body for a set with the fundamental model, entered by the whole workgroup behind the barrier that publishes s_best.
+// The rule on barriers is the kernel's: every decision is thread 0's, stored in LDS and read by all threads after the next barrier.
+__device__ void vf_finish_fundamental(const VerifyDev& e, int K, int bc, int bh, uint64_t seed, int lo_iters, double t2, double (*s_acc)[VF_ACC]) {
+  __shared__ double f_F[9];           // the accepted model
+  __shared__ double f_Fn[9];          // the candidate of the current round
+  __shared__ double f_norm[6];        // cx, cy, cu, cv, scale0, scale1
+  __shared__ double f_S[9][9], f_V[9][9];
+  __shared__ double f_nprev;          // |I_{l-1}|
+  __shared__ int f_ok, f_stop, f_rounds;
+  const int t = threadIdx.x;
+  if (t == 0) {
+    f_ok = 0; f_stop = 0; f_rounds = 0;
+    if (bc >= 0 && K >= 8) {
+      int idx[8];
+      ransac_sample8(seed, bh, K, idx);
+      double F[9];
+      if (fundamental8_dense(e.corr, idx, &f_S[0][0], 1, F)) {
+        for (int c = 0; c < 9; ++c) f_F[c] = F[c];
+        f_ok = 1;
+      }
+    }
+  }
+  __syncthreads();
+  if (!f_ok) {
+    if (t == 0) {
+      for (int c = 0; c < 8; ++c) e.record[c] = 0.f;
+      e.record[VF_NVALID] = (float)K;
+      e.record[VF_ERR_CORNER] = -1.f;
+      for (int c = 0; c < 9; ++c) e.hom[c] = 0.f;
+    }
+    return;
+  }
+  double F[9];
+  for (int c = 0; c < 9; ++c) F[c] = f_F[c];
+  if (lo_iters > 0) {
+    {  // |I_0|
+      double a[1] = {0.0};
+      for (int p = t; p < K; p += 1024) {
+        const float4 c4 = e.corr[p];
+        a[0] += sampson_in(F, c4.x, c4.y, c4.z, c4.w, t2) ? 1.0 : 0.0;
+      }
+      vf_partials(a, s_acc);
+      __syncthreads();
+      if (t == 0) f_nprev = vf_total(s_acc, 0);
+      __syncthreads();
+    }
+    for (int l = 1; l <= lo_iters; ++l) {
+      // (a) centroids of the inliers of the accepted model
+      {
+        double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int p = t; p < K; p += 1024) {
+          const float4 c4 = e.corr[p];
+          const double x = c4.x, y = c4.y, u = c4.z, v = c4.w;
+          if (sampson_in(F, x, y, u, v, t2)) { a[0] += 1.0; a[1] += x; a[2] += y; a[3] += u; a[4] += v; }
+        }
+        vf_partials(a, s_acc);
+      }
+      __syncthreads();
+      if (t == 0) {
+        const double n = vf_total(s_acc, 0);
+        f_stop = n < 8.0 ? 1 : 0;
+        if (n >= 8.0)
+          for (int c = 0; c < 4; ++c) f_norm[c] = vf_total(s_acc, 1 + c) / n;
+      }
+      __syncthreads();
+      if (f_stop) break;
+      const double cx = f_norm[0], cy = f_norm[1], cu = f_norm[2], cv = f_norm[3];
+      // (b) mean distances to the centroids
+      {
+        double a[3] = {0.0, 0.0, 0.0};
+        for (int p = t; p < K; p += 1024) {
+          const float4 c4 = e.corr[p];
+          const double x = c4.x, y = c4.y, u = c4.z, v = c4.w;
+          if (sampson_in(F, x, y, u, v, t2)) {
+            a[0] += 1.0;
+            a[1] += sqrt((x - cx) * (x - cx) + (y - cy) * (y - cy));
+            a[2] += sqrt((u - cu) * (u - cu) + (v - cv) * (v - cv));
+          }
+        }
+        vf_partials(a, s_acc);
+      }
+      __syncthreads();
+      if (t == 0) {
+        const double n = vf_total(s_acc, 0), m0 = vf_total(s_acc, 1) / n, m1 = vf_total(s_acc, 2) / n;
+        f_norm[4] = m0 == 0.0 ? 1.0 : sqrt(2.0) / m0;
+        f_norm[5] = m1 == 0.0 ? 1.0 : sqrt(2.0) / m1;
+      }
+      __syncthreads();
+      const double sc0 = f_norm[4], sc1 = f_norm[5];
+      // (c) the 9 x 9 matrix of sums over the normalised inliers, its smallest eigenvector, back to pixel coordinates, rank 2
+      {
+        double acc[45];
+        for (int c = 0; c < 45; ++c) acc[c] = 0.0;
+        for (int p = t; p < K; p += 1024) {
+          const float4 c4 = e.corr[p];
+          const double x = c4.x, y = c4.y, u = c4.z, v = c4.w;
+          if (sampson_in(F, x, y, u, v, t2)) vf_epipolar_add(acc, (x - cx) * sc0, (y - cy) * sc0, (u - cu) * sc1, (v - cv) * sc1);
+        }
+        vf_partials(acc, s_acc);
+      }
+      __syncthreads();
+      if (t == 0) {
+        int q = 0;
+        for (int i = 0; i < 9; ++i)
+          for (int j = i; j < 9; ++j) {
+            const double s = vf_total(s_acc, q);
+            f_S[i][j] = s; f_S[j][i] = s;
+            ++q;
+          }
+        double fn[9], Fd[9];
+        vf_jacobi(f_S, f_V, 9, fn);
+        vf_denormalise(fn, cx, cy, sc0, cu, cv, sc1, Fd);
+        bool ok = vf_unit(Fd);
+        if (ok) {
+          vf_rank2(Fd, f_S, f_V);
+          for (int c = 0; c < 9; ++c) f_Fn[c] = Fd[c];
+        }
+        f_stop = ok ? 0 : 1;
+      }
+      __syncthreads();
+      if (f_stop) break;
+      double Fc[9];
+      for (int c = 0; c < 9; ++c) Fc[c] = f_Fn[c];
+      // (d) the candidate's inliers against the accepted model's
+      {
+        double a[2] = {0.0, 0.0};
+        for (int p = t; p < K; p += 1024) {
+          const float4 c4 = e.corr[p];
+          const double x = c4.x, y = c4.y, u = c4.z, v = c4.w;
+          const bool was = sampson_in(F, x, y, u, v, t2), is = sampson_in(Fc, x, y, u, v, t2);
+          a[0] += is ? 1.0 : 0.0;
+          a[1] += is != was ? 1.0 : 0.0;
+        }
+        vf_partials(a, s_acc);
+      }
+      __syncthreads();
+      if (t == 0) {
+        const double n = vf_total(s_acc, 0), changed = vf_total(s_acc, 1);
+        if (n < f_nprev) {
+          f_stop = 1;                                     // fewer inliers: keep F_{l-1}
+        } else {
+          for (int c = 0; c < 9; ++c) f_F[c] = f_Fn[c];
+          f_nprev = n;
+          f_rounds = f_rounds + 1;
+          f_stop = changed == 0.0 ? 2 : 0;                // accepted; the same set again: converged
+        }
+      }
+      __syncthreads();
+      const int stop = f_stop;
+      if (stop != 1)
+        for (int c = 0; c < 9; ++c) F[c] = Fc[c];
+      if (stop) break;
+    }
+  }
+  // every path above ends behind a barrier that follows thread 0's last stores to f_F and f_rounds.  No accepted round (lo_iters == 0
+  // has none): the model is the best hypothesis made rank 2
+  if (f_rounds == 0) {
+    if (t == 0) {
+      double G[9];
+      for (int c = 0; c < 9; ++c) G[c] = f_F[c];
+      vf_rank2(G, f_S, f_V);
+      for (int c = 0; c < 9; ++c) f_F[c] = G[c];
+    }
+    __syncthreads();
+  }
+  for (int c = 0; c < 9; ++c) F[c] = f_F[c];
+  {
+    double a[1] = {0.0};
+    for (int p = t; p < K; p += 1024) {
+      const float4 c4 = e.corr[p];
+      const bool in = sampson_in(F, c4.x, c4.y, c4.z, c4.w, t2);
+      e.inlier[e.rows[p]] = in ? 1 : 0;
+      a[0] += in ? 1.0 : 0.0;
+    }
+    vf_partials(a, s_acc);
+  }
+  __syncthreads();
+  if (t == 0) {
+    e.record[VF_NVALID] = (float)K;
+    e.record[VF_OK] = 1.f;
+    e.record[VF_NINLIERS] = (float)vf_total(s_acc, 0);
+    e.record[VF_BEST_HYP] = (float)bh;
+    e.record[VF_BEST_HYP_INLIERS] = (float)bc;
+    e.record[VF_LO_ROUNDS] = (float)f_rounds;
+    e.record[VF_ERR_CORNER] = -1.f;
+    e.record[VF_RESERVED] = 0.f;
+    int m = 0;
+    for (int c = 1; c < 9; ++c)
+      if (fabs(F[c]) > fabs(F[m])) m = c;
+    const double sg = F[m] < 0.0 ? -1.0 : 1.0;
+    for (int c = 0; c < 9; ++c) e.hom[c] = (float)(sg * F[c]);
+  }
+}
+
 // one workgroup per set: best hypothesis (most inliers, first such), stage 2, final mask, record.  Every decision of stage 2 is taken by
 // thread 0, stored in LDS and read by all threads after the barrier that follows; the next store to the same word comes after a later
 // barrier.  No barrier sits under a condition that is not one of those words, a kernel argument or a per-set constant.
@@ -194,7 +632,7 @@ __global__ __launch_bounds__(1024) void verify_finish_kernel(const VerifyDev* __
   __shared__ double s_H[9];          // the accepted model
   __shared__ double s_Hn[9];         // the candidate of the current round
   __shared__ double s_norm[6];       // cx, cy, cu, cv, scale0, scale1
-  __shared__ double s_acc[16][44];
+  __shared__ double s_acc[16][VF_ACC];
   __shared__ double s_nprev;         // |I_{l-1}|
   __shared__ int s_ok, s_stop, s_rounds, s_bc, s_bh, s_cnt;
   const VerifyDev& e = vs[blockIdx.x];
@@ -212,6 +650,13 @@ __global__ __launch_bounds__(1024) void verify_finish_kernel(const VerifyDev* __
   if (lane == 0) { s_best[wave][0] = bc; s_best[wave][1] = bh; }
   if (t == 0) { s_ok = 0; s_stop = 0; s_rounds = 0; s_cnt = 0; }
   __syncthreads();
+  if (e.model == GIMS_VERIFY_MODEL_FUNDAMENTAL) {           // per set: the same for every thread of the workgroup
+    if (t == 0)
+      for (int w = 1; w < 16; ++w)
+        if (s_best[w][0] > bc || (s_best[w][0] == bc && s_best[w][1] < bh)) { bc = s_best[w][0]; bh = s_best[w][1]; }
+    vf_finish_fundamental(e, K, bc, bh, seed, lo_iters, t2, s_acc);
+    return;
+  }
   if (t == 0) {
     for (int w = 1; w < 16; ++w)
       if (s_best[w][0] > bc || (s_best[w][0] == bc && s_best[w][1] < bh)) { bc = s_best[w][0]; bh = s_best[w][1]; }
@@ -428,7 +873,7 @@ static void verify_layout(const gims_verify_set* sets, int n_sets, int iters, Ws
     d.nvalid = L.take<int32_t>(64);
     if (!recs) continue;
     d.kp0 = p.kpts0; d.kp1 = p.kpts1; d.matches0 = p.matches0;
-    d.n0 = p.n0; d.n1 = p.n1; d.height = p.height; d.width = p.width; d.has_ref = p.has_ref ? 1 : 0;
+    d.n0 = p.n0; d.n1 = p.n1; d.height = p.height; d.width = p.width; d.has_ref = p.has_ref ? 1 : 0; d.model = p.model;
     memcpy(d.href, p.h_ref, sizeof(d.href));
     d.inlier = p.inlier; d.record = p.record; d.hom = p.homography;
     recs[i] = d;
@@ -463,6 +908,10 @@ extern "C" int gims_verify_pairs(const gims_verify_set* sets, int32_t n_sets, fl
     GIMS_CHECK_ARG(p.n0 >= 0 && p.n1 >= 0 && (p.n0 == 0 || (p.kpts0 && p.inlier)) && (p.n1 == 0 || p.kpts1) && p.record && p.homography,
                    "gims_verify_pairs: set %d has a negative shape or a null pointer", i);
     GIMS_CHECK_ARG(p.matches0 || p.n0 == p.n1, "gims_verify_pairs: set %d has no matches0 (identity pairing) but n0 = %d != n1 = %d", i, p.n0, p.n1);
+    GIMS_CHECK_ARG(p.model == GIMS_VERIFY_MODEL_HOMOGRAPHY || p.model == GIMS_VERIFY_MODEL_FUNDAMENTAL,
+                   "gims_verify_pairs: set %d has model = %d (GIMS_VERIFY_MODEL_HOMOGRAPHY or GIMS_VERIFY_MODEL_FUNDAMENTAL)", i, p.model);
+    GIMS_CHECK_ARG(p.model != GIMS_VERIFY_MODEL_FUNDAMENTAL || !p.has_ref,
+                   "gims_verify_pairs: set %d has model = fundamental and a reference homography (has_ref): there is no error column for F", i);
   }
   std::vector<VerifyDev> h(n_sets);
   WsLayout L(work);

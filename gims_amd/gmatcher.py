@@ -1291,12 +1291,17 @@ class GMatcher(nn.Module):
         (``forward`` and ``match_pairs`` do, like the reference): its record has ``error='ValueError: need at least one array to
         concatenate'``, ``kept0 = kept1 = 0``, ``n_matches = 0`` and ``result=None``, the way parameter_search.py writes such a row.
 
-        ``verify``: None, or a dict with any of ``thresh``, ``iters``, ``lo_iters``, ``seed`` (the keywords of ``gims_amd.verify.verify_pairs``).
-        When given, every record also carries ``correct_matches`` (a 0-dim device tensor: the inliers of the verified homography, the
-        quantity parameter_search.py:161-165 records), ``homography`` [3, 3] and ``inlier`` [kept0] uint8 -- one ``verify_pairs`` call per
-        sub-batch, no extra host synchronisation; ``0 / None / None`` on a record with ``error``."""
-        if verify is not None and (not isinstance(verify, dict) or set(verify) - {"thresh", "iters", "lo_iters", "seed"}):
-            raise ValueError("verify must be None or a dict with keys among thresh, iters, lo_iters, seed")
+        ``verify``: None, or a dict with any of ``thresh``, ``iters``, ``lo_iters``, ``seed``, ``model`` (the keywords of
+        ``gims_amd.verify.verify_pairs``).  When given, every record also carries ``correct_matches`` (a 0-dim device tensor: the inliers of
+        the verified homography, the quantity parameter_search.py:161-165 records), ``homography`` [3, 3] and ``inlier`` [kept0] uint8 -- one
+        ``verify_pairs`` call per sub-batch, no extra host synchronisation; ``0 / None / None`` on a record with ``error``.  With
+        ``model='fundamental'`` (a camera that moved through a 3-D scene) the inliers are those of the fundamental matrix and the record
+        carries it as ``fundamental`` in place of ``homography``."""
+        if verify is not None and (not isinstance(verify, dict) or set(verify) - {"thresh", "iters", "lo_iters", "seed", "model"}):
+            raise ValueError("verify must be None or a dict with keys among thresh, iters, lo_iters, seed, model")
+        if verify is not None and verify.get("model", "homography") not in ("homography", "fundamental", 0, 1):
+            raise ValueError("verify['model'] must be 'homography' or 'fundamental'")
+        vkey = "fundamental" if verify is not None and verify.get("model", "homography") in ("fundamental", 1) else "homography"
         self._check_call(data, {})
         if data['keypoints0'].shape[0] != 1:
             raise ValueError("sweep takes one single-pair dict (B == 1)")
@@ -1341,7 +1346,7 @@ class GMatcher(nn.Module):
                     rec = dict(radius=radius, percentile=percentile, min_size=min_size, delaunay=delaunay, kept0=0, kept1=0, n_matches=0,
                                error=None, result=None)
                     if verify is not None:
-                        rec.update(correct_matches=0, homography=None, inlier=None)
+                        rec.update({'correct_matches': 0, vkey: None, 'inlier': None})
                     records[c0 + j] = rec
                     if j in dropped:
                         rec["error"] = "ValueError: need at least one array to concatenate"
@@ -1365,5 +1370,5 @@ class GMatcher(nn.Module):
                                      [{'matches0': r["result"]['matches0']} for r, _, _ in live], **verify)
                     col = hip.VERIFY_FIELDS.index("n_inliers")
                     for q, (rec, _, _) in enumerate(live):
-                        rec.update(correct_matches=v["records"][q, col], homography=v["homographies"][q], inlier=v["inlier"][q])
+                        rec.update({'correct_matches': v["records"][q, col], vkey: v["models"][q], 'inlier': v["inlier"][q]})
         return records

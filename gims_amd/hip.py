@@ -672,11 +672,23 @@ def eval_pairs(items, dist_thresh=3.0, n_iters=3, ransac_thresh=3.0, ransac_iter
 
 # ------------------------------------------------------------------------------------------------ geometric verification
 VERIFY_FIELDS = ("n_valid", "ok", "n_inliers", "best_hyp", "best_hyp_inliers", "lo_rounds", "err_corner")
+VERIFY_MODELS = {"homography": _K["GIMS_VERIFY_MODEL_HOMOGRAPHY"], "fundamental": _K["GIMS_VERIFY_MODEL_FUNDAMENTAL"]}
+
+
+def verify_model(model) -> int:
+    """GIMS_VERIFY_MODEL_* of a model given by name or by number."""
+    if isinstance(model, str) and model in VERIFY_MODELS:
+        return VERIFY_MODELS[model]
+    if isinstance(model, (int, np.integer)) and not isinstance(model, bool) and int(model) in VERIFY_MODELS.values():
+        return int(model)
+    raise GimsHipError(f"verify_pairs: model must be 'homography' (0) or 'fundamental' (1), not {model!r}")
 
 
 def verify_pairs(items, thresh=3.0, iters=3000, lo_iters=8, seed=0, work=None):
     """items: list of dicts with device tensors kpts0 [n0,2] f32, kpts1 [n1,2] f32, matches0 [n0] int64 or None (identity pairing, n0 == n1),
-    optionally h_ref (3x3 array-like) with height / width, and outputs inlier [n0] uint8, record [8] f32 (VERIFY_FIELDS), homography [9] f32.
+    optionally h_ref (3x3 array-like) with height / width, optionally model ('homography' / 0, the default, or 'fundamental' / 1; per item,
+    one call may mix both; h_ref with 'fundamental' is refused by the library), and outputs inlier [n0] uint8, record [8] f32 (VERIFY_FIELDS), homography [9] f32
+    (the fundamental matrix F, x1^T F x0 = 0, when that is the model).
     One batched asynchronous call; returns the workspace (keep it alive until the stream has passed the call).  See include/gims_hip.h."""
     lib = load()
     arr = (VerifySet * len(items))()
@@ -692,9 +704,10 @@ def verify_pairs(items, thresh=3.0, iters=3000, lo_iters=8, seed=0, work=None):
                 or it["homography"].dtype != torch.float32 or it["homography"].numel() < 9:
             raise GimsHipError("verify_pairs: outputs are inlier uint8 [n0], record float32 [8], homography float32 [9]")
         h_ref = it.get("h_ref")
+        model = verify_model(it.get("model", 0))
         h = np.asarray(h_ref, dtype=np.float32).reshape(9) if h_ref is not None else np.zeros(9, dtype=np.float32)
         arr[i] = VerifySet(_p(k0) if n0 else None, _p(k1) if n1 else None, _p(m0), n0, n1, int(it.get("height", 0)), int(it.get("width", 0)),
-                           int(h_ref is not None), 0, (C.c_float * 9)(*h.tolist()), _p(it["inlier"]) if n0 else None, _p(it["record"]),
+                           int(h_ref is not None), model, (C.c_float * 9)(*h.tolist()), _p(it["inlier"]) if n0 else None, _p(it["record"]),
                            _p(it["homography"]))
     need = int(lib.gims_verify_workspace_bytes(arr, len(items), int(iters)))
     if work is None or work.numel() * work.element_size() < need:

@@ -514,12 +514,53 @@ int gims_eval_pairs(const gims_eval_pair* h_pairs /* HOST array */, int32_t n_pa
  *   (GIMS_VERIFY_* below).  K < 4, iters == 0 or no hypothesis with a model: ok = 0, err_corner = -1, n_valid = K, zeros elsewhere.
  * GIMS_EINVAL: n_sets > 65535 (the sets are the grid's y dimension), iters > 2^20, lo_iters > 1024, a negative or non-finite thresh, a
  *   workspace smaller than gims_verify_workspace_bytes (checked before anything is enqueued).  Asynchronous; no host synchronisation.
+ *
+ * The FUNDAMENTAL-MATRIX model (model == GIMS_VERIFY_MODEL_FUNDAMENTAL; selected per set, one call may mix both models) -- what a camera
+ *   that moved through a 3-D scene needs, where a homography rejects correct matches off the dominant plane.  The reference keeps the
+ *   two-view utilities for it (utils/common.py:392-476: estimate_pose, compute_epipolar_error) next to its drivers.  The estimator is
+ *   again this build's own and parity with OpenCV is not claimed; its SPECIFICATION is this comment (restated in tests/fundamental_ref.py).
+ *   Everything is float64.  F is row-major and x1^T F x0 = 0 for x0 = (x, y, 1) of image 0, x1 = (u, v, 1) of image 1.
+ *   Correspondences: gathered exactly as above.  K < 8, iters == 0 or no hypothesis with a model: ok = 0 and zeros, as above.
+ *   inlier(F, x, y, u, v): a = F x0 (3), g = the first two entries of F^T x1, e = x1 . a, den = a0^2 + a1^2 + g0^2 + g1^2;
+ *     inlier iff den > 0 and e^2 <= thresh^2 * den (the squared Sampson distance e^2 / den <= thresh^2, without the division).
+ *   similarity(points): c = (sum of the points, in order) / n, m = (sum of the distances to c, in order) / n, s = sqrt(2) / m, or 1 when
+ *     m == 0; a point p is normalised to (p - c) * s.
+ *   denormalise(Fn; c0, s0, c1, s1) = T1^T Fn T0: M[r] = (Fn[r][0] s0, Fn[r][1] s0, Fn[r][2] - s0 (Fn[r][0] c0x + Fn[r][1] c0y));
+ *     F[0] = s1 M[0], F[1] = s1 M[1], F[2] = M[2] - s1 (c1x M[0] + c1y M[1]).
+ *   unit(F) = F / sqrt(sum of the nine squares, in order); fails when that root is 0 or anything is not finite.
+ *   Stage 1: hypothesis h takes EIGHT distinct indices from the sampler's stream above, state(seed, h), continued until eight distinct
+ *     values (the first four are the homography's sample).  The eight points of each image are normalised by their similarity; row k of
+ *     the 8 x 9 system is (u x, u y, u, v x, v y, v, x, y, 1) of the normalised pair k.  Null vector by Gauss-Jordan elimination with
+ *     complete pivoting: eight times, the pivot is the entry of largest magnitude among the rows and columns that held no pivot yet
+ *     (scanned by rows, then columns; a later entry replaces an earlier one only when strictly larger), no model when that magnitude is 0
+ *     or not finite; every OTHER row r (used or not) becomes row r - (A[r][pc] / pivot) * row p over all nine columns.  The column left
+ *     over is the free variable: f[free] = 1, f[pc] = -A[p][free] / A[p][pc] for the eight pivots; no named entry of F is fixed.
+ *     F_h = unit(denormalise(f)); no model (score -1) when anything is not finite.  No rank enforcement here.  score = #inliers of F_h;
+ *     best = highest score, lowest h among equals.
+ *   jacobi(S, n x n symmetric) -> the eigenvector of the smallest eigenvalue: V = I; 12 sweeps over p = 0 .. n-2, q = p+1 .. n-1; a
+ *     rotation is skipped when S[p][q] is exactly 0; d = S[q][q] - S[p][p], b = 2 S[p][q], t = (d >= 0 ? b : -b) / (|d| + hypot(d, b))
+ *     (no quotient that can overflow), c = 1 / sqrt(t^2 + 1), s = t c; for every k: (S[k][p], S[k][q]) <- (c S[k][p] - s S[k][q],
+ *     s S[k][p] + c S[k][q]); then the rows p and q likewise; S[p][q] = S[q][p] = 0; the columns p and q of V as those of S.  The
+ *     eigenvector is the column of V at the smallest diagonal entry (the first such).
+ *   rank2(F): v = jacobi(F^T F); F' = unit(F - (F v) v^T); F itself when that fails.
+ *   Stage 2, lo_iters == 0: the model is rank2(F_best) and the mask is taken under it.  (So every returned model has rank 2.)
+ *   Stage 2, lo_iters >= 1: F_0 = F_best (as scored, not rank 2), I_0 its inliers.  For l = 1 .. lo_iters:
+ *     stop if |I_{l-1}| < 8;  the two similarities of the point sets of I_{l-1};  S = the 9 x 9 matrix of the 45 sums a_i a_j over the
+ *     normalised inliers, a = the row above;  Fn = jacobi(S);  F' = rank2(denormalise(Fn)) after unit(); stop if anything fails or is not
+ *     finite;  I' = inliers of F';  if |I'| < |I_{l-1}|: stop and keep F_{l-1};  otherwise accept (F_l, I_l) = (F', I') and stop if
+ *     I' == I_{l-1}.  When no round was accepted, the model and the mask are those of lo_iters == 0.
+ *   Outputs: homography [9] receives F in float32, unit Frobenius norm, negated when its entry of largest magnitude (the first such) is
+ *     negative; GIMS_VERIFY_ERR_CORNER is always -1.  has_ref != 0 with this model, or a model other than the two below, is GIMS_EINVAL
+ *     (checked before anything is enqueued).  A set with model == GIMS_VERIFY_MODEL_HOMOGRAPHY computes exactly what it did before the
+ *     field had a meaning.
  */
+#define GIMS_VERIFY_MODEL_HOMOGRAPHY 0
+#define GIMS_VERIFY_MODEL_FUNDAMENTAL 1
 typedef struct gims_verify_set {
   const float* kpts0; const float* kpts1;   /* [n0][2], [n1][2] */
   const int64_t* matches0;                  /* [n0], or NULL: identity pairing */
   int32_t n0, n1, height, width;            /* image 0 size for the corner error (read with has_ref only) */
-  int32_t has_ref, reserved;
+  int32_t has_ref, model;                   /* model: GIMS_VERIFY_MODEL_* */
   float h_ref[9];                           /* reference homography, row-major (read with has_ref only) */
   uint8_t* inlier; float* record; float* homography;
 } gims_verify_set;

@@ -16,6 +16,10 @@ Timing: HIP events around each call.  The host needs milliseconds to pack 512 de
 events measure the host; so every measured call is preceded by a matrix product long enough to keep the GPU busy until the call's
 launches are queued (the start event is reached when that product ends).  What is reported is device time of the call's own launches.
 
+``--model fundamental`` measures the fundamental-matrix model instead: the same number of sets, points, matches and wrong matches, but
+of a two-view scene (random 3-D points at depth 4 .. 12 in front of two pinhole cameras, a rotation of a few degrees and a translation),
+variants ``fundamental_lo0`` and ``fundamental_lo8``; the evaluation route has no such model and is left out.
+
 Prints one JSON line (median, min, max in ms per variant, and the inlier totals of the two verify variants)."""
 import argparse
 import json
@@ -56,6 +60,36 @@ def make_sets(n_sets, n_points, seed, device):
     return datas, outs
 
 
+def make_two_view_sets(n_sets, n_points, seed, device):
+    """As make_sets, the correspondences those of a camera that moved through a 3-D scene."""
+    datas, outs = [], []
+    w, h = CANVAS
+    f = 700.0
+    for s in range(n_sets):
+        r = np.random.default_rng(seed + s)
+        ang = 0.1 * (r.random(3) - 0.5)
+        cx, cy, cz = np.cos(ang)
+        sx, sy, sz = np.sin(ang)
+        R = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]]) @ np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]]) @ np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
+        t = np.array([0.8, 0.2, 0.3]) * (r.random(3) + 0.5)
+        kp0 = (r.random((n_points, 2)) * [w, h]).astype(np.float32)
+        z = 4.0 + 8.0 * r.random(n_points)
+        X = np.concatenate([(kp0.astype(np.float64) - [w / 2, h / 2]) / f, np.ones((n_points, 1))], 1) * z[:, None]
+        Y = X @ R.T + t
+        seen = Y[:, :2] / Y[:, 2:3] * f + [w / 2, h / 2] + r.standard_normal((n_points, 2))
+        perm = r.permutation(n_points)
+        kp1 = np.zeros((n_points, 2), dtype=np.float32)
+        kp1[perm] = seen.astype(np.float32)
+        m0 = perm.astype(np.int64)
+        m0[r.random(n_points) < 0.13] = -1
+        wrong = np.nonzero((m0 > -1) & (r.random(n_points) < 0.3))[0]
+        m0[wrong] = perm[np.roll(wrong, 1)]
+        datas.append(dict(keypoints0=torch.from_numpy(kp0).to(device)[None], keypoints1=torch.from_numpy(kp1).to(device)[None],
+                          image0=np.zeros((h, w, 3), dtype=np.uint8)))
+        outs.append(dict(matches0=torch.from_numpy(m0).to(device)[None]))
+    return datas, outs
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--sets", type=int, default=512)
@@ -64,12 +98,17 @@ def main(argv=None):
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--seed", type=int, default=7000)
+    ap.add_argument("--model", choices=("homography", "fundamental"), default="homography")
     ap.add_argument("-o", "--output", default=None, help="also write the JSON record to this file")
     args = ap.parse_args(argv)
     dev = torch.device("cuda", torch.cuda.current_device())
-    datas, outs = make_sets(args.sets, args.points, args.seed, dev)
+    fundamental = args.model == "fundamental"
+    datas, outs = (make_two_view_sets if fundamental else make_sets)(args.sets, args.points, args.seed, dev)
     eye = [np.eye(3, dtype=np.float32)] * args.sets
     variants = {
+        "fundamental_lo0": lambda: verify_pairs(datas, outs, thresh=3.0, iters=args.iters, lo_iters=0, seed=0, model="fundamental"),
+        "fundamental_lo8": lambda: verify_pairs(datas, outs, thresh=3.0, iters=args.iters, lo_iters=8, seed=0, model="fundamental"),
+    } if fundamental else {
         "eval": lambda: evalh.evaluate_pairs(datas, outs, eye, ransac_thresh=3.0, ransac_iters=args.iters, seed=0),
         "eval_nogt": lambda: evalh.evaluate_pairs(datas, outs, eye, n_iters=0, ransac_thresh=3.0, ransac_iters=args.iters, seed=0),
         "verify_lo0": lambda: verify_pairs(datas, outs, thresh=3.0, iters=args.iters, lo_iters=0, seed=0),
@@ -106,11 +145,14 @@ def main(argv=None):
             if rep >= args.warmup:
                 times[name].append(e0.elapsed_time(e1))
     col = RECORD_FIELDS.index("n_inliers")
-    res = dict(sets=args.sets, points=args.points, iters=args.iters, reps=args.reps, host_issue_ms={k: round(v, 2) for k, v in host_ms.items()},
+    res = dict(model=args.model, sets=args.sets, points=args.points, iters=args.iters, reps=args.reps, host_issue_ms={k: round(v, 2) for k, v in host_ms.items()},
                correspondences_mean=float(np.mean([int((o["matches0"] > -1).sum()) for o in outs[:16]])),
                ms={k: dict(median=round(float(np.median(v)), 3), min=round(min(v), 3), max=round(max(v), 3)) for k, v in times.items()},
-               inliers_total={k: int(last[k]["records"][:, col].sum().item()) for k in ("verify_lo0", "verify_lo8")},
-               inliers_total_eval=int(last["eval"]["records"][:, evalh.RECORD_FIELDS.index("n_inliers")].sum().item()))
+               inliers_total={k: int(last[k]["records"][:, col].sum().item()) for k in variants if k not in ("eval", "eval_nogt")})
+    if fundamental:
+        res["lo_rounds_mean"] = float(last["fundamental_lo8"]["records"][:, RECORD_FIELDS.index("lo_rounds")].mean().item())
+    else:
+        res["inliers_total_eval"] = int(last["eval"]["records"][:, evalh.RECORD_FIELDS.index("n_inliers")].sum().item())
     line = json.dumps(res)
     print(line)
     if args.output:
