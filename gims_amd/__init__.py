@@ -7,6 +7,8 @@ from .gmatcher import GMatcher  # noqa: F401
 from .matching import Matching  # noqa: F401
 from .baselines import mnn, nn_match_pairs, nndr  # noqa: F401
 from .augment import ColorAug, ColorAugPlan  # noqa: F401
-from .verify import find_fundamental, find_homography, verify_pairs  # noqa: F401
+from .verify import (epipolar_error, estimate_pose, find_fundamental, find_homography, pose_error, pose_summary,  # noqa: F401
+                     verify_pairs)
 
-__all__ = ["GMatcher", "Matching", "nndr", "mnn", "nn_match_pairs", "ColorAug", "ColorAugPlan", "find_homography", "find_fundamental", "verify_pairs"]
+__all__ = ["GMatcher", "Matching", "nndr", "mnn", "nn_match_pairs", "ColorAug", "ColorAugPlan", "find_homography", "find_fundamental", "verify_pairs",
+           "estimate_pose", "pose_error", "epipolar_error", "pose_summary"]

@@ -859,24 +859,764 @@ __global__ __launch_bounds__(1024) void verify_finish_kernel(const VerifyDev* __
   }
 }
 
+// ---------------------------------------------------------------------------------------------- calibrated relative pose (model 3)
+// The five-point model, its guarded local optimisation and the pose of the result (specification: include/gims_hip.h).
+// Pose sets run in two kernels of their own -- the homography and fundamental kernels above are launched over the other sets of a call
+// and are the code they were --, the gather kernel is shared.
+constexpr int VP_MAXM = 10;        // models of one sample: the real roots of a degree-10 polynomial
+constexpr int VP_BISECT = 80;      // halvings per isolated root
+constexpr int VP_A = 200;          // the 10 x 20 elimination array (the 5 x 9 one before it lives in the same words)
+
+// the best model of workgroup b of the hypotheses kernel: 9 doubles behind the `iters` counters of a pose set (verify_layout)
+__device__ __forceinline__ double* vp_block_model(const VerifyDev& e, int iters, int b) {
+  return (double*)(e.hypcount + ((iters + 1) & ~1)) + 9 * b;
+}
+
+// five distinct indices from the stream of ransac_sample (eval_geom.h): its four, then one more
+__device__ void ransac_sample5(uint64_t seed, int hyp, int k, int (&idx)[5]) {
+  uint64_t state = seed ^ ((uint64_t)hyp * 0xD1342543DE82EF95ull);
+  int n = 0;
+  while (n < 5) {
+    state = splitmix(state);
+    const int c = (int)(state % (uint64_t)k);
+    bool dup = false;
+    for (int q = 0; q < n; ++q) dup = dup || idx[q] == c;
+    if (!dup) idx[n++] = c;
+  }
+}
+
+// camera coordinates of a correspondence: (x - cx) / fx, (y - cy) / fy for cam = fx0, fy0, cx0, cy0, fx1, fy1, cx1, cy1
+__device__ __forceinline__ void vp_norm(const float4 c, const double (&cam)[8], double& x, double& y, double& u, double& v) {
+  x = ((double)c.x - cam[2]) / cam[0];
+  y = ((double)c.y - cam[3]) / cam[1];
+  u = ((double)c.z - cam[6]) / cam[4];
+  v = ((double)c.w - cam[7]) / cam[5];
+}
+
+// variables 0: x, 1: y, 2: z, 3: the constant 1.  A quadratic form has ten coefficients (i <= j), a cubic one twenty; the column of
+// x^a y^b z^c among the twenty is base[a][b] + (3 - a - b - c):
+//   x^3 y^3 x^2y xy^2 | x^2z x^2 | y^2z y^2 | xyz xy | xz^2 xz x | yz^2 yz y | z^3 z^2 z 1
+__device__ __forceinline__ constexpr int vp_qi(int i, int j) { return i <= j ? 4 * i - i * (i - 1) / 2 + (j - i) : 4 * j - j * (j - 1) / 2 + (i - j); }
+__device__ __forceinline__ constexpr int vp_col(int i, int j, int k) {
+  const int a = (i == 0) + (j == 0) + (k == 0), b = (i == 1) + (j == 1) + (k == 1), c = (i == 2) + (j == 2) + (k == 2);
+  const int base = a == 0 ? (b == 0 ? 16 : b == 1 ? 13 : b == 2 ? 6 : 1) : a == 1 ? (b == 0 ? 10 : b == 1 ? 8 : 3) : a == 2 ? (b == 0 ? 4 : 2) : 0;
+  return base + (3 - a - b - c);
+}
+// q += s * (a * b) for two linear forms
+__device__ __forceinline__ void vp_ll(const double* a, const double* b, double s, double (&q)[10]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) q[vp_qi(i, j)] += s * (a[i] * b[j]);
+}
+// row += s * (q * l) for a quadratic and a linear form
+__device__ __forceinline__ void vp_ql(const double (&q)[10], const double* l, double s, double (&row)[20]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = i; j < 4; ++j)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) row[vp_col(i, j, k)] += s * (q[vp_qi(i, j)] * l[k]);
+}
+// out (na + nb - 1 coefficients, ascending) = a * b
+__device__ void vp_pmul(const double* a, int na, const double* b, int nb, double* out) {
+  for (int i = 0; i < na + nb - 1; ++i) out[i] = 0.0;
+  for (int i = 0; i < na; ++i)
+    for (int j = 0; j < nb; ++j) out[i + j] += a[i] * b[j];
+}
+__device__ __forceinline__ double vp_horner(const double* c, int deg, double z) {
+  double v = c[deg];
+  for (int i = deg - 1; i >= 0; --i) v = v * z + c[i];
+  return v;
+}
+
+// the real roots of the degree-10 polynomial c (ascending coefficients), ascending, by bisection between the roots of successive
+// derivatives inside the bound 1 + max |c_i / c_10|; -1 when c_10 is 0 or anything is not finite
+__device__ int vp_real_roots(const double (&c)[11], double (&roots)[VP_MAXM]) {
+  bool fin = c[10] != 0.0;
+  double bound = 0.0;
+  for (int i = 0; i < 11; ++i) fin = fin && isfinite(c[i]);
+  if (!fin) return -1;
+  for (int i = 0; i < 10; ++i) bound = fmax(bound, fabs(c[i] / c[10]));
+  bound = 1.0 + bound;
+  if (!isfinite(bound)) return -1;
+  double prev[VP_MAXM], q[11];
+  int nprev = 0;
+#pragma unroll 1
+  for (int d = 1; d <= 10; ++d) {
+    const int k = 10 - d;
+    for (int i = 0; i <= d; ++i) {
+      double f = 1.0;
+      for (int m = i + 1; m <= i + k; ++m) f *= (double)m;
+      q[i] = c[i + k] * f;
+    }
+    int ncur = 0;
+    double lo = -bound, flo = vp_horner(q, d, lo);
+#pragma unroll 1
+    for (int s = 0; s <= nprev; ++s) {
+      const double hi = s < nprev ? prev[s] : bound, fhi = vp_horner(q, d, hi);
+      if ((flo > 0.0) != (fhi > 0.0)) {
+        const bool sa = flo > 0.0;
+        double a = lo, b = hi;
+#pragma unroll 1
+        for (int it = 0; it < VP_BISECT; ++it) {
+          const double m = 0.5 * (a + b);
+          const bool same = (vp_horner(q, d, m) > 0.0) == sa;
+          a = same ? m : a;
+          b = same ? b : m;
+        }
+        roots[ncur++] = 0.5 * (a + b);                     // at most one root per interval: ncur <= d
+      }
+      lo = hi;
+      flo = fhi;
+    }
+    nprev = ncur;
+    for (int s = 0; s < ncur; ++s) prev[s] = roots[s];
+  }
+  return nprev;
+}
+
+// the ten cubic constraints of E = x X + y Y + z Z + W as 10 x 20 coefficients in A and their Gauss-Jordan elimination over the columns
+// 0 .. 9; prow10: four bits per column, the row of its pivot.  Returns the smallest pivot magnitude, -1 when the elimination fails
+__device__ double vp_constraints_eliminate(const double (&L)[9][4], double* A, int ld, uint64_t& prow10) {
+  // the ten cubic constraints: det E, then the entries of 2 E E^T E - tr(E E^T) E by rows, as 10 x 20 coefficients in A
+  {
+    double q[10], row[20];
+    for (int c = 0; c < 20; ++c) row[c] = 0.0;
+    for (int c = 0; c < 10; ++c) q[c] = 0.0;
+    vp_ll(L[4], L[8], 1.0, q); vp_ll(L[5], L[7], -1.0, q); vp_ql(q, L[0], 1.0, row);
+    for (int c = 0; c < 10; ++c) q[c] = 0.0;
+    vp_ll(L[3], L[8], 1.0, q); vp_ll(L[5], L[6], -1.0, q); vp_ql(q, L[1], -1.0, row);
+    for (int c = 0; c < 10; ++c) q[c] = 0.0;
+    vp_ll(L[3], L[7], 1.0, q); vp_ll(L[4], L[6], -1.0, q); vp_ql(q, L[2], 1.0, row);
+    for (int c = 0; c < 20; ++c) A[c * ld] = row[c];
+  }
+  {
+    double G[3][3][10], T[10];
+#pragma unroll 1
+    for (int i = 0; i < 3; ++i)
+#pragma unroll 1
+      for (int j = 0; j < 3; ++j) {
+        double q[10];
+        for (int c = 0; c < 10; ++c) q[c] = 0.0;
+        for (int k = 0; k < 3; ++k) vp_ll(L[3 * i + k], L[3 * j + k], 1.0, q);
+        for (int c = 0; c < 10; ++c) G[i][j][c] = q[c];
+      }
+    for (int c = 0; c < 10; ++c) T[c] = G[0][0][c] + G[1][1][c] + G[2][2][c];
+#pragma unroll 1
+    for (int i = 0; i < 3; ++i)
+#pragma unroll 1
+      for (int j = 0; j < 3; ++j) {
+        double row[20], q[10];
+        for (int c = 0; c < 20; ++c) row[c] = 0.0;
+        for (int k = 0; k < 3; ++k) {
+          for (int c = 0; c < 10; ++c) q[c] = G[i][k][c];
+          vp_ql(q, L[3 * k + j], 2.0, row);
+        }
+        for (int c = 0; c < 10; ++c) q[c] = T[c];
+        vp_ql(q, L[3 * i + j], -1.0, row);
+        for (int c = 0; c < 20; ++c) A[(20 * (1 + 3 * i + j) + c) * ld] = row[c];
+      }
+  }
+  // Gauss-Jordan over the columns 0 .. 9, the pivot of column c the largest entry among the rows without one
+  prow10 = 0ull;
+  double quality = INFINITY;
+  {
+    unsigned used = 0u;
+#pragma unroll 1
+    for (int c = 0; c < 10; ++c) {
+      int pr = -1;
+      double best = 0.0;
+      for (int r = 0; r < 10; ++r) {
+        if ((used >> r) & 1u) continue;
+        const double a = fabs(A[(20 * r + c) * ld]);
+        if (a > best) { best = a; pr = r; }
+      }
+      if (pr < 0 || !isfinite(best)) return -1.0;
+      quality = fmin(quality, best);
+      used |= 1u << pr;
+      prow10 |= (uint64_t)pr << (4 * c);
+      const double piv = A[(20 * pr + c) * ld];
+#pragma unroll 1
+      for (int r = 0; r < 10; ++r) {
+        if (r == pr) continue;
+        const double m = A[(20 * r + c) * ld] / piv;
+        for (int k = 0; k < 20; ++k) A[(20 * r + k) * ld] -= m * A[(20 * pr + k) * ld];
+      }
+    }
+  }
+  return quality;
+}
+
+// the models of the specification through five correspondences of the dense array, in ascending root order; returns their number.
+// A: VP_A doubles of LDS at stride ld (indexed by the pivot searches)
+__device__ int vp_five_point(const float4* __restrict__ corr, const int (&idx)[5], const double (&cam)[8], double* A, int ld, double (&E)[VP_MAXM][9]) {
+#pragma unroll 1
+  for (int k = 0; k < 5; ++k) {
+    double x, y, u, v;
+    vp_norm(corr[idx[k]], cam, x, y, u, v);
+    const double row[9] = {u * x, u * y, u, v * x, v * y, v, x, y, 1.0};
+#pragma unroll
+    for (int q = 0; q < 9; ++q) A[(9 * k + q) * ld] = row[q];
+  }
+  // the null space: Gauss-Jordan with complete pivoting, five pivots
+  unsigned rused = 0u, cused = 0u, prow = 0u, pcol = 0u;
+#pragma unroll 1
+  for (int s = 0; s < 5; ++s) {
+    int pr = -1, pc = -1;
+    double best = 0.0;
+#pragma unroll 1
+    for (int r = 0; r < 5; ++r) {
+      if ((rused >> r) & 1u) continue;
+      for (int c = 0; c < 9; ++c) {
+        if ((cused >> c) & 1u) continue;
+        const double a = fabs(A[(9 * r + c) * ld]);
+        if (a > best) { best = a; pr = r; pc = c; }
+      }
+    }
+    if (pr < 0 || !isfinite(best)) return 0;
+    rused |= 1u << pr;
+    cused |= 1u << pc;
+    prow |= (unsigned)pr << (4 * s);
+    pcol |= (unsigned)pc << (4 * s);
+    const double piv = A[(9 * pr + pc) * ld];
+#pragma unroll 1
+    for (int r = 0; r < 5; ++r) {
+      if (r == pr) continue;
+      const double m = A[(9 * r + pc) * ld] / piv;
+      for (int c = 0; c < 9; ++c) A[(9 * r + c) * ld] -= m * A[(9 * pr + c) * ld];
+    }
+  }
+  // L[e][j]: the coefficient of basis vector j (X, Y, Z, W) in entry e of E -- the linear form E_e in (x, y, z, 1)
+  double L[9][4];
+  bool fin = true;
+  {
+    unsigned freec = ~cused & 0x1ffu;
+#pragma unroll 1
+    for (int j = 0; j < 4; ++j) {
+      const int fc = __ffs((int)freec) - 1;                 // four of nine bits are clear in cused: 0 <= fc <= 8
+      freec &= freec - 1u;
+      for (int c = 0; c < 9; ++c) L[c][j] = c == fc ? 1.0 : 0.0;
+      for (int s = 0; s < 5; ++s) {
+        const int pr = (prow >> (4 * s)) & 15, pc = (pcol >> (4 * s)) & 15;
+        const double val = -A[(9 * pr + fc) * ld] / A[(9 * pr + pc) * ld];
+        fin = fin && isfinite(val);
+        L[pc][j] = val;
+      }
+    }
+  }
+  if (!fin) return 0;
+  // the hidden variable is pivoted: of the three orders of the basis (X, Y, Z) = (b0, b1, b2), (b0, b2, b1), (b2, b1, b0) the one whose
+  // elimination has the largest smallest pivot (the first such) is used; W = b3 always
+  uint64_t prow10 = 0ull;
+  {
+    int order = -1;
+    double bq = -1.0;
+#pragma unroll 1
+    for (int o = 0; o < 3; ++o) {
+      double Lp[9][4];
+      for (int e = 0; e < 9; ++e) {
+        Lp[e][0] = o == 2 ? L[e][2] : L[e][0];
+        Lp[e][1] = o == 1 ? L[e][2] : L[e][1];
+        Lp[e][2] = o == 1 ? L[e][1] : o == 2 ? L[e][0] : L[e][2];
+        Lp[e][3] = L[e][3];
+      }
+      const double q = vp_constraints_eliminate(Lp, A, ld, prow10);
+      if (q > bq) { bq = q; order = o; }
+    }
+    if (order < 0) return 0;
+    for (int e = 0; e < 9; ++e) {
+      const double l0 = L[e][0], l1 = L[e][1], l2 = L[e][2];
+      L[e][0] = order == 2 ? l2 : l0;
+      L[e][1] = order == 1 ? l2 : l1;
+      L[e][2] = order == 1 ? l1 : order == 2 ? l0 : l2;
+    }
+    if (order != 2) vp_constraints_eliminate(L, A, ld, prow10);
+  }
+  // the rows <x^2 z> - z <x^2>, <y^2 z> - z <y^2>, <xyz> - z <xy>: polynomials in z (ascending) that multiply x, y and 1
+  double Bz[3][3][5];
+  fin = true;
+#pragma unroll 1
+  for (int r = 0; r < 3; ++r) {
+    const int ra = (int)((prow10 >> (4 * (4 + 2 * r))) & 15ull), rb = (int)((prow10 >> (4 * (5 + 2 * r))) & 15ull);
+    const double pa = A[(20 * ra + 4 + 2 * r) * ld], pb = A[(20 * rb + 5 + 2 * r) * ld];
+    double a[10], b[10];
+    for (int k = 0; k < 10; ++k) {
+      a[k] = A[(20 * ra + 10 + k) * ld] / pa;
+      b[k] = A[(20 * rb + 10 + k) * ld] / pb;
+      fin = fin && isfinite(a[k]) && isfinite(b[k]);
+    }
+    for (int v = 0; v < 2; ++v) {
+      const int o = 3 * v;
+      Bz[r][v][0] = a[o + 2];
+      Bz[r][v][1] = a[o + 1] - b[o + 2];
+      Bz[r][v][2] = a[o] - b[o + 1];
+      Bz[r][v][3] = -b[o];
+      Bz[r][v][4] = 0.0;
+    }
+    Bz[r][2][0] = a[9];
+    Bz[r][2][1] = a[8] - b[9];
+    Bz[r][2][2] = a[7] - b[8];
+    Bz[r][2][3] = a[6] - b[7];
+    Bz[r][2][4] = -b[6];
+  }
+  if (!fin) return 0;
+  // its determinant, expanded along the first row: degree 10
+  double c11[11];
+  {
+    double m1[8], m2[8], t11[11];
+    vp_pmul(Bz[1][1], 4, Bz[2][2], 5, m1); vp_pmul(Bz[1][2], 5, Bz[2][1], 4, m2);
+    for (int i = 0; i < 8; ++i) m1[i] -= m2[i];
+    vp_pmul(Bz[0][0], 4, m1, 8, c11);
+    vp_pmul(Bz[1][0], 4, Bz[2][2], 5, m1); vp_pmul(Bz[1][2], 5, Bz[2][0], 4, m2);
+    for (int i = 0; i < 8; ++i) m1[i] -= m2[i];
+    vp_pmul(Bz[0][1], 4, m1, 8, t11);
+    for (int i = 0; i < 11; ++i) c11[i] -= t11[i];
+    vp_pmul(Bz[1][0], 4, Bz[2][1], 4, m1); vp_pmul(Bz[1][1], 4, Bz[2][0], 4, m2);
+    for (int i = 0; i < 7; ++i) m1[i] -= m2[i];
+    vp_pmul(Bz[0][2], 5, m1, 7, t11);
+    for (int i = 0; i < 11; ++i) c11[i] += t11[i];
+  }
+  double roots[VP_MAXM];
+  const int nr = vp_real_roots(c11, roots);
+  int nm = 0;
+#pragma unroll 1
+  for (int r = 0; r < nr; ++r) {
+    const double z = roots[r];
+    double M[3][3];
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) M[i][j] = vp_horner(Bz[i][j], 4, z);
+    double n[3] = {0.0, 0.0, 0.0}, best = -1.0;
+    for (int p = 0; p < 3; ++p) {                           // the row pairs (0, 1), (0, 2), (1, 2)
+      const int i = p == 2 ? 1 : 0, j = p == 0 ? 1 : 2;
+      const double c0 = M[i][1] * M[j][2] - M[i][2] * M[j][1], c1 = M[i][2] * M[j][0] - M[i][0] * M[j][2], c2 = M[i][0] * M[j][1] - M[i][1] * M[j][0];
+      if (fabs(c2) > best) { best = fabs(c2); n[0] = c0; n[1] = c1; n[2] = c2; }
+    }
+    if (n[2] == 0.0) continue;
+    const double x = n[0] / n[2], y = n[1] / n[2];
+    double e[9];
+    for (int q = 0; q < 9; ++q) e[q] = x * L[q][0] + y * L[q][1] + z * L[q][2] + L[q][3];
+    if (!vf_unit(e)) continue;
+    for (int q = 0; q < 9; ++q) E[nm][q] = e[q];
+    ++nm;
+  }
+  return nm;
+}
+
+// one workgroup per VF_HB hypotheses of one pose set: VF_HB lanes solve a sample each (elimination arrays in LDS, lane-minor), the
+// models of all samples are packed into LDS and scored VF_HB at a time exactly as the other models' kernel scores its VF_HB.
+// hypcount[h] = 16 score + 15 - (index of the best model): the finish kernel compares the scores and finds the model in the low bits
+__global__ __launch_bounds__(256) void verify_pose_hyp_kernel(const VerifyDev* __restrict__ vs, uint64_t seed, int iters, double thresh) {
+  __shared__ double s_A[VP_A][VF_HB];
+  __shared__ double s_E[VF_HB * VP_MAXM][10];
+  __shared__ int s_nm[VF_HB], s_off[VF_HB + 1], s_cnt[4][VF_HB], s_score[VF_HB * VP_MAXM];
+  const VerifyDev& e = vs[blockIdx.y];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int K = e.nvalid[0];
+  const int h0 = blockIdx.x * VF_HB;
+  if (K < 5) {                                             // the same for every thread of the workgroup
+    if (t < VF_HB && h0 + t < iters) e.hypcount[h0 + t] = -1;
+    return;
+  }
+  double cam[8];
+  for (int c = 0; c < 8; ++c) cam[c] = (double)e.href[c];
+  const double tn = thresh / ((cam[0] + cam[5]) / 2.0), t2 = tn * tn;
+  double E[VP_MAXM][9];
+  int nm = 0;
+  if (t < VF_HB) {
+    if (h0 + t < iters) {
+      int idx[5];
+      ransac_sample5(seed, h0 + t, K, idx);
+      nm = vp_five_point(e.corr, idx, cam, &s_A[0][t], VF_HB, E);
+    }
+    s_nm[t] = nm;
+  }
+  __syncthreads();
+  int off = 0;
+  if (t < VF_HB) {
+    for (int b = 0; b < t; ++b) off += s_nm[b];
+    for (int r = 0; r < nm; ++r)
+      for (int c = 0; c < 9; ++c) s_E[off + r][c] = E[r][c];
+    s_off[t] = off;
+    if (t == VF_HB - 1) s_off[VF_HB] = off + nm;
+  }
+  __syncthreads();
+  const int M = s_off[VF_HB];                              // the same for every thread of the workgroup, at most VF_HB * VP_MAXM
+  for (int g0 = 0; g0 < M; g0 += VF_HB) {
+    int cnt[VF_HB];
+#pragma unroll
+    for (int b = 0; b < VF_HB; ++b) cnt[b] = 0;
+    for (int p0 = 0; p0 < K; p0 += 256) {
+      const int p = p0 + t;
+      const bool have = p < K;
+      double x, y, u, v;
+      vp_norm(e.corr[have ? p : 0], cam, x, y, u, v);
+#pragma unroll
+      for (int b = 0; b < VF_HB; ++b) {
+        if (g0 + b < M) {
+          double F[9];
+#pragma unroll
+          for (int q = 0; q < 9; ++q) F[q] = s_E[g0 + b][q];
+          cnt[b] += have && sampson_in(F, x, y, u, v, t2) ? 1 : 0;
+        }
+      }
+      __syncthreads();                                       // keeps the models in LDS, as in the homography's loop
+    }
+#pragma unroll
+    for (int b = 0; b < VF_HB; ++b) {
+      int s = cnt[b];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+      if (lane == 0) s_cnt[wave][b] = s;
+    }
+    __syncthreads();
+    if (t < VF_HB && g0 + t < M) s_score[g0 + t] = s_cnt[0][t] + s_cnt[1][t] + s_cnt[2][t] + s_cnt[3][t];
+    __syncthreads();
+  }
+  int enc = -1, br = 0;
+  if (t < VF_HB && h0 + t < iters) {
+    int best = -1;
+    for (int r = 0; r < nm; ++r) {
+      const int sc = s_score[off + r];
+      if (sc > best) { best = sc; br = r; }
+    }
+    enc = nm > 0 ? best * 16 + 15 - br : -1;
+    e.hypcount[h0 + t] = enc;
+  }
+  if (t < VF_HB) s_nm[t] = enc;                             // (the model counts were last read before the scoring loop's barriers)
+  __syncthreads();
+  // the best hypothesis of the workgroup -- highest score, lowest h -- leaves its best model for the finish kernel: the best
+  // hypothesis of the set is the best one of its workgroup, so the model that was scored is the model that is refined
+  if (t < VF_HB && enc >= 0) {
+    bool win = true;
+    for (int b = 0; b < VF_HB; ++b) win = win && !((s_nm[b] >> 4) > (enc >> 4) || ((s_nm[b] >> 4) == (enc >> 4) && b < t));
+    if (win) {
+      double* dst = vp_block_model(e, iters, blockIdx.x);
+      for (int c = 0; c < 9; ++c) dst[c] = E[br][c];
+    }
+  }
+}
+
+// v1, v2, v3 of the specification's svd(E) (v3 at the smallest eigenvalue of E^T E), w1 = E v1, w2 = E v2 and their lengths (one thread;
+// S, V: the LDS of vf_jacobi)
+__device__ void vp_svd(const double (&E)[9], double (*S)[9], double (*V)[9], double (&v)[3][3], double (&w)[2][3], double (&s)[2]) {
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) S[i][j] = E[i] * E[j] + E[3 + i] * E[3 + j] + E[6 + i] * E[6 + j];
+  double unused[3];
+  vf_jacobi(S, V, 3, unused);
+  int m = 0;
+  for (int k = 1; k < 3; ++k)
+    if (S[k][k] < S[m][m]) m = k;
+  const int a = m == 0 ? 1 : 0, b = m == 2 ? 1 : 2;
+  for (int k = 0; k < 3; ++k) { v[0][k] = V[k][a]; v[1][k] = V[k][b]; v[2][k] = V[k][m]; }
+  for (int q = 0; q < 2; ++q) {
+    for (int r = 0; r < 3; ++r) w[q][r] = E[3 * r] * v[q][0] + E[3 * r + 1] * v[q][1] + E[3 * r + 2] * v[q][2];
+    s[q] = sqrt(w[q][0] * w[q][0] + w[q][1] * w[q][1] + w[q][2] * w[q][2]);
+  }
+}
+
+// ess(E) of the specification: singular values (1, 1, 0), unit norm; E itself when that fails
+__device__ void vp_ess(double (&E)[9], double (*S)[9], double (*V)[9]) {
+  double v[3][3], w[2][3], s[2];
+  vp_svd(E, S, V, v, w, s);
+  if (!(s[0] > 0.0 && s[1] > 0.0)) return;
+  double G[9];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) G[3 * r + c] = w[0][r] * v[0][c] / s[0] + w[1][r] * v[1][c] / s[1];
+  if (vf_unit(G))
+    for (int c = 0; c < 9; ++c) E[c] = G[c];
+}
+
+// the depth numerators of l1 x1 = l0 R x0 + t by least squares: in front of both cameras iff D > 0, n0 > 0 and n1 > 0
+__device__ __forceinline__ void vp_depths(const double* R, const double* tv, double x, double y, double u, double v, double& n0, double& n1, double& D) {
+  const double a0 = R[0] * x + R[1] * y + R[2], a1 = R[3] * x + R[4] * y + R[5], a2 = R[6] * x + R[7] * y + R[8];
+  const double aa = a0 * a0 + a1 * a1 + a2 * a2, bb = u * u + v * v + 1.0, ab = u * a0 + v * a1 + a2;
+  const double at = a0 * tv[0] + a1 * tv[1] + a2 * tv[2], bt = u * tv[0] + v * tv[1] + tv[2];
+  n0 = ab * bt - bb * at;
+  n1 = bt * aa - ab * at;
+  D = bb * aa - ab * ab;
+}
+
+// one workgroup per pose set: best hypothesis and model, the guarded local optimisation of the fundamental model on camera coordinates
+// with ess() in the place of rank2(), the mask, the four decompositions and the vote of the inliers.  The rule on barriers is the one of
+// verify_finish_kernel: every decision is thread 0's, stored in LDS and read by all threads after the next barrier.
+__global__ __launch_bounds__(1024) void verify_pose_finish_kernel(const VerifyDev* __restrict__ vs, uint64_t seed, int iters, int lo_iters, double thresh) {
+  __shared__ int s_best[16][2];
+  __shared__ double s_acc[16][VF_ACC];
+  __shared__ double f_F[9], f_Fn[9], f_norm[6], f_S[9][9], f_V[9][9], f_nprev;
+  __shared__ double p_R[2][9], p_t[3];
+  __shared__ int f_ok, f_stop, f_rounds, p_root, p_score, p_dec;
+  const VerifyDev& e = vs[blockIdx.x];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int K = e.nvalid[0];
+  double cam[8];
+  for (int c = 0; c < 8; ++c) cam[c] = (double)e.href[c];
+  const double tn = thresh / ((cam[0] + cam[5]) / 2.0), t2 = tn * tn;
+  int bc = -1, bh = 0x7fffffff;
+  // hypcount = 16 score + 15 - model (or -1): the hypotheses compare by score alone (>> 4 keeps -1), the lowest h among equals
+  for (int h = t; h < iters; h += 1024) {
+    const int c = e.hypcount[h];
+    if ((c >> 4) > (bc >> 4)) { bc = c; bh = h; }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    const int oc = __shfl_xor(bc, o, 64), oh = __shfl_xor(bh, o, 64);
+    if ((oc >> 4) > (bc >> 4) || ((oc >> 4) == (bc >> 4) && oh < bh)) { bc = oc; bh = oh; }
+  }
+  if (lane == 0) { s_best[wave][0] = bc; s_best[wave][1] = bh; }
+  __syncthreads();
+  if (t == 0) {
+    f_ok = 0; f_stop = 0; f_rounds = 0; p_dec = 0;
+    for (int w = 1; w < 16; ++w)
+      if ((s_best[w][0] >> 4) > (bc >> 4) || ((s_best[w][0] >> 4) == (bc >> 4) && s_best[w][1] < bh)) { bc = s_best[w][0]; bh = s_best[w][1]; }
+    if (bc >= 0 && K >= 5) {                                 // the model its workgroup of the hypotheses kernel left: nothing is solved again
+      const double* src = vp_block_model(e, iters, bh / VF_HB);
+      for (int c = 0; c < 9; ++c) f_F[c] = src[c];
+      f_ok = 1; p_root = 15 - (bc & 15); p_score = bc >> 4;
+      s_best[0][1] = bh;
+    }
+  }
+  __syncthreads();
+  if (!f_ok) {
+    if (t == 0) {
+      for (int c = 0; c < 8; ++c) e.record[c] = 0.f;
+      e.record[VF_NVALID] = (float)K;
+      e.record[VF_ERR_CORNER] = -1.f;
+      for (int c = 0; c < 24; ++c) e.hom[c] = 0.f;
+    }
+    return;
+  }
+  double F[9];
+  for (int c = 0; c < 9; ++c) F[c] = f_F[c];
+  if (lo_iters > 0) {
+    {  // |I_0|
+      double a[1] = {0.0};
+      for (int p = t; p < K; p += 1024) {
+        double x, y, u, v;
+        vp_norm(e.corr[p], cam, x, y, u, v);
+        a[0] += sampson_in(F, x, y, u, v, t2) ? 1.0 : 0.0;
+      }
+      vf_partials(a, s_acc);
+      __syncthreads();
+      if (t == 0) f_nprev = vf_total(s_acc, 0);
+      __syncthreads();
+    }
+    for (int l = 1; l <= lo_iters; ++l) {
+      // (a) centroids of the inliers of the accepted model
+      {
+        double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int p = t; p < K; p += 1024) {
+          double x, y, u, v;
+          vp_norm(e.corr[p], cam, x, y, u, v);
+          if (sampson_in(F, x, y, u, v, t2)) { a[0] += 1.0; a[1] += x; a[2] += y; a[3] += u; a[4] += v; }
+        }
+        vf_partials(a, s_acc);
+      }
+      __syncthreads();
+      if (t == 0) {
+        const double n = vf_total(s_acc, 0);
+        f_stop = n < 8.0 ? 1 : 0;
+        if (n >= 8.0)
+          for (int c = 0; c < 4; ++c) f_norm[c] = vf_total(s_acc, 1 + c) / n;
+      }
+      __syncthreads();
+      if (f_stop) break;
+      const double cx = f_norm[0], cy = f_norm[1], cu = f_norm[2], cv = f_norm[3];
+      // (b) mean distances to the centroids
+      {
+        double a[3] = {0.0, 0.0, 0.0};
+        for (int p = t; p < K; p += 1024) {
+          double x, y, u, v;
+          vp_norm(e.corr[p], cam, x, y, u, v);
+          if (sampson_in(F, x, y, u, v, t2)) {
+            a[0] += 1.0;
+            a[1] += sqrt((x - cx) * (x - cx) + (y - cy) * (y - cy));
+            a[2] += sqrt((u - cu) * (u - cu) + (v - cv) * (v - cv));
+          }
+        }
+        vf_partials(a, s_acc);
+      }
+      __syncthreads();
+      if (t == 0) {
+        const double n = vf_total(s_acc, 0), m0 = vf_total(s_acc, 1) / n, m1 = vf_total(s_acc, 2) / n;
+        f_norm[4] = m0 == 0.0 ? 1.0 : sqrt(2.0) / m0;
+        f_norm[5] = m1 == 0.0 ? 1.0 : sqrt(2.0) / m1;
+      }
+      __syncthreads();
+      const double sc0 = f_norm[4], sc1 = f_norm[5];
+      // (c) the 9 x 9 matrix of sums over the normalised inliers, its smallest eigenvector, back to camera coordinates, ess()
+      {
+        double acc[45];
+        for (int c = 0; c < 45; ++c) acc[c] = 0.0;
+        for (int p = t; p < K; p += 1024) {
+          double x, y, u, v;
+          vp_norm(e.corr[p], cam, x, y, u, v);
+          if (sampson_in(F, x, y, u, v, t2)) vf_epipolar_add(acc, (x - cx) * sc0, (y - cy) * sc0, (u - cu) * sc1, (v - cv) * sc1);
+        }
+        vf_partials(acc, s_acc);
+      }
+      __syncthreads();
+      if (t == 0) {
+        int q = 0;
+        for (int i = 0; i < 9; ++i)
+          for (int j = i; j < 9; ++j) {
+            const double s = vf_total(s_acc, q);
+            f_S[i][j] = s; f_S[j][i] = s;
+            ++q;
+          }
+        double fn[9], Fd[9];
+        vf_jacobi(f_S, f_V, 9, fn);
+        vf_denormalise(fn, cx, cy, sc0, cu, cv, sc1, Fd);
+        bool ok = vf_unit(Fd);
+        if (ok) {
+          vp_ess(Fd, f_S, f_V);
+          for (int c = 0; c < 9; ++c) f_Fn[c] = Fd[c];
+        }
+        f_stop = ok ? 0 : 1;
+      }
+      __syncthreads();
+      if (f_stop) break;
+      double Fc[9];
+      for (int c = 0; c < 9; ++c) Fc[c] = f_Fn[c];
+      // (d) the candidate's inliers against the accepted model's
+      {
+        double a[2] = {0.0, 0.0};
+        for (int p = t; p < K; p += 1024) {
+          double x, y, u, v;
+          vp_norm(e.corr[p], cam, x, y, u, v);
+          const bool was = sampson_in(F, x, y, u, v, t2), is = sampson_in(Fc, x, y, u, v, t2);
+          a[0] += is ? 1.0 : 0.0;
+          a[1] += is != was ? 1.0 : 0.0;
+        }
+        vf_partials(a, s_acc);
+      }
+      __syncthreads();
+      if (t == 0) {
+        const double n = vf_total(s_acc, 0), changed = vf_total(s_acc, 1);
+        if (n < f_nprev) {
+          f_stop = 1;                                     // fewer inliers: keep E_{l-1}
+        } else {
+          for (int c = 0; c < 9; ++c) f_F[c] = f_Fn[c];
+          f_nprev = n;
+          f_rounds = f_rounds + 1;
+          f_stop = changed == 0.0 ? 2 : 0;                // accepted; the same set again: converged
+        }
+      }
+      __syncthreads();
+      const int stop = f_stop;
+      if (stop != 1)
+        for (int c = 0; c < 9; ++c) F[c] = Fc[c];
+      if (stop) break;
+    }
+  }
+  // every path above ends behind a barrier that follows thread 0's last stores to f_F and f_rounds.  Thread 0: no accepted round -> ess()
+  // of the best model; the sign rule; the decompositions
+  if (t == 0) {
+    double G[9];
+    for (int c = 0; c < 9; ++c) G[c] = f_F[c];
+    if (f_rounds == 0) vp_ess(G, f_S, f_V);
+    int m = 0;
+    for (int c = 1; c < 9; ++c)
+      if (fabs(G[c]) > fabs(G[m])) m = c;
+    const double sg = G[m] < 0.0 ? -1.0 : 1.0;
+    for (int c = 0; c < 9; ++c) { G[c] = sg * G[c]; f_F[c] = G[c]; }
+    double v[3][3], w[2][3], s[2];
+    vp_svd(G, f_S, f_V, v, w, s);
+    if (s[0] > 0.0 && s[1] > 0.0) {
+      double u1[3], u2[3], u3[3];
+      for (int k = 0; k < 3; ++k) { u1[k] = w[0][k] / s[0]; u2[k] = w[1][k] / s[1]; }
+      u3[0] = u1[1] * u2[2] - u1[2] * u2[1]; u3[1] = u1[2] * u2[0] - u1[0] * u2[2]; u3[2] = u1[0] * u2[1] - u1[1] * u2[0];
+      const double n3 = sqrt(u3[0] * u3[0] + u3[1] * u3[1] + u3[2] * u3[2]);
+      if (n3 > 0.0) {
+        for (int k = 0; k < 3; ++k) u3[k] = u3[k] / n3;
+        const double c0 = v[0][1] * v[1][2] - v[0][2] * v[1][1], c1 = v[0][2] * v[1][0] - v[0][0] * v[1][2], c2 = v[0][0] * v[1][1] - v[0][1] * v[1][0];
+        const double sv = c0 * v[2][0] + c1 * v[2][1] + c2 * v[2][2] < 0.0 ? -1.0 : 1.0;
+        for (int r = 0; r < 3; ++r)
+          for (int c = 0; c < 3; ++c) {
+            const double uv = u3[r] * (sv * v[2][c]);
+            p_R[0][3 * r + c] = u2[r] * v[0][c] - u1[r] * v[1][c] + uv;
+            p_R[1][3 * r + c] = u1[r] * v[1][c] - u2[r] * v[0][c] + uv;
+          }
+        for (int k = 0; k < 3; ++k) p_t[k] = u3[k];
+        p_dec = 1;
+      }
+    }
+  }
+  __syncthreads();
+  for (int c = 0; c < 9; ++c) F[c] = f_F[c];
+  const int dec = p_dec;
+  {
+    double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    double Ra[9], Rb[9], tv[3];
+    for (int c = 0; c < 9; ++c) { Ra[c] = dec ? p_R[0][c] : 0.0; Rb[c] = dec ? p_R[1][c] : 0.0; }
+    for (int c = 0; c < 3; ++c) tv[c] = dec ? p_t[c] : 0.0;
+    for (int p = t; p < K; p += 1024) {
+      double x, y, u, v;
+      vp_norm(e.corr[p], cam, x, y, u, v);
+      const bool in = sampson_in(F, x, y, u, v, t2);
+      e.inlier[e.rows[p]] = in ? 1 : 0;
+      if (in) {
+        a[0] += 1.0;
+        double n0, n1, D;
+        vp_depths(Ra, tv, x, y, u, v, n0, n1, D);
+        a[1] += D > 0.0 && n0 > 0.0 && n1 > 0.0 ? 1.0 : 0.0;
+        a[2] += D > 0.0 && n0 < 0.0 && n1 < 0.0 ? 1.0 : 0.0;
+        vp_depths(Rb, tv, x, y, u, v, n0, n1, D);
+        a[3] += D > 0.0 && n0 > 0.0 && n1 > 0.0 ? 1.0 : 0.0;
+        a[4] += D > 0.0 && n0 < 0.0 && n1 < 0.0 ? 1.0 : 0.0;
+      }
+    }
+    vf_partials(a, s_acc);
+  }
+  __syncthreads();
+  if (t == 0) {
+    e.record[VF_NVALID] = (float)K;
+    e.record[VF_OK] = 1.f;
+    e.record[VF_NINLIERS] = (float)vf_total(s_acc, 0);
+    e.record[VF_BEST_HYP] = (float)s_best[0][1];
+    e.record[VF_BEST_HYP_INLIERS] = (float)p_score;
+    e.record[VF_LO_ROUNDS] = (float)f_rounds;
+    e.record[VF_ERR_CORNER] = -1.f;
+    e.record[VF_RESERVED] = 0.f;
+    for (int c = 0; c < 9; ++c) e.hom[c] = (float)F[c];
+    int w = 0;
+    double votes = vf_total(s_acc, 1);
+    for (int q = 1; q < 4; ++q) {
+      const double vq = vf_total(s_acc, 1 + q);
+      if (vq > votes) { votes = vq; w = q; }
+    }
+    const double st = (w & 1) ? -1.0 : 1.0;
+    for (int c = 0; c < 9; ++c) e.hom[9 + c] = dec ? (float)p_R[w >> 1][c] : 0.f;
+    for (int c = 0; c < 3; ++c) e.hom[18 + c] = dec ? (float)(st * p_t[c]) : 0.f;
+    e.hom[21] = dec ? (float)votes : 0.f;
+    e.hom[22] = (float)p_root;
+    e.hom[23] = 0.f;
+  }
+}
+
 // The workspace of gims_verify_pairs: the VerifyDev table, then per set the dense correspondences, their rows, the hypothesis counters and K.
 // recs == nullptr: sizing only.
+// The table holds the sets without the pose model first (recs[0 .. n_other - 1], in their order) and the pose sets after them, so that
+// each pair of kernels runs over its own contiguous part; every set finds its outputs through its pointers.
 static void verify_layout(const gims_verify_set* sets, int n_sets, int iters, WsLayout& L, VerifyDev* recs) {
   L.take<VerifyDev>(n_sets);
+  int n_other = 0;
+  for (int i = 0; i < n_sets; ++i) n_other += sets[i].model == GIMS_VERIFY_MODEL_POSE ? 0 : 1;
+  int at_other = 0, at_pose = n_other;
   for (int i = 0; i < n_sets; ++i) {
     const gims_verify_set& p = sets[i];
     VerifyDev d;
     memset(&d, 0, sizeof(d));
     d.corr = L.take<float4>(p.n0);
     d.rows = L.take<int32_t>(p.n0);
-    d.hypcount = L.take<int32_t>(iters);
+    // a pose set keeps, behind its counters, the best model (9 doubles) of every workgroup of the hypotheses kernel
+    d.hypcount = L.take<int32_t>(p.model == GIMS_VERIFY_MODEL_POSE ? (size_t)iters + 2 + 18 * (size_t)cdiv(iters, VF_HB) : (size_t)iters);
     d.nvalid = L.take<int32_t>(64);
     if (!recs) continue;
     d.kp0 = p.kpts0; d.kp1 = p.kpts1; d.matches0 = p.matches0;
     d.n0 = p.n0; d.n1 = p.n1; d.height = p.height; d.width = p.width; d.has_ref = p.has_ref ? 1 : 0; d.model = p.model;
     memcpy(d.href, p.h_ref, sizeof(d.href));
     d.inlier = p.inlier; d.record = p.record; d.hom = p.homography;
-    recs[i] = d;
+    recs[p.model == GIMS_VERIFY_MODEL_POSE ? at_pose++ : at_other++] = d;
   }
 }
 
@@ -903,13 +1643,25 @@ extern "C" int gims_verify_pairs(const gims_verify_set* sets, int32_t n_sets, fl
   GIMS_CHECK_ARG(n_sets <= 65535, "gims_verify_pairs: %d sets in one call (at most 65535)", n_sets);
   GIMS_CHECK_ARG(iters >= 0 && iters <= (1 << 20) && lo_iters >= 0 && lo_iters <= 1024, "gims_verify_pairs: bad iteration counts");
   GIMS_CHECK_ARG(thresh >= 0.f && isfinite(thresh), "gims_verify_pairs: the threshold must be finite and not negative");
+  int n_pose = 0;
   for (int i = 0; i < n_sets; ++i) {
     const gims_verify_set& p = sets[i];
     GIMS_CHECK_ARG(p.n0 >= 0 && p.n1 >= 0 && (p.n0 == 0 || (p.kpts0 && p.inlier)) && (p.n1 == 0 || p.kpts1) && p.record && p.homography,
                    "gims_verify_pairs: set %d has a negative shape or a null pointer", i);
     GIMS_CHECK_ARG(p.matches0 || p.n0 == p.n1, "gims_verify_pairs: set %d has no matches0 (identity pairing) but n0 = %d != n1 = %d", i, p.n0, p.n1);
-    GIMS_CHECK_ARG(p.model == GIMS_VERIFY_MODEL_HOMOGRAPHY || p.model == GIMS_VERIFY_MODEL_FUNDAMENTAL,
-                   "gims_verify_pairs: set %d has model = %d (GIMS_VERIFY_MODEL_HOMOGRAPHY or GIMS_VERIFY_MODEL_FUNDAMENTAL)", i, p.model);
+    GIMS_CHECK_ARG(p.model == GIMS_VERIFY_MODEL_HOMOGRAPHY || p.model == GIMS_VERIFY_MODEL_FUNDAMENTAL || p.model == GIMS_VERIFY_MODEL_POSE,
+                   "gims_verify_pairs: set %d has model = %d (GIMS_VERIFY_MODEL_HOMOGRAPHY, GIMS_VERIFY_MODEL_FUNDAMENTAL or GIMS_VERIFY_MODEL_POSE)", i,
+                   p.model);
+    if (p.model == GIMS_VERIFY_MODEL_POSE) {
+      GIMS_CHECK_ARG(!p.has_ref && p.h_ref[8] == 0.f,
+                     "gims_verify_pairs: set %d has model = pose: h_ref carries the intrinsics, so has_ref and h_ref[8] must be 0", i);
+      bool cam_ok = true;
+      for (int c = 0; c < 8; ++c) cam_ok = cam_ok && isfinite(p.h_ref[c]);
+      cam_ok = cam_ok && p.h_ref[0] > 0.f && p.h_ref[1] > 0.f && p.h_ref[4] > 0.f && p.h_ref[5] > 0.f;
+      GIMS_CHECK_ARG(cam_ok, "gims_verify_pairs: set %d has model = pose and intrinsics that are not finite, or a focal length that is not positive", i);
+      GIMS_CHECK_ARG(p.n0 < (1 << 27), "gims_verify_pairs: set %d has model = pose and n0 = %d (at most 2^27 - 1)", i, p.n0);
+      ++n_pose;
+    }
     GIMS_CHECK_ARG(p.model != GIMS_VERIFY_MODEL_FUNDAMENTAL || !p.has_ref,
                    "gims_verify_pairs: set %d has model = fundamental and a reference homography (has_ref): there is no error column for F", i);
   }
@@ -923,8 +1675,16 @@ extern "C" int gims_verify_pairs(const gims_verify_set* sets, int32_t n_sets, fl
   const VerifyDev* dev = (const VerifyDev*)work;
   const double t2 = (double)thresh * (double)thresh;
   hipLaunchKernelGGL(verify_gather_kernel, dim3(n_sets), dim3(1024), 0, s, dev);
-  if (iters > 0) hipLaunchKernelGGL(verify_hyp_kernel, dim3(cdiv(iters, VF_HB), n_sets), dim3(256), 0, s, dev, seed, iters, t2);
-  hipLaunchKernelGGL(verify_finish_kernel, dim3(n_sets), dim3(1024), 0, s, dev, seed, iters, lo_iters, t2);
+  const int n_other = n_sets - n_pose;
+  if (n_other > 0) {
+    if (iters > 0) hipLaunchKernelGGL(verify_hyp_kernel, dim3(cdiv(iters, VF_HB), n_other), dim3(256), 0, s, dev, seed, iters, t2);
+    hipLaunchKernelGGL(verify_finish_kernel, dim3(n_other), dim3(1024), 0, s, dev, seed, iters, lo_iters, t2);
+  }
+  if (n_pose > 0) {
+    if (iters > 0)
+      hipLaunchKernelGGL(verify_pose_hyp_kernel, dim3(cdiv(iters, VF_HB), n_pose), dim3(256), 0, s, dev + n_other, seed, iters, (double)thresh);
+    hipLaunchKernelGGL(verify_pose_finish_kernel, dim3(n_pose), dim3(1024), 0, s, dev + n_other, seed, iters, lo_iters, (double)thresh);
+  }
   GIMS_LAUNCH_CHECK();
   return GIMS_OK;
 }

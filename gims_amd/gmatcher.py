@@ -1296,12 +1296,18 @@ class GMatcher(nn.Module):
         the verified homography, the quantity parameter_search.py:161-165 records), ``homography`` [3, 3] and ``inlier`` [kept0] uint8 -- one
         ``verify_pairs`` call per sub-batch, no extra host synchronisation; ``0 / None / None`` on a record with ``error``.  With
         ``model='fundamental'`` (a camera that moved through a 3-D scene) the inliers are those of the fundamental matrix and the record
-        carries it as ``fundamental`` in place of ``homography``."""
-        if verify is not None and (not isinstance(verify, dict) or set(verify) - {"thresh", "iters", "lo_iters", "seed", "model"}):
-            raise ValueError("verify must be None or a dict with keys among thresh, iters, lo_iters, seed, model")
-        if verify is not None and verify.get("model", "homography") not in ("homography", "fundamental", 0, 1):
-            raise ValueError("verify['model'] must be 'homography' or 'fundamental'")
-        vkey = "fundamental" if verify is not None and verify.get("model", "homography") in ("fundamental", 1) else "homography"
+        carries it as ``fundamental`` in place of ``homography``.  With ``model='pose'`` and ``intrinsics=(K0, K1)`` (calibrated cameras)
+        the inliers are those of the essential matrix, carried as ``essential``, and the record also has the relative pose ``R`` [3, 3]
+        and ``t`` [3] (``gims_amd.verify.verify_pairs``)."""
+        if verify is not None and (not isinstance(verify, dict) or set(verify) - {"thresh", "iters", "lo_iters", "seed", "model", "intrinsics"}):
+            raise ValueError("verify must be None or a dict with keys among thresh, iters, lo_iters, seed, model, intrinsics")
+        vmodel = verify.get("model", "homography") if verify is not None else "homography"
+        if isinstance(vmodel, bool) or vmodel not in ("homography", "fundamental", "pose", 0, 1, 3):
+            raise ValueError("verify['model'] must be 'homography', 'fundamental' or 'pose'")
+        vpose = vmodel in ("pose", 3)
+        if verify is not None and vpose != (verify.get("intrinsics") is not None):
+            raise ValueError("verify['intrinsics'] = (K0, K1) goes with verify['model'] = 'pose', and only with it")
+        vkey = "essential" if vpose else "fundamental" if vmodel in ("fundamental", 1) else "homography"
         self._check_call(data, {})
         if data['keypoints0'].shape[0] != 1:
             raise ValueError("sweep takes one single-pair dict (B == 1)")
@@ -1347,6 +1353,8 @@ class GMatcher(nn.Module):
                                error=None, result=None)
                     if verify is not None:
                         rec.update({'correct_matches': 0, vkey: None, 'inlier': None})
+                        if vpose:
+                            rec.update({'R': None, 't': None})
                     records[c0 + j] = rec
                     if j in dropped:
                         rec["error"] = "ValueError: need at least one array to concatenate"
@@ -1371,4 +1379,6 @@ class GMatcher(nn.Module):
                     col = hip.VERIFY_FIELDS.index("n_inliers")
                     for q, (rec, _, _) in enumerate(live):
                         rec.update({'correct_matches': v["records"][q, col], vkey: v["models"][q], 'inlier': v["inlier"][q]})
+                        if vpose:
+                            rec.update({'R': v["R"][q], 't': v["t"][q]})
         return records

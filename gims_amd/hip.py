@@ -672,7 +672,9 @@ def eval_pairs(items, dist_thresh=3.0, n_iters=3, ransac_thresh=3.0, ransac_iter
 
 # ------------------------------------------------------------------------------------------------ geometric verification
 VERIFY_FIELDS = ("n_valid", "ok", "n_inliers", "best_hyp", "best_hyp_inliers", "lo_rounds", "err_corner")
-VERIFY_MODELS = {"homography": _K["GIMS_VERIFY_MODEL_HOMOGRAPHY"], "fundamental": _K["GIMS_VERIFY_MODEL_FUNDAMENTAL"]}
+VERIFY_MODELS = {"homography": _K["GIMS_VERIFY_MODEL_HOMOGRAPHY"], "fundamental": _K["GIMS_VERIFY_MODEL_FUNDAMENTAL"],
+                 "pose": _K["GIMS_VERIFY_MODEL_POSE"]}
+VERIFY_POSE_FLOATS = 24                  # what the `homography` output of a pose set receives: E[9], R[9], t[3], n_front, root, 0
 
 
 def verify_model(model) -> int:
@@ -681,14 +683,15 @@ def verify_model(model) -> int:
         return VERIFY_MODELS[model]
     if isinstance(model, (int, np.integer)) and not isinstance(model, bool) and int(model) in VERIFY_MODELS.values():
         return int(model)
-    raise GimsHipError(f"verify_pairs: model must be 'homography' (0) or 'fundamental' (1), not {model!r}")
+    raise GimsHipError(f"verify_pairs: model must be 'homography' (0), 'fundamental' (1) or 'pose' (3), not {model!r}")
 
 
 def verify_pairs(items, thresh=3.0, iters=3000, lo_iters=8, seed=0, work=None):
     """items: list of dicts with device tensors kpts0 [n0,2] f32, kpts1 [n1,2] f32, matches0 [n0] int64 or None (identity pairing, n0 == n1),
-    optionally h_ref (3x3 array-like) with height / width, optionally model ('homography' / 0, the default, or 'fundamental' / 1; per item,
-    one call may mix both; h_ref with 'fundamental' is refused by the library), and outputs inlier [n0] uint8, record [8] f32 (VERIFY_FIELDS), homography [9] f32
-    (the fundamental matrix F, x1^T F x0 = 0, when that is the model).
+    optionally h_ref (3x3 array-like) with height / width, optionally model ('homography' / 0, the default, 'fundamental' / 1 or 'pose' / 3;
+    per item, one call may mix them; h_ref with 'fundamental' is refused by the library), and outputs inlier [n0] uint8, record [8] f32 (VERIFY_FIELDS), homography [9] f32
+    (the fundamental matrix F, x1^T F x0 = 0, when that is the model).  An item with model 'pose' carries intrinsics=(K0, K1), two 3x3
+    array-likes, in the place of h_ref, and its `homography` output has VERIFY_POSE_FLOATS = 24 floats: E[9], R[9], t[3], n_front, root, 0.
     One batched asynchronous call; returns the workspace (keep it alive until the stream has passed the call).  See include/gims_hip.h."""
     lib = load()
     arr = (VerifySet * len(items))()
@@ -706,6 +709,15 @@ def verify_pairs(items, thresh=3.0, iters=3000, lo_iters=8, seed=0, work=None):
         h_ref = it.get("h_ref")
         model = verify_model(it.get("model", 0))
         h = np.asarray(h_ref, dtype=np.float32).reshape(9) if h_ref is not None else np.zeros(9, dtype=np.float32)
+        if model == VERIFY_MODELS["pose"]:
+            if h_ref is not None or it.get("intrinsics") is None or len(it["intrinsics"]) != 2:
+                raise GimsHipError("verify_pairs: model 'pose' takes intrinsics=(K0, K1) and no h_ref")
+            if it["homography"].numel() < VERIFY_POSE_FLOATS or not it["homography"].is_contiguous():
+                raise GimsHipError("verify_pairs: the homography output of model 'pose' has 24 contiguous floats (E, R, t, n_front, root, 0)")
+            k0m, k1m = (np.asarray(k, dtype=np.float64).reshape(3, 3) for k in it["intrinsics"])
+            h = np.array([k0m[0, 0], k0m[1, 1], k0m[0, 2], k0m[1, 2], k1m[0, 0], k1m[1, 1], k1m[0, 2], k1m[1, 2], 0.0], dtype=np.float32)
+        elif it.get("intrinsics") is not None:
+            raise GimsHipError("verify_pairs: intrinsics are read with model 'pose' only")
         arr[i] = VerifySet(_p(k0) if n0 else None, _p(k1) if n1 else None, _p(m0), n0, n1, int(it.get("height", 0)), int(it.get("width", 0)),
                            int(h_ref is not None), model, (C.c_float * 9)(*h.tolist()), _p(it["inlier"]) if n0 else None, _p(it["record"]),
                            _p(it["homography"]))

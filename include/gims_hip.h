@@ -553,16 +553,82 @@ int gims_eval_pairs(const gims_eval_pair* h_pairs /* HOST array */, int32_t n_pa
  *     negative; GIMS_VERIFY_ERR_CORNER is always -1.  has_ref != 0 with this model, or a model other than the two below, is GIMS_EINVAL
  *     (checked before anything is enqueued).  A set with model == GIMS_VERIFY_MODEL_HOMOGRAPHY computes exactly what it did before the
  *     field had a meaning.
+ *
+ * The calibrated RELATIVE-POSE model (model == GIMS_VERIFY_MODEL_POSE = 3; selected per set, one call may mix all three models) -- what
+ *   the reference's estimate_pose (utils/common.py:392-416: cv2.findEssentialMat + cv2.recoverPose) gives a caller with calibrated
+ *   cameras: an essential matrix E, the pose (R, t) with x1 ~ R x0 + t, and the inliers.  The value 2 stays refused: it was kept for an
+ *   essential matrix derived from the 8-point F, and that is no estimator -- on a planar or plane-dominated scene (this project's own
+ *   data) the 8-point system loses rank and its E is arbitrary, while five points determine E there.  So the model is a FIVE-POINT
+ *   estimator of this build's own; parity with OpenCV is not claimed; its SPECIFICATION is this comment (restated in tests/pose_ref.py).
+ *   Everything is float64 (the intrinsics and the coordinates are read as float32 and widened).
+ *   Inputs: h_ref[0..7] = fx0, fy0, cx0, cy0, fx1, fy1, cx1, cy1, h_ref[8] = 0, has_ref = 0.  A focal length or centre that is not finite,
+ *     a focal length <= 0, has_ref != 0, h_ref[8] != 0 or n0 >= 2^27 is GIMS_EINVAL before anything is enqueued.  Correspondences:
+ *     gathered exactly as above, then normalised to camera coordinates x = (x - cx0) / fx0, y = (y - cy0) / fy0, u = (u - cx1) / fx1,
+ *     v = (v - cy1) / fy1.  E is row-major and x1^T E x0 = 0 for x0 = (x, y, 1), x1 = (u, v, 1).
+ *   Threshold: thresh is in pixels; the model uses tn = thresh / f_mean with the reference's own f_mean = (fx0 + fy1) / 2
+ *     (utils/common.py:396) and the inlier test inlier(E, x, y, u, v) of the fundamental model with tn in the place of thresh.
+ *   Stage 1: hypothesis h takes FIVE distinct indices from the sampler's stream (the first four are the homography's sample).  Row k of
+ *     the 5 x 9 system is (u x, u y, u, v x, v y, v, x, y, 1).  Gauss-Jordan elimination with complete pivoting exactly as for F, five
+ *     pivots; the four columns left over, ascending, are the free columns c_0 .. c_3.  Basis vector j has b_j[c_j] = 1, b_j[c_i] = 0 for
+ *     the other free columns and b_j[pc] = -A[p][c_j] / A[p][pc] for the five pivots; X, Y, Z, W = b_0 .. b_3 and E = x X + y Y + z Z + W,
+ *     so every entry of E is a linear form in (x, y, z, 1).  No model when a pivot is 0 or anything is not finite.
+ *     The ten cubic constraints, in this order: det E = E00 (E11 E22 - E12 E21) - E01 (E10 E22 - E12 E20) + E02 (E10 E21 - E11 E20), then
+ *     the nine entries of 2 (E E^T) E - tr(E E^T) E by rows; each is built by products of the linear forms (linear x linear -> the ten
+ *     quadratic monomials, quadratic x linear -> the twenty cubic ones).  Their coefficients form a 10 x 20 matrix whose columns are
+ *       x^3 y^3 x^2y xy^2 | x^2z x^2 | y^2z y^2 | xyz xy | xz^2 xz x | yz^2 yz y | z^3 z^2 z 1      (columns 0 .. 19).
+ *     Gauss-Jordan over the columns 0 .. 9 in this order: the pivot of column c is the entry of largest magnitude of that column among
+ *     the rows that held no pivot yet (the first such), the elimination fails when it is 0 or not finite; every OTHER row r becomes
+ *     row r - (A[r][c] / pivot) * row p over all twenty columns.
+ *     The hidden variable is PIVOTED: matrix and elimination are formed for the three orders (X, Y, Z) = (b_0, b_1, b_2), (b_0, b_2, b_1),
+ *     (b_2, b_1, b_0) of the basis (W = b_3 always); the quality of an order is the smallest of its ten pivot magnitudes, -1 when its
+ *     elimination fails; the order of largest quality (the first such) is the one used from here on, no model when all three fail.
+ *     (With a fixed order, samples with four or five points on one plane lose the planted E by 1e-4 to 1e-2.)  With a, b = the rows of the pivots of the columns (4, 5), (6, 7), (8, 9),
+ *     each divided by its pivot, a - z b has no quadratic term in (x, y): it is x p(z) + y q(z) + r(z) with (ascending powers of z)
+ *       p = (a12, a11 - b12, a10 - b11, -b10), q = (a15, a14 - b15, a13 - b14, -b13), r = (a19, a18 - b19, a17 - b18, a16 - b17, -b16).
+ *     The three rows form a 3 x 3 matrix B(z) of polynomials with B(z) (x, y, 1)^T = 0; its determinant, expanded along the first row, is
+ *     the polynomial c_0 + c_1 z + .. + c_10 z^10.  No model when c_10 is 0 or a coefficient is not finite.
+ *     Real roots: bound = 1 + max_i |c_i / c_10|.  For d = 1 .. 10, q_d = the (10 - d)-th derivative of the polynomial (coefficient i is
+ *     c_{i+10-d} (i + 10 - d)! / i!); its roots are sought in the intervals between -bound, the roots of q_{d-1} (ascending) and bound:
+ *     an interval [a, b] holds a root iff (q_d(a) > 0) != (q_d(b) > 0); then 80 times m = (a + b) / 2 replaces the end at which
+ *     (q_d > 0) is what it is at m, and the root is the last (a + b) / 2.  Polynomials are evaluated by Horner's rule.  The roots of q_10
+ *     are the real roots of the polynomial, ascending, at most ten.  (A root of even multiplicity is not found.)
+ *     Each root z gives one model: of the cross products of the row pairs (0, 1), (0, 2), (1, 2) of B(z) the one whose third component
+ *     is largest in magnitude (the first such) is n; x = n0 / n2, y = n1 / n2; E = unit(x X + y Y + z Z + W); the root gives no model
+ *     when n2 is 0 or unit() fails.  The models of a hypothesis are numbered 0, 1, .. in ascending root order.
+ *     score(h) = the largest number of inliers of one of its models, the lowest model among equals; -1 without a model.  best = highest
+ *     score, lowest h among equals.  K < 5, iters == 0 or no hypothesis with a model: ok = 0 and zeros, as above.
+ *   ess(E), the projection onto the essential manifold: (d, V) = the diagonal and the eigenvector matrix of jacobi(E^T E); v3 = the
+ *     column of V at the smallest d (the first such), v1, v2 = the two other columns in ascending index; w_i = E v_i, s_i = |w_i|;
+ *     E' = unit(w1 v1^T / s1 + w2 v2^T / s2) (singular values 1, 1, 0 up to the unit norm); E itself when s1 or s2 is 0 or unit() fails.
+ *   Stage 2, lo_iters == 0: the model is ess(E_best) and the mask is taken under it.
+ *   Stage 2, lo_iters >= 1: the guarded local optimisation of the fundamental model on camera coordinates -- the similarities of the
+ *     inliers, the 45 sums, jacobi(S), denormalise, unit -- with ess() in the place of rank2(), the stop at fewer than 8 inliers and the
+ *     same acceptance: a round is accepted only while the inlier count does not fall.  When no round was accepted the model and the
+ *     mask are those of lo_iters == 0.  On plane-dominated inliers the linear 9 x 9 refit is degenerate like the 8-point system; the
+ *     guard is what keeps the five-point model there (the refit's candidate loses inliers and is dropped).
+ *   Stage 3, the pose of the returned E (after the sign rule below): v1, v2, v3, w1, w2, s1, s2 as in ess(E); u1 = w1 / s1, u2 = w2 / s2,
+ *     u3 = u1 x u2 divided by its length; v3 is negated when (v1 x v2) . v3 < 0.  Ra = u2 v1^T - u1 v2^T + u3 v3^T and
+ *     Rb = u1 v2^T - u2 v1^T + u3 v3^T (U W V^T and U W^T V^T for W = [0 -1 0; 1 0 0; 0 0 1]: det = +1); the four candidates are, in this
+ *     order, (Ra, u3), (Ra, -u3), (Rb, u3), (Rb, -u3).  No pose (R, t and n_front are 0) when s1 or s2 or |u1 x u2| is 0.
+ *     Triangulation of an inlier under (R, t): a = R x0; the least-squares depths of l1 x1 = l0 a + t have the numerators
+ *     n0 = (x1.a)(x1.t) - (x1.x1)(a.t), n1 = (x1.t)(a.a) - (x1.a)(a.t) over D = (x1.x1)(a.a) - (x1.a)^2; the inlier votes for the
+ *     candidate iff D > 0, n0 > 0 and n1 > 0 (for -t both numerators change sign).  The pose is the candidate with the most votes, the
+ *     lowest index among equals; n_front is its number of votes.
+ *   Outputs: the `homography` pointer of a pose set receives 24 floats: E[9] (unit Frobenius norm, negated when its entry of largest
+ *     magnitude, the first such, is negative), R[9] row-major, t[3] (unit norm), n_front, the index of the best model among the models
+ *     of the best hypothesis, 0.  The record keeps its seven columns; GIMS_VERIFY_ERR_CORNER is always -1.  A set with another model
+ *     computes exactly the bytes it computed before this model existed.
  */
 #define GIMS_VERIFY_MODEL_HOMOGRAPHY 0
 #define GIMS_VERIFY_MODEL_FUNDAMENTAL 1
+#define GIMS_VERIFY_MODEL_POSE 3
 typedef struct gims_verify_set {
   const float* kpts0; const float* kpts1;   /* [n0][2], [n1][2] */
   const int64_t* matches0;                  /* [n0], or NULL: identity pairing */
   int32_t n0, n1, height, width;            /* image 0 size for the corner error (read with has_ref only) */
   int32_t has_ref, model;                   /* model: GIMS_VERIFY_MODEL_* */
-  float h_ref[9];                           /* reference homography, row-major (read with has_ref only) */
-  uint8_t* inlier; float* record; float* homography;
+  float h_ref[9];                           /* reference homography, row-major (read with has_ref only); model 3: the intrinsics */
+  uint8_t* inlier; float* record; float* homography;     /* homography: 9 floats; model 3: 24 floats */
 } gims_verify_set;
 #define GIMS_VERIFY_NVALID 0            /* K */
 #define GIMS_VERIFY_OK 1

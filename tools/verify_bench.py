@@ -20,6 +20,9 @@ launches are queued (the start event is reached when that product ends).  What i
 of a two-view scene (random 3-D points at depth 4 .. 12 in front of two pinhole cameras, a rotation of a few degrees and a translation),
 variants ``fundamental_lo0`` and ``fundamental_lo8``; the evaluation route has no such model and is left out.
 
+``--model pose`` measures the calibrated relative-pose model on the same two-view scenes (focal length 700, principal point at the
+centre of the canvas), variants ``pose_lo0`` and ``pose_lo8``, with the threshold of the fundamental run (3 px).
+
 Prints one JSON line (median, min, max in ms per variant, and the inlier totals of the two verify variants)."""
 import argparse
 import json
@@ -98,17 +101,21 @@ def main(argv=None):
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--seed", type=int, default=7000)
-    ap.add_argument("--model", choices=("homography", "fundamental"), default="homography")
+    ap.add_argument("--model", choices=("homography", "fundamental", "pose"), default="homography")
     ap.add_argument("-o", "--output", default=None, help="also write the JSON record to this file")
     args = ap.parse_args(argv)
     dev = torch.device("cuda", torch.cuda.current_device())
-    fundamental = args.model == "fundamental"
-    datas, outs = (make_two_view_sets if fundamental else make_sets)(args.sets, args.points, args.seed, dev)
+    two_view = args.model in ("fundamental", "pose")
+    datas, outs = (make_two_view_sets if two_view else make_sets)(args.sets, args.points, args.seed, dev)
+    cam = np.array([[700.0, 0, CANVAS[0] / 2], [0, 700.0, CANVAS[1] / 2], [0, 0, 1]])
     eye = [np.eye(3, dtype=np.float32)] * args.sets
     variants = {
+        "pose_lo0": lambda: verify_pairs(datas, outs, thresh=3.0, iters=args.iters, lo_iters=0, seed=0, model="pose", intrinsics=(cam, cam)),
+        "pose_lo8": lambda: verify_pairs(datas, outs, thresh=3.0, iters=args.iters, lo_iters=8, seed=0, model="pose", intrinsics=(cam, cam)),
+    } if args.model == "pose" else {
         "fundamental_lo0": lambda: verify_pairs(datas, outs, thresh=3.0, iters=args.iters, lo_iters=0, seed=0, model="fundamental"),
         "fundamental_lo8": lambda: verify_pairs(datas, outs, thresh=3.0, iters=args.iters, lo_iters=8, seed=0, model="fundamental"),
-    } if fundamental else {
+    } if two_view else {
         "eval": lambda: evalh.evaluate_pairs(datas, outs, eye, ransac_thresh=3.0, ransac_iters=args.iters, seed=0),
         "eval_nogt": lambda: evalh.evaluate_pairs(datas, outs, eye, n_iters=0, ransac_thresh=3.0, ransac_iters=args.iters, seed=0),
         "verify_lo0": lambda: verify_pairs(datas, outs, thresh=3.0, iters=args.iters, lo_iters=0, seed=0),
@@ -149,8 +156,10 @@ def main(argv=None):
                correspondences_mean=float(np.mean([int((o["matches0"] > -1).sum()) for o in outs[:16]])),
                ms={k: dict(median=round(float(np.median(v)), 3), min=round(min(v), 3), max=round(max(v), 3)) for k, v in times.items()},
                inliers_total={k: int(last[k]["records"][:, col].sum().item()) for k in variants if k not in ("eval", "eval_nogt")})
-    if fundamental:
-        res["lo_rounds_mean"] = float(last["fundamental_lo8"]["records"][:, RECORD_FIELDS.index("lo_rounds")].mean().item())
+    if two_view:
+        res["lo_rounds_mean"] = float(last[args.model + "_lo8"]["records"][:, RECORD_FIELDS.index("lo_rounds")].mean().item())
+        if args.model == "pose":
+            res["n_front_total"] = {k: int(last[k]["n_front"].sum().item()) for k in variants}
     else:
         res["inliers_total_eval"] = int(last["eval"]["records"][:, evalh.RECORD_FIELDS.index("n_inliers")].sum().item())
     line = json.dumps(res)
