@@ -166,6 +166,9 @@ int device_cus();        // compute units of the current device (>= 8)
 int linear_x6_batch_launch(const gims_linear_args* dev_args, int count, int max_m, int max_n, hipStream_t s);
 int split_spl3_launch(const float* src, int64_t lds, uint16_t* dst, int64_t ldd, int64_t rows, int k, hipStream_t s);
 
+// sift.hip: GIMS_AUX_SIFT_DESCRIBE, the one auxiliary function of gims_run_ops without an entry point of its own
+int sift_describe_aux(const gims_aux_args& x, hipStream_t st);
+
 // sinkhorn2d.hip: the 2-D on-chip Sinkhorn (all iterations in one launch; see that file's header)
 struct OtR2Host { const float* z; int64_t ld; int n, m; float* u; float* v; float* status; float norm, log_mu_bin, log_nu_bin; };
 struct OtR2Plan { bool ok; int nx, nc, ppg, ngroups; size_t bytes; };

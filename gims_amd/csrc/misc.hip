@@ -347,6 +347,8 @@ extern "C" int gims_run_ops(const gims_op* ops, int32_t n_ops, void* stream) {
       else if (x.fn == GIMS_AUX_LAYERNORM_ACT)
         rc = gims_layernorm_act((const float*)x.p[0], x.i[0], x.i[1], (int32_t)x.i[2], (const float*)x.p[1], (const float*)x.p[2], x.f[0], (int32_t)x.i[3],
                                 (float*)x.p[3], x.i[4], (uint16_t*)x.p[4], (uint16_t*)x.p[5], x.i[5], stream);
+      else if (x.fn == GIMS_AUX_SIFT_DESCRIBE)
+        rc = sift_describe_aux(x, (hipStream_t)stream);
       else
         GIMS_CHECK_ARG(false, "gims_run_ops: op %d: unknown auxiliary function %d", i, x.fn);
     } else {

@@ -13,6 +13,8 @@
 //                         keypoints land in fixed slots [candidate * 18 + rank], with the sort keys of removeDuplicatedSorted
 //   sift_keep_kernel      after the host's stable key sorts: the first of every run of equal (image, x, y, size, angle)
 //   sift_scatter_kernel   compaction + the firstOctave = -1 rescale, per-image counts
+// and, over the Gaussian levels the detection leaves behind, the descriptor stage (GIMS_AUX_SIFT_DESCRIBE of gims_run_ops):
+//   sift_describe_kernel  one wave per keypoint: calcSIFTDescriptor, 128 values
 #include "common.h"
 
 #include <math.h>
@@ -455,6 +457,184 @@ __global__ void sift_scatter_kernel(const int64_t* __restrict__ perm, const int3
   atomicAdd(counts + S.image[s], 1);
 }
 
+// ---- descriptors: OpenCV 4.x calcSIFTDescriptor (d = 4, n = 8) over the detector's pyramid, restated (DESIGN.md 4.14;
+// include/gims_hip.h GIMS_AUX_SIFT_DESCRIBE has the arithmetic line by line, tests/sift_desc_ref.py is the NumPy restatement).
+constexpr int DESC_WAVES = 4;                  // keypoints per workgroup, one wave each
+constexpr int DESC_CHUNK = 256;                // candidate samples staged per pass: 9 KiB of LDS per wave
+constexpr int DESC_CELLS = 36, DESC_LEN = 128;
+
+struct DescTable {                             // Gaussian levels by pyramid octave
+  int n;
+  int h[GIMS_SIFT_MAX_OCTAVES], w[GIMS_SIFT_MAX_OCTAVES], diag[GIMS_SIFT_MAX_OCTAVES];   // diag = (int)sqrt(w^2 + h^2), double
+  int64_t gauss[GIMS_SIFT_MAX_OCTAVES];
+};
+
+// cvRound for values that may be anything: NaN and what does not fit an int go to +-1e9 (exact in float) first
+__device__ __forceinline__ int cv_round(float v) { return (int)rintf(fminf(fmaxf(v, -1e9f), 1e9f)); }
+
+// One wave per keypoint.  The (2 radius + 1)^2 samples are visited in OpenCV's order (i outer, j inner), DESC_CHUNK candidates at a
+// time: the lanes compute 64 candidates at once and append the kept ones -- their eight trilinear shares and their histogram corner --
+// to the wave's LDS slab in candidate order (ballot prefix).  Then lane c < 36 owns spatial cell c of hist[6][6][10] with its ten
+// orientation entries in registers (entry 8 is fed by o0 = 7, entry 9 only by o0 = -1, which an angle of -1 produces) and walks the
+// slab front to back: every histogram entry is the sum of its shares in ascending sample order from 0, whatever the chunking (a sample that misses the lane's cell adds +0.f, which changes no bit of a sum that is never -0).
+// Rows and columns that fall outside 0 < r < rows - 1, 0 < c < cols - 1 are cut from the loop bounds, not tested per sample: the kept
+// samples and their order are the same, and a keypoint of any size costs at most the pixels of its level.
+__global__ __launch_bounds__(64 * DESC_WAVES) void sift_describe_kernel(const float* __restrict__ pyr, int64_t stride, DescTable T,
+                                                                        const float* __restrict__ kp4, const int32_t* __restrict__ octave,
+                                                                        const int32_t* __restrict__ image, int n, int n_images,
+                                                                        float* __restrict__ out, int64_t ld, int32_t* __restrict__ bad) {
+#pragma clang fp contract(off)
+  __shared__ float4 s_val[DESC_WAVES][DESC_CHUNK * 2];     // [sample][8]: v000 v001 v010 v011 | v100 v101 v110 v111 (row, column, orientation)
+  __shared__ int s_key[DESC_WAVES][DESC_CHUNK];            // (r0 + 1) * 6 + (c0 + 1) in bits 4.., o0 in bits 0..3
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  float* const vals = (float*)s_val[wv];
+  int* const keys = s_key[wv];
+  for (int ki = blockIdx.x * DESC_WAVES + wv; ki < n; ki += gridDim.x * DESC_WAVES) {
+    float* dst_row = out + (int64_t)ki * ld;
+    const float4 kp = make_float4(kp4[4 * (int64_t)ki], kp4[4 * (int64_t)ki + 1], kp4[4 * (int64_t)ki + 2], kp4[4 * (int64_t)ki + 3]);
+    const int oc = octave[ki];
+    const int b = image ? image[ki] : 0;
+    int o = oc & 255;
+    o = o < 128 ? o : (-128 | o);
+    const int layer = (oc >> 8) & 255;
+    const int po = o + 1;                                    // firstOctave = -1
+    if (po < 0 || po >= T.n || layer >= SIFT_G || b < 0 || b >= n_images) {
+      dst_row[lane] = 0.f;
+      dst_row[lane + 64] = 0.f;
+      if (lane == 0) atomicAdd(bad, 1);
+      continue;
+    }
+    const float scale = o >= 0 ? 1.f / (float)(1 << o) : (float)(1 << -o);
+    const int rows = T.h[po], cols = T.w[po];
+    const float* img = pyr + (int64_t)b * stride + T.gauss[po] + (int64_t)layer * rows * cols;
+    const float ptx = kp.x * scale, pty = kp.y * scale, scl = kp.z * scale * 0.5f;
+    float ori = 360.f - kp.w;
+    if (fabsf(ori - 360.f) < 1.1920929e-07f) ori = 0.f;
+    const int px = cv_round(ptx), py = cv_round(pty);
+    const float arg = ori * (float)(3.14159265358979323846 / 180);
+    float cos_t = (float)cos((double)arg), sin_t = (float)sin((double)arg);
+    const float bins_per_rad = 8 / 360.f, exp_scale = -1.f / (4 * 4 * 0.5f), hist_width = 3.f * scl;
+    const int radius = min(cv_round(hist_width * 1.4142135623730951f * 5 * 0.5f), T.diag[po]);
+    cos_t /= hist_width;
+    sin_t /= hist_width;
+    // i in [i_lo, i_hi], j in [j_lo, j_hi]: the part of -radius .. radius with 0 < py + i < rows - 1, 0 < px + j < cols - 1
+    const int i_lo = (int)max((int64_t)-radius, (int64_t)1 - py), i_hi = (int)min((int64_t)radius, (int64_t)rows - 2 - py);
+    const int j_lo = (int)max((int64_t)-radius, (int64_t)1 - px), j_hi = (int)min((int64_t)radius, (int64_t)cols - 2 - px);
+    const int nj = j_hi - j_lo + 1;
+    const int total = (i_hi >= i_lo && nj > 0) ? (i_hi - i_lo + 1) * nj : 0;          // <= (rows - 2) * (cols - 2) < 2^30
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f, a5 = 0.f, a6 = 0.f, a7 = 0.f, a8 = 0.f, a9 = 0.f;   // hist[cell][0 .. 9]
+    const int cell = lane < DESC_CELLS ? lane : -64;
+    for (int q0 = 0; q0 < total; q0 += DESC_CHUNK) {
+      int cnt = 0;
+      for (int s = 0; s < DESC_CHUNK && q0 + s < total; s += 64) {
+        const int q = q0 + s + lane;
+        bool keep = false;
+        float v[8];
+        int key = 0;
+        if (q < total) {
+          const int i = i_lo + q / nj, j = j_lo + q % nj;
+          const float c_rot = (float)j * cos_t - (float)i * sin_t, r_rot = (float)j * sin_t + (float)i * cos_t;
+          float rbin = r_rot + 2 - 0.5f, cbin = c_rot + 2 - 0.5f;
+          if (rbin > -1 && rbin < 4 && cbin > -1 && cbin < 4) {
+            keep = true;
+            const float* p = img + (int64_t)(py + i) * cols + (px + j);
+            const float dx = p[1] - p[-1], dy = p[-cols] - p[cols];
+            const float mag = sqrtf(dx * dx + dy * dy) * (float)exp((double)((c_rot * c_rot + r_rot * r_rot) * exp_scale));
+            float obin = (fast_atan2(dy, dx) - ori) * bins_per_rad;
+            const float rf = floorf(rbin), cf = floorf(cbin), of = floorf(obin);
+            rbin -= rf; cbin -= cf; obin -= of;
+            int o0 = (int)of;
+            if (o0 < 0) o0 += 8;
+            if (o0 >= 8) o0 -= 8;
+            const float v_r1 = mag * rbin, v_r0 = mag - v_r1;
+            const float v_rc11 = v_r1 * cbin, v_rc10 = v_r1 - v_rc11, v_rc01 = v_r0 * cbin, v_rc00 = v_r0 - v_rc01;
+            v[1] = v_rc00 * obin; v[0] = v_rc00 - v[1];
+            v[3] = v_rc01 * obin; v[2] = v_rc01 - v[3];
+            v[5] = v_rc10 * obin; v[4] = v_rc10 - v[5];
+            v[7] = v_rc11 * obin; v[6] = v_rc11 - v[7];
+            // an angle in -1 .. 360 (cv::KeyPoint's range; -1 gives ori = 361) leaves o0 in -1 .. 7; a sample of any other angle whose
+            // o0 falls outside that is dropped (code 14), where OpenCV would write outside its histogram
+            key = ((((int)rf + 1) * 6 + (int)cf + 1) << 4) | (o0 >= -1 && o0 <= 7 ? o0 & 15 : 14);
+          }
+        }
+        const uint64_t m = __ballot(keep);
+        if (keep) {
+          const int pos = cnt + __popcll(m & ((1ull << lane) - 1));
+          s_val[wv][2 * pos] = make_float4(v[0], v[1], v[2], v[3]);
+          s_val[wv][2 * pos + 1] = make_float4(v[4], v[5], v[6], v[7]);
+          keys[pos] = key;
+        }
+        cnt += __popcll(m);
+      }
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      for (int p0 = 0; p0 < cnt; p0 += 64) {
+        const int mine = p0 + lane < cnt ? keys[p0 + lane] : 0;
+        const int m = min(64, cnt - p0);
+        for (int t = 0; t < m; ++t) {
+          const int key = __builtin_amdgcn_readlane(mine, t);              // wave-uniform
+          const int dc = cell - (key >> 4);                                // 0, 1, 6, 7: this lane's cell is (r0 + dr, c0 + dc)
+          const bool hit = (dc & ~7) == 0 && ((0xC3 >> (dc & 7)) & 1);
+          const int pair = hit ? (dc & 1) | ((dc >> 1) & 2) : 0;
+          const float2 sh = *(const float2*)(vals + (p0 + t) * 8 + pair * 2);
+          const float v0 = hit ? sh.x : 0.f, v1 = hit ? sh.y : 0.f;
+          switch (key & 15) {                                              // o0: entries o0 and o0 + 1 of the cell
+            case 0: a0 += v0; a1 += v1; break;
+            case 1: a1 += v0; a2 += v1; break;
+            case 2: a2 += v0; a3 += v1; break;
+            case 3: a3 += v0; a4 += v1; break;
+            case 4: a4 += v0; a5 += v1; break;
+            case 5: a5 += v0; a6 += v1; break;
+            case 6: a6 += v0; a7 += v1; break;
+            case 7: a7 += v0; a8 += v1; break;
+            case 15: {
+              // o0 = -1 (ori above 360: angle -1).  idx - 1 is entry 9 of the cell BEFORE in the flat hist[360], idx entry 0 of this one:
+              // this lane's entry 0 takes its own second share, its entry 9 the first share of the pair that lands in the cell after it
+              a0 += v1;
+              const int dn = dc + 1;
+              const bool hn = (dn & ~7) == 0 && ((0xC3 >> (dn & 7)) & 1);
+              const float vn = vals[(p0 + t) * 8 + (hn ? (dn & 1) | ((dn >> 1) & 2) : 0) * 2];
+              a9 += hn ? vn : 0.f;
+              break;
+            }
+            default: break;                                                // code 14: an o0 outside -1 .. 7, dropped
+          }
+        }
+      }
+      __builtin_amdgcn_wave_barrier();                                     // the slab is refilled by the next chunk
+    }
+    // finalise: fold the circular orientation entries, the interior 4 x 4 cells are the 128 values
+    __builtin_amdgcn_wave_barrier();
+    if (lane < DESC_CELLS) {
+      const int ci = lane / 6 - 1, cj = lane % 6 - 1;
+      if (ci >= 0 && ci < 4 && cj >= 0 && cj < 4) {
+        float* d = vals + (ci * 4 + cj) * 8;
+        d[0] = a0 + a8; d[1] = a1 + a9; d[2] = a2; d[3] = a3; d[4] = a4; d[5] = a5; d[6] = a6; d[7] = a7;
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    float nrm2 = 0.f;
+    for (int k = 0; k < DESC_LEN; ++k) nrm2 += vals[k] * vals[k];           // every lane the same sum, k ascending
+    const float thr = sqrtf(nrm2) * 0.2f;
+    const float d0 = fminf(vals[lane], thr), d1 = fminf(vals[lane + 64], thr);
+    __builtin_amdgcn_wave_barrier();
+    vals[lane] = d0;
+    vals[lane + 64] = d1;
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    nrm2 = 0.f;
+    for (int k = 0; k < DESC_LEN; ++k) nrm2 += vals[k] * vals[k];
+    const float f = 512.f / fmaxf(sqrtf(nrm2), 1.1920929e-07f);
+    dst_row[lane] = fminf(fmaxf(rintf(d0 * f), 0.f), 255.f);               // saturate_cast<uchar>: round half to even, clamp
+    dst_row[lane + 64] = fminf(fmaxf(rintf(d1 * f), 0.f), 255.f);
+    __builtin_amdgcn_wave_barrier();                                       // the slab is refilled by the next keypoint
+  }
+}
+
 static BlurTaps taps_of(const gims_sift_info& L, int i) {
   BlurTaps t = {};
   t.r = L.ksize[i] / 2;
@@ -484,6 +664,36 @@ static int slots_of(float* f, int64_t cap, int64_t* k, int32_t* i32, SiftSlots* 
   S->x = f; S->y = f + n; S->size = f + 2 * n; S->angle = f + 3 * n; S->resp = f + 4 * n;
   S->octave = i32; S->image = i32 + n;
   S->k0 = k; S->k1 = k + n; S->k2 = k + 2 * n;
+  return GIMS_OK;
+}
+
+// GIMS_AUX_SIFT_DESCRIBE of gims_run_ops (include/gims_hip.h): every argument check precedes the first HIP call
+int sift_describe_aux(const gims_aux_args& x, hipStream_t st) {
+  const int64_t n = x.i[0], n_images = x.i[1], h = x.i[2], w = x.i[3], ld = x.i[4];
+  GIMS_CHECK_ARG(n >= 0 && n <= INT32_MAX, "sift_describe: n = %lld is out of range", (long long)n);
+  GIMS_CHECK_ARG(n_images >= 1 && n_images <= INT32_MAX, "sift_describe: n_images = %lld (at least 1)", (long long)n_images);
+  GIMS_CHECK_ARG(x.p[3] || n_images == 1, "sift_describe: the image index may be NULL only when n_images == 1");
+  GIMS_CHECK_ARG(ld >= DESC_LEN, "sift_describe: ld = %lld is below the 128 values of a descriptor", (long long)ld);
+  GIMS_CHECK_ARG(x.i[5] == 0, "sift_describe: i[5] is reserved and must be 0");
+  gims_sift_info L;
+  if (h < 1 || w < 1 || h > INT32_MAX || w > INT32_MAX || sift_layout((int)h, (int)w, &L) != GIMS_OK) {
+    set_error("sift_describe: unsupported image size %lld x %lld", (long long)h, (long long)w);
+    return GIMS_EINVAL;
+  }
+  if (n == 0) return GIMS_OK;
+  GIMS_CHECK_ARG(x.p[0] && x.p[1] && x.p[2] && x.p[4] && x.p[5], "sift_describe: pyr, kp4, octave, out and bad must not be NULL");
+  DescTable T = {};
+  T.n = L.n_octaves;
+  for (int o = 0; o < L.n_octaves; ++o) {
+    T.h[o] = L.oct_h[o]; T.w[o] = L.oct_w[o]; T.gauss[o] = L.gauss_offset[o];
+    T.diag[o] = (int)sqrt((double)L.oct_w[o] * L.oct_w[o] + (double)L.oct_h[o] * L.oct_h[o]);
+  }
+  int32_t* bad = (int32_t*)const_cast<void*>(x.p[5]);
+  GIMS_HIP(hipMemsetAsync(bad, 0, sizeof(int32_t), st));
+  const int blocks = (int)std::min<int64_t>((n + DESC_WAVES - 1) / DESC_WAVES, 1 << 16);
+  sift_describe_kernel<<<blocks, 64 * DESC_WAVES, 0, st>>>((const float*)x.p[0], L.image_floats, T, (const float*)x.p[1], (const int32_t*)x.p[2],
+                                                           (const int32_t*)x.p[3], (int)n, (int)n_images, (float*)const_cast<void*>(x.p[4]), ld, bad);
+  GIMS_LAUNCH_CHECK();
   return GIMS_OK;
 }
 

@@ -16,6 +16,10 @@ it is PARITY UNPINNED against OpenCV itself (see csrc/patches.hip and DESIGN.md)
 per image a dict of device tensors that ``keypoint_arrays``, ``filter_max_num``, ``pad_training_keypoints`` and
 ``extract_patches`` take without a host round trip.  ``device_front_end`` is ``sift_forward_device`` with that detector, batched
 over ``data['image']``; ``Matching({'front_end': frontend.device_front_end})`` selects it (the default stays OpenCV's).
+
+``sift_describe_device`` / ``sift_detect_and_compute_device`` add the 128-d SIFT descriptor of those keypoints over the detector's
+pyramid (csrc/sift.hip), ``root_sift`` the reference's RootSIFT, and ``sift_baseline_front_end`` the front end of the
+classical baseline (SIFT + NNDR / MNN, ``gims_amd.baselines``) that learned matchers are reported against.
 """
 from __future__ import annotations
 
@@ -152,6 +156,81 @@ def sift_detect_device(img_or_batch, device=None):
     t = t.to(dev)
     out = hip.sift_detect(t.unsqueeze(0) if single else t)
     return out[0] if single else out
+
+
+def _image_batch(img_or_batch, dev):
+    """uint8 [H, W] / [H, W, 3] / [B, H, W(, 3)] (array, tensor or list of equal-size images) -> (tensor [B, ...] on dev, single)."""
+    if isinstance(img_or_batch, (list, tuple)):
+        img_or_batch = torch.stack([torch.as_tensor(np.asarray(im) if not torch.is_tensor(im) else im) for im in img_or_batch])
+    t = img_or_batch if torch.is_tensor(img_or_batch) else torch.from_numpy(np.ascontiguousarray(img_or_batch))
+    single = t.dim() == 2 or (t.dim() == 3 and t.shape[2] == 3)       # as sift_detect_device reads it
+    return (t.unsqueeze(0) if single else t).to(dev), single
+
+
+def _describe(pyr, h, w, kps, dev):
+    """One hip.sift_describe call for the keypoints of every image of the pyramid buffer; raises IndexError on bad keypoints."""
+    parts = [keypoint_arrays(k) for k in kps]
+    counts = [len(p[0]) for p in parts]
+    kp4 = torch.cat([_on(p[0], dev).float().reshape(-1, 4) for p in parts]).contiguous()
+    octv = torch.cat([_on(p[1], dev).to(torch.int32).reshape(-1) for p in parts]).contiguous()
+    image = torch.from_numpy(np.repeat(np.arange(len(kps), dtype=np.int32), counts)).to(dev) if len(kps) > 1 else None
+    desc, bad = hip.sift_describe(pyr, h, w, len(kps), kp4, octv, image)
+    if len(kp4) and int(bad.item()):
+        raise IndexError(f"{int(bad.item())} keypoint(s) reference a pyramid level that does not exist (octave / layer out of range)")
+    return list(torch.split(desc, counts))
+
+
+def sift_describe_device(img_or_batch, keypoints, device=None):
+    """128-d SIFT descriptors on the device (csrc/sift.hip, OpenCV 4.x calcSIFTDescriptor restated) for given keypoints:
+    one dict of device tensors per image, as ``sift_detect_device`` returns, or anything ``keypoint_arrays`` accepts.  Returns float32
+    [n, 128] (integer-valued, 0 .. 255) per image: a tensor for one image, a list for a batch.  The keypoints are described over the
+    DETECTOR's pyramid of the image (what ``detectAndCompute`` does); ``cv2.SIFT.compute`` builds its pyramid from the octaves of the
+    provided keypoints, which is not restated.  Keypoints whose octave / layer fall outside the pyramid raise IndexError with their
+    count, like ``extract_patches``."""
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    t, single = _image_batch(img_or_batch, dev)
+    kps = [keypoints] if single else list(keypoints)
+    if len(kps) != t.shape[0]:
+        raise ValueError(f"sift_describe_device: {t.shape[0]} image(s) but {len(kps)} keypoint set(s)")
+    out = _describe(hip.sift_pyramid_buffer(t), int(t.shape[1]), int(t.shape[2]), kps, dev)
+    return out[0] if single else out
+
+
+def sift_detect_and_compute_device(img_or_batch, max_keypoints=-1, device=None):
+    """``detectAndCompute``: ``sift_detect_device``, ``filter_max_num(max_keypoints)``, then ``sift_describe_device`` over the pyramid the
+    detection built (it is built once).  Returns (keypoints, descriptors): a dict and a float32 [n, 128] tensor for one image, lists of
+    them for a batch of equal-size images."""
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    t, single = _image_batch(img_or_batch, dev)
+    dets, pyr = hip.sift_detect(t, return_pyramid=True)
+    dets = [filter_max_num(d, max_keypoints) for d in dets]
+    desc = _describe(pyr, int(t.shape[1]), int(t.shape[2]), dets, dev)
+    return (dets[0], desc[0]) if single else (dets, desc)
+
+
+def root_sift(desc, eps=1e-7, l2norm=False):
+    """The reference's ``rootSIFT`` (utils/common.py:698-708) on tensors, [n, C]: L1-normalise with ``+ eps``, then the square root;
+    ``l2norm=True`` then applies ``desc_l2norm`` (687-696): x / sqrt(sum x^2 + 1e-10).  Torch plumbing; the input is not modified."""
+    d = desc / (desc.sum(dim=1, keepdim=True) + eps)
+    d = torch.sqrt(d)
+    if l2norm:
+        d = d / d.pow(2).sum(dim=1, keepdim=True).add(1e-10).pow(0.5)
+    return d
+
+
+def sift_baseline_front_end(data, device):
+    """The classical baseline's front end: SIFT keypoints and SIFT / RootSIFT descriptors, all on the device, no CAR-HyNet.
+    data: {'image': uint8 [B, H, W, 3], 'max_keypoints': int (default -1), 'root': bool (default False)}.  Returns {'keypoints',
+    'scores', 'descriptors'}: lists with one tensor per image -- (n, 2), (n,), (128, n); ``baselines.nn_match_pairs`` reads the
+    descriptors as ``descriptors0/1[None]``."""
+    img = data["image"]
+    dets, descs = sift_detect_and_compute_device(list(img) if not torch.is_tensor(img) and not isinstance(img, np.ndarray) else img,
+                                                 data.get("max_keypoints", -1), device)
+    if isinstance(dets, dict):
+        dets, descs = [dets], [descs]
+    if data.get("root", False):
+        descs = [root_sift(d) for d in descs]
+    return {"keypoints": [d["pt"] for d in dets], "scores": [d["response"] for d in dets], "descriptors": [d.t().contiguous() for d in descs]}
 
 
 def device_front_end(data, device):

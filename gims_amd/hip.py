@@ -64,6 +64,7 @@ AugPlan = ABI.structs["gims_aug_plan"]          # one image's colour augmentatio
 GUARD_PEAKED, GUARD_RANGE = _K["GIMS_GUARD_PEAKED"], _K["GIMS_GUARD_RANGE"]
 AUX_SPLIT_SPL32, AUX_SAGE_MEAN_SPLIT, AUX_KENC_FIRST = _K["GIMS_AUX_SPLIT_SPL32"], _K["GIMS_AUX_SAGE_MEAN_SPLIT"], _K["GIMS_AUX_KENC_FIRST"]
 AUX_SAGE_MEAN, AUX_KENC_FIRST_LINEAR, AUX_LAYERNORM_ACT = _K["GIMS_AUX_SAGE_MEAN"], _K["GIMS_AUX_KENC_FIRST_LINEAR"], _K["GIMS_AUX_LAYERNORM_ACT"]
+AUX_SIFT_DESCRIBE = _K["GIMS_AUX_SIFT_DESCRIBE"]     # SIFT descriptors: reached through gims_run_ops only (no entry point of its own)
 SIFT_MAX_OCTAVES, SIFT_MAX_RADIUS, SIFT_SLOTS = _K["GIMS_SIFT_MAX_OCTAVES"], _K["GIMS_SIFT_MAX_RADIUS"], _K["GIMS_SIFT_SLOTS"]
 
 
@@ -934,9 +935,7 @@ def sift_pyramid(images: torch.Tensor):
     assert t.is_cuda
     B, H, W, c = t.shape
     L = sift_layout(H, W)
-    pyr = torch.empty(B * L.image_floats, dtype=torch.float32, device=t.device)
-    scratch = torch.empty(B * L.scratch_floats, dtype=torch.float32, device=t.device)
-    _check(load().gims_sift_pyramid(_p(t), B, H, W, c, _p(pyr), _p(scratch), _stream()), "gims_sift_pyramid")
+    pyr = sift_pyramid_buffer(t)
     gauss, dog = [], []
     for b in range(B):
         base = b * L.image_floats
@@ -950,12 +949,13 @@ def sift_pyramid(images: torch.Tensor):
     return gauss, dog
 
 
-def sift_detect(images: torch.Tensor, cand_cap: int | None = None):
+def sift_detect(images: torch.Tensor, cand_cap: int | None = None, return_pyramid: bool = False):
     """OpenCV SIFT detect on the device for a batch of equal-size images: uint8 [B, H, W, 3] (BGR) or [B, H, W] ->
     one dict per image of device tensors pt f32 [n, 2], size, angle, response f32 [n], octave int32 [n], in OpenCV's output order.
     Every pixel and keypoint is computed by the HIP kernels; the stable key sorts between them are torch plumbing.  The one host
     read per call is the final count (with the extremum count: when it exceeds the candidate capacity the buffers grow and the
-    call repeats, so nothing is dropped)."""
+    call repeats, so nothing is dropped).  return_pyramid=True: (that list, pyr) with the float pyramid buffer [B * image_floats] the
+    call filled, which sift_describe reads (gims_sift_layout has its layout)."""
     t = _sift_images(images)
     assert t.is_cuda
     B, H, W, c = t.shape
@@ -997,7 +997,44 @@ def sift_detect(images: torch.Tensor, cand_cap: int | None = None):
         out.append({"pt": pt[off:off + n], "size": size[off:off + n], "angle": angle[off:off + n], "response": resp[off:off + n],
                     "octave": octave[off:off + n]})
         off += n
-    return out
+    return (out, pyr) if return_pyramid else out
+
+
+def sift_pyramid_buffer(images: torch.Tensor):
+    """gims_sift_pyramid alone: images uint8 [B, H, W, 3] / [B, H, W] on the device -> the float pyramid buffer [B * image_floats] that
+    sift_detect(return_pyramid=True) also hands back (bit for bit: detection runs the same call first)."""
+    t = _sift_images(images)
+    assert t.is_cuda
+    B, H, W, c = t.shape
+    L = sift_layout(H, W)
+    pyr = torch.empty(B * L.image_floats, dtype=torch.float32, device=t.device)
+    scratch = torch.empty(B * L.scratch_floats, dtype=torch.float32, device=t.device)
+    _check(load().gims_sift_pyramid(_p(t), B, H, W, c, _p(pyr), _p(scratch), _stream()), "gims_sift_pyramid")
+    return pyr
+
+
+def op_sift_describe(pyr, h, w, n_images, kp4, octave, image, out, bad) -> Op:
+    """The descriptor stage as an op of gims_run_ops (include/gims_hip.h GIMS_AUX_SIFT_DESCRIBE): the one way to reach it."""
+    return op_aux(AUX_SIFT_DESCRIBE, (pyr, kp4, octave, image, out, bad), (kp4.shape[0], n_images, h, w, out.stride(0), 0))
+
+
+def sift_describe(pyr: torch.Tensor, h: int, w: int, n_images: int, kp4: torch.Tensor, octave: torch.Tensor, image: torch.Tensor | None = None):
+    """OpenCV's calcSIFTDescriptor over the detector's pyramid (csrc/sift.hip sift_describe_kernel): pyr from
+    sift_detect(return_pyramid=True) / sift_pyramid_buffer for n_images images of h x w; kp4 f32 [n, 4] (x, y, size, angle), octave
+    int32 [n] and image int32 [n] (None: one image) as detection returns them -> (desc f32 [n, 128], integer-valued 0 .. 255;
+    bad int32 [1] on the device: keypoints whose octave / layer / image is outside the pyramid, described as zeros).  This is the
+    detectAndCompute descriptor: cv2.SIFT.compute would rebuild a pyramid from the keypoints' octaves, which is not restated.
+    Asynchronous; no host read."""
+    assert pyr.dtype == torch.float32 and pyr.is_cuda and pyr.is_contiguous()
+    assert kp4.dtype == torch.float32 and kp4.is_cuda and kp4.is_contiguous() and kp4.dim() == 2 and kp4.shape[1] == 4
+    assert octave.dtype == torch.int32 and octave.is_cuda and octave.is_contiguous() and octave.shape[0] == kp4.shape[0]
+    assert image is None or (image.dtype == torch.int32 and image.is_cuda and image.is_contiguous() and image.shape[0] == kp4.shape[0])
+    L = sift_layout(h, w)
+    assert pyr.numel() >= n_images * L.image_floats, "the pyramid buffer is smaller than n_images pyramids of this image size"
+    out = torch.empty((kp4.shape[0], 128), dtype=torch.float32, device=pyr.device)
+    bad = torch.zeros(1, dtype=torch.int32, device=pyr.device)
+    run_ops(make_ops([op_sift_describe(pyr, h, w, n_images, kp4, octave, image, out, bad)]))
+    return out, bad
 
 
 def patch_affine(kp4: torch.Tensor, kp_octave: torch.Tensor):

@@ -227,7 +227,54 @@ int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t
  *   GIMS_AUX_SAGE_MEAN          gims_sage_mean          p = {h, indptr, indices, out}               i = {ldh, n, c, ldo}
  *   GIMS_AUX_KENC_FIRST_LINEAR  gims_kenc_first_linear  p, i as GIMS_AUX_KENC_FIRST
  *   GIMS_AUX_LAYERNORM_ACT      gims_layernorm_act      p = {x, a2, b2, out, out_hi, out_lo}        i = {ldx, rows, c, act, ldo, ld_split}  f = {eps}
- * f holds the floating-point arguments in declaration order (eps is a float in the entry point and travels as one: no conversion on the way). */
+ * f holds the floating-point arguments in declaration order (eps is a float in the entry point and travels as one: no conversion on the way).
+ *
+ * GIMS_AUX_SIFT_DESCRIBE is the one function of this table WITHOUT a stand-alone entry point: the exported surface of this ABI version
+ * is closed (its count is pinned), so the descriptor stage is reached through the table only; an entry point of its own belongs to the
+ * next ABI version.  It computes OpenCV 4.x calcSIFTDescriptor (d = 4, n = 8: 128 values) for n keypoints over the detector's own
+ * pyramid (the detectAndCompute descriptor; NOT the pyramid cv2.SIFT.compute rebuilds from the octaves of provided keypoints).  This
+ * library's restatement: parity with OpenCV is unpinned, as for detection.  kernel: sift_describe_kernel, gims_amd/csrc/sift.hip.
+ *   p[0] pyr    float [n_images][image_floats], filled by gims_sift_pyramid / gims_sift_detect for the same h, w
+ *   p[1] kp4    float [n][4] = x, y, size, angle, as detection returns them
+ *   p[2] octave int32 [n], packed as detection returns it
+ *   p[3] image  int32 [n], the image of every keypoint; may be NULL when n_images == 1
+ *   p[4] out    float [n][ld]; 128 integer-valued floats in 0 .. 255 per keypoint (OpenCV's CV_32F descriptors)
+ *   p[5] bad    device int32 [1]: set to the number of bad keypoints
+ *   i = {n, n_images, h, w, ld, 0}
+ * GIMS_EINVAL before any HIP call: a NULL pyr / kp4 / octave / out / bad while n > 0; n < 0; n_images < 1, or p[3] == NULL with
+ * n_images > 1; an h, w that gims_sift_layout refuses; ld < 128; i[5] != 0.  n == 0 is GIMS_OK and touches nothing.  Asynchronous: no
+ * host synchronisation (bad is written by a memset node and the kernel).
+ * All arithmetic is float32 without fused multiply-add; exp, cos and sin are taken in double and rounded to float; fastAtan2 is the
+ * detector's polynomial; cvRound = rint (half to even), cvFloor = floor.  Per keypoint (x, y, size, angle, octave, image b):
+ *   o = octave & 255; o = o < 128 ? o : (-128 | o); layer = (octave >> 8) & 255; scale = o >= 0 ? 1.f / (1 << o) : (float)(1 << -o).
+ *   The level is Gaussian image `layer` of pyramid octave o + 1 (firstOctave = -1), rows x cols.  BAD (128 zeros, counted) when o + 1
+ *   is outside 0 .. n_octaves - 1, layer outside 0 .. 5, or b outside 0 .. n_images - 1.
+ *   ptf = (x * scale, y * scale); scl = size * scale * 0.5f; ori = 360.f - angle, 0 when |ori - 360.f| < FLT_EPSILON;
+ *   pt = (cvRound(ptf.x), cvRound(ptf.y)); cos_t = cos(ori * (float)(CV_PI / 180)), sin_t likewise; bins_per_rad = 8 / 360.f;
+ *   exp_scale = -1.f / (4 * 4 * 0.5f); hist_width = 3.f * scl; radius = cvRound(hist_width * 1.4142135623730951f * 5 * 0.5f), then
+ *   radius = min(radius, (int)sqrt((double)cols * cols + (double)rows * rows)); then cos_t /= hist_width, sin_t /= hist_width.
+ *   (cvRound of a value beyond +-1e9 or of a NaN takes +-1e9 / -1e9: such a keypoint has no sample inside any level.)
+ *   Samples, i = -radius .. radius (outer), j = -radius .. radius (inner): c_rot = j * cos_t - i * sin_t; r_rot = j * sin_t + i * cos_t;
+ *   rbin = r_rot + 2 - 0.5f; cbin = c_rot + 2 - 0.5f; r = pt.y + i; c = pt.x + j; kept iff rbin > -1 && rbin < 4 && cbin > -1 && cbin < 4
+ *   && r > 0 && r < rows - 1 && c > 0 && c < cols - 1.  Kept: dx = img(r, c+1) - img(r, c-1); dy = img(r-1, c) - img(r+1, c);
+ *   mag = sqrtf(dx*dx + dy*dy) * (float)exp((double)((c_rot*c_rot + r_rot*r_rot) * exp_scale)); obin = (fastAtan2(dy, dx) - ori) * bins_per_rad.
+ *   Trilinear vote: r0 = cvFloor(rbin), c0 = cvFloor(cbin), o0 = cvFloor(obin); rbin -= r0, cbin -= c0, obin -= o0; o0 += 8 if o0 < 0,
+ *   o0 -= 8 if o0 >= 8; v_r1 = mag * rbin, v_r0 = mag - v_r1; v_rc11 = v_r1 * cbin, v_rc10 = v_r1 - v_rc11, v_rc01 = v_r0 * cbin,
+ *   v_rc00 = v_r0 - v_rc01; v_rcoXY1 = v_rcXY * obin, v_rcoXY0 = v_rcXY - v_rcoXY1; the eight are added to hist[6][6][10] at
+ *   idx = ((r0+1) * 6 + c0 + 1) * 10 + o0 plus 0 (000), 1 (001), 10 (010), 11 (011), 60 (100), 61 (101), 70 (110), 71 (111).
+ *   An angle in -1 .. 360 (cv::KeyPoint's range; -1, "not applicable", gives ori = 361) leaves o0 in -1 .. 7 after that one wrap.  o0 = -1
+ *   is kept as it is: idx - 1 is orientation entry 9 of the cell BEFORE in the flat histogram and idx entry 0 of the sample's own cell, so
+ *   entry 9 is live and the fold below matters; the one share that would land before the histogram (cell 0, o0 = -1) is dropped.  A sample
+ *   of any other angle whose o0 falls outside -1 .. 7 is dropped, where OpenCV would write outside its histogram.
+ *   Finalise: for i, j in 0 .. 3, idx = ((i+1) * 6 + (j+1)) * 10: hist[idx] += hist[idx+8], hist[idx+1] += hist[idx+9],
+ *   dst[(i*4 + j) * 8 + k] = hist[idx + k], k < 8.  nrm2 = sum of dst[k]^2, k ascending; thr = sqrtf(nrm2) * 0.2f; dst[k] = min(dst[k], thr);
+ *   nrm2 summed again; f = 512.f / max(sqrtf(nrm2), FLT_EPSILON); out[k] = (float)saturate_cast<uchar>(dst[k] * f) (half to even, 0 .. 255).
+ * Summation order: each of the 360 histogram entries is the sum of its contributions in ascending sample order (i outer, j inner) from 0,
+ * as OpenCV's sequential loop leaves it; no float atomics; the result depends on neither launch geometry, batch composition nor run.
+ * Nothing caps size: a keypoint with more samples than one LDS chunk is processed in chunks, in the same order.  Cost: one wave walks
+ * all samples of a keypoint, at most the (rows - 2) * (cols - 2) interior pixels of its level, 256 at a time; a keypoint that covers the
+ * 2x level of a 16384 x 16384 image is up to 2^30 samples on one wave (seconds, not microseconds).  A caller that takes keypoints from
+ * an untrusted source bounds size itself. */
 #define GIMS_OP_AUX 2
 #define GIMS_AUX_SPLIT_SPL32 0
 #define GIMS_AUX_SAGE_MEAN_SPLIT 1
@@ -235,6 +282,7 @@ int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t
 #define GIMS_AUX_SAGE_MEAN 3
 #define GIMS_AUX_KENC_FIRST_LINEAR 4
 #define GIMS_AUX_LAYERNORM_ACT 5
+#define GIMS_AUX_SIFT_DESCRIBE 6
 typedef struct gims_aux_args { int32_t fn, reserved; const void* p[6]; int64_t i[6]; float f[2]; } gims_aux_args;
 typedef struct gims_op { int32_t kind; int32_t reserved; union { gims_linear_args lin; gims_attn_args att; gims_aux_args aux; } u; } gims_op;
 int gims_run_ops(const gims_op* ops /* HOST */, int32_t n_ops, void* stream);
