@@ -168,6 +168,8 @@ int split_spl3_launch(const float* src, int64_t lds, uint16_t* dst, int64_t ldd,
 
 // sift.hip: GIMS_AUX_SIFT_DESCRIBE, the one auxiliary function of gims_run_ops without an entry point of its own
 int sift_describe_aux(const gims_aux_args& x, hipStream_t st);
+// nms.hip: GIMS_AUX_DIOU_NMS, likewise reached through gims_run_ops only
+int diou_nms_aux(const gims_aux_args& x, hipStream_t st);
 
 // sinkhorn2d.hip: the 2-D on-chip Sinkhorn (all iterations in one launch; see that file's header)
 struct OtR2Host { const float* z; int64_t ld; int n, m; float* u; float* v; float* status; float norm, log_mu_bin, log_nu_bin; };

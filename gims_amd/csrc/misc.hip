@@ -349,6 +349,8 @@ extern "C" int gims_run_ops(const gims_op* ops, int32_t n_ops, void* stream) {
                                 (float*)x.p[3], x.i[4], (uint16_t*)x.p[4], (uint16_t*)x.p[5], x.i[5], stream);
       else if (x.fn == GIMS_AUX_SIFT_DESCRIBE)
         rc = sift_describe_aux(x, (hipStream_t)stream);
+      else if (x.fn == GIMS_AUX_DIOU_NMS)
+        rc = diou_nms_aux(x, (hipStream_t)stream);
       else
         GIMS_CHECK_ARG(false, "gims_run_ops: op %d: unknown auxiliary function %d", i, x.fn);
     } else {

@@ -20,6 +20,11 @@ over ``data['image']``; ``Matching({'front_end': frontend.device_front_end})`` s
 ``sift_describe_device`` / ``sift_detect_and_compute_device`` add the 128-d SIFT descriptor of those keypoints over the detector's
 pyramid (csrc/sift.hip), ``root_sift`` the reference's RootSIFT, and ``sift_baseline_front_end`` the front end of the
 classical baseline (SIFT + NNDR / MNN, ``gims_amd.baselines``) that learned matchers are reported against.
+
+``diou_nms_device`` / ``process_diou_nms`` are the reference's keypoint thinning ``process_diou_nms`` (utils/common.py:720-807; the line
+it keeps commented out at 863) on the device (csrc/nms.hip).  Every front end applies it between detection and
+``filter_max_num`` when ``data['diou_nms']`` is set: ``True`` for the reference's settings (radius 4, threshold 0.3) or a dict
+``{'radius', 'iou_thresh'}``; absent, ``None`` or ``False`` leaves everything as it was.  ``with_diou_nms(front_end)`` sets the key.
 """
 from __future__ import annotations
 
@@ -94,6 +99,102 @@ def filter_max_num(kps, max_num):
         idxs = np.fliplr(np.reshape(np.argsort(responses), (1, -1))).reshape(-1)
         return [kps[idxs[n]] for n in range(max_num)]
     return kps
+
+
+NMS_DEFAULT = (4, 0.3)        # the reference's gconfig: iou_borders, iou_thresh (utils/common.py:846-847)
+
+
+def _nms_args(radius, iou_thresh):
+    """The reference's argument rules -> (radius as the op takes it: 0.0 = boxes from the size, threshold), or None when radius == 0
+    (the reference returns its input).  ValueError for a negative / non-finite radius or a threshold outside (0, 1)."""
+    if radius is not None and radius == 0:
+        return None
+    thr = float(iou_thresh or 0.5)
+    rad = 0.0 if radius is None else float(radius)
+    if not np.isfinite(rad) or rad < 0:
+        raise ValueError(f"diou_nms: radius = {radius!r} (a positive number, or None for boxes from the keypoint size)")
+    if not 0.0 < thr < 1.0:
+        raise ValueError(f"diou_nms: iou_thresh = {iou_thresh!r} is outside (0, 1)")
+    return rad, thr
+
+
+def _nms_settings(spec):
+    """data['diou_nms'] -> None (off) or (radius, iou_thresh)."""
+    if spec is None or spec is False:
+        return None
+    if spec is True:
+        return NMS_DEFAULT
+    if isinstance(spec, dict):
+        return spec.get("radius", NMS_DEFAULT[0]), spec.get("iou_thresh", NMS_DEFAULT[1])
+    raise TypeError("data['diou_nms'] is True or a dict {'radius', 'iou_thresh'}")
+
+
+def _nms_rows(kp4s, resps, rad, thr, shape, dev):
+    """One hip.diou_nms call for the keypoints of every image (kp4 [n_b, 4] and response [n_b] per image, on dev) -> per image the
+    selected rows (int64, local) in the result's order.  The order handed to the op: descending response, equal responses with the
+    higher row first; a non-finite response takes the keypoint out (the op counts the -1 left in its place as bad)."""
+    counts = [int(k.shape[0]) for k in kp4s]
+    n = sum(counts)
+    if n == 0:
+        return [torch.zeros(0, dtype=torch.int64, device=dev) for _ in counts]
+    kp4 = torch.cat([k.float().reshape(-1, 4) for k in kp4s]).contiguous()
+    resp = torch.cat([r.float().reshape(-1) for r in resps])
+    bounds = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    order = torch.sort(resp, stable=True)[1].flip(0)                      # descending; NaN first, dropped below
+    if len(counts) > 1:
+        image = torch.repeat_interleave(torch.arange(len(counts), device=dev), torch.as_tensor(counts, device=dev), output_size=n)
+        order = order[torch.sort(image[order], stable=True)[1]]
+    order = torch.where(torch.isfinite(resp[order]), order, torch.full_like(order, -1)).to(torch.int32).contiguous()
+    h, w = (1 << 30, 1 << 30) if shape is None else (max(int(shape[0]), 1), max(int(shape[1]), 1))
+    keep, count = hip.diou_nms(kp4, order, hip.upload(bounds, dev), rad, thr, h, w)
+    kept = count.cpu().numpy()                                            # the one host read of the call
+    return [keep[bounds[b]:bounds[b] + int(kept[b])].long() - int(bounds[b]) for b in range(len(counts))]
+
+
+def diou_nms_device(kps, radius=4, iou_thresh=0.3, shape=None, device=None):
+    """The reference's ``process_diou_nms(keypoints, radius, iou_thresh)`` on the device (csrc/nms.hip) for one dict of
+    device tensors (what ``sift_detect_device`` returns) or a list of them, which goes through the kernel as one batch.  Returns the
+    dict(s) with every field indexed by the result: the surviving keypoints in descending response, as the reference returns them.
+    ``radius=None``: boxes from the keypoint size; ``radius == 0`` returns the input unchanged and a falsy ``iou_thresh`` means 0.5
+    (both rules are the reference's own); a threshold outside (0, 1) or a negative radius raises ValueError.  ``shape`` = (height,
+    width) of the image(s) bounds the search grid; it changes the speed only.  Equal responses are processed higher row first (the
+    reference leaves them to NumPy's sort); between identical boxes that cannot change the result.  One host synchronisation per call."""
+    args = _nms_args(radius, iou_thresh)
+    if args is None:
+        return kps
+    single = _is_device_dict(kps)
+    lst = [kps] if single else list(kps)
+    if not lst:
+        return kps
+    dev = torch.device(device) if device is not None else lst[0]["pt"].device
+    parts = [keypoint_arrays(k) for k in lst]
+    rows = _nms_rows([_on(p[0], dev) for p in parts], [_on(p[2], dev) for p in parts], args[0], args[1], shape, dev)
+    out = [{name: v[r.to(v.device)] for name, v in k.items()} for k, r in zip(lst, rows)]
+    return out[0] if single else out
+
+
+def process_diou_nms(keypoints, radius=None, iou_thresh=0.3):
+    """The reference's function with its signature, for a list (or array) of cv2.KeyPoint-like objects (``pt``, ``size``,
+    ``response``): uploads them, runs the op on the current device and returns the selected objects as a list, in the reference's order.
+    Differences: an empty input returns an empty list (the reference raises there), and equal responses of DIFFERENT boxes are
+    processed higher row first, where the reference leaves the order to NumPy's sort."""
+    args = _nms_args(radius, iou_thresh)
+    if args is None:
+        return keypoints
+    if len(keypoints) == 0:
+        return []
+    dev = torch.device("cuda", torch.cuda.current_device())
+    kp4 = np.array([[k.pt[0], k.pt[1], k.size, 0.0] for k in keypoints], dtype=np.float32)
+    resp = np.array([k.response for k in keypoints], dtype=np.float32)
+    rows = _nms_rows([_on(kp4, dev)], [_on(resp, dev)], args[0], args[1], None, dev)[0].cpu().tolist()
+    return [keypoints[i] for i in rows]
+
+
+def with_diou_nms(front_end, radius=4, iou_thresh=0.3):
+    """A front end that runs ``front_end`` with ``data['diou_nms']`` set: ``Matching({'front_end': with_diou_nms(device_front_end)})``."""
+    def thinned(data, device):
+        return front_end({**data, "diou_nms": {"radius": radius, "iou_thresh": iou_thresh}}, device)
+    return thinned
 
 
 class PaddedKeyPoint:
@@ -196,13 +297,17 @@ def sift_describe_device(img_or_batch, keypoints, device=None):
     return out[0] if single else out
 
 
-def sift_detect_and_compute_device(img_or_batch, max_keypoints=-1, device=None):
+def sift_detect_and_compute_device(img_or_batch, max_keypoints=-1, device=None, diou_nms=None):
     """``detectAndCompute``: ``sift_detect_device``, ``filter_max_num(max_keypoints)``, then ``sift_describe_device`` over the pyramid the
     detection built (it is built once).  Returns (keypoints, descriptors): a dict and a float32 [n, 128] tensor for one image, lists of
-    them for a batch of equal-size images."""
+    them for a batch of equal-size images.  ``diou_nms`` (``True`` or ``{'radius', 'iou_thresh'}``, as ``data['diou_nms']``) thins the
+    detections with ``diou_nms_device`` before ``filter_max_num``, the images as one batch."""
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     t, single = _image_batch(img_or_batch, dev)
     dets, pyr = hip.sift_detect(t, return_pyramid=True)
+    nms = _nms_settings(diou_nms)
+    if nms is not None:
+        dets = diou_nms_device(dets, nms[0], nms[1], (int(t.shape[1]), int(t.shape[2])), dev)
     dets = [filter_max_num(d, max_keypoints) for d in dets]
     desc = _describe(pyr, int(t.shape[1]), int(t.shape[2]), dets, dev)
     return (dets[0], desc[0]) if single else (dets, desc)
@@ -220,12 +325,13 @@ def root_sift(desc, eps=1e-7, l2norm=False):
 
 def sift_baseline_front_end(data, device):
     """The classical baseline's front end: SIFT keypoints and SIFT / RootSIFT descriptors, all on the device, no CAR-HyNet.
-    data: {'image': uint8 [B, H, W, 3], 'max_keypoints': int (default -1), 'root': bool (default False)}.  Returns {'keypoints',
+    data: {'image': uint8 [B, H, W, 3], 'max_keypoints': int (default -1), 'root': bool (default False), 'diou_nms': see
+    ``sift_detect_and_compute_device`` (default off)}.  Returns {'keypoints',
     'scores', 'descriptors'}: lists with one tensor per image -- (n, 2), (n,), (128, n); ``baselines.nn_match_pairs`` reads the
     descriptors as ``descriptors0/1[None]``."""
     img = data["image"]
     dets, descs = sift_detect_and_compute_device(list(img) if not torch.is_tensor(img) and not isinstance(img, np.ndarray) else img,
-                                                 data.get("max_keypoints", -1), device)
+                                                 data.get("max_keypoints", -1), device, **({"diou_nms": data["diou_nms"]} if "diou_nms" in data else {}))
     if isinstance(dets, dict):
         dets, descs = [dets], [descs]
     if data.get("root", False):
@@ -235,8 +341,17 @@ def sift_baseline_front_end(data, device):
 
 def device_front_end(data, device):
     """``sift_forward_device`` with ``sift_detect_device`` as the detector, the detection batched over ``data['image']``.  Hand it to
-    ``Matching`` as ``config['front_end']``."""
-    dets = iter(sift_detect_device(list(data["image"]) if not torch.is_tensor(data["image"]) else data["image"], device))
+    ``Matching`` as ``config['front_end']``.  With ``data['diou_nms']`` set the detections of all images are thinned in one
+    ``diou_nms_device`` call before ``sift_forward_device`` sees them."""
+    dets = sift_detect_device(list(data["image"]) if not torch.is_tensor(data["image"]) else data["image"], device)
+    nms = _nms_settings(data.get("diou_nms"))
+    if nms is not None:
+        if isinstance(dets, dict):
+            dets = [dets]
+        sizes = {tuple(im.shape[:2]) for im in data["image"]}
+        dets = diou_nms_device(dets, nms[0], nms[1], sizes.pop() if len(sizes) == 1 else None, device)
+        data = {**data, "diou_nms": None}
+    dets = iter(dets)
     return sift_forward_device(data, device, detector=lambda img: next(dets))
 
 
@@ -244,13 +359,18 @@ def sift_forward_device(data, device, detector=None):
     """``utils.common.sift_forward`` (common.py:837-893; ``data['is_train']``: pad_training_keypoints) with patches and descriptors on the device.
     data: {'image': uint8 [B, H, W, 3], 'max_keypoints': int, 'carhynet': gims_amd.carhynet.CARHyNet (or any object with
     ``_forward_nhwc`` / ``compute_des_batches``)}.  Returns {'keypoints', 'scores', 'descriptors'}: lists with one tensor per
-    image -- (n, 2), (n,), (256, n) with the 128-d descriptor duplicated (common.py:890-892)."""
+    image -- (n, 2), (n,), (256, n) with the 128-d descriptor duplicated (common.py:890-892).  ``data['diou_nms']`` (``True`` or
+    ``{'radius', 'iou_thresh'}``) thins every image's detections where the reference's commented-out line stands (common.py:863),
+    before ``filter_max_num``: ``diou_nms_device`` for device detections, ``process_diou_nms`` for host keypoint lists."""
     det = detector or data.get("detector") or _default_detector()
+    nms = _nms_settings(data.get("diou_nms"))
     net = data["carhynet"]
     kpts, descs, scores = [], [], []
     for img in data["image"]:
         img = np.asarray(img.cpu() if torch.is_tensor(img) else img)
         k = det(img)
+        if nms is not None:
+            k = diou_nms_device(k, nms[0], nms[1], img.shape[:2], device) if _is_device_dict(k) else process_diou_nms(list(k), nms[0], nms[1])
         k = filter_max_num(k if _is_device_dict(k) else list(k), data.get("max_keypoints", -1))
         if data.get("is_train", False):
             k = pad_training_keypoints(k, data.get("max_keypoints", -1), img.shape)

@@ -65,6 +65,7 @@ GUARD_PEAKED, GUARD_RANGE = _K["GIMS_GUARD_PEAKED"], _K["GIMS_GUARD_RANGE"]
 AUX_SPLIT_SPL32, AUX_SAGE_MEAN_SPLIT, AUX_KENC_FIRST = _K["GIMS_AUX_SPLIT_SPL32"], _K["GIMS_AUX_SAGE_MEAN_SPLIT"], _K["GIMS_AUX_KENC_FIRST"]
 AUX_SAGE_MEAN, AUX_KENC_FIRST_LINEAR, AUX_LAYERNORM_ACT = _K["GIMS_AUX_SAGE_MEAN"], _K["GIMS_AUX_KENC_FIRST_LINEAR"], _K["GIMS_AUX_LAYERNORM_ACT"]
 AUX_SIFT_DESCRIBE = _K["GIMS_AUX_SIFT_DESCRIBE"]     # SIFT descriptors: reached through gims_run_ops only (no entry point of its own)
+AUX_DIOU_NMS = _K["GIMS_AUX_DIOU_NMS"]               # DIoU-NMS keypoint thinning: likewise
 SIFT_MAX_OCTAVES, SIFT_MAX_RADIUS, SIFT_SLOTS = _K["GIMS_SIFT_MAX_OCTAVES"], _K["GIMS_SIFT_MAX_RADIUS"], _K["GIMS_SIFT_SLOTS"]
 
 
@@ -1035,6 +1036,38 @@ def sift_describe(pyr: torch.Tensor, h: int, w: int, n_images: int, kp4: torch.T
     bad = torch.zeros(1, dtype=torch.int32, device=pyr.device)
     run_ops(make_ops([op_sift_describe(pyr, h, w, n_images, kp4, octave, image, out, bad)]))
     return out, bad
+
+
+def diou_nms_workspace_bytes(n: int, n_images: int) -> int:
+    """The workspace of GIMS_AUX_DIOU_NMS for n keypoints in n_images images: the formula of include/gims_hip.h (csrc/nms.hip nms_layout
+    carves it), every region rounded up to 256 bytes.  Plain arithmetic: the library has no size query for it."""
+    al = lambda x: (x + 255) & ~255
+    return 2 * al(16 * n) + 3 * al(4 * n) + al(4 * (2 * n + 64 * n_images)) + al(n)
+
+
+def op_diou_nms(kp4, order, offsets, keep, count, work, n_images, height, width, radius, iou_thresh) -> Op:
+    """The keypoint thinning as an op of gims_run_ops (include/gims_hip.h GIMS_AUX_DIOU_NMS): the one way to reach it.  radius 0: boxes
+    from the keypoint size."""
+    return op_aux(AUX_DIOU_NMS, (kp4, order, offsets, keep, count, work), (kp4.shape[0], n_images, height, width, work.numel() * work.element_size(), 0),
+                  (radius, iou_thresh))
+
+
+def diou_nms(kp4: torch.Tensor, order: torch.Tensor, offsets: torch.Tensor, radius: float, iou_thresh: float, height: int, width: int):
+    """The reference's process_diou_nms (utils/common.py:720-807) for a batch of images on the device (csrc/nms.hip): kp4
+    f32 [n, 4] (x, y, size, angle) of all images, image b holding rows offsets[b] .. offsets[b + 1] - 1 (offsets int32 [n_images + 1] on
+    the device); order int32 [n]: per image a permutation of its own (global) rows, the processing order -- descending score.  radius > 0:
+    fixed boxes of that side, 0: boxes from the keypoint size; 0 < iou_thresh < 1; height, width: the extent of the search grid (speed
+    only).  -> (keep int32 [n]: per image its result rows, global, then -1; count int32 [n_images + 1]: kept per image, then the number
+    of bad keypoints -- non-finite, negative size in size mode, order entries outside their image).  Asynchronous; no host read."""
+    assert kp4.dtype == torch.float32 and kp4.is_cuda and kp4.is_contiguous() and kp4.dim() == 2 and kp4.shape[1] == 4
+    assert order.dtype == torch.int32 and order.is_cuda and order.is_contiguous() and order.shape == (kp4.shape[0],)
+    assert offsets.dtype == torch.int32 and offsets.is_cuda and offsets.is_contiguous() and offsets.dim() == 1 and offsets.numel() >= 2
+    n, n_images = kp4.shape[0], offsets.numel() - 1
+    keep = torch.empty(n, dtype=torch.int32, device=kp4.device)
+    count = torch.zeros(n_images + 1, dtype=torch.int32, device=kp4.device)
+    work = torch.empty(diou_nms_workspace_bytes(n, n_images), dtype=torch.uint8, device=kp4.device)
+    run_ops(make_ops([op_diou_nms(kp4, order, offsets, keep, count, work, n_images, height, width, radius, iou_thresh)]))
+    return keep, count
 
 
 def patch_affine(kp4: torch.Tensor, kp_octave: torch.Tensor):

@@ -274,7 +274,49 @@ int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t
  * Nothing caps size: a keypoint with more samples than one LDS chunk is processed in chunks, in the same order.  Cost: one wave walks
  * all samples of a keypoint, at most the (rows - 2) * (cols - 2) interior pixels of its level, 256 at a time; a keypoint that covers the
  * 2x level of a 16384 x 16384 image is up to 2^30 samples on one wave (seconds, not microseconds).  A caller that takes keypoints from
- * an untrusted source bounds size itself. */
+ * an untrusted source bounds size itself.
+ *
+ * GIMS_AUX_DIOU_NMS is the second function of this table without a stand-alone entry point, for the same reason.  It is the reference's
+ * keypoint thinning process_diou_nms(k, radius, iou_thresh) (utils/common.py:720-807: greedy DIoU non-maximum suppression over boxes
+ * around the keypoints), index for index, for a batch of images in one call.  kernel: diou_nms_kernel, gims_amd/csrc/nms.hip.
+ *   p[0] kp4     float [n][4] = x, y, size, angle, as detection returns them; angle is not read
+ *   p[1] order   int32 [n]: the processing order, GLOBAL rows.  Segment b holds a permutation of its own rows offsets[b] .. offsets[b+1] - 1;
+ *                a value outside the segment is skipped and counted bad, never dereferenced
+ *   p[2] offsets device int32 [n_images + 1]: the keypoints are grouped into n_images contiguous segments; clamped to 0 .. n on the device
+ *   p[3] keep    int32 [n].  Per segment: the result rows (global), then -1
+ *   p[4] count   int32 [n_images + 1]: kept per image, then bad
+ *   p[5] work    workspace, 16-byte aligned, of at least
+ *                  2 * al256(16 n) + 3 * al256(4 n) + al256(4 * (2 n + 64 n_images)) + al256(n) bytes, al256(x) = (x + 255) & ~255
+ *   i = {n, n_images, height, width, work_bytes, 0}     f = {radius, iou_thresh}
+ * radius > 0 selects fixed boxes, radius == 0 boxes from the keypoint size.  0 < iou_thresh < 1.  height, width: the extent the search
+ * grid covers; they affect speed only, never the result (keypoints outside it are clamped into the border cells).
+ * GIMS_EINVAL before any HIP call, each with a message naming diou_nms: a NULL pointer while n > 0; n < 0 (or above 2^29); n_images < 1
+ * (or above 2^20); height or width < 1; radius negative or not finite; iou_thresh outside (0, 1) or not finite; work_bytes below the
+ * formula; a misaligned work; i[5] != 0.  n == 0 is GIMS_OK after the same checks and touches nothing.  One memset node and one kernel,
+ * whatever the data; no host synchronisation; capturable by gims_ops_graph_create.
+ * Boxes.  Half-widths and corners are computed in double and rounded once: half = (double)radius / 2, or (double)size / 2 in size mode;
+ * x1 = (float)((double)x - half), y1 likewise, x2 = (float)((double)x + half), y2 likewise (what the reference's Python-float lambdas
+ * followed by .astype(np.float32) produce).  Everything after that is float32, one rounding per operation, no fused multiply-add:
+ *   area = (x2 - x1 + 1) * (y2 - y1 + 1); cx = (x1 + x2) / 2; cy = (y1 + y2) / 2.
+ * Pair test, for a kept keypoint i and a later keypoint o:
+ *   w = max(0, min(x2i, x2o) - max(x1i, x1o) + 1), h likewise; inter = w * h; iou = inter / ((area_i + area_o) - inter);
+ *   diag = (max(x2i, x2o) - min(x1i, x1o))^2 + (max(y2i, y2o) - min(y1i, y1o))^2; cd = (cxi - cxo)^2 + (cyi - cyo)^2;
+ *   diou = iou - cd / (diag + 1e-10f); o SURVIVES i iff diou <= (float)iou_thresh.  (beta is the reference's default 1: not exposed.)
+ * Greedy rule.  Walk the processing order: the first undecided keypoint is kept, every later keypoint that does not survive it is
+ * suppressed; repeat.  The result per image is the kept keypoints in processing order, each replaced by the LOWEST row of the same
+ * image, among the rows of its processing order, whose four corners compare equal (float ==) to its own: the reference's
+ * argwhere(...)[0][0] map-back.  With iou_thresh < 1 two identical boxes always suppress one another (diou == 1), so no row appears twice.
+ * Bad keypoints.  x, y or size not finite, or size < 0 in size mode.  A bad keypoint is never kept, suppresses nothing and is counted in
+ * count[n_images], as is every entry of order that lies outside its segment.
+ * The order is an input: the Python layer makes it descending score, equal scores with the higher row first.  Ties between identical
+ * boxes cannot change the result; ties between different boxes are decided by that rule, where the reference leaves them to NumPy's sort.
+ * How it is computed.  A keypoint can only be suppressed by one whose box overlaps its own (w > 0 and h > 0: otherwise
+ * diou <= 0 < iou_thresh), and then x1 and y1 of the two differ by less than the larger side + 1.  One workgroup per image bins its
+ * keypoints by (x1, y1) into a uniform grid of at most 2 m + 63 cells whose cell side exceeds the image's largest side + 1, so 3 x 3 cells
+ * hold every partner, and relaxes statuses in rounds: an undecided keypoint is suppressed as soon as an earlier partner it does not
+ * survive is kept, kept once all such partners are suppressed.  That reproduces the sequential rule exactly, in 2-6 rounds on detector
+ * output or random points and in as many rounds as keypoints on a chain of overlapping boxes with descending scores.  The locality
+ * argument needs the squares of the coordinates to be finite floats (|x|, |y|, size below 1e18). */
 #define GIMS_OP_AUX 2
 #define GIMS_AUX_SPLIT_SPL32 0
 #define GIMS_AUX_SAGE_MEAN_SPLIT 1
@@ -283,6 +325,7 @@ int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t
 #define GIMS_AUX_KENC_FIRST_LINEAR 4
 #define GIMS_AUX_LAYERNORM_ACT 5
 #define GIMS_AUX_SIFT_DESCRIBE 6
+#define GIMS_AUX_DIOU_NMS 7
 typedef struct gims_aux_args { int32_t fn, reserved; const void* p[6]; int64_t i[6]; float f[2]; } gims_aux_args;
 typedef struct gims_op { int32_t kind; int32_t reserved; union { gims_linear_args lin; gims_attn_args att; gims_aux_args aux; } u; } gims_op;
 int gims_run_ops(const gims_op* ops /* HOST */, int32_t n_ops, void* stream);
