@@ -33,13 +33,14 @@ __device__ bool solve8(double (&A)[8][9]) {
   return true;
 }
 
-__device__ bool homography4(const float* p0, const float* p1, const int (&idx)[4], const int32_t* midx, const int64_t* matches0,
-                            double (&H)[9]) {
+// the 8 x 9 system of four point pairs and its solution; false without a finite model.  load(k, x, y, u, v) fetches pair k: the rows of
+// a pair are formed right behind its loads, whoever loads them (homography4 below, homography4_dense of verify.hip)
+template <class Load>
+__device__ __forceinline__ bool homography4_solve(Load load, double (&H)[9]) {
   double A[8][9];
   for (int k = 0; k < 4; ++k) {
-    const int i = midx[idx[k]];
-    const int j = (int)matches0[i];
-    const double x = p0[2 * i], y = p0[2 * i + 1], u = p1[2 * j], v = p1[2 * j + 1];
+    double x, y, u, v;
+    load(k, x, y, u, v);
     const double r0[9] = {x, y, 1, 0, 0, 0, -u * x, -u * y, u};
     const double r1[9] = {0, 0, 0, x, y, 1, -v * x, -v * y, v};
     for (int c = 0; c < 9; ++c) { A[2 * k][c] = r0[c]; A[2 * k + 1][c] = r1[c]; }
@@ -49,6 +50,15 @@ __device__ bool homography4(const float* p0, const float* p1, const int (&idx)[4
   for (int c = 0; c < 8; ++c) { H[c] = A[c][8]; fin = fin && isfinite(H[c]); }
   H[8] = 1.0;
   return fin;
+}
+
+__device__ bool homography4(const float* p0, const float* p1, const int (&idx)[4], const int32_t* midx, const int64_t* matches0,
+                            double (&H)[9]) {
+  return homography4_solve([&](int k, double& x, double& y, double& u, double& v) {
+    const int i = midx[idx[k]];
+    const int j = (int)matches0[i];
+    x = p0[2 * i]; y = p0[2 * i + 1]; u = p1[2 * j]; v = p1[2 * j + 1];
+  }, H);
 }
 
 __device__ __forceinline__ double reproj2(const double (&H)[9], double x, double y, double u, double v) {
@@ -81,10 +91,13 @@ __device__ __forceinline__ uint64_t splitmix(uint64_t x) {
   x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
   return x ^ (x >> 31);
 }
-__device__ void ransac_sample(uint64_t seed, int hyp, int k, int (&idx)[4]) {     // sampler of the specification in include/gims_hip.h
+// sampler of the specification in include/gims_hip.h: N distinct indices below k.  A larger N continues the stream of a smaller one,
+// so the first four of an eight-point sample are the four-point sample of the same hypothesis
+template <int N>
+__device__ void ransac_sample(uint64_t seed, int hyp, int k, int (&idx)[N]) {
   uint64_t state = seed ^ ((uint64_t)hyp * 0xD1342543DE82EF95ull);
   int n = 0;
-  while (n < 4) {
+  while (n < N) {
     state = splitmix(state);
     const int c = (int)(state % (uint64_t)k);
     bool dup = false;

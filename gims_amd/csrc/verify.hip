@@ -1,14 +1,22 @@
-// Ground-truth-free geometric verification: the RANSAC homography over a set of correspondences and its inlier mask -- what
+// Ground-truth-free geometric verification: a RANSAC model over a set of correspondences and its inlier mask -- what
 // the reference's drivers get from cv2.findHomography(points0, points1, RANSAC | USAC_DEFAULT) (eval_homography.py:191, eval_matches.py:71,164,
 // tools/parameter_search.py:161) -- as an entry point of its own, with a guarded, normalised local optimisation of the best hypothesis.
-// The estimator is this build's own and fully specified in include/gims_hip.h; stage 1 and the lo_iters == 0 refit are those of
-// gims_eval_pairs (csrc/eval.hip) through the helpers of eval_geom.h.  Three kernels, batched over sets, one launch each:
-//   gather      one workgroup per set: ordered compaction of the correspondences into a dense float4 {x, y, u, v} array;
-//   hypotheses  one workgroup per VF_HB hypotheses: VF_HB lanes solve a model each into LDS, then every thread scores one correspondence per
-//               tile (one coalesced 16-byte load) against all VF_HB models (LDS broadcast reads), counters in registers;
-//   finish      one workgroup per set: best hypothesis, stage 2, mask, record, corner error.
-// A set may ask for the fundamental-matrix model instead (gims_verify_set.model): the same three launches, the model a per-set branch that
-// is uniform over the workgroup.  The homography branch is the code it was before the second model existed.
+// The estimator is this build's own and fully specified in include/gims_hip.h; the homography's stage 1 and its lo_iters == 0 refit are
+// those of gims_eval_pairs (csrc/eval.hip) through the helpers of eval_geom.h.
+//
+// Three models, chosen per set (gims_verify_set.model): homography, fundamental matrix, calibrated relative pose.  What they share is
+// written once and templated on a model policy (HomographyModel, FundamentalModel, PoseModel below: minimum count, coordinates, inlier
+// predicate, the sums of a refit and its solve):
+//   vf_score        up to VF_HB models in LDS against all correspondences, counters in registers;
+//   vf_local_opt    the guarded local optimisation, its LDS state in one struct (VfLo), the rule on barriers stated above it;
+//   vf_best, vf_no_model, vf_final_sweep, vf_sign   the prologue and epilogue of a finish kernel.
+// Five kernels, batched over sets:
+//   gather                one workgroup per set: ordered compaction of the correspondences into a dense float4 {x, y, u, v} array;
+//   hyp / pose_hyp        one workgroup per VF_HB hypotheses: VF_HB lanes solve a sample each into LDS, then every thread scores one
+//                         correspondence per tile (one coalesced 16-byte load) against the models (LDS broadcast reads);
+//   finish / pose_finish  one workgroup per set: best hypothesis, stage 2, mask, record (and corner error, or the pose).
+// Homography and fundamental sets share the second and third kernel, the model a per-set branch that is uniform over the workgroup; pose
+// sets run in the last two, launched over their own part of the set table (a sample of theirs has up to ten models).
 #include "common.h"
 #include "eval_geom.h"
 
@@ -34,8 +42,8 @@ struct VerifyDev {
 // record layout (float[8]): GIMS_VERIFY_* of include/gims_hip.h
 enum { VF_NVALID = 0, VF_OK = 1, VF_NINLIERS = 2, VF_BEST_HYP = 3, VF_BEST_HYP_INLIERS = 4, VF_LO_ROUNDS = 5, VF_ERR_CORNER = 6, VF_RESERVED = 7 };
 
-constexpr int VF_HB = 16;          // hypotheses per workgroup of the scoring kernel
-constexpr int VF_ACC = 45;         // widest row of per-wave partial sums: the 45 sums of the fundamental refit (the homography's uses 44)
+constexpr int VF_HB = 16;          // hypotheses per workgroup of the scoring kernels
+constexpr int VF_ACC = 45;         // widest row of per-wave partial sums: the 45 sums of the epipolar refit (the homography's uses 44)
 constexpr int VF_JACOBI_SWEEPS = 12;
 
 // ---------------------------------------------------------------------------------------------- gather
@@ -73,35 +81,13 @@ __global__ __launch_bounds__(1024) void verify_gather_kernel(const VerifyDev* __
   if (t == 0) e.nvalid[0] = base;
 }
 
-// homography4 of eval_geom.h on the dense array: the same rows, the same elimination
+// ---------------------------------------------------------------------------------------------- minimal models on the dense array
+// homography4 of eval_geom.h on the dense array: other loads, the same system
 __device__ bool homography4_dense(const float4* __restrict__ corr, const int (&idx)[4], double (&H)[9]) {
-  double A[8][9];
-  for (int k = 0; k < 4; ++k) {
+  return homography4_solve([&](int k, double& x, double& y, double& u, double& v) {
     const float4 c = corr[idx[k]];
-    const double x = c.x, y = c.y, u = c.z, v = c.w;
-    const double r0[9] = {x, y, 1, 0, 0, 0, -u * x, -u * y, u};
-    const double r1[9] = {0, 0, 0, x, y, 1, -v * x, -v * y, v};
-    for (int q = 0; q < 9; ++q) { A[2 * k][q] = r0[q]; A[2 * k + 1][q] = r1[q]; }
-  }
-  if (!solve8(A)) return false;
-  bool fin = true;
-  for (int q = 0; q < 8; ++q) { H[q] = A[q][8]; fin = fin && isfinite(H[q]); }
-  H[8] = 1.0;
-  return fin;
-}
-
-// ---------------------------------------------------------------------------------------------- fundamental matrix: the minimal model
-// eight distinct indices from the stream of ransac_sample (eval_geom.h): its four, then four more
-__device__ void ransac_sample8(uint64_t seed, int hyp, int k, int (&idx)[8]) {
-  uint64_t state = seed ^ ((uint64_t)hyp * 0xD1342543DE82EF95ull);
-  int n = 0;
-  while (n < 8) {
-    state = splitmix(state);
-    const int c = (int)(state % (uint64_t)k);
-    bool dup = false;
-    for (int q = 0; q < n; ++q) dup = dup || idx[q] == c;
-    if (!dup) idx[n++] = c;
-  }
+    x = c.x; y = c.y; u = c.z; v = c.w;
+  }, H);
 }
 
 // inlier(F, x, y, u, v) of the specification: squared Sampson distance <= thresh^2, without the division
@@ -138,16 +124,20 @@ __device__ void vf_denormalise(const double (&Fn)[9], double cx, double cy, doub
   }
 }
 
-// null vector of the 8 x 9 system by Gauss-Jordan elimination with complete pivoting; the column without a pivot is the free variable.
-// The array is indexed by the pivot search, so it lives in LDS: entry (r, c) at A[(9 r + c) ld]
-__device__ bool vf_null8x9(double* A, int ld, double (&f)[9]) {
-  unsigned rused = 0u, cused = 0u, prow = 0u, pcol = 0u;      // prow, pcol: four bits per elimination step
+// Gauss-Jordan elimination with complete pivoting of an R x 9 system (R = 8: the fundamental model, R = 5: the five-point solver); the
+// 9 - R columns left without a pivot (the clear bits of cused) are the free variables of its null space.  prow, pcol: four bits per
+// elimination step.  The array is indexed by the pivot search, so it lives in LDS: entry (r, c) at A[(9 r + c) ld].  The variable of
+// step s for the free column fc is -A(prow_s, fc) / A(prow_s, pcol_s); false when a pivot is 0 or not finite
+template <int R>
+__device__ __forceinline__ bool vf_eliminate(double* A, int ld, unsigned& cused, unsigned& prow, unsigned& pcol) {
+  unsigned rused = 0u;
+  cused = 0u; prow = 0u; pcol = 0u;
 #pragma unroll 1
-  for (int s = 0; s < 8; ++s) {
+  for (int s = 0; s < R; ++s) {
     int pr = -1, pc = -1;
     double best = 0.0;
 #pragma unroll 1
-    for (int r = 0; r < 8; ++r) {
+    for (int r = 0; r < R; ++r) {
       if ((rused >> r) & 1u) continue;
       for (int c = 0; c < 9; ++c) {
         if ((cused >> c) & 1u) continue;
@@ -162,27 +152,16 @@ __device__ bool vf_null8x9(double* A, int ld, double (&f)[9]) {
     pcol |= (unsigned)pc << (4 * s);
     const double piv = A[(9 * pr + pc) * ld];
 #pragma unroll 1
-    for (int r = 0; r < 8; ++r) {
+    for (int r = 0; r < R; ++r) {
       if (r == pr) continue;
       const double m = A[(9 * r + pc) * ld] / piv;
       for (int c = 0; c < 9; ++c) A[(9 * r + c) * ld] -= m * A[(9 * pr + c) * ld];
     }
   }
-  const int fc = __ffs((int)(~cused & 0x1ffu)) - 1;          // eight of nine bits are set: 0 <= fc <= 8
-  bool fin = true;
-#pragma unroll
-  for (int c = 0; c < 9; ++c) f[c] = 1.0;                    // the free variable keeps this value
-  for (int s = 0; s < 8; ++s) {
-    const int pr = (prow >> (4 * s)) & 15, pc = (pcol >> (4 * s)) & 15;
-    const double val = -A[(9 * pr + fc) * ld] / A[(9 * pr + pc) * ld];
-    fin = fin && isfinite(val);
-#pragma unroll
-    for (int c = 0; c < 9; ++c) f[c] = c == pc ? val : f[c];
-  }
-  return fin;
+  return true;
 }
 
-// F_h of the specification through eight correspondences of the dense array; A: 72 doubles of LDS at stride ld (vf_null8x9)
+// F_h of the specification through eight correspondences of the dense array; A: 72 doubles of LDS at stride ld (vf_eliminate)
 __device__ bool fundamental8_dense(const float4* __restrict__ corr, const int (&idx)[8], double* A, int ld, double (&F)[9]) {
   double cx = 0.0, cy = 0.0, cu = 0.0, cv = 0.0;
 #pragma unroll 1
@@ -209,125 +188,27 @@ __device__ bool fundamental8_dense(const float4* __restrict__ corr, const int (&
 #pragma unroll
     for (int q = 0; q < 9; ++q) A[(9 * k + q) * ld] = row[q];
   }
+  // the null vector: the column without a pivot is the free variable and keeps the value 1
+  unsigned cused, prow, pcol;
+  if (!vf_eliminate<8>(A, ld, cused, prow, pcol)) return false;
+  const int fc = __ffs((int)(~cused & 0x1ffu)) - 1;          // eight of nine bits are set: 0 <= fc <= 8
   double fn[9];
-  if (!vf_null8x9(A, ld, fn)) return false;
+  bool fin = true;
+#pragma unroll
+  for (int c = 0; c < 9; ++c) fn[c] = 1.0;
+  for (int s = 0; s < 8; ++s) {
+    const int pr = (prow >> (4 * s)) & 15, pc = (pcol >> (4 * s)) & 15;
+    const double val = -A[(9 * pr + fc) * ld] / A[(9 * pr + pc) * ld];
+    fin = fin && isfinite(val);
+#pragma unroll
+    for (int c = 0; c < 9; ++c) fn[c] = c == pc ? val : fn[c];
+  }
+  if (!fin) return false;
   vf_denormalise(fn, cx, cy, s0, cu, cv, s1, F);
   return vf_unit(F);
 }
 
-// the hypotheses kernel's body for a set with the fundamental model: as the homography's below, eight points per model, Sampson scoring
-__device__ void vf_hyp_fundamental(const VerifyDev& e, int K, int h0, uint64_t seed, int iters, double t2, double (*s_H)[10], int* s_ok,
-                                   int (*s_cnt)[VF_HB]) {
-  __shared__ double s_A[72][VF_HB];                       // the elimination arrays of the VF_HB solving lanes, lane-minor
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  if (K < 8) {                                             // the same for every thread of the workgroup
-    if (t < VF_HB && h0 + t < iters) e.hypcount[h0 + t] = -1;
-    return;
-  }
-  if (t < VF_HB) {
-    double F[9];
-    bool ok = false;
-    if (h0 + t < iters) {
-      int idx[8];
-      ransac_sample8(seed, h0 + t, K, idx);
-      ok = fundamental8_dense(e.corr, idx, &s_A[0][t], VF_HB, F);
-    }
-    for (int c = 0; c < 9; ++c) s_H[t][c] = ok ? F[c] : 0.0;
-    s_ok[t] = ok ? 1 : 0;
-  }
-  __syncthreads();
-  int cnt[VF_HB];
-#pragma unroll
-  for (int b = 0; b < VF_HB; ++b) cnt[b] = 0;
-  for (int p0 = 0; p0 < K; p0 += 256) {                  // K is the same for the whole workgroup
-    const int p = p0 + t;
-    const bool have = p < K;
-    const float4 c = e.corr[have ? p : 0];
-    const double x = c.x, y = c.y, u = c.z, v = c.w;
-#pragma unroll
-    for (int b = 0; b < VF_HB; ++b) {
-      double F[9];
-#pragma unroll
-      for (int q = 0; q < 9; ++q) F[q] = s_H[b][q];
-      cnt[b] += have && sampson_in(F, x, y, u, v, t2) ? 1 : 0;
-    }
-    __syncthreads();                                       // keeps the models in LDS, as in the homography's loop
-  }
-#pragma unroll
-  for (int b = 0; b < VF_HB; ++b) {
-    int s = cnt[b];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if (lane == 0) s_cnt[wave][b] = s;
-  }
-  __syncthreads();
-  if (t < VF_HB && h0 + t < iters)
-    e.hypcount[h0 + t] = s_ok[t] ? s_cnt[0][t] + s_cnt[1][t] + s_cnt[2][t] + s_cnt[3][t] : -1;
-}
-
-// ---------------------------------------------------------------------------------------------- hypotheses
-// one workgroup per VF_HB hypotheses of one set.  The first VF_HB lanes solve one model each (their elimination array is indexed by the
-// pivot search and lives in scratch); the scoring loop keeps VF_HB counters in registers and reads the models at wave-uniform LDS addresses.
-__global__ __launch_bounds__(256) void verify_hyp_kernel(const VerifyDev* __restrict__ vs, uint64_t seed, int iters, double t2) {
-  __shared__ double s_H[VF_HB][10];
-  __shared__ int s_ok[VF_HB];
-  __shared__ int s_cnt[4][VF_HB];
-  const VerifyDev& e = vs[blockIdx.y];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int K = e.nvalid[0];
-  const int h0 = blockIdx.x * VF_HB;
-  if (e.model == GIMS_VERIFY_MODEL_FUNDAMENTAL) {           // per set: the same for every thread of the workgroup
-    vf_hyp_fundamental(e, K, h0, seed, iters, t2, s_H, s_ok, s_cnt);
-    return;
-  }
-  if (K < 4) {                                             // the same for every thread of the workgroup
-    if (t < VF_HB && h0 + t < iters) e.hypcount[h0 + t] = -1;
-    return;
-  }
-  if (t < VF_HB) {
-    double H[9];
-    bool ok = false;
-    if (h0 + t < iters) {
-      int idx[4];
-      ransac_sample(seed, h0 + t, K, idx);
-      ok = homography4_dense(e.corr, idx, H);
-    }
-    for (int c = 0; c < 9; ++c) s_H[t][c] = ok ? H[c] : 0.0;
-    s_ok[t] = ok ? 1 : 0;
-  }
-  __syncthreads();
-  int cnt[VF_HB];
-#pragma unroll
-  for (int b = 0; b < VF_HB; ++b) cnt[b] = 0;
-  for (int p0 = 0; p0 < K; p0 += 256) {                  // K is the same for the whole workgroup
-    const int p = p0 + t;
-    const bool have = p < K;
-    const float4 c = e.corr[have ? p : 0];
-    const double x = c.x, y = c.y, u = c.z, v = c.w;
-#pragma unroll
-    for (int b = 0; b < VF_HB; ++b) {
-      double H[9];
-#pragma unroll
-      for (int q = 0; q < 9; ++q) H[q] = s_H[b][q];
-      cnt[b] += have && reproj2(H, x, y, u, v) <= t2 ? 1 : 0;
-    }
-    // the models are read from LDS again for every tile (wave-uniform addresses: broadcasts).  Without this barrier the compiler hoists
-    // all VF_HB models out of the loop, 288 registers, and the kernel runs at one wave per SIMD or spills
-    __syncthreads();
-  }
-#pragma unroll
-  for (int b = 0; b < VF_HB; ++b) {
-    int s = cnt[b];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if (lane == 0) s_cnt[wave][b] = s;
-  }
-  __syncthreads();
-  if (t < VF_HB && h0 + t < iters)
-    e.hypcount[h0 + t] = s_ok[t] ? s_cnt[0][t] + s_cnt[1][t] + s_cnt[2][t] + s_cnt[3][t] : -1;
-}
-
-// ---------------------------------------------------------------------------------------------- finish
+// ---------------------------------------------------------------------------------------------- sums over the correspondences, refits
 // the per-thread sums of a sweep over the correspondences, reduced across each wave into one LDS row per wave; after the caller's barrier
 // thread 0 adds the 16 rows in wave order (vf_total)
 template <int N>
@@ -352,8 +233,9 @@ __device__ __forceinline__ void vf_normal_add(double (&acc)[44], double x, doubl
     for (int b = a; b < 8; ++b) acc[q++] += r0[a] * r0[b] + r1[a] * r1[b];
   for (int a = 0; a < 8; ++a) acc[36 + a] += r0[a] * u + r1[a] * v;
 }
-// thread 0: the reduced normal equations -> solve8; true and h[0..7] when the solve succeeds with finite entries
-__device__ bool vf_normal_solve(const double (*s_acc)[VF_ACC], double (&h)[8]) {
+// thread 0: the reduced normal equations -> solve8; true and h[0..7] when the solve succeeds with finite entries.  Out of line: its two
+// callers in verify_finish_kernel (the lo_iters == 0 refit and HomographyModel::refit) then share one 8 x 9 array of scratch
+__device__ __noinline__ bool vf_normal_solve(const double (*s_acc)[VF_ACC], double (&h)[8]) {
   double A[8][9];
   int q = 0;
   for (int a = 0; a < 8; ++a)
@@ -368,8 +250,14 @@ __device__ bool vf_normal_solve(const double (*s_acc)[VF_ACC], double (&h)[8]) {
   for (int c = 0; c < 8; ++c) { h[c] = A[c][8]; fin = fin && isfinite(h[c]); }
   return fin;
 }
+// the 45 sums a_i a_j (i <= j) that one normalised correspondence adds
+__device__ __forceinline__ void vf_epipolar_add(double (&acc)[45], double x, double y, double u, double v) {
+  const double a[9] = {u * x, u * y, u, v * x, v * y, v, x, y, 1.0};
+  int q = 0;
+  for (int i = 0; i < 9; ++i)
+    for (int j = i; j < 9; ++j) acc[q++] += a[i] * a[j];
+}
 
-// ---------------------------------------------------------------------------------------------- fundamental matrix: refit and rank 2
 // jacobi(S) of the specification on an n x n symmetric matrix held in LDS (leading dimension 9): the eigenvector of the smallest
 // eigenvalue.  One thread; S is destroyed, V receives all eigenvectors.
 __device__ void vf_jacobi(double (*S)[9], double (*V)[9], int n, double* vec) {
@@ -422,187 +310,421 @@ __device__ void vf_rank2(double (&F)[9], double (*S)[9], double (*V)[9]) {
     for (int c = 0; c < 9; ++c) F[c] = G[c];
 }
 
-// the 45 sums a_i a_j (i <= j) that one normalised correspondence adds
-__device__ __forceinline__ void vf_epipolar_add(double (&acc)[45], double x, double y, double u, double v) {
-  const double a[9] = {u * x, u * y, u, v * x, v * y, v, x, y, 1.0};
-  int q = 0;
-  for (int i = 0; i < 9; ++i)
-    for (int j = i; j < 9; ++j) acc[q++] += a[i] * a[j];
+// v1, v2, v3 of the specification's svd(E) (v3 at the smallest eigenvalue of E^T E), w1 = E v1, w2 = E v2 and their lengths (one thread;
+// S, V: the LDS of vf_jacobi)
+__device__ void vp_svd(const double (&E)[9], double (*S)[9], double (*V)[9], double (&v)[3][3], double (&w)[2][3], double (&s)[2]) {
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) S[i][j] = E[i] * E[j] + E[3 + i] * E[3 + j] + E[6 + i] * E[6 + j];
+  double unused[3];
+  vf_jacobi(S, V, 3, unused);
+  int m = 0;
+  for (int k = 1; k < 3; ++k)
+    if (S[k][k] < S[m][m]) m = k;
+  const int a = m == 0 ? 1 : 0, b = m == 2 ? 1 : 2;
+  for (int k = 0; k < 3; ++k) { v[0][k] = V[k][a]; v[1][k] = V[k][b]; v[2][k] = V[k][m]; }
+  for (int q = 0; q < 2; ++q) {
+    for (int r = 0; r < 3; ++r) w[q][r] = E[3 * r] * v[q][0] + E[3 * r + 1] * v[q][1] + E[3 * r + 2] * v[q][2];
+    s[q] = sqrt(w[q][0] * w[q][0] + w[q][1] * w[q][1] + w[q][2] * w[q][2]);
+  }
 }
 
-// the finish kernel's body for a set with the fundamental model, entered by the whole workgroup behind the barrier that publishes s_best.
-// The rule on barriers is the kernel's: every decision is thread 0's, stored in LDS and read by all threads after the next barrier.
-__device__ void vf_finish_fundamental(const VerifyDev& e, int K, int bc, int bh, uint64_t seed, int lo_iters, double t2, double (*s_acc)[VF_ACC]) {
-  __shared__ double f_F[9];           // the accepted model
-  __shared__ double f_Fn[9];          // the candidate of the current round
-  __shared__ double f_norm[6];        // cx, cy, cu, cv, scale0, scale1
-  __shared__ double f_S[9][9], f_V[9][9];
-  __shared__ double f_nprev;          // |I_{l-1}|
-  __shared__ int f_ok, f_stop, f_rounds;
-  const int t = threadIdx.x;
-  if (t == 0) {
-    f_ok = 0; f_stop = 0; f_rounds = 0;
-    if (bc >= 0 && K >= 8) {
-      int idx[8];
-      ransac_sample8(seed, bh, K, idx);
-      double F[9];
-      if (fundamental8_dense(e.corr, idx, &f_S[0][0], 1, F)) {
-        for (int c = 0; c < 9; ++c) f_F[c] = F[c];
-        f_ok = 1;
+// ess(E) of the specification: singular values (1, 1, 0), unit norm; E itself when that fails
+__device__ void vp_ess(double (&E)[9], double (*S)[9], double (*V)[9]) {
+  double v[3][3], w[2][3], s[2];
+  vp_svd(E, S, V, v, w, s);
+  if (!(s[0] > 0.0 && s[1] > 0.0)) return;
+  double G[9];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) G[3 * r + c] = w[0][r] * v[0][c] / s[0] + w[1][r] * v[1][c] / s[1];
+  if (vf_unit(G))
+    for (int c = 0; c < 9; ++c) E[c] = G[c];
+}
+
+// camera coordinates of a correspondence: (x - cx) / fx, (y - cy) / fy for cam = fx0, fy0, cx0, cy0, fx1, fy1, cx1, cy1
+__device__ __forceinline__ void vp_norm(const float4 c, const double (&cam)[8], double& x, double& y, double& u, double& v) {
+  x = ((double)c.x - cam[2]) / cam[0];
+  y = ((double)c.y - cam[3]) / cam[1];
+  u = ((double)c.z - cam[6]) / cam[4];
+  v = ((double)c.w - cam[7]) / cam[5];
+}
+
+// ---------------------------------------------------------------------------------------------- the models
+// What the shared code below is templated on.  MIN: the least number of inliers a refit takes (and of correspondences a hypothesis of
+// the homography and the fundamental model takes; a pose set needs five, which its kernels check); NACC: the sums of a refit;
+// coords: the coordinates a correspondence is judged in (cam is read by the pose model only); inlier; add: what one normalised inlier
+// adds to the NACC sums; refit: thread 0's solve of the reduced sums (S, V: the LDS of vf_jacobi) and the way back through the
+// similarities (cx, cy, sc0), (cu, cv, sc1) into out, false when there is no finite candidate; minimal: the model of hypothesis hyp.
+struct HomographyModel {
+  static constexpr int MIN = 4, NACC = 44;
+  static __device__ __forceinline__ void coords(const float4 c, const double (&)[8], double& x, double& y, double& u, double& v) {
+    x = c.x; y = c.y; u = c.z; v = c.w;
+  }
+  static __device__ __forceinline__ bool inlier(const double (&H)[9], double x, double y, double u, double v, double t2) {
+    return reproj2(H, x, y, u, v) <= t2;
+  }
+  static __device__ __forceinline__ void add(double (&acc)[44], double x, double y, double u, double v) { vf_normal_add(acc, x, y, u, v); }
+  static __device__ __forceinline__ bool minimal(const float4* __restrict__ corr, uint64_t seed, int hyp, int K, double*, int, double (&H)[9]) {
+    int idx[4];
+    ransac_sample(seed, hyp, K, idx);
+    return homography4_dense(corr, idx, H);
+  }
+  static __device__ __forceinline__ bool refit(const double (*s_acc)[VF_ACC], double (*)[9], double (*)[9], double cx, double cy, double sc0,
+                                               double cu, double cv, double sc1, double* out) {
+    double h[8];
+    bool ok = vf_normal_solve(s_acc, h);
+    if (ok) {
+      const double Hn[9] = {h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], 1.0};
+      double M[9], Hd[9];
+      for (int r = 0; r < 3; ++r) {                   // M = Hn T0
+        M[3 * r] = Hn[3 * r] * sc0;
+        M[3 * r + 1] = Hn[3 * r + 1] * sc0;
+        M[3 * r + 2] = Hn[3 * r + 2] - sc0 * (Hn[3 * r] * cx + Hn[3 * r + 1] * cy);
       }
+      for (int c = 0; c < 3; ++c) {                   // H' = T1^-1 M
+        Hd[c] = M[c] / sc1 + cu * M[6 + c];
+        Hd[3 + c] = M[3 + c] / sc1 + cv * M[6 + c];
+        Hd[6 + c] = M[6 + c];
+      }
+      const double w = Hd[8];
+      ok = w != 0.0 && isfinite(w);
+      if (ok) {
+        for (int c = 0; c < 9; ++c) { Hd[c] = Hd[c] / w; ok = ok && isfinite(Hd[c]); }
+        for (int c = 0; c < 9; ++c) out[c] = Hd[c];
+      }
+    }
+    return ok;
+  }
+};
+
+// x1^T M x0 = 0 with the Sampson distance: the fundamental matrix on pixel coordinates, made rank 2, and (CALIBRATED) the essential
+// matrix on camera coordinates, projected onto the essential manifold
+template <bool CALIBRATED>
+struct EpipolarModel {
+  static constexpr int MIN = 8, NACC = 45;
+  static __device__ __forceinline__ void coords(const float4 c, const double (&cam)[8], double& x, double& y, double& u, double& v) {
+    if constexpr (CALIBRATED) {
+      vp_norm(c, cam, x, y, u, v);
+    } else {
+      x = c.x; y = c.y; u = c.z; v = c.w;
     }
   }
-  __syncthreads();
-  if (!f_ok) {
-    if (t == 0) {
-      for (int c = 0; c < 8; ++c) e.record[c] = 0.f;
-      e.record[VF_NVALID] = (float)K;
-      e.record[VF_ERR_CORNER] = -1.f;
-      for (int c = 0; c < 9; ++c) e.hom[c] = 0.f;
-    }
-    return;
+  static __device__ __forceinline__ bool inlier(const double (&F)[9], double x, double y, double u, double v, double t2) {
+    return sampson_in(F, x, y, u, v, t2);
   }
-  double F[9];
-  for (int c = 0; c < 9; ++c) F[c] = f_F[c];
-  if (lo_iters > 0) {
-    {  // |I_0|
-      double a[1] = {0.0};
-      for (int p = t; p < K; p += 1024) {
-        const float4 c4 = e.corr[p];
-        a[0] += sampson_in(F, c4.x, c4.y, c4.z, c4.w, t2) ? 1.0 : 0.0;
-      }
-      vf_partials(a, s_acc);
-      __syncthreads();
-      if (t == 0) f_nprev = vf_total(s_acc, 0);
-      __syncthreads();
-    }
-    for (int l = 1; l <= lo_iters; ++l) {
-      // (a) centroids of the inliers of the accepted model
-      {
-        double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-        for (int p = t; p < K; p += 1024) {
-          const float4 c4 = e.corr[p];
-          const double x = c4.x, y = c4.y, u = c4.z, v = c4.w;
-          if (sampson_in(F, x, y, u, v, t2)) { a[0] += 1.0; a[1] += x; a[2] += y; a[3] += u; a[4] += v; }
-        }
-        vf_partials(a, s_acc);
-      }
-      __syncthreads();
-      if (t == 0) {
-        const double n = vf_total(s_acc, 0);
-        f_stop = n < 8.0 ? 1 : 0;
-        if (n >= 8.0)
-          for (int c = 0; c < 4; ++c) f_norm[c] = vf_total(s_acc, 1 + c) / n;
-      }
-      __syncthreads();
-      if (f_stop) break;
-      const double cx = f_norm[0], cy = f_norm[1], cu = f_norm[2], cv = f_norm[3];
-      // (b) mean distances to the centroids
-      {
-        double a[3] = {0.0, 0.0, 0.0};
-        for (int p = t; p < K; p += 1024) {
-          const float4 c4 = e.corr[p];
-          const double x = c4.x, y = c4.y, u = c4.z, v = c4.w;
-          if (sampson_in(F, x, y, u, v, t2)) {
-            a[0] += 1.0;
-            a[1] += sqrt((x - cx) * (x - cx) + (y - cy) * (y - cy));
-            a[2] += sqrt((u - cu) * (u - cu) + (v - cv) * (v - cv));
-          }
-        }
-        vf_partials(a, s_acc);
-      }
-      __syncthreads();
-      if (t == 0) {
-        const double n = vf_total(s_acc, 0), m0 = vf_total(s_acc, 1) / n, m1 = vf_total(s_acc, 2) / n;
-        f_norm[4] = m0 == 0.0 ? 1.0 : sqrt(2.0) / m0;
-        f_norm[5] = m1 == 0.0 ? 1.0 : sqrt(2.0) / m1;
-      }
-      __syncthreads();
-      const double sc0 = f_norm[4], sc1 = f_norm[5];
-      // (c) the 9 x 9 matrix of sums over the normalised inliers, its smallest eigenvector, back to pixel coordinates, rank 2
-      {
-        double acc[45];
-        for (int c = 0; c < 45; ++c) acc[c] = 0.0;
-        for (int p = t; p < K; p += 1024) {
-          const float4 c4 = e.corr[p];
-          const double x = c4.x, y = c4.y, u = c4.z, v = c4.w;
-          if (sampson_in(F, x, y, u, v, t2)) vf_epipolar_add(acc, (x - cx) * sc0, (y - cy) * sc0, (u - cu) * sc1, (v - cv) * sc1);
-        }
-        vf_partials(acc, s_acc);
-      }
-      __syncthreads();
-      if (t == 0) {
-        int q = 0;
-        for (int i = 0; i < 9; ++i)
-          for (int j = i; j < 9; ++j) {
-            const double s = vf_total(s_acc, q);
-            f_S[i][j] = s; f_S[j][i] = s;
-            ++q;
-          }
-        double fn[9], Fd[9];
-        vf_jacobi(f_S, f_V, 9, fn);
-        vf_denormalise(fn, cx, cy, sc0, cu, cv, sc1, Fd);
-        bool ok = vf_unit(Fd);
-        if (ok) {
-          vf_rank2(Fd, f_S, f_V);
-          for (int c = 0; c < 9; ++c) f_Fn[c] = Fd[c];
-        }
-        f_stop = ok ? 0 : 1;
-      }
-      __syncthreads();
-      if (f_stop) break;
-      double Fc[9];
-      for (int c = 0; c < 9; ++c) Fc[c] = f_Fn[c];
-      // (d) the candidate's inliers against the accepted model's
-      {
-        double a[2] = {0.0, 0.0};
-        for (int p = t; p < K; p += 1024) {
-          const float4 c4 = e.corr[p];
-          const double x = c4.x, y = c4.y, u = c4.z, v = c4.w;
-          const bool was = sampson_in(F, x, y, u, v, t2), is = sampson_in(Fc, x, y, u, v, t2);
-          a[0] += is ? 1.0 : 0.0;
-          a[1] += is != was ? 1.0 : 0.0;
-        }
-        vf_partials(a, s_acc);
-      }
-      __syncthreads();
-      if (t == 0) {
-        const double n = vf_total(s_acc, 0), changed = vf_total(s_acc, 1);
-        if (n < f_nprev) {
-          f_stop = 1;                                     // fewer inliers: keep F_{l-1}
-        } else {
-          for (int c = 0; c < 9; ++c) f_F[c] = f_Fn[c];
-          f_nprev = n;
-          f_rounds = f_rounds + 1;
-          f_stop = changed == 0.0 ? 2 : 0;                // accepted; the same set again: converged
-        }
-      }
-      __syncthreads();
-      const int stop = f_stop;
-      if (stop != 1)
-        for (int c = 0; c < 9; ++c) F[c] = Fc[c];
-      if (stop) break;
-    }
+  static __device__ __forceinline__ void add(double (&acc)[45], double x, double y, double u, double v) { vf_epipolar_add(acc, x, y, u, v); }
+  // rank2(F) or ess(E) of the specification (one thread)
+  static __device__ __forceinline__ void project(double (&F)[9], double (*S)[9], double (*V)[9]) {
+    if constexpr (CALIBRATED) vp_ess(F, S, V);
+    else vf_rank2(F, S, V);
   }
-  // every path above ends behind a barrier that follows thread 0's last stores to f_F and f_rounds.  No accepted round (lo_iters == 0
-  // has none): the model is the best hypothesis made rank 2
-  if (f_rounds == 0) {
-    if (t == 0) {
-      double G[9];
-      for (int c = 0; c < 9; ++c) G[c] = f_F[c];
-      vf_rank2(G, f_S, f_V);
-      for (int c = 0; c < 9; ++c) f_F[c] = G[c];
+  // the 9 x 9 matrix of sums, its smallest eigenvector, back through the similarities, unit norm, the projection
+  static __device__ __forceinline__ bool refit(const double (*s_acc)[VF_ACC], double (*S)[9], double (*V)[9], double cx, double cy, double sc0,
+                                               double cu, double cv, double sc1, double* out) {
+    int q = 0;
+    for (int i = 0; i < 9; ++i)
+      for (int j = i; j < 9; ++j) {
+        const double s = vf_total(s_acc, q);
+        S[i][j] = s; S[j][i] = s;
+        ++q;
+      }
+    double fn[9], Fd[9];
+    vf_jacobi(S, V, 9, fn);
+    vf_denormalise(fn, cx, cy, sc0, cu, cv, sc1, Fd);
+    const bool ok = vf_unit(Fd);
+    if (ok) {
+      project(Fd, S, V);
+      for (int c = 0; c < 9; ++c) out[c] = Fd[c];
     }
+    return ok;
+  }
+};
+struct FundamentalModel : EpipolarModel<false> {
+  // eight indices: the four of the homography's sample, then four more.  A: 72 doubles of LDS at stride ld
+  static __device__ __forceinline__ bool minimal(const float4* __restrict__ corr, uint64_t seed, int hyp, int K, double* A, int ld, double (&F)[9]) {
+    int idx[8];
+    ransac_sample(seed, hyp, K, idx);
+    return fundamental8_dense(corr, idx, A, ld, F);
+  }
+};
+using PoseModel = EpipolarModel<true>;           // its hypotheses are the five-point solver's: up to ten models per sample, no `minimal`
+
+// ---------------------------------------------------------------------------------------------- scoring
+// Scores the models in the rows g0 .. min(g0 + VF_HB, M) - 1 of s_M (LDS) against the K correspondences of the set, by the whole
+// workgroup of 256: every thread takes one correspondence per tile and keeps VF_HB counters in registers; the models are read at
+// wave-uniform LDS addresses.  Leaves the sums of wave w in s_cnt[w][0 .. VF_HB - 1]; the caller's barrier publishes them.
+template <class Model>
+__device__ __forceinline__ void vf_score(const VerifyDev& e, int K, const double (&cam)[8], double t2, const double (*s_M)[10], int g0, int M,
+                                         int (*s_cnt)[VF_HB]) {
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  int cnt[VF_HB];
+#pragma unroll
+  for (int b = 0; b < VF_HB; ++b) cnt[b] = 0;
+  for (int p0 = 0; p0 < K; p0 += 256) {                  // K is the same for the whole workgroup
+    const int p = p0 + t;
+    const bool have = p < K;
+    double x, y, u, v;
+    Model::coords(e.corr[have ? p : 0], cam, x, y, u, v);
+#pragma unroll
+    for (int b = 0; b < VF_HB; ++b) {
+      if (g0 + b < M) {
+        double Mb[9];
+#pragma unroll
+        for (int q = 0; q < 9; ++q) Mb[q] = s_M[g0 + b][q];
+        cnt[b] += have && Model::inlier(Mb, x, y, u, v, t2) ? 1 : 0;
+      }
+    }
+    // the models are read from LDS again for every tile (wave-uniform addresses: broadcasts).  Without this barrier the compiler hoists
+    // all VF_HB models out of the loop, 288 registers, and the kernel runs at one wave per SIMD or spills
     __syncthreads();
   }
-  for (int c = 0; c < 9; ++c) F[c] = f_F[c];
-  {
+#pragma unroll
+  for (int b = 0; b < VF_HB; ++b) {
+    int s = cnt[b];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (lane == 0) s_cnt[wave][b] = s;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- hypotheses (homography, fundamental)
+// The first VF_HB lanes solve one model each (the homography's elimination array is indexed by the pivot search and lives in scratch,
+// the fundamental model's in s_A, lane-minor); then vf_score.  hypcount[h] = the score, -1 without a model.
+template <class Model>
+__device__ __forceinline__ void vf_hypotheses(const VerifyDev& e, int K, int h0, uint64_t seed, int iters, double t2, double (*s_A)[VF_HB],
+                                              double (*s_H)[10], int* s_ok, int (*s_cnt)[VF_HB]) {
+  const int t = threadIdx.x;
+  if (K < Model::MIN) {                                    // the same for every thread of the workgroup
+    if (t < VF_HB && h0 + t < iters) e.hypcount[h0 + t] = -1;
+    return;
+  }
+  if (t < VF_HB) {
+    double H[9];
+    bool ok = false;
+    if (h0 + t < iters) ok = Model::minimal(e.corr, seed, h0 + t, K, &s_A[0][t], VF_HB, H);
+    for (int c = 0; c < 9; ++c) s_H[t][c] = ok ? H[c] : 0.0;
+    s_ok[t] = ok ? 1 : 0;
+  }
+  __syncthreads();
+  const double cam[8] = {};                                // no camera in these models
+  vf_score<Model>(e, K, cam, t2, s_H, 0, VF_HB, s_cnt);
+  __syncthreads();
+  if (t < VF_HB && h0 + t < iters)
+    e.hypcount[h0 + t] = s_ok[t] ? s_cnt[0][t] + s_cnt[1][t] + s_cnt[2][t] + s_cnt[3][t] : -1;
+}
+
+// one workgroup per VF_HB hypotheses of one set.  The register budget is stated (8 waves per SIMD: 64 VGPRs, which the kernel meets
+// without a spill): left to itself the scheduler spreads the constant rows of the four-point system over 62 to 84 registers, depending
+// on code that has nothing to do with them
+__global__ __launch_bounds__(256, 8) void verify_hyp_kernel(const VerifyDev* __restrict__ vs, uint64_t seed, int iters, double t2) {
+  __shared__ double s_A[72][VF_HB];                       // the elimination arrays of the VF_HB lanes that solve a fundamental matrix
+  __shared__ double s_H[VF_HB][10];
+  __shared__ int s_ok[VF_HB];
+  __shared__ int s_cnt[4][VF_HB];
+  const VerifyDev& e = vs[blockIdx.y];
+  const int K = e.nvalid[0];
+  const int h0 = blockIdx.x * VF_HB;
+  if (e.model == GIMS_VERIFY_MODEL_FUNDAMENTAL)             // per set: the same for every thread of the workgroup
+    vf_hypotheses<FundamentalModel>(e, K, h0, seed, iters, t2, s_A, s_H, s_ok, s_cnt);
+  else
+    vf_hypotheses<HomographyModel>(e, K, h0, seed, iters, t2, s_A, s_H, s_ok, s_cnt);
+}
+
+// ---------------------------------------------------------------------------------------------- the pieces of a finish kernel
+// The best hypothesis of a set -- highest hypcount >> SHIFT, lowest index among equals -- by a workgroup of 1024.  Ends behind a barrier;
+// only thread 0 returns the result in (bc, bh): bc the counter itself (-1 when no hypothesis has a model, or iters == 0).
+template <int SHIFT>
+__device__ __forceinline__ void vf_best(const VerifyDev& e, int iters, int (*s_best)[2], int& bc, int& bh) {
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  bc = -1; bh = 0x7fffffff;
+  for (int h = t; h < iters; h += 1024) {
+    const int c = e.hypcount[h];
+    if ((c >> SHIFT) > (bc >> SHIFT)) { bc = c; bh = h; }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    const int oc = __shfl_xor(bc, o, 64), oh = __shfl_xor(bh, o, 64);
+    if ((oc >> SHIFT) > (bc >> SHIFT) || ((oc >> SHIFT) == (bc >> SHIFT) && oh < bh)) { bc = oc; bh = oh; }
+  }
+  if (lane == 0) { s_best[wave][0] = bc; s_best[wave][1] = bh; }
+  __syncthreads();
+  if (t == 0)
+    for (int w = 1; w < 16; ++w)
+      if ((s_best[w][0] >> SHIFT) > (bc >> SHIFT) || ((s_best[w][0] >> SHIFT) == (bc >> SHIFT) && s_best[w][1] < bh)) {
+        bc = s_best[w][0]; bh = s_best[w][1];
+      }
+}
+
+// the outputs of a set without a model (the mask was cleared by the gather kernel); width: the floats of its model output
+__device__ __forceinline__ void vf_no_model(const VerifyDev& e, int K, int width) {
+  if (threadIdx.x == 0) {
+    for (int c = 0; c < 8; ++c) e.record[c] = 0.f;
+    e.record[VF_NVALID] = (float)K;
+    e.record[VF_ERR_CORNER] = -1.f;
+    for (int c = 0; c < width; ++c) e.hom[c] = 0.f;
+  }
+}
+
+// the sign rule of the specification: the factor that makes the entry of largest magnitude (the first such) positive
+__device__ __forceinline__ double vf_sign(const double (&F)[9]) {
+  int m = 0;
+  for (int c = 1; c < 9; ++c)
+    if (fabs(F[c]) > fabs(F[m])) m = c;
+  return F[m] < 0.0 ? -1.0 : 1.0;
+}
+
+// the LDS state of stage 2, one per finish kernel.  Thread 0 stores M (the model of the best hypothesis), stop = 0 and rounds = 0 before
+// the barrier in front of vf_local_opt
+struct VfLo {
+  double M[9];             // the accepted model
+  double Mn[9];            // the candidate of the current round
+  double norm[6];          // cx, cy, cu, cv, scale0, scale1
+  double S[9][9], V[9][9]; // thread 0's eigen-solves (and, before stage 2, the elimination array of its minimal solve)
+  double nprev;            // |I_{l-1}|
+  int stop, rounds;
+};
+
+// The guarded local optimisation of the specification, by a workgroup of 1024: |I_0|, then per round (a) the centroids of the inliers of
+// the accepted model, (b) their mean distances to them, (c) the model's sums over the normalised inliers and thread 0's refit, (d) the
+// candidate's inliers against the accepted model's; the candidate is accepted unless it has fewer.  Stops after lo_iters rounds, when
+// fewer than Model::MIN inliers are left, when a refit fails, when a candidate is refused, or (accepted) when the inlier set repeats.
+//
+// THE RULE ON BARRIERS, which holds in this function and in the kernels that call it: every decision is taken by thread 0, stored in LDS
+// and read by all threads after the barrier that follows; the next store to the same word comes after a later barrier.  No barrier sits
+// under a condition that is not one of those words, a kernel argument or a per-set constant.
+//
+// Returns behind a barrier that follows thread 0's last stores to lo.M and lo.rounds (lo_iters <= 0: nothing is done).
+template <class Model>
+__device__ __forceinline__ void vf_local_opt(const VerifyDev& e, int K, const double (&cam)[8], double t2, int lo_iters, VfLo& lo,
+                                             double (*s_acc)[VF_ACC]) {
+  if (lo_iters <= 0) return;
+  const int t = threadIdx.x;
+  constexpr double least = Model::MIN;
+  double F[9];
+  for (int c = 0; c < 9; ++c) F[c] = lo.M[c];
+  {  // |I_0|
     double a[1] = {0.0};
     for (int p = t; p < K; p += 1024) {
-      const float4 c4 = e.corr[p];
-      const bool in = sampson_in(F, c4.x, c4.y, c4.z, c4.w, t2);
+      double x, y, u, v;
+      Model::coords(e.corr[p], cam, x, y, u, v);
+      a[0] += Model::inlier(F, x, y, u, v, t2) ? 1.0 : 0.0;
+    }
+    vf_partials(a, s_acc);
+    __syncthreads();
+    if (t == 0) lo.nprev = vf_total(s_acc, 0);
+    __syncthreads();
+  }
+  for (int l = 1; l <= lo_iters; ++l) {
+    // (a) centroids of the inliers of the accepted model
+    {
+      double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+      for (int p = t; p < K; p += 1024) {
+        double x, y, u, v;
+        Model::coords(e.corr[p], cam, x, y, u, v);
+        if (Model::inlier(F, x, y, u, v, t2)) { a[0] += 1.0; a[1] += x; a[2] += y; a[3] += u; a[4] += v; }
+      }
+      vf_partials(a, s_acc);
+    }
+    __syncthreads();
+    if (t == 0) {
+      const double n = vf_total(s_acc, 0);
+      lo.stop = n < least ? 1 : 0;
+      if (n >= least)
+        for (int c = 0; c < 4; ++c) lo.norm[c] = vf_total(s_acc, 1 + c) / n;
+    }
+    __syncthreads();
+    if (lo.stop) break;
+    const double cx = lo.norm[0], cy = lo.norm[1], cu = lo.norm[2], cv = lo.norm[3];
+    // (b) mean distances to the centroids
+    {
+      double a[3] = {0.0, 0.0, 0.0};
+      for (int p = t; p < K; p += 1024) {
+        double x, y, u, v;
+        Model::coords(e.corr[p], cam, x, y, u, v);
+        if (Model::inlier(F, x, y, u, v, t2)) {
+          a[0] += 1.0;
+          a[1] += sqrt((x - cx) * (x - cx) + (y - cy) * (y - cy));
+          a[2] += sqrt((u - cu) * (u - cu) + (v - cv) * (v - cv));
+        }
+      }
+      vf_partials(a, s_acc);
+    }
+    __syncthreads();
+    if (t == 0) {
+      const double n = vf_total(s_acc, 0), m0 = vf_total(s_acc, 1) / n, m1 = vf_total(s_acc, 2) / n;
+      lo.norm[4] = m0 == 0.0 ? 1.0 : sqrt(2.0) / m0;
+      lo.norm[5] = m1 == 0.0 ? 1.0 : sqrt(2.0) / m1;
+    }
+    __syncthreads();
+    const double sc0 = lo.norm[4], sc1 = lo.norm[5];
+    // (c) the model's sums over the normalised inliers, thread 0's refit and the way back to the coordinates of the inlier test
+    {
+      double acc[Model::NACC];
+      for (int c = 0; c < Model::NACC; ++c) acc[c] = 0.0;
+      for (int p = t; p < K; p += 1024) {
+        double x, y, u, v;
+        Model::coords(e.corr[p], cam, x, y, u, v);
+        if (Model::inlier(F, x, y, u, v, t2)) Model::add(acc, (x - cx) * sc0, (y - cy) * sc0, (u - cu) * sc1, (v - cv) * sc1);
+      }
+      vf_partials(acc, s_acc);
+    }
+    __syncthreads();
+    if (t == 0) lo.stop = Model::refit(s_acc, lo.S, lo.V, cx, cy, sc0, cu, cv, sc1, lo.Mn) ? 0 : 1;
+    __syncthreads();
+    if (lo.stop) break;
+    double Fc[9];
+    for (int c = 0; c < 9; ++c) Fc[c] = lo.Mn[c];
+    // (d) the candidate's inliers against the accepted model's
+    {
+      double a[2] = {0.0, 0.0};
+      for (int p = t; p < K; p += 1024) {
+        double x, y, u, v;
+        Model::coords(e.corr[p], cam, x, y, u, v);
+        const bool was = Model::inlier(F, x, y, u, v, t2), is = Model::inlier(Fc, x, y, u, v, t2);
+        a[0] += is ? 1.0 : 0.0;
+        a[1] += is != was ? 1.0 : 0.0;
+      }
+      vf_partials(a, s_acc);
+    }
+    __syncthreads();
+    if (t == 0) {
+      const double n = vf_total(s_acc, 0), changed = vf_total(s_acc, 1);
+      if (n < lo.nprev) {
+        lo.stop = 1;                                    // fewer inliers: keep the model of round l - 1
+      } else {
+        for (int c = 0; c < 9; ++c) lo.M[c] = lo.Mn[c];
+        lo.nprev = n;
+        lo.rounds = lo.rounds + 1;
+        lo.stop = changed == 0.0 ? 2 : 0;               // accepted; the same set again: converged
+      }
+    }
+    __syncthreads();
+    const int stop = lo.stop;
+    if (stop != 1)
+      for (int c = 0; c < 9; ++c) F[c] = Fc[c];
+    if (stop) break;
+  }
+}
+
+// The final sweep: the mask under the model F, the inlier count in column 0 of the NSUM sums -- an inlier may add to the others through
+// extra(a, x, y, u, v) --, a barrier, and thread 0 writes the record (err_corner = -1).  score: the inliers of the best hypothesis bh
+struct VfNoExtra {
+  __device__ __forceinline__ void operator()(double (&)[1], double, double, double, double) const {}
+};
+template <class Model, int NSUM, class Extra>
+__device__ __forceinline__ void vf_final_sweep(const VerifyDev& e, int K, const double (&cam)[8], double t2, const double (&F)[9], int bh, int score,
+                                               const VfLo& lo, double (*s_acc)[VF_ACC], Extra extra) {
+  const int t = threadIdx.x;
+  {
+    double a[NSUM];
+    for (int c = 0; c < NSUM; ++c) a[c] = 0.0;
+    for (int p = t; p < K; p += 1024) {
+      double x, y, u, v;
+      Model::coords(e.corr[p], cam, x, y, u, v);
+      const bool in = Model::inlier(F, x, y, u, v, t2);
       e.inlier[e.rows[p]] = in ? 1 : 0;
-      a[0] += in ? 1.0 : 0.0;
+      if (in) {
+        a[0] += 1.0;
+        extra(a, x, y, u, v);
+      }
     }
     vf_partials(a, s_acc);
   }
@@ -612,257 +734,112 @@ __device__ void vf_finish_fundamental(const VerifyDev& e, int K, int bc, int bh,
     e.record[VF_OK] = 1.f;
     e.record[VF_NINLIERS] = (float)vf_total(s_acc, 0);
     e.record[VF_BEST_HYP] = (float)bh;
-    e.record[VF_BEST_HYP_INLIERS] = (float)bc;
-    e.record[VF_LO_ROUNDS] = (float)f_rounds;
+    e.record[VF_BEST_HYP_INLIERS] = (float)score;
+    e.record[VF_LO_ROUNDS] = (float)lo.rounds;
     e.record[VF_ERR_CORNER] = -1.f;
     e.record[VF_RESERVED] = 0.f;
-    int m = 0;
-    for (int c = 1; c < 9; ++c)
-      if (fabs(F[c]) > fabs(F[m])) m = c;
-    const double sg = F[m] < 0.0 ? -1.0 : 1.0;
-    for (int c = 0; c < 9; ++c) e.hom[c] = (float)(sg * F[c]);
   }
 }
 
-// one workgroup per set: best hypothesis (most inliers, first such), stage 2, final mask, record.  Every decision of stage 2 is taken by
-// thread 0, stored in LDS and read by all threads after the barrier that follows; the next store to the same word comes after a later
-// barrier.  No barrier sits under a condition that is not one of those words, a kernel argument or a per-set constant.
-__global__ __launch_bounds__(1024) void verify_finish_kernel(const VerifyDev* __restrict__ vs, uint64_t seed, int iters, int lo_iters, double t2) {
-  __shared__ int s_best[16][2];
-  __shared__ double s_H[9];          // the accepted model
-  __shared__ double s_Hn[9];         // the candidate of the current round
-  __shared__ double s_norm[6];       // cx, cy, cu, cv, scale0, scale1
-  __shared__ double s_acc[16][VF_ACC];
-  __shared__ double s_nprev;         // |I_{l-1}|
-  __shared__ int s_ok, s_stop, s_rounds, s_bc, s_bh, s_cnt;
-  const VerifyDev& e = vs[blockIdx.x];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int K = e.nvalid[0];
-  int bc = -1, bh = 0x7fffffff;
-  for (int h = t; h < iters; h += 1024) {
-    const int c = e.hypcount[h];
-    if (c > bc) { bc = c; bh = h; }
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    const int oc = __shfl_xor(bc, o, 64), oh = __shfl_xor(bh, o, 64);
-    if (oc > bc || (oc == bc && oh < bh)) { bc = oc; bh = oh; }
-  }
-  if (lane == 0) { s_best[wave][0] = bc; s_best[wave][1] = bh; }
-  if (t == 0) { s_ok = 0; s_stop = 0; s_rounds = 0; s_cnt = 0; }
-  __syncthreads();
-  if (e.model == GIMS_VERIFY_MODEL_FUNDAMENTAL) {           // per set: the same for every thread of the workgroup
-    if (t == 0)
-      for (int w = 1; w < 16; ++w)
-        if (s_best[w][0] > bc || (s_best[w][0] == bc && s_best[w][1] < bh)) { bc = s_best[w][0]; bh = s_best[w][1]; }
-    vf_finish_fundamental(e, K, bc, bh, seed, lo_iters, t2, s_acc);
-    return;
-  }
-  if (t == 0) {
-    for (int w = 1; w < 16; ++w)
-      if (s_best[w][0] > bc || (s_best[w][0] == bc && s_best[w][1] < bh)) { bc = s_best[w][0]; bh = s_best[w][1]; }
-    if (bc >= 0 && K >= 4) {
-      int idx[4];
-      ransac_sample(seed, bh, K, idx);
-      double H[9];
-      if (homography4_dense(e.corr, idx, H)) {
-        for (int c = 0; c < 9; ++c) s_H[c] = H[c];
-        s_ok = 1; s_bc = bc; s_bh = bh;
+// ---------------------------------------------------------------------------------------------- finish (homography, fundamental)
+// thread 0 solves the best hypothesis (bc, bh) again into lo.M; true, for every thread and behind a barrier, when the set has a model
+template <class Model>
+__device__ __forceinline__ bool vf_best_model(const VerifyDev& e, int K, int bc, int bh, uint64_t seed, VfLo& lo, int* s_flag) {
+  if (threadIdx.x == 0) {
+    s_flag[0] = 0; s_flag[1] = 0;
+    lo.stop = 0; lo.rounds = 0;
+    if (bc >= 0 && K >= Model::MIN) {
+      double M[9];
+      if (Model::minimal(e.corr, seed, bh, K, &lo.S[0][0], 1, M)) {
+        for (int c = 0; c < 9; ++c) lo.M[c] = M[c];
+        s_flag[0] = 1;
       }
     }
   }
   __syncthreads();
-  if (!s_ok) {
+  return s_flag[0] != 0;
+}
+
+// one workgroup per set: best hypothesis (most inliers, first such), stage 2, final mask, record
+__global__ __launch_bounds__(1024) void verify_finish_kernel(const VerifyDev* __restrict__ vs, uint64_t seed, int iters, int lo_iters, double t2) {
+  __shared__ int s_best[16][2];
+  __shared__ double s_acc[16][VF_ACC];
+  __shared__ VfLo s_lo;
+  __shared__ int s_flag[2];          // 0: the set has a model; 1: the inlier count of the lo_iters == 0 refit
+  const VerifyDev& e = vs[blockIdx.x];
+  const int t = threadIdx.x;
+  const int K = e.nvalid[0];
+  const double cam[8] = {};          // no camera in these models
+  int bc, bh;
+  vf_best<0>(e, iters, s_best, bc, bh);
+  double F[9];
+  if (e.model == GIMS_VERIFY_MODEL_FUNDAMENTAL) {           // per set: the same for every thread of the workgroup
+    if (!vf_best_model<FundamentalModel>(e, K, bc, bh, seed, s_lo, s_flag)) {
+      vf_no_model(e, K, 9);
+      return;
+    }
+    vf_local_opt<FundamentalModel>(e, K, cam, t2, lo_iters, s_lo, s_acc);
+    // no accepted round (lo_iters == 0 has none): the model is the best hypothesis made rank 2
+    if (s_lo.rounds == 0) {
+      if (t == 0) {
+        double G[9];
+        for (int c = 0; c < 9; ++c) G[c] = s_lo.M[c];
+        FundamentalModel::project(G, s_lo.S, s_lo.V);
+        for (int c = 0; c < 9; ++c) s_lo.M[c] = G[c];
+      }
+      __syncthreads();
+    }
+    for (int c = 0; c < 9; ++c) F[c] = s_lo.M[c];
+    vf_final_sweep<FundamentalModel, 1>(e, K, cam, t2, F, bh, bc, s_lo, s_acc, VfNoExtra());
     if (t == 0) {
-      for (int c = 0; c < 8; ++c) e.record[c] = 0.f;
-      e.record[VF_NVALID] = (float)K;
-      e.record[VF_ERR_CORNER] = -1.f;
-      for (int c = 0; c < 9; ++c) e.hom[c] = 0.f;
+      const double sg = vf_sign(F);
+      for (int c = 0; c < 9; ++c) e.hom[c] = (float)(sg * F[c]);
     }
     return;
   }
-  double H[9];
-  for (int c = 0; c < 9; ++c) H[c] = s_H[c];
+  if (!vf_best_model<HomographyModel>(e, K, bc, bh, seed, s_lo, s_flag)) {
+    vf_no_model(e, K, 9);
+    return;
+  }
   if (lo_iters == 0) {
     // the single unguarded refit of gims_eval_pairs: normal equations over the inliers of the best hypothesis, raw coordinates
+    for (int c = 0; c < 9; ++c) F[c] = s_lo.M[c];
     double acc[44];
     for (int c = 0; c < 44; ++c) acc[c] = 0.0;
     int nin = 0;
     for (int p = t; p < K; p += 1024) {
       const float4 c4 = e.corr[p];
       const double x = c4.x, y = c4.y, u = c4.z, v = c4.w;
-      if (reproj2(H, x, y, u, v) <= t2) {
+      if (reproj2(F, x, y, u, v) <= t2) {
         ++nin;
         vf_normal_add(acc, x, y, u, v);
       }
     }
     vf_partials(acc, s_acc);
-    atomicAdd(&s_cnt, nin);
+    atomicAdd(&s_flag[1], nin);
     __syncthreads();
     if (t == 0) {
       double h[8];
-      if (s_cnt >= 4 && vf_normal_solve(s_acc, h)) {
-        for (int c = 0; c < 8; ++c) s_H[c] = h[c];
-        s_H[8] = 1.0;
+      if (s_flag[1] >= 4 && vf_normal_solve(s_acc, h)) {
+        for (int c = 0; c < 8; ++c) s_lo.M[c] = h[c];
+        s_lo.M[8] = 1.0;
       }
     }
     __syncthreads();
   } else {
-    {  // |I_0|
-      double a[1] = {0.0};
-      for (int p = t; p < K; p += 1024) {
-        const float4 c4 = e.corr[p];
-        a[0] += reproj2(H, c4.x, c4.y, c4.z, c4.w) <= t2 ? 1.0 : 0.0;
-      }
-      vf_partials(a, s_acc);
-      __syncthreads();
-      if (t == 0) s_nprev = vf_total(s_acc, 0);
-      __syncthreads();
-    }
-    for (int l = 1; l <= lo_iters; ++l) {
-      // (a) centroids of the inliers of the accepted model
-      {
-        double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-        for (int p = t; p < K; p += 1024) {
-          const float4 c4 = e.corr[p];
-          const double x = c4.x, y = c4.y, u = c4.z, v = c4.w;
-          if (reproj2(H, x, y, u, v) <= t2) { a[0] += 1.0; a[1] += x; a[2] += y; a[3] += u; a[4] += v; }
-        }
-        vf_partials(a, s_acc);
-      }
-      __syncthreads();
-      if (t == 0) {
-        const double n = vf_total(s_acc, 0);
-        s_stop = n < 4.0 ? 1 : 0;
-        if (n >= 4.0)
-          for (int c = 0; c < 4; ++c) s_norm[c] = vf_total(s_acc, 1 + c) / n;
-      }
-      __syncthreads();
-      if (s_stop) break;
-      const double cx = s_norm[0], cy = s_norm[1], cu = s_norm[2], cv = s_norm[3];
-      // (b) mean distances to the centroids
-      {
-        double a[3] = {0.0, 0.0, 0.0};
-        for (int p = t; p < K; p += 1024) {
-          const float4 c4 = e.corr[p];
-          const double x = c4.x, y = c4.y, u = c4.z, v = c4.w;
-          if (reproj2(H, x, y, u, v) <= t2) {
-            a[0] += 1.0;
-            a[1] += sqrt((x - cx) * (x - cx) + (y - cy) * (y - cy));
-            a[2] += sqrt((u - cu) * (u - cu) + (v - cv) * (v - cv));
-          }
-        }
-        vf_partials(a, s_acc);
-      }
-      __syncthreads();
-      if (t == 0) {
-        const double n = vf_total(s_acc, 0), m0 = vf_total(s_acc, 1) / n, m1 = vf_total(s_acc, 2) / n;
-        s_norm[4] = m0 == 0.0 ? 1.0 : sqrt(2.0) / m0;
-        s_norm[5] = m1 == 0.0 ? 1.0 : sqrt(2.0) / m1;
-      }
-      __syncthreads();
-      const double sc0 = s_norm[4], sc1 = s_norm[5];
-      // (c) normal equations over the normalised inliers, solve, back to pixel coordinates
-      {
-        double acc[44];
-        for (int c = 0; c < 44; ++c) acc[c] = 0.0;
-        for (int p = t; p < K; p += 1024) {
-          const float4 c4 = e.corr[p];
-          const double x = c4.x, y = c4.y, u = c4.z, v = c4.w;
-          if (reproj2(H, x, y, u, v) <= t2) vf_normal_add(acc, (x - cx) * sc0, (y - cy) * sc0, (u - cu) * sc1, (v - cv) * sc1);
-        }
-        vf_partials(acc, s_acc);
-      }
-      __syncthreads();
-      if (t == 0) {
-        double h[8];
-        bool ok = vf_normal_solve(s_acc, h);
-        if (ok) {
-          const double Hn[9] = {h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], 1.0};
-          double M[9], Hd[9];
-          for (int r = 0; r < 3; ++r) {                   // M = Hn T0
-            M[3 * r] = Hn[3 * r] * sc0;
-            M[3 * r + 1] = Hn[3 * r + 1] * sc0;
-            M[3 * r + 2] = Hn[3 * r + 2] - sc0 * (Hn[3 * r] * cx + Hn[3 * r + 1] * cy);
-          }
-          for (int c = 0; c < 3; ++c) {                   // H' = T1^-1 M
-            Hd[c] = M[c] / sc1 + cu * M[6 + c];
-            Hd[3 + c] = M[3 + c] / sc1 + cv * M[6 + c];
-            Hd[6 + c] = M[6 + c];
-          }
-          const double w = Hd[8];
-          ok = w != 0.0 && isfinite(w);
-          if (ok) {
-            for (int c = 0; c < 9; ++c) { Hd[c] = Hd[c] / w; ok = ok && isfinite(Hd[c]); }
-            for (int c = 0; c < 9; ++c) s_Hn[c] = Hd[c];
-          }
-        }
-        s_stop = ok ? 0 : 1;
-      }
-      __syncthreads();
-      if (s_stop) break;
-      double Hc[9];
-      for (int c = 0; c < 9; ++c) Hc[c] = s_Hn[c];
-      // (d) the candidate's inliers against the accepted model's
-      {
-        double a[2] = {0.0, 0.0};
-        for (int p = t; p < K; p += 1024) {
-          const float4 c4 = e.corr[p];
-          const double x = c4.x, y = c4.y, u = c4.z, v = c4.w;
-          const bool was = reproj2(H, x, y, u, v) <= t2, is = reproj2(Hc, x, y, u, v) <= t2;
-          a[0] += is ? 1.0 : 0.0;
-          a[1] += is != was ? 1.0 : 0.0;
-        }
-        vf_partials(a, s_acc);
-      }
-      __syncthreads();
-      if (t == 0) {
-        const double n = vf_total(s_acc, 0), changed = vf_total(s_acc, 1);
-        if (n < s_nprev) {
-          s_stop = 1;                                     // fewer inliers: keep H_{l-1}
-        } else {
-          for (int c = 0; c < 9; ++c) s_H[c] = s_Hn[c];
-          s_nprev = n;
-          s_rounds = s_rounds + 1;
-          s_stop = changed == 0.0 ? 2 : 0;                // accepted; the same set again: converged
-        }
-      }
-      __syncthreads();
-      const int stop = s_stop;
-      if (stop != 1)
-        for (int c = 0; c < 9; ++c) H[c] = Hc[c];
-      if (stop) break;
-    }
+    vf_local_opt<HomographyModel>(e, K, cam, t2, lo_iters, s_lo, s_acc);
   }
-  // every path above ends behind a barrier that follows thread 0's last store to s_H
-  for (int c = 0; c < 9; ++c) H[c] = s_H[c];
-  {
-    double a[1] = {0.0};
-    for (int p = t; p < K; p += 1024) {
-      const float4 c4 = e.corr[p];
-      const bool in = reproj2(H, c4.x, c4.y, c4.z, c4.w) <= t2;
-      e.inlier[e.rows[p]] = in ? 1 : 0;
-      a[0] += in ? 1.0 : 0.0;
-    }
-    vf_partials(a, s_acc);
-  }
-  __syncthreads();
+  for (int c = 0; c < 9; ++c) F[c] = s_lo.M[c];
+  vf_final_sweep<HomographyModel, 1>(e, K, cam, t2, F, bh, bc, s_lo, s_acc, VfNoExtra());
   if (t == 0) {
-    e.record[VF_NVALID] = (float)K;
-    e.record[VF_OK] = 1.f;
-    e.record[VF_NINLIERS] = (float)vf_total(s_acc, 0);
-    e.record[VF_BEST_HYP] = (float)s_bh;
-    e.record[VF_BEST_HYP_INLIERS] = (float)s_bc;
-    e.record[VF_LO_ROUNDS] = (float)s_rounds;
-    e.record[VF_ERR_CORNER] = e.has_ref ? corner_error(H, e.href, e.height, e.width) : -1.f;
-    e.record[VF_RESERVED] = 0.f;
-    for (int c = 0; c < 9; ++c) e.hom[c] = (float)H[c];
+    if (e.has_ref) e.record[VF_ERR_CORNER] = corner_error(F, e.href, e.height, e.width);
+    for (int c = 0; c < 9; ++c) e.hom[c] = (float)F[c];
   }
 }
 
 // ---------------------------------------------------------------------------------------------- calibrated relative pose (model 3)
-// The five-point model, its guarded local optimisation and the pose of the result (specification: include/gims_hip.h).
-// Pose sets run in two kernels of their own -- the homography and fundamental kernels above are launched over the other sets of a call
-// and are the code they were --, the gather kernel is shared.
+// The five-point model and the pose of the result (specification: include/gims_hip.h).  Pose sets run in two kernels of
+// their own, built from the pieces above; the gather kernel is shared.
 constexpr int VP_MAXM = 10;        // models of one sample: the real roots of a degree-10 polynomial
 constexpr int VP_BISECT = 80;      // halvings per isolated root
 constexpr int VP_A = 200;          // the 10 x 20 elimination array (the 5 x 9 one before it lives in the same words)
@@ -870,27 +847,6 @@ constexpr int VP_A = 200;          // the 10 x 20 elimination array (the 5 x 9 o
 // the best model of workgroup b of the hypotheses kernel: 9 doubles behind the `iters` counters of a pose set (verify_layout)
 __device__ __forceinline__ double* vp_block_model(const VerifyDev& e, int iters, int b) {
   return (double*)(e.hypcount + ((iters + 1) & ~1)) + 9 * b;
-}
-
-// five distinct indices from the stream of ransac_sample (eval_geom.h): its four, then one more
-__device__ void ransac_sample5(uint64_t seed, int hyp, int k, int (&idx)[5]) {
-  uint64_t state = seed ^ ((uint64_t)hyp * 0xD1342543DE82EF95ull);
-  int n = 0;
-  while (n < 5) {
-    state = splitmix(state);
-    const int c = (int)(state % (uint64_t)k);
-    bool dup = false;
-    for (int q = 0; q < n; ++q) dup = dup || idx[q] == c;
-    if (!dup) idx[n++] = c;
-  }
-}
-
-// camera coordinates of a correspondence: (x - cx) / fx, (y - cy) / fy for cam = fx0, fy0, cx0, cy0, fx1, fy1, cx1, cy1
-__device__ __forceinline__ void vp_norm(const float4 c, const double (&cam)[8], double& x, double& y, double& u, double& v) {
-  x = ((double)c.x - cam[2]) / cam[0];
-  y = ((double)c.y - cam[3]) / cam[1];
-  u = ((double)c.z - cam[6]) / cam[4];
-  v = ((double)c.w - cam[7]) / cam[5];
 }
 
 // variables 0: x, 1: y, 2: z, 3: the constant 1.  A quadratic form has ten coefficients (i <= j), a cubic one twenty; the column of
@@ -1059,34 +1015,9 @@ __device__ int vp_five_point(const float4* __restrict__ corr, const int (&idx)[5
 #pragma unroll
     for (int q = 0; q < 9; ++q) A[(9 * k + q) * ld] = row[q];
   }
-  // the null space: Gauss-Jordan with complete pivoting, five pivots
-  unsigned rused = 0u, cused = 0u, prow = 0u, pcol = 0u;
-#pragma unroll 1
-  for (int s = 0; s < 5; ++s) {
-    int pr = -1, pc = -1;
-    double best = 0.0;
-#pragma unroll 1
-    for (int r = 0; r < 5; ++r) {
-      if ((rused >> r) & 1u) continue;
-      for (int c = 0; c < 9; ++c) {
-        if ((cused >> c) & 1u) continue;
-        const double a = fabs(A[(9 * r + c) * ld]);
-        if (a > best) { best = a; pr = r; pc = c; }
-      }
-    }
-    if (pr < 0 || !isfinite(best)) return 0;
-    rused |= 1u << pr;
-    cused |= 1u << pc;
-    prow |= (unsigned)pr << (4 * s);
-    pcol |= (unsigned)pc << (4 * s);
-    const double piv = A[(9 * pr + pc) * ld];
-#pragma unroll 1
-    for (int r = 0; r < 5; ++r) {
-      if (r == pr) continue;
-      const double m = A[(9 * r + pc) * ld] / piv;
-      for (int c = 0; c < 9; ++c) A[(9 * r + c) * ld] -= m * A[(9 * pr + c) * ld];
-    }
-  }
+  // the null space: five pivots, four free columns
+  unsigned cused, prow, pcol;
+  if (!vf_eliminate<5>(A, ld, cused, prow, pcol)) return 0;
   // L[e][j]: the coefficient of basis vector j (X, Y, Z, W) in entry e of E -- the linear form E_e in (x, y, z, 1)
   double L[9][4];
   bool fin = true;
@@ -1204,14 +1135,14 @@ __device__ int vp_five_point(const float4* __restrict__ corr, const int (&idx)[5
 }
 
 // one workgroup per VF_HB hypotheses of one pose set: VF_HB lanes solve a sample each (elimination arrays in LDS, lane-minor), the
-// models of all samples are packed into LDS and scored VF_HB at a time exactly as the other models' kernel scores its VF_HB.
+// models of all samples are packed into LDS and scored VF_HB at a time by vf_score.
 // hypcount[h] = 16 score + 15 - (index of the best model): the finish kernel compares the scores and finds the model in the low bits
 __global__ __launch_bounds__(256) void verify_pose_hyp_kernel(const VerifyDev* __restrict__ vs, uint64_t seed, int iters, double thresh) {
   __shared__ double s_A[VP_A][VF_HB];
   __shared__ double s_E[VF_HB * VP_MAXM][10];
   __shared__ int s_nm[VF_HB], s_off[VF_HB + 1], s_cnt[4][VF_HB], s_score[VF_HB * VP_MAXM];
   const VerifyDev& e = vs[blockIdx.y];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int t = threadIdx.x;
   const int K = e.nvalid[0];
   const int h0 = blockIdx.x * VF_HB;
   if (K < 5) {                                             // the same for every thread of the workgroup
@@ -1226,7 +1157,7 @@ __global__ __launch_bounds__(256) void verify_pose_hyp_kernel(const VerifyDev* _
   if (t < VF_HB) {
     if (h0 + t < iters) {
       int idx[5];
-      ransac_sample5(seed, h0 + t, K, idx);
+      ransac_sample(seed, h0 + t, K, idx);
       nm = vp_five_point(e.corr, idx, cam, &s_A[0][t], VF_HB, E);
     }
     s_nm[t] = nm;
@@ -1243,32 +1174,7 @@ __global__ __launch_bounds__(256) void verify_pose_hyp_kernel(const VerifyDev* _
   __syncthreads();
   const int M = s_off[VF_HB];                              // the same for every thread of the workgroup, at most VF_HB * VP_MAXM
   for (int g0 = 0; g0 < M; g0 += VF_HB) {
-    int cnt[VF_HB];
-#pragma unroll
-    for (int b = 0; b < VF_HB; ++b) cnt[b] = 0;
-    for (int p0 = 0; p0 < K; p0 += 256) {
-      const int p = p0 + t;
-      const bool have = p < K;
-      double x, y, u, v;
-      vp_norm(e.corr[have ? p : 0], cam, x, y, u, v);
-#pragma unroll
-      for (int b = 0; b < VF_HB; ++b) {
-        if (g0 + b < M) {
-          double F[9];
-#pragma unroll
-          for (int q = 0; q < 9; ++q) F[q] = s_E[g0 + b][q];
-          cnt[b] += have && sampson_in(F, x, y, u, v, t2) ? 1 : 0;
-        }
-      }
-      __syncthreads();                                       // keeps the models in LDS, as in the homography's loop
-    }
-#pragma unroll
-    for (int b = 0; b < VF_HB; ++b) {
-      int s = cnt[b];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-      if (lane == 0) s_cnt[wave][b] = s;
-    }
+    vf_score<PoseModel>(e, K, cam, t2, s_E, g0, M, s_cnt);
     __syncthreads();
     if (t < VF_HB && g0 + t < M) s_score[g0 + t] = s_cnt[0][t] + s_cnt[1][t] + s_cnt[2][t] + s_cnt[3][t];
     __syncthreads();
@@ -1297,36 +1203,6 @@ __global__ __launch_bounds__(256) void verify_pose_hyp_kernel(const VerifyDev* _
   }
 }
 
-// v1, v2, v3 of the specification's svd(E) (v3 at the smallest eigenvalue of E^T E), w1 = E v1, w2 = E v2 and their lengths (one thread;
-// S, V: the LDS of vf_jacobi)
-__device__ void vp_svd(const double (&E)[9], double (*S)[9], double (*V)[9], double (&v)[3][3], double (&w)[2][3], double (&s)[2]) {
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) S[i][j] = E[i] * E[j] + E[3 + i] * E[3 + j] + E[6 + i] * E[6 + j];
-  double unused[3];
-  vf_jacobi(S, V, 3, unused);
-  int m = 0;
-  for (int k = 1; k < 3; ++k)
-    if (S[k][k] < S[m][m]) m = k;
-  const int a = m == 0 ? 1 : 0, b = m == 2 ? 1 : 2;
-  for (int k = 0; k < 3; ++k) { v[0][k] = V[k][a]; v[1][k] = V[k][b]; v[2][k] = V[k][m]; }
-  for (int q = 0; q < 2; ++q) {
-    for (int r = 0; r < 3; ++r) w[q][r] = E[3 * r] * v[q][0] + E[3 * r + 1] * v[q][1] + E[3 * r + 2] * v[q][2];
-    s[q] = sqrt(w[q][0] * w[q][0] + w[q][1] * w[q][1] + w[q][2] * w[q][2]);
-  }
-}
-
-// ess(E) of the specification: singular values (1, 1, 0), unit norm; E itself when that fails
-__device__ void vp_ess(double (&E)[9], double (*S)[9], double (*V)[9]) {
-  double v[3][3], w[2][3], s[2];
-  vp_svd(E, S, V, v, w, s);
-  if (!(s[0] > 0.0 && s[1] > 0.0)) return;
-  double G[9];
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) G[3 * r + c] = w[0][r] * v[0][c] / s[0] + w[1][r] * v[1][c] / s[1];
-  if (vf_unit(G))
-    for (int c = 0; c < 9; ++c) E[c] = G[c];
-}
-
 // the depth numerators of l1 x1 = l0 R x0 + t by least squares: in front of both cameras iff D > 0, n0 > 0 and n1 > 0
 __device__ __forceinline__ void vp_depths(const double* R, const double* tv, double x, double y, double u, double v, double& n0, double& n1, double& D) {
   const double a0 = R[0] * x + R[1] * y + R[2], a1 = R[3] * x + R[4] * y + R[5], a2 = R[6] * x + R[7] * y + R[8];
@@ -1337,190 +1213,46 @@ __device__ __forceinline__ void vp_depths(const double* R, const double* tv, dou
   D = bb * aa - ab * ab;
 }
 
-// one workgroup per pose set: best hypothesis and model, the guarded local optimisation of the fundamental model on camera coordinates
-// with ess() in the place of rank2(), the mask, the four decompositions and the vote of the inliers.  The rule on barriers is the one of
-// verify_finish_kernel: every decision is thread 0's, stored in LDS and read by all threads after the next barrier.
+// one workgroup per pose set: best hypothesis and model, stage 2 on camera coordinates, the mask, the four decompositions and the vote
+// of the inliers
 __global__ __launch_bounds__(1024) void verify_pose_finish_kernel(const VerifyDev* __restrict__ vs, uint64_t seed, int iters, int lo_iters, double thresh) {
   __shared__ int s_best[16][2];
   __shared__ double s_acc[16][VF_ACC];
-  __shared__ double f_F[9], f_Fn[9], f_norm[6], f_S[9][9], f_V[9][9], f_nprev;
+  __shared__ VfLo s_lo;
   __shared__ double p_R[2][9], p_t[3];
-  __shared__ int f_ok, f_stop, f_rounds, p_root, p_score, p_dec;
+  __shared__ int s_ok, p_dec;
   const VerifyDev& e = vs[blockIdx.x];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int t = threadIdx.x;
   const int K = e.nvalid[0];
   double cam[8];
   for (int c = 0; c < 8; ++c) cam[c] = (double)e.href[c];
   const double tn = thresh / ((cam[0] + cam[5]) / 2.0), t2 = tn * tn;
-  int bc = -1, bh = 0x7fffffff;
   // hypcount = 16 score + 15 - model (or -1): the hypotheses compare by score alone (>> 4 keeps -1), the lowest h among equals
-  for (int h = t; h < iters; h += 1024) {
-    const int c = e.hypcount[h];
-    if ((c >> 4) > (bc >> 4)) { bc = c; bh = h; }
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    const int oc = __shfl_xor(bc, o, 64), oh = __shfl_xor(bh, o, 64);
-    if ((oc >> 4) > (bc >> 4) || ((oc >> 4) == (bc >> 4) && oh < bh)) { bc = oc; bh = oh; }
-  }
-  if (lane == 0) { s_best[wave][0] = bc; s_best[wave][1] = bh; }
-  __syncthreads();
+  int bc, bh;
+  vf_best<4>(e, iters, s_best, bc, bh);
   if (t == 0) {
-    f_ok = 0; f_stop = 0; f_rounds = 0; p_dec = 0;
-    for (int w = 1; w < 16; ++w)
-      if ((s_best[w][0] >> 4) > (bc >> 4) || ((s_best[w][0] >> 4) == (bc >> 4) && s_best[w][1] < bh)) { bc = s_best[w][0]; bh = s_best[w][1]; }
+    s_ok = 0; s_lo.stop = 0; s_lo.rounds = 0; p_dec = 0;
     if (bc >= 0 && K >= 5) {                                 // the model its workgroup of the hypotheses kernel left: nothing is solved again
       const double* src = vp_block_model(e, iters, bh / VF_HB);
-      for (int c = 0; c < 9; ++c) f_F[c] = src[c];
-      f_ok = 1; p_root = 15 - (bc & 15); p_score = bc >> 4;
-      s_best[0][1] = bh;
+      for (int c = 0; c < 9; ++c) s_lo.M[c] = src[c];
+      s_ok = 1;
     }
   }
   __syncthreads();
-  if (!f_ok) {
-    if (t == 0) {
-      for (int c = 0; c < 8; ++c) e.record[c] = 0.f;
-      e.record[VF_NVALID] = (float)K;
-      e.record[VF_ERR_CORNER] = -1.f;
-      for (int c = 0; c < 24; ++c) e.hom[c] = 0.f;
-    }
+  if (!s_ok) {
+    vf_no_model(e, K, 24);
     return;
   }
-  double F[9];
-  for (int c = 0; c < 9; ++c) F[c] = f_F[c];
-  if (lo_iters > 0) {
-    {  // |I_0|
-      double a[1] = {0.0};
-      for (int p = t; p < K; p += 1024) {
-        double x, y, u, v;
-        vp_norm(e.corr[p], cam, x, y, u, v);
-        a[0] += sampson_in(F, x, y, u, v, t2) ? 1.0 : 0.0;
-      }
-      vf_partials(a, s_acc);
-      __syncthreads();
-      if (t == 0) f_nprev = vf_total(s_acc, 0);
-      __syncthreads();
-    }
-    for (int l = 1; l <= lo_iters; ++l) {
-      // (a) centroids of the inliers of the accepted model
-      {
-        double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-        for (int p = t; p < K; p += 1024) {
-          double x, y, u, v;
-          vp_norm(e.corr[p], cam, x, y, u, v);
-          if (sampson_in(F, x, y, u, v, t2)) { a[0] += 1.0; a[1] += x; a[2] += y; a[3] += u; a[4] += v; }
-        }
-        vf_partials(a, s_acc);
-      }
-      __syncthreads();
-      if (t == 0) {
-        const double n = vf_total(s_acc, 0);
-        f_stop = n < 8.0 ? 1 : 0;
-        if (n >= 8.0)
-          for (int c = 0; c < 4; ++c) f_norm[c] = vf_total(s_acc, 1 + c) / n;
-      }
-      __syncthreads();
-      if (f_stop) break;
-      const double cx = f_norm[0], cy = f_norm[1], cu = f_norm[2], cv = f_norm[3];
-      // (b) mean distances to the centroids
-      {
-        double a[3] = {0.0, 0.0, 0.0};
-        for (int p = t; p < K; p += 1024) {
-          double x, y, u, v;
-          vp_norm(e.corr[p], cam, x, y, u, v);
-          if (sampson_in(F, x, y, u, v, t2)) {
-            a[0] += 1.0;
-            a[1] += sqrt((x - cx) * (x - cx) + (y - cy) * (y - cy));
-            a[2] += sqrt((u - cu) * (u - cu) + (v - cv) * (v - cv));
-          }
-        }
-        vf_partials(a, s_acc);
-      }
-      __syncthreads();
-      if (t == 0) {
-        const double n = vf_total(s_acc, 0), m0 = vf_total(s_acc, 1) / n, m1 = vf_total(s_acc, 2) / n;
-        f_norm[4] = m0 == 0.0 ? 1.0 : sqrt(2.0) / m0;
-        f_norm[5] = m1 == 0.0 ? 1.0 : sqrt(2.0) / m1;
-      }
-      __syncthreads();
-      const double sc0 = f_norm[4], sc1 = f_norm[5];
-      // (c) the 9 x 9 matrix of sums over the normalised inliers, its smallest eigenvector, back to camera coordinates, ess()
-      {
-        double acc[45];
-        for (int c = 0; c < 45; ++c) acc[c] = 0.0;
-        for (int p = t; p < K; p += 1024) {
-          double x, y, u, v;
-          vp_norm(e.corr[p], cam, x, y, u, v);
-          if (sampson_in(F, x, y, u, v, t2)) vf_epipolar_add(acc, (x - cx) * sc0, (y - cy) * sc0, (u - cu) * sc1, (v - cv) * sc1);
-        }
-        vf_partials(acc, s_acc);
-      }
-      __syncthreads();
-      if (t == 0) {
-        int q = 0;
-        for (int i = 0; i < 9; ++i)
-          for (int j = i; j < 9; ++j) {
-            const double s = vf_total(s_acc, q);
-            f_S[i][j] = s; f_S[j][i] = s;
-            ++q;
-          }
-        double fn[9], Fd[9];
-        vf_jacobi(f_S, f_V, 9, fn);
-        vf_denormalise(fn, cx, cy, sc0, cu, cv, sc1, Fd);
-        bool ok = vf_unit(Fd);
-        if (ok) {
-          vp_ess(Fd, f_S, f_V);
-          for (int c = 0; c < 9; ++c) f_Fn[c] = Fd[c];
-        }
-        f_stop = ok ? 0 : 1;
-      }
-      __syncthreads();
-      if (f_stop) break;
-      double Fc[9];
-      for (int c = 0; c < 9; ++c) Fc[c] = f_Fn[c];
-      // (d) the candidate's inliers against the accepted model's
-      {
-        double a[2] = {0.0, 0.0};
-        for (int p = t; p < K; p += 1024) {
-          double x, y, u, v;
-          vp_norm(e.corr[p], cam, x, y, u, v);
-          const bool was = sampson_in(F, x, y, u, v, t2), is = sampson_in(Fc, x, y, u, v, t2);
-          a[0] += is ? 1.0 : 0.0;
-          a[1] += is != was ? 1.0 : 0.0;
-        }
-        vf_partials(a, s_acc);
-      }
-      __syncthreads();
-      if (t == 0) {
-        const double n = vf_total(s_acc, 0), changed = vf_total(s_acc, 1);
-        if (n < f_nprev) {
-          f_stop = 1;                                     // fewer inliers: keep E_{l-1}
-        } else {
-          for (int c = 0; c < 9; ++c) f_F[c] = f_Fn[c];
-          f_nprev = n;
-          f_rounds = f_rounds + 1;
-          f_stop = changed == 0.0 ? 2 : 0;                // accepted; the same set again: converged
-        }
-      }
-      __syncthreads();
-      const int stop = f_stop;
-      if (stop != 1)
-        for (int c = 0; c < 9; ++c) F[c] = Fc[c];
-      if (stop) break;
-    }
-  }
-  // every path above ends behind a barrier that follows thread 0's last stores to f_F and f_rounds.  Thread 0: no accepted round -> ess()
-  // of the best model; the sign rule; the decompositions
+  vf_local_opt<PoseModel>(e, K, cam, t2, lo_iters, s_lo, s_acc);
+  // thread 0: no accepted round -> ess() of the best model; the sign rule; the decompositions
   if (t == 0) {
     double G[9];
-    for (int c = 0; c < 9; ++c) G[c] = f_F[c];
-    if (f_rounds == 0) vp_ess(G, f_S, f_V);
-    int m = 0;
-    for (int c = 1; c < 9; ++c)
-      if (fabs(G[c]) > fabs(G[m])) m = c;
-    const double sg = G[m] < 0.0 ? -1.0 : 1.0;
-    for (int c = 0; c < 9; ++c) { G[c] = sg * G[c]; f_F[c] = G[c]; }
+    for (int c = 0; c < 9; ++c) G[c] = s_lo.M[c];
+    if (s_lo.rounds == 0) PoseModel::project(G, s_lo.S, s_lo.V);
+    const double sg = vf_sign(G);
+    for (int c = 0; c < 9; ++c) { G[c] = sg * G[c]; s_lo.M[c] = G[c]; }
     double v[3][3], w[2][3], s[2];
-    vp_svd(G, f_S, f_V, v, w, s);
+    vp_svd(G, s_lo.S, s_lo.V, v, w, s);
     if (s[0] > 0.0 && s[1] > 0.0) {
       double u1[3], u2[3], u3[3];
       for (int k = 0; k < 3; ++k) { u1[k] = w[0][k] / s[0]; u2[k] = w[1][k] / s[1]; }
@@ -1542,41 +1274,23 @@ __global__ __launch_bounds__(1024) void verify_pose_finish_kernel(const VerifyDe
     }
   }
   __syncthreads();
-  for (int c = 0; c < 9; ++c) F[c] = f_F[c];
+  double F[9];
+  for (int c = 0; c < 9; ++c) F[c] = s_lo.M[c];
   const int dec = p_dec;
-  {
-    double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    double Ra[9], Rb[9], tv[3];
-    for (int c = 0; c < 9; ++c) { Ra[c] = dec ? p_R[0][c] : 0.0; Rb[c] = dec ? p_R[1][c] : 0.0; }
-    for (int c = 0; c < 3; ++c) tv[c] = dec ? p_t[c] : 0.0;
-    for (int p = t; p < K; p += 1024) {
-      double x, y, u, v;
-      vp_norm(e.corr[p], cam, x, y, u, v);
-      const bool in = sampson_in(F, x, y, u, v, t2);
-      e.inlier[e.rows[p]] = in ? 1 : 0;
-      if (in) {
-        a[0] += 1.0;
-        double n0, n1, D;
-        vp_depths(Ra, tv, x, y, u, v, n0, n1, D);
-        a[1] += D > 0.0 && n0 > 0.0 && n1 > 0.0 ? 1.0 : 0.0;
-        a[2] += D > 0.0 && n0 < 0.0 && n1 < 0.0 ? 1.0 : 0.0;
-        vp_depths(Rb, tv, x, y, u, v, n0, n1, D);
-        a[3] += D > 0.0 && n0 > 0.0 && n1 > 0.0 ? 1.0 : 0.0;
-        a[4] += D > 0.0 && n0 < 0.0 && n1 < 0.0 ? 1.0 : 0.0;
-      }
-    }
-    vf_partials(a, s_acc);
-  }
-  __syncthreads();
+  double Ra[9], Rb[9], tv[3];
+  for (int c = 0; c < 9; ++c) { Ra[c] = dec ? p_R[0][c] : 0.0; Rb[c] = dec ? p_R[1][c] : 0.0; }
+  for (int c = 0; c < 3; ++c) tv[c] = dec ? p_t[c] : 0.0;
+  // the votes of an inlier: in front of both cameras under (Ra, t), (Ra, -t), (Rb, t), (Rb, -t)
+  vf_final_sweep<PoseModel, 5>(e, K, cam, t2, F, bh, bc >> 4, s_lo, s_acc, [&](double (&a)[5], double x, double y, double u, double v) {
+    double n0, n1, D;
+    vp_depths(Ra, tv, x, y, u, v, n0, n1, D);
+    a[1] += D > 0.0 && n0 > 0.0 && n1 > 0.0 ? 1.0 : 0.0;
+    a[2] += D > 0.0 && n0 < 0.0 && n1 < 0.0 ? 1.0 : 0.0;
+    vp_depths(Rb, tv, x, y, u, v, n0, n1, D);
+    a[3] += D > 0.0 && n0 > 0.0 && n1 > 0.0 ? 1.0 : 0.0;
+    a[4] += D > 0.0 && n0 < 0.0 && n1 < 0.0 ? 1.0 : 0.0;
+  });
   if (t == 0) {
-    e.record[VF_NVALID] = (float)K;
-    e.record[VF_OK] = 1.f;
-    e.record[VF_NINLIERS] = (float)vf_total(s_acc, 0);
-    e.record[VF_BEST_HYP] = (float)s_best[0][1];
-    e.record[VF_BEST_HYP_INLIERS] = (float)p_score;
-    e.record[VF_LO_ROUNDS] = (float)f_rounds;
-    e.record[VF_ERR_CORNER] = -1.f;
-    e.record[VF_RESERVED] = 0.f;
     for (int c = 0; c < 9; ++c) e.hom[c] = (float)F[c];
     int w = 0;
     double votes = vf_total(s_acc, 1);
@@ -1588,7 +1302,7 @@ __global__ __launch_bounds__(1024) void verify_pose_finish_kernel(const VerifyDe
     for (int c = 0; c < 9; ++c) e.hom[9 + c] = dec ? (float)p_R[w >> 1][c] : 0.f;
     for (int c = 0; c < 3; ++c) e.hom[18 + c] = dec ? (float)(st * p_t[c]) : 0.f;
     e.hom[21] = dec ? (float)votes : 0.f;
-    e.hom[22] = (float)p_root;
+    e.hom[22] = (float)(15 - (bc & 15));                    // the index of the best model among those of its sample
     e.hom[23] = 0.f;
   }
 }

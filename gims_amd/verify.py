@@ -117,7 +117,9 @@ def _is_camera_pair(c) -> bool:
         return False
 
 
-def _find(name, model, least, points0, points1, thresh, iters, lo_iters, seed):
+def _one_set(name, model, least, width, points0, points1, thresh, iters, lo_iters, seed, **item):
+    """One set of row-by-row correspondences through ``gims_verify_pairs``: ``(model floats [width], mask [K] uint8)`` as device tensors,
+    or None below ``least`` points or without a model.  ``item``: further fields of the set (``intrinsics``).  One host read."""
     dev = points0.device if isinstance(points0, torch.Tensor) and points0.is_cuda else torch.device("cuda", torch.cuda.current_device())
     p0 = torch.as_tensor(points0).to(device=dev, dtype=torch.float32).reshape(-1, 2).contiguous()
     p1 = torch.as_tensor(points1).to(device=dev, dtype=torch.float32).reshape(-1, 2).contiguous()
@@ -125,15 +127,20 @@ def _find(name, model, least, points0, points1, thresh, iters, lo_iters, seed):
         raise ValueError(f"{name}: {tuple(p0.shape)} and {tuple(p1.shape)} points do not correspond row by row")
     k = int(p0.shape[0])
     if k < least:
-        return None, None
+        return None
     record = torch.zeros(8, dtype=torch.float32, device=dev)
-    hom = torch.zeros(9, dtype=torch.float32, device=dev)
+    out = torch.zeros(width, dtype=torch.float32, device=dev)
     mask = torch.empty(k, dtype=torch.uint8, device=dev)
-    work = hip.verify_pairs([dict(kpts0=p0, kpts1=p1, matches0=None, inlier=mask, record=record, homography=hom, model=model)], thresh, iters,
-                            lo_iters, seed)
+    work = hip.verify_pairs([dict(kpts0=p0, kpts1=p1, matches0=None, inlier=mask, record=record, homography=out, model=model, **item)],
+                            thresh, iters, lo_iters, seed)
     ok = bool(record[RECORD_FIELDS.index("ok")].item())              # the host read: the stream has passed the call, `work` may go
     del work
-    return (hom.view(3, 3), mask.view(k, 1)) if ok else (None, None)
+    return (out, mask) if ok else None
+
+
+def _find(name, model, least, points0, points1, thresh, iters, lo_iters, seed):
+    r = _one_set(name, model, least, 9, points0, points1, thresh, iters, lo_iters, seed)
+    return (r[0].view(3, 3), r[1].view(-1, 1)) if r is not None else (None, None)
 
 
 def find_homography(points0, points1, thresh: float = 3.0, iters: int = 3000, lo_iters: int = 8, seed: int = 0):
@@ -164,23 +171,9 @@ def estimate_pose(kpts0, kpts1, K0, K1, thresh: float = 1.0, iters: int = 3000, 
     (include/gims_hip.h), not OpenCV's.
 
     This call SYNCHRONISES with the device (it reads whether a model was found); the batched ``verify_pairs(model='pose')`` does not."""
-    dev = kpts0.device if isinstance(kpts0, torch.Tensor) and kpts0.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    p0 = torch.as_tensor(kpts0).to(device=dev, dtype=torch.float32).reshape(-1, 2).contiguous()
-    p1 = torch.as_tensor(kpts1).to(device=dev, dtype=torch.float32).reshape(-1, 2).contiguous()
-    if p0.shape != p1.shape:
-        raise ValueError(f"estimate_pose: {tuple(p0.shape)} and {tuple(p1.shape)} points do not correspond row by row")
-    k = int(p0.shape[0])
-    if k < 5:
-        return None
-    record = torch.zeros(8, dtype=torch.float32, device=dev)
-    out = torch.zeros(hip.VERIFY_POSE_FLOATS, dtype=torch.float32, device=dev)
-    mask = torch.empty(k, dtype=torch.uint8, device=dev)
     cams = tuple(np.asarray(c.cpu() if isinstance(c, torch.Tensor) else c, dtype=np.float64) for c in (K0, K1))
-    work = hip.verify_pairs([dict(kpts0=p0, kpts1=p1, matches0=None, inlier=mask, record=record, homography=out, model="pose", intrinsics=cams)],
-                            thresh, iters, lo_iters, seed)
-    ok = bool(record[RECORD_FIELDS.index("ok")].item())              # the host read: the stream has passed the call, `work` may go
-    del work
-    return (out[9:18].view(3, 3), out[18:21], mask.bool()) if ok else None
+    r = _one_set("estimate_pose", "pose", 5, hip.VERIFY_POSE_FLOATS, kpts0, kpts1, thresh, iters, lo_iters, seed, intrinsics=cams)
+    return (r[0][9:18].view(3, 3), r[0][18:21], r[1].bool()) if r is not None else None
 
 
 def _f64(a, dev=None) -> torch.Tensor:
