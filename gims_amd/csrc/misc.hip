@@ -468,6 +468,8 @@ extern "C" int gims_layernorm_act(const float* x, int64_t ldx, int64_t rows, int
   using namespace gims;
   GIMS_CHECK_ARG(x && a2 && b2 && (out || out_hi) && rows >= 0 && c >= 2 && c <= 512, "gims_layernorm_act: bad arguments (2 <= c <= 512)");
   GIMS_CHECK_ARG((out_hi == nullptr) == (out_lo == nullptr), "gims_layernorm_act: out_hi and out_lo come together");
+  GIMS_CHECK_ARG(ldx >= c && (!out || ldo >= c) && (!out_hi || ld_split >= 2 * (int64_t)((c + 31) / 32 * 32)),
+                 "gims_layernorm_act: pitch below the row width (ldx, ldo >= c; SPL32 pitch >= 2 * c rounded up to 32 channels)");
   if (rows == 0) return GIMS_OK;
   hipLaunchKernelGGL(layernorm_act_kernel, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, x, ldx, rows, c, a2, b2, eps,
                      act, out, ldo, out_hi, out_lo, ld_split);
@@ -539,6 +541,7 @@ extern "C" int gims_gather_rows(const float* src, int64_t lds, const int32_t* id
                                 int64_t ldd, void* stream) {
   using namespace gims;
   GIMS_CHECK_ARG(src && idx && dst && n >= 0 && c > 0, "gims_gather_rows: bad arguments");
+  GIMS_CHECK_ARG(lds >= c && ldd >= c, "gims_gather_rows: pitch below the row width");
   if (n == 0) return GIMS_OK;
   hipLaunchKernelGGL(gather_rows_kernel, dim3(cdiv(n, 4)), dim3(256), 0, (hipStream_t)stream, src, lds, idx, n, c, dst, ldd);
   GIMS_LAUNCH_CHECK();

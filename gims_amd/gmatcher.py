@@ -1325,7 +1325,7 @@ class GMatcher(nn.Module):
             stats["ingests"] += 1
             dev = base[0]["kp"].device
             n_rows = base[0]["kp"].shape[0] + base[1]["kp"].shape[0]
-            per = max(1, int(rows if rows is not None else cfg['sweep_rows']) // n_rows)
+            per = max(1, int(rows if rows is not None else cfg['sweep_rows']) // max(n_rows, 1))     # a pair without keypoints: the build's check speaks
             if min(g["kp"].shape[0] for g in base) >= 2 and not all(s[3] for s in settings):
                 # the workspace of one entry's two images (the slots are never written by this call: it only sizes)
                 z = torch.empty(8, dtype=torch.int32, device=dev)

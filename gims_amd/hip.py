@@ -555,8 +555,11 @@ def _upload_structs(arr, device):
 
 
 def ingest_images(items, d, desc_out, kpts_out, score_out):
-    """items: list of IngestImage (host).  One launch for the batch."""
+    """items: list of IngestImage (host).  One launch for the batch; none, and None back, when every image is empty (the entry point
+    refuses max_n = 0, and the caller's own check of the keypoint counts is what has to speak then)."""
     lib = load()
+    if not any(i.n > 0 for i in items):
+        return None
     arr = (IngestImage * len(items))(*items)
     dev_arr = _upload_structs(arr, desc_out.device)
     _check(lib.gims_ingest_images(_p(dev_arr), len(items), max(i.n for i in items), d, _p(desc_out), desc_out.stride(0),

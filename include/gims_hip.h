@@ -362,7 +362,7 @@ int gims_kenc_first_linear(const float* kpts, const float* norm3, const int32_t*
  * replaces: class LayerNorm (gmatcher.py:74-85) as MLP() inserts it between Conv1d and ReLU (gmatcher.py:19-23):
  *   y[r, :] = a2 * (x[r, :] - mean_r) / (std_r + eps) + b2   over the c channels of point r, std UNBIASED (c - 1),
  *   eps added to the std.  out (f32, may be NULL or == x) and/or out_hi/out_lo (SPL32 split planes, see gims_linear).
- * 2 <= c <= 512.
+ * 2 <= c <= 512.  GIMS_EINVAL before any HIP call: ldx < c, ldo < c with out given, ld_split < 2 * (c rounded up to 32) with the planes given.
  */
 int gims_layernorm_act(const float* x, int64_t ldx, int64_t rows, int32_t c, const float* a2, const float* b2, float eps,
                        int32_t act, float* out /* may be NULL */, int64_t ldo, uint16_t* out_hi /* may be NULL */,
@@ -388,7 +388,7 @@ int gims_sage_mean_split(const float* h, int64_t ldh, const int32_t* indptr, con
  * Fixed summation order: the result is deterministic. */
 int gims_pair_stats(const int64_t* matches0, const float* scores0, const int32_t* table, int32_t n_pairs, float* out, void* stream);
 
-/* Gather rows: dst[i, :] = src[idx[i], :]  (kept-keypoint compaction, gmatcher.py:244-249). */
+/* Gather rows: dst[i, :] = src[idx[i], :]  (kept-keypoint compaction, gmatcher.py:244-249).  lds, ldd >= c (GIMS_EINVAL otherwise). */
 int gims_gather_rows(const float* src, int64_t lds, const int32_t* idx, int32_t n, int32_t c,
                      float* dst, int64_t ldd, void* stream);
 
