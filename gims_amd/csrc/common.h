@@ -166,6 +166,9 @@ int device_cus();        // compute units of the current device (>= 8)
 int linear_x6_batch_launch(const gims_linear_args* dev_args, int count, int max_m, int max_n, hipStream_t s);
 int split_spl3_launch(const float* src, int64_t lds, uint16_t* dst, int64_t ldd, int64_t rows, int k, hipStream_t s);
 
+// linear_mlp.hip: GIMS_OP_MLP of gims_run_ops, one layer's MLP in one launch
+int mlp_fused_launch(const gims_linear_args& a, hipStream_t s);
+
 // sift.hip: GIMS_AUX_SIFT_DESCRIBE, the one auxiliary function of gims_run_ops without an entry point of its own
 int sift_describe_aux(const gims_aux_args& x, hipStream_t st);
 // nms.hip: GIMS_AUX_DIOU_NMS, likewise reached through gims_run_ops only

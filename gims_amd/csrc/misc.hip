@@ -328,6 +328,8 @@ extern "C" int gims_run_ops(const gims_op* ops, int32_t n_ops, void* stream) {
       rc = gims_linear(&ops[i].u.lin, stream);
     } else if (ops[i].kind == GIMS_OP_ATTENTION) {
       rc = gims_attention(&ops[i].u.att, stream);
+    } else if (ops[i].kind == GIMS_OP_MLP) {
+      rc = mlp_fused_launch(ops[i].u.lin, (hipStream_t)stream);
     } else if (ops[i].kind == GIMS_OP_AUX) {
       const gims_aux_args& x = ops[i].u.aux;
       if (x.fn == GIMS_AUX_SPLIT_SPL32)

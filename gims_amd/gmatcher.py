@@ -312,12 +312,20 @@ class GMatcher(nn.Module):
             # attention kernel then exponentiates the MFMA result as it is (hip.attention(..., q_prescaled=True))
             wq = (wq.double() * hip.ATTN_Q_SCALE).float()
             bq = (bq.double() * hip.ATTN_Q_SCALE).float()
+            w1, b1 = sd[p + "mlp.3.weight"][:, :, 0], sd[p + "mlp.3.bias"]
+            e0f = lin(w0f, b0f, True) if w0f is not None else None
+            mlp_op = None
+            if e0f is not None and x3 and not ln and D == 256:
+                # the one-launch MLP (hip.op_mlp) reads [W0 ; W1 with its K axis in register order] and b0 | b1 as ONE buffer each; the
+                # two-launch path keeps its own W1 and takes W0 / b0 as views of these (no second copy of the larger matrix)
+                mlp_op = {"w": hip.split_spl32(dev(torch.cat([w0f, hip.mlp_w1_permute(w1)], 0))), "b": dev(torch.cat([b0f, b1]))}
+                e0f.update(w=mlp_op["w"][:2 * D], b=mlp_op["b"][:2 * D])
             P["layers"].append({
-                "mlp0_fused": lin(w0f, b0f, True) if w0f is not None else None,
+                "mlp0_fused": e0f, "mlp_op": mlp_op,
                 "qkv": lin(torch.cat([wq, wk, wv], 0), torch.cat([bq, bk, bv], 0), True),
                 "merge": lin(wm, sd[p + "attn.merge.bias"], True),
                 "mlp0": lin(w0, b0, True),
-                "mlp1": lin(sd[p + "mlp.3.weight"][:, :, 0], sd[p + "mlp.3.bias"], True),
+                "mlp1": lin(w1, b1, True),
                 "ln": lnp(p + "mlp.1"),
                 "cross": self.config['transformer_layers'][l] == 'cross',
             })
@@ -338,6 +346,23 @@ class GMatcher(nn.Module):
 
 
     _use_graph = os.environ.get("GIMS_OPS_GRAPH", "0") == "1"      # opt-in: measured gain <= 3 % (tools/graph_probe.py)
+
+    # The MLP of a layer as ONE launch (hip.op_mlp: the hidden activation stays in registers) from this many keypoint rows on --
+    # the first measured size at which it beats the two launches (a lone 128-row workgroup is a serial chain of 48 stages, where the two
+    # launches switch to smaller tiles).  Its second product sums in another order than the MLP1 launch, so WHICH of the two a call takes
+    # shows in the last bits -- like the attention kernel families that 'auto', 'bf16' and 'f16' select by launch shape.
+    # attention_precision='bf16x3' is the configuration whose results do not depend on what shares a batch with a pair
+    # (tests/test_sweep_gpu.py::test_sub_batch_size_does_not_change_the_results): it keeps the two launches at every size.
+    # GIMS_MLP_FUSED=0 | 1 (never | wherever the kernel serves the shape, at every size) overrides for A/B runs; read per call.
+    mlp_fused_rows = 24576
+
+    def _mlp_fused(self, P, n_tot):
+        if not P["layers"] or P["layers"][0]["mlp_op"] is None:      # linear_precision='f32', fuse_merge=False, LayerNorm, another width
+            return False
+        env = os.environ.get("GIMS_MLP_FUSED")
+        if env in ("0", "1"):
+            return env == "1"
+        return self.config['attention_precision'] != 'bf16x3' and n_tot >= self.mlp_fused_rows
 
     @staticmethod
     def _lin(e, a0, **kw):
@@ -931,9 +956,11 @@ class GMatcher(nn.Module):
         # bf16x3: all GEMM operands travel as split-bf16 SPL32 buffers written by the producing kernel's epilogue; only the residual stream `desc`
         # also exists in f32 (dpl: its SPL32 copy) -- and, with LayerNorm, the hidden activations in front of the norm kernel.  f32: all in f32.
         # msg: attention output, mrg: merged message (fuse_merge=False), hid: MLP hidden layer as the second conv reads it
+        one_mlp = self._mlp_fused(P, n_tot)        # (then no hidden-layer buffer: it is part of the key through hid = None)
+        self.linear_launches_per_layer = 2 if one_mlp else (3 if cfg['fuse_merge'] else 4)
         b = dict(desc=desc, src=A("dpl", 2 * D, bf) if x3 else desc, stat=stat, self_pr=self_pr, cross_pr=cross_pr,
                  msg=A("mpl", 2 * D, bf) if x3 else A("msg", D, f32), mrg=A("gpl", 2 * D, bf) if x3 else A("mrg", D, f32),
-                 hid=A("hpl", 4 * D, bf) if x3 else A("hid", 2 * D, f32), hid_ln=A("hid_ln", 2 * D, f32) if (x3 and P["ln"]) else None,
+                 hid=None if one_mlp else (A("hpl", 4 * D, bf) if x3 else A("hid", 2 * D, f32)), hid_ln=A("hid_ln", 2 * D, f32) if (x3 and P["ln"]) else None,
                  # bf16 / half attention: Q|K|V as one 16-bit buffer [rows][768] (a layer writes and reads it in its own format); x3 attention (and the
                  # guarded redo): the same three matrices as SPL32 hi/lo planes
                  qkv_b=A("qkv", 3 * D, bf) if not all(a == 2 for a in amode) else None,
@@ -954,7 +981,8 @@ class GMatcher(nn.Module):
     def _layer_ops(self, P, b, n_tot, max_nq, amode, calibrated, guarded):
         """The launches of the attentional layers on the buffers b (see _layers) as [(label, gims_op)]: per layer the Q/K/V projection ('qkv'),
         the attention ('attn_self' | 'attn_cross'; both with a suffix that names the tier), for a guarded layer the two redo launches ('guard'),
-        and the MLP with the residual update ('mlp': two launches, three with fuse_merge=False, one more with LayerNorm)."""
+        and the MLP with the residual update ('mlp': two launches, three with fuse_merge=False, one more with LayerNorm; ONE, hip.op_mlp,
+        when the table has no hidden-layer buffer: b["hid"] is None, see _mlp_fused)."""
         cfg, D, H = self.config, self.config['descriptor_dim'], self._heads
         x3, ln, stat = P["x3"], P["ln"], b["stat"]
         desc, src, msg, mrg, hid, qkv_b, qkv_s = b["desc"], b["src"], b["msg"], b["mrg"], b["hid"], b["qkv_b"], b["qkv_s"]
@@ -984,6 +1012,9 @@ class GMatcher(nn.Module):
                 lst.append(("guard", self._lin_op(L["qkv"], src, out_split=qkv_s, guard=gd)))
                 lst.append(("guard", hip.op_attention(qkv_s, pr, max_nq, H, None, 0, D, 2 * D, out_split=msg, q_prescaled=True, x3=True, guard=gd)))
             m, e0 = msg, L["mlp0_fused"]
+            if hid is None:                    # desc += MLP([desc | message]) in one launch; dpl follows
+                lst.append(("mlp", hip.op_mlp(src, msg, L["mlp_op"]["w"], L["mlp_op"]["b"], desc, src, residual=desc)))
+                continue
             if e0 is None:                     # fuse_merge=False: the reference's operation order
                 lst.append(("mlp", self._lin_op(L["merge"], msg, **to(mrg))))
                 m, e0 = mrg, L["mlp0"]

@@ -270,6 +270,30 @@ def op_linear(args: LinearArgs) -> Op:
     return o
 
 
+OP_MLP = _K["GIMS_OP_MLP"]
+# where channel c of a 32-channel block of W1's K axis sits in the copy GIMS_OP_MLP reads: position 16 s + 8 h + j holds channel
+# (r & 3) + 8 (r >> 2) + 4 h, r = 8 s + j (include/gims_hip.h)
+MLP_W1_ORDER = tuple((r & 3) + 8 * (r >> 2) + 4 * h for s in range(2) for h in range(2) for r in range(8 * s, 8 * s + 8))
+
+
+def mlp_w1_permute(w1: torch.Tensor) -> torch.Tensor:
+    """W1 [n, hidden] with its K axis reordered inside every 32-channel block as GIMS_OP_MLP reads it (MLP_W1_ORDER)."""
+    n, k = w1.shape
+    assert k % 32 == 0
+    return w1.reshape(n, k // 32, 32)[:, :, list(MLP_W1_ORDER)].reshape(n, k).contiguous()
+
+
+def op_mlp(a0, a1, w, bias, out, out_split, residual=None) -> Op:
+    """One layer's MLP in one launch (include/gims_hip.h GIMS_OP_MLP): out = residual + W1 relu(W0 [a0 | a1] + b0) + b1 on SPL32 operands;
+    w = SPL32 of [W0 ; mlp_w1_permute(W1)] (3n rows), bias = b0 | b1."""
+    n = a0.shape[1] // 2
+    assert w.shape[0] == 3 * n and bias.numel() == 3 * n and bias.dtype == torch.float32 and bias.is_contiguous()
+    o = Op()
+    o.kind = OP_MLP
+    o.u.lin = linear_args(a0, w, bias=bias, a1=a1, residual=residual, out=out, act=ACT_RELU, precision=PREC_BF16X3, n=n, spl=True, out_split=out_split)
+    return o
+
+
 def _attn_flags(q_prescaled, x3, f16, no_range=False):
     assert not (x3 and f16)
     return (1 if q_prescaled else 0) | (ATTN_X3 if x3 else 0) | (ATTN_F16 if f16 else 0) | (ATTN_NO_RANGE if no_range else 0)

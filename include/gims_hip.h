@@ -216,6 +216,23 @@ int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t
  */
 #define GIMS_OP_LINEAR 0
 #define GIMS_OP_ATTENTION 1
+/* GIMS_OP_MLP: one layer's MLP (gmatcher.py:141-142) in ONE launch, reached through this table only (the exported surface of this ABI
+ * version is closed, see GIMS_AUX_SIFT_DESCRIBE): the payload is u.lin and describes
+ *   out = residual + W1 relu(W0 [a0 | a1] + b0) + b1
+ * on pre-split SPL32 operands, the hidden activation staying in registers (kernel: mlp_fused_x3_kernel, gims_amd/csrc/linear_mlp.hip).
+ *   a0, a1 (lda0, lda1; a0_lo = a0 + 32, a1_lo = a1 + 32)   the two K segments, k0 = n channels each, k = 2n
+ *   w (w_lo = w + 32, ldw >= 2k)   ONE SPL32 buffer of 3n rows: rows 0 .. 2n-1 are W0 [2n][k]; rows 2n .. 3n-1 are W1 [n][2n] with its K axis
+ *                                  permuted inside every 32-channel block: position 16 s + 8 h + j (s, h in 0 .. 1, j in 0 .. 7) holds
+ *                                  channel (r & 3) + 8 (r >> 2) + 4 h of the block, r = 8 s + j -- the order in which a lane of the first
+ *                                  product holds its results
+ *   bias   [3n] = b0 | b1          residual (may be NULL; may alias out_f32), out_f32 (ldc), out_hi / out_lo = out_hi + 32 (ld_split): as gims_linear.
+ *                                  out_hi may alias a0 (the layer's residual stream and its SPL32 copy): a workgroup writes its rows after it has read them
+ *   act = GIMS_ACT_RELU (the hidden layer's), precision = GIMS_PREC_BF16X3, scale = 1, flags = 0, out_bf16 = NULL, no guard, no range_stat.
+ * The hidden values are bit for bit those of the two gims_linear launches it replaces (same K order, same split arithmetic); the second
+ * product sums the two halves of its K range separately, so results differ from theirs by f32 summation order only.
+ * GIMS_EINVAL before any HIP call for every shape it does not serve: anything but n = 256, k = 512, k0 = 256, and the alignment of
+ * gims_linear's pre-split operands. */
+#define GIMS_OP_MLP 3
 /* GIMS_OP_AUX: the small kernels of the encoder stage in front of the layers (GraphSAGE, gmatcher.py:145-162, 268-269; keypoint encoder,
  * gmatcher.py:87-97, 270-271), so that that stage replays from a table like the layers do -- between the one host synchronisation of a batch and
  * the layers the device waits for the host, and a dozen calls across the ABI were most of that wait.  fn selects the entry point, p / i are its
