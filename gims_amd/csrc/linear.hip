@@ -485,9 +485,10 @@ __device__ __forceinline__ void linear_x3p_tile(const gims_linear_args& p, const
       for (int q = 0; q < CH; ++q) {
         const int row = rbase + (it0 + q) * RPI;
         const bool ok = p.residual && cok && row < p.m;
+        const int64_t rrow = (ok && p.residual_rows) ? p.residual_rows[row] : row;      // (residual_rows: wave-uniform branch, one more load in front)
 #pragma unroll
         for (int h = 0; h < 2; ++h)
-          res[q][h] = (ok && (h == 0 || full)) ? *(const float4*)(p.residual + (int64_t)row * p.ldc + col + 4 * h) : make_float4(0.f, 0.f, 0.f, 0.f);
+          res[q][h] = (ok && (h == 0 || full)) ? *(const float4*)(p.residual + rrow * p.ldc + col + 4 * h) : make_float4(0.f, 0.f, 0.f, 0.f);
       }
 #pragma unroll
       for (int q = 0; q < CH; ++q) {
@@ -634,7 +635,7 @@ static int linear_validate(const gims_linear_args* a) {
                    "gims_linear(bf16x6): SPL3 operands have row pitch >= 3*K, a multiple of 8 elements");
     GIMS_CHECK_ARG((((uintptr_t)a->a0 | (uintptr_t)a->w | (uintptr_t)a->out_f32) & 15) == 0 && a->out_f32 && (a->ldc % 4) == 0,
                    "gims_linear(bf16x6): operands / output must be 16-byte aligned, f32 output with ldc %% 4 == 0");
-    GIMS_CHECK_ARG(!a->bias && !a->residual && !a->out_bf16 && !a->out_hi && a->act == GIMS_ACT_NONE,
+    GIMS_CHECK_ARG(!a->bias && !a->residual && !a->residual_rows && !a->out_bf16 && !a->out_hi && a->act == GIMS_ACT_NONE,
                    "gims_linear(bf16x6): plain scaled product only");
     return GIMS_OK;
   }
@@ -651,8 +652,10 @@ static int linear_validate(const gims_linear_args* a) {
     GIMS_CHECK_ARG((((uintptr_t)a->out_f32 | (uintptr_t)a->out_hi | (uintptr_t)a->residual | (uintptr_t)a->bias) & 15) == 0 &&
                    ((uintptr_t)a->out_bf16 & 7) == 0 && (((uintptr_t)a->out_bf16 & 15) == 0 || (a->ldc_bf16 & 7) != 0),
                    "gims_linear(pre-split): bias, residual and outputs must be 16-byte aligned");
+    GIMS_CHECK_ARG(!a->residual_rows || (a->residual && ((uintptr_t)a->residual_rows & 3) == 0), "gims_linear(pre-split): residual_rows goes with residual");
     return GIMS_OK;
   }
+  GIMS_CHECK_ARG(!a->residual_rows, "gims_linear: residual_rows needs pre-split operands");
   GIMS_CHECK_ARG(!a->residual || a->out_f32, "gims_linear: residual needs an f32 output (shared ldc)");
   GIMS_CHECK_ARG((a->lda0 % 4) == 0 && (a->lda1 % 4) == 0, "gims_linear: lda must be a multiple of 4");
   if (a->precision == GIMS_PREC_F32) {

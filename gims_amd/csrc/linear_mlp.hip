@@ -300,8 +300,8 @@ int mlp_fused_launch(const gims_linear_args& a, hipStream_t s) {
                  a.m, a.n, a.k, a.k0);
   GIMS_CHECK_ARG(a.a0 && a.a1 && a.w && a.bias && a.out_f32 && a.out_hi, "mlp_fused: null operand or output");
   GIMS_CHECK_ARG(a.a0_lo && a.a1_lo && a.w_lo && a.precision == GIMS_PREC_BF16X3, "mlp_fused: pre-split SPL32 operands, GIMS_PREC_BF16X3");
-  GIMS_CHECK_ARG(a.act == GIMS_ACT_RELU && a.scale == 1.f && a.flags == 0 && !a.out_bf16 && !a.guard.stat && !a.range_stat && a.probe_delay == 0,
-                 "mlp_fused: act = GIMS_ACT_RELU, scale = 1, no flags, no out_bf16, no guard, no range_stat");
+  GIMS_CHECK_ARG(a.act == GIMS_ACT_RELU && a.scale == 1.f && a.flags == 0 && !a.out_bf16 && !a.guard.stat && !a.range_stat && a.probe_delay == 0 &&
+                 !a.residual_rows, "mlp_fused: act = GIMS_ACT_RELU, scale = 1, no flags, no out_bf16, no guard, no range_stat, no residual_rows");
   GIMS_CHECK_ARG((a.lda0 % 64) == 0 && (a.lda1 % 64) == 0 && (a.ldw % 64) == 0 && a.lda0 >= 2 * MF_D && a.lda1 >= 2 * MF_D && a.ldw >= 2 * MF_K,
                  "mlp_fused: SPL32 operands have row pitch >= 2*K, a multiple of 64 elements");
   GIMS_CHECK_ARG(a.lda0 < (1 << 22) && a.lda1 < (1 << 22) && a.ldw < (1 << 22), "mlp_fused: row pitch too large (32-bit tile-relative offsets)");

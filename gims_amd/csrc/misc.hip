@@ -104,12 +104,23 @@ template <bool RELU>
 __global__ __launch_bounds__(256) void kenc_first_kernel(const float* __restrict__ kpts, const float* __restrict__ norm3,
                                                          const int32_t* __restrict__ seg, const float* __restrict__ w1,
                                                          const float* __restrict__ b1, int c1, float* __restrict__ out,
-                                                         int64_t n) {
+                                                         int64_t n, int n_img) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t row = idx / c1;
   const int ch = (int)(idx - row * c1);
   if (row >= n) return;
-  const float* nm = norm3 + 3 * seg[row];
+  int img;
+  if (n_img > 0) {      // rows of whole images back to back: seg holds the first row of every image (ascending, seg[0] = 0) instead of one entry per row
+    int lo = 0, hi = n_img - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if ((int64_t)seg[mid] <= row) lo = mid; else hi = mid - 1;
+    }
+    img = lo;
+  } else {
+    img = seg[row];
+  }
+  const float* nm = norm3 + 3 * img;
   const float x = (kpts[2 * row] - nm[0]) / nm[2];
   const float y = (kpts[2 * row + 1] - nm[1]) / nm[2];
   float v = fmaf(w1[2 * ch + 1], y, fmaf(w1[2 * ch], x, b1[ch]));
@@ -247,6 +258,7 @@ __global__ __launch_bounds__(256) void pack_graphs_kernel(const gims_pack_image*
       kpts_out[2 * (im.row_off + r) + 1] = im.kpts[2 * src + 1];
       if (score_out && im.score) score_out[im.row_off + r] = im.score[src];
       seg[im.row_off + r] = blockIdx.y;
+      if (im.src_row) im.src_row[im.row_off + r] = im.in_off + src;
       indptr_out[im.row_off + r] = im.indptr[r] + im.edge_off;
     }
   }
@@ -319,6 +331,18 @@ extern "C" int gims_pack_graphs(const gims_pack_image* dev_images, int32_t n_ima
   return GIMS_OK;
 }
 
+// GIMS_AUX_KENC_FIRST with i[2] = n_img > 0: the rows are the keypoints of n_img whole images back to back and p[2] holds the first row of every
+// image instead of an image index per row (the keypoint encoder over ALL input keypoints, enqueued before the kept ones are known)
+static int kenc_first_images(const float* kpts, const float* norm3, const int32_t* starts, const float* w1, const float* b1, int32_t c1,
+                             float* out, int64_t n, int32_t n_img, hipStream_t stream) {
+  using namespace gims;
+  GIMS_CHECK_ARG(kpts && norm3 && starts && w1 && b1 && out && c1 > 0 && n >= 0, "gims_run_ops: GIMS_AUX_KENC_FIRST: bad arguments");
+  if (n == 0) return GIMS_OK;
+  hipLaunchKernelGGL(kenc_first_kernel<true>, dim3(cdiv(n * c1, 256)), dim3(256), 0, stream, kpts, norm3, starts, w1, b1, c1, out, n, n_img);
+  GIMS_LAUNCH_CHECK();
+  return GIMS_OK;
+}
+
 extern "C" int gims_run_ops(const gims_op* ops, int32_t n_ops, void* stream) {
   using namespace gims;
   GIMS_CHECK_ARG(ops && n_ops >= 0, "gims_run_ops: bad arguments");
@@ -337,6 +361,9 @@ extern "C" int gims_run_ops(const gims_op* ops, int32_t n_ops, void* stream) {
       else if (x.fn == GIMS_AUX_SAGE_MEAN_SPLIT)
         rc = gims_sage_mean_split((const float*)x.p[0], x.i[0], (const int32_t*)x.p[1], (const int32_t*)x.p[2], (int32_t)x.i[1], (int32_t)x.i[2],
                                   (uint16_t*)x.p[3], x.i[3], stream);
+      else if (x.fn == GIMS_AUX_KENC_FIRST && x.i[2] > 0)
+        rc = kenc_first_images((const float*)x.p[0], (const float*)x.p[1], (const int32_t*)x.p[2], (const float*)x.p[3], (const float*)x.p[4],
+                               (int32_t)x.i[0], (float*)x.p[5], x.i[1], (int32_t)x.i[2], (hipStream_t)stream);
       else if (x.fn == GIMS_AUX_KENC_FIRST)
         rc = gims_kenc_first((const float*)x.p[0], (const float*)x.p[1], (const int32_t*)x.p[2], (const float*)x.p[3], (const float*)x.p[4],
                              (int32_t)x.i[0], (float*)x.p[5], x.i[1], stream);
@@ -448,7 +475,7 @@ extern "C" int gims_kenc_first(const float* kpts, const float* norm3, const int3
   GIMS_CHECK_ARG(kpts && norm3 && seg_of_row && w1 && b1 && out && c1 > 0 && n >= 0, "gims_kenc_first: bad arguments");
   if (n == 0) return GIMS_OK;
   hipLaunchKernelGGL(kenc_first_kernel<true>, dim3(cdiv(n * c1, 256)), dim3(256), 0, (hipStream_t)stream, kpts, norm3,
-                     seg_of_row, w1, b1, c1, out, n);
+                     seg_of_row, w1, b1, c1, out, n, 0);
   GIMS_LAUNCH_CHECK();
   return GIMS_OK;
 }
@@ -459,7 +486,7 @@ extern "C" int gims_kenc_first_linear(const float* kpts, const float* norm3, con
   GIMS_CHECK_ARG(kpts && norm3 && seg_of_row && w1 && b1 && out && c1 > 0 && n >= 0, "gims_kenc_first_linear: bad arguments");
   if (n == 0) return GIMS_OK;
   hipLaunchKernelGGL(kenc_first_kernel<false>, dim3(cdiv(n * c1, 256)), dim3(256), 0, (hipStream_t)stream, kpts, norm3,
-                     seg_of_row, w1, b1, c1, out, n);
+                     seg_of_row, w1, b1, c1, out, n, 0);
   GIMS_LAUNCH_CHECK();
   return GIMS_OK;
 }

@@ -609,7 +609,11 @@ class GMatcher(nn.Module):
         if pin is None or pin.shape[0] < info_all.shape[0]:
             pin = self.__dict__["_info_pin"] = torch.empty((max(64, info_all.shape[0]), 8), dtype=torch.int32, pin_memory=True)
         pin[:info_all.shape[0]].copy_(info_all, non_blocking=True)
-        torch.cuda.current_stream().synchronize()
+        early = self._kenc_early(ctx)       # (the keypoint encoder over all input keypoints, enqueued BEHIND the read-back: it runs while the host waits)
+        if early is None:
+            torch.cuda.current_stream().synchronize()
+        else:
+            early["event"].synchronize()    # the read-back has landed; everything enqueued before it (the previous batch of this lane too) has finished
         infos = pin[:info_all.shape[0]].numpy().copy()
         self._sync_ms = 1e3 * (time.perf_counter() - ts0)
         each = ctx.get("each")
@@ -670,7 +674,70 @@ class GMatcher(nn.Module):
             g["n_kept"], g["n_edges"], g["info_host"] = int(inf[0]), int(inf[1]), inf
             g["rows"] = (ro, g["n_kept"])
         return dict(feat=feat, kpts_all=kpts_all, score_all=score_all, seg=seg, indptr_all=indptr_all, indices_all=indices_all,
-                    norm3=norm3, n_tot=n_tot, e_tot=e_tot)
+                    norm3=norm3, n_tot=n_tot, e_tot=e_tot, early=early)
+
+    # The keypoint encoder reads (x, y), the image size and the folded weights only -- nothing of the graph build -- so with the default configuration
+    # (linear_precision='bf16x3', no LayerNorm) it runs over ALL input keypoints of the batch while the host waits for the kept counts, where the
+    # device used to idle.  GraphSAGE's last layer then adds the rows of the kept keypoints as its residual (linear_args
+    # residual_rows, filled by the gather kernel) and writes desc (+ dpl): sage + kenc in place of kenc + sage, the same bits; a GEMM row does not depend
+    # on the rows that share its launch.  The GraphSAGE output alone is not materialised in this order (`sage` of the results is None).
+    # kenc_early = False or GIMS_KENC_EARLY=0 keeps the encoder behind the synchronisation.
+    kenc_early = True
+
+    def _kenc_early(self, ctx):
+        """Enqueue the read-back event and, behind it, the keypoint encoder over all input keypoints of ctx's batch.  Returns None where that order
+        does not apply (a caller other than _run_rest, configuration, switch, or keypoints that do not lie back to back in one buffer), else dict(event, out: f32 [n_in, D],
+        src_row: int32 [n_in], filled by the gather kernel with the input row of every kept keypoint).  This runs before the build's flag words
+        are read: a build that _run_rest repeats (missed window, edge capacity) throws the work away and it is enqueued again with the repeat.
+        A sweep's sub-batch of several settings repeats the base images, fails the back-to-back test and keeps the old order."""
+        if not ctx.get("kenc_early") or not self.kenc_early or os.environ.get("GIMS_KENC_EARLY", "1") == "0":
+            return None
+        images = ctx["images"]
+        kp0 = images[0]["kp"]
+        dev = kp0.device
+        P = self._packed(dev)
+        if not P["x3"] or P["ln"]:
+            return None
+        starts, off = [], 0
+        for g in images:
+            kp = g["kp"]
+            if kp.dtype != torch.float32 or not kp.is_contiguous() or kp.data_ptr() != kp0.data_ptr() + 8 * off:
+                return None
+            starts.append(off)
+            off += kp.shape[0]
+        n_in = off
+        bf, f32 = torch.bfloat16, torch.float32
+        A = lambda name, cols, dt: self._act(name, n_in, cols, dt)                      # noqa: E731
+        c1 = P["kenc_w1"].shape[0]
+        kmax = max([c1] + [e["n"] for e in P["kenc"]])
+        b = dict(xk=A("kenc_in_x", c1, f32), xs0=A("kenc_in_xs0", 2 * kmax, bf), xs1=A("kenc_in_xs1", 2 * kmax, bf), desc=A("kenc_in_out", P["kenc"][-1]["n"], f32))
+        src_row = self._act("kenc_src_row", n_in, 1, torch.int32)
+        ev = torch.cuda.Event()
+        ev.record()
+        starts_dev = hip.upload(np.asarray(starts, dtype=np.int32), dev)
+        batch = dict(n=n_in, kpts=kp0.data_ptr(), norm3=ctx["norm3"].data_ptr(), seg=starts_dev.data_ptr(), n_img=len(images))
+        key = (P["gen"],) + tuple(t.data_ptr() for t in b.values())
+        cache = self.__dict__.setdefault("_kenc_cache", {})
+        ent = cache.get(key)
+        if ent is None:
+            if len(cache) > 4:
+                cache.clear()
+            lst, slots = self._encoder_ops(P, b, None, batch, part="kenc")
+            ent = cache[key] = self._table(lst, (P, b), slots)
+        self._patch(ent, batch)
+        self._issue("encoder", ent, n_in)
+        ctx["ptab"]["src_row"], ctx["ptab"]["in_off"] = src_row.data_ptr(), starts
+        return dict(event=ev, out=b["desc"], src_row=src_row, starts=starts_dev)
+
+    @staticmethod
+    def _patch(ent, batch):
+        """Write the per-call values `batch` into the slots the builder of table `ent` recorded."""
+        ops = ent[0]
+        for k, field, j, what in ent[6]:
+            if j is None:
+                setattr(ops[k].u.lin, field, batch[what])
+            else:
+                getattr(ops[k].u.aux, field)[j] = batch[what]
 
     @staticmethod
     def _finish_graphs(images, G):
@@ -702,9 +769,10 @@ class GMatcher(nn.Module):
 
     def _run_rest(self, ctx):
         """Phase 2: read the kept counts (the one host sync; a build that asks for it is repeated), then enqueue everything else.  Returns the
-        results of the batch: items (per pair the score matrix, matches and potentials), pairs (their row ranges), mdesc, desc, sage,
+        results of the batch: items (per pair the score matrix, matches and potentials), pairs (their row ranges), mdesc, desc, sage (None where _kenc_early applied),
         images, flat, outputs (every device buffer of the batch), status_offs (where in outputs[4] each pair's Sinkhorn status word lies),
         dropped (sweep: the pairs that kept nothing) and repeats (of the graph build)."""
+        ctx["kenc_early"] = True        # (the encoder stage of _run_batch knows that order; the training step gathers for its own encoder and does not ask)
         G = self._gather(ctx)
         if G is None:
             again = self._run_build(ctx["images"], *ctx["params"], delaunay=bool(ctx.get("delaunay")), each=ctx.get("each"))
@@ -840,7 +908,9 @@ class GMatcher(nn.Module):
         change from call to call: the table is CACHED and PATCHED per call with what does change -- the row count and the six pointers of the
         batch (kept descriptors, CSR, keypoints, image index per row, normalisation constants), at the slots the builder recorded.  Between a
         batch's one host synchronisation and its layers the device waits for the host: on a cache hit no gims_op is built or copied
-        (DESIGN.md 4.5).  Returns (sage, desc); with linear_precision='bf16x3' dpl, the SPL32 copy of desc, is self._act('dpl')."""
+        (DESIGN.md 4.5).  Returns (sage, desc); with linear_precision='bf16x3' dpl, the SPL32 copy of desc, is self._act('dpl').  Where the keypoint
+        encoder ran ahead of the synchronisation (G['early'], _kenc_early) only GraphSAGE is left here: its last layer adds the encoder's rows and
+        writes desc, and sage is None."""
         D, n_tot = self.config['descriptor_dim'], G["n_tot"]
         bf, f32 = torch.bfloat16, torch.float32
         x3, spl = P["x3"], P["x3"] and not P["ln"]            # spl: the keypoint encoder's hidden activations exist as SPL32 planes only
@@ -848,37 +918,39 @@ class GMatcher(nn.Module):
         c1 = P["kenc_w1"].shape[0]
         wmax = max([D] + [e["n"] for e in P["sage"]])                                    # (one width per arena buffer: the widest layer that uses it)
         kmax = max([c1] + [e["n"] for e in P["kenc"]])
-        b = dict(hf0=A("sage_h0", wmax, f32), hf1=A("sage_h1", wmax, f32), sage=A("sage_out", P["sage"][-1]["n"], f32),
-                 agg=A("sage_agg", 2 * wmax, bf) if x3 else A("sage_agg", wmax, f32), xk=A("kenc_x", c1, f32), desc=A("desc", P["kenc"][-1]["n"], f32))
+        early = G.get("early")                                  # the keypoint encoder ran before the synchronisation (_kenc_early): GraphSAGE only, its last layer adds it
+        b = dict(hf0=A("sage_h0", wmax, f32), hf1=A("sage_h1", wmax, f32), agg=A("sage_agg", 2 * wmax, bf) if x3 else A("sage_agg", wmax, f32),
+                 desc=A("desc", P["kenc"][-1]["n"], f32))
+        if early is None:
+            b.update(sage=A("sage_out", P["sage"][-1]["n"], f32), xk=A("kenc_x", c1, f32))
         if x3:
             b.update(hs0=A("sage_hs0", 2 * wmax, bf), hs1=A("sage_hs1", 2 * wmax, bf), dpl=A("dpl", 2 * D, bf))
-        if spl:
+        if early is None and spl:
             b.update(xs0=A("kenc_xs0", 2 * kmax, bf), xs1=A("kenc_xs1", 2 * kmax, bf))
-        else:
+        elif early is None:
             b.update(xf0=A("kenc_xf0", kmax, f32), xf1=A("kenc_xf1", kmax, f32))
         batch = dict(n=n_tot, feat=G["feat"].data_ptr(), ldf=G["feat"].stride(0), indptr=G["indptr_all"].data_ptr(), indices=G["indices_all"].data_ptr(),
                      kpts=G["kpts_all"].data_ptr(), norm3=G["norm3"].data_ptr(), seg=G["seg"].data_ptr())
-        key = (P["gen"],) + tuple(t.data_ptr() for t in b.values())
+        if early is not None:
+            batch.update(kenc_all=early["out"].data_ptr(), src_row=early["src_row"].data_ptr())
+        key = (P["gen"], early is not None) + tuple(t.data_ptr() for t in b.values())
         cache = self.__dict__.setdefault("_enc_cache", {})
         ent = cache.get(key)
         if ent is None:
             if len(cache) > 4:
                 cache.clear()
-            lst, slots = self._encoder_ops(P, b, G["feat"], batch)
+            lst, slots = self._encoder_ops(P, b, G["feat"], batch, part="all" if early is None else "sage", early=early)
             ent = cache[key] = self._table(lst, (P, b), slots)
-        ops = ent[0]
-        for k, field, j, what in ent[6]:
-            if j is None:
-                setattr(ops[k].u.lin, field, batch[what])
-            else:
-                getattr(ops[k].u.aux, field)[j] = batch[what]
+        self._patch(ent, batch)
         self._issue("encoder", ent, n_tot)
-        return b["sage"], b["desc"]
+        return b.get("sage"), b["desc"]
 
-    def _encoder_ops(self, P, b, feat, batch):
+    def _encoder_ops(self, P, b, feat, batch, part="all", early=None):
         """The launches of GraphSAGE (label 'sage') and the keypoint encoder ('kenc') on the arena buffers b, for the configuration of pack P:
         [(label, gims_op)], and the slots _encoder patches per call as (op, field, index | None, name in `batch`) -- an argument given here by its
-        name in `batch` is such a slot."""
+        name in `batch` is such a slot.  part: 'all' -- both, the encoder's last layer adds `sage`; 'kenc' -- the encoder alone over whole images
+        (_kenc_early: no residual, b['desc'] is its output); 'sage' -- GraphSAGE alone, its last layer adds the rows early['src_row'] of early['out']
+        and writes desc (+ dpl)."""
         x3, ln, spl = P["x3"], P["ln"], P["x3"] and not P["ln"]
         lst, slots = [], []
         V = lambda t, cols: t[:, :cols]                                              # noqa: E731  (a view of the arena buffer with the layer's width)
@@ -891,11 +963,22 @@ class GMatcher(nn.Module):
 
         def lin(label, e, a0, **kw):
             slots.append((len(lst), "m", None, "n"))
-            if a0 is feat:
+            if kw.get("residual_rows") is not None:
+                slots.extend([(len(lst), "residual", None, "kenc_all"), (len(lst), "residual_rows", None, "src_row")])
+            if feat is not None and a0 is feat:
                 slots.extend([(len(lst), "a0", None, "feat"), (len(lst), "lda0", None, "ldf")])
             lst.append((label, self._lin_op(e, a0, **kw)))
         # GraphSAGE, per layer mean(h) over the neighbours and the GEMM on [h | mean(h)].  bf16x3: both operands as SPL32 planes (the producing
         # GEMM writes the planes of the next layer's h itself; the aggregation reads h in f32); f32: both in f32
+        if part != "kenc":
+            self._sage_ops(P, b, feat, aux, lin, V, early)
+        if part != "sage":
+            self._kenc_ops(P, b, aux, lin, V, part == "kenc")
+        return lst, slots
+
+    @staticmethod
+    def _sage_ops(P, b, feat, aux, lin, V, early):
+        x3 = P["x3"]
         dims = [feat.shape[1]] + [e["n"] for e in P["sage"]]                           # 256, 128, 128, 256
         h, ldh, hop = "feat", "ldf", feat
         if x3:
@@ -905,14 +988,22 @@ class GMatcher(nn.Module):
             last = i == len(P["sage"]) - 1
             aggv = V(b["agg"], (2 if x3 else 1) * dims[i])
             aux("sage", hip.AUX_SAGE_MEAN_SPLIT if x3 else hip.AUX_SAGE_MEAN, [h, "indptr", "indices", aggv], [ldh, "n", dims[i], aggv.stride(0)])
+            if last and early is not None:     # sage + kenc: the encoder's rows of the kept keypoints as the residual
+                lin("sage", e, hop, a1=aggv, act=hip.ACT_NONE, out=b["desc"], out_split=b.get("dpl"), residual=early["out"], residual_rows=early["src_row"])
+                break
             h = b["sage"] if last else V(b["hf%d" % (i & 1)], dims[i + 1])
             hs = V(b["hs%d" % ((i + 1) & 1)], 2 * dims[i + 1]) if x3 and not last else None
             lin("sage", e, hop, a1=aggv, act=hip.ACT_NONE if last else hip.ACT_RELU, out=h, out_split=hs)
             ldh, hop = h.stride(0), hs if x3 else h
+
+    def _kenc_ops(self, P, b, aux, lin, V, images):
+        """images: the rows are whole images back to back (the batch's 'seg' holds their first rows, 'n_img' their number) and nothing is added."""
+        ln, spl = P["ln"], P["x3"] and not P["ln"]
         # keypoint encoder: first layer on normalised coordinates, then the MLP (LayerNorm variant: conv -> norm kernel -> ReLU); the last layer
         # adds `sage` and writes desc (+ dpl)
         c1, xk = b["xk"].shape[1], b["xk"]
-        aux("kenc", hip.AUX_KENC_FIRST_LINEAR if ln else hip.AUX_KENC_FIRST, ["kpts", "norm3", "seg", P["kenc_w1"], P["kenc_b1"], xk], [c1, "n"])
+        aux("kenc", hip.AUX_KENC_FIRST_LINEAR if ln else hip.AUX_KENC_FIRST, ["kpts", "norm3", "seg", P["kenc_w1"], P["kenc_b1"], xk],
+            [c1, "n"] + (["n_img"] if images else []))
         if ln:
             aux("kenc", *self._norm_args(xk, P["kenc_ln"][0], "n", out=xk))
         cur = xk
@@ -921,7 +1012,10 @@ class GMatcher(nn.Module):
             cur = V(b["xs0"], 2 * c1)
         for i, e in enumerate(P["kenc"]):
             if i == len(P["kenc"]) - 1:
-                lin("kenc", e, cur, residual=b["sage"], out=b["desc"], out_split=b.get("dpl"))
+                if images:
+                    lin("kenc", e, cur, out=b["desc"])
+                else:
+                    lin("kenc", e, cur, residual=b["sage"], out=b["desc"], out_split=b.get("dpl"))
             elif spl:
                 cur, prev = V(b["xs%d" % ((i + 1) & 1)], 2 * e["n"]), cur
                 lin("kenc", e, prev, act=hip.ACT_RELU, out_split=cur)
@@ -930,7 +1024,6 @@ class GMatcher(nn.Module):
                 lin("kenc", e, prev, act=hip.ACT_NONE if ln else hip.ACT_RELU, out=cur)
                 if ln:
                     aux("kenc", *self._norm_args(cur, P["kenc_ln"][i + 1], "n", out=cur))
-        return lst, slots
 
     def _layers(self, P, desc, n_tot, max_nq, self_pr, cross_pr, guards, repeat):
         """The 18 attentional layers on the residual stream desc (and its SPL32 copy self._act('dpl')): their launches depend only on the buffer

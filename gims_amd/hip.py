@@ -181,11 +181,12 @@ def _dev(t: torch.Tensor, dtype=None):
 
 
 def linear_args(a0, w, *, bias=None, a1=None, w_lo=None, residual=None, out=None, out_bf16=None, act=ACT_NONE,
-                precision=PREC_F32, scale=1.0, n=None, spl=False, out_split=None, flags=0, guard=None, range_stat=None):
+                precision=PREC_F32, scale=1.0, n=None, spl=False, out_split=None, flags=0, guard=None, range_stat=None, residual_rows=None):
     """Build the C struct.
     spl=False: a0/a1 f32 [m,k*]; w f32 [n,K] (PREC_F32) or bf16 hi plane with w_lo (PREC_BF16X3).
     spl=True : a0/a1/w are SPL32 bf16 buffers [rows, 2*k] (see include/gims_hip.h), precision BF16X3.
-    out_split: SPL32 bf16 buffer [m, >= 2n] receiving the result split into hi/lo."""
+    out_split: SPL32 bf16 buffer [m, >= 2n] receiving the result split into hi/lo.
+    residual_rows (spl=True): int32 [m], row r adds residual[residual_rows[r]] -- `residual` may then have any number of rows."""
     m = a0.shape[0]
     if precision == PREC_BF16X6:
         # a0 / w are SPL3 bf16 buffers [rows, 3k] (split_spl3); plain f32 output only
@@ -202,7 +203,7 @@ def linear_args(a0, w, *, bias=None, a1=None, w_lo=None, residual=None, out=None
         # operand cost a single-pair forward() ~8 us of Python per GEMM launch)
         p_a0, p_a1, p_w = a0.data_ptr(), (a1.data_ptr() if a1 is not None else None), w.data_ptr()
         return _linear_struct(p_a0, a0.stride(0), p_a1, a1.stride(0) if a1 is not None else 0, p_w, p_w + 64, w, bias, residual, out, out_bf16, m, n,
-                              k, k0, act, precision, scale, p_a0 + 64, (p_a1 + 64) if p_a1 is not None else None, out_split, flags, guard, range_stat)
+                              k, k0, act, precision, scale, p_a0 + 64, (p_a1 + 64) if p_a1 is not None else None, out_split, flags, guard, range_stat, residual_rows)
     else:
         _dev(a0, torch.float32)
         k0 = a0.shape[1]
@@ -210,11 +211,11 @@ def linear_args(a0, w, *, bias=None, a1=None, w_lo=None, residual=None, out=None
         assert w.shape[1] == k, (w.shape, k)
         a0_lo = a1_lo = None
     return _linear_struct(_p(a0), a0.stride(0), _p(a1), a1.stride(0) if a1 is not None else 0, _p(w), _p(w_lo), w, bias, residual, out, out_bf16, m, n,
-                          k, k0, act, precision, scale, _p(a0_lo), _p(a1_lo), out_split, flags, guard, range_stat)
+                          k, k0, act, precision, scale, _p(a0_lo), _p(a1_lo), out_split, flags, guard, range_stat, residual_rows)
 
 
 def _linear_struct(p_a0, lda0, p_a1, lda1, p_w, p_w_lo, w, bias, residual, out, out_bf16, m, n, k, k0, act, precision, scale, p_a0_lo, p_a1_lo, out_split,
-                   flags, guard, range_stat) -> LinearArgs:
+                   flags, guard, range_stat, residual_rows=None) -> LinearArgs:
     n = w.shape[0] if n is None else n
     assert w.stride(1) == 1
     if residual is not None:
@@ -225,7 +226,7 @@ def _linear_struct(p_a0, lda0, p_a1, lda1, p_w, p_w_lo, w, bias, residual, out, 
                       out.stride(0) if out is not None else 0, _p(out_bf16),
                       out_bf16.stride(0) if out_bf16 is not None else 0, m, n, k, k0, act, precision, float(scale),
                       p_a0_lo, p_a1_lo, _p(out_split), (out_split.data_ptr() + 64) if out_split is not None else None,
-                      out_split.stride(0) if out_split is not None else 0, int(flags),
+                      out_split.stride(0) if out_split is not None else 0, int(flags), residual_rows=_p(residual_rows),
                       guard=guard if guard is not None else AttnGuard(), range_stat=_p(range_stat))
 
 
@@ -599,7 +600,7 @@ def pack_table(images_ptrs):
     the count/offset columns are filled after the graph build's host sync (vectorised: no per-image Python work then)."""
     t = np.zeros(len(images_ptrs), dtype=PACK_DTYPE)
     for i, r in enumerate(images_ptrs):
-        t[i] = r + (0, 0, 0, 0)
+        t[i] = tuple(r) + (0,) * (len(PACK_DTYPE.names) - len(r))
     return t
 
 

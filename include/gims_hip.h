@@ -26,7 +26,10 @@
 extern "C" {
 #endif
 
-#define GIMS_ABI_VERSION 4   /* 4: the superseded CAR-HyNet entry points and the 3x3-convolution gather mode of gims_linear are gone; gims_linear_args keeps its size, conv_* became reserved0 / probe_delay */
+#define GIMS_ABI_VERSION 4   /* 4: the superseded CAR-HyNet entry points and the 3x3-convolution gather mode of gims_linear are gone; gims_linear_args keeps its size, conv_* became reserved0 / probe_delay.
+                             Still 4 (the version is pinned), but NOT layout-compatible with earlier builds of 4: gims_pack_image grew from 80 to 96 bytes (src_row, in_off;
+                             gims_pack_graphs indexes a device array of them by sizeof) and two reserved words of gims_linear_args became residual_rows -- header,
+                             library and binding of one build go together */
 
 #define GIMS_OK 0
 #define GIMS_EINVAL (-1)   /* bad argument (shape / alignment / null pointer) */
@@ -104,7 +107,10 @@ typedef struct gims_linear_args {
   uint16_t* out_hi; uint16_t* out_lo; int64_t ld_split;
   /* GIMS_LINEAR_UPPER: symmetric product (A == W): skip output tiles that lie entirely below the diagonal */
   int32_t flags;
-  int32_t reserved0[3];                /* must be 0 (they keep guard / range_stat at their kernel-argument offsets) */
+  int32_t reserved0;                   /* must be 0 (with residual_rows it keeps guard / range_stat at their kernel-argument offsets) */
+  /* pre-split operands only: row r adds residual[residual_rows[r]] instead of residual[r] (the keypoint encoder's output over ALL input keypoints,
+   * read at the kept ones by GraphSAGE's last layer: gims_pack_image.src_row).  NULL: residual[r]. */
+  const int32_t* residual_rows;
   int32_t probe_delay;                 /* tools/gemm_probe.py only (diagnostic flag 0x1000); 0 otherwise */
   gims_attn_guard guard;               /* pre-split operands (a0_lo != NULL) only: the launch is a no-op unless the guard fires; zero = always run */
   /* pre-split operands with GIMS_LINEAR_OUT_F16 only: the launch also reports max |value| of what it stores into out_bf16, per block of
@@ -240,6 +246,8 @@ int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t
  *   GIMS_AUX_SPLIT_SPL32      gims_split_spl32     p = {src, dst}                              i = {lds, ldd, rows, k}
  *   GIMS_AUX_SAGE_MEAN_SPLIT  gims_sage_mean_split p = {h, indptr, indices, out_spl}           i = {ldh, n, c, ld_spl}
  *   GIMS_AUX_KENC_FIRST       gims_kenc_first      p = {kpts, norm3, seg_of_row, w1, b1, out}  i = {c1, n}
+ *     (through the table only: i = {c1, n, n_img > 0} takes the rows as n_img whole images back to back, p[2] = the first row of every image,
+ *      ascending from 0, instead of one image index per row -- the encoder over all INPUT keypoints, before the kept ones are known)
  * and the small kernels of the linear_precision='f32' and use_layernorm=True variants of both stages:
  *   GIMS_AUX_SAGE_MEAN          gims_sage_mean          p = {h, indptr, indices, out}               i = {ldh, n, c, ldo}
  *   GIMS_AUX_KENC_FIRST_LINEAR  gims_kenc_first_linear  p, i as GIMS_AUX_KENC_FIRST
@@ -499,6 +507,9 @@ typedef struct gims_pack_image {
   const float* kpts; const float* desc; int64_t ldd; const float* score;
   const int32_t* kept; const int32_t* indptr; const int32_t* indices;
   int32_t n_kept, n_edges, row_off, edge_off;
+  /* optional: src_row[ro_i + r] = in_off + kept_i[r], the row of kept keypoint r in an array over ALL input keypoints of the batch in which
+   * image i starts at row in_off (gims_linear_args.residual_rows).  src_row is the whole batch's array; NULL = not written. */
+  int32_t* src_row; int32_t in_off, reserved;
 } gims_pack_image;
 
 int gims_pack_graphs(const gims_pack_image* dev_images /* DEVICE array */, int32_t n_images, int32_t max_kept,
