@@ -3,12 +3,12 @@
 Public surface mirrors the reference: ``GMatcher(config).forward(data)`` and ``Matching(config).forward(data)``.
 Kernels live in ``gims_amd/csrc`` (HIP, gfx950) behind the C ABI of ``include/gims_hip.h``.
 """
-from .gmatcher import GMatcher  # noqa: F401
+from .gmatcher import GMatcher, ImageFeatures  # noqa: F401
 from .matching import Matching  # noqa: F401
 from .baselines import mnn, nn_match_pairs, nndr  # noqa: F401
 from .augment import ColorAug, ColorAugPlan  # noqa: F401
 from .verify import (epipolar_error, estimate_pose, find_fundamental, find_homography, pose_error, pose_summary,  # noqa: F401
                      verify_pairs)
 
-__all__ = ["GMatcher", "Matching", "nndr", "mnn", "nn_match_pairs", "ColorAug", "ColorAugPlan", "find_homography", "find_fundamental", "verify_pairs",
+__all__ = ["GMatcher", "ImageFeatures", "Matching", "nndr", "mnn", "nn_match_pairs", "ColorAug", "ColorAugPlan", "find_homography", "find_fundamental", "verify_pairs",
            "estimate_pose", "pose_error", "epipolar_error", "pose_summary"]

@@ -173,6 +173,8 @@ int mlp_fused_launch(const gims_linear_args& a, hipStream_t s);
 int sift_describe_aux(const gims_aux_args& x, hipStream_t st);
 // nms.hip: GIMS_AUX_DIOU_NMS, likewise reached through gims_run_ops only
 int diou_nms_aux(const gims_aux_args& x, hipStream_t st);
+// features.hip: GIMS_AUX_ASSEMBLE_ROWS, likewise
+int assemble_rows_aux(const gims_aux_args& x, hipStream_t st);
 
 // sinkhorn2d.hip: the 2-D on-chip Sinkhorn (all iterations in one launch; see that file's header)
 struct OtR2Host { const float* z; int64_t ld; int n, m; float* u; float* v; float* status; float norm, log_mu_bin, log_nu_bin; };

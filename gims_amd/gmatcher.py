@@ -20,6 +20,7 @@ from __future__ import annotations
 import math
 import os
 import time
+import weakref
 from typing import Dict, List
 
 import numpy as np
@@ -60,6 +61,7 @@ class PairResults(list):
     """List of per-pair result dicts; ``.flat`` additionally exposes the batch-concatenated match tensors (what the
     per-pair entries are views of) so statistics can be reduced without touching each pair separately."""
     flat = None
+    datas = None      # match_features: per pair the dict match_pairs would have left behind (None from match_pairs: its callers hold the dicts)
 
 
 class GraphHandle:
@@ -79,6 +81,39 @@ class GraphHandle:
         deg = (self.indptr[1:] - self.indptr[:-1]).long()
         dst = torch.repeat_interleave(torch.arange(deg.numel(), device=deg.device), deg)
         return self.indices.long(), dst
+
+
+class ImageFeatures:
+    """One image as the matcher sees it behind its encoder stage (``GMatcher.encode_images``): everything of a match that does not depend
+    on the partner image.  Immutable.  Device tensors: ``keypoints`` [n, 2], ``descriptors`` [n, 256] (point-major), ``scores`` [n] -- the
+    kept ones --, ``kept`` (int32 indices into the input), ``graph`` (``GraphHandle``) and ``encoded`` f32 [n, 256], the residual stream the
+    attentional layers start from.  Host values: ``n``, ``n_edges``, ``shape`` (the image's), ``setting`` = (radius, percentile, min_size,
+    delaunay) and ``gen``, the generation of the weight pack the image was encoded with: features are valid for those weights only
+    (``GMatcher.match_features`` refuses others)."""
+    __slots__ = ("keypoints", "descriptors", "scores", "kept", "graph", "encoded", "n", "n_edges", "shape", "setting", "gen", "_owner")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            object.__setattr__(self, k, kw[k])
+
+    def __setattr__(self, name, value):
+        raise AttributeError("ImageFeatures is immutable")
+
+    __delattr__ = __setattr__
+
+    @property
+    def device(self):
+        return self.encoded.device
+
+    def __repr__(self):
+        return f"ImageFeatures(n={self.n}, n_edges={self.n_edges}, shape={tuple(self.shape)}, setting={self.setting}, gen={self.gen}, device='{self.device}')"
+
+
+class _ImageShape:
+    """Stands where a data dict holds an image of which only ``.shape`` is read (``match_features``' ``datas``)."""
+
+    def __init__(self, shape):
+        self.shape = tuple(shape)
 
 
 class GMatcher(nn.Module):
@@ -788,17 +823,27 @@ class GMatcher(nn.Module):
     def _run_batch(self, ctx, G):
         """_run_rest for the batch gathered in G: encoder, layers, scores, Sinkhorn and selection, all enqueued without a host sync."""
         images = ctx["images"]
-        cfg = self.config
-        dev = images[0]["kp"].device
-        P = self._packed(dev)
-        D = cfg['descriptor_dim']
-        St = lambda name: GMatcher._Stage(self, name)   # noqa: E731
+        P = self._packed(images[0]["kp"].device)
         feat, kpts_all, score_all, n_tot = G["feat"], G["kpts_all"], G["score_all"], G["n_tot"]
         # ---- GraphSAGE over the merged CSR of all images (gmatcher.py:145-162, 268-269) and keypoint encoder (gmatcher.py:26-33, 87-97);
         #      desc = sage + kenc (gmatcher.py:270-271)
         sage, desc = self._encoder(P, G)
-        # ---- attentional GNN (gmatcher.py:99-143): per layer QKV -> flash attention -> merge -> MLP -> residual
         pairs = [(images[2 * p]["rows"], images[2 * p + 1]["rows"]) for p in range(len(images) // 2)]
+        res = self._match_rows(P, desc, n_tot, pairs, max(g["n_kept"] for g in images), ctx)
+        self._finish_graphs(images, G)
+        res.update(sage=sage, images=images, outputs=res["outputs"] + [feat, kpts_all, score_all, ctx["pool"]])
+        return res
+
+    def _match_rows(self, P, desc, n_tot, pairs, max_nq, ctx):
+        """Everything behind the encoder stage, for _run_batch and match_features alike: the residual stream desc [n_tot, D] (and, with
+        linear_precision='bf16x3', its SPL32 copy self._act('dpl')) hold the encoded rows of the batch, pairs = [((o0, n0), (o1, n1))] are the row
+        ranges of every pair's two images, max_nq the longest of them.  Layers, final projection, scores, Sinkhorn and selection, all enqueued
+        without a host sync; ctx: the mode of the call (guards, repeat, streamed; see _run_build)."""
+        cfg = self.config
+        dev = desc.device
+        D = cfg['descriptor_dim']
+        St = lambda name: GMatcher._Stage(self, name)   # noqa: E731
+        # ---- attentional GNN (gmatcher.py:99-143): per layer QKV -> flash attention -> merge -> MLP -> residual
         # problem tables travel as kernel arguments (hip.upload): a pageable torch.tensor(..., device=) would block this
         # thread until the stream drains and stop the host from running ahead of the GPU
         # (problem tables and layer activations live in per-lane arenas: stable addresses let the launch tables be cached)
@@ -806,7 +851,7 @@ class GMatcher(nn.Module):
         cpr = np.asarray([q for (o0, n0), (o1, n1) in pairs for q in ((o0, n0, o1, n1), (o1, n1, o0, n0))], dtype=np.int32)
         # (ONE upload for both tables: a launch and ~15 us of host time less per call on the single-pair path)
         both = hip.upload(np.concatenate([spr, cpr]), dev, out=self._buf("attn_pr", spr.nbytes + cpr.nbytes + 32))
-        stat = self._layers(P, desc, n_tot, max(g["n_kept"] for g in images), both[:spr.shape[0]], both[spr.shape[0]:], bool(ctx.get("guards")), bool(ctx.get("repeat")))
+        stat = self._layers(P, desc, n_tot, max_nq, both[:spr.shape[0]], both[spr.shape[0]:], bool(ctx.get("guards")), bool(ctx.get("repeat")))
         if stat is not None:
             self._attention_stats_enqueue(stat)
         # ---- final projection, score matrix, Sinkhorn, selection (gmatcher.py:273-294)
@@ -844,10 +889,9 @@ class GMatcher(nn.Module):
             # `sinkhorn_status()` after a synchronise.)
             hip.sinkhorn_match(probs, P["alpha"], cfg['sinkhorn_iterations'], cfg['match_threshold'], work, otf)
             status_offs = np.cumsum([it["n"] + it["m"] + 3 for it in items]) - 1
-        self._finish_graphs(images, G)
-        return dict(items=items, pairs=pairs, mdesc=mdesc, desc=desc, sage=sage, images=images,
+        return dict(items=items, pairs=pairs, mdesc=mdesc, desc=desc,
                     flat=dict(matches0=m0_all, scores0=s0_all, n0=[n0 for (_, n0), _ in pairs], n1=[n1 for _, (_, n1) in pairs]),
-                    outputs=[m0_all, m1_all, s0_all, s1_all, uv_all, mdesc, feat, kpts_all, score_all, ctx["pool"]], status_offs=status_offs)
+                    outputs=[m0_all, m1_all, s0_all, s1_all, uv_all, mdesc], status_offs=status_offs)
 
     # ------------------------------------------------------------------ encoder and layer stages: launch tables
     # Each stage's launches are spelled ONCE, by its builder (_encoder_ops, _layer_ops), as a list of (stage-timer label, gims_op); the list is
@@ -1395,6 +1439,137 @@ class GMatcher(nn.Module):
             return (s.get('radius', 25), s.get('percentile', 7), s.get('min_size', 8), bool(s.get('delaunay', False)))
         radius, percentile, min_size = s
         return (radius, percentile, min_size, False)
+
+    # ------------------------------------------------------------------ image sets: encode each image once, match many pairs
+    @torch.no_grad()
+    def encode_images(self, images: List[dict], *, radius=25, percentile=7, min_size=8, delaunay=False, each=None) -> List[ImageFeatures]:
+        """Everything of a match that belongs to ONE image -- graph build, kept-keypoint compaction, GraphSAGE, keypoint encoder -- for a list
+        of images in one batched pass.  ``images``: dicts ``{'keypoints': (1, N, 2) | (N, 2), 'descriptors': (1, 256, N) |
+        (256, N), 'scores': (1, N) | (N,), 'image': anything with the image's .shape}`` -- what a front end returns per image, plus the image;
+        any number of them.  ``each``: one ``(radius, percentile, min_size[, delaunay])`` per image instead of the four keyword values.
+        Returns one ``ImageFeatures`` per image, in order, for ``match_features``; they are valid for the current weights.  One host
+        synchronisation (the kept counts).  An image that keeps nothing raises ``ValueError`` like ``forward``.  Evaluation only."""
+        if self.training:
+            raise NotImplementedError("encode_images serves evaluation only: call model.eval() first (training runs through forward(mode='train'))")
+        if not images:
+            raise ValueError("encode_images: the image list is empty")
+        if each is not None:
+            if len(each) != len(images):
+                raise ValueError(f"encode_images: each holds {len(each)} settings for {len(images)} images")
+            each = [self._graph_setting(e) if isinstance(e, dict) or len(e) == 3 else (e[0], e[1], e[2], bool(e[3])) for e in each]
+        raw = []
+        for k, im in enumerate(images):
+            kp, de, sc = im['keypoints'], im['descriptors'], im['scores']
+            kp, de, sc = (kp[0] if kp.dim() == 3 else kp), (de[0] if de.dim() == 3 else de), (sc[0] if sc.dim() == 2 else sc)
+            if kp.device.type != "cuda":
+                raise hip.GimsHipError("GMatcher runs on the GPU only (no CPU fallback): move the inputs to 'cuda'")
+            if kp.dim() != 2 or kp.shape[1] != 2 or de.dim() != 2 or de.shape[1] != kp.shape[0] or sc.shape != (kp.shape[0],):
+                raise ValueError(f"encode_images: image {k}: keypoints {tuple(kp.shape)}, descriptors {tuple(de.shape)} and scores {tuple(sc.shape)} "
+                                 "are not (N, 2), (256, N) and (N,)")
+            raw.append((kp, de, sc, tuple(im['image'].shape)))
+        with hip.pinned_stream():
+            ctx = self._run_build(self._ingest(raw), radius, percentile, min_size, delaunay=bool(delaunay), each=each)
+            while True:
+                ctx["kenc_early"] = True            # the encoder stage in the order _run_rest gives it
+                G = self._gather(ctx)
+                if G is not None:
+                    break
+                ctx = self._run_build(ctx["images"], *ctx["params"], delaunay=bool(ctx.get("delaunay")), each=ctx.get("each"))
+            batch = ctx["images"]
+            P = self._packed(batch[0]["kp"].device)
+            _, desc = self._encoder(P, G)
+            with GMatcher._Stage(self, "store"):
+                encoded = desc.clone()               # out of the lane arena: the next call overwrites it, and the layers update it in place
+            self._finish_graphs(batch, G)
+        owner = weakref.ref(self)
+        feats = []
+        for k, g in enumerate(batch):
+            ro, nk = g["rows"]
+            h = g["graph"]
+            feats.append(ImageFeatures(keypoints=h.ndata["point"], descriptors=h.ndata["feat"], scores=h.ndata["score"], kept=g["kept"], graph=h,
+                                       encoded=encoded[ro:ro + nk], n=nk, n_edges=g["n_edges"], shape=g["shape"],
+                                       setting=tuple(each[k]) if each is not None else (radius, percentile, min_size, bool(delaunay)),
+                                       gen=P["gen"], _owner=owner))
+        return feats
+
+    @torch.no_grad()
+    def match_features(self, feats: List[ImageFeatures], pairs) -> PairResults:
+        """Match the index pairs ``pairs = [(i, j), ...]`` over the encoded images ``feats`` (``encode_images``) in ONE batched pass: the batch
+        has the layout ``match_pairs`` gives the same pairs in the same order, its residual stream is filled from the features by one
+        launch (hip.assemble_rows; every entry gets its own copy of its images' rows, the layers update them in place), and the layers,
+        scores, Sinkhorn and selection run as they do there -- the results are bit for bit ``match_pairs``'.  ``i == j`` is allowed.  No
+        graph build, no encoder, and no host synchronisation on this call's work (with ``attention_precision='auto'`` the call folds in
+        the statistic of the PREVIOUS batch like every batch does, which waits for that batch's read-back).
+
+        Returns the ``PairResults`` of ``match_pairs`` (``keypoints0/1`` and ``descriptors0/1`` are views of the features; ``.flat`` as
+        there) with ``.datas``: per pair a dict shaped like the one ``match_pairs`` leaves behind (kept keypoints, descriptors, scores,
+        ``kept_kpts0/1_indices``, ``graph0/1``, ``image0/1`` as objects with the image's ``.shape``), for ``verify_pairs``,
+        ``evalh.evaluate_pairs`` and ``shard.pair_stats``.  ``ValueError``: an empty pair list, an index out of range, features of another
+        device, of another matcher, or of other weights (after ``load_state_dict`` / ``.to()``)."""
+        if self.training:
+            raise NotImplementedError("match_features serves evaluation only: call model.eval() first")
+        feats = list(feats)
+        pairs = [(int(i), int(j)) for i, j in pairs]
+        if not pairs:
+            raise ValueError("match_features: the pair list is empty")
+        for p, (i, j) in enumerate(pairs):
+            if not (0 <= i < len(feats) and 0 <= j < len(feats)):
+                raise ValueError(f"match_features: pair {p} = ({i}, {j}) has an index out of range (there are {len(feats)} images)")
+        used = sorted({k for pr in pairs for k in pr})
+        dev = feats[used[0]].device
+        for k in used:
+            f = feats[k]
+            if not isinstance(f, ImageFeatures):
+                raise TypeError(f"match_features: feats[{k}] is {type(f).__name__}, not ImageFeatures")
+            if f.device != dev or dev.index != torch.cuda.current_device():
+                raise ValueError(f"match_features: feats[{k}] lives on another device ({f.device}) than the batch runs on "
+                                 f"(cuda:{torch.cuda.current_device()}, with feats[{used[0]}] on {dev})")
+            if f._owner() is not self:
+                raise ValueError(f"match_features: feats[{k}] was encoded by another matcher")
+        D = self.config['descriptor_dim']
+        St = lambda name: GMatcher._Stage(self, name)   # noqa: E731
+        with hip.pinned_stream():
+            self._lane = 0
+            P = self._packed(dev)
+            for k in used:
+                if feats[k].gen != P["gen"]:
+                    raise ValueError(f"match_features: feats[{k}] was encoded with weight generation {feats[k].gen}, the matcher now holds "
+                                     f"generation {P['gen']} (the weights changed or moved): encode the images again")
+            rows, segs, o = [], [], 0
+            for i, j in pairs:
+                ni, nj = feats[i].n, feats[j].n
+                rows.append(((o, ni), (o + ni, nj)))
+                segs += [(feats[i].encoded, o), (feats[j].encoded, o + ni)]
+                o += ni + nj
+            n_tot = o
+            desc = self._act("desc", n_tot, D, torch.float32)
+            dpl = self._act("dpl", n_tot, 2 * D, torch.bfloat16) if P["x3"] else None
+            with St("assemble"):
+                table = hip.assemble_rows(segs, desc, dpl, D)
+            res = self._last = self._match_rows(P, desc, n_tot, rows, max(feats[k].n for k in used), dict(guards=True))
+            res.update(images=[], table=table, dropped=[], repeats=0)
+        outs, datas = [], []
+        for (i, j), it, ((o0, n0), (o1, n1)) in zip(pairs, res["items"], rows):
+            data = {}
+            for side, f in (("0", feats[i]), ("1", feats[j])):
+                data['keypoints' + side] = f.keypoints[None]
+                data['descriptors' + side] = f.descriptors.t()[None]
+                data['scores' + side] = f.scores[None]
+                data['kept_kpts%s_indices' % side] = [f.kept]
+                data['graph' + side] = [f.graph]
+                data['image' + side] = _ImageShape(f.shape)
+            datas.append(data)
+            outs.append({
+                'keypoints0': data['keypoints0'], 'keypoints1': data['keypoints1'],
+                'descriptors0': data['descriptors0'], 'descriptors1': data['descriptors1'],
+                'matches0': it["matches0"][None], 'matches1': it["matches1"][None],
+                'matching_scores0': it["mscores0"][None], 'matching_scores1': it["mscores1"][None],
+                'mdesc0': res["mdesc"][o0:o0 + n0], 'mdesc1': res["mdesc"][o1:o1 + n1],
+            })
+        outs = PairResults(outs)
+        outs.flat = [res["flat"]]
+        outs.datas = datas
+        return outs
 
     # ------------------------------------------------------------------ one pair under a grid of graph parameters
     @torch.no_grad()

@@ -66,6 +66,7 @@ AUX_SPLIT_SPL32, AUX_SAGE_MEAN_SPLIT, AUX_KENC_FIRST = _K["GIMS_AUX_SPLIT_SPL32"
 AUX_SAGE_MEAN, AUX_KENC_FIRST_LINEAR, AUX_LAYERNORM_ACT = _K["GIMS_AUX_SAGE_MEAN"], _K["GIMS_AUX_KENC_FIRST_LINEAR"], _K["GIMS_AUX_LAYERNORM_ACT"]
 AUX_SIFT_DESCRIBE = _K["GIMS_AUX_SIFT_DESCRIBE"]     # SIFT descriptors: reached through gims_run_ops only (no entry point of its own)
 AUX_DIOU_NMS = _K["GIMS_AUX_DIOU_NMS"]               # DIoU-NMS keypoint thinning: likewise
+AUX_ASSEMBLE_ROWS = _K["GIMS_AUX_ASSEMBLE_ROWS"]     # desc / dpl of a batch of pairs from per-image stores of encoded rows: likewise
 SIFT_MAX_OCTAVES, SIFT_MAX_RADIUS, SIFT_SLOTS = _K["GIMS_SIFT_MAX_OCTAVES"], _K["GIMS_SIFT_MAX_RADIUS"], _K["GIMS_SIFT_SLOTS"]
 
 
@@ -1096,6 +1097,74 @@ def diou_nms(kp4: torch.Tensor, order: torch.Tensor, offsets: torch.Tensor, radi
     work = torch.empty(diou_nms_workspace_bytes(n, n_images), dtype=torch.uint8, device=kp4.device)
     run_ops(make_ops([op_diou_nms(kp4, order, offsets, keep, count, work, n_images, height, width, radius, iou_thresh)]))
     return keep, count
+
+
+def assemble_table(segments, n_rows: int, k: int, device) -> np.ndarray:
+    """The segment table of GIMS_AUX_ASSEMBLE_ROWS (include/gims_hip.h) as a host array int64 [n_seg, 4] = {source address, source pitch
+    in floats, rows, first destination row}, ascending by first destination row.  segments: (source f32 [rows, >= k] with unit stride along
+    the row, first destination row) each; the same source may appear any number of times.  Checks what the device cannot: dtype, layout,
+    alignment and device of every source, and that the destination ranges are disjoint and inside 0 .. n_rows - 1 (ValueError)."""
+    device = torch.device(device)
+    tab = np.empty((len(segments), 4), dtype=np.int64)
+    for s, (src, first) in enumerate(segments):
+        if src.dtype != torch.float32:
+            raise ValueError(f"assemble_rows: segment {s}: the source is {src.dtype}, not float32")
+        if src.dim() != 2 or src.shape[1] < k or (src.shape[1] > 1 and src.stride(1) != 1):
+            raise ValueError(f"assemble_rows: segment {s}: the source must be [rows, >= {k}] with unit stride along the row, got {tuple(src.shape)} / {src.stride()}")
+        if src.device != device and not (src.device.type == device.type and None in (src.device.index, device.index)):
+            raise ValueError(f"assemble_rows: segment {s}: the source is on {src.device}, the outputs on {device}")
+        pitch = src.stride(0) if src.shape[0] > 1 else max(src.stride(0), k)
+        if src.data_ptr() % 16 or pitch % 4 or pitch < 0:
+            raise ValueError(f"assemble_rows: segment {s}: the source must be 16-byte aligned with a row pitch that is a multiple of 4 floats")
+        if first < 0 or first + src.shape[0] > n_rows:
+            raise ValueError(f"assemble_rows: segment {s}: destination rows {first} .. {first + src.shape[0] - 1} lie outside the {n_rows} rows of the output")
+        tab[s] = (src.data_ptr(), pitch, src.shape[0], first)
+    tab = tab[np.argsort(tab[:, 3], kind="stable")]
+    ends = tab[:-1, 3] + tab[:-1, 2]
+    bad = np.nonzero(ends > tab[1:, 3])[0]
+    if len(bad):
+        raise ValueError(f"assemble_rows: the destination rows {tab[bad[0], 3]} .. {ends[bad[0]] - 1} and those from {tab[bad[0] + 1, 3]} on overlap")
+    return tab
+
+
+def op_assemble_rows(table, n_seg: int, n_rows: int, k: int, out, out_split) -> Op:
+    """GIMS_AUX_ASSEMBLE_ROWS as an op of gims_run_ops (include/gims_hip.h): the one way to reach it.  table: the device copy of
+    assemble_table's array; out f32 [n_rows, >= k] and / or out_split SPL32 bf16 [n_rows, >= 2 k]."""
+    return op_aux(AUX_ASSEMBLE_ROWS, (table, out, out_split), (n_seg, n_rows, k, 0 if out is None else out.stride(0),
+                                                               0 if out_split is None else out_split.stride(0), 0))
+
+
+def upload_large(arr: np.ndarray, device) -> torch.Tensor:
+    """upload() for a table of any size: in pieces of at most 1 MiB (what one gims_upload_table call takes) into one device buffer."""
+    a = np.ascontiguousarray(arr).reshape(-1)
+    raw = a.view(np.uint8)
+    step = 1 << 20
+    if raw.nbytes <= step:
+        return upload(arr, device)
+    buf = torch.empty(((raw.nbytes + 15) // 16 * 16 + 16,), dtype=torch.uint8, device=device)
+    for o in range(0, raw.nbytes, step):
+        upload(raw[o:o + step], device, out=buf[o:])
+    return buf[:raw.nbytes].view(_NP2TORCH[a.dtype.name]).view(arr.shape)
+
+
+def assemble_rows(segments, out, out_split, k: int):
+    """Fill rows of out (f32 [n_rows, >= k], or None) and out_split (its SPL32 copy, bf16 [n_rows, >= 2 k], or None) from stores of encoded
+    rows in ONE launch (csrc/features.hip): segments = [(source f32 [rows, >= k], first destination row)], see
+    assemble_table.  Rows that no segment covers are left as they are.  Asynchronous; returns what must stay alive until the launch has
+    run: the device table (the sources and outputs are the caller's)."""
+    ref = out if out is not None else out_split
+    if ref is None:
+        raise ValueError("assemble_rows: out and out_split are both None")
+    n_rows = ref.shape[0]
+    if out is not None and (out.dtype != torch.float32 or out.dim() != 2 or out.shape[1] < k or out.stride(1) != 1):
+        raise ValueError("assemble_rows: out must be float32 [n_rows, >= k] with unit stride along the row")
+    if out_split is not None and (out_split.dtype != torch.bfloat16 or out_split.dim() != 2 or out_split.shape[0] != n_rows or out_split.shape[1] < 2 * k
+                                  or out_split.stride(1) != 1):
+        raise ValueError("assemble_rows: out_split must be bfloat16 [n_rows, >= 2 k] with unit stride along the row")
+    tab = assemble_table(segments, n_rows, k, ref.device)
+    dev_tab = upload_large(tab, ref.device) if len(tab) else None
+    run_ops(make_ops([op_assemble_rows(dev_tab, len(tab), n_rows, k, out, out_split)]))
+    return dev_tab
 
 
 def patch_affine(kp4: torch.Tensor, kp_octave: torch.Tensor):

@@ -17,7 +17,7 @@ dict.  This shell does the same through a FRONT END, looked up in this order:
 """
 import torch
 
-from .gmatcher import GMatcher
+from .gmatcher import GMatcher, _ImageShape
 
 
 def _find_front_end(config):
@@ -66,6 +66,35 @@ class Matching(torch.nn.Module):
         pred, data = self._front(data)
         pred = {**pred, **self.gmodel(data)}
         return pred
+
+    def extract(self, data):
+        """Image sets: the front end runs ONCE over all images of ``data['image']`` (a batch ``[B, H, W, 3]`` or a list of
+        images), then ``GMatcher.encode_images`` encodes them in one pass -> one ``ImageFeatures`` per image for ``match_features``.
+        ``data``: ``{'image', 'carhynet', 'device', 'radius' / 'percentile' / 'min_size' / 'delaunay' (forward()'s defaults), optional
+        'diou_nms'}``; with ``'keypoints'`` / ``'descriptors'`` / ``'scores'`` lists (one tensor per image) already in it the front end is
+        skipped, as ``forward`` skips it per side.  ``data`` is not mutated."""
+        image = data['image']
+        imgs = list(image) if isinstance(image, (list, tuple)) else [image[b] for b in range(image.shape[0])]
+        if 'keypoints' in data:
+            pred = {k: data[k] for k in ('keypoints', 'descriptors', 'scores')}
+        else:
+            if self._front_end is None:
+                raise NotImplementedError("no 'keypoints' in data and no front end: pass config['front_end'] (a callable like "
+                                          "utils.common.sift_forward) or run where `utils.common.sift_forward` is importable")
+            pred = self._front_end({'image': image, 'max_keypoints': self.max_keypoints, 'carhynet': data.get('carhynet'),
+                                    **({'diou_nms': data['diou_nms']} if 'diou_nms' in data else {})}, device=data['device'])
+        if not (len(pred['keypoints']) == len(pred['descriptors']) == len(pred['scores']) == len(imgs)):
+            raise ValueError(f"extract: {len(imgs)} images, but keypoints / descriptors / scores of "
+                             f"{len(pred['keypoints'])} / {len(pred['descriptors'])} / {len(pred['scores'])}")
+        # (the matcher reads an image's shape the way forward() reads data['image0'].shape: with the batch axis in front)
+        items = [{'keypoints': pred['keypoints'][b], 'descriptors': pred['descriptors'][b], 'scores': pred['scores'][b],
+                  'image': _ImageShape(tuple(im.shape) if len(im.shape) == 4 else (1,) + tuple(im.shape))} for b, im in enumerate(imgs)]
+        return self.gmodel.encode_images(items, radius=data.get('radius', 25), percentile=data.get('percentile', 7),
+                                         min_size=data.get('min_size', 8), delaunay=bool(data.get('delaunay', False)))
+
+    def match_features(self, feats, pairs):
+        """``GMatcher.match_features``: the index pairs ``pairs`` over the features ``extract`` returned, in one batched pass."""
+        return self.gmodel.match_features(feats, pairs)
 
     def sweep(self, data, grid, **kwargs):
         """The pair of ``data`` under every graph setting of ``grid``: the front end (detection, patches, descriptors) runs ONCE, then

@@ -341,7 +341,34 @@ int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t
  * hold every partner, and relaxes statuses in rounds: an undecided keypoint is suppressed as soon as an earlier partner it does not
  * survive is kept, kept once all such partners are suppressed.  That reproduces the sequential rule exactly, in 2-6 rounds on detector
  * output or random points and in as many rounds as keypoints on a chain of overlapping boxes with descending scores.  The locality
- * argument needs the squares of the coordinates to be finite floats (|x|, |y|, size below 1e18). */
+ * argument needs the squares of the coordinates to be finite floats (|x|, |y|, size below 1e18).
+ *
+ * GIMS_AUX_ASSEMBLE_ROWS is the third function of this table without a stand-alone entry point, for the same reason.  It fills the two
+ * buffers the layer stage of a batch reads -- the residual stream, f32 [n_rows][k], and its SPL32 copy, bf16 [n_rows][2 k] -- from stores of
+ * already encoded rows (image-set matching, DESIGN.md 4.16: an image is encoded once and matched in many pairs; every pair entry needs its
+ * own copy of its images' rows because the layers update them in place).  kernel: assemble_rows_kernel, gims_amd/csrc/features.hip.
+ *   p[0] table     device int64 [n_seg][4] = {source address (const float*), source pitch in floats, rows, first destination row}, 8-byte
+ *                  aligned, ascending by first destination row, the destination ranges disjoint.  The same source may appear in any number
+ *                  of segments.  Row j < rows of a segment is the k floats at source + j * pitch and goes to destination row first + j.
+ *   p[1] out       float [n_rows][ld_out], or NULL
+ *   p[2] out_split SPL32 bf16 [n_rows][ld_split], or NULL.  At least one of the two is non-NULL.
+ *   i = {n_seg, n_rows, k, ld_out, ld_split, 0}
+ * Per element x = source[j * pitch + c], c < k: out[r][c] = x (the bits as they are); hi = bf16(x), round to nearest even (a NaN stays a
+ * NaN); lo = bf16(x - bf2f(hi)), the subtraction in float32; out_split[r][spl_col(c)] = hi and out_split[r][spl_col(c) + 32] = lo,
+ * spl_col(c) = 64 (c / 32) + c % 32: bit for bit what gims_split_spl32 and the epilogues of gims_linear write.
+ * GIMS_EINVAL before any HIP call, each with a message naming assemble_rows: a NULL table while n_seg > 0; both outputs NULL; n_seg or n_rows
+ * negative (or above 2^31 - 1); k <= 0 or k % 32 != 0; ld_out < k or ld_split < 2 k for a non-NULL output; an output that breaks the
+ * alignment rules of gims_linear's pre-split operands (out: 16-byte aligned, ld_out a multiple of 4; out_split: 128-byte aligned, ld_split a
+ * multiple of 64 below 2^22); a misaligned table; i[5] != 0.  i[5] is reserved for selecting a later form of the function and is checked before
+ * everything else: a non-zero value is refused as an unknown auxiliary function form of gims_run_ops (the message names both), whatever the
+ * other arguments hold.  n_seg == 0 or n_rows == 0 is GIMS_OK after the same checks and touches nothing.
+ * The source addresses and pitches live in device memory, so the CALLER guarantees them: every source row readable, 16-byte aligned addresses,
+ * pitches that are multiples of 4 (hip.assemble_rows checks this and the order and disjointness of the destinations on the host).
+ * On the device a segment is clipped to the rows 0 .. n_rows - 1 and a segment with rows <= 0 is skipped; a destination row that no segment
+ * covers is left as it was.  Nothing outside rows [0, n_rows) of either output is ever written, whatever the table holds (a table that is
+ * not ascending or not disjoint leaves unspecified rows inside that range).  One kernel whatever n_seg is (a wave finds the segment of its
+ * rows by a binary search over the first destination rows: scalar work, no thread per table entry); no host synchronisation; capturable by
+ * gims_ops_graph_create. */
 #define GIMS_OP_AUX 2
 #define GIMS_AUX_SPLIT_SPL32 0
 #define GIMS_AUX_SAGE_MEAN_SPLIT 1
@@ -351,6 +378,7 @@ int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t
 #define GIMS_AUX_LAYERNORM_ACT 5
 #define GIMS_AUX_SIFT_DESCRIBE 6
 #define GIMS_AUX_DIOU_NMS 7
+#define GIMS_AUX_ASSEMBLE_ROWS 8
 typedef struct gims_aux_args { int32_t fn, reserved; const void* p[6]; int64_t i[6]; float f[2]; } gims_aux_args;
 typedef struct gims_op { int32_t kind; int32_t reserved; union { gims_linear_args lin; gims_attn_args att; gims_aux_args aux; } u; } gims_op;
 int gims_run_ops(const gims_op* ops /* HOST */, int32_t n_ops, void* stream);
