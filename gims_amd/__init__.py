@@ -9,6 +9,7 @@ from .baselines import mnn, nn_match_pairs, nndr  # noqa: F401
 from .augment import ColorAug, ColorAugPlan  # noqa: F401
 from .verify import (epipolar_error, estimate_pose, find_fundamental, find_homography, pose_error, pose_summary,  # noqa: F401
                      verify_pairs)
+from .tracks import Tracks, build_tracks  # noqa: F401
 
 __all__ = ["GMatcher", "ImageFeatures", "Matching", "nndr", "mnn", "nn_match_pairs", "ColorAug", "ColorAugPlan", "find_homography", "find_fundamental", "verify_pairs",
-           "estimate_pose", "pose_error", "epipolar_error", "pose_summary"]
+           "estimate_pose", "pose_error", "epipolar_error", "pose_summary", "build_tracks", "Tracks"]

@@ -175,6 +175,8 @@ int sift_describe_aux(const gims_aux_args& x, hipStream_t st);
 int diou_nms_aux(const gims_aux_args& x, hipStream_t st);
 // features.hip: GIMS_AUX_ASSEMBLE_ROWS, likewise
 int assemble_rows_aux(const gims_aux_args& x, hipStream_t st);
+// tracks.hip: GIMS_AUX_BUILD_TRACKS, likewise
+int build_tracks_aux(const gims_aux_args& x, hipStream_t st);
 
 // sinkhorn2d.hip: the 2-D on-chip Sinkhorn (all iterations in one launch; see that file's header)
 struct OtR2Host { const float* z; int64_t ld; int n, m; float* u; float* v; float* status; float norm, log_mu_bin, log_nu_bin; };

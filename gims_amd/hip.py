@@ -67,6 +67,12 @@ AUX_SAGE_MEAN, AUX_KENC_FIRST_LINEAR, AUX_LAYERNORM_ACT = _K["GIMS_AUX_SAGE_MEAN
 AUX_SIFT_DESCRIBE = _K["GIMS_AUX_SIFT_DESCRIBE"]     # SIFT descriptors: reached through gims_run_ops only (no entry point of its own)
 AUX_DIOU_NMS = _K["GIMS_AUX_DIOU_NMS"]               # DIoU-NMS keypoint thinning: likewise
 AUX_ASSEMBLE_ROWS = _K["GIMS_AUX_ASSEMBLE_ROWS"]     # desc / dpl of a batch of pairs from per-image stores of encoded rows: likewise
+AUX_BUILD_TRACKS = _K["GIMS_AUX_BUILD_TRACKS"]       # multi-view tracks from the matches of an image set: likewise
+TRACKS_TABLE_WORDS, TRACKS_KEEP_CONFLICTING = _K["GIMS_TRACKS_TABLE_WORDS"], _K["GIMS_TRACKS_KEEP_CONFLICTING"]
+TRACKS_SCAN_TILE = _K["GIMS_TRACKS_SCAN_TILE"]           # elements per workgroup of the op's scans: N around its multiples are the seams
+TRACKS_SHORT_SEGMENT = _K["GIMS_TRACKS_SHORT_SEGMENT"]   # components up to this size are ranked by one lane, larger ones by a wave
+TRACKS_LONG_SEGMENT = _K["GIMS_TRACKS_LONG_SEGMENT"]     # ... and above max(this, N / 1024) -- tracks_huge(N) -- by a prefix count over the nodes
+TRACKS_COUNTERS = ("n_tracks", "n_obs", "n_conflicting", "n_edges", "n_bad", "status")      # the first words of the op's int32 [8] counters
 SIFT_MAX_OCTAVES, SIFT_MAX_RADIUS, SIFT_SLOTS = _K["GIMS_SIFT_MAX_OCTAVES"], _K["GIMS_SIFT_MAX_RADIUS"], _K["GIMS_SIFT_SLOTS"]
 
 
@@ -1165,6 +1171,94 @@ def assemble_rows(segments, out, out_split, k: int):
     dev_tab = upload_large(tab, ref.device) if len(tab) else None
     run_ops(make_ops([op_assemble_rows(dev_tab, len(tab), n_rows, k, out, out_split)]))
     return dev_tab
+
+
+def _same_device(t: torch.Tensor, device: torch.device) -> bool:
+    return t.device == device or (t.device.type == device.type and None in (t.device.index, device.index))
+
+
+def tracks_table(entries, counts, device) -> np.ndarray:
+    """The pair table of GIMS_AUX_BUILD_TRACKS (include/gims_hip.h) as a host array int64 [n_pairs + 1, 8] = {address of matches0, of the
+    scores or 0, of the mask or 0, n_a, n_b, start_a, start_b, first row}, the last entry holding the total number of rows.  entries:
+    (a, b, matches0, scores or None, mask or None) each -- image indices into counts (the keypoint count of every image) and 1-D contiguous
+    tensors of counts[a] elements, int64 / float32 / uint8.  Checks what the device cannot (ValueError): the indices, dtype, layout, length
+    and device of every tensor, and that all rows together stay below 2^31."""
+    device = torch.device(device)
+    counts = [int(c) for c in counts]
+    if any(c < 0 for c in counts):
+        raise ValueError("build_tracks: a keypoint count is negative")
+    start = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
+    tab = np.zeros((len(entries) + 1, TRACKS_TABLE_WORDS), dtype=np.int64)
+    row = 0
+    for p, (a, b, m0, sc, mask) in enumerate(entries):
+        if not (0 <= a < len(counts) and 0 <= b < len(counts)):
+            raise ValueError(f"build_tracks: pair {p}: the image index of ({a}, {b}) is out of range (0 .. {len(counts) - 1})")
+        for name, t, dt in (("matches0", m0, torch.int64), ("matching_scores0", sc, torch.float32), ("the inlier mask", mask, torch.uint8)):
+            if t is None and name != "matches0":
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != dt:
+                raise ValueError(f"build_tracks: pair {p}: {name} must be a {dt} tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+            if t.dim() != 1 or (t.numel() > 1 and t.stride(0) != 1):
+                raise ValueError(f"build_tracks: pair {p}: {name} must be 1-D with unit stride, got {tuple(t.shape)} / {t.stride()}")
+            if t.numel() != counts[a]:
+                raise ValueError(f"build_tracks: pair {p}: {name} has {t.numel()} elements, image {a} has {counts[a]} keypoints")
+            if not _same_device(t, device):
+                raise ValueError(f"build_tracks: pair {p}: {name} is on {t.device}, the outputs on {device}")
+        tab[p] = (m0.data_ptr(), 0 if sc is None else sc.data_ptr(), 0 if mask is None else mask.data_ptr(), counts[a], counts[b], start[a], start[b], row)
+        row += counts[a]
+    if row > 2 ** 31 - 1 or start[-1] > 2 ** 30:
+        raise ValueError(f"build_tracks: {row} rows / {start[-1]} keypoints in all: at most 2^31 - 1 rows and 2^30 keypoints")
+    tab[len(entries), TRACKS_TABLE_WORDS - 1] = row
+    return tab
+
+
+def tracks_work_bytes(n_pairs: int, n_images: int, n: int) -> int:
+    """The workspace of GIMS_AUX_BUILD_TRACKS for n keypoints in all: the formula of include/gims_hip.h (csrc/tracks.hip trk_layout carves
+    it).  It depends on neither n_pairs nor n_images: the pair table is read where it lies."""
+    al = lambda x: (x + 255) & ~255
+    return 12 * al(4 * n) + al(4 * (n // TRACKS_SCAN_TILE + 2)) + al(4 * (n // (tracks_huge(n) + 1) + 1) * (n // TRACKS_SCAN_TILE + 1)) + 256
+
+
+def tracks_huge(n: int) -> int:
+    """The component size above which GIMS_AUX_BUILD_TRACKS ranks a component by a prefix count over the nodes (H of include/gims_hip.h)."""
+    return max(TRACKS_LONG_SEGMENT, n // 1024)
+
+
+def tracks_out_layout(n: int):
+    """Word offsets into the int32 output buffer of GIMS_AUX_BUILD_TRACKS (include/gims_hip.h): (indptr, obs_image, obs_keypoint, conflict,
+    total words); conflict is uint8 [n // 2] packed into its words."""
+    cap_t = n // 2
+    return 0, cap_t + 1, cap_t + 1 + n, cap_t + 1 + 2 * n, cap_t + 1 + 2 * n + (cap_t + 3) // 4
+
+
+def op_build_tracks(table, start, track_of, out, counters, work, n_pairs: int, n_images: int, n: int, min_length: int = 2,
+                    keep_conflicting: bool = False, min_score: float = 0.0) -> Op:
+    """GIMS_AUX_BUILD_TRACKS as an op of gims_run_ops (include/gims_hip.h): the one way to reach it.  table: the device copy of
+    tracks_table's array; start int32 [n_images + 1]; track_of int32 [n]; out int32 [tracks_out_layout(n)[-1]]; counters int32 [8]; work
+    uint8 [tracks_work_bytes(...)]."""
+    return op_aux(AUX_BUILD_TRACKS, (table, start, track_of, out, counters, work),
+                  (n_pairs, n_images, n, int(min_length) | (TRACKS_KEEP_CONFLICTING if keep_conflicting else 0),
+                   0 if work is None else work.numel() * work.element_size(), 0), (min_score,))
+
+
+def build_tracks(entries, counts, device, min_length: int = 2, keep_conflicting: bool = False, min_score: float | None = None):
+    """Multi-view tracks from the matches of an image set on the device (csrc/tracks.hip): entries and counts as
+    tracks_table takes them; min_score None: no entry's scores are read.  -> (track_of int32 [N], out int32 -- see tracks_out_layout --,
+    counters int32 [8] -- TRACKS_COUNTERS --, start int32 [n_images + 1], and what must stay alive until the launches have run).
+    Asynchronous; no host read: the caller reads the counters to size its views."""
+    if min_score is None:
+        entries = [(a, b, m0, None, mask) for a, b, m0, _, mask in entries]
+    tab = tracks_table(entries, counts, device)
+    n_images, n = len(counts), int(sum(int(c) for c in counts))
+    start = upload(np.concatenate([[0], np.cumsum([int(c) for c in counts])]).astype(np.int32), device)
+    dev_tab = upload_large(tab, device)
+    track_of = torch.full((n,), -1, dtype=torch.int32, device=device)       # (the op leaves it alone when there is nothing to join)
+    out = torch.empty(tracks_out_layout(n)[-1], dtype=torch.int32, device=device)
+    counters = torch.empty(8, dtype=torch.int32, device=device)
+    work = torch.empty(tracks_work_bytes(len(entries), n_images, n), dtype=torch.uint8, device=device)
+    run_ops(make_ops([op_build_tracks(dev_tab, start, track_of, out, counters, work, len(entries), n_images, n, min_length, keep_conflicting,
+                                      0.0 if min_score is None else min_score)]))
+    return track_of, out, counters, start, (dev_tab, work, entries)
 
 
 def patch_affine(kp4: torch.Tensor, kp_octave: torch.Tensor):

@@ -368,7 +368,60 @@ int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t
  * covers is left as it was.  Nothing outside rows [0, n_rows) of either output is ever written, whatever the table holds (a table that is
  * not ascending or not disjoint leaves unspecified rows inside that range).  One kernel whatever n_seg is (a wave finds the segment of its
  * rows by a binary search over the first destination rows: scalar work, no thread per table entry); no host synchronisation; capturable by
- * gims_ops_graph_create. */
+ * gims_ops_graph_create.
+ *
+ * GIMS_AUX_BUILD_TRACKS is the fourth function of this table without a stand-alone entry point, for the same reason.  It merges the pairwise
+ * matches of a set of images (image-set matching) into multi-view tracks.  This library's own specification:
+ * the reference matches one pair and has no counterpart.  kernels: trk_*_kernel, gims_amd/csrc/tracks.hip.
+ *   Nodes.   Keypoint i of image k is node g = start[k] + i; start is the exclusive prefix of the keypoint counts, N = start[n_images].
+ *   Edges.   Row i < n_a of a pair (a, b) with j = matches0[i] is an edge {start_a + i, start_b + j} iff 0 <= j < n_b, and scores is NULL or
+ *            scores[i] >= min_score (a NaN score is no edge), and mask is NULL or mask[i] != 0.  j == -1 is "no match"; any other j outside
+ *            0 .. n_b - 1 is ignored and counted in n_bad, as is a row whose nodes fall outside 0 .. N - 1: such a value is never an index.
+ *            A pair may appear twice, in both directions, or with a == b (i == j is then a no-op that still counts as an accepted row).
+ *   Tracks.  The connected components with at least min_length nodes.  A component CONFLICTS when two of its nodes lie in one image; without
+ *            GIMS_TRACKS_KEEP_CONFLICTING the conflicting ones are dropped whole.  Tracks are numbered in ascending order of their smallest node,
+ *            a track's observations are listed in ascending node order: the result is a function of the edge SET alone.
+ *   p[0] table    device int64 [n_pairs + 1][GIMS_TRACKS_TABLE_WORDS], 8-byte aligned.  Entry p < n_pairs = {address of matches0 (const
+ *                 int64_t [n_a]), address of scores (const float [n_a]) or 0, address of mask (const uint8_t [n_a]) or 0, n_a, n_b, start_a,
+ *                 start_b, first row}; first row = the sum of n_a over the entries in front (entry 0: 0).  Entry n_pairs = seven zeros and
+ *                 the total number of rows, at most 2^31 - 1.
+ *   p[1] start    device int32 [n_images + 1], ascending from 0 to N
+ *   p[2] track_of int32 [N]: the track of every node, or -1
+ *   p[3] out      int32 [(N/2 + 1) + N + N + (N/2 + 3) / 4] (integer division): indptr [N/2 + 1] | obs_image [N] | obs_keypoint [N] | conflict, uint8 [N/2]
+ *                 packed.  With T tracks and n_obs observations the call writes indptr[0 .. T], obs_*[0 .. n_obs - 1] and conflict[0 .. T - 1]
+ *                 and nothing behind them.  Track t holds observations indptr[t] .. indptr[t + 1] - 1; conflict[t] is 1 for a conflicting track
+ *                 (never without GIMS_TRACKS_KEEP_CONFLICTING).
+ *   p[4] counters int32 [8] = {n_tracks, n_obs, n_conflicting, n_edges, n_bad, status, 0, 0}.  n_conflicting counts the conflicting components
+ *                 whatever the flag and min_length; n_edges the accepted rows, duplicates included.  status: 0, or non-zero when a row's bounded
+ *                 retry loop ran out (bit 0) or a parent chain was not descending (bit 1) -- neither can happen; the outputs are then unspecified
+ *                 (but inside their buffers) and the caller must not use them.
+ *   p[5] work     workspace, 16-byte aligned, of at least
+ *                   12 * al256(4 N) + al256(4 * (N / GIMS_TRACKS_SCAN_TILE + 2)) + al256(4 * (N / (H + 1) + 1) * (N / GIMS_TRACKS_SCAN_TILE + 1)) + 256
+ *                 bytes, H = max(GIMS_TRACKS_LONG_SEGMENT, N / 1024), al256(x) = (x + 255) & ~255, every division an integer division
+ *   i = {n_pairs, n_images, N, min_length | flags, work_bytes, 0}     f = {min_score}
+ *   min_length >= 2; the one flag is GIMS_TRACKS_KEEP_CONFLICTING.  min_score is read only by entries with scores.
+ * GIMS_EINVAL before any HIP call, each with a message naming build_tracks: n_pairs outside 0 .. 2^24; n_images outside 1 .. 2^24; N outside
+ * 0 .. 2^30; min_length outside 2 .. 2^24 or an unknown flag; a NaN min_score; a NULL start, out or counters; a NULL table while n_pairs > 0; a
+ * NULL track_of or work while N > 0; a misaligned table (8), start / track_of / out / counters (4) or work (16); work_bytes below the formula
+ * while N > 0; i[5] != 0.  i[5] is reserved for selecting a later form of the function and is checked before everything else: a non-zero value
+ * is refused as an unknown auxiliary function form of gims_run_ops (the message names both), whatever the other arguments hold.
+ * N == 0 or n_pairs == 0 is GIMS_OK after the same checks: it zeroes the counters, writes indptr[0] = 0 and touches nothing else (track_of
+ * included: a caller that wants its -1 writes them).
+ * The table lives in device memory, so the CALLER guarantees it: every matches0 / scores / mask readable for n_a elements, the first rows
+ * as stated (hip.tracks_table builds it).  What matches0 HOLDS is not trusted.  Nothing outside track_of, out, counters and work is ever
+ * written.  A linear sequence of memset nodes and kernels on the stream, the same whatever the data; no host synchronisation; capturable by
+ * gims_ops_graph_create.
+ * How it is computed.  A lock-free union-find over the rows of all pairs (a wave finds the pair of its 64 rows by binary search over the first
+ * rows) hooks the larger root under the smaller by compare-and-swap, so a component's root is its smallest node whatever the interleaving.
+ * Workgroups on different XCDs share parent[] in that launch: per-XCD L2s are not coherent and a CU's L1 is never refreshed by another CU's
+ * stores, so every access to parent[] there is an agent-scope atomic, and a row retries at most N times (a failed compare-and-swap means
+ * another hook succeeded, and there are at most N - 1).  Then, each a launch of its own: roots and component sizes; an exclusive scan of the
+ * sizes (three phases, tiles of GIMS_TRACKS_SCAN_TILE); members claim slots of their component's segment; every member's position is its rank
+ * by counting among the component's nodes -- one lane for a component of up to GIMS_TRACKS_SHORT_SEGMENT nodes, a wave for a larger one, s^2 / 64
+ * steps for s nodes -- which removes the order of the claims.  A component of more than H nodes (see work; wrong matches glue tracks into a
+ * few such components, and there are at most N / (H + 1) <= 1024 of them) is ranked by a prefix count over the nodes instead: members per
+ * scan tile, a scan of those counts, and the earlier nodes of the same component inside the tile -- linear in N whatever its size.  Scans of
+ * the keep flags and of the kept sizes give track numbers and indptr. */
 #define GIMS_OP_AUX 2
 #define GIMS_AUX_SPLIT_SPL32 0
 #define GIMS_AUX_SAGE_MEAN_SPLIT 1
@@ -379,6 +432,12 @@ int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t
 #define GIMS_AUX_SIFT_DESCRIBE 6
 #define GIMS_AUX_DIOU_NMS 7
 #define GIMS_AUX_ASSEMBLE_ROWS 8
+#define GIMS_AUX_BUILD_TRACKS 9
+#define GIMS_TRACKS_TABLE_WORDS 8
+#define GIMS_TRACKS_SCAN_TILE 2048
+#define GIMS_TRACKS_SHORT_SEGMENT 32
+#define GIMS_TRACKS_LONG_SEGMENT 1024
+#define GIMS_TRACKS_KEEP_CONFLICTING (1 << 30)
 typedef struct gims_aux_args { int32_t fn, reserved; const void* p[6]; int64_t i[6]; float f[2]; } gims_aux_args;
 typedef struct gims_op { int32_t kind; int32_t reserved; union { gims_linear_args lin; gims_attn_args att; gims_aux_args aux; } u; } gims_op;
 int gims_run_ops(const gims_op* ops /* HOST */, int32_t n_ops, void* stream);
