@@ -10,6 +10,8 @@ from .augment import ColorAug, ColorAugPlan  # noqa: F401
 from .verify import (epipolar_error, estimate_pose, find_fundamental, find_homography, pose_error, pose_summary,  # noqa: F401
                      verify_pairs)
 from .tracks import Tracks, build_tracks  # noqa: F401
+from .triangulate import Points3D, cameras_from_pose, triangulate_tracks  # noqa: F401
 
 __all__ = ["GMatcher", "ImageFeatures", "Matching", "nndr", "mnn", "nn_match_pairs", "ColorAug", "ColorAugPlan", "find_homography", "find_fundamental", "verify_pairs",
-           "estimate_pose", "pose_error", "epipolar_error", "pose_summary", "build_tracks", "Tracks"]
+           "estimate_pose", "pose_error", "epipolar_error", "pose_summary", "build_tracks", "Tracks",
+           "triangulate_tracks", "Points3D", "cameras_from_pose"]

@@ -73,6 +73,11 @@ TRACKS_SCAN_TILE = _K["GIMS_TRACKS_SCAN_TILE"]           # elements per workgrou
 TRACKS_SHORT_SEGMENT = _K["GIMS_TRACKS_SHORT_SEGMENT"]   # components up to this size are ranked by one lane, larger ones by a wave
 TRACKS_LONG_SEGMENT = _K["GIMS_TRACKS_LONG_SEGMENT"]     # ... and above max(this, N / 1024) -- tracks_huge(N) -- by a prefix count over the nodes
 TRACKS_COUNTERS = ("n_tracks", "n_obs", "n_conflicting", "n_edges", "n_bad", "status")      # the first words of the op's int32 [8] counters
+AUX_TRIANGULATE_TRACKS = _K["GIMS_AUX_TRIANGULATE_TRACKS"]   # robust multi-view triangulation of tracks from known cameras: likewise
+TRI_CAMERA_WORDS, TRI_MAX_OBS = _K["GIMS_TRI_CAMERA_WORDS"], _K["GIMS_TRI_MAX_OBS"]
+TRI_SHORT_TRACK = _K["GIMS_TRI_SHORT_TRACK"]             # tracks up to this length are served by that many lanes, up to 64 by a wave: the seams
+TRI_COUNTERS = ("n_ok", "n_low_angle", "n_no_model", "n_too_short", "n_too_long", "n_bad_obs", "n_inlier_obs")
+TRI_TOO_SHORT, TRI_NO_MODEL, TRI_LOW_ANGLE, TRI_TOO_LONG = 1, 2, 4, 8      # the bits of the op's per-track status
 SIFT_MAX_OCTAVES, SIFT_MAX_RADIUS, SIFT_SLOTS = _K["GIMS_SIFT_MAX_OCTAVES"], _K["GIMS_SIFT_MAX_RADIUS"], _K["GIMS_SIFT_SLOTS"]
 
 
@@ -1259,6 +1264,70 @@ def build_tracks(entries, counts, device, min_length: int = 2, keep_conflicting:
     run_ops(make_ops([op_build_tracks(dev_tab, start, track_of, out, counters, work, len(entries), n_images, n, min_length, keep_conflicting,
                                       0.0 if min_score is None else min_score)]))
     return track_of, out, counters, start, (dev_tab, work, entries)
+
+
+def triangulate_out_layout(T: int, n_obs: int) -> dict:
+    """BYTE offsets into the one buffer of GIMS_AUX_TRIANGULATE_TRACKS (include/gims_hip.h; csrc/triangulate.hip tri_layout carves it): xyz
+    float64 [T, 3], max_angle / rms_error float32 [T], n_inliers int32 [T], obs_error float32 [n_obs], status uint8 [T], obs_inlier uint8
+    [n_obs], counters int32 [8]; 'outputs' = the bytes of all of these, 'scratch' = the offset of the kernels' scratch behind them (the same
+    value), 'bytes' = the whole buffer.  Every region starts on a 256-byte boundary."""
+    al = lambda x: (x + 255) & ~255      # noqa: E731
+    off, at = {}, 0
+    for name, size in (("xyz", 24 * T), ("max_angle", 4 * T), ("rms_error", 4 * T), ("n_inliers", 4 * T), ("obs_error", 4 * n_obs), ("status", T),
+                       ("obs_inlier", n_obs), ("counters", 32)):
+        off[name] = at
+        at += al(size)
+    off["outputs"] = off["scratch"] = at
+    off["bytes"] = at + 2 * al(4 * T) + al(8)
+    return off
+
+
+def triangulate_cameras(K, R, t, counts) -> np.ndarray:
+    """The camera records of GIMS_AUX_TRIANGULATE_TRACKS as a host array float64 [n_images, 18] = {fx, fy, cx, cy, R row-major, t, first node,
+    n_k}: K [n, 3, 3], R [n, 3, 3], t [n, 3] (world to camera: x_c = R X + t) and the keypoint count of every image."""
+    K, R, t = (np.asarray(x, dtype=np.float64) for x in (K, R, t))
+    n = len(counts)
+    rec = np.zeros((n, TRI_CAMERA_WORDS), dtype=np.float64)
+    rec[:, 0], rec[:, 1], rec[:, 2], rec[:, 3] = K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2]
+    rec[:, 4:13], rec[:, 13:16] = R.reshape(n, 9), t.reshape(n, 3)
+    rec[:, 16] = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])[:-1]
+    rec[:, 17] = counts
+    return rec
+
+
+def op_triangulate_tracks(indptr, obs_image, obs_keypoint, kpts, cams, out, T: int, n_obs: int, n_images: int, n: int, thresh: float = 4.0,
+                          min_angle: float = 1.5, max_hyp: int = 64, refine_iters: int = 10) -> Op:
+    """GIMS_AUX_TRIANGULATE_TRACKS as an op of gims_run_ops (include/gims_hip.h): the one way to reach it.  indptr int32 [T + 1], obs_image /
+    obs_keypoint int32 [n_obs], kpts float32 [n, 2], cams float64 [n_images, 18], out uint8 [triangulate_out_layout(T, n_obs)['bytes']]."""
+    if not (0 <= int(max_hyp) <= 65535 and 0 <= int(refine_iters) <= 255):
+        raise ValueError(f"triangulate_tracks: max_hyp = {max_hyp} must be 0 .. 65535 and refine_iters = {refine_iters} 0 .. 255")
+    return op_aux(AUX_TRIANGULATE_TRACKS, (indptr, obs_image, obs_keypoint, kpts, cams, out),
+                  (T, n_obs, n_images, n, int(max_hyp) | (int(refine_iters) << 16), 0), (thresh, min_angle))
+
+
+def triangulate_views(out: torch.Tensor, T: int, n_obs: int) -> dict:
+    """The typed views of the op's buffer, by triangulate_out_layout."""
+    o = triangulate_out_layout(T, n_obs)
+    cut = lambda name, size, dt: out[o[name]:o[name] + size].view(dt)      # noqa: E731
+    return dict(xyz=cut("xyz", 24 * T, torch.float64).view(T, 3), max_angle=cut("max_angle", 4 * T, torch.float32),
+                rms_error=cut("rms_error", 4 * T, torch.float32), n_inliers=cut("n_inliers", 4 * T, torch.int32),
+                obs_error=cut("obs_error", 4 * n_obs, torch.float32), status=cut("status", T, torch.uint8),
+                obs_inlier=cut("obs_inlier", n_obs, torch.uint8), counters=cut("counters", 32, torch.int32))
+
+
+def triangulate_tracks(indptr, obs_image, obs_keypoint, kpts, cams: np.ndarray, thresh: float = 4.0, min_angle: float = 1.5, max_hyp: int = 64,
+                       refine_iters: int = 10):
+    """Robust triangulation of every track on the device (csrc/triangulate.hip): device tensors as op_triangulate_tracks takes
+    them, cams the HOST records of triangulate_cameras.  -> (the views of triangulate_views, and what must stay alive until the launches have
+    run).  Asynchronous; no host read."""
+    device = indptr.device
+    T, n_obs, n = indptr.numel() - 1, obs_image.numel(), kpts.shape[0]
+    rec = np.ascontiguousarray(cams, dtype=np.float64).reshape(-1, TRI_CAMERA_WORDS)
+    dev_cams = upload_large(rec.view(np.uint8).reshape(-1), device).view(torch.float64) if rec.size else torch.zeros(0, dtype=torch.float64, device=device)
+    out = torch.empty(triangulate_out_layout(T, n_obs)["bytes"], dtype=torch.uint8, device=device)
+    run_ops(make_ops([op_triangulate_tracks(indptr, obs_image, obs_keypoint, kpts, dev_cams, out, T, n_obs, len(rec), n, thresh, min_angle, max_hyp,
+                                            refine_iters)]))
+    return triangulate_views(out, T, n_obs), (dev_cams, out, indptr, obs_image, obs_keypoint, kpts)
 
 
 def patch_affine(kp4: torch.Tensor, kp_octave: torch.Tensor):

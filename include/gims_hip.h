@@ -421,7 +421,71 @@ int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t
  * steps for s nodes -- which removes the order of the claims.  A component of more than H nodes (see work; wrong matches glue tracks into a
  * few such components, and there are at most N / (H + 1) <= 1024 of them) is ranked by a prefix count over the nodes instead: members per
  * scan tile, a scan of those counts, and the earlier nodes of the same component inside the tile -- linear in N whatever its size.  Scans of
- * the keep flags and of the kept sizes give track numbers and indptr. */
+ * the keep flags and of the kept sizes give track numbers and indptr.
+ *
+ * GIMS_AUX_TRIANGULATE_TRACKS is the fifth function of this table without a stand-alone entry point, for the same reason.  It turns every track
+ * of a GIMS_AUX_BUILD_TRACKS result into a 3-D point from known cameras, robustly, and says which observations of the track agree with it
+ * (DESIGN.md 4.18).  This library's own specification: the reference matches one pair and has no counterpart.  kernels: tri_classify_kernel,
+ * tri_track_kernel, gims_amd/csrc/triangulate.hip; tests/triangulate_ref.py is the NumPy float64 restatement.  All arithmetic is float64.
+ *   p[0] indptr        device int32 [T + 1]; track t holds observations indptr[t] .. indptr[t + 1] - 1.  NOT trusted (below)
+ *   p[1] obs_image     device int32 [n_obs]
+ *   p[2] obs_keypoint  device int32 [n_obs]
+ *   p[3] kpts          float [N][2]: the pixel (u, v) of every keypoint of every image, the images back to back
+ *   p[4] cams          double [n_images][GIMS_TRI_CAMERA_WORDS], 8-byte aligned: {fx, fy, cx, cy, R row-major [9], t [3], first node, n_k}.  World
+ *                      to camera is x_c = R X + t (the convention of gims_verify_pairs' pose model: camera 0 = world gives x1 ~ R x0 + t).
+ *                      first node and n_k are the image's place in kpts (exact as doubles): keypoint i of image k is node first_k + i.
+ *   p[5] out           8-byte aligned, never NULL: one buffer, every region on a 256-byte boundary (al256(x) = (x + 255) & ~255), in this order:
+ *                        double xyz [T][3] | float max_angle [T] | float rms_error [T] | int32 n_inliers [T] | float obs_error [n_obs] |
+ *                        uint8 status [T] | uint8 obs_inlier [n_obs] | int32 counters [8] | scratch: int32 [T] | int32 [T] | int32 [2]
+ *                      that is al256(24 T) + 3 al256(4 T) + al256(4 n_obs) + al256(T) + al256(n_obs) + 256 bytes of outputs and
+ *                      2 al256(4 T) + 256 bytes of scratch behind them (hip.triangulate_out_layout has the offsets).
+ *                      counters = {n_ok, n_low_angle, n_no_model, n_too_short, n_too_long, n_bad_obs, n_inlier_obs, 0}.
+ *   i = {T, n_obs, n_images, N, max_hyp | refine_iters << 16, 0}     f = {thresh (pixels), min_angle (degrees)}
+ * Observation.  Observation o of a track is (image k, keypoint i) = (obs_image, obs_keypoint)[indptr[t] + o].  Its pixel (u, v) is
+ *   kpts[first_k + i] read as double, its ray d = R^T x / |x| with x = ((u - cx) / fx, (v - cy) / fy, 1), its centre C = -R^T t.  It is BAD when
+ *   k is outside 0 .. n_images - 1, i is outside 0 .. n_k - 1, first_k + i is outside 0 .. N - 1, u or v is not finite, or camera k is bad: one
+ *   of its 18 words is not finite, or fx <= 0, or fy <= 0.  A bad observation is ignored, counted in n_bad_obs and never used as an index;
+ *   its obs_error is -1 and its obs_inlier 0.  The other observations of the track, in track order, are its USABLE observations, L of them.
+ * Midpoint of a set S.  A = sum over S of (I - d d^T), b = sum of (I - d d^T) C; X = adj(A) b / det A by the cofactor formula of a symmetric
+ *   3 x 3 matrix: c00 = a11 a22 - a12^2, c01 = a02 a12 - a01 a22, c02 = a01 a12 - a02 a11, c11 = a00 a22 - a02^2, c12 = a01 a02 - a00 a12,
+ *   c22 = a00 a11 - a01^2, det = a00 c00 + a01 c01 + a02 c02.  DEGENERATE iff !(det > 1e-12 |S|^3); two rays at angle theta give det = 2 sin^2 theta.
+ * Reprojection.  x_c = R X + t, z = x_c[2], e^2 = (fx x_c[0] / z + cx - u)^2 + (fy x_c[1] / z + cy - v)^2; INLIER iff z > 0 and e^2 <= thresh^2
+ *   (thresh^2 is the float thresh squared in double).
+ * Angle at X between observations p and q: atan2(|a x b|, a . b) in degrees, a = X - C_p, b = X - C_q.
+ * Hypotheses, when max_hyp >= 1.  Number the pairs (p, q), p < q, of the usable observations lexicographically: E = L (L - 1) / 2 pairs.
+ *   H = min(E, max_hyp); hypothesis h < H is pair number floor(h E / H) in 64-bit integers (L == 2: the one pair).  Its X is the midpoint
+ *   of the two; it is INVALID when that solve is degenerate or the angle at X between the two is below min_angle.  Its score is the number
+ *   n_h of inliers among ALL usable observations and the sum c_h of their e^2.  The best hypothesis has the largest n_h, then the smallest c_h,
+ *   then the smallest h, and needs n_h >= 2; S is its inlier set.  max_hyp == 0: no hypothesis stage, S = every usable observation.
+ * Final model.  X = the midpoint of S (degenerate: NO_MODEL).  Then at most refine_iters rounds of Gauss-Newton on the cost sum over S of e^2:
+ *   with the 2 x 3 Jacobians J of the residuals r, (sum J^T J) s = -(sum J^T r) by the same cofactor solve; the round is TAKEN iff det > 0,
+ *   every observation of S has z > 0 at X + s and the cost at X + s is strictly below the cost at X; the first round that is not taken ends
+ *   the loop (a NaN anywhere refuses the round).  Then every usable observation is classified once at the final X: obs_inlier, obs_error =
+ *   sqrt(e^2) as float (-1 when z <= 0), n_inliers, rms_error = sqrt(sum of inlier e^2 / n_inliers).  max_angle is the largest angle at X
+ *   between two final inliers (the kernel takes the pair of the smallest cosine and evaluates the formula above on it).
+ * status, uint8 bits: 1 TOO_SHORT, L < 2 (or a bad indptr range); 2 NO_MODEL, no valid hypothesis with two inliers, a degenerate final solve,
+ *   or the final inliers are fewer than two or all lie in one image; 4 LOW_ANGLE, max_angle < min_angle; 8 TOO_LONG, more than GIMS_TRI_MAX_OBS
+ *   observations (bad ones included): the track is not processed, which bounds the cost of a track (such a track can only come from
+ *   GIMS_TRACKS_KEEP_CONFLICTING).  A track with status 0 or LOW_ANGLE has a model: xyz, max_angle, rms_error, n_inliers and the obs_* of its
+ *   usable observations are as above.  A track with any other status has none: xyz, max_angle, rms_error and n_inliers are zero, and all its
+ *   observations have obs_error -1 and obs_inlier 0.  Every output of every track is written by every call; no output is ever a NaN.
+ *   n_bad_obs counts over the tracks with a good range and at most GIMS_TRI_MAX_OBS observations; n_inlier_obs is the sum of n_inliers.
+ * GIMS_EINVAL before any HIP call, each with a message naming triangulate_tracks: T, n_obs or N outside 0 .. 2^30; n_images outside 0 .. 2^24;
+ * i[4] negative or refine_iters above 255 (max_hyp is its low 16 bits: 0 .. 65535); thresh not finite or <= 0; min_angle not finite or outside
+ * [0, 180); a NULL out; any other NULL pointer while T > 0; cams or out not 8-byte aligned, another pointer not 4-byte aligned; i[5] != 0.  i[5]
+ * is reserved for selecting a later form of the function and is checked before everything else: a non-zero value is refused as an unknown
+ * auxiliary function form of gims_run_ops (the message names both), whatever the other arguments hold.  T == 0 is GIMS_OK after the same
+ * checks and writes the counters only.
+ * indptr lives in device memory and is not trusted: a track whose range is descending or leaves 0 .. n_obs is TOO_SHORT and touches no
+ * observation.  (Ranges that overlap are each processed; the slots they share hold the result of one of them.)  Nothing outside out is written.
+ * A fixed sequence of memset nodes and four launches, the same whatever the data; no host synchronisation; capturable by
+ * gims_ops_graph_create.
+ * How it is computed.  A thread per track checks the range, writes the tracks that are not processed and appends the others to a list per
+ * class.  A track of up to GIMS_TRI_SHORT_TRACK observations is served by a group of that many lanes (sixteen tracks a wave), one of up to 64 by a
+ * wave, both with one observation per lane held in registers; a longer one by a wave that walks the observations in slots of 64.  Rays and
+ * centres are computed once per track and staged in LDS.  Every sum over observations is the lane's own sum in ascending order, then a
+ * butterfly over the group's lanes; there are no float atomics, and the group size depends on the track's length alone, so the outputs of a track
+ * are bit-identical alone or inside any batch, at any position, and across runs.  Counters are integer atomics, summed per workgroup first. */
 #define GIMS_OP_AUX 2
 #define GIMS_AUX_SPLIT_SPL32 0
 #define GIMS_AUX_SAGE_MEAN_SPLIT 1
@@ -438,6 +502,10 @@ int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t
 #define GIMS_TRACKS_SHORT_SEGMENT 32
 #define GIMS_TRACKS_LONG_SEGMENT 1024
 #define GIMS_TRACKS_KEEP_CONFLICTING (1 << 30)
+#define GIMS_AUX_TRIANGULATE_TRACKS 10
+#define GIMS_TRI_CAMERA_WORDS 18
+#define GIMS_TRI_MAX_OBS 1024
+#define GIMS_TRI_SHORT_TRACK 4
 typedef struct gims_aux_args { int32_t fn, reserved; const void* p[6]; int64_t i[6]; float f[2]; } gims_aux_args;
 typedef struct gims_op { int32_t kind; int32_t reserved; union { gims_linear_args lin; gims_attn_args att; gims_aux_args aux; } u; } gims_op;
 int gims_run_ops(const gims_op* ops /* HOST */, int32_t n_ops, void* stream);
