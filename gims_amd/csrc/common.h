@@ -163,6 +163,7 @@ void* pinned_once(const char* key, size_t bytes);
 int current_device();
 int device_cus();        // compute units of the current device (>= 8)
 // linear6.hip: exact-class bf16x6 GEMM on SPL3 operands (batched), and its operand split
+void count_linear_launch(int kind);      // linear.hip: gims_linear_launch_counts (GIMS_LINEAR_KERNEL_*), bumped at the launch site
 int linear_x6_batch_launch(const gims_linear_args* dev_args, int count, int max_m, int max_n, hipStream_t s);
 int split_spl3_launch(const float* src, int64_t lds, uint16_t* dst, int64_t ldd, int64_t rows, int k, hipStream_t s);
 

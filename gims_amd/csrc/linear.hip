@@ -15,6 +15,8 @@
 
 #include <stdlib.h>
 
+#include <atomic>
+
 namespace gims {
 
 constexpr int BM = 128, BN = 128;
@@ -670,13 +672,43 @@ static int linear_validate(const gims_linear_args* a) {
   return GIMS_OK;
 }
 
+// which kernel instance served a launch, counted per process (gims_linear_launch_counts: the instance tests assert that a shape ran on the
+// instance it is meant to pin)
+namespace gims {
+static std::atomic<uint64_t> g_linear_launch_counts[GIMS_LINEAR_KERNEL_KINDS];
+void count_linear_launch(int kind) { g_linear_launch_counts[kind].fetch_add(1, std::memory_order_relaxed); }
+}  // namespace gims
+
+// the census kind of a pre-split instance; an instantiation without a kind does not compile
+template <int TM, int TN, int WM, int WN, int S, bool HI_ONLY, bool WALK>
+constexpr int x3p_kind() {
+  constexpr int W = WM * WN;
+  if (WALK) return TM == 256 && TN == 256 && W == 8 && S == 2 && !HI_ONLY ? GIMS_LINEAR_KERNEL_X3P_256X256_W8_S2_WALK : -1;
+  if (HI_ONLY) {
+    if (TM == 64 && TN == 64 && W == 4 && S == 4) return GIMS_LINEAR_KERNEL_X3P_64X64_W4_S4_HI;
+    if (TM == 128 && TN == 128 && W == 4 && S == 4) return GIMS_LINEAR_KERNEL_X3P_128X128_W4_S4_HI;
+    if (TM == 256 && TN == 128 && W == 8 && S == 3) return GIMS_LINEAR_KERNEL_X3P_256X128_W8_S3_HI;
+    if (TM == 256 && TN == 128 && W == 8 && S == 2) return GIMS_LINEAR_KERNEL_X3P_256X128_W8_S2_HI;
+    if (TM == 256 && TN == 256 && W == 8 && S == 4) return GIMS_LINEAR_KERNEL_X3P_256X256_W8_S4_HI;
+    return -1;
+  }
+  if (TM == 64 && TN == 64 && W == 4 && S == 3) return GIMS_LINEAR_KERNEL_X3P_64X64_W4_S3;
+  if (TM == 128 && TN == 32 && W == 4 && S == 2) return GIMS_LINEAR_KERNEL_X3P_128X32_W4_S2;
+  if (TM == 128 && TN == 64 && W == 4 && S == 2) return GIMS_LINEAR_KERNEL_X3P_128X64_W4_S2;
+  if (TM == 128 && TN == 128 && W == 8 && S == 2) return GIMS_LINEAR_KERNEL_X3P_128X128_W8_S2;
+  if (TM == 128 && TN == 128 && W == 4 && S == 2) return GIMS_LINEAR_KERNEL_X3P_128X128_W4_S2;
+  if (TM == 256 && TN == 256 && W == 8 && S == 2) return GIMS_LINEAR_KERNEL_X3P_256X256_W8_S2;
+  return -1;
+}
+
 // The register-staged bf16x3 kernels (one problem / a batch of them) share one geometry: 256 threads, four operand planes of LDS.
 template <typename K, typename A>
-static int x3_launch(K kernel, dim3 grid, const A& args, hipStream_t s) {
+static int x3_launch(K kernel, dim3 grid, const A& args, hipStream_t s, int kind) {
   using namespace gims;
   constexpr int lds = 4 * X3_PLANE * (int)sizeof(uint16_t);
   GIMS_LDS_ATTR((const void*)kernel, lds);
   hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, args);
+  count_linear_launch(kind);
   GIMS_LAUNCH_CHECK();
   return GIMS_OK;
 }
@@ -702,6 +734,9 @@ static int x3p_launch(const gims_linear_args& a, hipStream_t s) {
     GIMS_LDS_ATTR((const void*)linear_x3p_kernel<TM, TN, WM, WN, S, HI_ONLY>, lds);
     hipLaunchKernelGGL((linear_x3p_kernel<TM, TN, WM, WN, S, HI_ONLY>), dim3(n_tiles), dim3(block), lds, s, a);
   }
+  constexpr int kind = x3p_kind<TM, TN, WM, WN, S, HI_ONLY, WALK>();
+  static_assert(kind >= 0 && kind < GIMS_LINEAR_KERNEL_KINDS, "every pre-split instance has a GIMS_LINEAR_KERNEL_* kind");
+  count_linear_launch(kind);
   GIMS_LAUNCH_CHECK();
   return GIMS_OK;
 }
@@ -714,8 +749,9 @@ extern "C" int gims_linear(const gims_linear_args* a, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid(cdiv(a->n, BN), cdiv(a->m, BM));
   if (!a->a0_lo) {
-    if (a->precision == GIMS_PREC_BF16X3) return x3_launch(linear_bf16x3_kernel, grid, *a, s);
+    if (a->precision == GIMS_PREC_BF16X3) return x3_launch(linear_bf16x3_kernel, grid, *a, s, GIMS_LINEAR_KERNEL_BF16X3);
     hipLaunchKernelGGL(linear_f32_kernel, grid, dim3(256), 0, s, *a);
+    count_linear_launch(GIMS_LINEAR_KERNEL_F32);
     GIMS_LAUNCH_CHECK();
     return GIMS_OK;
   }
@@ -781,12 +817,21 @@ extern "C" int gims_linear_batch(const gims_linear_args* dev_args, int32_t count
     return linear_x6_batch_launch(dev_args, count, max_m, max_n, s);
   } else if (precision == GIMS_PREC_F32) {
     hipLaunchKernelGGL(linear_f32_batch_kernel, grid, dim3(256), 0, s, dev_args);
+    count_linear_launch(GIMS_LINEAR_KERNEL_F32_BATCH);
   } else if (precision == GIMS_PREC_BF16X3) {
-    return x3_launch(linear_bf16x3_batch_kernel, grid, dev_args, s);
+    return x3_launch(linear_bf16x3_batch_kernel, grid, dev_args, s, GIMS_LINEAR_KERNEL_BF16X3_BATCH);
   } else {
     GIMS_CHECK_ARG(false, "gims_linear_batch: unknown precision %d", precision);
   }
   GIMS_LAUNCH_CHECK();
+  return GIMS_OK;
+}
+
+extern "C" int gims_linear_launch_counts(uint64_t* counts, int32_t n, int32_t reset) {
+  GIMS_CHECK_ARG(counts || n == 0, "gims_linear_launch_counts: null pointer");
+  for (int i = 0; i < n && i < GIMS_LINEAR_KERNEL_KINDS; ++i) counts[i] = gims::g_linear_launch_counts[i].load(std::memory_order_relaxed);
+  for (int i = GIMS_LINEAR_KERNEL_KINDS; i < n; ++i) counts[i] = 0;
+  if (reset) for (auto& c : gims::g_linear_launch_counts) c.store(0, std::memory_order_relaxed);
   return GIMS_OK;
 }
 

@@ -222,6 +222,7 @@ int linear_x6_batch_launch(const gims_linear_args* dev_args, int count, int max_
   GIMS_CHECK_ARG(count >= 1 && count <= X6_MAX_PROBLEMS, "gims_linear_batch(bf16x6): at most %d problems per launch", X6_MAX_PROBLEMS);
   const int64_t bound = (int64_t)cdiv(max_n, X6_TN) * cdiv(max_m, X6_TM) * count;      // workgroups beyond the tile list exit at once
   hipLaunchKernelGGL(linear_x6_kernel, dim3((int)(bound < 256 ? bound : 256)), dim3(512), X6_LDS_BYTES + X6_TABLE_BYTES, s, dev_args, count);
+  count_linear_launch(GIMS_LINEAR_KERNEL_X6_BATCH);
   GIMS_LAUNCH_CHECK();
   return GIMS_OK;
 }

@@ -661,6 +661,19 @@ def attention_launch_counts(reset: bool = False) -> dict:
     return dict(zip(ATTN_KERNEL_KINDS, (int(x) for x in buf)))
 
 
+# GIMS_LINEAR_KERNEL_* of the header, in value order, under their lower-case names ("f32", "x6_batch", "x3p_128x128_w4_s2", ...)
+LINEAR_KERNEL_NAMES = tuple(k[len("GIMS_LINEAR_KERNEL_"):].lower() for k, _ in sorted(
+    ((k, v) for k, v in _K.items() if k.startswith("GIMS_LINEAR_KERNEL_") and k != "GIMS_LINEAR_KERNEL_KINDS"), key=lambda kv: kv[1]))
+assert len(LINEAR_KERNEL_NAMES) == _K["GIMS_LINEAR_KERNEL_KINDS"]
+
+
+def linear_launch_counts(reset: bool = False) -> dict:
+    """GEMM launches of this process per kernel instance since the last reset (include/gims_hip.h GIMS_LINEAR_KERNEL_*)."""
+    buf = (C.c_uint64 * len(LINEAR_KERNEL_NAMES))()
+    _check(load().gims_linear_launch_counts(buf, len(LINEAR_KERNEL_NAMES), int(reset)), "gims_linear_launch_counts")
+    return dict(zip(LINEAR_KERNEL_NAMES, (int(x) for x in buf)))
+
+
 def sinkhorn_rescues() -> int:
     """On-chip solves of this process that gave up and were re-solved by a rescue path on the current device (synchronises)."""
     n = int(load().gims_sinkhorn_rescues())

@@ -147,6 +147,31 @@ int gims_split_bf16(const float* src, uint16_t* hi, uint16_t* lo, int64_t n, voi
 int gims_split_spl3(const float* src, int64_t lds, uint16_t* dst, int64_t ldd, int64_t rows, int32_t k, void* stream);
 int gims_split_spl32(const float* src, int64_t lds, uint16_t* dst, int64_t ldd, int64_t rows, int32_t k, void* stream);
 
+/* Which kernel instance served the gims_linear / gims_linear_batch launches of this process so far (host-side counters, one per instance;
+ * thread-safe): counts[k] for k < min(n, GIMS_LINEAR_KERNEL_KINDS), the rest zero; reset != 0 clears them afterwards.  gims_linear picks
+ * the pre-split instance from the launch shape (tile geometry, waves and ring stages: X3P_<rows>x<cols>_W<waves>_S<stages>, HI = the
+ * one-pass GIMS_LINEAR_HI_ONLY body): the instance tests use this to assert that a shape reached the instance it is meant to pin.
+ * Test / diagnostic hook. */
+#define GIMS_LINEAR_KERNEL_F32 0                      /* linear_f32_kernel: register-staged exact-f32 MFMA */
+#define GIMS_LINEAR_KERNEL_BF16X3 1                   /* linear_bf16x3_kernel: register-staged, A split on the fly */
+#define GIMS_LINEAR_KERNEL_F32_BATCH 2                /* linear_f32_batch_kernel (gims_linear_batch) */
+#define GIMS_LINEAR_KERNEL_BF16X3_BATCH 3             /* linear_bf16x3_batch_kernel (gims_linear_batch) */
+#define GIMS_LINEAR_KERNEL_X6_BATCH 4                 /* linear_x6_kernel: the persistent six-pass GEMM (gims_linear_batch) */
+#define GIMS_LINEAR_KERNEL_X3P_64X64_W4_S3 5          /* pre-split: launches of at most 128 tiles of 128 x 128 */
+#define GIMS_LINEAR_KERNEL_X3P_64X64_W4_S4_HI 6
+#define GIMS_LINEAR_KERNEL_X3P_128X32_W4_S2 7         /* n <= 32 */
+#define GIMS_LINEAR_KERNEL_X3P_128X64_W4_S2 8         /* n <= 64 */
+#define GIMS_LINEAR_KERNEL_X3P_128X128_W8_S2 9        /* up to 256 tiles: one per CU on eight waves */
+#define GIMS_LINEAR_KERNEL_X3P_128X128_W4_S2 10       /* more than 256 tiles */
+#define GIMS_LINEAR_KERNEL_X3P_128X128_W4_S4_HI 11
+#define GIMS_LINEAR_KERNEL_X3P_256X256_W8_S2 12       /* at least 192 tiles of 256 x 256 */
+#define GIMS_LINEAR_KERNEL_X3P_256X256_W8_S2_WALK 13  /* the same behind a guard, one round of workgroups that walk the tiles */
+#define GIMS_LINEAR_KERNEL_X3P_256X128_W8_S3_HI 14    /* the one-pass Q/K/V projection */
+#define GIMS_LINEAR_KERNEL_X3P_256X128_W8_S2_HI 15    /* GIMS_X3P_QKV=2 only */
+#define GIMS_LINEAR_KERNEL_X3P_256X256_W8_S4_HI 16    /* GIMS_X3P_QKV=0 only */
+#define GIMS_LINEAR_KERNEL_KINDS 17
+int gims_linear_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t reset);
+
 /* ------------------------------------------------------------------------------------------------
  * Multi-head attention message   O = softmax(Q K^T / sqrt(dh)) V   per head, flash-style.
  * replaces: attention() + the head view of MultiHeadedAttention.forward (gmatcher.py:35-39,109-113).

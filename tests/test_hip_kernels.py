@@ -160,7 +160,9 @@ def test_linear_bf16x6(hip, shapes, k, upper):
     for (m, n), (a, w, out, _, _) in zip(shapes, keep):
         ref = a.astype(np.float64) @ w.astype(np.float64).T * 0.5
         scale_ref = np.abs(a).astype(np.float64) @ np.abs(w).astype(np.float64).T * 0.5
-        o = out.cpu().numpy()[:, :n]
+        o = out.cpu().numpy()
+        assert np.isnan(o[:, n:]).all(), f"{m}x{n}: a pad column of the output (ld {o.shape[1]}) was written"
+        o = o[:, :n]
         err = np.abs(o - ref) / scale_ref
         if upper:
             err = err[np.triu_indices(m, 1, n)]
@@ -473,7 +475,10 @@ def test_guarded_launches_that_walk_their_tiles(hip, monkeypatch, fires):
         stat.copy_(torch.from_numpy(st))
         qkv6 = torch.full((rows, 1536), sentinel, dtype=torch.int16, device="cuda").view(torch.bfloat16)
         msg = torch.full((rows, 512), sentinel, dtype=torch.int16, device="cuda").view(torch.bfloat16)
+        hip.linear_launch_counts(reset=True)
         hip.linear(xs, ws, out_split=qkv6, precision=hip.PREC_BF16X3, spl=True, guard=guard)
+        # the launch census: the walked instance, or under GIMS_GUARD_WALK=0 the full grid of the same 256 x 256 tile
+        assert {k: v for k, v in hip.linear_launch_counts().items() if v} == {"x3p_256x256_w8_s2_walk" if walk == "1" else "x3p_256x256_w8_s2": 1}
         hip.attention(qkv6, pr, n, H, None, out_split=msg, x3=True, q_prescaled=True, guard=guard)
         assert int(stat.cpu().numpy()[H, 3]) == int(fires)
         outs[walk] = (qkv6.view(torch.int16).clone(), msg.view(torch.int16).clone())
