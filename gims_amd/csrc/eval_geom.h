@@ -1,7 +1,8 @@
 // Device helpers of the homography estimation shared by csrc/eval.hip (evaluation against a ground truth) and csrc/verify.hip
 // (ground-truth-free verification): the float64 elimination, the 4-point model, the reprojection error, the sampler of the
 // specification in include/gims_hip.h and the corner error.  Both files score and refit with these very functions, so that the same
-// inputs give the same model in either entry point.
+// inputs give the same model in either entry point.  Also here: the polynomial product and evaluation that the five-point solver of
+// verify.hip and the P3P solver of csrc/resect.hip share (resect.hip takes the sampler from here as well).
 #pragma once
 #include "common.h"
 
@@ -104,6 +105,20 @@ __device__ void ransac_sample(uint64_t seed, int hyp, int k, int (&idx)[N]) {
     for (int q = 0; q < n; ++q) dup = dup || idx[q] == c;
     if (!dup) idx[n++] = c;
   }
+}
+
+// ---------------------------------------------------------------------------------------------- polynomials (ascending coefficients)
+// shared by the five-point solver of verify.hip and the P3P solver of resect.hip
+// out (na + nb - 1 coefficients, ascending) = a * b
+__device__ void vp_pmul(const double* a, int na, const double* b, int nb, double* out) {
+  for (int i = 0; i < na + nb - 1; ++i) out[i] = 0.0;
+  for (int i = 0; i < na; ++i)
+    for (int j = 0; j < nb; ++j) out[i + j] += a[i] * b[j];
+}
+__device__ __forceinline__ double vp_horner(const double* c, int deg, double z) {
+  double v = c[deg];
+  for (int i = deg - 1; i >= 0; --i) v = v * z + c[i];
+  return v;
 }
 
 }  // namespace gims

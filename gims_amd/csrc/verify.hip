@@ -874,17 +874,7 @@ __device__ __forceinline__ void vp_ql(const double (&q)[10], const double* l, do
 #pragma unroll
       for (int k = 0; k < 4; ++k) row[vp_col(i, j, k)] += s * (q[vp_qi(i, j)] * l[k]);
 }
-// out (na + nb - 1 coefficients, ascending) = a * b
-__device__ void vp_pmul(const double* a, int na, const double* b, int nb, double* out) {
-  for (int i = 0; i < na + nb - 1; ++i) out[i] = 0.0;
-  for (int i = 0; i < na; ++i)
-    for (int j = 0; j < nb; ++j) out[i + j] += a[i] * b[j];
-}
-__device__ __forceinline__ double vp_horner(const double* c, int deg, double z) {
-  double v = c[deg];
-  for (int i = deg - 1; i >= 0; --i) v = v * z + c[i];
-  return v;
-}
+// (vp_pmul and vp_horner, the polynomial product and evaluation, live in eval_geom.h: csrc/resect.hip uses them too)
 
 // the real roots of the degree-10 polynomial c (ascending coefficients), ascending, by bisection between the roots of successive
 // derivatives inside the bound 1 + max |c_i / c_10|; -1 when c_10 is 0 or anything is not finite

@@ -78,6 +78,10 @@ TRI_CAMERA_WORDS, TRI_MAX_OBS = _K["GIMS_TRI_CAMERA_WORDS"], _K["GIMS_TRI_MAX_OB
 TRI_SHORT_TRACK = _K["GIMS_TRI_SHORT_TRACK"]             # tracks up to this length are served by that many lanes, up to 64 by a wave: the seams
 TRI_COUNTERS = ("n_ok", "n_low_angle", "n_no_model", "n_too_short", "n_too_long", "n_bad_obs", "n_inlier_obs")
 TRI_TOO_SHORT, TRI_NO_MODEL, TRI_LOW_ANGLE, TRI_TOO_LONG = 1, 2, 4, 8      # the bits of the op's per-track status
+AUX_RESECT_IMAGES = _K["GIMS_AUX_RESECT_IMAGES"]             # absolute poses from 2-D to 3-D matches (resection): likewise
+RESECT_CAMERA_WORDS = _K["GIMS_RESECT_CAMERA_WORDS"]
+RESECT_HB = _K["GIMS_RESECT_HB"]                             # hypotheses per workgroup of the scoring kernel: the seam of `iters`
+RESECT_COUNTERS = ("n_ok", "n_failed", "n_corr_total", "n_inlier_total")
 SIFT_MAX_OCTAVES, SIFT_MAX_RADIUS, SIFT_SLOTS = _K["GIMS_SIFT_MAX_OCTAVES"], _K["GIMS_SIFT_MAX_RADIUS"], _K["GIMS_SIFT_SLOTS"]
 
 
@@ -1341,6 +1345,87 @@ def triangulate_tracks(indptr, obs_image, obs_keypoint, kpts, cams: np.ndarray, 
     run_ops(make_ops([op_triangulate_tracks(indptr, obs_image, obs_keypoint, kpts, dev_cams, out, T, n_obs, len(rec), n, thresh, min_angle, max_hyp,
                                             refine_iters)]))
     return triangulate_views(out, T, n_obs), (dev_cams, out, indptr, obs_image, obs_keypoint, kpts)
+
+
+def resect_cameras(K, counts, which=None) -> np.ndarray:
+    """The entry records of GIMS_AUX_RESECT_IMAGES as a host array float64 [m, 6] = {fx, fy, cx, cy, first node, n_k}: K [n, 3, 3] and the
+    keypoint count of every image of the set, which = the images to resect in the caller's order (default: all of them)."""
+    K = np.asarray(K, dtype=np.float64).reshape(-1, 3, 3)
+    start = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
+    which = np.arange(len(counts), dtype=np.int64) if which is None else np.asarray(which, dtype=np.int64).reshape(-1)
+    rec = np.zeros((len(which), RESECT_CAMERA_WORDS), dtype=np.float64)
+    rec[:, 0], rec[:, 1], rec[:, 2], rec[:, 3] = K[which, 0, 0], K[which, 1, 1], K[which, 0, 2], K[which, 1, 2]
+    rec[:, 4], rec[:, 5] = start[which], np.asarray(counts, dtype=np.int64)[which]
+    return rec
+
+
+def _resect_slots(cams) -> np.ndarray:
+    rec = np.asarray(cams, dtype=np.float64).reshape(-1, RESECT_CAMERA_WORDS)
+    n_k = rec[:, 5]
+    if len(rec) and not (np.isfinite(n_k).all() and (n_k >= 0).all() and (n_k <= 2 ** 30).all() and (n_k == np.floor(n_k)).all() and n_k.sum() <= 2 ** 30):
+        raise ValueError("resect_images: every n_k must be an integer in 0 .. 2^30, and their sum at most 2^30")
+    return np.concatenate([[0], np.cumsum(n_k.astype(np.int64))])
+
+
+def resect_out_layout(cams, iters: int = 0) -> dict:
+    """BYTE offsets into the one buffer of GIMS_AUX_RESECT_IMAGES (include/gims_hip.h; csrc/resect.hip rs_layout carves it) for the host
+    records cams [m, 6]: pose float64 [m, 12], n_corr / ok / n_inliers / best_hyp / best_hyp_inliers / lo_rounds int32 [m], rms_error float32
+    [m], kp_inlier uint8 [S], kp_error float32 [S], counters int32 [8], S = the sum of n_k; 'outputs' = the bytes of all of these = 'scratch',
+    the offset of the kernels' scratch (which holds iters counters per entry), 'bytes' = the whole buffer; 'slots' = the m + 1 offsets of
+    the entries in kp_inlier / kp_error.  Every region starts on a 256-byte boundary."""
+    al = lambda x: (x + 255) & ~255      # noqa: E731
+    slots = _resect_slots(cams)
+    m, S = len(slots) - 1, int(slots[-1])
+    off, at = {}, 0
+    for name, size in (("pose", 96 * m), ("n_corr", 4 * m), ("ok", 4 * m), ("n_inliers", 4 * m), ("best_hyp", 4 * m), ("best_hyp_inliers", 4 * m),
+                       ("lo_rounds", 4 * m), ("rms_error", 4 * m), ("kp_inlier", S), ("kp_error", 4 * S), ("counters", 32)):
+        off[name] = at
+        at += al(size)
+    off["outputs"] = off["scratch"] = at
+    off["bytes"] = at + al(56 * m) + al(48 * S) + al(4 * m * int(iters))
+    off["slots"] = [int(s) for s in slots]
+    return off
+
+
+def op_resect_images(track_of, xyz, use, kpts, cams: np.ndarray, out, n: int, T: int, thresh: float = 4.0, iters: int = 1024, lo_iters: int = 8,
+                     min_inliers: int = 12, seed: int = 0) -> Op:
+    """GIMS_AUX_RESECT_IMAGES as an op of gims_run_ops (include/gims_hip.h): the one way to reach it.  track_of int32 [n], xyz float64 [T, 3],
+    use uint8 [T], kpts float32 [n, 2] on the device; cams the HOST records float64 [m, 6] (C-contiguous; the caller keeps the array alive
+    for as long as the op is run); out uint8 [resect_out_layout(cams, iters)['bytes']]."""
+    if not (0 <= int(iters) <= 65535 and 0 <= int(lo_iters) <= 255 and 0 <= int(min_inliers) <= 2 ** 30):
+        raise ValueError(f"resect_images: iters = {iters} must be 0 .. 65535, lo_iters = {lo_iters} 0 .. 255 and min_inliers = {min_inliers} 0 .. 2^30")
+    if not (isinstance(cams, np.ndarray) and cams.dtype == np.float64 and cams.flags["C_CONTIGUOUS"] and cams.size % RESECT_CAMERA_WORDS == 0):
+        raise ValueError("resect_images: cams must be a C-contiguous float64 host array [m, 6] (resect_cameras)")
+    m = cams.size // RESECT_CAMERA_WORDS
+    s64 = int(seed) & 0xFFFFFFFFFFFFFFFF                      # the seed's 64 bits, as the signed word of the table
+    return op_aux(AUX_RESECT_IMAGES, (track_of, xyz, use, kpts, cams.ctypes.data if m else None, out),
+                  (m, n, T, int(iters) | (int(lo_iters) << 16) | (int(min_inliers) << 24), s64 - (1 << 64) if s64 >> 63 else s64, 0), (thresh, 0.0))
+
+
+def resect_views(out: torch.Tensor, cams, iters: int = 0) -> dict:
+    """The typed views of the op's buffer, by resect_out_layout."""
+    o = resect_out_layout(cams, iters)
+    m, S = len(o["slots"]) - 1, o["slots"][-1]
+    cut = lambda name, size, dt: out[o[name]:o[name] + size].view(dt)      # noqa: E731
+    v = {k: cut(k, 4 * m, torch.int32) for k in ("n_corr", "ok", "n_inliers", "best_hyp", "best_hyp_inliers", "lo_rounds")}
+    v.update(pose=cut("pose", 96 * m, torch.float64).view(m, 12), rms_error=cut("rms_error", 4 * m, torch.float32),
+             kp_inlier=cut("kp_inlier", S, torch.uint8), kp_error=cut("kp_error", 4 * S, torch.float32), counters=cut("counters", 32, torch.int32),
+             slots=o["slots"])
+    return v
+
+
+def resect_images(track_of, xyz, use, kpts, cams: np.ndarray, thresh: float = 4.0, iters: int = 1024, lo_iters: int = 8, min_inliers: int = 12,
+                  seed: int = 0, n: int | None = None, T: int | None = None):
+    """Absolute poses of the entries of cams on the device (csrc/resect.hip): device tensors as op_resect_images takes them,
+    cams the HOST records of resect_cameras; n, T: the sizes to state when a tensor is a stand-in for an empty one (default: the tensors' own).
+    -> (the views of resect_views, and what must stay alive until the launches have run).
+    Asynchronous; no host read."""
+    device = track_of.device
+    rec = np.ascontiguousarray(cams, dtype=np.float64).reshape(-1, RESECT_CAMERA_WORDS)
+    out = torch.empty(max(resect_out_layout(rec, iters)["bytes"], 16), dtype=torch.uint8, device=device)
+    run_ops(make_ops([op_resect_images(track_of, xyz, use, kpts, rec, out, track_of.numel() if n is None else n, use.numel() if T is None else T, thresh, iters, lo_iters,
+                                       min_inliers, seed)]))
+    return resect_views(out, rec, iters), (rec, out, track_of, xyz, use, kpts)
 
 
 def patch_affine(kp4: torch.Tensor, kp_octave: torch.Tensor):

@@ -510,7 +510,90 @@ int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t
  * wave, both with one observation per lane held in registers; a longer one by a wave that walks the observations in slots of 64.  Rays and
  * centres are computed once per track and staged in LDS.  Every sum over observations is the lane's own sum in ascending order, then a
  * butterfly over the group's lanes; there are no float atomics, and the group size depends on the track's length alone, so the outputs of a track
- * are bit-identical alone or inside any batch, at any position, and across runs.  Counters are integer atomics, summed per workgroup first. */
+ * are bit-identical alone or inside any batch, at any position, and across runs.  Counters are integer atomics, summed per workgroup first.
+ *
+ * GIMS_AUX_RESECT_IMAGES is the sixth function of this table without a stand-alone entry point, for the same reason.  It gives every listed
+ * image its absolute pose from 2-D to 3-D correspondences -- the keypoints whose track already has a 3-D point -- robustly (resection,
+ * DESIGN.md 4.19).  This library's own specification: the reference matches one pair and has no counterpart.  kernels: resect_gather_kernel,
+ * resect_hyp_kernel, resect_finish_kernel, gims_amd/csrc/resect.hip; tests/resect_ref.py is the NumPy float64 restatement.  All arithmetic
+ * is float64.
+ *   p[0] track_of  device int32 [N]: the track of every node (GIMS_AUX_BUILD_TRACKS).  NOT trusted: an entry outside 0 .. T - 1 is "no track"
+ *   p[1] xyz       device double [T][3], 8-byte aligned: the point of every track (GIMS_AUX_TRIANGULATE_TRACKS)
+ *   p[2] use       device uint8 [T]: non-zero = the point may serve as a correspondence
+ *   p[3] kpts      device float [N][2]: the pixel (u, v) of every keypoint of every image, the images back to back
+ *   p[4] cams      HOST double [m][GIMS_RESECT_CAMERA_WORDS], 8-byte aligned, read during the call like the op table itself: one record
+ *                  {fx, fy, cx, cy, first node, n_k} per image to resect (an ENTRY), in the caller's order; an image may be listed twice.
+ *                  Keypoint i < n_k of entry e is node first_e + i.  n_k sizes the entry's slots in the output, so it is checked (below); the
+ *                  other five words are data: a record is GOOD when they are finite and fx > 0 and fy > 0, and an entry with a bad record
+ *                  has no correspondence.  The records travel to the device as kernel arguments: a captured graph holds their values.
+ *   p[5] out       device, 16-byte aligned, never NULL: one buffer, every region on a 256-byte boundary (al256(x) = (x + 255) & ~255), with
+ *                  S = the sum of n_k over the entries, in this order:
+ *                    double pose [m][12] | int32 n_corr [m] | int32 ok [m] | int32 n_inliers [m] | int32 best_hyp [m] |
+ *                    int32 best_hyp_inliers [m] | int32 lo_rounds [m] | float rms_error [m] | uint8 kp_inlier [S] | float kp_error [S] |
+ *                    int32 counters [8] | scratch: 56 m bytes | double [S][6] | int32 [m][iters]
+ *                  that is al256(96 m) + 7 al256(4 m) + al256(S) + al256(4 S) + 256 bytes of outputs and al256(56 m) + al256(48 S) +
+ *                  al256(4 m iters) bytes of scratch behind them (hip.resect_out_layout has the offsets).  The slots of entry e in kp_inlier and
+ *                  kp_error are [o_e, o_e + n_k), o_e = the sum of n_k over the entries in front: the entries lie back to back, a duplicated
+ *                  image has slots of its own.  counters = {n_ok, n_failed, n_corr_total, n_inlier_total, 0, 0, 0, 0}.
+ *   i = {m, N, T, iters | lo_iters << 16 | min_inliers << 24, seed (its 64 bits), 0}     f = {thresh (pixels), 0}
+ * Correspondences of entry e.  Keypoint i gives node g = first + i (in double) and t = track_of[g].  It is a correspondence iff the record is
+ *   good, 0 <= g < N, 0 <= t < T, use[t] != 0, and the three words of xyz[t] and the pixel (u, v) = kpts[g] are finite.  The dense list holds the
+ *   correspondences {X = xyz[t], u, v} (u, v read as double) in ascending i; K is its length (n_corr).
+ * Hypothesis h < iters, when K >= 3.  Three distinct indices below K from the sampler of gims_verify_pairs for (seed, h): state = seed ^
+ *   (h * 0xD1342543DE82EF95), then repeatedly state = splitmix64(state), candidate = state mod K, kept unless already drawn.  They give (X1, X2,
+ *   X3) and the unit bearings f_i = x / |x|, x = ((u - cx) / fx, (v - cy) / fy, 1).  With c_ij = f_i . f_j, a = |X1 - X2|^2, b = |X1 - X3|^2,
+ *   c = |X2 - X3|^2 and the distances s_i of the points from the centre written s2 = u s1, s3 = v s1 (P3P by the law of cosines):
+ *     q(u) = u^2 - 2 c12 u + 1,   N(u) = (b - c) q(u) - a (1 - u^2) = ((b - c) - a) - 2 c12 (b - c) u + ((b - c) + a) u^2,
+ *     D(u) = 2 a (c23 u - c13),   v = N(u) / D(u),   and u is a real root of the quartic  P = b q D^2 - a (D^2 + N^2 - 2 c13 N D),
+ *   whose five coefficients are built by polynomial products (D D, q (D D), N N, N D; out[i + j] += a[i] b[j], i outer, j inner, ascending).
+ *   Its real roots, ascending: none when P_4 == 0 or a coefficient is not finite; otherwise inside the bound B = 1 + max |P_i / P_4|, for
+ *   d = 1 .. 4 the roots of the (4 - d)-th derivative are sought in the intervals between -B, the roots of the derivative before it and B:
+ *   an interval [x, y] holds a root iff (p(x) > 0) != (p(y) > 0), found by 80 halvings (the midpoint replaces the end whose sign it shares;
+ *   the root is the last midpoint); polynomials are evaluated by Horner's rule.  Root number j (0 .. 3, ascending) gives a MODEL iff
+ *   a > 0 and |e1 x (X3 - X1)|^2 > 1e-18 b (the world triangle is not degenerate; e1 below), u > 0, |D(u)| > 1e-12 a, q(u) > 0, v > 0, and
+ *   every word of the result is finite.  Then s1 = sqrt(a / q(u)), Y_i = s_i f_i, and with the frame of a triangle (P1, P2, P3)
+ *     e1 = (P2 - P1)^, e3 = (e1 x (P3 - P1))^, e2 = e3 x e1,  E = [e1 e2 e3] (columns):   R = E_Y E_X^T,  t = Y1 - R X1.
+ * Reprojection under (R, t).  x_c = R X + t, z = x_c[2], e^2 = (fx x_c[0] / z + cx - u)^2 + (fy x_c[1] / z + cy - v)^2; INLIER iff z > 0 and
+ *   e^2 <= thresh^2 (thresh^2 is the float thresh squared in double): the rule of GIMS_AUX_TRIANGULATE_TRACKS.
+ * Score.  The score of a model is its number of inliers among the K correspondences.  The best model is the one of the largest score, then
+ *   of the smallest h, then of the smallest root number j.  No floating-point number enters the choice.  best_hyp = its h, best_hyp_inliers =
+ *   its score.
+ * Stage 2, the guarded local optimisation.  The current model starts as the best model; n and c are its inlier count and the sum of e^2 over
+ *   its inliers.  At most lo_iters rounds, and none while n < 4 (three correspondences fit their model): over the inliers of the current model, with y = R X, x_c = y + t, the residual r = (ru, rv) of the
+ *   reprojection and its 2 x 6 Jacobian for the update R <- exp([w]x) R, t <- t + dt in the order (w, dt),
+ *     au = fx / z, bu = -fx x_c[0] / z^2, av = fy / z, bv = -fy x_c[1] / z^2,
+ *     Ju = (bu y1, au y2 - bu y0, -au y1, au, 0, bu),   Jv = (bv y1 - av y2, -bv y0, av y0, 0, av, bv),
+ *   solve (sum J^T J) d = -(sum J^T r): Gaussian elimination on the 6 x 7 array with partial pivoting (the pivot of column c is the first row
+ *   at or below c of the largest magnitude; rows are swapped; the rows below are reduced), then back substitution; the solve is REGULAR iff
+ *   every pivot's magnitude is above 1e-12 times the largest diagonal entry of the matrix.  exp([w]x) = I + A [w]x + B [w]x^2, theta = |w|,
+ *   A = sin(theta) / theta, B = (1 - cos(theta)) / theta^2 for theta > 1e-8, else A = 1, B = 1/2.  The round is TAKEN iff the solve is regular,
+ *   every word of the candidate is finite, and the candidate's own inlier count n' and inlier cost c' have n' > n, or n' == n and c' < c
+ *   with both costs rounded to float32 for this comparison (an improvement below one part in 2^24 of the cost is none, and the decision does
+ *   not hang on the last bits of two float64 sums); the candidate then becomes the current model.  The first round that is not taken ends the loop; lo_rounds counts the rounds taken.
+ * Final sweep.  Every correspondence is classified once under the final model: kp_inlier, kp_error = sqrt(e^2) as float (at most FLT_MAX; -1
+ *   when z <= 0), n_inliers, rms_error = sqrt(sum of inlier e^2 / n_inliers).
+ * ok = 1 iff K >= 3, a model exists and n_inliers >= max(min_inliers, 4) (three points fit every model of their own sample: four is the
+ *   first count that says anything).  An entry with ok = 0 has NO POSE: its twelve pose words, n_inliers and rms_error are zero, the
+ *   kp_inlier of all its slots 0 and their kp_error -1; best_hyp, best_hyp_inliers and lo_rounds still say what was found (-1, 0, 0 when no
+ *   hypothesis gave a model).  With ok = 1, pose = {R row-major, t}, world to camera x_c = R X + t -- the convention of
+ *   GIMS_AUX_TRIANGULATE_TRACKS and of the pose model; a slot whose keypoint is no correspondence has kp_inlier 0 and kp_error -1.  Every output
+ *   of every entry is written by every call; no output is ever a NaN.  n_ok + n_failed = m; n_corr_total is the sum of K, n_inlier_total the
+ *   sum of n_inliers.
+ * GIMS_EINVAL before any HIP call, each with a message naming resect_images: m outside 0 .. 2^24; N or T outside 0 .. 2^30; i[3] negative or
+ * min_inliers above 2^30 (iters is its low 16 bits, lo_iters the next 8); thresh not finite or <= 0; f[1] != 0; a NULL out; any other NULL
+ * pointer while m > 0; out not 16-byte aligned, xyz or cams not 8-byte aligned, track_of or kpts not 4-byte aligned; an n_k that is not an
+ * integer in 0 .. 2^30, or S above 2^30; i[5] != 0.  i[5] is reserved for selecting a later form of the function and is checked before
+ * everything else: a non-zero value is refused as an unknown auxiliary function form of gims_run_ops (the message names both), whatever
+ * the other arguments hold.  m == 0 is GIMS_OK after the same checks and writes the counters only.
+ * Nothing outside out is written.  A fixed sequence of memset nodes, the upload of the records and three launches (two when iters == 0), the
+ * same whatever the data; no host synchronisation; capturable by gims_ops_graph_create.
+ * How it is computed.  gather: a workgroup per entry compacts the correspondences in order (ballots and a prefix over the waves).  hyp: a
+ * workgroup of 256 per GIMS_RESECT_HB hypotheses of an entry; that many lanes solve one P3P sample each into LDS, then every thread scores one
+ * correspondence per tile against the models that exist, sixteen at a time: their counters stay in registers and each model is read at a
+ * wave-uniform LDS address.  finish: a workgroup per entry finds the best hypothesis, solves its sample again, runs stage 2 and the final
+ * sweep.  The 27 sums of the normal equations and the inlier cost are a thread's own sum in ascending order, a butterfly over the wave, then
+ * the waves in order; there are no float atomics, so the outputs of an entry are bit-identical alone or inside any batch, at any position,
+ * and across runs.  Counters are integer atomics. */
 #define GIMS_OP_AUX 2
 #define GIMS_AUX_SPLIT_SPL32 0
 #define GIMS_AUX_SAGE_MEAN_SPLIT 1
@@ -531,6 +614,9 @@ int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t
 #define GIMS_TRI_CAMERA_WORDS 18
 #define GIMS_TRI_MAX_OBS 1024
 #define GIMS_TRI_SHORT_TRACK 4
+#define GIMS_AUX_RESECT_IMAGES 11
+#define GIMS_RESECT_CAMERA_WORDS 6
+#define GIMS_RESECT_HB 16
 typedef struct gims_aux_args { int32_t fn, reserved; const void* p[6]; int64_t i[6]; float f[2]; } gims_aux_args;
 typedef struct gims_op { int32_t kind; int32_t reserved; union { gims_linear_args lin; gims_attn_args att; gims_aux_args aux; } u; } gims_op;
 int gims_run_ops(const gims_op* ops /* HOST */, int32_t n_ops, void* stream);
