@@ -8,7 +8,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgims_hip.so")
-SOURCES = ["linear.hip", "linear_mlp.hip", "linear6.hip", "carhynet.hip", "attention.hip", "sinkhorn.hip", "sinkhorn2d.hip", "misc.hip", "agc.hip", "delaunay.hip", "eval.hip", "verify.hip", "patches.hip", "sift.hip", "warp.hip", "train.hip", "train_attn.hip", "optim.hip", "nn.hip", "augment.hip", "nms.hip", "features.hip", "tracks.hip", "triangulate.hip", "resect.hip"]
+SOURCES = ["linear.hip", "linear_mlp.hip", "linear6.hip", "carhynet.hip", "attention.hip", "sinkhorn.hip", "sinkhorn2d.hip", "misc.hip", "agc.hip", "delaunay.hip", "eval.hip", "verify.hip", "patches.hip", "sift.hip", "warp.hip", "train.hip", "train_attn.hip", "optim.hip", "nn.hip", "augment.hip", "nms.hip", "features.hip", "tracks.hip", "triangulate.hip", "resect.hip", "ba.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-result"]
 # per-file extras: keep MFMA accumulators in VGPRs (gfx950 has a unified VGPR/AGPR file) -- the softmax reads S
 # straight out of the MFMA result registers instead of through v_accvgpr_read copies
@@ -16,7 +16,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # Sinkhorn kernel pins for its slab of the transport matrix, the pairing copies push that kernel into scratch spills
 # resect.hip: no contraction into fused multiply-adds -- the roots of a P3P sample's quartic are found to the last bit of its computed
 # coefficients, so the float64 operations are kept as the specification states them and the restatement performs them
-EXTRA = {"resect.hip": ["-ffp-contract=off"], "attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "train_attn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "sinkhorn.hip": ["-fno-slp-vectorize"], "sinkhorn2d.hip": ["-fno-slp-vectorize"]}
+# ba.hip: likewise no contraction -- the Cholesky factorisation and the sums of the normal equations are the operations the
+# specification states, one product and one sum at a time, which is what lets tests/ba_ref.py follow them
+EXTRA = {"resect.hip": ["-ffp-contract=off"], "ba.hip": ["-ffp-contract=off"], "attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "train_attn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "sinkhorn.hip": ["-fno-slp-vectorize"], "sinkhorn2d.hip": ["-fno-slp-vectorize"]}
 
 
 def _stale() -> bool:

@@ -1,0 +1,191 @@
+"""Bundle adjustment: joint refinement of cameras and points, on the device (kernels: gims_amd/csrc/ba.hip,
+GIMS_AUX_BUNDLE_ADJUST).
+
+``resect_images`` gives every image a pose from its own correspondences and ``triangulate_tracks`` gives every track a point from cameras
+taken as known, so the errors of the incremental loop only accumulate.  ``bundle_adjust`` is the step that joins what the loop has
+estimated: it moves the free cameras and the points together so that the reprojection cost over all the inlier observations goes down,
+in one asynchronous op and without reading tracks, keypoints, points or poses back::
+
+    estimate_pose(0, 1) -> triangulate_tracks -> resect_images(the rest) -> triangulate_tracks(all) -> bundle_adjust -> ...
+
+The specification (include/gims_hip.h has it in full; tests/ba_ref.py is its NumPy restatement).  World to camera is ``x_c = R X + t``.
+``iters`` Levenberg-Marquardt rounds; a round eliminates the points (Schur complement), factors the dense reduced camera system (6 x 6
+blocks, at most 128 free cameras) by Cholesky, substitutes back, and is taken iff the cost goes down and every observation stays in
+front of its camera; after five rounds in a row that were not taken the rest do nothing.  The inlier set is an input and is not decided
+again.  All arithmetic is float64; the output bytes are identical across runs.
+
+The gauge.  A reconstruction is defined up to a similarity: seven numbers that no observation fixes.  ``fixed`` names the cameras that do
+not move; the default is the first two posed images in index order, which fixes position, orientation and -- through the distance between
+the two -- the scale.  With fewer than two fixed cameras the damping alone keeps the rounds regular and the result drifts."""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import torch
+
+from . import hip
+from .resect import _nonempty
+from .triangulate import _host
+
+
+class Adjusted:
+    """The result of ``bundle_adjust``.  Device tensors: ``xyz`` float64 [T, 3] (points that were not active are copied through), ``records``
+    float64 [n, 18] -- the camera records of the op, the format ``triangulate_tracks`` takes as ``cameras`` -- and its views ``R`` [n, 3, 3] and
+    ``t`` [n, 3] (absent, fixed and held cameras are copied through), ``obs_error`` float32 [n_obs] (pixels, under the final state; -1 for an
+    observation that was not active), ``cam_obs`` int32 [n] (active observations per image), ``history`` float64 [iters + 1, 2] ({cost,
+    lambda} at the start and after every round), ``taken`` uint8 [iters].  ``mode``: the host list of the cameras' modes (0 absent, 1
+    fixed, 2 free).
+
+    ``stats`` (n_free, n_fixed, n_held, n_points, n_active_obs, n_bad_obs, rounds_taken, status) reads the op's counters back on first
+    access, and ``cameras()`` reads the records: these two synchronise with the device; everything else is handed over asynchronously."""
+
+    def __init__(self, views: dict, mode, K, keep):
+        self.xyz, self.records = views["xyz"], views["cams"]
+        self.R, self.t = self.records[:, 4:13].unflatten(1, (3, 3)), self.records[:, 13:16]
+        self.obs_error, self.cam_obs, self.history, self.taken = views["obs_error"], views["cam_obs"], views["history"], views["taken"]
+        self.mode = [int(m) for m in mode]
+        self._K, self._counters, self._keep, self._stats = K, views["counters"], keep, None
+
+    @property
+    def stats(self) -> dict:
+        if self._stats is None:
+            with torch.cuda.device(self._counters.device):
+                pin = torch.empty(8, dtype=torch.int32, pin_memory=True)
+                pin.copy_(self._counters, non_blocking=True)
+                done = torch.cuda.Event()
+                done.record()
+                done.synchronize()      # the host synchronisation of .stats
+            self._stats = dict(zip(hip.BA_COUNTERS, (int(v) for v in pin.tolist())))
+        return self._stats
+
+    def cameras(self):
+        """The host ``(K, R, t)`` triple for the next ``triangulate_tracks`` / ``resect_images`` / ``bundle_adjust`` call; the absent
+        cameras hold NaN poses, as they did on the way in.
+
+        This call SYNCHRONISES with the device: it reads the records back."""
+        rec = self.records.cpu().numpy()
+        R, t = rec[:, 4:13].reshape(-1, 3, 3).copy(), rec[:, 13:16].copy()
+        absent = np.array(self.mode, dtype=np.int64) == hip.BA_ABSENT
+        R[absent], t[absent] = np.nan, np.nan
+        return self._K.copy(), R, t
+
+    def __len__(self):
+        return int(self.xyz.shape[0])
+
+    def __repr__(self):
+        return f"Adjusted(n_points={len(self)}, n_images={len(self.mode)}, n_free={sum(m == hip.BA_FREE for m in self.mode)})"
+
+
+def _check(points, tracks, images, cameras, fixed, use_obs, use_points, iters, huber, lambda0):
+    """Everything bundle_adjust checks before the device is touched -> (keypoint tensors, host records, host K, modes, obs mask, point mask)."""
+    name = "bundle_adjust"
+    if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or not 0 <= iters <= 255:
+        raise ValueError(f"{name}: iters must be an integer in 0 .. 255, got {iters!r}")
+    if isinstance(huber, bool) or not (isinstance(huber, (int, float)) and math.isfinite(huber) and huber >= 0):
+        raise ValueError(f"{name}: huber must be finite and >= 0 (pixels; 0: the squared loss), got {huber!r}")
+    if isinstance(lambda0, bool) or not (isinstance(lambda0, (int, float)) and math.isfinite(lambda0) and lambda0 > 0 and float(np.float32(lambda0)) > 0
+                                         and math.isfinite(float(np.float32(lambda0)))):
+        raise ValueError(f"{name}: lambda0 must be finite and > 0 (as a float32), got {lambda0!r}")
+    for attr in ("indptr", "obs_image", "obs_keypoint", "image_start"):
+        if not hasattr(tracks, attr):
+            raise ValueError(f"{name}: tracks must be the Tracks of build_tracks (it has no {attr})")
+    for attr in ("xyz", "obs_inlier", "valid"):
+        if not hasattr(points, attr):
+            raise ValueError(f"{name}: points must be the Points3D of triangulate_tracks (it has no {attr})")
+    start = list(tracks.image_start)
+    n_images = len(start) - 1
+    if len(images) != n_images:
+        raise ValueError(f"{name}: {len(images)} images are given, the tracks were built over {n_images}")
+    kpts = []
+    for k, im in enumerate(images):
+        t = im.keypoints if hasattr(im, "keypoints") else im
+        if not isinstance(t, torch.Tensor) or not t.dtype.is_floating_point:
+            raise ValueError(f"{name}: image {k}: the keypoints must be a floating-point tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+        if t.numel() != 2 * (start[k + 1] - start[k]) or (t.dim() >= 1 and t.numel() and t.shape[-1] != 2):
+            raise ValueError(f"{name}: image {k}: keypoints of shape {tuple(t.shape)}, the tracks were built over {start[k + 1] - start[k]} keypoints ([n_k, 2])")
+        kpts.append(t)
+    if not isinstance(cameras, (tuple, list)) or len(cameras) != 3:
+        raise ValueError(f"{name}: cameras must be (K [n, 3, 3], R [n, 3, 3], t [n, 3])")
+    try:
+        K, R, t = _host(cameras[0], "K", (None, 3, 3)), _host(cameras[1], "R", (None, 3, 3)), _host(cameras[2], "t", (None, 3))
+    except ValueError as e:
+        raise ValueError(str(e).replace("triangulate_tracks", name)) from None
+    if not len(K) == len(R) == len(t) == n_images:
+        raise ValueError(f"{name}: {len(K)} / {len(R)} / {len(t)} cameras (K / R / t) for {n_images} images")
+    posed = np.isfinite(R).all(axis=(1, 2)) & np.isfinite(t).all(axis=1) if n_images else np.zeros(0, bool)
+    Kp = K[posed]
+    if len(Kp) and ((Kp[:, 0, 1] != 0).any() or (Kp[:, 1, 0] != 0).any() or (Kp[:, 2] != np.array([0.0, 0.0, 1.0])).any()):
+        raise ValueError(f"{name}: K must be [[fx, 0, cx], [0, fy, cy], [0, 0, 1]]: skew or another last row is not supported")
+    if len(Kp) and not (np.isfinite(Kp).all() and (Kp[:, 0, 0] > 0).all() and (Kp[:, 1, 1] > 0).all()):
+        raise ValueError(f"{name}: the K of a posed camera must be finite with fx > 0 and fy > 0")
+    if fixed is None:
+        fixed = [int(k) for k in np.flatnonzero(posed)[:2]]
+    fixed = list(fixed)
+    for k in fixed:
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= k < n_images:
+            raise ValueError(f"{name}: fixed holds {k!r}: an image index must be an integer in 0 .. {n_images - 1}")
+        if not posed[k]:
+            raise ValueError(f"{name}: fixed holds {k}: that image has no pose (its R or t is not finite)")
+    mode = np.where(posed, hip.BA_FREE, hip.BA_ABSENT).astype(np.int32)
+    mode[fixed] = hip.BA_FIXED
+    n_free = int((mode == hip.BA_FREE).sum())
+    if n_free > hip.BA_MAX_FREE_CAMERAS:
+        raise ValueError(f"{name}: {n_free} free cameras, at most {hip.BA_MAX_FREE_CAMERAS} (fix more of them, or adjust a part of the set)")
+    device = tracks.indptr.device
+    for attr in ("indptr", "obs_image", "obs_keypoint"):
+        x = getattr(tracks, attr)
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.int32 or x.device != device:
+            raise ValueError(f"{name}: tracks.{attr} must be an int32 tensor on {device}, got {getattr(x, 'dtype', None)} on {getattr(x, 'device', None)}")
+    T, n_obs = tracks.indptr.numel() - 1, tracks.obs_image.numel()
+    xyz = points.xyz
+    if not isinstance(xyz, torch.Tensor) or xyz.dtype != torch.float64 or tuple(xyz.shape) != (T, 3) or xyz.device != device:
+        raise ValueError(f"{name}: points.xyz must be a float64 tensor [{T}, 3] on {device}, got {getattr(xyz, 'dtype', None)} "
+                         f"{tuple(getattr(xyz, 'shape', ()))} on {getattr(xyz, 'device', None)}")
+    obs = points.obs_inlier if use_obs is None else use_obs
+    if not isinstance(obs, torch.Tensor) or obs.dtype not in (torch.bool, torch.uint8) or tuple(obs.shape) != (n_obs,) or obs.device != device:
+        raise ValueError(f"{name}: use_obs must be a bool or uint8 tensor [{n_obs}] on {device} (points.obs_inlier)")
+    pts = points.valid if use_points is None else use_points
+    if not isinstance(pts, torch.Tensor) or pts.dtype not in (torch.bool, torch.uint8) or tuple(pts.shape) != (T,) or pts.device != device:
+        raise ValueError(f"{name}: use_points must be a bool or uint8 tensor [{T}] on {device} (points.valid or points.filter(...))")
+    for k, x in enumerate(kpts):
+        if x.device != device:
+            raise ValueError(f"{name}: image {k}: the keypoints are on {x.device}, the tracks on {device}")
+    if device.type != "cuda":
+        raise ValueError(f"{name}: the tracks are on {device}: cameras and points are adjusted on the GPU, from device tensors")
+    counts = [start[k + 1] - start[k] for k in range(n_images)]
+    return kpts, hip.triangulate_cameras(K, R, t, counts), K, mode, obs, pts
+
+
+def bundle_adjust(points, tracks, images, cameras, *, fixed=None, use_obs=None, use_points=None, iters: int = 20, huber: float = 0.0,
+                  lambda0: float = 1e-4) -> Adjusted:
+    """Refine the posed cameras and the points jointly, on the device.
+
+    ``points``: the ``Points3D`` of ``triangulate_tracks`` (the starting points); ``tracks``: the ``Tracks`` they belong to; ``images``: the
+    list the tracks were built over -- ``ImageFeatures`` or [n_k, 2] tensors of pixel coordinates.  ``cameras``: the host triple ``(K [n, 3,
+    3], R [n, 3, 3], t [n, 3])`` of ``triangulate_tracks`` and ``Poses.cameras`` (the starting cameras); an image whose R or t is not
+    finite is ABSENT: its observations are ignored.  ``fixed``: the image indices that do not move (default: the first two posed images in
+    index order -- this fixes the gauge, scale included; see the module text); every other posed camera is free, at most 128 of them.
+    ``use_obs``: bool / uint8 [n_obs], the observations that enter the cost (default ``points.obs_inlier``); the set is NOT decided again
+    inside the op.  ``use_points``: bool / uint8 [T] (default ``points.valid``).  A point needs two such observations in posed cameras to
+    move; a free camera with fewer than four is held.  ``iters``: Levenberg-Marquardt rounds (0 .. 255); ``huber``: the Huber bound in
+    pixels, 0 for the squared loss; ``lambda0``: the starting damping.
+
+    ValueError, before the device is touched: a count that disagrees with ``tracks.image_start``, cameras of another shape or count, a K
+    of a posed camera with skew, another last row or a focal length that is not positive, an index of ``fixed`` out of range or without a
+    pose, more than 128 free cameras, tensors of a wrong dtype, shape or device, a parameter out of range.
+
+    Host synchronisation: NONE.  ``Adjusted.stats`` and ``Adjusted.cameras()`` read back."""
+    kpts, rec, K, mode, obs, pts = _check(points, tracks, images, cameras, fixed, use_obs, use_points, iters, huber, lambda0)
+    device = tracks.indptr.device
+    with torch.cuda.device(device):
+        allk = torch.cat([k.reshape(-1, 2).float() for k in kpts]).contiguous() if kpts else torch.zeros((0, 2), device=device)
+        T, n_obs, n = tracks.indptr.numel() - 1, tracks.obs_image.numel(), allk.shape[0]
+        dev_cams = (hip.upload_large(rec.view(np.uint8).reshape(-1), device).view(torch.float64).view(-1, hip.TRI_CAMERA_WORDS) if rec.size
+                    else torch.zeros((1, hip.TRI_CAMERA_WORDS), dtype=torch.float64, device=device))
+        views, keep = hip.bundle_adjust(tracks.indptr.contiguous(), _nonempty(tracks.obs_image.contiguous(), (1,), torch.int32),
+                                        _nonempty(tracks.obs_keypoint.contiguous(), (1,), torch.int32), _nonempty(obs.contiguous().view(torch.uint8), (1,), torch.uint8),
+                                        _nonempty(pts.contiguous().view(torch.uint8), (1,), torch.uint8), _nonempty(allk, (1, 2), torch.float32),
+                                        _nonempty(points.xyz.contiguous(), (1, 3), torch.float64), dev_cams, mode, iters=int(iters), huber=float(huber),
+                                        lambda0=float(lambda0), T=T, n_obs=n_obs, n=n)
+    return Adjusted(views, mode, K, keep)

@@ -1,0 +1,733 @@
+// Bundle adjustment: GIMS_AUX_BUNDLE_ADJUST of gims_run_ops refines the free cameras and the active points of a Tracks /
+// Points3D / camera-record set jointly, by Levenberg-Marquardt rounds on the reprojection cost with the Schur complement over the points.
+// include/gims_hip.h has the contract; tests/ba_ref.py is the NumPy restatement.  All arithmetic is float64 on the vector ALU, compiled
+// without contraction into fused multiply-adds, so the operations are the ones the specification states.
+//
+// Launches, the same whatever the data (n_free = the cameras of mode 2, counted on the host): memset nodes -> the slot tables (upload_table)
+// -> init (copies, the record check) -> classify (a thread per track: active observations and points, cam_obs) -> slots (held cameras, the
+// scan of the list sizes) -> fill (a workgroup per slot: its observations in ascending order) -> prep (a thread per track: the moving
+// slot of every observation) -> cost + decide (the starting cost) ->
+// per round { point (a thread per track: V, g_p, V*^-1, W, W V*^-1) -> camera (a wave per slot: U, g_c, its block row of S in LDS) ->
+// solve (one workgroup: Cholesky, the two substitutions, the candidate cameras) -> back (a thread per track: the candidate point, its
+// cost) -> decide (one workgroup: the ordered sum of the costs, one thread decides) } -> finish.  camera and solve are left out when
+// n_free == 0.  The state (cost, lambda, which of the two buffers is current, the reject count) lives in a block on the device.
+// Every floating-point sum has one order: a track's observations ascending in one thread; a camera's observations as the lane's own
+// ascending sum and a butterfly over the wave (U, g_c), or one after the other (the block row); the tracks' costs as a thread's own
+// ascending sum, a butterfly, then the waves in order.  No order depends on the grid.
+#include "common.h"
+
+#include <cfloat>
+#include <vector>
+
+namespace gims {
+
+constexpr int BA_CAM = GIMS_TRI_CAMERA_WORDS;
+constexpr int BA_MAX_OBS = GIMS_TRI_MAX_OBS;
+constexpr int BA_MAX_FREE = GIMS_BA_MAX_FREE_CAMERAS;
+constexpr int BA_MAX_REJECTS = GIMS_BA_MAX_REJECTS;
+constexpr int BA_THREADS = 256;
+constexpr int BA_SOLVE_THREADS = 1024;
+constexpr int BA_REC = 50;                                     // per observation: Ju, Jv [12] | ru, rv [2] | W [6][3] | W V*^-1 [6][3]
+constexpr int BA_PT = 9;                                       // per point: V*^-1 (a00 a01 a02 a11 a12 a22) | g_p [3]
+enum { BA_N_FREE = 0, BA_N_FIXED, BA_N_HELD, BA_N_POINTS, BA_N_ACTIVE_OBS, BA_N_BAD_OBS, BA_ROUNDS_TAKEN, BA_STATUS, BA_COUNTERS = 8 };
+enum { BA_BAD_CAMERA = 1, BA_BAD_START = 2 };
+enum { BA_F_IRREGULAR = 1, BA_F_NOT_FINITE = 2, BA_F_BEHIND = 4 };
+enum { BA_ABSENT = -1, BA_FIXED = -2 };                        // slot_of: or the slot 0 .. n_free - 1 of a camera of mode 2
+
+struct BaState {                                               // 256 bytes, zeroed by a memset node
+  double cost, lambda;
+  int32_t cur, rejects, stop, taken, status, flags, n_points, n_act, n_bad, n_held;
+};
+
+struct BaOut {
+  double *xyz, *cams, *history;                                // xyz and cams are also buffer 0 of the state
+  float* obs_error;
+  int32_t *cam_obs, *counters;
+  uint8_t* taken;
+  BaState* st;                                                 // scratch from here on
+  int32_t *slot_of, *slot_cam, *slot_ptr, *held, *obs_track, *obs_node, *cam_list, *obs_mslot, *obs_dup;
+  double *xyz1, *cams1, *pt_rec, *obs_rec, *trackcost, *S, *rhs;
+  uint8_t *pt_act, *obs_act;
+};
+static size_t ba_layout(void* base, int64_t T, int64_t n_obs, int64_t n_images, int64_t iters, int64_t n_free, BaOut& w) {
+  WsLayout L(base);
+  const size_t n = (size_t)(6 * n_free);
+  w.xyz = L.take<double>((size_t)T * 3);
+  w.cams = L.take<double>((size_t)n_images * BA_CAM);
+  w.obs_error = L.take<float>((size_t)n_obs);
+  w.cam_obs = L.take<int32_t>((size_t)n_images);
+  w.history = L.take<double>((size_t)(iters + 1) * 2);
+  w.taken = L.take<uint8_t>((size_t)iters);
+  w.counters = L.take<int32_t>(BA_COUNTERS);
+  w.st = (BaState*)L.take<double>(32);                         // scratch from here on
+  w.slot_of = L.take<int32_t>((size_t)n_images);
+  w.slot_cam = L.take<int32_t>((size_t)n_free);
+  w.slot_ptr = L.take<int32_t>((size_t)n_free + 1);
+  w.held = L.take<int32_t>((size_t)n_free);
+  w.xyz1 = L.take<double>((size_t)T * 3);
+  w.cams1 = L.take<double>((size_t)n_images * BA_CAM);
+  w.pt_act = L.take<uint8_t>((size_t)T);
+  w.obs_act = L.take<uint8_t>((size_t)n_obs);
+  w.obs_track = L.take<int32_t>((size_t)n_obs);
+  w.obs_node = L.take<int32_t>((size_t)n_obs);
+  w.cam_list = L.take<int32_t>((size_t)n_obs);
+  w.obs_mslot = L.take<int32_t>((size_t)n_obs);
+  w.obs_dup = L.take<int32_t>((size_t)n_obs);
+  w.pt_rec = L.take<double>((size_t)T * BA_PT);
+  w.obs_rec = L.take<double>((size_t)n_obs * BA_REC);
+  w.trackcost = L.take<double>((size_t)T);
+  w.S = L.take<double>(n * n);
+  w.rhs = L.take<double>(n);
+  return L.bytes();
+}
+
+struct BaArgs {
+  const int32_t *indptr, *obs_image, *obs_keypoint;
+  const uint8_t *obs_use, *point_use;
+  const float* kpts;
+  const double *xyz_in, *cams_in;
+  BaOut out;
+  int T, n_obs, n_images, iters, n_free, n_fixed;
+  int64_t N;
+  double huber, lambda0;
+};
+
+__device__ __forceinline__ bool ba_finite(double x) { return fabs(x) <= DBL_MAX; }       // (false for a NaN)
+__device__ __forceinline__ double* ba_xyz(const BaArgs& a, int which) { return which ? a.out.xyz1 : a.out.xyz; }
+__device__ __forceinline__ double* ba_cams(const BaArgs& a, int which) { return which ? a.out.cams1 : a.out.cams; }
+__device__ __forceinline__ bool ba_range(const BaArgs& a, int t, int& beg, int& len) {
+  const int b = a.indptr[t], e = a.indptr[t + 1];
+  beg = b;
+  len = e - b;
+  return b >= 0 && e >= b && e <= a.n_obs && e - b <= BA_MAX_OBS;
+}
+// the slot of an observation's camera when that camera moves (mode 2 and not held), else -1; k is in range (the observation is active)
+__device__ __forceinline__ int ba_moving_slot(const BaArgs& a, int k) {
+  const int s = a.out.slot_of[k];
+  return s >= 0 && s < a.n_free && a.out.held[s] == 0 ? s : -1;
+}
+
+// residual, depth and, when J is asked for, the Jacobians of one observation: c = the camera record, X the point, (u, v) the pixel
+struct BaJac { double ju[6], jv[6], pu[3], pv[3]; };
+template <bool JAC>
+__device__ __forceinline__ void ba_observe(const double* c, const double* X, double u, double v, double& ru, double& rv, double& z, BaJac* J) {
+  const double fx = c[0], fy = c[1], cx = c[2], cy = c[3];
+  const double* R = c + 4;
+  const double y0 = R[0] * X[0] + R[1] * X[1] + R[2] * X[2], y1 = R[3] * X[0] + R[4] * X[1] + R[5] * X[2], y2 = R[6] * X[0] + R[7] * X[1] + R[8] * X[2];
+  const double x = y0 + c[13], y = y1 + c[14];
+  z = y2 + c[15];
+  ru = fx * x / z + cx - u, rv = fy * y / z + cy - v;
+  if (JAC) {
+    const double au = fx / z, bu = -fx * x / (z * z), av = fy / z, bv = -fy * y / (z * z);
+    J->ju[0] = bu * y1, J->ju[1] = au * y2 - bu * y0, J->ju[2] = -au * y1, J->ju[3] = au, J->ju[4] = 0.0, J->ju[5] = bu;
+    J->jv[0] = bv * y1 - av * y2, J->jv[1] = -bv * y0, J->jv[2] = av * y0, J->jv[3] = 0.0, J->jv[4] = av, J->jv[5] = bv;
+#pragma unroll
+    for (int m = 0; m < 3; ++m) J->pu[m] = au * R[m] + bu * R[6 + m], J->pv[m] = av * R[3 + m] + bv * R[6 + m];
+  }
+}
+// rho(e^2) of the cost
+__device__ __forceinline__ double ba_rho(double e2, double huber) {
+  if (!(huber > 0.0)) return e2;
+  const double e = sqrt(e2);
+  return e <= huber ? e2 : 2.0 * huber * e - huber * huber;
+}
+
+// ---------------------------------------------------------------------------------------------- init
+__global__ __launch_bounds__(BA_THREADS) void ba_init_kernel(BaArgs a) {
+  const int64_t i = (int64_t)blockIdx.x * BA_THREADS + threadIdx.x;
+  if (i == 0) a.out.st->lambda = a.lambda0;
+  if (i < a.n_images) {
+    bool good = true;
+    for (int j = 0; j < BA_CAM; ++j) {
+      const double w = a.cams_in[i * BA_CAM + j];
+      a.out.cams[i * BA_CAM + j] = w, a.out.cams1[i * BA_CAM + j] = w;
+      good = good && ba_finite(w);
+    }
+    good = good && a.cams_in[i * BA_CAM] > 0.0 && a.cams_in[i * BA_CAM + 1] > 0.0;
+    if (a.out.slot_of[i] != BA_ABSENT && !good) atomicOr(&a.out.st->status, BA_BAD_CAMERA);
+    a.out.cam_obs[i] = 0;
+  }
+  if (i < a.T)
+    for (int j = 0; j < 3; ++j) {
+      const double w = a.xyz_in[i * 3 + j];
+      a.out.xyz[i * 3 + j] = w, a.out.xyz1[i * 3 + j] = w;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- classify
+__global__ __launch_bounds__(BA_THREADS) void ba_classify_kernel(BaArgs a) {
+  const int t = blockIdx.x * BA_THREADS + threadIdx.x;
+  if (t >= a.T) return;
+  a.out.trackcost[t] = 0.0;
+  a.out.pt_act[t] = 0;
+  int beg, len;
+  if (!ba_range(a, t, beg, len)) return;                       // a bad range, or a track that is too long: it touches no observation
+  const double* X = a.xyz_in + (int64_t)3 * t;
+  const bool point = a.point_use[t] != 0 && ba_finite(X[0]) && ba_finite(X[1]) && ba_finite(X[2]);
+  int n = 0;
+  for (int o = beg; o < beg + len; ++o) {
+    bool ok = false;
+    const int k = a.obs_image[o], i = a.obs_keypoint[o];
+    if (point && a.obs_use[o] != 0 && k >= 0 && k < a.n_images && a.out.slot_of[k] != BA_ABSENT) {
+      const double* r = a.cams_in + (int64_t)BA_CAM * k;
+      bool fin = true;
+      for (int j = 0; j < BA_CAM; ++j) fin = fin && ba_finite(r[j]);
+      const double node = r[16] + (double)i;
+      if (fin && r[0] > 0.0 && r[1] > 0.0 && i >= 0 && (double)i < r[17] && node >= 0.0 && node < (double)a.N) {
+        const int64_t g = (int64_t)node;                       // 0 .. N - 1
+        if (ba_finite((double)a.kpts[2 * g]) && ba_finite((double)a.kpts[2 * g + 1])) {
+          ok = true;
+          a.out.obs_node[o] = (int32_t)g;
+        }
+      }
+    }
+    a.out.obs_act[o] = ok ? 1 : 0;
+    n += ok ? 1 : 0;
+  }
+  const bool active = n >= 2;
+  a.out.pt_act[t] = active ? 1 : 0;
+  for (int o = beg; o < beg + len; ++o) {
+    if (a.out.obs_act[o] == 0) continue;
+    if (!active) {
+      a.out.obs_act[o] = 0;
+      continue;
+    }
+    a.out.obs_track[o] = t;
+    atomicAdd(a.out.cam_obs + a.obs_image[o], 1);              // integers: the order of the race changes nothing
+  }
+  if (active) atomicAdd(&a.out.st->n_points, 1), atomicAdd(&a.out.st->n_act, n);
+  if (len - (active ? n : 0) > 0) atomicAdd(&a.out.st->n_bad, len - (active ? n : 0));
+}
+
+// ---------------------------------------------------------------------------------------------- slots, lists
+__global__ __launch_bounds__(BA_MAX_FREE) void ba_slots_kernel(BaArgs a) {
+  const int s = threadIdx.x;
+  if (s < a.n_free) a.out.held[s] = a.out.cam_obs[a.out.slot_cam[s]] < 4 ? 1 : 0;
+  __syncthreads();
+  if (s == 0) {
+    int at = 0, held = 0;
+    for (int j = 0; j < a.n_free; ++j) {
+      a.out.slot_ptr[j] = at;
+      if (a.out.held[j]) ++held; else at += a.out.cam_obs[a.out.slot_cam[j]];
+    }
+    a.out.slot_ptr[a.n_free] = at;                             // <= n_obs: every active observation has one camera
+    a.out.st->n_held = held;
+  }
+}
+
+__global__ __launch_bounds__(BA_THREADS) void ba_fill_kernel(BaArgs a) {
+  __shared__ int s_w[BA_THREADS / 64];
+  const int s = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  if (a.out.held[s]) return;                                   // (the same for every thread)
+  const int cam = a.out.slot_cam[s], first = a.out.slot_ptr[s], cap = a.out.slot_ptr[s + 1] - first;
+  int K = 0;
+  for (int o0 = 0; o0 < a.n_obs; o0 += BA_THREADS) {
+    const int o = o0 + t;
+    const bool ok = o < a.n_obs && a.out.obs_act[o] != 0 && a.obs_image[o] == cam;
+    const unsigned long long bal = __ballot(ok);
+    if (lane == 0) s_w[wave] = __popcll(bal);
+    __syncthreads();
+    int before = __popcll(bal & ((1ull << lane) - 1ull)), total = 0;
+    for (int w = 0; w < BA_THREADS / 64; ++w) {
+      before += w < wave ? s_w[w] : 0;
+      total += s_w[w];
+    }
+    const int at = K + before;
+    if (ok && at < cap && first >= 0 && first + at < a.n_obs) a.out.cam_list[first + at] = o;
+    K += total;
+    __syncthreads();
+  }
+}
+
+// The slot of every observation whose camera moves (-1 otherwise), and how many earlier observations of its track lie in the same slot:
+// both hold for the whole call, and the camera kernel orders two observations of one track in one image by the second.
+__global__ __launch_bounds__(BA_THREADS) void ba_prep_kernel(BaArgs a) {
+  const int t = blockIdx.x * BA_THREADS + threadIdx.x;
+  if (t >= a.T || a.out.pt_act[t] == 0) return;
+  int beg, len;
+  if (!ba_range(a, t, beg, len)) return;                       // (never: the point is active)
+  for (int o = beg; o < beg + len; ++o) {
+    const int m = a.out.obs_act[o] != 0 ? ba_moving_slot(a, a.obs_image[o]) : -1;
+    int dup = 0;
+    for (int o2 = beg; o2 < o && m >= 0; ++o2) dup += a.out.obs_mslot[o2] == m ? 1 : 0;
+    a.out.obs_mslot[o] = m, a.out.obs_dup[o] = dup;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- point
+__global__ __launch_bounds__(BA_THREADS) void ba_point_kernel(BaArgs a) {
+  const int t = blockIdx.x * BA_THREADS + threadIdx.x;
+  const BaState* st = a.out.st;
+  if (t >= a.T || st->stop || a.out.pt_act[t] == 0) return;
+  int beg, len;
+  if (!ba_range(a, t, beg, len)) return;                       // (never: the point is active)
+  const double lambda = st->lambda;
+  const double* cams = ba_cams(a, st->cur);
+  const double* Xp = ba_xyz(a, st->cur) + (int64_t)3 * t;
+  const double X[3] = {Xp[0], Xp[1], Xp[2]};
+  double V[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, g[3] = {0.0, 0.0, 0.0};
+  for (int o = beg; o < beg + len; ++o) {
+    if (a.out.obs_act[o] == 0) continue;
+    const int k = a.obs_image[o];
+    const int64_t node = a.out.obs_node[o];
+    BaJac J;
+    double ru, rv, z;
+    ba_observe<true>(cams + (int64_t)BA_CAM * k, X, (double)a.kpts[2 * node], (double)a.kpts[2 * node + 1], ru, rv, z, &J);
+    if (a.huber > 0.0) {
+      const double e = sqrt(ru * ru + rv * rv);
+      if (e > a.huber) {
+        const double sw = sqrt(a.huber / e);
+        ru = ru * sw, rv = rv * sw;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) J.ju[j] = J.ju[j] * sw, J.jv[j] = J.jv[j] * sw;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) J.pu[j] = J.pu[j] * sw, J.pv[j] = J.pv[j] * sw;
+      }
+    }
+    V[0] += J.pu[0] * J.pu[0] + J.pv[0] * J.pv[0], V[1] += J.pu[0] * J.pu[1] + J.pv[0] * J.pv[1], V[2] += J.pu[0] * J.pu[2] + J.pv[0] * J.pv[2];
+    V[3] += J.pu[1] * J.pu[1] + J.pv[1] * J.pv[1], V[4] += J.pu[1] * J.pu[2] + J.pv[1] * J.pv[2], V[5] += J.pu[2] * J.pu[2] + J.pv[2] * J.pv[2];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) g[j] += J.pu[j] * ru + J.pv[j] * rv;
+    double* rec = a.out.obs_rec + (int64_t)BA_REC * o;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) rec[j] = J.ju[j], rec[6 + j] = J.jv[j];
+    rec[12] = ru, rec[13] = rv;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) rec[14 + j] = J.pu[j], rec[17 + j] = J.pv[j];      // (until the second pass below)
+  }
+  V[0] += lambda * fmax(V[0], 1e-6), V[3] += lambda * fmax(V[3], 1e-6), V[5] += lambda * fmax(V[5], 1e-6);
+  const double c00 = V[3] * V[5] - V[4] * V[4], c01 = V[2] * V[4] - V[1] * V[5], c02 = V[1] * V[4] - V[2] * V[3];
+  const double c11 = V[0] * V[5] - V[2] * V[2], c12 = V[1] * V[2] - V[0] * V[4], c22 = V[0] * V[3] - V[1] * V[1];
+  const double det = V[0] * c00 + V[1] * c01 + V[2] * c02;
+  if (!(ba_finite(det) && det > 0.0)) atomicOr(&a.out.st->flags, BA_F_IRREGULAR);
+  const double I[3][3] = {{c00 / det, c01 / det, c02 / det}, {c01 / det, c11 / det, c12 / det}, {c02 / det, c12 / det, c22 / det}};
+  double* pr = a.out.pt_rec + (int64_t)BA_PT * t;
+  pr[0] = I[0][0], pr[1] = I[0][1], pr[2] = I[0][2], pr[3] = I[1][1], pr[4] = I[1][2], pr[5] = I[2][2];
+  pr[6] = g[0], pr[7] = g[1], pr[8] = g[2];
+  if (a.n_free == 0) return;
+  for (int o = beg; o < beg + len; ++o) {
+    if (a.out.obs_act[o] == 0 || ba_moving_slot(a, a.obs_image[o]) < 0) continue;
+    double* rec = a.out.obs_rec + (int64_t)BA_REC * o;
+    const double pu[3] = {rec[14], rec[15], rec[16]}, pv[3] = {rec[17], rec[18], rec[19]};
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+      const double ju = rec[c], jv = rec[6 + c];
+      const double w[3] = {ju * pu[0] + jv * pv[0], ju * pu[1] + jv * pv[1], ju * pu[2] + jv * pv[2]};
+#pragma unroll
+      for (int m = 0; m < 3; ++m) {
+        rec[14 + 3 * c + m] = w[m];
+        rec[32 + 3 * c + m] = w[0] * I[0][m] + w[1] * I[1][m] + w[2] * I[2][m];
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- camera
+// One wave per slot.  U and g_c: the lane's own sum over its observations of the list (lane, lane + 64, ...), then a butterfly.  The block
+// row of S: the observations of the list one after the other; for each, lane j takes observation j of its track and subtracts its 6 x 6
+// block from the column block of its slot (different slots: different entries; the same slot: in turn), lanes 0 .. 5 the right-hand side.
+__global__ __launch_bounds__(64) void ba_camera_kernel(BaArgs a) {
+  __shared__ double s_row[6 * 6 * BA_MAX_FREE], s_b[6];
+  const int s = blockIdx.x, lane = threadIdx.x, n = 6 * a.n_free;
+  const BaState* st = a.out.st;
+  if (st->stop) return;
+  double* Srow = a.out.S + (int64_t)6 * s * n;
+  if (a.out.held[s]) {                                         // a held camera does not move: an identity block, a zero right-hand side
+    for (int e = lane; e < 6 * n; e += 64) Srow[e] = e % n == 6 * s + e / n ? 1.0 : 0.0;
+    if (lane < 6) a.out.rhs[6 * s + lane] = 0.0;
+    return;
+  }
+  const int first = a.out.slot_ptr[s];
+  int cnt = a.out.slot_ptr[s + 1] - first;
+  if (first < 0 || cnt < 0 || first + cnt > a.n_obs) cnt = 0;   // (never: ba_slots_kernel wrote them)
+  const int32_t* list = a.out.cam_list + first;
+  double acc[27];
+#pragma unroll
+  for (int j = 0; j < 27; ++j) acc[j] = 0.0;
+  for (int idx = lane; idx < cnt; idx += 64) {
+    const int o = list[idx];
+    if (o < 0 || o >= a.n_obs) continue;                       // (never)
+    const double* rec = a.out.obs_rec + (int64_t)BA_REC * o;
+    double ju[6], jv[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) ju[j] = rec[j], jv[j] = rec[6 + j];
+    const double ru = rec[12], rv = rec[13];
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = i; j < 6; ++j) acc[k++] += ju[i] * ju[j] + jv[i] * jv[j];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) acc[21 + i] += ju[i] * ru + jv[i] * rv;
+  }
+#pragma unroll
+  for (int j = 0; j < 27; ++j)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc[j] += __shfl_xor(acc[j], o, 64);
+  for (int e = lane; e < 6 * n; e += 64) s_row[e] = 0.0;
+  __syncthreads();
+  const double lambda = st->lambda;
+  if (lane < 36) {
+    const int r = lane / 6, c = lane % 6, i = r < c ? r : c, j = r < c ? c : r;
+    double u = 0.0;
+    int k = 0;
+#pragma unroll
+    for (int p = 0; p < 6; ++p)
+#pragma unroll
+      for (int q = p; q < 6; ++q) {
+        if (p == i && q == j) u = acc[k];
+        ++k;
+      }
+    if (r == c) u += lambda * fmax(u, 1e-6);
+    s_row[r * n + 6 * s + c] = u;
+  } else if (lane < 42) {
+    double gc = 0.0;
+#pragma unroll
+    for (int p = 0; p < 6; ++p)
+      if (p == lane - 36) gc = acc[21 + p];
+    s_b[lane - 36] = -gc;
+  }
+  __syncthreads();
+  for (int idx = 0; idx < cnt; ++idx) {
+    const int o = list[idx];
+    if (o < 0 || o >= a.n_obs) continue;                       // (never; the same for every lane)
+    const int p = a.out.obs_track[o];
+    int beg, len;
+    if (p < 0 || p >= a.T || !ba_range(a, p, beg, len)) continue;
+    const double* rec = a.out.obs_rec + (int64_t)BA_REC * o;
+    double y[18];
+#pragma unroll
+    for (int j = 0; j < 18; ++j) y[j] = rec[32 + j];           // (one address for the wave)
+    if (lane < 6) {
+      const double* gp = a.out.pt_rec + (int64_t)BA_PT * p + 6;
+      double v = 0.0;
+#pragma unroll
+      for (int r = 0; r < 6; ++r)
+        if (r == lane) v = (y[3 * r] * gp[0] + y[3 * r + 1] * gp[1]) + y[3 * r + 2] * gp[2];
+      s_b[lane] += v;
+    }
+    // lane j takes observation j of the track (in passes of 64): its whole 6 x 6 block, into the column block of its own slot; two
+    // observations of the track in one slot go in turn, the earlier first (obs_dup), so every entry keeps the order of the specification
+    for (int o0 = 0; o0 < len; o0 += 64) {
+      const int o2 = beg + o0 + lane;
+      const int k2 = o0 + lane < len ? a.out.obs_mslot[o2] : -1;
+      const int dup = k2 >= 0 ? a.out.obs_dup[o2] : 0;
+      double w[18];
+      if (k2 >= 0 && k2 < a.n_free) {
+        const double* wr = a.out.obs_rec + (int64_t)BA_REC * o2 + 14;
+#pragma unroll
+        for (int j = 0; j < 18; ++j) w[j] = wr[j];
+      }
+      bool pending = k2 >= 0 && k2 < a.n_free;
+      for (int rk = 0; __ballot(pending) != 0ull; ++rk) {
+        if (pending && dup <= rk) {
+          double* dst = s_row + 6 * k2;
+#pragma unroll
+          for (int r = 0; r < 6; ++r)
+#pragma unroll
+            for (int c = 0; c < 6; ++c) dst[r * n + c] -= (y[3 * r] * w[3 * c] + y[3 * r + 1] * w[3 * c + 1]) + y[3 * r + 2] * w[3 * c + 2];
+          pending = false;
+        }
+        __builtin_amdgcn_wave_barrier();
+      }
+    }
+  }
+  __syncthreads();
+  for (int e = lane; e < 6 * n; e += 64) Srow[e] = s_row[e];
+  if (lane < 6) a.out.rhs[6 * s + lane] = s_b[lane];
+}
+
+// ---------------------------------------------------------------------------------------------- solve
+// S = L L^T in place (the lower triangle), column by column: the pivot, the column, then the trailing rows; every entry (i, k) loses
+// L[i][j] L[k][j] for j ascending, one product at a time.  L y = b by columns (j ascending), L^T d = y by rows (j descending).
+__global__ __launch_bounds__(BA_SOLVE_THREADS) void ba_solve_kernel(BaArgs a) {
+  __shared__ double s_col[6 * BA_MAX_FREE], s_b[6 * BA_MAX_FREE], s_y[6 * BA_MAX_FREE];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, n = 6 * a.n_free;
+  BaState* st = a.out.st;
+  if (st->stop) return;
+  double* S = a.out.S;
+  bool regular = (st->flags & BA_F_IRREGULAR) == 0;            // a point's V* was not regular: there is nothing to solve
+  for (int i = t; i < n; i += BA_SOLVE_THREADS) s_b[i] = a.out.rhs[i];
+  __syncthreads();
+  for (int j = 0; j < n && regular; ++j) {
+    const double d = S[(int64_t)j * n + j];
+    __syncthreads();
+    if (!(ba_finite(d) && d > 0.0)) {                          // the same for every thread
+      regular = false;
+      break;
+    }
+    const double l = sqrt(d);
+    for (int i = j + t; i < n; i += BA_SOLVE_THREADS) {
+      const double v = i == j ? l : S[(int64_t)i * n + j] / l;
+      S[(int64_t)i * n + j] = v;
+      s_col[i] = v;
+    }
+    __syncthreads();
+    for (int i = j + 1 + wave; i < n; i += BA_SOLVE_THREADS / 64) {
+      const double li = s_col[i];
+      for (int k = j + 1 + lane; k <= i; k += 64) S[(int64_t)i * n + k] -= li * s_col[k];
+    }
+    __syncthreads();
+  }
+  if (regular) {
+    for (int j = 0; j < n; ++j) {
+      const double yj = s_b[j] / S[(int64_t)j * n + j];
+      if (t == 0) s_y[j] = yj;
+      for (int i = j + 1 + t; i < n; i += BA_SOLVE_THREADS) s_b[i] -= S[(int64_t)i * n + j] * yj;
+      __syncthreads();
+    }
+    for (int j = n - 1; j >= 0; --j) {
+      const double xj = s_y[j] / S[(int64_t)j * n + j];
+      if (t == 0) s_b[j] = xj;
+      for (int k = t; k < j; k += BA_SOLVE_THREADS) s_y[k] -= S[(int64_t)j * n + k] * xj;
+      __syncthreads();
+    }
+  }
+  for (int i = t; i < n; i += BA_SOLVE_THREADS) a.out.rhs[i] = regular ? s_b[i] : 0.0;
+  if (!regular) {
+    if (t == 0) atomicOr(&st->flags, BA_F_IRREGULAR);
+    return;
+  }
+  if (t < a.n_free && a.out.held[t] == 0) {                    // the candidate camera of slot t, into the buffer that is not current
+    const int cam = a.out.slot_cam[t];
+    const double* cur = ba_cams(a, st->cur) + (int64_t)BA_CAM * cam;
+    double* cand = ba_cams(a, st->cur ^ 1) + (int64_t)BA_CAM * cam;
+    const double* d = s_b + 6 * t;
+    const double th2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2], th = sqrt(th2);
+    const double ca = th > 1e-8 ? sin(th) / th : 1.0, cb = th > 1e-8 ? (1.0 - cos(th)) / th2 : 0.5;
+    const double W[3][3] = {{0.0, -d[2], d[1]}, {d[2], 0.0, -d[0]}, {-d[1], d[0], 0.0}};
+    bool fin = true;
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) {
+        double ex[3];
+        for (int m = 0; m < 3; ++m) ex[m] = (i == m ? 1.0 : 0.0) + ca * W[i][m] + cb * (W[i][0] * W[0][m] + W[i][1] * W[1][m] + W[i][2] * W[2][m]);
+        const double v = ex[0] * cur[4 + j] + ex[1] * cur[7 + j] + ex[2] * cur[10 + j];
+        cand[4 + 3 * i + j] = v;
+        fin = fin && ba_finite(v);
+      }
+    for (int i = 0; i < 3; ++i) {
+      const double v = cur[13 + i] + d[3 + i];
+      cand[13 + i] = v;
+      fin = fin && ba_finite(v);
+    }
+    if (!fin) atomicOr(&st->flags, BA_F_NOT_FINITE);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- back substitution, cost
+// initial: the cost of the current state.  Otherwise: the candidate point of the track into the buffer that is not current, and the
+// candidate's cost over the track's observations.
+__global__ __launch_bounds__(BA_THREADS) void ba_back_kernel(BaArgs a, int initial) {
+  const int t = blockIdx.x * BA_THREADS + threadIdx.x;
+  BaState* st = a.out.st;
+  if (t >= a.T || st->stop || a.out.pt_act[t] == 0) return;
+  int beg, len;
+  if (!ba_range(a, t, beg, len)) return;                       // (never: the point is active)
+  const int which = initial ? st->cur : st->cur ^ 1;
+  const double* cams = ba_cams(a, which);
+  double X[3];
+  if (initial) {
+    for (int m = 0; m < 3; ++m) X[m] = ba_xyz(a, which)[(int64_t)3 * t + m];
+  } else {
+    const double* pr = a.out.pt_rec + (int64_t)BA_PT * t;
+    double s[3] = {pr[6], pr[7], pr[8]};
+    if (a.n_free > 0)
+      for (int o = beg; o < beg + len; ++o) {
+        if (a.out.obs_act[o] == 0) continue;
+        const int k = ba_moving_slot(a, a.obs_image[o]);
+        if (k < 0) continue;
+        const double *w = a.out.obs_rec + (int64_t)BA_REC * o + 14, *dc = a.out.rhs + 6 * k;
+        for (int c = 0; c < 6; ++c)
+#pragma unroll
+          for (int m = 0; m < 3; ++m) s[m] += w[3 * c + m] * dc[c];
+      }
+    const double I[3][3] = {{pr[0], pr[1], pr[2]}, {pr[1], pr[3], pr[4]}, {pr[2], pr[4], pr[5]}};
+    const double* cur = ba_xyz(a, st->cur) + (int64_t)3 * t;
+    bool fin = true;
+    for (int m = 0; m < 3; ++m) {
+      X[m] = cur[m] + -(I[m][0] * s[0] + I[m][1] * s[1] + I[m][2] * s[2]);
+      ba_xyz(a, which)[(int64_t)3 * t + m] = X[m];
+      fin = fin && ba_finite(X[m]);
+    }
+    if (!fin) atomicOr(&st->flags, BA_F_NOT_FINITE);
+  }
+  double cost = 0.0;
+  bool front = true;
+  for (int o = beg; o < beg + len; ++o) {
+    if (a.out.obs_act[o] == 0) continue;
+    const int64_t node = a.out.obs_node[o];
+    double ru, rv, z;
+    ba_observe<false>(cams + (int64_t)BA_CAM * a.obs_image[o], X, (double)a.kpts[2 * node], (double)a.kpts[2 * node + 1], ru, rv, z, nullptr);
+    front = front && z > 0.0;
+    cost += ba_rho(ru * ru + rv * rv, a.huber);
+  }
+  a.out.trackcost[t] = cost;
+  if (!front) atomicOr(&st->flags, BA_F_BEHIND);
+}
+
+// ---------------------------------------------------------------------------------------------- decide
+__global__ __launch_bounds__(BA_THREADS) void ba_decide_kernel(BaArgs a, int round) {
+  __shared__ double s_part[BA_THREADS / 64];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  BaState* st = a.out.st;
+  double v = 0.0;
+  for (int i = t; i < a.T; i += BA_THREADS) v += a.out.pt_act[i] ? a.out.trackcost[i] : 0.0;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if (lane == 0) s_part[wave] = v;
+  __syncthreads();
+  if (t != 0) return;
+  double total = s_part[0];
+  for (int w = 1; w < BA_THREADS / 64; ++w) total += s_part[w];
+  if (round < 0) {                                             // the starting cost
+    if (st->flags != 0 || !ba_finite(total)) st->status |= BA_BAD_START;
+    if (st->status != 0) st->stop = 1;
+    st->cost = st->status != 0 ? 0.0 : total;
+    st->flags = 0;
+    a.out.history[0] = st->cost, a.out.history[1] = st->lambda;
+    return;
+  }
+  int take = 0;
+  if (!st->stop) {
+    take = st->flags == 0 && ba_finite(total) && (float)total < (float)st->cost ? 1 : 0;
+    if (take) {
+      st->cost = total, st->cur ^= 1, st->rejects = 0, st->taken += 1;
+      st->lambda = fmax(st->lambda / 10.0, 1e-12);
+    } else {
+      st->lambda = fmin(10.0 * st->lambda, 1e12);
+      if (++st->rejects >= BA_MAX_REJECTS) st->stop = 1;
+    }
+    st->flags = 0;
+  }
+  a.out.history[2 * (round + 1)] = st->cost, a.out.history[2 * (round + 1) + 1] = st->lambda;
+  a.out.taken[round] = (uint8_t)take;
+}
+
+// ---------------------------------------------------------------------------------------------- finish
+__global__ __launch_bounds__(BA_THREADS) void ba_finish_kernel(BaArgs a) {
+  const int64_t i = (int64_t)blockIdx.x * BA_THREADS + threadIdx.x;
+  const BaState* st = a.out.st;
+  const int cur = st->cur;
+  if (i == 0) {
+    int32_t* c = a.out.counters;
+    c[BA_N_FREE] = a.n_free - st->n_held, c[BA_N_FIXED] = a.n_fixed, c[BA_N_HELD] = st->n_held, c[BA_N_POINTS] = st->n_points;
+    c[BA_N_ACTIVE_OBS] = st->n_act, c[BA_N_BAD_OBS] = st->n_bad, c[BA_ROUNDS_TAKEN] = st->taken, c[BA_STATUS] = st->status;
+  }
+  if (i < a.n_images && cur == 1 && a.out.slot_of[i] >= 0)
+    for (int j = 4; j < 16; ++j) a.out.cams[i * BA_CAM + j] = a.out.cams1[i * BA_CAM + j];
+  if (i >= a.T || a.out.pt_act[i] == 0) return;
+  int beg, len;
+  if (!ba_range(a, (int)i, beg, len)) return;                  // (never: the point is active)
+  double X[3];
+  for (int m = 0; m < 3; ++m) X[m] = ba_xyz(a, cur)[i * 3 + m];
+  if (cur == 1)
+    for (int m = 0; m < 3; ++m) a.out.xyz[i * 3 + m] = X[m];
+  if (st->status != 0) return;                                 // nothing was computed: every obs_error stays -1
+  const double* cams = ba_cams(a, cur);                        // (buffer 1 when cur == 1: the copy above touches buffer 0 only)
+  for (int o = beg; o < beg + len; ++o) {
+    if (a.out.obs_act[o] == 0) continue;
+    const int64_t node = a.out.obs_node[o];
+    double ru, rv, z;
+    ba_observe<false>(cams + (int64_t)BA_CAM * a.obs_image[o], X, (double)a.kpts[2 * node], (double)a.kpts[2 * node + 1], ru, rv, z, nullptr);
+    const double err = sqrt(ru * ru + rv * rv);
+    a.out.obs_error[o] = z > 0.0 && err == err ? (err < (double)FLT_MAX ? (float)err : FLT_MAX) : -1.f;
+  }
+}
+
+// GIMS_AUX_BUNDLE_ADJUST of gims_run_ops (include/gims_hip.h): every argument check precedes the first HIP call
+int bundle_adjust_aux(const gims_aux_args& x, hipStream_t st) {
+  const int64_t T = x.i[0], n_obs = x.i[1], n_images = x.i[2], N = x.i[3], iters = x.i[4];
+  const float huber = x.f[0], lambda0 = x.f[1];
+  // i[5] is where a later form of this function (a blocked or iterative reduced solve) would be selected: it is read FIRST
+  GIMS_CHECK_ARG(x.i[5] == 0, "gims_run_ops: unknown auxiliary function form: bundle_adjust with i[5] = %lld (i[5] is reserved and must be 0)",
+                 (long long)x.i[5]);
+  GIMS_CHECK_ARG(T >= 0 && T <= (1 << 30), "bundle_adjust: T = %lld is out of range (0 .. 2^30)", (long long)T);
+  GIMS_CHECK_ARG(n_obs >= 0 && n_obs <= (1 << 30), "bundle_adjust: n_obs = %lld is out of range (0 .. 2^30)", (long long)n_obs);
+  GIMS_CHECK_ARG(n_images >= 0 && n_images <= (1 << 24), "bundle_adjust: n_images = %lld is out of range (0 .. 2^24)", (long long)n_images);
+  GIMS_CHECK_ARG(N >= 0 && N <= (1 << 30), "bundle_adjust: N = %lld is out of range (0 .. 2^30)", (long long)N);
+  GIMS_CHECK_ARG(iters >= 0 && iters <= 255, "bundle_adjust: iters = %lld is out of range (0 .. 255)", (long long)iters);
+  GIMS_CHECK_ARG(huber - huber == 0.f && huber >= 0.f, "bundle_adjust: huber = %g must be finite and >= 0", (double)huber);
+  GIMS_CHECK_ARG(lambda0 - lambda0 == 0.f && lambda0 > 0.f, "bundle_adjust: lambda0 = %g must be finite and > 0", (double)lambda0);
+  GIMS_CHECK_ARG(x.p[5], "bundle_adjust: the output buffer is NULL");
+  GIMS_CHECK_ARG(x.p[0], "bundle_adjust: the table is NULL");
+  GIMS_CHECK_ARG(((uintptr_t)x.p[5] & 15) == 0, "bundle_adjust: the output buffer must be 16-byte aligned");
+  GIMS_CHECK_ARG((((uintptr_t)x.p[0] | (uintptr_t)x.p[2] | (uintptr_t)x.p[3]) & 7) == 0, "bundle_adjust: the table, xyz and cams must be 8-byte aligned");
+  GIMS_CHECK_ARG((((uintptr_t)x.p[1] | (uintptr_t)x.p[4]) & 3) == 0, "bundle_adjust: kpts and mode must be 4-byte aligned");
+  const int64_t* tab = (const int64_t*)x.p[0];                 // a HOST array, like the op table itself
+  GIMS_CHECK_ARG(tab[5] == 0 && tab[6] == 0 && tab[7] == 0, "bundle_adjust: the table words 5 .. 7 are reserved and must be 0");
+  GIMS_CHECK_ARG(((tab[0] | tab[1] | tab[2]) & 3) == 0, "bundle_adjust: indptr, obs_image and obs_keypoint must be 4-byte aligned");
+  GIMS_CHECK_ARG(T == 0 || (tab[0] && tab[1] && tab[2] && tab[3] && tab[4] && x.p[1] && x.p[2]),
+                 "bundle_adjust: indptr, obs_image, obs_keypoint, obs_use, point_use, kpts or xyz is NULL while T = %lld", (long long)T);
+  GIMS_CHECK_ARG(n_images == 0 || (x.p[3] && x.p[4]), "bundle_adjust: cams or mode is NULL while n_images = %lld", (long long)n_images);
+  const int32_t* mode = (const int32_t*)x.p[4];                // a HOST array too: the number of free cameras sizes the reduced system
+  std::vector<int32_t> slot_of((size_t)n_images), slot_cam;
+  int64_t n_fixed = 0;
+  for (int64_t k = 0; k < n_images; ++k) {
+    GIMS_CHECK_ARG(mode[k] >= 0 && mode[k] <= 2, "bundle_adjust: image %lld: mode = %d is out of range (0 absent, 1 fixed, 2 free)", (long long)k, mode[k]);
+    slot_of[(size_t)k] = mode[k] == 0 ? BA_ABSENT : mode[k] == 1 ? BA_FIXED : (int32_t)slot_cam.size();
+    if (mode[k] == 2) slot_cam.push_back((int32_t)k);
+    n_fixed += mode[k] == 1;
+  }
+  const int64_t n_free = (int64_t)slot_cam.size();
+  GIMS_CHECK_ARG(n_free <= BA_MAX_FREE, "bundle_adjust: %lld free cameras, at most GIMS_BA_MAX_FREE_CAMERAS = %d (a larger set needs the blocked reduced solve)",
+                 (long long)n_free, BA_MAX_FREE);
+
+  BaArgs a;
+  ba_layout((void*)x.p[5], T, n_obs, n_images, iters, n_free, a.out);
+  a.indptr = (const int32_t*)tab[0], a.obs_image = (const int32_t*)tab[1], a.obs_keypoint = (const int32_t*)tab[2];
+  a.obs_use = (const uint8_t*)tab[3], a.point_use = (const uint8_t*)tab[4];
+  a.kpts = (const float*)x.p[1], a.xyz_in = (const double*)x.p[2], a.cams_in = (const double*)x.p[3];
+  a.T = (int)T, a.n_obs = (int)n_obs, a.n_images = (int)n_images, a.iters = (int)iters, a.n_free = (int)n_free, a.n_fixed = (int)n_fixed;
+  a.N = N, a.huber = (double)huber, a.lambda0 = (double)lambda0;
+  GIMS_HIP(hipMemsetAsync(a.out.st, 0, 256, st));
+  if (iters > 0) GIMS_HIP(hipMemsetAsync(a.out.taken, 0, (size_t)iters, st));
+  if (n_obs > 0) {
+    GIMS_HIP(hipMemsetD32Async((hipDeviceptr_t)a.out.obs_error, (int)0xBF800000u, (size_t)n_obs, st));      // -1.f
+    GIMS_HIP(hipMemsetAsync(a.out.obs_act, 0, (size_t)n_obs, st));
+  }
+  if (n_images > 0) {
+    const int rc = upload_table(slot_of.data(), sizeof(int32_t) * (size_t)n_images, a.out.slot_of, st);
+    if (rc != GIMS_OK) return rc;
+  }
+  if (n_free > 0) {
+    const int rc = upload_table(slot_cam.data(), sizeof(int32_t) * (size_t)n_free, a.out.slot_cam, st);
+    if (rc != GIMS_OK) return rc;
+  }
+  const int64_t most = T > n_images ? T : n_images;
+  const unsigned g_all = (unsigned)(most > 0 ? cdiv(most, BA_THREADS) : 1), g_T = (unsigned)(T > 0 ? cdiv(T, BA_THREADS) : 1);
+  ba_init_kernel<<<g_all, BA_THREADS, 0, st>>>(a);
+  GIMS_LAUNCH_CHECK();
+  ba_classify_kernel<<<g_T, BA_THREADS, 0, st>>>(a);
+  GIMS_LAUNCH_CHECK();
+  ba_slots_kernel<<<1, BA_MAX_FREE, 0, st>>>(a);
+  GIMS_LAUNCH_CHECK();
+  if (n_free > 0) {
+    ba_fill_kernel<<<(unsigned)n_free, BA_THREADS, 0, st>>>(a);
+    GIMS_LAUNCH_CHECK();
+    ba_prep_kernel<<<g_T, BA_THREADS, 0, st>>>(a);
+    GIMS_LAUNCH_CHECK();
+  }
+  ba_back_kernel<<<g_T, BA_THREADS, 0, st>>>(a, 1);
+  GIMS_LAUNCH_CHECK();
+  ba_decide_kernel<<<1, BA_THREADS, 0, st>>>(a, -1);
+  GIMS_LAUNCH_CHECK();
+  for (int r = 0; r < (int)iters; ++r) {
+    ba_point_kernel<<<g_T, BA_THREADS, 0, st>>>(a);
+    GIMS_LAUNCH_CHECK();
+    if (n_free > 0) {
+      ba_camera_kernel<<<(unsigned)n_free, 64, 0, st>>>(a);
+      GIMS_LAUNCH_CHECK();
+      ba_solve_kernel<<<1, BA_SOLVE_THREADS, 0, st>>>(a);
+      GIMS_LAUNCH_CHECK();
+    }
+    ba_back_kernel<<<g_T, BA_THREADS, 0, st>>>(a, 0);
+    GIMS_LAUNCH_CHECK();
+    ba_decide_kernel<<<1, BA_THREADS, 0, st>>>(a, r);
+    GIMS_LAUNCH_CHECK();
+  }
+  ba_finish_kernel<<<g_all, BA_THREADS, 0, st>>>(a);
+  GIMS_LAUNCH_CHECK();
+  return GIMS_OK;
+}
+
+}  // namespace gims

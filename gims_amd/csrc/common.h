@@ -182,6 +182,8 @@ int build_tracks_aux(const gims_aux_args& x, hipStream_t st);
 int triangulate_tracks_aux(const gims_aux_args& x, hipStream_t st);
 // resect.hip: GIMS_AUX_RESECT_IMAGES, likewise
 int resect_images_aux(const gims_aux_args& x, hipStream_t st);
+// ba.hip: GIMS_AUX_BUNDLE_ADJUST, likewise
+int bundle_adjust_aux(const gims_aux_args& x, hipStream_t st);
 
 // sinkhorn2d.hip: the 2-D on-chip Sinkhorn (all iterations in one launch; see that file's header)
 struct OtR2Host { const float* z; int64_t ld; int n, m; float* u; float* v; float* status; float norm, log_mu_bin, log_nu_bin; };

@@ -82,6 +82,11 @@ AUX_RESECT_IMAGES = _K["GIMS_AUX_RESECT_IMAGES"]             # absolute poses fr
 RESECT_CAMERA_WORDS = _K["GIMS_RESECT_CAMERA_WORDS"]
 RESECT_HB = _K["GIMS_RESECT_HB"]                             # hypotheses per workgroup of the scoring kernel: the seam of `iters`
 RESECT_COUNTERS = ("n_ok", "n_failed", "n_corr_total", "n_inlier_total")
+AUX_BUNDLE_ADJUST = _K["GIMS_AUX_BUNDLE_ADJUST"]             # joint refinement of cameras and points (bundle adjustment): likewise; 12 is unassigned
+BA_TABLE_WORDS, BA_MAX_FREE_CAMERAS, BA_MAX_REJECTS = _K["GIMS_BA_TABLE_WORDS"], _K["GIMS_BA_MAX_FREE_CAMERAS"], _K["GIMS_BA_MAX_REJECTS"]
+BA_COUNTERS = ("n_free", "n_fixed", "n_held", "n_points", "n_active_obs", "n_bad_obs", "rounds_taken", "status")
+BA_BAD_CAMERA, BA_BAD_START = 1, 2                           # the bits of the status counter
+BA_ABSENT, BA_FIXED, BA_FREE = 0, 1, 2                       # the modes of a camera
 SIFT_MAX_OCTAVES, SIFT_MAX_RADIUS, SIFT_SLOTS = _K["GIMS_SIFT_MAX_OCTAVES"], _K["GIMS_SIFT_MAX_RADIUS"], _K["GIMS_SIFT_SLOTS"]
 
 
@@ -1335,12 +1340,17 @@ def triangulate_views(out: torch.Tensor, T: int, n_obs: int) -> dict:
 def triangulate_tracks(indptr, obs_image, obs_keypoint, kpts, cams: np.ndarray, thresh: float = 4.0, min_angle: float = 1.5, max_hyp: int = 64,
                        refine_iters: int = 10):
     """Robust triangulation of every track on the device (csrc/triangulate.hip): device tensors as op_triangulate_tracks takes
-    them, cams the HOST records of triangulate_cameras.  -> (the views of triangulate_views, and what must stay alive until the launches have
-    run).  Asynchronous; no host read."""
+    them, cams the HOST records of triangulate_cameras, or the same records as a device tensor.  -> (the views of triangulate_views, and
+    what must stay alive until the launches have run).  Asynchronous; no host read."""
     device = indptr.device
     T, n_obs, n = indptr.numel() - 1, obs_image.numel(), kpts.shape[0]
-    rec = np.ascontiguousarray(cams, dtype=np.float64).reshape(-1, TRI_CAMERA_WORDS)
-    dev_cams = upload_large(rec.view(np.uint8).reshape(-1), device).view(torch.float64) if rec.size else torch.zeros(0, dtype=torch.float64, device=device)
+    if isinstance(cams, torch.Tensor):                           # the records already on the device (Adjusted.records of bundle_adjust): used where they lie
+        if cams.dtype != torch.float64 or cams.device != device or not cams.is_contiguous() or cams.numel() % TRI_CAMERA_WORDS:
+            raise ValueError(f"triangulate_tracks: device camera records must be a contiguous float64 tensor [n_images, 18] on {device}")
+        rec, dev_cams = cams.view(-1, TRI_CAMERA_WORDS), cams
+    else:
+        rec = np.ascontiguousarray(cams, dtype=np.float64).reshape(-1, TRI_CAMERA_WORDS)
+        dev_cams = upload_large(rec.view(np.uint8).reshape(-1), device).view(torch.float64) if rec.size else torch.zeros(0, dtype=torch.float64, device=device)
     out = torch.empty(triangulate_out_layout(T, n_obs)["bytes"], dtype=torch.uint8, device=device)
     run_ops(make_ops([op_triangulate_tracks(indptr, obs_image, obs_keypoint, kpts, dev_cams, out, T, n_obs, len(rec), n, thresh, min_angle, max_hyp,
                                             refine_iters)]))
@@ -1426,6 +1436,74 @@ def resect_images(track_of, xyz, use, kpts, cams: np.ndarray, thresh: float = 4.
     run_ops(make_ops([op_resect_images(track_of, xyz, use, kpts, rec, out, track_of.numel() if n is None else n, use.numel() if T is None else T, thresh, iters, lo_iters,
                                        min_inliers, seed)]))
     return resect_views(out, rec, iters), (rec, out, track_of, xyz, use, kpts)
+
+
+def ba_out_layout(T: int, n_obs: int, n_images: int, iters: int, n_free: int) -> dict:
+    """BYTE offsets into the one buffer of GIMS_AUX_BUNDLE_ADJUST (include/gims_hip.h; csrc/ba.hip ba_layout carves it): xyz float64 [T, 3],
+    cams float64 [n_images, 18], obs_error float32 [n_obs], cam_obs int32 [n_images], history float64 [iters + 1, 2], taken uint8 [iters],
+    counters int32 [8]; 'outputs' = the bytes of all of these = 'scratch', the offset of the kernels' scratch (which holds the 6 n_free square
+    reduced system), 'bytes' = the whole buffer.  Every region starts on a 256-byte boundary."""
+    al = lambda x: (x + 255) & ~255      # noqa: E731
+    n = 6 * n_free
+    off, at = {}, 0
+    for name, size in (("xyz", 24 * T), ("cams", 144 * n_images), ("obs_error", 4 * n_obs), ("cam_obs", 4 * n_images), ("history", 16 * (iters + 1)),
+                       ("taken", iters), ("counters", 32)):
+        off[name] = at
+        at += al(size)
+    off["outputs"] = off["scratch"] = at
+    off["bytes"] = at + (256 + al(4 * n_images) + 2 * al(4 * n_free) + al(4 * n_free + 4) + al(24 * T) + al(144 * n_images) + al(T) + al(n_obs)
+                         + 5 * al(4 * n_obs) + al(72 * T) + al(400 * n_obs) + al(8 * T) + al(8 * n * n) + al(8 * n))
+    return off
+
+
+def ba_table(indptr, obs_image, obs_keypoint, obs_use, point_use) -> np.ndarray:
+    """The HOST table of GIMS_AUX_BUNDLE_ADJUST, int64 [8]: the addresses of the five device arrays (tensors, raw addresses, or None) and
+    three reserved zeros.  The caller keeps it, and the tensors, alive for as long as the op is run."""
+    tab = np.zeros(BA_TABLE_WORDS, dtype=np.int64)
+    for k, t in enumerate((indptr, obs_image, obs_keypoint, obs_use, point_use)):
+        tab[k] = 0 if t is None else t if isinstance(t, int) else t.data_ptr()
+    return tab
+
+
+def op_bundle_adjust(table: np.ndarray, kpts, xyz, cams, mode: np.ndarray, out, T: int, n_obs: int, n: int, iters: int = 20, huber: float = 0.0,
+                     lambda0: float = 1e-4) -> Op:
+    """GIMS_AUX_BUNDLE_ADJUST as an op of gims_run_ops (include/gims_hip.h): the one way to reach it.  table: the HOST int64 [8] of ba_table;
+    kpts float32 [n, 2], xyz float64 [T, 3], cams float64 [n_images, 18] on the device; mode: HOST int32 [n_images] (0 absent, 1 fixed,
+    2 free; C-contiguous; the caller keeps both host arrays alive for as long as the op is run); out uint8
+    [ba_out_layout(T, n_obs, n_images, iters, n_free)['bytes']]."""
+    if not (isinstance(table, np.ndarray) and table.dtype == np.int64 and table.flags["C_CONTIGUOUS"] and table.size == BA_TABLE_WORDS):
+        raise ValueError("bundle_adjust: table must be a C-contiguous int64 host array [8] (ba_table)")
+    if not (isinstance(mode, np.ndarray) and mode.dtype == np.int32 and mode.flags["C_CONTIGUOUS"] and mode.ndim == 1):
+        raise ValueError("bundle_adjust: mode must be a C-contiguous int32 host array [n_images]")
+    return op_aux(AUX_BUNDLE_ADJUST, (table.ctypes.data, kpts, xyz, cams, mode.ctypes.data if mode.size else None, out),
+                  (T, n_obs, mode.size, n, int(iters), 0), (huber, lambda0))
+
+
+def ba_views(out: torch.Tensor, T: int, n_obs: int, n_images: int, iters: int, n_free: int) -> dict:
+    """The typed views of the op's buffer, by ba_out_layout."""
+    o = ba_out_layout(T, n_obs, n_images, iters, n_free)
+    cut = lambda name, size, dt: out[o[name]:o[name] + size].view(dt)      # noqa: E731
+    return dict(xyz=cut("xyz", 24 * T, torch.float64).view(T, 3), cams=cut("cams", 144 * n_images, torch.float64).view(n_images, TRI_CAMERA_WORDS),
+                obs_error=cut("obs_error", 4 * n_obs, torch.float32), cam_obs=cut("cam_obs", 4 * n_images, torch.int32),
+                history=cut("history", 16 * (iters + 1), torch.float64).view(iters + 1, 2), taken=cut("taken", iters, torch.uint8),
+                counters=cut("counters", 32, torch.int32))
+
+
+def bundle_adjust(indptr, obs_image, obs_keypoint, obs_use, point_use, kpts, xyz, cams, mode: np.ndarray, iters: int = 20, huber: float = 0.0,
+                  lambda0: float = 1e-4, T: int | None = None, n_obs: int | None = None, n: int | None = None):
+    """Joint refinement of the free cameras and the active points on the device (csrc/ba.hip): device tensors as
+    op_bundle_adjust takes them (cams the DEVICE records float64 [n_images, 18]), mode the HOST int32 [n_images]; T, n_obs, n: the sizes to
+    state when a tensor is a stand-in for an empty one (default: the tensors' own).  -> (the views of ba_views, and what must stay alive
+    until the launches have run).  Asynchronous; no host read."""
+    mode = np.ascontiguousarray(mode, dtype=np.int32).reshape(-1)
+    T = indptr.numel() - 1 if T is None else T
+    n_obs = obs_image.numel() if n_obs is None else n_obs
+    n = kpts.shape[0] if n is None else n
+    n_free = int((mode == BA_FREE).sum())
+    table = ba_table(indptr, obs_image, obs_keypoint, obs_use, point_use)
+    out = torch.empty(ba_out_layout(T, n_obs, mode.size, iters, n_free)["bytes"], dtype=torch.uint8, device=xyz.device)
+    run_ops(make_ops([op_bundle_adjust(table, kpts, xyz, cams, mode, out, T, n_obs, n, iters, huber, lambda0)]))
+    return ba_views(out, T, n_obs, mode.size, iters, n_free), (table, mode, out, indptr, obs_image, obs_keypoint, obs_use, point_use, kpts, xyz, cams)
 
 
 def patch_affine(kp4: torch.Tensor, kp_octave: torch.Tensor):

@@ -97,6 +97,19 @@ def _check(tracks, images, cameras, thresh, min_angle, max_hyp, refine_iters):
             raise ValueError(f"triangulate_tracks: image {k}: keypoints of shape {tuple(t.shape)}, the tracks were built over {start[k + 1] - start[k]} "
                              "keypoints ([n_k, 2])")
         kpts.append(t)
+    device = tracks.indptr.device
+    if isinstance(cameras, torch.Tensor):                        # the op's records on the device: Adjusted.records of bundle_adjust
+        if cameras.dtype != torch.float64 or tuple(cameras.shape) != (n_images, hip.TRI_CAMERA_WORDS) or cameras.device != device or device.type != "cuda":
+            raise ValueError(f"triangulate_tracks: device camera records must be a float64 tensor [{n_images}, {hip.TRI_CAMERA_WORDS}] on the tracks' "
+                             f"GPU, got {cameras.dtype} {tuple(cameras.shape)} on {cameras.device}")
+        for name in ("indptr", "obs_image", "obs_keypoint"):
+            x = getattr(tracks, name)
+            if x.dtype != torch.int32 or x.device != device:
+                raise ValueError(f"triangulate_tracks: tracks.{name} must be an int32 tensor on {device}, got {x.dtype} on {x.device}")
+        for k, x in enumerate(kpts):
+            if x.device != device:
+                raise ValueError(f"triangulate_tracks: image {k}: the keypoints are on {x.device}, the tracks on {device}")
+        return kpts, cameras.contiguous()
     if not isinstance(cameras, (tuple, list)) or len(cameras) != 3:
         raise ValueError("triangulate_tracks: cameras must be (K [n, 3, 3], R [n, 3, 3], t [n, 3])")
     K, R, t = _host(cameras[0], "K", (None, 3, 3)), _host(cameras[1], "R", (None, 3, 3)), _host(cameras[2], "t", (None, 3))
@@ -105,7 +118,6 @@ def _check(tracks, images, cameras, thresh, min_angle, max_hyp, refine_iters):
     if n_images and ((K[:, 0, 1] != 0).any() or (K[:, 1, 0] != 0).any() or (K[:, 2] != np.array([0.0, 0.0, 1.0])).any()):
         raise ValueError("triangulate_tracks: K must be [[fx, 0, cx], [0, fy, cy], [0, 0, 1]]: skew or another last row is not supported")
     counts = [start[k + 1] - start[k] for k in range(n_images)]
-    device = tracks.indptr.device
     for name in ("indptr", "obs_image", "obs_keypoint"):
         x = getattr(tracks, name)
         if x.dtype != torch.int32 or x.device != device:
@@ -124,8 +136,10 @@ def triangulate_tracks(tracks, images, cameras, *, thresh: float = 4.0, min_angl
     ``images``: the list the tracks were built over -- ``ImageFeatures`` (``.keypoints`` is read) or [n_k, 2] tensors of pixel coordinates;
     they are concatenated as ``Tracks.points`` does.  ``cameras``: ``(K [n, 3, 3], R [n, 3, 3], t [n, 3])`` as arrays or tensors, world to
     camera ``x_c = R X + t``; they are turned into the op's float64 records on the host (give them as host values: a device tensor is copied
-    back first, which waits for the device).  ``thresh``: the inlier bound in pixels; ``min_angle``: degrees; ``max_hyp``: the number of
-    two-view hypotheses per track (0: none, every observation enters the solve); ``refine_iters``: Gauss-Newton rounds.
+    back first, which waits for the device); or the op's own records as a device tensor float64 [n, 18] (``Adjusted.records`` of
+    ``bundle_adjust``), which are used where they lie, with no host step.  ``thresh``: the inlier bound in pixels; ``min_angle``: degrees;
+    ``max_hyp``: the number of two-view hypotheses per track (0: none, every observation enters the solve); ``refine_iters``: Gauss-Newton
+    rounds.
 
     ValueError, before the device is touched: a count that disagrees with ``tracks.image_start``, cameras of another shape or count, a K
     with skew or a last row other than (0, 0, 1), tensors of a wrong dtype or on different devices, a parameter out of range.

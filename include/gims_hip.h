@@ -593,7 +593,105 @@ int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t
  * wave-uniform LDS address.  finish: a workgroup per entry finds the best hypothesis, solves its sample again, runs stage 2 and the final
  * sweep.  The 27 sums of the normal equations and the inlier cost are a thread's own sum in ascending order, a butterfly over the wave, then
  * the waves in order; there are no float atomics, so the outputs of an entry are bit-identical alone or inside any batch, at any position,
- * and across runs.  Counters are integer atomics. */
+ * and across runs.  Counters are integer atomics.
+ *
+ * GIMS_AUX_BUNDLE_ADJUST is the seventh function of this table without a stand-alone entry point, for the same reason.  It refines the free
+ * cameras and the active points of the chain jointly: Levenberg-Marquardt rounds on the reprojection cost with the Schur complement over the
+ * points (bundle adjustment).  This library's own specification: the reference matches one pair and has no counterpart.
+ * kernels: ba_*_kernel, gims_amd/csrc/ba.hip; tests/ba_ref.py is the NumPy float64 restatement.  All arithmetic is float64, one operation
+ * at a time as written here (the file is compiled without contraction into fused multiply-adds).  (Number 12 is unassigned and refused.)
+ *   p[0] table  HOST int64 [GIMS_BA_TABLE_WORDS], 8-byte aligned, read during the call like the op table itself: the device addresses
+ *               {indptr int32 [T + 1], obs_image int32 [n_obs], obs_keypoint int32 [n_obs], obs_use uint8 [n_obs], point_use uint8 [T], 0, 0, 0}
+ *               (GIMS_AUX_BUILD_TRACKS gives the first three; obs_use and point_use are obs_inlier and status == 0 of
+ *               GIMS_AUX_TRIANGULATE_TRACKS, or the caller's choice).  The three reserved words must be 0.
+ *   p[1] kpts   device float [N][2]: the pixel (u, v) of every keypoint of every image, the images back to back
+ *   p[2] xyz    device double [T][3], 8-byte aligned: the starting points
+ *   p[3] cams   device double [n_images][GIMS_TRI_CAMERA_WORDS], 8-byte aligned: the starting cameras, the records of
+ *               GIMS_AUX_TRIANGULATE_TRACKS {fx, fy, cx, cy, R row-major [9], t [3], first node, n_k}, world to camera x_c = R X + t
+ *   p[4] mode   HOST int32 [n_images], read during the call: 0 ABSENT (the camera's observations are ignored), 1 FIXED, 2 FREE.  The free
+ *               cameras are counted before any HIP call: n_free sizes the reduced system and the scratch.  Free camera number s in image
+ *               order has SLOT s.  The modes travel to the device as kernel arguments: a captured graph holds their values.
+ *   p[5] out    device, 16-byte aligned, never NULL: one buffer, every region on a 256-byte boundary (al256(x) = (x + 255) & ~255), with
+ *               n = 6 n_free, in this order:
+ *                 double xyz [T][3] | double cams [n_images][18] | float obs_error [n_obs] | int32 cam_obs [n_images] |
+ *                 double history [iters + 1][2] | uint8 taken [iters] | int32 counters [8] |
+ *                 scratch: 256 bytes of state | int32 [n_images] | int32 [n_free] | int32 [n_free + 1] | int32 [n_free] | double [T][3] |
+ *                 double [n_images][18] | uint8 [T] | uint8 [n_obs] | int32 [n_obs] x 5 | double [T][9] |
+ *                 double [n_obs][50] | double [T] | double [n][n] | double [n]
+ *               that is al256(24 T) + al256(144 n_images) + al256(4 n_obs) + al256(4 n_images) + al256(16 (iters + 1)) + al256(iters) + 256
+ *               bytes of outputs and 256 + al256(4 n_images) + 2 al256(4 n_free) + al256(4 n_free + 4) + al256(24 T) + al256(144 n_images) +
+ *               al256(T) + al256(n_obs) + 5 al256(4 n_obs) + al256(72 T) + al256(400 n_obs) + al256(8 T) + al256(8 n^2) + al256(8 n) bytes of
+ *               scratch behind them (hip.ba_out_layout has the offsets).  The cams region has the format of p[3]: it can be handed to a later
+ *               GIMS_AUX_TRIANGULATE_TRACKS op as its p[4], and xyz to a later GIMS_AUX_RESECT_IMAGES op as its p[1].
+ *               counters = {n_free, n_fixed, n_held, n_points, n_active_obs, n_bad_obs, rounds_taken, status}.
+ *   i = {T, n_obs, n_images, N, iters, 0}     f = {huber (pixels; 0: the squared loss), lambda0}
+ * Activity.  Nothing in device memory is trusted.  A track whose indptr range descends or leaves 0 .. n_obs, or holds more than
+ *   GIMS_TRI_MAX_OBS observations, is INACTIVE and touches no observation.  Observation o of another track t, (image k, keypoint i) =
+ *   (obs_image, obs_keypoint)[o], is a CANDIDATE iff point_use[t] != 0, the three words of xyz[t] are finite, obs_use[o] != 0, 0 <= k <
+ *   n_images, mode[k] != 0, the 18 words of camera k are finite with fx > 0 and fy > 0, 0 <= i < n_k, the node g = first_k + i (in double)
+ *   lies in 0 .. N - 1 and the pixel (u, v) = kpts[g] is finite -- the rule of GIMS_AUX_TRIANGULATE_TRACKS; a value that fails its test is
+ *   never used as an index.  Point t is ACTIVE iff its track has at least two candidates; an observation is ACTIVE iff it is a candidate
+ *   of an active point.  cam_obs[k] = the active observations in image k.  A free camera with cam_obs < 4 is HELD: it does not move
+ *   (it keeps its slot: an identity block and a zero right-hand side in the reduced system) and its observations count as those of a
+ *   fixed camera.  n_free counts the free cameras that are not held, n_fixed the cameras of mode 1, n_points the active points;
+ *   n_bad_obs = the observations that are not active, over the tracks with a good range and at most GIMS_TRI_MAX_OBS observations.
+ * status.  Bit 1: a camera of mode 1 or 2 has a word that is not finite, or fx <= 0, or fy <= 0.  Bit 2: at the start an active
+ *   observation has z <= 0, or the cost is not finite.  With status != 0 the op changes nothing: xyz and cams equal the inputs, every
+ *   obs_error is -1, every history row is {0, lambda0}, taken and rounds_taken are 0; the other counters and cam_obs are as above.
+ * Model.  For an active observation with y = R X, x_c = y + t, z = x_c[2]: the residual r = (ru, rv) = (fx x_c[0] / z + cx - u,
+ *   fy x_c[1] / z + cy - v), e^2 = ru^2 + rv^2, and with au = fx / z, bu = -fx x_c[0] / z^2, av = fy / z, bv = -fy x_c[1] / z^2 the camera
+ *   Jacobian of GIMS_AUX_RESECT_IMAGES stage 2 for the update R <- exp([w]x) R, t <- t + dt in the order (w, dt),
+ *     Ju = (bu y1, au y2 - bu y0, -au y1, au, 0, bu),   Jv = (bv y1 - av y2, -bv y0, av y0, 0, av, bv),
+ *   and the point Jacobian Pu[m] = au R[0][m] + bu R[2][m], Pv[m] = av R[1][m] + bv R[2][m].  With huber > 0 and e = sqrt(e^2) > huber, ru,
+ *   rv and the eighteen Jacobian words are each multiplied by sqrt(huber / e) (iteratively reweighted least squares: the weight of the
+ *   observation is min(1, huber / e)).  cost = the sum over the active observations of rho(e^2): rho = e^2 when huber == 0 or e <= huber,
+ *   else (2 huber) e - huber huber.  The cost of a point is the sum over its active observations in ascending o; the cost is the sum of the
+ *   points' costs (inactive points give 0) in this order: thread j of 256 adds the points j, j + 256, ... ascending, the 64 threads of a
+ *   wave are summed by a butterfly (offsets 32, 16, .. 1), and the four waves are added in order.
+ * One round, at the current state (X, R, t), lambda and cost.  Per active point, over its active observations in ascending o:
+ *   V = sum (Pu Pu^T + Pv Pv^T) (each entry of the upper triangle: Pu[i] Pu[j] + Pv[i] Pv[j], added to the sum), g_p = sum (Pu ru + Pv rv);
+ *   V* = V with lambda max(V_ii, 1e-6) added to each diagonal entry; V*^-1 = adj / det by the cofactor formula of
+ *   GIMS_AUX_TRIANGULATE_TRACKS, every entry divided by det.  Per observation of a camera that moves (free, not held): W[c][m] = Ju[c] Pu[m] +
+ *   Jv[c] Pv[m] (6 x 3) and Y = W V*^-1, Y[c][m] = W[c][0] I[0][m] + W[c][1] I[1][m] + W[c][2] I[2][m].  Per slot s that is not held, over
+ *   the active observations of its image in ascending o: the 21 sums U = sum (Ju[i] Ju[j] + Jv[i] Jv[j]) and the six g_c = sum (Ju[i] ru +
+ *   Jv[i] rv), each as lane l of 64 adding the observations number l, l + 64, ... of the list and a butterfly over the lanes; U* = U with
+ *   lambda max(U_ii, 1e-6) added to the diagonal.  The block row s of the reduced system starts as U* in block s, zeros elsewhere, and
+ *   b_s = -g_c; then for every observation o of the list in ascending order, with p its point: b_s[r] += (Y_o[r][0] g_p[0] + Y_o[r][1]
+ *   g_p[1]) + Y_o[r][2] g_p[2], and for every active observation o' of p in ascending order whose camera moves, in slot k: S[6 s + r][6 k + c]
+ *   -= (Y_o[r][0] W_o'[c][0] + Y_o[r][1] W_o'[c][1]) + Y_o[r][2] W_o'[c][2].  S = L L^T by Cholesky without pivoting: for j ascending, l =
+ *   sqrt(S_jj), L_ij = S_ij / l for i > j, then S_ik -= L_ij L_kj for j < k <= i.  The round is REGULAR iff the det of every active point
+ *   is finite and > 0 and every pivot S_jj is finite and > 0.  L y = b: for j ascending y_j = b_j / L_jj, then b_i -= L_ij y_j for i > j;
+ *   L^T d = y: for j descending d_j = y_j / L_jj, then y_k -= L_jk d_j for k < j.  Per active point s = g_p, then for its active observations
+ *   in ascending o whose camera moves, for c ascending: s[m] += W[c][m] d[6 k + c]; dX[m] = -((I[m][0] s[0] + I[m][1] s[1]) + I[m][2] s[2]).
+ *   The candidate: X + dX; for a moving camera R' = exp([w]x) R, t' = t + dt with (w, dt) its six words of d and exp as in
+ *   GIMS_AUX_RESECT_IMAGES (theta > 1e-8: A = sin(theta) / theta, B = (1 - cos(theta)) / theta^2, else 1 and 1/2).
+ *   The round is TAKEN iff it is regular, every candidate word is finite, every active observation has z > 0 under the candidate, and
+ *   the candidate's cost is below the current cost with both rounded to float32 for this comparison (the rule and the reason of
+ *   GIMS_AUX_RESECT_IMAGES).  Taken: the candidate becomes the state, lambda <- max(lambda / 10, 1e-12).  Not taken: the state stays,
+ *   lambda <- min(10 lambda, 1e12).  After GIMS_BA_MAX_REJECTS consecutive rounds that were not taken the remaining rounds do nothing
+ *   (their history rows repeat the last one, their taken is 0).  history[0] = {the starting cost, lambda0}, history[r + 1] = {cost,
+ *   lambda} after round r; taken[r] = 1 iff round r was taken.  The inlier set is an input (obs_use) and is not decided again: the cost
+ *   is a continuous function of the parameters.  The gauge is the caller's: it is fixed by the cameras of mode 1.
+ * Outputs.  xyz and cams: the final state; inactive points and absent, fixed and held cameras are copied through bit for bit (the one way
+ *   a NaN reaches an output: it was in the input), as are the eight words of a free camera that are not R or t.  obs_error: sqrt(e^2) as
+ *   float (at most FLT_MAX) under the final state, -1 for an observation that is not active.  Every output is written by every call.
+ * GIMS_EINVAL before any HIP call, each with a message naming bundle_adjust: T, n_obs or N outside 0 .. 2^30; n_images outside 0 .. 2^24;
+ * iters outside 0 .. 255; huber negative or not finite; lambda0 not finite or <= 0; a NULL out or table; kpts, xyz or one of the five
+ * table addresses NULL while T > 0; cams or mode NULL while n_images > 0; out not 16-byte aligned, the table, xyz or cams not 8-byte
+ * aligned, kpts, mode, indptr, obs_image or obs_keypoint not 4-byte aligned; a reserved table word that is not 0; a mode outside 0 .. 2;
+ * more than GIMS_BA_MAX_FREE_CAMERAS free cameras (a 768 x 768 reduced system, 4.7 MB of scratch; a larger set needs a blocked or an
+ * iterative reduced solve: the later form that i[5] is reserved for); i[5] != 0.  i[5] is checked before everything else: a non-zero value
+ * is refused as an unknown auxiliary function form of gims_run_ops (the message names both), whatever the other arguments hold.  T == 0,
+ * and no free camera together with no active point, are GIMS_OK: the inputs are copied through and the counters written.
+ * Nothing outside out is written.  A fixed sequence of memset nodes, the upload of the slot tables and 8 + 5 iters launches (6 + 3 iters
+ * when n_free == 0), the same whatever the data: all decisions live in the state block.  No host synchronisation; capturable by
+ * gims_ops_graph_create.  (Track ranges that overlap are each processed; what they share holds the result of one of them.)
+ * How it is computed.  The state has two buffers for points and cameras; a round writes its candidate into the one that is not current and
+ * a taken round swaps them.  A thread per track forms V, g_p, V*^-1, W and Y; a wave per slot forms U, g_c and its block row of S in LDS,
+ * walking a list of its observations that a count (integer atomics), a scan and an ordered fill build once per call (lane j takes
+ * observation j of the walked observation's track, so the blocks of one walked observation are formed side by side); one workgroup of
+ * 1024 factors S in place and solves; a thread per track substitutes back and sums its candidate cost; one workgroup sums the costs and
+ * one thread decides.  There are no float atomics and no sum whose order depends on the grid: the output bytes are identical across runs. */
 #define GIMS_OP_AUX 2
 #define GIMS_AUX_SPLIT_SPL32 0
 #define GIMS_AUX_SAGE_MEAN_SPLIT 1
@@ -617,6 +715,11 @@ int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t
 #define GIMS_AUX_RESECT_IMAGES 11
 #define GIMS_RESECT_CAMERA_WORDS 6
 #define GIMS_RESECT_HB 16
+/* 12 is unassigned and stays refused as an unknown auxiliary function */
+#define GIMS_AUX_BUNDLE_ADJUST 13
+#define GIMS_BA_TABLE_WORDS 8
+#define GIMS_BA_MAX_FREE_CAMERAS 128
+#define GIMS_BA_MAX_REJECTS 5
 typedef struct gims_aux_args { int32_t fn, reserved; const void* p[6]; int64_t i[6]; float f[2]; } gims_aux_args;
 typedef struct gims_op { int32_t kind; int32_t reserved; union { gims_linear_args lin; gims_attn_args att; gims_aux_args aux; } u; } gims_op;
 int gims_run_ops(const gims_op* ops /* HOST */, int32_t n_ops, void* stream);

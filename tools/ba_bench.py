@@ -1,0 +1,175 @@
+"""Bundle adjustment on the device against the host route: the scene of tools/resect_bench.py -- --images + 2 cameras on an
+arc around 8192 planted points, every image sees 4096 of them with 0.5 px of noise, the matches of the pairs (k, k + 1 .. k + --neighbours)
+are the planted correspondences with a fraction --wrong of the rows pointed at a random keypoint.  Images 0 and 1 are posed and stay fixed;
+build_tracks, triangulate_tracks (the points of the posed pair), resect_images for the others, triangulate_tracks (all), then
+bundle_adjust with every resected camera free.  Reports
+  device_op       GIMS_AUX_BUNDLE_ADJUST alone, by device events around the op (gims_run_ops_timed): median, min, max of --runs runs; the
+                  same with iters = 0 (`setup_ms`: what is not a round) and the difference per round (`per_round_ms`)
+  bundle_adjust   the whole gims_amd.bundle_adjust call on the host clock, to the end of the device work (and the enqueue alone)
+  host_route      what a caller does without the op: read tracks, masks, points and all keypoints back, then adjust on the host -- the NumPy
+                  restatement, run for --host-rounds rounds and scaled to --iters of them (`extrapolated_ms`: an EXTRAPOLATION, the
+                  restatement was not run to the end), and scipy.optimize.least_squares (trf, sparse analytic Jacobian, at most --iters
+                  evaluations) when scipy imports (`scipy`: null otherwise)
+and what the adjustment did: rms reprojection error and the worst |R - planted|, |t - planted| before and after.  One JSON line, ms.
+gims_run_ops_timed times whole ops, so the split of a round by kernel is taken from a kernel trace of this tool.
+
+Usage: python tools/ba_bench.py [--images 48] [--points 8192] [--kpts 4096] [--iters 20] [--runs 10] [--host-rounds 2 (0: the device side only)] [--no-scipy]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import gims_amd  # noqa: E402
+from gims_amd import hip  # noqa: E402
+from tests import ba_ref as B  # noqa: E402
+from tests import triangulate_ref as R  # noqa: E402
+
+DEV = "cuda"
+
+
+def op_alone(dev, mode, iters, runs, warmup):
+    T, n_obs, n = dev["indptr"].numel() - 1, dev["obs_image"].numel(), dev["kpts"].shape[0]
+    n_free = int((mode == 2).sum())
+    out = torch.empty(hip.ba_out_layout(T, n_obs, len(mode), iters, n_free)["bytes"], dtype=torch.uint8, device=DEV)
+    table = hip.ba_table(*(dev[k] for k in ("indptr", "obs_image", "obs_keypoint", "obs_use", "point_use")))
+    ops = hip.make_ops([hip.op_bundle_adjust(table, dev["kpts"], dev["xyz"], dev["cams"], mode, out, T, n_obs, n, iters, 0.0, 1e-4)])
+    ev = hip.EventPool(2)
+    ms = []
+    for it in range(warmup + runs):
+        hip.run_ops_timed(ops, ev)
+        torch.cuda.synchronize()
+        if it >= warmup:
+            ms.append(ev.elapsed_ms()[0])
+    views = hip.ba_views(out, T, n_obs, len(mode), iters, n_free)
+    return {"median_ms": round(float(np.median(ms)), 4), "min_ms": round(float(np.min(ms)), 4), "max_ms": round(float(np.max(ms)), 4), "runs": len(ms),
+            "stats": dict(zip(hip.BA_COUNTERS, views["counters"].tolist())), "taken": views["taken"].tolist()}
+
+
+def scipy_route(host, mode, iters):
+    """scipy.optimize.least_squares on the same cost (squared loss), the same parameters (w, dt per free camera; the points), a sparse
+    analytic Jacobian from the restatement's model."""
+    from scipy.optimize import least_squares
+    from scipy.sparse import csr_matrix
+    cl = B.classify(*(host[k] for k in B.ARGS[:5]), host["kpts"], host["xyz"], host["cams"], mode)
+    ao = np.flatnonzero(cl["obs_act"])
+    ot, ok_ = cl["obs_track"][ao], host["obs_image"][ao].astype(np.int64)
+    uv = host["kpts"][cl["obs_node"][ao]].astype(np.float64)
+    slot_cam = np.flatnonzero(mode == 2)
+    held = cl["cam_obs"][slot_cam] < 4
+    slot_of = np.full(len(mode), -1, np.int64)
+    slot_of[slot_cam[~held]] = np.flatnonzero(~held)
+    oslot, T, ns = slot_of[ok_], len(host["xyz"]), len(slot_cam)
+    X0, C0, act = host["xyz"], host["cams"], cl["pt_act"]
+
+    def state(p):
+        return B.apply_step(X0, C0, slot_cam, held, act, p[:6 * ns].reshape(ns, 6), p[6 * ns:].reshape(T, 3))
+
+    def fun(p):
+        return B.residuals(*state(p), ao, ot, ok_, uv)
+
+    def jac(p):
+        # (the camera Jacobian of the model is taken at the current rotation: exact at w = 0, first order in w elsewhere)
+        X, C = state(p)
+        _, _, _, Ju, Jv, Pu, Pv = B.observe(C, X[ot], ok_, uv)
+        rows, cols, vals = [], [], []
+        for half, (Jc, Jp) in enumerate(((Ju, Pu), (Jv, Pv))):
+            r = 2 * np.arange(len(ao)) + half
+            mv = oslot >= 0
+            for c in range(6):
+                rows.append(r[mv]), cols.append(6 * oslot[mv] + c), vals.append(Jc[mv, c])
+            for m_ in range(3):
+                rows.append(r), cols.append(6 * ns + 3 * ot + m_), vals.append(Jp[:, m_])
+        return csr_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(2 * len(ao), 6 * ns + 3 * T))
+
+    t = time.perf_counter()
+    res = least_squares(fun, np.zeros(6 * ns + 3 * T), jac=jac, method="trf", tr_solver="lsmr", x_scale="jac", max_nfev=iters)
+    return {"ms": round((time.perf_counter() - t) * 1e3, 1), "nfev": int(res.nfev), "rms": round(float(np.sqrt(2 * res.cost / len(ao))), 5)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--images", type=int, default=48)
+    ap.add_argument("--points", type=int, default=8192)
+    ap.add_argument("--kpts", type=int, default=4096)
+    ap.add_argument("--neighbours", type=int, default=6)
+    ap.add_argument("--wrong", type=float, default=0.0005)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--runs", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--host-rounds", type=int, default=2)
+    ap.add_argument("--no-scipy", action="store_true")
+    a = ap.parse_args()
+    torch.set_grad_enabled(False)
+    n_images = a.images + 2
+    m = R.planted_matches(1, n_images, a.points, a.kpts, noise=0.5, w_wrong=a.wrong, neighbours=a.neighbours)
+    kpts = [torch.from_numpy(k).to(DEV) for k in m["kpts"]]
+    outs = [{"matches0": torch.from_numpy(x).to(DEV)[None]} for x in m["matches"]]
+    Rn, tn = m["R"].copy(), m["t"].copy()
+    Rn[2:], tn[2:] = np.nan, np.nan
+    out = {"images": a.images, "points": a.points, "kpts": a.kpts, "pairs": len(m["pairs"]), "wrong": a.wrong, "iters": a.iters}
+
+    tracks = gims_amd.build_tracks(m["counts"], m["pairs"], outs)
+    first = gims_amd.triangulate_tracks(tracks, kpts, (m["K"], Rn, tn))
+    poses = gims_amd.resect_images(first, tracks, kpts, m["K"], list(range(2, n_images)), seed=0)
+    cams = poses.cameras(m["K"], Rn, tn)
+    pts = gims_amd.triangulate_tracks(tracks, kpts, cams)
+    out["scene"] = {"n_tracks": tracks.n_tracks, "n_obs": int(tracks.obs_image.numel()), "valid": int(pts.valid.sum()), "resected": poses.stats["n_ok"]}
+    posed = np.isfinite(cams[1]).all(axis=(1, 2))
+    mode = np.where(posed, 2, 0).astype(np.int32)
+    mode[:2] = 1
+    rec = hip.triangulate_cameras(*cams, m["counts"])
+    dev = dict(indptr=tracks.indptr.contiguous(), obs_image=tracks.obs_image.contiguous(), obs_keypoint=tracks.obs_keypoint.contiguous(),
+               obs_use=pts.obs_inlier.contiguous(), point_use=pts.valid.view(torch.uint8).contiguous(), kpts=torch.cat(kpts).contiguous(), xyz=pts.xyz.contiguous(),
+               cams=torch.from_numpy(rec).to(DEV))
+    out["device_op"] = op_alone(dev, mode, a.iters, a.runs, a.warmup)
+    out["device_op"]["setup_ms"] = op_alone(dev, mode, 0, a.runs, a.warmup)["median_ms"]
+    out["device_op"]["per_round_ms"] = round((out["device_op"]["median_ms"] - out["device_op"]["setup_ms"]) / max(a.iters, 1), 4)
+
+    gims_amd.bundle_adjust(pts, tracks, kpts, cams, iters=a.iters)
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    adj = gims_amd.bundle_adjust(pts, tracks, kpts, cams, iters=a.iters)
+    t_enq = time.perf_counter()
+    torch.cuda.synchronize()
+    out["bundle_adjust"] = {"wall_ms": round((time.perf_counter() - t) * 1e3, 3), "enqueue_ms": round((t_enq - t) * 1e3, 3)}
+    stats, hist = adj.stats, adj.history.cpu().numpy()
+    out["stats"] = stats
+    n_act = max(stats["n_active_obs"], 1)
+    Ka, Ra, ta = adj.cameras()
+    out["rms_px"] = {"before": round(float(np.sqrt(hist[0, 0] / n_act)), 5), "after": round(float(np.sqrt(hist[-1, 0] / n_act)), 5)}
+    out["worst_dR"] = {"before": round(float(np.abs(cams[1] - m["R"])[posed].max()), 6), "after": round(float(np.abs(Ra - m["R"])[posed].max()), 6)}
+    out["worst_dt"] = {"before": round(float(np.abs(cams[2] - m["t"])[posed].max()), 6), "after": round(float(np.abs(ta - m["t"])[posed].max()), 6)}
+
+    if a.host_rounds <= 0:                                       # the device side only (for a kernel trace)
+        print(json.dumps(out))
+        return
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    host = {k: v.cpu().numpy() for k, v in dev.items()}
+    t_read = time.perf_counter()
+    rounds = max(1, min(a.host_rounds, max(a.iters, 1)))
+    want = B.adjust(*(host[k] for k in B.ARGS[:8]), mode, iters=rounds)
+    rest_ms = (time.perf_counter() - t_read) * 1e3
+    out["host_route"] = {"readback_ms": round((t_read - t) * 1e3, 2), "restatement_ms": round(rest_ms, 1), "restatement_rounds": rounds,
+                         "extrapolated_ms": round((t_read - t) * 1e3 + rest_ms * a.iters / rounds, 1)}
+    out["results_equal"] = bool(np.array_equal(want["taken"], adj.taken.cpu().numpy()[:rounds]))
+    out["max_cost_diff"] = float(np.abs(want["history"][:, 0] - hist[:rounds + 1, 0]).max() / max(hist[0, 0], 1.0))
+    out["host_over_device"] = round(out["host_route"]["extrapolated_ms"] / out["device_op"]["median_ms"], 1)
+    out["scipy"] = None
+    if not a.no_scipy:
+        try:
+            import scipy
+            out["scipy"] = dict(scipy_route(host, mode, a.iters), version=scipy.__version__, readback_ms=out["host_route"]["readback_ms"])
+        except ImportError:
+            pass
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
