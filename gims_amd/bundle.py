@@ -10,9 +10,10 @@ in one asynchronous op and without reading tracks, keypoints, points or poses ba
 
 The specification (include/gims_hip.h has it in full; tests/ba_ref.py is its NumPy restatement).  World to camera is ``x_c = R X + t``.
 ``iters`` Levenberg-Marquardt rounds; a round eliminates the points (Schur complement), factors the dense reduced camera system (6 x 6
-blocks, at most 128 free cameras) by Cholesky, substitutes back, and is taken iff the cost goes down and every observation stays in
-front of its camera; after five rounds in a row that were not taken the rest do nothing.  The inlier set is an input and is not decided
-again.  All arithmetic is float64; the output bytes are identical across runs.
+blocks, at most 128 free cameras) by Cholesky -- or, with ``solver='pcg'``, solves it by preconditioned conjugate gradients without
+forming it (GIMS_AUX_BUNDLE_ADJUST_PCG; at most 65536 free cameras) --, substitutes back, and is taken iff the cost goes
+down and every observation stays in front of its camera; after five rounds in a row that were not taken the rest do nothing.  The
+inlier set is an input and is not decided again.  All arithmetic is float64; the output bytes are identical across runs.
 
 The gauge.  A reconstruction is defined up to a similarity: seven numbers that no observation fixes.  ``fixed`` names the cameras that do
 not move; the default is the first two posed images in index order, which fixes position, orientation and -- through the distance between
@@ -34,8 +35,10 @@ class Adjusted:
     float64 [n, 18] -- the camera records of the op, the format ``triangulate_tracks`` takes as ``cameras`` -- and its views ``R`` [n, 3, 3] and
     ``t`` [n, 3] (absent, fixed and held cameras are copied through), ``obs_error`` float32 [n_obs] (pixels, under the final state; -1 for an
     observation that was not active), ``cam_obs`` int32 [n] (active observations per image), ``history`` float64 [iters + 1, 2] ({cost,
-    lambda} at the start and after every round), ``taken`` uint8 [iters].  ``mode``: the host list of the cameras' modes (0 absent, 1
-    fixed, 2 free).
+    lambda} at the start and after every round), ``taken`` uint8 [iters].  With ``solver='pcg'`` also ``cg_used`` int32 [iters] (the
+    conjugate-gradient iterations of every round) and ``cg_res`` float64 [iters] (sqrt(rho_stop / rho_0), the preconditioned residual the
+    round's iteration stopped at, relative to its start); both are ``None`` for the dense solver.  ``mode``: the host list of the cameras'
+    modes (0 absent, 1 fixed, 2 free).
 
     ``stats`` (n_free, n_fixed, n_held, n_points, n_active_obs, n_bad_obs, rounds_taken, status) reads the op's counters back on first
     access, and ``cameras()`` reads the records: these two synchronise with the device; everything else is handed over asynchronously."""
@@ -44,6 +47,7 @@ class Adjusted:
         self.xyz, self.records = views["xyz"], views["cams"]
         self.R, self.t = self.records[:, 4:13].unflatten(1, (3, 3)), self.records[:, 13:16]
         self.obs_error, self.cam_obs, self.history, self.taken = views["obs_error"], views["cam_obs"], views["history"], views["taken"]
+        self.cg_used, self.cg_res = views.get("cg_used"), views.get("cg_res")
         self.mode = [int(m) for m in mode]
         self._K, self._counters, self._keep, self._stats = K, views["counters"], keep, None
 
@@ -77,9 +81,15 @@ class Adjusted:
         return f"Adjusted(n_points={len(self)}, n_images={len(self.mode)}, n_free={sum(m == hip.BA_FREE for m in self.mode)})"
 
 
-def _check(points, tracks, images, cameras, fixed, use_obs, use_points, iters, huber, lambda0):
+def _check(points, tracks, images, cameras, fixed, use_obs, use_points, iters, huber, lambda0, solver="dense", cg_iters=64, cg_tol=1e-6):
     """Everything bundle_adjust checks before the device is touched -> (keypoint tensors, host records, host K, modes, obs mask, point mask)."""
     name = "bundle_adjust"
+    if solver not in ("dense", "pcg"):
+        raise ValueError(f"{name}: solver must be 'dense' or 'pcg', got {solver!r}")
+    if isinstance(cg_iters, bool) or not isinstance(cg_iters, (int, np.integer)) or not 1 <= cg_iters <= hip.BA_PCG_MAX_CG_ITERS:
+        raise ValueError(f"{name}: cg_iters must be an integer in 1 .. {hip.BA_PCG_MAX_CG_ITERS}, got {cg_iters!r}")
+    if isinstance(cg_tol, bool) or not (isinstance(cg_tol, (int, float)) and math.isfinite(cg_tol) and 0 <= cg_tol < 1):
+        raise ValueError(f"{name}: cg_tol must be finite with 0 <= cg_tol < 1, got {cg_tol!r}")
     if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or not 0 <= iters <= 255:
         raise ValueError(f"{name}: iters must be an integer in 0 .. 255, got {iters!r}")
     if isinstance(huber, bool) or not (isinstance(huber, (int, float)) and math.isfinite(huber) and huber >= 0):
@@ -130,8 +140,10 @@ def _check(points, tracks, images, cameras, fixed, use_obs, use_points, iters, h
     mode = np.where(posed, hip.BA_FREE, hip.BA_ABSENT).astype(np.int32)
     mode[fixed] = hip.BA_FIXED
     n_free = int((mode == hip.BA_FREE).sum())
-    if n_free > hip.BA_MAX_FREE_CAMERAS:
-        raise ValueError(f"{name}: {n_free} free cameras, at most {hip.BA_MAX_FREE_CAMERAS} (fix more of them, or adjust a part of the set)")
+    if solver == "dense" and n_free > hip.BA_MAX_FREE_CAMERAS:
+        raise ValueError(f"{name}: {n_free} free cameras, at most {hip.BA_MAX_FREE_CAMERAS} (fix more of them, adjust a part of the set, or use solver='pcg')")
+    if n_free > hip.BA_PCG_MAX_FREE_CAMERAS:
+        raise ValueError(f"{name}: {n_free} free cameras, at most {hip.BA_PCG_MAX_FREE_CAMERAS} with solver='pcg'")
     device = tracks.indptr.device
     for attr in ("indptr", "obs_image", "obs_keypoint"):
         x = getattr(tracks, attr)
@@ -158,7 +170,7 @@ def _check(points, tracks, images, cameras, fixed, use_obs, use_points, iters, h
 
 
 def bundle_adjust(points, tracks, images, cameras, *, fixed=None, use_obs=None, use_points=None, iters: int = 20, huber: float = 0.0,
-                  lambda0: float = 1e-4) -> Adjusted:
+                  lambda0: float = 1e-4, solver: str = "dense", cg_iters: int = 64, cg_tol: float = 1e-6) -> Adjusted:
     """Refine the posed cameras and the points jointly, on the device.
 
     ``points``: the ``Points3D`` of ``triangulate_tracks`` (the starting points); ``tracks``: the ``Tracks`` they belong to; ``images``: the
@@ -171,12 +183,17 @@ def bundle_adjust(points, tracks, images, cameras, *, fixed=None, use_obs=None, 
     move; a free camera with fewer than four is held.  ``iters``: Levenberg-Marquardt rounds (0 .. 255); ``huber``: the Huber bound in
     pixels, 0 for the squared loss; ``lambda0``: the starting damping.
 
+    ``solver``: ``'dense'`` factors the reduced camera system by Cholesky (at most 128 free cameras); ``'pcg'`` solves it by preconditioned
+    conjugate gradients without forming it (at most 65536 free cameras): at most ``cg_iters`` (1 .. 256) iterations per
+    round, stopped early once the preconditioned residual has fallen to ``cg_tol`` (0 <= cg_tol < 1) of its start.  The two arguments are
+    checked and then ignored by ``'dense'``.
+
     ValueError, before the device is touched: a count that disagrees with ``tracks.image_start``, cameras of another shape or count, a K
     of a posed camera with skew, another last row or a focal length that is not positive, an index of ``fixed`` out of range or without a
-    pose, more than 128 free cameras, tensors of a wrong dtype, shape or device, a parameter out of range.
+    pose, more than 128 free cameras (65536 with ``solver='pcg'``), tensors of a wrong dtype, shape or device, a parameter out of range.
 
     Host synchronisation: NONE.  ``Adjusted.stats`` and ``Adjusted.cameras()`` read back."""
-    kpts, rec, K, mode, obs, pts = _check(points, tracks, images, cameras, fixed, use_obs, use_points, iters, huber, lambda0)
+    kpts, rec, K, mode, obs, pts = _check(points, tracks, images, cameras, fixed, use_obs, use_points, iters, huber, lambda0, solver, cg_iters, cg_tol)
     device = tracks.indptr.device
     with torch.cuda.device(device):
         allk = torch.cat([k.reshape(-1, 2).float() for k in kpts]).contiguous() if kpts else torch.zeros((0, 2), device=device)
@@ -187,5 +204,5 @@ def bundle_adjust(points, tracks, images, cameras, *, fixed=None, use_obs=None, 
                                         _nonempty(tracks.obs_keypoint.contiguous(), (1,), torch.int32), _nonempty(obs.contiguous().view(torch.uint8), (1,), torch.uint8),
                                         _nonempty(pts.contiguous().view(torch.uint8), (1,), torch.uint8), _nonempty(allk, (1, 2), torch.float32),
                                         _nonempty(points.xyz.contiguous(), (1, 3), torch.float64), dev_cams, mode, iters=int(iters), huber=float(huber),
-                                        lambda0=float(lambda0), T=T, n_obs=n_obs, n=n)
+                                        lambda0=float(lambda0), T=T, n_obs=n_obs, n=n, solver=solver, cg_iters=int(cg_iters), cg_tol=float(cg_tol))
     return Adjusted(views, mode, K, keep)

@@ -14,9 +14,12 @@
 // Every floating-point sum has one order: a track's observations ascending in one thread; a camera's observations as the lane's own
 // ascending sum and a butterfly over the wave (U, g_c), or one after the other (the block row); the tracks' costs as a thread's own
 // ascending sum, a butterfly, then the waves in order.  No order depends on the grid.
+// GIMS_AUX_BUNDLE_ADJUST_PCG, further down, shares init, classify, point, back, decide and finish and replaces camera and
+// solve by a matrix-free conjugate-gradient iteration, so that the number of free cameras is not bound by a dense reduced system.
 #include "common.h"
 
 #include <cfloat>
+#include <cstring>
 #include <vector>
 
 namespace gims {
@@ -37,6 +40,8 @@ enum { BA_ABSENT = -1, BA_FIXED = -2 };                        // slot_of: or th
 struct BaState {                                               // 256 bytes, zeroed by a memset node
   double cost, lambda;
   int32_t cur, rejects, stop, taken, status, flags, n_points, n_act, n_bad, n_held;
+  double rho, rho0;                                            // the conjugate-gradient form only, from here on
+  int32_t cg_done, cg_used;
 };
 
 struct BaOut {
@@ -48,6 +53,8 @@ struct BaOut {
   int32_t *slot_of, *slot_cam, *slot_ptr, *held, *obs_track, *obs_node, *cam_list, *obs_mslot, *obs_dup;
   double *xyz1, *cams1, *pt_rec, *obs_rec, *trackcost, *S, *rhs;
   uint8_t *pt_act, *obs_act;
+  int32_t *cg_used, *list_tmp, *cursor;                        // the conjugate-gradient form only, from here on (rhs is its x, S stays NULL)
+  double *cg_res, *y, *slot_rec, *vr, *vz, *vp, *vq;
 };
 static size_t ba_layout(void* base, int64_t T, int64_t n_obs, int64_t n_images, int64_t iters, int64_t n_free, BaOut& w) {
   WsLayout L(base);
@@ -90,6 +97,8 @@ struct BaArgs {
   int T, n_obs, n_images, iters, n_free, n_fixed;
   int64_t N;
   double huber, lambda0;
+  int cg_iters;                                                // the conjugate-gradient form only
+  double cg_tol2;
 };
 
 __device__ __forceinline__ bool ba_finite(double x) { return fabs(x) <= DBL_MAX; }       // (false for a NaN)
@@ -634,8 +643,491 @@ __global__ __launch_bounds__(BA_THREADS) void ba_finish_kernel(BaArgs a) {
   }
 }
 
-// GIMS_AUX_BUNDLE_ADJUST of gims_run_ops (include/gims_hip.h): every argument check precedes the first HIP call
-int bundle_adjust_aux(const gims_aux_args& x, hipStream_t st) {
+// ================================================================================================ the conjugate-gradient form
+// GIMS_AUX_BUNDLE_ADJUST_PCG: the same rounds, but the camera step d of a round comes from preconditioned conjugate
+// gradients on the Schur complement S, which is never formed.  Per round: point (as above) -> pcg_setup (a wave per slot: U*, b, the block
+// M_s of the preconditioner and its 6 x 6 Cholesky factor) -> pcg_init (one workgroup: x = 0, z = M^-1 r, p = z, rho_0) -> cg_iters times
+// { pcg_y (a thread per track: y = V*^-1 sum W^T p) -> pcg_sp (a wave per slot: q = U* p - sum W y) -> pcg_step (one workgroup: the two dot
+// products, x, r, z, the stop test, p) } -> pcg_cand (a thread per slot: the candidate camera) -> back -> decide.  The iterations after
+// the stop are launched and return at once: cg_done lives in the state block.  The lists of the slots are built once per call, with cost
+// linear in n_obs up to the ordering: slots (held, an exclusive scan of cam_obs) -> fill (a thread per observation, an integer cursor per
+// slot: any order) -> sort (BA_SORT_SPLIT workgroups per slot, 256 entries at a time: every entry goes to the place its rank gives it: ascending).
+constexpr int BA_PCG_MAX_FREE = GIMS_BA_PCG_MAX_FREE_CAMERAS;
+constexpr int BA_PCG_MAX_ITERS = GIMS_BA_PCG_MAX_CG_ITERS;
+constexpr int BA_SORT_SPLIT = 16;                              // workgroups that share the ordering of one slot's list, 256 entries at a time
+constexpr int BA_SLOT_REC = 42;                                // per slot: U* (the upper triangle by rows, 21) | L of M_s = L L^T (the lower triangle by rows, 21)
+
+static size_t ba_pcg_layout(void* base, int64_t T, int64_t n_obs, int64_t n_images, int64_t iters, int64_t n_free, BaOut& w) {
+  WsLayout L(base);
+  w.xyz = L.take<double>((size_t)T * 3);
+  w.cams = L.take<double>((size_t)n_images * BA_CAM);
+  w.obs_error = L.take<float>((size_t)n_obs);
+  w.cam_obs = L.take<int32_t>((size_t)n_images);
+  w.history = L.take<double>((size_t)(iters + 1) * 2);
+  w.taken = L.take<uint8_t>((size_t)iters);
+  w.counters = L.take<int32_t>(BA_COUNTERS);
+  w.cg_used = L.take<int32_t>((size_t)iters);
+  w.cg_res = L.take<double>((size_t)iters);
+  w.st = (BaState*)L.take<double>(32);                         // scratch from here on
+  w.slot_of = L.take<int32_t>((size_t)n_images);
+  w.slot_cam = L.take<int32_t>((size_t)n_free);
+  w.slot_ptr = L.take<int32_t>((size_t)n_free + 1);
+  w.held = L.take<int32_t>((size_t)n_free);
+  w.cursor = L.take<int32_t>((size_t)n_free);
+  w.xyz1 = L.take<double>((size_t)T * 3);
+  w.cams1 = L.take<double>((size_t)n_images * BA_CAM);
+  w.pt_act = L.take<uint8_t>((size_t)T);
+  w.obs_act = L.take<uint8_t>((size_t)n_obs);
+  w.obs_track = L.take<int32_t>((size_t)n_obs);
+  w.obs_node = L.take<int32_t>((size_t)n_obs);
+  w.cam_list = L.take<int32_t>((size_t)n_obs);
+  w.list_tmp = L.take<int32_t>((size_t)n_obs);
+  w.pt_rec = L.take<double>((size_t)T * BA_PT);
+  w.obs_rec = L.take<double>((size_t)n_obs * BA_REC);
+  w.trackcost = L.take<double>((size_t)T);
+  w.y = L.take<double>((size_t)T * 3);
+  w.slot_rec = L.take<double>((size_t)n_free * BA_SLOT_REC);
+  w.rhs = L.take<double>((size_t)n_free * 6);                  // x of the iteration, then the step d that back reads
+  w.vr = L.take<double>((size_t)n_free * 6);
+  w.vz = L.take<double>((size_t)n_free * 6);
+  w.vp = L.take<double>((size_t)n_free * 6);
+  w.vq = L.take<double>((size_t)n_free * 6);
+  w.obs_mslot = w.obs_dup = nullptr, w.S = nullptr;            // (the dense form's)
+  return L.bytes();
+}
+
+__device__ __forceinline__ double ba_wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// the sum over a workgroup of BA_THREADS: a butterfly per wave, then the waves in order; every thread gets the same bits
+__device__ __forceinline__ double ba_block_sum(double v, double* s_part) {
+  v = ba_wave_sum(v);
+  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double total = s_part[0];
+  for (int w = 1; w < BA_THREADS / 64; ++w) total += s_part[w];
+  __syncthreads();
+  return total;
+}
+__device__ __forceinline__ double ba_dot6(const double* v, const double* w) {
+  return ((((v[0] * w[0] + v[1] * w[1]) + v[2] * w[2]) + v[3] * w[3]) + v[4] * w[4]) + v[5] * w[5];
+}
+// z = M^-1 r from the factor L (the lower triangle by rows): L y = r by columns (j ascending), L^T z = y by rows (j descending)
+__device__ __forceinline__ void ba_msolve(const double* Lf, const double* r, double* z) {
+  double L[21], b[6], y[6];
+#pragma unroll
+  for (int j = 0; j < 21; ++j) L[j] = Lf[j];
+#pragma unroll
+  for (int j = 0; j < 6; ++j) b[j] = r[j];
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    y[j] = b[j] / L[j * (j + 1) / 2 + j];
+#pragma unroll
+    for (int i = j + 1; i < 6; ++i) b[i] -= L[i * (i + 1) / 2 + j] * y[j];
+  }
+#pragma unroll
+  for (int j = 5; j >= 0; --j) {
+    z[j] = y[j] / L[j * (j + 1) / 2 + j];
+#pragma unroll
+    for (int k = 0; k < j; ++k) y[k] -= L[j * (j + 1) / 2 + k] * z[j];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- slots, lists (any number of slots)
+__global__ __launch_bounds__(BA_THREADS) void ba_pcg_slots_kernel(BaArgs a) {
+  __shared__ int s_sum[BA_THREADS], s_held[BA_THREADS];
+  const int t = threadIdx.x, per = (a.n_free + BA_THREADS - 1) / BA_THREADS;
+  const int lo = t * per < a.n_free ? t * per : a.n_free, hi = lo + per < a.n_free ? lo + per : a.n_free;
+  int sum = 0, held = 0;
+  for (int s = lo; s < hi; ++s) {
+    const int c = a.out.cam_obs[a.out.slot_cam[s]];
+    a.out.held[s] = c < 4 ? 1 : 0, a.out.cursor[s] = 0;
+    if (c < 4) ++held; else sum += c;
+  }
+  s_sum[t] = sum, s_held[t] = held;
+  __syncthreads();
+  if (t == 0) {
+    int at = 0, h = 0;
+    for (int j = 0; j < BA_THREADS; ++j) {
+      const int v = s_sum[j];
+      s_sum[j] = at, at += v, h += s_held[j];
+    }
+    a.out.slot_ptr[a.n_free] = at;                             // <= n_obs: every active observation has one camera
+    a.out.st->n_held = h;
+  }
+  __syncthreads();
+  int at = s_sum[t];
+  for (int s = lo; s < hi; ++s) {
+    a.out.slot_ptr[s] = at;
+    if (a.out.held[s] == 0) at += a.out.cam_obs[a.out.slot_cam[s]];
+  }
+}
+
+__global__ __launch_bounds__(BA_THREADS) void ba_pcg_fill_kernel(BaArgs a) {
+  const int o = blockIdx.x * BA_THREADS + threadIdx.x;
+  if (o >= a.n_obs || a.out.obs_act[o] == 0) return;
+  const int s = ba_moving_slot(a, a.obs_image[o]);             // (in range: the observation is active)
+  if (s < 0) return;
+  const int first = a.out.slot_ptr[s], cap = a.out.slot_ptr[s + 1] - first;
+  const int at = atomicAdd(a.out.cursor + s, 1);               // integers: the order of the race is undone by the sort
+  if (at < cap && first >= 0 && first + at < a.n_obs) a.out.list_tmp[first + at] = o;
+}
+
+__global__ __launch_bounds__(BA_THREADS) void ba_pcg_sort_kernel(BaArgs a) {
+  __shared__ int s_tile[BA_THREADS];
+  const int s = blockIdx.x, t = threadIdx.x, first = a.out.slot_ptr[s];
+  int cnt = a.out.slot_ptr[s + 1] - first;
+  if (first < 0 || cnt < 0 || first + cnt > a.n_obs) cnt = 0;   // (never: ba_pcg_slots_kernel wrote them)
+  const int32_t* src = a.out.list_tmp + first;
+  for (int base = blockIdx.y * BA_THREADS; base < cnt; base += BA_SORT_SPLIT * BA_THREADS) {      // (the same trip count for every thread)
+    const int mine = base + t < cnt ? src[base + t] : 0x7fffffff;
+    int rank = 0;
+    for (int tb = 0; tb < cnt; tb += BA_THREADS) {
+      __syncthreads();
+      s_tile[t] = tb + t < cnt ? src[tb + t] : 0x7fffffff;
+      __syncthreads();
+      const int m = cnt - tb < BA_THREADS ? cnt - tb : BA_THREADS;
+      for (int j = 0; j < m; ++j) rank += s_tile[j] < mine ? 1 : 0;
+    }
+    if (base + t < cnt && rank < cnt) a.out.cam_list[first + rank] = mine;      // the entries differ: the ranks are 0 .. cnt - 1
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- setup of a round's system
+// One wave per slot.  U, g_c as in the camera kernel; then, in the same order (the lane's own ascending sum, a butterfly), B = sum Y_o g_p
+// and the 21 sums of Y_o W_o^T over the slot's own observations.  b = -g_c + B goes into r; M = U* - sum Y W^T is factored in registers.
+__global__ __launch_bounds__(64) void ba_pcg_setup_kernel(BaArgs a) {
+  const int s = blockIdx.x, lane = threadIdx.x;
+  BaState* st = a.out.st;
+  if (st->stop) return;
+  double* srec = a.out.slot_rec + (int64_t)BA_SLOT_REC * s;
+  double* rs = a.out.vr + (int64_t)6 * s;
+  if (a.out.held[s]) {                                         // a held camera does not move: identity blocks and a zero right-hand side
+    if (lane < BA_SLOT_REC) {
+      const int k = lane < 21 ? lane : lane - 21;
+      const bool diag = lane < 21 ? (k == 0 || k == 6 || k == 11 || k == 15 || k == 18 || k == 20) : (k == 0 || k == 2 || k == 5 || k == 9 || k == 14 || k == 20);
+      srec[lane] = diag ? 1.0 : 0.0;
+    }
+    if (lane < 6) rs[lane] = 0.0;
+    return;
+  }
+  const int first = a.out.slot_ptr[s];
+  int cnt = a.out.slot_ptr[s + 1] - first;
+  if (first < 0 || cnt < 0 || first + cnt > a.n_obs) cnt = 0;   // (never)
+  const int32_t* list = a.out.cam_list + first;
+  double acc[27];
+#pragma unroll
+  for (int j = 0; j < 27; ++j) acc[j] = 0.0;
+  for (int idx = lane; idx < cnt; idx += 64) {
+    const int o = list[idx];
+    if (o < 0 || o >= a.n_obs) continue;                       // (never)
+    const double* rec = a.out.obs_rec + (int64_t)BA_REC * o;
+    double ju[6], jv[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) ju[j] = rec[j], jv[j] = rec[6 + j];
+    const double ru = rec[12], rv = rec[13];
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = i; j < 6; ++j) acc[k++] += ju[i] * ju[j] + jv[i] * jv[j];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) acc[21 + i] += ju[i] * ru + jv[i] * rv;
+  }
+#pragma unroll
+  for (int j = 0; j < 27; ++j) acc[j] = ba_wave_sum(acc[j]);
+  const double lambda = st->lambda;
+  {
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      acc[k] += lambda * fmax(acc[k], 1e-6);                   // the diagonal entry (i, i) leads row i of the triangle
+      k += 6 - i;
+    }
+  }
+  double am[27];                                               // the 21 sums of Y W^T (upper triangle), then B
+#pragma unroll
+  for (int j = 0; j < 27; ++j) am[j] = 0.0;
+  for (int idx = lane; idx < cnt; idx += 64) {
+    const int o = list[idx];
+    if (o < 0 || o >= a.n_obs) continue;                       // (never)
+    const int p = a.out.obs_track[o];
+    if (p < 0 || p >= a.T) continue;                           // (never)
+    const double* rec = a.out.obs_rec + (int64_t)BA_REC * o;
+    const double* gp = a.out.pt_rec + (int64_t)BA_PT * p + 6;
+    double w[18], y[18];
+#pragma unroll
+    for (int j = 0; j < 18; ++j) w[j] = rec[14 + j], y[j] = rec[32 + j];
+    const double g0 = gp[0], g1 = gp[1], g2 = gp[2];
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = i; j < 6; ++j) am[k++] += (y[3 * i] * w[3 * j] + y[3 * i + 1] * w[3 * j + 1]) + y[3 * i + 2] * w[3 * j + 2];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) am[21 + i] += (y[3 * i] * g0 + y[3 * i + 1] * g1) + y[3 * i + 2] * g2;
+  }
+#pragma unroll
+  for (int j = 0; j < 27; ++j) am[j] = ba_wave_sum(am[j]);
+  double m[6][6];                                              // M, the lower triangle; every lane holds the same bits
+  {
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = i; j < 6; ++j) {
+        m[j][i] = acc[k] - am[k];
+        ++k;
+      }
+  }
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    const double d = m[j][j];
+    ok = ok && ba_finite(d) && d > 0.0;
+    const double l = sqrt(d);
+    m[j][j] = l;
+#pragma unroll
+    for (int i = j + 1; i < 6; ++i) m[i][j] = m[i][j] / l;
+#pragma unroll
+    for (int i = j + 1; i < 6; ++i)
+#pragma unroll
+      for (int k = j + 1; k <= i; ++k) m[i][k] -= m[i][j] * m[k][j];
+  }
+  if (lane != 0) return;
+#pragma unroll
+  for (int j = 0; j < 21; ++j) srec[j] = acc[j];
+  {
+    int k = 21;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = 0; j <= i; ++j) srec[k++] = m[i][j];
+  }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) rs[i] = -acc[21 + i] + am[21 + i];
+  if (!ok) atomicOr(&st->flags, BA_F_IRREGULAR);
+}
+
+// ---------------------------------------------------------------------------------------------- the iteration
+// One workgroup: thread j takes the slots j, j + BA_THREADS, ...  x = 0, z = M^-1 r, p = z, rho_0 = r . z
+__global__ __launch_bounds__(BA_THREADS) void ba_pcg_init_kernel(BaArgs a) {
+  __shared__ double s_part[BA_THREADS / 64];
+  const int t = threadIdx.x;
+  BaState* st = a.out.st;
+  if (st->stop) return;
+  const bool irregular = (st->flags & BA_F_IRREGULAR) != 0;    // a point's V* or a slot's M was not regular: there is nothing to solve
+  double part = 0.0;
+  for (int s = t; s < a.n_free; s += BA_THREADS) {
+    double z[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) a.out.rhs[6 * s + j] = 0.0;
+    if (irregular) continue;
+    ba_msolve(a.out.slot_rec + (int64_t)BA_SLOT_REC * s + 21, a.out.vr + 6 * s, z);
+#pragma unroll
+    for (int j = 0; j < 6; ++j) a.out.vz[6 * s + j] = z[j], a.out.vp[6 * s + j] = z[j];
+    part += ba_dot6(a.out.vr + 6 * s, z);
+  }
+  const double rho = ba_block_sum(part, s_part);
+  if (t != 0) return;
+  const bool good = !irregular && ba_finite(rho) && rho >= 0.0;
+  if (!irregular && !good) atomicOr(&st->flags, BA_F_IRREGULAR);
+  st->rho = good ? rho : 0.0, st->rho0 = good ? rho : 0.0;
+  st->cg_used = 0, st->cg_done = !good || rho == 0.0 ? 1 : 0;
+}
+
+// y = V*^-1 sum W_o^T p_slot(o): a thread per track, its observations ascending, c ascending inside an observation
+__global__ __launch_bounds__(BA_THREADS) void ba_pcg_y_kernel(BaArgs a) {
+  const int t = blockIdx.x * BA_THREADS + threadIdx.x;
+  const BaState* st = a.out.st;
+  if (t >= a.T || st->stop || st->cg_done || a.out.pt_act[t] == 0) return;
+  int beg, len;
+  if (!ba_range(a, t, beg, len)) return;                       // (never: the point is active)
+  double s[3] = {0.0, 0.0, 0.0};
+  for (int o = beg; o < beg + len; ++o) {
+    if (a.out.obs_act[o] == 0) continue;
+    const int k = ba_moving_slot(a, a.obs_image[o]);
+    if (k < 0) continue;
+    const double *w = a.out.obs_rec + (int64_t)BA_REC * o + 14, *pc = a.out.vp + 6 * k;
+    for (int c = 0; c < 6; ++c)
+#pragma unroll
+      for (int m = 0; m < 3; ++m) s[m] += w[3 * c + m] * pc[c];
+  }
+  const double* pr = a.out.pt_rec + (int64_t)BA_PT * t;
+  const double I[3][3] = {{pr[0], pr[1], pr[2]}, {pr[1], pr[3], pr[4]}, {pr[2], pr[4], pr[5]}};
+#pragma unroll
+  for (int m = 0; m < 3; ++m) a.out.y[(int64_t)3 * t + m] = (I[m][0] * s[0] + I[m][1] * s[1]) + I[m][2] * s[2];
+}
+
+// q_s = U*_s p_s - sum W_o y_track(o): a wave per slot, the lane's own ascending sum over the list and a butterfly
+__global__ __launch_bounds__(64) void ba_pcg_sp_kernel(BaArgs a) {
+  const int s = blockIdx.x, lane = threadIdx.x;
+  const BaState* st = a.out.st;
+  if (st->stop || st->cg_done) return;
+  const int first = a.out.slot_ptr[s];
+  int cnt = a.out.slot_ptr[s + 1] - first;
+  if (first < 0 || cnt < 0 || first + cnt > a.n_obs) cnt = 0;   // (never)
+  const int32_t* list = a.out.cam_list + first;
+  double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int idx = lane; idx < cnt; idx += 64) {
+    const int o = list[idx];
+    if (o < 0 || o >= a.n_obs) continue;                       // (never)
+    const int p = a.out.obs_track[o];
+    if (p < 0 || p >= a.T) continue;                           // (never)
+    const double *w = a.out.obs_rec + (int64_t)BA_REC * o + 14, *y = a.out.y + (int64_t)3 * p;
+    const double y0 = y[0], y1 = y[1], y2 = y[2];
+#pragma unroll
+    for (int r = 0; r < 6; ++r) acc[r] += (w[3 * r] * y0 + w[3 * r + 1] * y1) + w[3 * r + 2] * y2;
+  }
+#pragma unroll
+  for (int r = 0; r < 6; ++r) acc[r] = ba_wave_sum(acc[r]);
+  if (lane >= 6) return;
+  const double *U = a.out.slot_rec + (int64_t)BA_SLOT_REC * s, *pc = a.out.vp + 6 * s;
+  double up = 0.0, wy = 0.0;
+#pragma unroll
+  for (int r = 0; r < 6; ++r)
+    if (r == lane) wy = acc[r];
+  for (int c = 0; c < 6; ++c) {
+    const int i = lane < c ? lane : c, j = lane < c ? c : lane;
+    const double term = U[i * 6 - i * (i - 1) / 2 + (j - i)] * pc[c];
+    up = c == 0 ? term : up + term;
+  }
+  a.out.vq[6 * s + lane] = up - wy;
+}
+
+// One workgroup: alpha = rho / (p . q), x += alpha p, r -= alpha q, z = M^-1 r, rho' = r . z, the stop test, p = z + (rho' / rho) p
+__global__ __launch_bounds__(BA_THREADS) void ba_pcg_step_kernel(BaArgs a, int last) {
+  __shared__ double s_part[BA_THREADS / 64];
+  const int t = threadIdx.x;
+  BaState* st = a.out.st;
+  if (st->stop || st->cg_done) return;
+  const double rho = st->rho, rho0 = st->rho0;
+  double part = 0.0;
+  for (int s = t; s < a.n_free; s += BA_THREADS) part += ba_dot6(a.out.vp + 6 * s, a.out.vq + 6 * s);
+  const double pq = ba_block_sum(part, s_part);
+  if (!(ba_finite(pq) && pq > 0.0)) {                          // the same for every thread
+    if (t == 0) atomicOr(&st->flags, BA_F_IRREGULAR), st->cg_done = 1, st->cg_used += 1;
+    return;
+  }
+  const double alpha = rho / pq;
+  part = 0.0;
+  for (int s = t; s < a.n_free; s += BA_THREADS) {
+    double r[6], z[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      a.out.rhs[6 * s + j] = a.out.rhs[6 * s + j] + alpha * a.out.vp[6 * s + j];
+      r[j] = a.out.vr[6 * s + j] - alpha * a.out.vq[6 * s + j];
+      a.out.vr[6 * s + j] = r[j];
+    }
+    ba_msolve(a.out.slot_rec + (int64_t)BA_SLOT_REC * s + 21, r, z);
+#pragma unroll
+    for (int j = 0; j < 6; ++j) a.out.vz[6 * s + j] = z[j];
+    part += ba_dot6(r, z);
+  }
+  const double rho1 = ba_block_sum(part, s_part);
+  const bool good = ba_finite(rho1) && rho1 >= 0.0;
+  const bool done = !good || rho1 <= a.cg_tol2 * rho0 || last != 0;
+  if (!done) {
+    const double beta = rho1 / rho;
+    for (int s = t; s < a.n_free; s += BA_THREADS)
+#pragma unroll
+      for (int j = 0; j < 6; ++j) a.out.vp[6 * s + j] = a.out.vz[6 * s + j] + beta * a.out.vp[6 * s + j];
+  }
+  if (t != 0) return;
+  if (!good) atomicOr(&st->flags, BA_F_IRREGULAR);
+  st->rho = rho1, st->cg_used += 1, st->cg_done = done ? 1 : 0;
+}
+
+// The candidate camera of every slot that moves, into the buffer that is not current (the last part of the solve kernel), and the
+// round's cg_used and cg_res.  An irregular round has d = 0.
+__global__ __launch_bounds__(BA_THREADS) void ba_pcg_cand_kernel(BaArgs a, int round) {
+  const int s = blockIdx.x * BA_THREADS + threadIdx.x;
+  BaState* st = a.out.st;
+  if (st->stop) return;
+  const bool regular = (st->flags & BA_F_IRREGULAR) == 0;
+  if (s == 0) {
+    a.out.cg_used[round] = st->cg_used;
+    a.out.cg_res[round] = regular && st->rho0 > 0.0 ? sqrt(st->rho / st->rho0) : 0.0;
+  }
+  if (s >= a.n_free) return;
+  if (!regular) {
+#pragma unroll
+    for (int j = 0; j < 6; ++j) a.out.rhs[6 * s + j] = 0.0;
+    return;
+  }
+  if (a.out.held[s] != 0) return;
+  const int cam = a.out.slot_cam[s];
+  const double* cur = ba_cams(a, st->cur) + (int64_t)BA_CAM * cam;
+  double* cand = ba_cams(a, st->cur ^ 1) + (int64_t)BA_CAM * cam;
+  const double* d = a.out.rhs + 6 * s;
+  const double th2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2], th = sqrt(th2);
+  const double ca = th > 1e-8 ? sin(th) / th : 1.0, cb = th > 1e-8 ? (1.0 - cos(th)) / th2 : 0.5;
+  const double W[3][3] = {{0.0, -d[2], d[1]}, {d[2], 0.0, -d[0]}, {-d[1], d[0], 0.0}};
+  bool fin = true;
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      double ex[3];
+      for (int m = 0; m < 3; ++m) ex[m] = (i == m ? 1.0 : 0.0) + ca * W[i][m] + cb * (W[i][0] * W[0][m] + W[i][1] * W[1][m] + W[i][2] * W[2][m]);
+      const double v = ex[0] * cur[4 + j] + ex[1] * cur[7 + j] + ex[2] * cur[10 + j];
+      cand[4 + 3 * i + j] = v;
+      fin = fin && ba_finite(v);
+    }
+  for (int i = 0; i < 3; ++i) {
+    const double v = cur[13 + i] + d[3 + i];
+    cand[13 + i] = v;
+    fin = fin && ba_finite(v);
+  }
+  if (!fin) atomicOr(&st->flags, BA_F_NOT_FINITE);
+}
+
+// the launches of the conjugate-gradient form behind init and classify: 8 + iters (6 + 3 cg_iters) in all, 5 + 3 iters when n_free == 0
+static int ba_pcg_launches(const BaArgs& a, unsigned g_all, unsigned g_T, hipStream_t st) {
+  const unsigned g_obs = (unsigned)(a.n_obs > 0 ? cdiv((int64_t)a.n_obs, BA_THREADS) : 1), g_slots = (unsigned)cdiv((int64_t)(a.n_free > 0 ? a.n_free : 1), BA_THREADS);
+  if (a.n_free > 0) {
+    ba_pcg_slots_kernel<<<1, BA_THREADS, 0, st>>>(a);
+    GIMS_LAUNCH_CHECK();
+    ba_pcg_fill_kernel<<<g_obs, BA_THREADS, 0, st>>>(a);
+    GIMS_LAUNCH_CHECK();
+    ba_pcg_sort_kernel<<<dim3((unsigned)a.n_free, BA_SORT_SPLIT), BA_THREADS, 0, st>>>(a);
+    GIMS_LAUNCH_CHECK();
+  }
+  ba_back_kernel<<<g_T, BA_THREADS, 0, st>>>(a, 1);
+  GIMS_LAUNCH_CHECK();
+  ba_decide_kernel<<<1, BA_THREADS, 0, st>>>(a, -1);
+  GIMS_LAUNCH_CHECK();
+  for (int r = 0; r < a.iters; ++r) {
+    ba_point_kernel<<<g_T, BA_THREADS, 0, st>>>(a);
+    GIMS_LAUNCH_CHECK();
+    if (a.n_free > 0) {
+      ba_pcg_setup_kernel<<<(unsigned)a.n_free, 64, 0, st>>>(a);
+      GIMS_LAUNCH_CHECK();
+      ba_pcg_init_kernel<<<1, BA_THREADS, 0, st>>>(a);
+      GIMS_LAUNCH_CHECK();
+      for (int it = 0; it < a.cg_iters; ++it) {
+        ba_pcg_y_kernel<<<g_T, BA_THREADS, 0, st>>>(a);
+        GIMS_LAUNCH_CHECK();
+        ba_pcg_sp_kernel<<<(unsigned)a.n_free, 64, 0, st>>>(a);
+        GIMS_LAUNCH_CHECK();
+        ba_pcg_step_kernel<<<1, BA_THREADS, 0, st>>>(a, it + 1 == a.cg_iters ? 1 : 0);
+        GIMS_LAUNCH_CHECK();
+      }
+      ba_pcg_cand_kernel<<<g_slots, BA_THREADS, 0, st>>>(a, r);
+      GIMS_LAUNCH_CHECK();
+    }
+    ba_back_kernel<<<g_T, BA_THREADS, 0, st>>>(a, 0);
+    GIMS_LAUNCH_CHECK();
+    ba_decide_kernel<<<1, BA_THREADS, 0, st>>>(a, r);
+    GIMS_LAUNCH_CHECK();
+  }
+  ba_finish_kernel<<<g_all, BA_THREADS, 0, st>>>(a);
+  GIMS_LAUNCH_CHECK();
+  return GIMS_OK;
+}
+
+// GIMS_AUX_BUNDLE_ADJUST and GIMS_AUX_BUNDLE_ADJUST_PCG of gims_run_ops (include/gims_hip.h): every argument check precedes the first HIP call
+static int ba_aux(const gims_aux_args& x, hipStream_t st, const bool pcg) {
   const int64_t T = x.i[0], n_obs = x.i[1], n_images = x.i[2], N = x.i[3], iters = x.i[4];
   const float huber = x.f[0], lambda0 = x.f[1];
   // i[5] is where a later form of this function (a blocked or iterative reduced solve) would be selected: it is read FIRST
@@ -654,7 +1146,7 @@ int bundle_adjust_aux(const gims_aux_args& x, hipStream_t st) {
   GIMS_CHECK_ARG((((uintptr_t)x.p[0] | (uintptr_t)x.p[2] | (uintptr_t)x.p[3]) & 7) == 0, "bundle_adjust: the table, xyz and cams must be 8-byte aligned");
   GIMS_CHECK_ARG((((uintptr_t)x.p[1] | (uintptr_t)x.p[4]) & 3) == 0, "bundle_adjust: kpts and mode must be 4-byte aligned");
   const int64_t* tab = (const int64_t*)x.p[0];                 // a HOST array, like the op table itself
-  GIMS_CHECK_ARG(tab[5] == 0 && tab[6] == 0 && tab[7] == 0, "bundle_adjust: the table words 5 .. 7 are reserved and must be 0");
+  GIMS_CHECK_ARG(pcg || (tab[5] == 0 && tab[6] == 0 && tab[7] == 0), "bundle_adjust: the table words 5 .. 7 are reserved and must be 0");
   GIMS_CHECK_ARG(((tab[0] | tab[1] | tab[2]) & 3) == 0, "bundle_adjust: indptr, obs_image and obs_keypoint must be 4-byte aligned");
   GIMS_CHECK_ARG(T == 0 || (tab[0] && tab[1] && tab[2] && tab[3] && tab[4] && x.p[1] && x.p[2]),
                  "bundle_adjust: indptr, obs_image, obs_keypoint, obs_use, point_use, kpts or xyz is NULL while T = %lld", (long long)T);
@@ -669,11 +1161,23 @@ int bundle_adjust_aux(const gims_aux_args& x, hipStream_t st) {
     n_fixed += mode[k] == 1;
   }
   const int64_t n_free = (int64_t)slot_cam.size();
-  GIMS_CHECK_ARG(n_free <= BA_MAX_FREE, "bundle_adjust: %lld free cameras, at most GIMS_BA_MAX_FREE_CAMERAS = %d (a larger set needs the blocked reduced solve)",
+  GIMS_CHECK_ARG(pcg || n_free <= BA_MAX_FREE, "bundle_adjust: %lld free cameras, at most GIMS_BA_MAX_FREE_CAMERAS = %d (a larger set needs the blocked reduced solve)",
                  (long long)n_free, BA_MAX_FREE);
+  GIMS_CHECK_ARG(!pcg || n_free <= BA_PCG_MAX_FREE, "bundle_adjust: %lld free cameras, at most GIMS_BA_PCG_MAX_FREE_CAMERAS = %d", (long long)n_free, BA_PCG_MAX_FREE);
+  double cg_tol = 0.0;
+  if (pcg) {                                                   // the words of this form, behind the checks the two forms share
+    memcpy(&cg_tol, tab + 6, sizeof(double));
+    GIMS_CHECK_ARG(tab[5] >= 1 && tab[5] <= BA_PCG_MAX_ITERS, "bundle_adjust: cg_iters = %lld (table word 5) is out of range (1 .. %d)", (long long)tab[5], BA_PCG_MAX_ITERS);
+    GIMS_CHECK_ARG(cg_tol - cg_tol == 0.0 && cg_tol >= 0.0 && cg_tol < 1.0, "bundle_adjust: cg_tol = %g (table word 6) must be finite with 0 <= cg_tol < 1", cg_tol);
+    GIMS_CHECK_ARG(tab[7] == 0, "bundle_adjust: the table word 7 is reserved and must be 0");
+  }
 
   BaArgs a;
-  ba_layout((void*)x.p[5], T, n_obs, n_images, iters, n_free, a.out);
+  if (pcg)
+    ba_pcg_layout((void*)x.p[5], T, n_obs, n_images, iters, n_free, a.out);
+  else
+    ba_layout((void*)x.p[5], T, n_obs, n_images, iters, n_free, a.out);
+  a.cg_iters = pcg ? (int)tab[5] : 0, a.cg_tol2 = cg_tol * cg_tol;
   a.indptr = (const int32_t*)tab[0], a.obs_image = (const int32_t*)tab[1], a.obs_keypoint = (const int32_t*)tab[2];
   a.obs_use = (const uint8_t*)tab[3], a.point_use = (const uint8_t*)tab[4];
   a.kpts = (const float*)x.p[1], a.xyz_in = (const double*)x.p[2], a.cams_in = (const double*)x.p[3];
@@ -681,6 +1185,10 @@ int bundle_adjust_aux(const gims_aux_args& x, hipStream_t st) {
   a.N = N, a.huber = (double)huber, a.lambda0 = (double)lambda0;
   GIMS_HIP(hipMemsetAsync(a.out.st, 0, 256, st));
   if (iters > 0) GIMS_HIP(hipMemsetAsync(a.out.taken, 0, (size_t)iters, st));
+  if (pcg && iters > 0) {
+    GIMS_HIP(hipMemsetAsync(a.out.cg_used, 0, sizeof(int32_t) * (size_t)iters, st));
+    GIMS_HIP(hipMemsetAsync(a.out.cg_res, 0, sizeof(double) * (size_t)iters, st));
+  }
   if (n_obs > 0) {
     GIMS_HIP(hipMemsetD32Async((hipDeviceptr_t)a.out.obs_error, (int)0xBF800000u, (size_t)n_obs, st));      // -1.f
     GIMS_HIP(hipMemsetAsync(a.out.obs_act, 0, (size_t)n_obs, st));
@@ -699,6 +1207,7 @@ int bundle_adjust_aux(const gims_aux_args& x, hipStream_t st) {
   GIMS_LAUNCH_CHECK();
   ba_classify_kernel<<<g_T, BA_THREADS, 0, st>>>(a);
   GIMS_LAUNCH_CHECK();
+  if (pcg) return ba_pcg_launches(a, g_all, g_T, st);
   ba_slots_kernel<<<1, BA_MAX_FREE, 0, st>>>(a);
   GIMS_LAUNCH_CHECK();
   if (n_free > 0) {
@@ -729,5 +1238,8 @@ int bundle_adjust_aux(const gims_aux_args& x, hipStream_t st) {
   GIMS_LAUNCH_CHECK();
   return GIMS_OK;
 }
+
+int bundle_adjust_aux(const gims_aux_args& x, hipStream_t st) { return ba_aux(x, st, false); }
+int bundle_adjust_pcg_aux(const gims_aux_args& x, hipStream_t st) { return ba_aux(x, st, true); }
 
 }  // namespace gims

@@ -84,6 +84,8 @@ RESECT_HB = _K["GIMS_RESECT_HB"]                             # hypotheses per wo
 RESECT_COUNTERS = ("n_ok", "n_failed", "n_corr_total", "n_inlier_total")
 AUX_BUNDLE_ADJUST = _K["GIMS_AUX_BUNDLE_ADJUST"]             # joint refinement of cameras and points (bundle adjustment): likewise; 12 is unassigned
 BA_TABLE_WORDS, BA_MAX_FREE_CAMERAS, BA_MAX_REJECTS = _K["GIMS_BA_TABLE_WORDS"], _K["GIMS_BA_MAX_FREE_CAMERAS"], _K["GIMS_BA_MAX_REJECTS"]
+AUX_BUNDLE_ADJUST_PCG = _K["GIMS_AUX_BUNDLE_ADJUST_PCG"]     # the same with a matrix-free conjugate-gradient reduced solve: no 128-camera cap
+BA_PCG_MAX_FREE_CAMERAS, BA_PCG_MAX_CG_ITERS = _K["GIMS_BA_PCG_MAX_FREE_CAMERAS"], _K["GIMS_BA_PCG_MAX_CG_ITERS"]
 BA_COUNTERS = ("n_free", "n_fixed", "n_held", "n_points", "n_active_obs", "n_bad_obs", "rounds_taken", "status")
 BA_BAD_CAMERA, BA_BAD_START = 1, 2                           # the bits of the status counter
 BA_ABSENT, BA_FIXED, BA_FREE = 0, 1, 2                       # the modes of a camera
@@ -1456,12 +1458,31 @@ def ba_out_layout(T: int, n_obs: int, n_images: int, iters: int, n_free: int) ->
     return off
 
 
-def ba_table(indptr, obs_image, obs_keypoint, obs_use, point_use) -> np.ndarray:
+def ba_pcg_out_layout(T: int, n_obs: int, n_images: int, iters: int, n_free: int) -> dict:
+    """BYTE offsets into the one buffer of GIMS_AUX_BUNDLE_ADJUST_PCG (include/gims_hip.h; csrc/ba.hip ba_pcg_layout carves it): the seven
+    output regions of ba_out_layout at the same offsets, then cg_used int32 [iters] and cg_res float64 [iters]; 'outputs' = 'scratch' =
+    the offset of the kernels' scratch, which is linear in every size (no reduced system is stored), 'bytes' = the whole buffer."""
+    al = lambda x: (x + 255) & ~255      # noqa: E731
+    off, at = {}, 0
+    for name, size in (("xyz", 24 * T), ("cams", 144 * n_images), ("obs_error", 4 * n_obs), ("cam_obs", 4 * n_images), ("history", 16 * (iters + 1)),
+                       ("taken", iters), ("counters", 32), ("cg_used", 4 * iters), ("cg_res", 8 * iters)):
+        off[name] = at
+        at += al(size)
+    off["outputs"] = off["scratch"] = at
+    off["bytes"] = at + (256 + al(4 * n_images) + 3 * al(4 * n_free) + al(4 * n_free + 4) + al(24 * T) + al(144 * n_images) + al(T) + al(n_obs)
+                         + 4 * al(4 * n_obs) + al(72 * T) + al(400 * n_obs) + al(8 * T) + al(24 * T) + al(336 * n_free) + 5 * al(48 * n_free))
+    return off
+
+
+def ba_table(indptr, obs_image, obs_keypoint, obs_use, point_use, cg_iters: int = 0, cg_tol: float = 0.0) -> np.ndarray:
     """The HOST table of GIMS_AUX_BUNDLE_ADJUST, int64 [8]: the addresses of the five device arrays (tensors, raw addresses, or None) and
-    three reserved zeros.  The caller keeps it, and the tensors, alive for as long as the op is run."""
+    three reserved zeros.  For GIMS_AUX_BUNDLE_ADJUST_PCG word 5 is cg_iters and word 6 the bit pattern of the double cg_tol (the
+    defaults leave both 0).  The caller keeps it, and the tensors, alive for as long as the op is run."""
     tab = np.zeros(BA_TABLE_WORDS, dtype=np.int64)
     for k, t in enumerate((indptr, obs_image, obs_keypoint, obs_use, point_use)):
         tab[k] = 0 if t is None else t if isinstance(t, int) else t.data_ptr()
+    tab[5] = int(cg_iters)
+    tab[6:7] = np.array([cg_tol], dtype=np.float64).view(np.int64)
     return tab
 
 
@@ -1489,17 +1510,44 @@ def ba_views(out: torch.Tensor, T: int, n_obs: int, n_images: int, iters: int, n
                 counters=cut("counters", 32, torch.int32))
 
 
+def op_bundle_adjust_pcg(table: np.ndarray, kpts, xyz, cams, mode: np.ndarray, out, T: int, n_obs: int, n: int, iters: int = 20, huber: float = 0.0,
+                         lambda0: float = 1e-4) -> Op:
+    """GIMS_AUX_BUNDLE_ADJUST_PCG as an op of gims_run_ops (include/gims_hip.h): the arguments of op_bundle_adjust, with the table of
+    ba_table(..., cg_iters=, cg_tol=) and out uint8 [ba_pcg_out_layout(T, n_obs, n_images, iters, n_free)['bytes']]."""
+    op = op_bundle_adjust(table, kpts, xyz, cams, mode, out, T, n_obs, n, iters, huber, lambda0)      # (the same checks of the host arrays)
+    op.u.aux.fn = AUX_BUNDLE_ADJUST_PCG
+    return op
+
+
+def ba_pcg_views(out: torch.Tensor, T: int, n_obs: int, n_images: int, iters: int, n_free: int) -> dict:
+    """The typed views of the buffer of GIMS_AUX_BUNDLE_ADJUST_PCG, by ba_pcg_out_layout: those of ba_views, cg_used and cg_res."""
+    o = ba_pcg_out_layout(T, n_obs, n_images, iters, n_free)
+    views = ba_views(out, T, n_obs, n_images, iters, n_free)      # (the seven regions lie at the offsets of the dense form)
+    views["cg_used"] = out[o["cg_used"]:o["cg_used"] + 4 * iters].view(torch.int32)
+    views["cg_res"] = out[o["cg_res"]:o["cg_res"] + 8 * iters].view(torch.float64)
+    return views
+
+
 def bundle_adjust(indptr, obs_image, obs_keypoint, obs_use, point_use, kpts, xyz, cams, mode: np.ndarray, iters: int = 20, huber: float = 0.0,
-                  lambda0: float = 1e-4, T: int | None = None, n_obs: int | None = None, n: int | None = None):
+                  lambda0: float = 1e-4, T: int | None = None, n_obs: int | None = None, n: int | None = None, solver: str = "dense",
+                  cg_iters: int = 64, cg_tol: float = 1e-6):
     """Joint refinement of the free cameras and the active points on the device (csrc/ba.hip): device tensors as
     op_bundle_adjust takes them (cams the DEVICE records float64 [n_images, 18]), mode the HOST int32 [n_images]; T, n_obs, n: the sizes to
     state when a tensor is a stand-in for an empty one (default: the tensors' own).  -> (the views of ba_views, and what must stay alive
-    until the launches have run).  Asynchronous; no host read."""
+    until the launches have run).  Asynchronous; no host read.  solver='pcg': GIMS_AUX_BUNDLE_ADJUST_PCG with cg_iters and cg_tol
+    (DESIGN.md 4.21), the views of ba_pcg_views; with 'dense' the two are not used."""
+    if solver not in ("dense", "pcg"):
+        raise ValueError(f"bundle_adjust: solver must be 'dense' or 'pcg', got {solver!r}")
     mode = np.ascontiguousarray(mode, dtype=np.int32).reshape(-1)
     T = indptr.numel() - 1 if T is None else T
     n_obs = obs_image.numel() if n_obs is None else n_obs
     n = kpts.shape[0] if n is None else n
     n_free = int((mode == BA_FREE).sum())
+    if solver == "pcg":
+        table = ba_table(indptr, obs_image, obs_keypoint, obs_use, point_use, cg_iters=cg_iters, cg_tol=cg_tol)
+        out = torch.empty(ba_pcg_out_layout(T, n_obs, mode.size, iters, n_free)["bytes"], dtype=torch.uint8, device=xyz.device)
+        run_ops(make_ops([op_bundle_adjust_pcg(table, kpts, xyz, cams, mode, out, T, n_obs, n, iters, huber, lambda0)]))
+        return ba_pcg_views(out, T, n_obs, mode.size, iters, n_free), (table, mode, out, indptr, obs_image, obs_keypoint, obs_use, point_use, kpts, xyz, cams)
     table = ba_table(indptr, obs_image, obs_keypoint, obs_use, point_use)
     out = torch.empty(ba_out_layout(T, n_obs, mode.size, iters, n_free)["bytes"], dtype=torch.uint8, device=xyz.device)
     run_ops(make_ops([op_bundle_adjust(table, kpts, xyz, cams, mode, out, T, n_obs, n, iters, huber, lambda0)]))

@@ -691,7 +691,68 @@ int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t
  * walking a list of its observations that a count (integer atomics), a scan and an ordered fill build once per call (lane j takes
  * observation j of the walked observation's track, so the blocks of one walked observation are formed side by side); one workgroup of
  * 1024 factors S in place and solves; a thread per track substitutes back and sums its candidate cost; one workgroup sums the costs and
- * one thread decides.  There are no float atomics and no sum whose order depends on the grid: the output bytes are identical across runs. */
+ * one thread decides.  There are no float atomics and no sum whose order depends on the grid: the output bytes are identical across runs.
+ *
+ * GIMS_AUX_BUNDLE_ADJUST_PCG is the eighth: the same adjustment for up to GIMS_BA_PCG_MAX_FREE_CAMERAS free cameras.  The
+ * model, the activity rules, the status bits, the held-camera rule, the Levenberg-Marquardt schedule, the TAKEN rule, the two-buffer state
+ * and the seven outputs are those of GIMS_AUX_BUNDLE_ADJUST, word for word; what differs is where the camera step d of a round comes from:
+ * preconditioned conjugate gradients on the Schur complement S, which is applied and never formed, with a block-Jacobi preconditioner.
+ * GIMS_AUX_BUNDLE_ADJUST itself is unchanged.  kernels: ba_pcg_*_kernel, gims_amd/csrc/ba.hip; tests/ba_pcg_ref.py is the restatement.
+ *   p[], i[] and f[] as for GIMS_AUX_BUNDLE_ADJUST (i[5] is the form word: read first, must be 0), except the table, whose words 5 .. 7 are
+ *               {cg_iters (1 .. GIMS_BA_PCG_MAX_CG_ITERS), the bit pattern of the double cg_tol (finite, 0 <= cg_tol < 1), 0}, and
+ *   p[5] out    the seven output regions of GIMS_AUX_BUNDLE_ADJUST in their order, then
+ *                 int32 cg_used [iters] | double cg_res [iters] |
+ *                 scratch: 256 bytes of state | int32 [n_images] | int32 [n_free] | int32 [n_free + 1] | int32 [n_free] x 2 | double [T][3] |
+ *                 double [n_images][18] | uint8 [T] | uint8 [n_obs] | int32 [n_obs] x 4 | double [T][9] | double [n_obs][50] | double [T] |
+ *                 double [T][3] | double [n_free][42] | double [n_free][6] x 5
+ *               every region on a 256-byte boundary: the outputs of GIMS_AUX_BUNDLE_ADJUST + al256(4 iters) + al256(8 iters) bytes of outputs
+ *               and 256 + al256(4 n_images) + 3 al256(4 n_free) + al256(4 n_free + 4) + al256(24 T) + al256(144 n_images) + al256(T) +
+ *               al256(n_obs) + 4 al256(4 n_obs) + al256(72 T) + al256(400 n_obs) + al256(8 T) + al256(24 T) + al256(336 n_free) +
+ *               5 al256(48 n_free) bytes of scratch (hip.ba_pcg_out_layout has the offsets): linear in T, n_obs, n_images and n_free,
+ *               there is no n x n region.  cg_used[r] = the conjugate-gradient iterations that did work in round r, cg_res[r] =
+ *               sqrt(rho_stop / rho_0) of round r; both 0 for a round that did nothing, for every round when n_free == 0, and cg_res = 0
+ *               for a round that is not regular or has rho_0 = 0.
+ * One round.  V, g_p, V*, V*^-1 = I, W, Y = W V*^-1 per observation, U, g_c and U* per slot are those of GIMS_AUX_BUNDLE_ADJUST.  "The
+ *   slot's order" below is the order stated there for U: lane l of 64 adds the terms of the observations number l, l + 64, ... of the
+ *   slot's list (the active observations of its image, ascending in o) and the lanes are summed by a butterfly (offsets 32 .. 1).
+ *   Per slot s that is not held, each sum in the slot's order:
+ *     B[r] = sum (Y_o[r][0] g_p[0] + Y_o[r][1] g_p[1]) + Y_o[r][2] g_p[2] (g_p of the observation's point),   b_s[r] = -g_c[r] + B[r];
+ *     N[i][j] = sum (Y_o[i][0] W_o[j][0] + Y_o[i][1] W_o[j][1]) + Y_o[i][2] W_o[j][2] for i <= j (the slot's own observations only: no
+ *     cross term between two observations of one track), M_s[i][j] = M_s[j][i] = U*[i][j] - N[i][j].  M_s is symmetric positive definite
+ *     whenever V* is: every term Jc^T Jc - W V*^-1 W^T is positive semi-definite and the damping makes the sum definite.  M_s = L L^T by
+ *     the Cholesky of GIMS_AUX_BUNDLE_ADJUST on 6 x 6 (for j ascending: l = sqrt(M_jj), L_ij = M_ij / l for i > j, M_ik -= L_ij L_kj for
+ *     j < k <= i); M^-1 r: L y = r (j ascending: y_j = r_j / L_jj, then r_i -= L_ij y_j for i > j), L^T z = y (j descending: z_j = y_j /
+ *     L_jj, then y_k -= L_jk z_j for k < j).
+ *   A held slot is outside the system: its six words of every vector are 0, and d = 0.
+ *   The product q = S v.  Per active point, s = 0, then over its active observations in ascending o whose camera moves, in slot k, for c
+ *   ascending: s[m] += W_o[c][m] v[6 k + c]; y[m] = (I[m][0] s[0] + I[m][1] s[1]) + I[m][2] s[2].  Per slot that is not held: q_s[r] =
+ *   ((((U*[r][0] v_s[0] + U*[r][1] v_s[1]) + U*[r][2] v_s[2]) + ...) + U*[r][5] v_s[5]) - sum (W_o[r][0] y[0] + W_o[r][1] y[1]) + W_o[r][2]
+ *   y[2], y of the observation's point, the sum in the slot's order.
+ *   A dot product v . w is per slot ((((v0 w0 + v1 w1) + v2 w2) + v3 w3) + v4 w4) + v5 w5, and the slots are summed by the scheme of the
+ *   cost: thread j of 256 adds the slots j, j + 256, ... ascending (a held slot gives 0), a butterfly per wave, the four waves in order.
+ *   x = 0, r = b, z = M^-1 r, p = z, rho_0 = rho = r . z.  With rho_0 = 0 there is no iteration and d = 0.  Iteration number it = 1 ..
+ *   cg_iters: q = S p; pq = p . q; alpha = rho / pq; x <- x + alpha p; r <- r - alpha q; z = M^-1 r; rho' = r . z; the iteration STOPS iff
+ *   rho' <= (cg_tol cg_tol) rho_0 or it = cg_iters; otherwise p <- z + (rho' / rho) p, rho <- rho'.  d = x, rho_stop = the last rho'.
+ *   The round is REGULAR iff the det of every active point and every pivot of every M_s is finite and > 0, every pq is finite and > 0 and
+ *   every rho (rho_0 and each rho') is finite and >= 0; the first value that fails ends the iteration (cg_used counts the iteration that
+ *   found it), d = 0 and the round is not taken.  Back-substitution from d, the candidate, TAKEN, lambda, the stop after
+ *   GIMS_BA_MAX_REJECTS rounds and the history are those of GIMS_AUX_BUNDLE_ADJUST.
+ * GIMS_EINVAL before any HIP call, each with a message naming bundle_adjust: everything GIMS_AUX_BUNDLE_ADJUST refuses, with
+ * GIMS_BA_PCG_MAX_FREE_CAMERAS in the place of its cap; cg_iters outside 1 .. GIMS_BA_PCG_MAX_CG_ITERS; cg_tol not finite, negative or >= 1;
+ * table word 7 not 0.  The three words of this form are checked last, behind everything the two forms share.
+ * Nothing outside out is written.  A fixed sequence of memset nodes, the upload of the slot tables and 8 + iters (6 + 3 cg_iters) launches:
+ * init, classify, slots, fill, sort, back, decide; per round point, setup, cg-init, cg_iters x {y, S p, step}, candidate, back, decide;
+ * finish -- 5 + 3 iters when n_free == 0 (init, classify, back, decide; point, back, decide; finish).  The sequence depends on iters,
+ * cg_iters and n_free == 0 only: the iterations after the stop are launched and return at once, the decision lives in the state block.
+ * No host synchronisation; capturable by gims_ops_graph_create.  No cooperative launch and no barrier across workgroups: workgroups
+ * exchange data across kernel boundaries only.
+ * How it is computed.  The lists: cam_obs is counted by integer atomics as before; one workgroup scans it into the slots' ranges; a thread
+ * per observation takes a place in its slot's range from an integer cursor (any order); workgroups of 256 per slot (sixteen share a long list) then put every entry where
+ * its rank among the slot's entries says, so the list ends ascending in o whatever the race was (linear in n_obs up to this ordering,
+ * which costs the square of a slot's list length over 256 threads).  A wave per slot forms U*, b, M_s and its factor in registers; a
+ * thread per track forms y; a wave per slot forms q_s; one workgroup of 256 does the dot products, the vector updates and M^-1, and one
+ * thread of it decides.  There are no float atomics and no sum whose order depends on the grid: the output bytes are identical across
+ * runs and graph replays. */
 #define GIMS_OP_AUX 2
 #define GIMS_AUX_SPLIT_SPL32 0
 #define GIMS_AUX_SAGE_MEAN_SPLIT 1
@@ -720,6 +781,9 @@ int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t
 #define GIMS_BA_TABLE_WORDS 8
 #define GIMS_BA_MAX_FREE_CAMERAS 128
 #define GIMS_BA_MAX_REJECTS 5
+#define GIMS_AUX_BUNDLE_ADJUST_PCG 14
+#define GIMS_BA_PCG_MAX_FREE_CAMERAS 65536
+#define GIMS_BA_PCG_MAX_CG_ITERS 256
 typedef struct gims_aux_args { int32_t fn, reserved; const void* p[6]; int64_t i[6]; float f[2]; } gims_aux_args;
 typedef struct gims_op { int32_t kind; int32_t reserved; union { gims_linear_args lin; gims_attn_args att; gims_aux_args aux; } u; } gims_op;
 int gims_run_ops(const gims_op* ops /* HOST */, int32_t n_ops, void* stream);

@@ -11,9 +11,14 @@ bundle_adjust with every resected camera free.  Reports
                   restatement was not run to the end), and scipy.optimize.least_squares (trf, sparse analytic Jacobian, at most --iters
                   evaluations) when scipy imports (`scipy`: null otherwise)
 and what the adjustment did: rms reprojection error and the worst |R - planted|, |t - planted| before and after.  One JSON line, ms.
+--solver pcg runs GIMS_AUX_BUNDLE_ADJUST_PCG with --cg-iters and --cg-tol and adds `cg_used` per round; the restatement of
+the host route is then tests/ba_pcg_ref.py.  The dense solver takes at most 128 free cameras; the scene above that cap is the same
+generator with more images at the same spacing, the arc wound round the scene (--images 254 --span-pi 5 --solver pcg: 256 images, 254
+of them free; on an arc of pi the first two of 256 images would be too close to triangulate from).
 gims_run_ops_timed times whole ops, so the split of a round by kernel is taken from a kernel trace of this tool.
 
 Usage: python tools/ba_bench.py [--images 48] [--points 8192] [--kpts 4096] [--iters 20] [--runs 10] [--host-rounds 2 (0: the device side only)] [--no-scipy]
+                               [--solver dense|pcg] [--cg-iters 64] [--cg-tol 1e-6] [--span-pi 1] [--no-restatement]
 """
 import argparse
 import json
@@ -27,18 +32,21 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import gims_amd  # noqa: E402
 from gims_amd import hip  # noqa: E402
+from tests import ba_pcg_ref as P  # noqa: E402
 from tests import ba_ref as B  # noqa: E402
 from tests import triangulate_ref as R  # noqa: E402
 
 DEV = "cuda"
 
 
-def op_alone(dev, mode, iters, runs, warmup):
+def op_alone(dev, mode, iters, runs, warmup, solver="dense", cg_iters=64, cg_tol=1e-6):
     T, n_obs, n = dev["indptr"].numel() - 1, dev["obs_image"].numel(), dev["kpts"].shape[0]
     n_free = int((mode == 2).sum())
-    out = torch.empty(hip.ba_out_layout(T, n_obs, len(mode), iters, n_free)["bytes"], dtype=torch.uint8, device=DEV)
-    table = hip.ba_table(*(dev[k] for k in ("indptr", "obs_image", "obs_keypoint", "obs_use", "point_use")))
-    ops = hip.make_ops([hip.op_bundle_adjust(table, dev["kpts"], dev["xyz"], dev["cams"], mode, out, T, n_obs, n, iters, 0.0, 1e-4)])
+    pcg = solver == "pcg"
+    layout, make_op, make_views = (hip.ba_pcg_out_layout, hip.op_bundle_adjust_pcg, hip.ba_pcg_views) if pcg else (hip.ba_out_layout, hip.op_bundle_adjust, hip.ba_views)
+    out = torch.empty(layout(T, n_obs, len(mode), iters, n_free)["bytes"], dtype=torch.uint8, device=DEV)
+    table = hip.ba_table(*(dev[k] for k in ("indptr", "obs_image", "obs_keypoint", "obs_use", "point_use")), **(dict(cg_iters=cg_iters, cg_tol=cg_tol) if pcg else {}))
+    ops = hip.make_ops([make_op(table, dev["kpts"], dev["xyz"], dev["cams"], mode, out, T, n_obs, n, iters, 0.0, 1e-4)])
     ev = hip.EventPool(2)
     ms = []
     for it in range(warmup + runs):
@@ -46,9 +54,12 @@ def op_alone(dev, mode, iters, runs, warmup):
         torch.cuda.synchronize()
         if it >= warmup:
             ms.append(ev.elapsed_ms()[0])
-    views = hip.ba_views(out, T, n_obs, len(mode), iters, n_free)
-    return {"median_ms": round(float(np.median(ms)), 4), "min_ms": round(float(np.min(ms)), 4), "max_ms": round(float(np.max(ms)), 4), "runs": len(ms),
-            "stats": dict(zip(hip.BA_COUNTERS, views["counters"].tolist())), "taken": views["taken"].tolist()}
+    views = make_views(out, T, n_obs, len(mode), iters, n_free)
+    res = {"median_ms": round(float(np.median(ms)), 4), "min_ms": round(float(np.min(ms)), 4), "max_ms": round(float(np.max(ms)), 4), "runs": len(ms),
+           "stats": dict(zip(hip.BA_COUNTERS, views["counters"].tolist())), "taken": views["taken"].tolist(), "scratch_mb": round(out.numel() / 2 ** 20, 1)}
+    if pcg:
+        res["cg_used"], res["cg_res_max"] = views["cg_used"].tolist(), float(views["cg_res"].max()) if iters else 0.0
+    return res
 
 
 def scipy_route(host, mode, iters):
@@ -104,15 +115,23 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--host-rounds", type=int, default=2)
     ap.add_argument("--no-scipy", action="store_true")
+    ap.add_argument("--no-restatement", action="store_true", help="the host route by scipy only (the NumPy restatement takes minutes on a large scene)")
+    ap.add_argument("--span-pi", type=float, default=1.0, help="the arc of the cameras in units of pi (more than 2: the arc winds round the scene)")
+    ap.add_argument("--solver", choices=("dense", "pcg"), default="dense")
+    ap.add_argument("--cg-iters", type=int, default=64)
+    ap.add_argument("--cg-tol", type=float, default=1e-6)
     a = ap.parse_args()
+    solve = dict(solver=a.solver, cg_iters=a.cg_iters, cg_tol=a.cg_tol)
     torch.set_grad_enabled(False)
     n_images = a.images + 2
-    m = R.planted_matches(1, n_images, a.points, a.kpts, noise=0.5, w_wrong=a.wrong, neighbours=a.neighbours)
+    m = R.planted_matches(1, n_images, a.points, a.kpts, noise=0.5, w_wrong=a.wrong, neighbours=a.neighbours, span=a.span_pi * np.pi)
     kpts = [torch.from_numpy(k).to(DEV) for k in m["kpts"]]
     outs = [{"matches0": torch.from_numpy(x).to(DEV)[None]} for x in m["matches"]]
     Rn, tn = m["R"].copy(), m["t"].copy()
     Rn[2:], tn[2:] = np.nan, np.nan
-    out = {"images": a.images, "points": a.points, "kpts": a.kpts, "pairs": len(m["pairs"]), "wrong": a.wrong, "iters": a.iters}
+    out = {"images": a.images, "points": a.points, "kpts": a.kpts, "pairs": len(m["pairs"]), "wrong": a.wrong, "iters": a.iters, "solver": a.solver}
+    if a.solver == "pcg":
+        out.update(cg_iters=a.cg_iters, cg_tol=a.cg_tol)
 
     tracks = gims_amd.build_tracks(m["counts"], m["pairs"], outs)
     first = gims_amd.triangulate_tracks(tracks, kpts, (m["K"], Rn, tn))
@@ -127,14 +146,14 @@ def main():
     dev = dict(indptr=tracks.indptr.contiguous(), obs_image=tracks.obs_image.contiguous(), obs_keypoint=tracks.obs_keypoint.contiguous(),
                obs_use=pts.obs_inlier.contiguous(), point_use=pts.valid.view(torch.uint8).contiguous(), kpts=torch.cat(kpts).contiguous(), xyz=pts.xyz.contiguous(),
                cams=torch.from_numpy(rec).to(DEV))
-    out["device_op"] = op_alone(dev, mode, a.iters, a.runs, a.warmup)
-    out["device_op"]["setup_ms"] = op_alone(dev, mode, 0, a.runs, a.warmup)["median_ms"]
+    out["device_op"] = op_alone(dev, mode, a.iters, a.runs, a.warmup, **solve)
+    out["device_op"]["setup_ms"] = op_alone(dev, mode, 0, a.runs, a.warmup, **solve)["median_ms"]
     out["device_op"]["per_round_ms"] = round((out["device_op"]["median_ms"] - out["device_op"]["setup_ms"]) / max(a.iters, 1), 4)
 
-    gims_amd.bundle_adjust(pts, tracks, kpts, cams, iters=a.iters)
+    gims_amd.bundle_adjust(pts, tracks, kpts, cams, iters=a.iters, **solve)
     torch.cuda.synchronize()
     t = time.perf_counter()
-    adj = gims_amd.bundle_adjust(pts, tracks, kpts, cams, iters=a.iters)
+    adj = gims_amd.bundle_adjust(pts, tracks, kpts, cams, iters=a.iters, **solve)
     t_enq = time.perf_counter()
     torch.cuda.synchronize()
     out["bundle_adjust"] = {"wall_ms": round((time.perf_counter() - t) * 1e3, 3), "enqueue_ms": round((t_enq - t) * 1e3, 3)}
@@ -154,7 +173,19 @@ def main():
     host = {k: v.cpu().numpy() for k, v in dev.items()}
     t_read = time.perf_counter()
     rounds = max(1, min(a.host_rounds, max(a.iters, 1)))
-    want = B.adjust(*(host[k] for k in B.ARGS[:8]), mode, iters=rounds)
+    if a.no_restatement:
+        out["host_route"] = {"readback_ms": round((t_read - t) * 1e3, 2)}
+        out["scipy"] = None
+        if not a.no_scipy:
+            try:
+                import scipy
+                out["scipy"] = dict(scipy_route(host, mode, a.iters), version=scipy.__version__, readback_ms=out["host_route"]["readback_ms"])
+            except ImportError:
+                pass
+        print(json.dumps(out))
+        return
+    want = (P.adjust(*(host[k] for k in B.ARGS[:8]), mode, iters=rounds, cg_iters=a.cg_iters, cg_tol=a.cg_tol) if a.solver == "pcg"
+            else B.adjust(*(host[k] for k in B.ARGS[:8]), mode, iters=rounds))
     rest_ms = (time.perf_counter() - t_read) * 1e3
     out["host_route"] = {"readback_ms": round((t_read - t) * 1e3, 2), "restatement_ms": round(rest_ms, 1), "restatement_rounds": rounds,
                          "extrapolated_ms": round((t_read - t) * 1e3 + rest_ms * a.iters / rounds, 1)}
