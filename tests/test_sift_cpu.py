@@ -7,6 +7,7 @@ import pytest
 
 from gims_amd import hip
 from tests import sift_ref as R
+from tests.sift_cases import blob as _blob
 
 
 @pytest.mark.parametrize("h,w", [(480, 640), (680, 850), (517, 333), (640, 800), (12, 16), (9, 9)])
@@ -52,11 +53,6 @@ def test_fast_atan2_within_its_error():
     assert d.max() < 0.01                       # the polynomial's error is about 0.006 degrees
     assert ((a >= 0) & (a < 360)).all()
     assert R.fast_atan2(np.float32(0), np.float32(1)) == 0 and abs(R.fast_atan2(np.float32(1), np.float32(0)) - 90) < 1e-4
-
-
-def _blob(h, w, cx, cy, s):
-    yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
-    return np.clip(np.rint(60 + 150 * np.exp(-((xx - cx) ** 2 + (yy - cy) ** 2) / (2 * s * s))), 0, 255).astype(np.uint8)
 
 
 def test_isotropic_blob_position_and_size():
