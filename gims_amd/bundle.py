@@ -17,7 +17,12 @@ inlier set is an input and is not decided again.  All arithmetic is float64; the
 
 The gauge.  A reconstruction is defined up to a similarity: seven numbers that no observation fixes.  ``fixed`` names the cameras that do
 not move; the default is the first two posed images in index order, which fixes position, orientation and -- through the distance between
-the two -- the scale.  With fewer than two fixed cameras the damping alone keeps the rounds regular and the result drifts."""
+the two -- the scale.  With fewer than two fixed cameras the damping alone keeps the rounds regular and the result drifts.
+
+Focal lengths.  ``refine_focal`` (with ``solver='pcg'``; DESIGN.md 4.22, GIMS_AUX_BUNDLE_ADJUST_FOCAL) makes the focal lengths unknowns: every
+posed image belongs to at most one focal group, and a group has one unknown, a relative scale of ``fx`` and ``fy`` of all its images (the
+aspect ratio and the principal point stay).  A group collects the observations of all its images, those of fixed cameras included: fixing
+a pose fixes the gauge, not the lens."""
 from __future__ import annotations
 
 import math
@@ -38,17 +43,23 @@ class Adjusted:
     lambda} at the start and after every round), ``taken`` uint8 [iters].  With ``solver='pcg'`` also ``cg_used`` int32 [iters] (the
     conjugate-gradient iterations of every round) and ``cg_res`` float64 [iters] (sqrt(rho_stop / rho_0), the preconditioned residual the
     round's iteration stopped at, relative to its start); both are ``None`` for the dense solver.  ``mode``: the host list of the cameras'
-    modes (0 absent, 1 fixed, 2 free).
+    modes (0 absent, 1 fixed, 2 free).  ``K`` float64 [n, 4]: the view fx, fy, cx, cy of ``records``.  With ``refine_focal`` also
+    ``focal_scale`` float64 [n_groups] (refined focal / starting focal of every group; 1 for a held group), ``group_obs`` int32 [n_groups]
+    (the active observations of the group's images) and ``group``, the host list of the images' dense group ids (-1: fixed intrinsics);
+    the three are ``None`` without it.
 
     ``stats`` (n_free, n_fixed, n_held, n_points, n_active_obs, n_bad_obs, rounds_taken, status) reads the op's counters back on first
     access, and ``cameras()`` reads the records: these two synchronise with the device; everything else is handed over asynchronously."""
 
-    def __init__(self, views: dict, mode, K, keep):
+    def __init__(self, views: dict, mode, K, keep, group=None):
         self.xyz, self.records = views["xyz"], views["cams"]
         self.R, self.t = self.records[:, 4:13].unflatten(1, (3, 3)), self.records[:, 13:16]
         self.obs_error, self.cam_obs, self.history, self.taken = views["obs_error"], views["cam_obs"], views["history"], views["taken"]
         self.cg_used, self.cg_res = views.get("cg_used"), views.get("cg_res")
         self.mode = [int(m) for m in mode]
+        self.K = self.records[:, 0:4]
+        self.focal_scale, self.group_obs = views.get("focal_scale"), views.get("group_obs")
+        self.group = None if group is None else [int(g) for g in group]
         self._K, self._counters, self._keep, self._stats = K, views["counters"], keep, None
 
     @property
@@ -65,14 +76,17 @@ class Adjusted:
 
     def cameras(self):
         """The host ``(K, R, t)`` triple for the next ``triangulate_tracks`` / ``resect_images`` / ``bundle_adjust`` call; the absent
-        cameras hold NaN poses, as they did on the way in.
+        cameras hold NaN poses, as they did on the way in.  With ``refine_focal`` K holds the refined fx and fy of the records.
 
         This call SYNCHRONISES with the device: it reads the records back."""
         rec = self.records.cpu().numpy()
         R, t = rec[:, 4:13].reshape(-1, 3, 3).copy(), rec[:, 13:16].copy()
         absent = np.array(self.mode, dtype=np.int64) == hip.BA_ABSENT
         R[absent], t[absent] = np.nan, np.nan
-        return self._K.copy(), R, t
+        K = self._K.copy()
+        if self.group is not None:
+            K[:, 0, 0], K[:, 1, 1] = rec[:, 0], rec[:, 1]
+        return K, R, t
 
     def __len__(self):
         return int(self.xyz.shape[0])
@@ -81,8 +95,46 @@ class Adjusted:
         return f"Adjusted(n_points={len(self)}, n_images={len(self.mode)}, n_free={sum(m == hip.BA_FREE for m in self.mode)})"
 
 
-def _check(points, tracks, images, cameras, fixed, use_obs, use_points, iters, huber, lambda0, solver="dense", cg_iters=64, cg_tol=1e-6):
-    """Everything bundle_adjust checks before the device is touched -> (keypoint tensors, host records, host K, modes, obs mask, point mask)."""
+def _focal_groups(name, refine_focal, solver, posed, K):
+    """The dense host group ids int32 [n_images] (-1: fixed intrinsics) of ``refine_focal``, or None."""
+    if refine_focal is None:
+        return None
+    if solver != "pcg":
+        raise ValueError(f"{name}: refine_focal needs the matrix-free solver: pass solver='pcg' (the dense reduced system has no focal block)")
+    n_images = len(posed)
+    group = np.full(n_images, -1, np.int32)
+    if isinstance(refine_focal, str):
+        if refine_focal not in ("shared", "per_image"):
+            raise ValueError(f"{name}: refine_focal must be None, 'shared', 'per_image' or {n_images} integers, got {refine_focal!r}")
+        group[posed] = 0 if refine_focal == "shared" else np.arange(int(posed.sum()), dtype=np.int32)
+    else:
+        try:
+            ids = list(refine_focal)
+        except TypeError:
+            raise ValueError(f"{name}: refine_focal must be None, 'shared', 'per_image' or {n_images} integers, got {refine_focal!r}") from None
+        if len(ids) != n_images:
+            raise ValueError(f"{name}: refine_focal holds {len(ids)} group ids for {n_images} images")
+        for k, g in enumerate(ids):
+            if isinstance(g, bool) or not isinstance(g, (int, np.integer)):
+                raise ValueError(f"{name}: refine_focal[{k}] = {g!r}: a group id must be an integer (-1: the intrinsics stay fixed)")
+            if g < -1:
+                raise ValueError(f"{name}: refine_focal[{k}] = {g}: a group id must be >= -1 (-1: the intrinsics stay fixed)")
+        dense = {}
+        for k, g in enumerate(ids):                                # dense ids in the order of first appearance among the posed images
+            if posed[k] and g >= 0:
+                group[k] = dense.setdefault(int(g), len(dense))
+    for g in range(int(group.max()) + 1 if n_images else 0):
+        mine = np.flatnonzero(group == g)
+        ratio = K[mine, 0, 0] / K[mine, 1, 1]
+        if (np.abs(ratio - ratio[0]) > 1e-12 * np.abs(ratio[0])).any():
+            raise ValueError(f"{name}: the images {mine.tolist()} of one focal group have different fx / fy ratios: one scale cannot serve them "
+                             "(give them groups of their own)")
+    return group
+
+
+def _check(points, tracks, images, cameras, fixed, use_obs, use_points, iters, huber, lambda0, solver="dense", cg_iters=64, cg_tol=1e-6, refine_focal=None):
+    """Everything bundle_adjust checks before the device is touched -> (keypoint tensors, host records, host K, modes, obs mask, point mask,
+    focal groups or None)."""
     name = "bundle_adjust"
     if solver not in ("dense", "pcg"):
         raise ValueError(f"{name}: solver must be 'dense' or 'pcg', got {solver!r}")
@@ -139,6 +191,7 @@ def _check(points, tracks, images, cameras, fixed, use_obs, use_points, iters, h
             raise ValueError(f"{name}: fixed holds {k}: that image has no pose (its R or t is not finite)")
     mode = np.where(posed, hip.BA_FREE, hip.BA_ABSENT).astype(np.int32)
     mode[fixed] = hip.BA_FIXED
+    group = _focal_groups(name, refine_focal, solver, posed, K)
     n_free = int((mode == hip.BA_FREE).sum())
     if solver == "dense" and n_free > hip.BA_MAX_FREE_CAMERAS:
         raise ValueError(f"{name}: {n_free} free cameras, at most {hip.BA_MAX_FREE_CAMERAS} (fix more of them, adjust a part of the set, or use solver='pcg')")
@@ -166,11 +219,11 @@ def _check(points, tracks, images, cameras, fixed, use_obs, use_points, iters, h
     if device.type != "cuda":
         raise ValueError(f"{name}: the tracks are on {device}: cameras and points are adjusted on the GPU, from device tensors")
     counts = [start[k + 1] - start[k] for k in range(n_images)]
-    return kpts, hip.triangulate_cameras(K, R, t, counts), K, mode, obs, pts
+    return kpts, hip.triangulate_cameras(K, R, t, counts), K, mode, obs, pts, group
 
 
 def bundle_adjust(points, tracks, images, cameras, *, fixed=None, use_obs=None, use_points=None, iters: int = 20, huber: float = 0.0,
-                  lambda0: float = 1e-4, solver: str = "dense", cg_iters: int = 64, cg_tol: float = 1e-6) -> Adjusted:
+                  lambda0: float = 1e-4, solver: str = "dense", cg_iters: int = 64, cg_tol: float = 1e-6, refine_focal=None) -> Adjusted:
     """Refine the posed cameras and the points jointly, on the device.
 
     ``points``: the ``Points3D`` of ``triangulate_tracks`` (the starting points); ``tracks``: the ``Tracks`` they belong to; ``images``: the
@@ -188,12 +241,20 @@ def bundle_adjust(points, tracks, images, cameras, *, fixed=None, use_obs=None, 
     round, stopped early once the preconditioned residual has fallen to ``cg_tol`` (0 <= cg_tol < 1) of its start.  The two arguments are
     checked and then ignored by ``'dense'``.
 
+    ``refine_focal`` (``solver='pcg'`` only): ``None`` keeps every K as given; ``'shared'`` refines one relative scale of
+    the focal lengths of all posed images; ``'per_image'`` one per posed image; a sequence of ``n_images`` integers gives every image its
+    focal group (-1: its intrinsics stay fixed).  ``Adjusted.focal_scale`` has the refined / starting focal of every group, ``Adjusted.K``
+    and ``Adjusted.cameras()`` the refined intrinsics.  A group with fewer than four active observations is held.
+
     ValueError, before the device is touched: a count that disagrees with ``tracks.image_start``, cameras of another shape or count, a K
     of a posed camera with skew, another last row or a focal length that is not positive, an index of ``fixed`` out of range or without a
-    pose, more than 128 free cameras (65536 with ``solver='pcg'``), tensors of a wrong dtype, shape or device, a parameter out of range.
+    pose, more than 128 free cameras (65536 with ``solver='pcg'``), tensors of a wrong dtype, shape or device, a parameter out of range,
+    ``refine_focal`` with ``solver='dense'``, of a wrong length, with an id that is no integer or is below -1, or with a group whose
+    images differ in fx / fy.
 
     Host synchronisation: NONE.  ``Adjusted.stats`` and ``Adjusted.cameras()`` read back."""
-    kpts, rec, K, mode, obs, pts = _check(points, tracks, images, cameras, fixed, use_obs, use_points, iters, huber, lambda0, solver, cg_iters, cg_tol)
+    kpts, rec, K, mode, obs, pts, group = _check(points, tracks, images, cameras, fixed, use_obs, use_points, iters, huber, lambda0, solver, cg_iters, cg_tol,
+                                                 refine_focal)
     device = tracks.indptr.device
     with torch.cuda.device(device):
         allk = torch.cat([k.reshape(-1, 2).float() for k in kpts]).contiguous() if kpts else torch.zeros((0, 2), device=device)
@@ -204,5 +265,5 @@ def bundle_adjust(points, tracks, images, cameras, *, fixed=None, use_obs=None, 
                                         _nonempty(tracks.obs_keypoint.contiguous(), (1,), torch.int32), _nonempty(obs.contiguous().view(torch.uint8), (1,), torch.uint8),
                                         _nonempty(pts.contiguous().view(torch.uint8), (1,), torch.uint8), _nonempty(allk, (1, 2), torch.float32),
                                         _nonempty(points.xyz.contiguous(), (1, 3), torch.float64), dev_cams, mode, iters=int(iters), huber=float(huber),
-                                        lambda0=float(lambda0), T=T, n_obs=n_obs, n=n, solver=solver, cg_iters=int(cg_iters), cg_tol=float(cg_tol))
-    return Adjusted(views, mode, K, keep)
+                                        lambda0=float(lambda0), T=T, n_obs=n_obs, n=n, solver=solver, cg_iters=int(cg_iters), cg_tol=float(cg_tol), group=group)
+    return Adjusted(views, mode, K, keep, group)

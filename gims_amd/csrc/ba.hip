@@ -16,6 +16,8 @@
 // ascending sum, a butterfly, then the waves in order.  No order depends on the grid.
 // GIMS_AUX_BUNDLE_ADJUST_PCG, further down, shares init, classify, point, back, decide and finish and replaces camera and
 // solve by a matrix-free conjugate-gradient iteration, so that the number of free cameras is not bound by a dense reduced system.
+// GIMS_AUX_BUNDLE_ADJUST_FOCAL, behind that, is the conjugate-gradient form with one more unknown per focal group: it launches
+// the kernels of the two forms above as they are and adds kernels of its own for the group terms.
 #include "common.h"
 
 #include <cfloat>
@@ -1126,8 +1128,599 @@ static int ba_pcg_launches(const BaArgs& a, unsigned g_all, unsigned g_T, hipStr
   return GIMS_OK;
 }
 
-// GIMS_AUX_BUNDLE_ADJUST and GIMS_AUX_BUNDLE_ADJUST_PCG of gims_run_ops (include/gims_hip.h): every argument check precedes the first HIP call
-static int ba_aux(const gims_aux_args& x, hipStream_t st, const bool pcg) {
+// ================================================================================================ the focal form
+// GIMS_AUX_BUNDLE_ADJUST_FOCAL: the conjugate-gradient form with one more unknown per focal group, the relative scale ds of
+// the focal lengths of the group's images.  The reduced system has the unknowns [6 words per slot | 1 word per group].  Every posed image
+// that is a slot or lies in a group has an ascending list of its active observations ("listed images": the slots first, in slot order, so
+// that setup reads a slot's list where it always did; then the others in image order).  Per round: point (as above) -> focal_point (a
+// thread per track: Fu, Fv, G, G V*^-1 of the observations of moving groups) -> pcg_setup (as above) -> focal_image (a wave per listed
+// image: the image's share of A, g_g, sum G V*^-1 G^T, sum G V*^-1 g_p, and C_s) -> focal_group (a workgroup per group: A*, b_g, M_g) ->
+// focal_init -> cg_iters times { focal_y -> focal_sp (a wave per listed image: q_s and the image's share of q_g) -> focal_gq (a workgroup
+// per group: q_g) -> focal_step } -> pcg_cand (as above) -> focal_cand (the candidate focal lengths and scales) -> focal_back -> decide.
+// The order of every sum: per image, lane l takes the entries l, l + 64, ... of the image's list, then the butterfly; per group, thread j
+// of 256 takes the group's images j, j + 256, ... in ascending image index, a butterfly per wave, then the four waves in order; a dot
+// product is the slot sum of 4.21, then the group sum by the same scheme over the groups, and the two are added in that order.
+constexpr int BA_FREC = 8;                                     // per observation of a moving group: Fu, Fv | G [3] | G V*^-1 [3]
+constexpr int BA_IPART = 4;                                    // per image: its share of A, g_g, sum G V*^-1 G^T, sum G V*^-1 g_p
+
+struct BaFocal {                                               // what the focal form has next to BaArgs
+  int n_groups, n_lists;
+  int32_t *group_of, *list_of, *gimg_ptr, *gimg_list, *gheld, *group_obs;
+  double *scale, *scale1;                                      // the product of the taken (1 + ds): the two buffers of the state (scale is the output)
+  double *obs_frec, *img_part, *img_q, *cvec, *grec, *gx, *gr, *gz, *gp, *gq;
+};
+
+static size_t ba_focal_layout(void* base, int64_t T, int64_t n_obs, int64_t n_images, int64_t iters, int64_t n_free, int64_t n_groups, BaOut& w, BaFocal& f) {
+  WsLayout L(base);
+  w.xyz = L.take<double>((size_t)T * 3);
+  w.cams = L.take<double>((size_t)n_images * BA_CAM);
+  w.obs_error = L.take<float>((size_t)n_obs);
+  w.cam_obs = L.take<int32_t>((size_t)n_images);
+  w.history = L.take<double>((size_t)(iters + 1) * 2);
+  w.taken = L.take<uint8_t>((size_t)iters);
+  w.counters = L.take<int32_t>(BA_COUNTERS);
+  w.cg_used = L.take<int32_t>((size_t)iters);
+  w.cg_res = L.take<double>((size_t)iters);
+  f.scale = L.take<double>((size_t)n_groups);
+  f.group_obs = L.take<int32_t>((size_t)n_groups);
+  w.st = (BaState*)L.take<double>(32);                         // scratch from here on
+  w.slot_of = L.take<int32_t>((size_t)n_images);
+  w.slot_cam = L.take<int32_t>((size_t)n_images);              // the image of every list: the slots, then the other listed images
+  w.slot_ptr = L.take<int32_t>((size_t)n_images + 1);
+  w.held = L.take<int32_t>((size_t)n_free);
+  w.cursor = L.take<int32_t>((size_t)n_images);
+  w.xyz1 = L.take<double>((size_t)T * 3);
+  w.cams1 = L.take<double>((size_t)n_images * BA_CAM);
+  w.pt_act = L.take<uint8_t>((size_t)T);
+  w.obs_act = L.take<uint8_t>((size_t)n_obs);
+  w.obs_track = L.take<int32_t>((size_t)n_obs);
+  w.obs_node = L.take<int32_t>((size_t)n_obs);
+  w.cam_list = L.take<int32_t>((size_t)n_obs);
+  w.list_tmp = L.take<int32_t>((size_t)n_obs);
+  w.pt_rec = L.take<double>((size_t)T * BA_PT);
+  w.obs_rec = L.take<double>((size_t)n_obs * BA_REC);
+  w.trackcost = L.take<double>((size_t)T);
+  w.y = L.take<double>((size_t)T * 3);
+  w.slot_rec = L.take<double>((size_t)n_free * BA_SLOT_REC);
+  w.rhs = L.take<double>((size_t)n_free * 6);
+  w.vr = L.take<double>((size_t)n_free * 6);
+  w.vz = L.take<double>((size_t)n_free * 6);
+  w.vp = L.take<double>((size_t)n_free * 6);
+  w.vq = L.take<double>((size_t)n_free * 6);
+  f.cvec = L.take<double>((size_t)n_free * 6);
+  f.group_of = L.take<int32_t>((size_t)n_images);
+  f.list_of = L.take<int32_t>((size_t)n_images);
+  f.gimg_list = L.take<int32_t>((size_t)n_images);
+  f.img_part = L.take<double>((size_t)n_images * BA_IPART);
+  f.img_q = L.take<double>((size_t)n_images * 2);
+  f.obs_frec = L.take<double>((size_t)n_obs * BA_FREC);
+  f.gimg_ptr = L.take<int32_t>((size_t)n_groups + 1);
+  f.gheld = L.take<int32_t>((size_t)n_groups);
+  f.scale1 = L.take<double>((size_t)n_groups);
+  f.grec = L.take<double>((size_t)n_groups * 2);
+  f.gx = L.take<double>((size_t)n_groups);
+  f.gr = L.take<double>((size_t)n_groups);
+  f.gz = L.take<double>((size_t)n_groups);
+  f.gp = L.take<double>((size_t)n_groups);
+  f.gq = L.take<double>((size_t)n_groups);
+  w.obs_mslot = w.obs_dup = nullptr, w.S = nullptr;            // (the dense form's)
+  return L.bytes();
+}
+
+// the group of an image when that group moves, else -1; k is in range
+__device__ __forceinline__ int ba_moving_group(const BaFocal& f, int k) {
+  const int g = f.group_of[k];
+  return g >= 0 && g < f.n_groups && f.gheld[g] == 0 ? g : -1;
+}
+
+// ---------------------------------------------------------------------------------------------- groups, lists
+// a thread per group: the active observations of its images (integers: any order), held or not, the scale 1 in both buffers
+__global__ __launch_bounds__(BA_THREADS) void ba_focal_groups_kernel(BaArgs a, BaFocal f) {
+  const int g = blockIdx.x * BA_THREADS + threadIdx.x;
+  if (g >= f.n_groups) return;
+  int beg = f.gimg_ptr[g], end = f.gimg_ptr[g + 1], n = 0;
+  if (beg < 0 || end < beg || end > a.n_images) end = beg = 0;  // (never: the host built the table)
+  for (int j = beg; j < end; ++j) {
+    const int k = f.gimg_list[j];
+    n += k >= 0 && k < a.n_images ? a.out.cam_obs[k] : 0;
+  }
+  f.group_obs[g] = n, f.gheld[g] = n < 4 ? 1 : 0;
+  f.scale[g] = 1.0, f.scale1[g] = 1.0;
+}
+
+// one workgroup: which slots are held, and the exclusive scan of the list sizes of ALL the listed images (a held camera's observations
+// still count for its group)
+__global__ __launch_bounds__(BA_THREADS) void ba_focal_lists_kernel(BaArgs a, BaFocal f) {
+  __shared__ int s_sum[BA_THREADS], s_held[BA_THREADS];
+  const int t = threadIdx.x, L = f.n_lists, per = (L + BA_THREADS - 1) / BA_THREADS;
+  const int lo = t * per < L ? t * per : L, hi = lo + per < L ? lo + per : L;
+  int sum = 0, held = 0;
+  for (int li = lo; li < hi; ++li) {
+    const int c = a.out.cam_obs[a.out.slot_cam[li]];
+    a.out.cursor[li] = 0;
+    if (li < a.n_free) a.out.held[li] = c < 4 ? 1 : 0, held += c < 4 ? 1 : 0;
+    sum += c;
+  }
+  s_sum[t] = sum, s_held[t] = held;
+  __syncthreads();
+  if (t == 0) {
+    int at = 0, h = 0;
+    for (int j = 0; j < BA_THREADS; ++j) {
+      const int v = s_sum[j];
+      s_sum[j] = at, at += v, h += s_held[j];
+    }
+    a.out.slot_ptr[L] = at;                                    // <= n_obs: every active observation has one camera
+    a.out.st->n_held = h;
+  }
+  __syncthreads();
+  int at = s_sum[t];
+  for (int li = lo; li < hi; ++li) {
+    a.out.slot_ptr[li] = at;
+    at += a.out.cam_obs[a.out.slot_cam[li]];
+  }
+}
+
+__global__ __launch_bounds__(BA_THREADS) void ba_focal_fill_kernel(BaArgs a, BaFocal f) {
+  const int o = blockIdx.x * BA_THREADS + threadIdx.x;
+  if (o >= a.n_obs || a.out.obs_act[o] == 0) return;
+  const int li = f.list_of[a.obs_image[o]];                    // (in range: the observation is active)
+  if (li < 0 || li >= f.n_lists) return;
+  const int first = a.out.slot_ptr[li], cap = a.out.slot_ptr[li + 1] - first;
+  const int at = atomicAdd(a.out.cursor + li, 1);              // integers: the order of the race is undone by the sort
+  if (at >= 0 && at < cap && first >= 0 && first + at < a.n_obs) a.out.list_tmp[first + at] = o;
+}
+
+// ---------------------------------------------------------------------------------------------- the focal words of a round
+// A thread per track, behind ba_point_kernel (which left V*^-1 in pt_rec): Fu = fx x / z, Fv = fy y / z with the Huber factor, G = Fu Pu +
+// Fv Pv and G V*^-1, for every active observation whose image lies in a moving group.
+__global__ __launch_bounds__(BA_THREADS) void ba_focal_point_kernel(BaArgs a, BaFocal f) {
+  const int t = blockIdx.x * BA_THREADS + threadIdx.x;
+  const BaState* st = a.out.st;
+  if (t >= a.T || st->stop || a.out.pt_act[t] == 0) return;
+  int beg, len;
+  if (!ba_range(a, t, beg, len)) return;                       // (never: the point is active)
+  const double* cams = ba_cams(a, st->cur);
+  const double* Xp = ba_xyz(a, st->cur) + (int64_t)3 * t;
+  const double X[3] = {Xp[0], Xp[1], Xp[2]};
+  const double* pr = a.out.pt_rec + (int64_t)BA_PT * t;
+  const double I[3][3] = {{pr[0], pr[1], pr[2]}, {pr[1], pr[3], pr[4]}, {pr[2], pr[4], pr[5]}};
+  for (int o = beg; o < beg + len; ++o) {
+    if (a.out.obs_act[o] == 0) continue;
+    const int k = a.obs_image[o];
+    if (ba_moving_group(f, k) < 0) continue;
+    const int64_t node = a.out.obs_node[o];
+    const double* c = cams + (int64_t)BA_CAM * k;
+    BaJac J;
+    double ru, rv, z;
+    ba_observe<true>(c, X, (double)a.kpts[2 * node], (double)a.kpts[2 * node + 1], ru, rv, z, &J);
+    const double* R = c + 4;
+    const double x = (R[0] * X[0] + R[1] * X[1] + R[2] * X[2]) + c[13], y = (R[3] * X[0] + R[4] * X[1] + R[5] * X[2]) + c[14];
+    double Fu = c[0] * x / z, Fv = c[1] * y / z;
+    if (a.huber > 0.0) {
+      const double e = sqrt(ru * ru + rv * rv);
+      if (e > a.huber) {
+        const double sw = sqrt(a.huber / e);
+        Fu = Fu * sw, Fv = Fv * sw;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) J.pu[j] = J.pu[j] * sw, J.pv[j] = J.pv[j] * sw;
+      }
+    }
+    double* fr = f.obs_frec + (int64_t)BA_FREC * o;
+    const double G[3] = {Fu * J.pu[0] + Fv * J.pv[0], Fu * J.pu[1] + Fv * J.pv[1], Fu * J.pu[2] + Fv * J.pv[2]};
+    fr[0] = Fu, fr[1] = Fv;
+#pragma unroll
+    for (int m = 0; m < 3; ++m) fr[2 + m] = G[m], fr[5 + m] = (G[0] * I[0][m] + G[1] * I[1][m]) + G[2] * I[2][m];
+  }
+}
+
+// A wave per listed image whose group moves: the image's share of A = sum Fu^2 + Fv^2, g_g = sum Fu ru + Fv rv, sum G V*^-1 G^T and
+// sum G V*^-1 g_p, and, when the image is a slot that moves, C_s[c] = sum Ju[c] Fu + Jv[c] Fv: the lane's own ascending sum, a butterfly.
+__global__ __launch_bounds__(64) void ba_focal_image_kernel(BaArgs a, BaFocal f) {
+  const int li = blockIdx.x, lane = threadIdx.x;
+  const BaState* st = a.out.st;
+  if (li >= f.n_lists || st->stop) return;
+  const int k = a.out.slot_cam[li];
+  if (k < 0 || k >= a.n_images || ba_moving_group(f, k) < 0) return;
+  const bool slot = li < a.n_free && a.out.held[li] == 0;
+  const int first = a.out.slot_ptr[li];
+  int cnt = a.out.slot_ptr[li + 1] - first;
+  if (first < 0 || cnt < 0 || first + cnt > a.n_obs) cnt = 0;   // (never)
+  const int32_t* list = a.out.cam_list + first;
+  double acc[10];
+#pragma unroll
+  for (int j = 0; j < 10; ++j) acc[j] = 0.0;
+  for (int idx = lane; idx < cnt; idx += 64) {
+    const int o = list[idx];
+    if (o < 0 || o >= a.n_obs) continue;                       // (never)
+    const int p = a.out.obs_track[o];
+    if (p < 0 || p >= a.T) continue;                           // (never)
+    const double *rec = a.out.obs_rec + (int64_t)BA_REC * o, *fr = f.obs_frec + (int64_t)BA_FREC * o, *gp = a.out.pt_rec + (int64_t)BA_PT * p + 6;
+    const double Fu = fr[0], Fv = fr[1];
+    acc[0] += Fu * Fu + Fv * Fv;
+    acc[1] += Fu * rec[12] + Fv * rec[13];
+    acc[2] += (fr[5] * fr[2] + fr[6] * fr[3]) + fr[7] * fr[4];
+    acc[3] += (fr[5] * gp[0] + fr[6] * gp[1]) + fr[7] * gp[2];
+    if (slot) {
+#pragma unroll
+      for (int c = 0; c < 6; ++c) acc[4 + c] += rec[c] * Fu + rec[6 + c] * Fv;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 10; ++j) acc[j] = ba_wave_sum(acc[j]);
+  if (lane != 0) return;
+#pragma unroll
+  for (int j = 0; j < BA_IPART; ++j) f.img_part[(int64_t)BA_IPART * k + j] = acc[j];
+  if (slot) {
+#pragma unroll
+    for (int c = 0; c < 6; ++c) f.cvec[6 * li + c] = acc[4 + c];
+  }
+}
+
+// the sum of v[k] over the images k of group g, by the scheme of the cost sum: thread j takes the images j, j + BA_THREADS, ...
+__device__ __forceinline__ double ba_group_sum(const BaFocal& f, int g, const double* v, int stride, int n_images, double* s_part) {
+  int beg = f.gimg_ptr[g], end = f.gimg_ptr[g + 1];
+  if (beg < 0 || end < beg || end > n_images) end = beg = 0;    // (never)
+  double part = 0.0;
+  for (int j = beg + (int)threadIdx.x; j < end; j += BA_THREADS) {
+    const int k = f.gimg_list[j];
+    if (k >= 0 && k < n_images) part += v[(int64_t)stride * k];
+  }
+  return ba_block_sum(part, s_part);
+}
+
+// A workgroup per group: A* = A + lambda max(A, 1e-6), b_g = -g_g + sum G V*^-1 g_p into r, M_g = A* - sum G V*^-1 G^T
+__global__ __launch_bounds__(BA_THREADS) void ba_focal_group_kernel(BaArgs a, BaFocal f) {
+  __shared__ double s_part[BA_THREADS / 64];
+  const int g = blockIdx.x;
+  BaState* st = a.out.st;
+  if (st->stop) return;
+  if (f.gheld[g]) {                                            // a held group does not move: an identity entry, a zero right-hand side
+    if (threadIdx.x == 0) f.grec[2 * g] = 1.0, f.grec[2 * g + 1] = 1.0, f.gr[g] = 0.0;
+    return;
+  }
+  const double A = ba_group_sum(f, g, f.img_part, BA_IPART, a.n_images, s_part), gg = ba_group_sum(f, g, f.img_part + 1, BA_IPART, a.n_images, s_part);
+  const double E = ba_group_sum(f, g, f.img_part + 2, BA_IPART, a.n_images, s_part), B = ba_group_sum(f, g, f.img_part + 3, BA_IPART, a.n_images, s_part);
+  if (threadIdx.x != 0) return;
+  const double As = A + st->lambda * fmax(A, 1e-6), M = As - E;
+  f.grec[2 * g] = As, f.grec[2 * g + 1] = M, f.gr[g] = -gg + B;
+  if (!(ba_finite(M) && M > 0.0)) atomicOr(&st->flags, BA_F_IRREGULAR);
+}
+
+// ---------------------------------------------------------------------------------------------- the iteration
+__global__ __launch_bounds__(BA_THREADS) void ba_focal_init_kernel(BaArgs a, BaFocal f) {
+  __shared__ double s_part[BA_THREADS / 64];
+  const int t = threadIdx.x;
+  BaState* st = a.out.st;
+  if (st->stop) return;
+  const bool irregular = (st->flags & BA_F_IRREGULAR) != 0;
+  double part = 0.0;
+  for (int s = t; s < a.n_free; s += BA_THREADS) {
+    double z[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) a.out.rhs[6 * s + j] = 0.0;
+    if (irregular) continue;
+    ba_msolve(a.out.slot_rec + (int64_t)BA_SLOT_REC * s + 21, a.out.vr + 6 * s, z);
+#pragma unroll
+    for (int j = 0; j < 6; ++j) a.out.vz[6 * s + j] = z[j], a.out.vp[6 * s + j] = z[j];
+    part += ba_dot6(a.out.vr + 6 * s, z);
+  }
+  const double rho_s = ba_block_sum(part, s_part);
+  part = 0.0;
+  for (int g = t; g < f.n_groups; g += BA_THREADS) {
+    f.gx[g] = 0.0;
+    if (irregular) continue;
+    const double z = f.gr[g] / f.grec[2 * g + 1];
+    f.gz[g] = z, f.gp[g] = z;
+    part += f.gr[g] * z;
+  }
+  const double rho = rho_s + ba_block_sum(part, s_part);
+  if (t != 0) return;
+  const bool good = !irregular && ba_finite(rho) && rho >= 0.0;
+  if (!irregular && !good) atomicOr(&st->flags, BA_F_IRREGULAR);
+  st->rho = good ? rho : 0.0, st->rho0 = good ? rho : 0.0;
+  st->cg_used = 0, st->cg_done = !good || rho == 0.0 ? 1 : 0;
+}
+
+// y = V*^-1 sum (W_o^T p_slot(o) + G_o^T p_group(o)): a thread per track, its observations ascending, the camera term before the group term
+__global__ __launch_bounds__(BA_THREADS) void ba_focal_y_kernel(BaArgs a, BaFocal f) {
+  const int t = blockIdx.x * BA_THREADS + threadIdx.x;
+  const BaState* st = a.out.st;
+  if (t >= a.T || st->stop || st->cg_done || a.out.pt_act[t] == 0) return;
+  int beg, len;
+  if (!ba_range(a, t, beg, len)) return;                       // (never: the point is active)
+  double s[3] = {0.0, 0.0, 0.0};
+  for (int o = beg; o < beg + len; ++o) {
+    if (a.out.obs_act[o] == 0) continue;
+    const int k = ba_moving_slot(a, a.obs_image[o]), g = ba_moving_group(f, a.obs_image[o]);
+    if (k >= 0) {
+      const double *w = a.out.obs_rec + (int64_t)BA_REC * o + 14, *pc = a.out.vp + 6 * k;
+      for (int c = 0; c < 6; ++c)
+#pragma unroll
+        for (int m = 0; m < 3; ++m) s[m] += w[3 * c + m] * pc[c];
+    }
+    if (g >= 0) {
+      const double *G = f.obs_frec + (int64_t)BA_FREC * o + 2, pg = f.gp[g];
+#pragma unroll
+      for (int m = 0; m < 3; ++m) s[m] += G[m] * pg;
+    }
+  }
+  const double* pr = a.out.pt_rec + (int64_t)BA_PT * t;
+  const double I[3][3] = {{pr[0], pr[1], pr[2]}, {pr[1], pr[3], pr[4]}, {pr[2], pr[4], pr[5]}};
+#pragma unroll
+  for (int m = 0; m < 3; ++m) a.out.y[(int64_t)3 * t + m] = (I[m][0] * s[0] + I[m][1] * s[1]) + I[m][2] * s[2];
+}
+
+// A wave per listed image.  A slot: q_s = (U*_s p_s + C_s p_g) - sum W_o y (without the C_s term when its group does not move).  An
+// image of a moving group: its share of q_g, C_s^T p_s (0 when it is no moving slot) and sum G_o y.
+__global__ __launch_bounds__(64) void ba_focal_sp_kernel(BaArgs a, BaFocal f) {
+  const int li = blockIdx.x, lane = threadIdx.x;
+  const BaState* st = a.out.st;
+  if (li >= f.n_lists || st->stop || st->cg_done) return;
+  const int k = a.out.slot_cam[li];
+  if (k < 0 || k >= a.n_images) return;                        // (never)
+  const int g = ba_moving_group(f, k);
+  const bool is_slot = li < a.n_free, moving = is_slot && a.out.held[li] == 0;
+  if (!is_slot && g < 0) return;
+  const int first = a.out.slot_ptr[li];
+  int cnt = a.out.slot_ptr[li + 1] - first;
+  if (first < 0 || cnt < 0 || first + cnt > a.n_obs) cnt = 0;   // (never)
+  if (!moving && g < 0) cnt = 0;                               // a held slot outside a moving group: q = p
+  const int32_t* list = a.out.cam_list + first;
+  double acc[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int idx = lane; idx < cnt; idx += 64) {
+    const int o = list[idx];
+    if (o < 0 || o >= a.n_obs) continue;                       // (never)
+    const int p = a.out.obs_track[o];
+    if (p < 0 || p >= a.T) continue;                           // (never)
+    const double* y = a.out.y + (int64_t)3 * p;
+    const double y0 = y[0], y1 = y[1], y2 = y[2];
+    if (moving) {
+      const double* w = a.out.obs_rec + (int64_t)BA_REC * o + 14;
+#pragma unroll
+      for (int r = 0; r < 6; ++r) acc[r] += (w[3 * r] * y0 + w[3 * r + 1] * y1) + w[3 * r + 2] * y2;
+    }
+    if (g >= 0) {
+      const double* G = f.obs_frec + (int64_t)BA_FREC * o + 2;
+      acc[6] += (G[0] * y0 + G[1] * y1) + G[2] * y2;
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 7; ++r) acc[r] = ba_wave_sum(acc[r]);
+  if (lane == 0 && g >= 0) {
+    f.img_q[2 * (int64_t)k] = moving ? ba_dot6(f.cvec + 6 * li, a.out.vp + 6 * li) : 0.0;
+    f.img_q[2 * (int64_t)k + 1] = acc[6];
+  }
+  if (lane >= 6 || !is_slot) return;
+  const double *U = a.out.slot_rec + (int64_t)BA_SLOT_REC * li, *pc = a.out.vp + 6 * li;
+  double up = 0.0, wy = 0.0;
+#pragma unroll
+  for (int r = 0; r < 6; ++r)
+    if (r == lane) wy = acc[r];
+  for (int c = 0; c < 6; ++c) {
+    const int i = lane < c ? lane : c, j = lane < c ? c : lane;
+    const double term = U[i * 6 - i * (i - 1) / 2 + (j - i)] * pc[c];
+    up = c == 0 ? term : up + term;
+  }
+  if (moving && g >= 0) up = up + f.cvec[6 * li + lane] * f.gp[g];
+  a.out.vq[6 * li + lane] = up - wy;
+}
+
+// A workgroup per group: q_g = (A*_g p_g + sum C_s^T p_s) - sum G_o y, the two sums over the group's images
+__global__ __launch_bounds__(BA_THREADS) void ba_focal_gq_kernel(BaArgs a, BaFocal f) {
+  __shared__ double s_part[BA_THREADS / 64];
+  const int g = blockIdx.x;
+  const BaState* st = a.out.st;
+  if (st->stop || st->cg_done) return;
+  if (f.gheld[g]) {
+    if (threadIdx.x == 0) f.gq[g] = f.gp[g];
+    return;
+  }
+  const double cs = ba_group_sum(f, g, f.img_q, 2, a.n_images, s_part), gy = ba_group_sum(f, g, f.img_q + 1, 2, a.n_images, s_part);
+  if (threadIdx.x == 0) f.gq[g] = (f.grec[2 * g] * f.gp[g] + cs) - gy;
+}
+
+__global__ __launch_bounds__(BA_THREADS) void ba_focal_step_kernel(BaArgs a, BaFocal f, int last) {
+  __shared__ double s_part[BA_THREADS / 64];
+  const int t = threadIdx.x;
+  BaState* st = a.out.st;
+  if (st->stop || st->cg_done) return;
+  const double rho = st->rho, rho0 = st->rho0;
+  double part = 0.0;
+  for (int s = t; s < a.n_free; s += BA_THREADS) part += ba_dot6(a.out.vp + 6 * s, a.out.vq + 6 * s);
+  const double pq_s = ba_block_sum(part, s_part);
+  part = 0.0;
+  for (int g = t; g < f.n_groups; g += BA_THREADS) part += f.gp[g] * f.gq[g];
+  const double pq = pq_s + ba_block_sum(part, s_part);
+  if (!(ba_finite(pq) && pq > 0.0)) {                          // the same for every thread
+    if (t == 0) atomicOr(&st->flags, BA_F_IRREGULAR), st->cg_done = 1, st->cg_used += 1;
+    return;
+  }
+  const double alpha = rho / pq;
+  part = 0.0;
+  for (int s = t; s < a.n_free; s += BA_THREADS) {
+    double r[6], z[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      a.out.rhs[6 * s + j] = a.out.rhs[6 * s + j] + alpha * a.out.vp[6 * s + j];
+      r[j] = a.out.vr[6 * s + j] - alpha * a.out.vq[6 * s + j];
+      a.out.vr[6 * s + j] = r[j];
+    }
+    ba_msolve(a.out.slot_rec + (int64_t)BA_SLOT_REC * s + 21, r, z);
+#pragma unroll
+    for (int j = 0; j < 6; ++j) a.out.vz[6 * s + j] = z[j];
+    part += ba_dot6(r, z);
+  }
+  const double rho1_s = ba_block_sum(part, s_part);
+  part = 0.0;
+  for (int g = t; g < f.n_groups; g += BA_THREADS) {
+    f.gx[g] = f.gx[g] + alpha * f.gp[g];
+    const double r = f.gr[g] - alpha * f.gq[g], z = r / f.grec[2 * g + 1];
+    f.gr[g] = r, f.gz[g] = z;
+    part += r * z;
+  }
+  const double rho1 = rho1_s + ba_block_sum(part, s_part);
+  const bool good = ba_finite(rho1) && rho1 >= 0.0;
+  const bool done = !good || rho1 <= a.cg_tol2 * rho0 || last != 0;
+  if (!done) {
+    const double beta = rho1 / rho;
+    for (int s = t; s < a.n_free; s += BA_THREADS)
+#pragma unroll
+      for (int j = 0; j < 6; ++j) a.out.vp[6 * s + j] = a.out.vz[6 * s + j] + beta * a.out.vp[6 * s + j];
+    for (int g = t; g < f.n_groups; g += BA_THREADS) f.gp[g] = f.gz[g] + beta * f.gp[g];
+  }
+  if (t != 0) return;
+  if (!good) atomicOr(&st->flags, BA_F_IRREGULAR);
+  st->rho = rho1, st->cg_used += 1, st->cg_done = done ? 1 : 0;
+}
+
+// Behind ba_pcg_cand_kernel: the candidate fx' = fx (1 + ds), fy' = fy (1 + ds) of every image of a moving group and the candidate scale
+// of the group, into the buffers that are not current.  1 + ds <= 0 or a focal length that is not finite: the round is not taken.
+__global__ __launch_bounds__(BA_THREADS) void ba_focal_cand_kernel(BaArgs a, BaFocal f) {
+  const int i = blockIdx.x * BA_THREADS + threadIdx.x;
+  BaState* st = a.out.st;
+  if (st->stop) return;
+  if ((st->flags & BA_F_IRREGULAR) != 0) {                     // an irregular round has ds = 0 and is not taken
+    if (i < f.n_groups) f.gx[i] = 0.0;
+    return;
+  }
+  if (i < f.n_groups && f.gheld[i] == 0) (st->cur ? f.scale : f.scale1)[i] = (st->cur ? f.scale1 : f.scale)[i] * (1.0 + f.gx[i]);
+  if (i >= a.n_images) return;
+  const int g = ba_moving_group(f, i);
+  if (g < 0) return;
+  const double* cur = ba_cams(a, st->cur) + (int64_t)BA_CAM * i;
+  double* cand = ba_cams(a, st->cur ^ 1) + (int64_t)BA_CAM * i;
+  const double f1 = 1.0 + f.gx[g], fx = cur[0] * f1, fy = cur[1] * f1;
+  cand[0] = fx, cand[1] = fy;
+  if (!(f1 > 0.0 && ba_finite(fx) && ba_finite(fy))) atomicOr(&st->flags, BA_F_NOT_FINITE);
+}
+
+// ba_back_kernel(initial = 0) with the group term: s = g_p + sum (W_o^T d_slot(o) + G_o^T ds_group(o)), the observations ascending
+__global__ __launch_bounds__(BA_THREADS) void ba_focal_back_kernel(BaArgs a, BaFocal f) {
+  const int t = blockIdx.x * BA_THREADS + threadIdx.x;
+  BaState* st = a.out.st;
+  if (t >= a.T || st->stop || a.out.pt_act[t] == 0) return;
+  int beg, len;
+  if (!ba_range(a, t, beg, len)) return;                       // (never: the point is active)
+  const int which = st->cur ^ 1;
+  const double* cams = ba_cams(a, which);
+  const double* pr = a.out.pt_rec + (int64_t)BA_PT * t;
+  double s[3] = {pr[6], pr[7], pr[8]};
+  for (int o = beg; o < beg + len; ++o) {
+    if (a.out.obs_act[o] == 0) continue;
+    const int k = ba_moving_slot(a, a.obs_image[o]), g = ba_moving_group(f, a.obs_image[o]);
+    if (k >= 0) {
+      const double *w = a.out.obs_rec + (int64_t)BA_REC * o + 14, *dc = a.out.rhs + 6 * k;
+      for (int c = 0; c < 6; ++c)
+#pragma unroll
+        for (int m = 0; m < 3; ++m) s[m] += w[3 * c + m] * dc[c];
+    }
+    if (g >= 0) {
+      const double *G = f.obs_frec + (int64_t)BA_FREC * o + 2, dg = f.gx[g];
+#pragma unroll
+      for (int m = 0; m < 3; ++m) s[m] += G[m] * dg;
+    }
+  }
+  const double I[3][3] = {{pr[0], pr[1], pr[2]}, {pr[1], pr[3], pr[4]}, {pr[2], pr[4], pr[5]}};
+  const double* cur = ba_xyz(a, st->cur) + (int64_t)3 * t;
+  double X[3];
+  bool fin = true;
+  for (int m = 0; m < 3; ++m) {
+    X[m] = cur[m] + -(I[m][0] * s[0] + I[m][1] * s[1] + I[m][2] * s[2]);
+    ba_xyz(a, which)[(int64_t)3 * t + m] = X[m];
+    fin = fin && ba_finite(X[m]);
+  }
+  if (!fin) atomicOr(&st->flags, BA_F_NOT_FINITE);
+  double cost = 0.0;
+  bool front = true;
+  for (int o = beg; o < beg + len; ++o) {
+    if (a.out.obs_act[o] == 0) continue;
+    const int64_t node = a.out.obs_node[o];
+    double ru, rv, z;
+    ba_observe<false>(cams + (int64_t)BA_CAM * a.obs_image[o], X, (double)a.kpts[2 * node], (double)a.kpts[2 * node + 1], ru, rv, z, nullptr);
+    front = front && z > 0.0;
+    cost += ba_rho(ru * ru + rv * rv, a.huber);
+  }
+  a.out.trackcost[t] = cost;
+  if (!front) atomicOr(&st->flags, BA_F_BEHIND);
+}
+
+// Behind ba_finish_kernel: the refined fx, fy of the images of moving groups and the scales, when the current buffer is the second
+__global__ __launch_bounds__(BA_THREADS) void ba_focal_finish_kernel(BaArgs a, BaFocal f) {
+  const int i = blockIdx.x * BA_THREADS + threadIdx.x;
+  if (a.out.st->cur != 1) return;
+  if (i < f.n_groups) f.scale[i] = f.scale1[i];
+  if (i < a.n_images && ba_moving_group(f, i) >= 0) a.out.cams[(int64_t)i * BA_CAM] = a.out.cams1[(int64_t)i * BA_CAM], a.out.cams[(int64_t)i * BA_CAM + 1] = a.out.cams1[(int64_t)i * BA_CAM + 1];
+}
+
+// the launches of the focal form behind init and classify, for n_groups > 0: 6 + iters (10 + 4 cg_iters) + 2 when there are slots
+static int ba_focal_launches(const BaArgs& a, const BaFocal& f, unsigned g_all, unsigned g_T, hipStream_t st) {
+  const unsigned g_obs = (unsigned)(a.n_obs > 0 ? cdiv((int64_t)a.n_obs, BA_THREADS) : 1), g_slots = (unsigned)cdiv((int64_t)(a.n_free > 0 ? a.n_free : 1), BA_THREADS);
+  const unsigned g_groups = (unsigned)cdiv((int64_t)f.n_groups, BA_THREADS), L = (unsigned)f.n_lists;
+  const int64_t most = a.n_images > f.n_groups ? a.n_images : f.n_groups;
+  const unsigned g_ig = (unsigned)cdiv(most, BA_THREADS);
+  ba_focal_groups_kernel<<<g_groups, BA_THREADS, 0, st>>>(a, f);
+  GIMS_LAUNCH_CHECK();
+  if (L > 0) {
+    ba_focal_lists_kernel<<<1, BA_THREADS, 0, st>>>(a, f);
+    GIMS_LAUNCH_CHECK();
+    ba_focal_fill_kernel<<<g_obs, BA_THREADS, 0, st>>>(a, f);
+    GIMS_LAUNCH_CHECK();
+    ba_pcg_sort_kernel<<<dim3(L, BA_SORT_SPLIT), BA_THREADS, 0, st>>>(a);      // (a list per listed image: slot_ptr has n_lists + 1 entries)
+    GIMS_LAUNCH_CHECK();
+  }
+  ba_back_kernel<<<g_T, BA_THREADS, 0, st>>>(a, 1);
+  GIMS_LAUNCH_CHECK();
+  ba_decide_kernel<<<1, BA_THREADS, 0, st>>>(a, -1);
+  GIMS_LAUNCH_CHECK();
+  for (int r = 0; r < a.iters; ++r) {
+    ba_point_kernel<<<g_T, BA_THREADS, 0, st>>>(a);
+    GIMS_LAUNCH_CHECK();
+    ba_focal_point_kernel<<<g_T, BA_THREADS, 0, st>>>(a, f);
+    GIMS_LAUNCH_CHECK();
+    if (a.n_free > 0) {
+      ba_pcg_setup_kernel<<<(unsigned)a.n_free, 64, 0, st>>>(a);
+      GIMS_LAUNCH_CHECK();
+    }
+    if (L > 0) {
+      ba_focal_image_kernel<<<L, 64, 0, st>>>(a, f);
+      GIMS_LAUNCH_CHECK();
+    }
+    ba_focal_group_kernel<<<(unsigned)f.n_groups, BA_THREADS, 0, st>>>(a, f);
+    GIMS_LAUNCH_CHECK();
+    ba_focal_init_kernel<<<1, BA_THREADS, 0, st>>>(a, f);
+    GIMS_LAUNCH_CHECK();
+    for (int it = 0; it < a.cg_iters; ++it) {
+      ba_focal_y_kernel<<<g_T, BA_THREADS, 0, st>>>(a, f);
+      GIMS_LAUNCH_CHECK();
+      if (L > 0) {
+        ba_focal_sp_kernel<<<L, 64, 0, st>>>(a, f);
+        GIMS_LAUNCH_CHECK();
+      }
+      ba_focal_gq_kernel<<<(unsigned)f.n_groups, BA_THREADS, 0, st>>>(a, f);
+      GIMS_LAUNCH_CHECK();
+      ba_focal_step_kernel<<<1, BA_THREADS, 0, st>>>(a, f, it + 1 == a.cg_iters ? 1 : 0);
+      GIMS_LAUNCH_CHECK();
+    }
+    ba_pcg_cand_kernel<<<g_slots, BA_THREADS, 0, st>>>(a, r);
+    GIMS_LAUNCH_CHECK();
+    ba_focal_cand_kernel<<<g_ig, BA_THREADS, 0, st>>>(a, f);
+    GIMS_LAUNCH_CHECK();
+    ba_focal_back_kernel<<<g_T, BA_THREADS, 0, st>>>(a, f);
+    GIMS_LAUNCH_CHECK();
+    ba_decide_kernel<<<1, BA_THREADS, 0, st>>>(a, r);
+    GIMS_LAUNCH_CHECK();
+  }
+  ba_finish_kernel<<<g_all, BA_THREADS, 0, st>>>(a);
+  GIMS_LAUNCH_CHECK();
+  ba_focal_finish_kernel<<<g_ig, BA_THREADS, 0, st>>>(a, f);
+  GIMS_LAUNCH_CHECK();
+  return GIMS_OK;
+}
+
+// GIMS_AUX_BUNDLE_ADJUST, GIMS_AUX_BUNDLE_ADJUST_PCG and GIMS_AUX_BUNDLE_ADJUST_FOCAL of gims_run_ops (include/gims_hip.h): every argument
+// check precedes the first HIP call.  form: 0 dense, 1 conjugate gradients, 2 conjugate gradients with focal groups.
+static int ba_aux(const gims_aux_args& x, hipStream_t st, const int form) {
+  const bool pcg = form != 0, focal = form == 2;
   const int64_t T = x.i[0], n_obs = x.i[1], n_images = x.i[2], N = x.i[3], iters = x.i[4];
   const float huber = x.f[0], lambda0 = x.f[1];
   // i[5] is where a later form of this function (a blocked or iterative reduced solve) would be selected: it is read FIRST
@@ -1169,11 +1762,42 @@ static int ba_aux(const gims_aux_args& x, hipStream_t st, const bool pcg) {
     memcpy(&cg_tol, tab + 6, sizeof(double));
     GIMS_CHECK_ARG(tab[5] >= 1 && tab[5] <= BA_PCG_MAX_ITERS, "bundle_adjust: cg_iters = %lld (table word 5) is out of range (1 .. %d)", (long long)tab[5], BA_PCG_MAX_ITERS);
     GIMS_CHECK_ARG(cg_tol - cg_tol == 0.0 && cg_tol >= 0.0 && cg_tol < 1.0, "bundle_adjust: cg_tol = %g (table word 6) must be finite with 0 <= cg_tol < 1", cg_tol);
-    GIMS_CHECK_ARG(tab[7] == 0, "bundle_adjust: the table word 7 is reserved and must be 0");
+    GIMS_CHECK_ARG(focal || tab[7] == 0, "bundle_adjust: the table word 7 is reserved and must be 0");
+  }
+  // the focal form: table word 7 is the HOST array group[n_images]; the groups and the listed images are counted here, before any HIP call
+  int64_t n_groups = 0;
+  std::vector<int32_t> group_of, list_of, gimg_ptr, gimg_list;
+  if (focal) {
+    GIMS_CHECK_ARG(n_images == 0 || tab[7] != 0, "bundle_adjust: group (table word 7) is NULL while n_images = %lld", (long long)n_images);
+    GIMS_CHECK_ARG((tab[7] & 3) == 0, "bundle_adjust: group (table word 7) must be 4-byte aligned");
+    const int32_t* group = (const int32_t*)tab[7];
+    group_of.assign((size_t)n_images, -1), list_of.assign((size_t)n_images, -1);
+    for (int64_t k = 0; k < n_images; ++k) {
+      if (mode[k] == 0) continue;                              // an absent image's entry is ignored
+      GIMS_CHECK_ARG(group[k] >= -1 && group[k] < n_images, "bundle_adjust: image %lld: group = %d is out of range (-1 fixed intrinsics, 0 .. n_images - 1 = %lld)",
+                     (long long)k, group[k], (long long)n_images - 1);
+      group_of[(size_t)k] = group[k];
+      if (group[k] + 1 > n_groups) n_groups = group[k] + 1;
+    }
+    gimg_ptr.assign((size_t)n_groups + 1, 0);
+    for (int64_t k = 0; k < n_images; ++k)
+      if (group_of[(size_t)k] >= 0) ++gimg_ptr[(size_t)group_of[(size_t)k] + 1];
+    for (int64_t g = 0; g < n_groups; ++g) gimg_ptr[(size_t)g + 1] += gimg_ptr[(size_t)g];
+    gimg_list.resize((size_t)gimg_ptr[(size_t)n_groups]);
+    std::vector<int32_t> at(gimg_ptr.begin(), gimg_ptr.end() - 1);
+    for (int64_t k = 0; k < n_images; ++k)                     // ascending image index inside every group
+      if (group_of[(size_t)k] >= 0) gimg_list[(size_t)at[(size_t)group_of[(size_t)k]]++] = (int32_t)k;
+    for (int64_t s = 0; s < n_free; ++s) list_of[(size_t)slot_cam[(size_t)s]] = (int32_t)s;
+    for (int64_t k = 0; k < n_images; ++k)                     // the listed images: the slots, then the other images of the groups
+      if (mode[k] == 1 && group_of[(size_t)k] >= 0) list_of[(size_t)k] = (int32_t)slot_cam.size(), slot_cam.push_back((int32_t)k);
   }
 
   BaArgs a;
-  if (pcg)
+  BaFocal f;
+  memset(&f, 0, sizeof(f));
+  if (focal)
+    ba_focal_layout((void*)x.p[5], T, n_obs, n_images, iters, n_free, n_groups, a.out, f);
+  else if (pcg)
     ba_pcg_layout((void*)x.p[5], T, n_obs, n_images, iters, n_free, a.out);
   else
     ba_layout((void*)x.p[5], T, n_obs, n_images, iters, n_free, a.out);
@@ -1197,8 +1821,16 @@ static int ba_aux(const gims_aux_args& x, hipStream_t st, const bool pcg) {
     const int rc = upload_table(slot_of.data(), sizeof(int32_t) * (size_t)n_images, a.out.slot_of, st);
     if (rc != GIMS_OK) return rc;
   }
-  if (n_free > 0) {
-    const int rc = upload_table(slot_cam.data(), sizeof(int32_t) * (size_t)n_free, a.out.slot_cam, st);
+  if (!slot_cam.empty()) {
+    const int rc = upload_table(slot_cam.data(), sizeof(int32_t) * slot_cam.size(), a.out.slot_cam, st);
+    if (rc != GIMS_OK) return rc;
+  }
+  if (focal && n_groups > 0) {
+    f.n_groups = (int)n_groups, f.n_lists = (int)slot_cam.size();
+    int rc = upload_table(group_of.data(), sizeof(int32_t) * (size_t)n_images, f.group_of, st);
+    if (rc == GIMS_OK) rc = upload_table(list_of.data(), sizeof(int32_t) * (size_t)n_images, f.list_of, st);
+    if (rc == GIMS_OK) rc = upload_table(gimg_ptr.data(), sizeof(int32_t) * gimg_ptr.size(), f.gimg_ptr, st);
+    if (rc == GIMS_OK && !gimg_list.empty()) rc = upload_table(gimg_list.data(), sizeof(int32_t) * gimg_list.size(), f.gimg_list, st);
     if (rc != GIMS_OK) return rc;
   }
   const int64_t most = T > n_images ? T : n_images;
@@ -1207,7 +1839,8 @@ static int ba_aux(const gims_aux_args& x, hipStream_t st, const bool pcg) {
   GIMS_LAUNCH_CHECK();
   ba_classify_kernel<<<g_T, BA_THREADS, 0, st>>>(a);
   GIMS_LAUNCH_CHECK();
-  if (pcg) return ba_pcg_launches(a, g_all, g_T, st);
+  if (focal && n_groups > 0) return ba_focal_launches(a, f, g_all, g_T, st);
+  if (pcg) return ba_pcg_launches(a, g_all, g_T, st);             // (the focal form without a group is this form)
   ba_slots_kernel<<<1, BA_MAX_FREE, 0, st>>>(a);
   GIMS_LAUNCH_CHECK();
   if (n_free > 0) {
@@ -1239,7 +1872,8 @@ static int ba_aux(const gims_aux_args& x, hipStream_t st, const bool pcg) {
   return GIMS_OK;
 }
 
-int bundle_adjust_aux(const gims_aux_args& x, hipStream_t st) { return ba_aux(x, st, false); }
-int bundle_adjust_pcg_aux(const gims_aux_args& x, hipStream_t st) { return ba_aux(x, st, true); }
+int bundle_adjust_aux(const gims_aux_args& x, hipStream_t st) { return ba_aux(x, st, 0); }
+int bundle_adjust_pcg_aux(const gims_aux_args& x, hipStream_t st) { return ba_aux(x, st, 1); }
+int bundle_adjust_focal_aux(const gims_aux_args& x, hipStream_t st) { return ba_aux(x, st, 2); }
 
 }  // namespace gims

@@ -86,6 +86,7 @@ AUX_BUNDLE_ADJUST = _K["GIMS_AUX_BUNDLE_ADJUST"]             # joint refinement 
 BA_TABLE_WORDS, BA_MAX_FREE_CAMERAS, BA_MAX_REJECTS = _K["GIMS_BA_TABLE_WORDS"], _K["GIMS_BA_MAX_FREE_CAMERAS"], _K["GIMS_BA_MAX_REJECTS"]
 AUX_BUNDLE_ADJUST_PCG = _K["GIMS_AUX_BUNDLE_ADJUST_PCG"]     # the same with a matrix-free conjugate-gradient reduced solve: no 128-camera cap
 BA_PCG_MAX_FREE_CAMERAS, BA_PCG_MAX_CG_ITERS = _K["GIMS_BA_PCG_MAX_FREE_CAMERAS"], _K["GIMS_BA_PCG_MAX_CG_ITERS"]
+AUX_BUNDLE_ADJUST_FOCAL = _K["GIMS_AUX_BUNDLE_ADJUST_FOCAL"]  # the conjugate-gradient form with a focal scale per group of images; 15 is unassigned
 BA_COUNTERS = ("n_free", "n_fixed", "n_held", "n_points", "n_active_obs", "n_bad_obs", "rounds_taken", "status")
 BA_BAD_CAMERA, BA_BAD_START = 1, 2                           # the bits of the status counter
 BA_ABSENT, BA_FIXED, BA_FREE = 0, 1, 2                       # the modes of a camera
@@ -1474,15 +1475,38 @@ def ba_pcg_out_layout(T: int, n_obs: int, n_images: int, iters: int, n_free: int
     return off
 
 
-def ba_table(indptr, obs_image, obs_keypoint, obs_use, point_use, cg_iters: int = 0, cg_tol: float = 0.0) -> np.ndarray:
+def ba_focal_out_layout(T: int, n_obs: int, n_images: int, iters: int, n_free: int, n_groups: int) -> dict:
+    """BYTE offsets into the one buffer of GIMS_AUX_BUNDLE_ADJUST_FOCAL (include/gims_hip.h; csrc/ba.hip ba_focal_layout carves it): the nine
+    output regions of ba_pcg_out_layout at the same offsets, then focal_scale float64 [n_groups] and group_obs int32 [n_groups]; 'outputs'
+    = 'scratch' = the offset of the kernels' scratch, which is linear in every size, 'bytes' = the whole buffer."""
+    al = lambda x: (x + 255) & ~255      # noqa: E731
+    off, at = {}, 0
+    for name, size in (("xyz", 24 * T), ("cams", 144 * n_images), ("obs_error", 4 * n_obs), ("cam_obs", 4 * n_images), ("history", 16 * (iters + 1)),
+                       ("taken", iters), ("counters", 32), ("cg_used", 4 * iters), ("cg_res", 8 * iters), ("focal_scale", 8 * n_groups), ("group_obs", 4 * n_groups)):
+        off[name] = at
+        at += al(size)
+    off["outputs"] = off["scratch"] = at
+    off["bytes"] = at + (256 + 3 * al(4 * n_images) + al(4 * n_images + 4) + al(4 * n_free) + al(24 * T) + al(144 * n_images) + al(T) + al(n_obs)
+                         + 4 * al(4 * n_obs) + al(72 * T) + al(400 * n_obs) + al(8 * T) + al(24 * T) + al(336 * n_free) + 6 * al(48 * n_free)
+                         + 3 * al(4 * n_images) + al(32 * n_images) + al(16 * n_images) + al(64 * n_obs) + al(4 * n_groups + 4) + al(4 * n_groups)
+                         + al(8 * n_groups) + al(16 * n_groups) + 5 * al(8 * n_groups))
+    return off
+
+
+def ba_table(indptr, obs_image, obs_keypoint, obs_use, point_use, cg_iters: int = 0, cg_tol: float = 0.0, group=None) -> np.ndarray:
     """The HOST table of GIMS_AUX_BUNDLE_ADJUST, int64 [8]: the addresses of the five device arrays (tensors, raw addresses, or None) and
     three reserved zeros.  For GIMS_AUX_BUNDLE_ADJUST_PCG word 5 is cg_iters and word 6 the bit pattern of the double cg_tol (the
-    defaults leave both 0).  The caller keeps it, and the tensors, alive for as long as the op is run."""
+    defaults leave both 0).  For GIMS_AUX_BUNDLE_ADJUST_FOCAL word 7 is the address of ``group``, a C-contiguous int32 HOST array
+    [n_images] (or a raw address).  The caller keeps it, the group array and the tensors alive for as long as the op is run."""
     tab = np.zeros(BA_TABLE_WORDS, dtype=np.int64)
     for k, t in enumerate((indptr, obs_image, obs_keypoint, obs_use, point_use)):
         tab[k] = 0 if t is None else t if isinstance(t, int) else t.data_ptr()
     tab[5] = int(cg_iters)
     tab[6:7] = np.array([cg_tol], dtype=np.float64).view(np.int64)
+    if group is not None:
+        if not isinstance(group, int) and not (isinstance(group, np.ndarray) and group.dtype == np.int32 and group.flags["C_CONTIGUOUS"] and group.ndim == 1):
+            raise ValueError("bundle_adjust: group must be a C-contiguous int32 host array [n_images]")
+        tab[7] = group if isinstance(group, int) else group.ctypes.data if group.size else 0
     return tab
 
 
@@ -1528,21 +1552,56 @@ def ba_pcg_views(out: torch.Tensor, T: int, n_obs: int, n_images: int, iters: in
     return views
 
 
+def op_bundle_adjust_focal(table: np.ndarray, kpts, xyz, cams, mode: np.ndarray, out, T: int, n_obs: int, n: int, iters: int = 20, huber: float = 0.0,
+                           lambda0: float = 1e-4) -> Op:
+    """GIMS_AUX_BUNDLE_ADJUST_FOCAL as an op of gims_run_ops (include/gims_hip.h): the arguments of op_bundle_adjust_pcg, with the table of
+    ba_table(..., cg_iters=, cg_tol=, group=) and out uint8 [ba_focal_out_layout(T, n_obs, n_images, iters, n_free, n_groups)['bytes']]."""
+    op = op_bundle_adjust(table, kpts, xyz, cams, mode, out, T, n_obs, n, iters, huber, lambda0)      # (the same checks of the host arrays)
+    op.u.aux.fn = AUX_BUNDLE_ADJUST_FOCAL
+    return op
+
+
+def ba_focal_groups(mode: np.ndarray, group: np.ndarray) -> int:
+    """n_groups as the op counts it: 1 + the largest id among the posed images (0 when every id is -1)."""
+    ids = np.asarray(group)[np.asarray(mode) != BA_ABSENT]
+    return int(ids.max()) + 1 if ids.size and ids.max() >= 0 else 0
+
+
+def ba_focal_views(out: torch.Tensor, T: int, n_obs: int, n_images: int, iters: int, n_free: int, n_groups: int) -> dict:
+    """The typed views of the buffer of GIMS_AUX_BUNDLE_ADJUST_FOCAL, by ba_focal_out_layout: those of ba_pcg_views, focal_scale, group_obs."""
+    o = ba_focal_out_layout(T, n_obs, n_images, iters, n_free, n_groups)
+    views = ba_pcg_views(out, T, n_obs, n_images, iters, n_free)      # (the nine regions lie at the offsets of function 14)
+    views["focal_scale"] = out[o["focal_scale"]:o["focal_scale"] + 8 * n_groups].view(torch.float64)
+    views["group_obs"] = out[o["group_obs"]:o["group_obs"] + 4 * n_groups].view(torch.int32)
+    return views
+
+
 def bundle_adjust(indptr, obs_image, obs_keypoint, obs_use, point_use, kpts, xyz, cams, mode: np.ndarray, iters: int = 20, huber: float = 0.0,
                   lambda0: float = 1e-4, T: int | None = None, n_obs: int | None = None, n: int | None = None, solver: str = "dense",
-                  cg_iters: int = 64, cg_tol: float = 1e-6):
+                  cg_iters: int = 64, cg_tol: float = 1e-6, group: np.ndarray | None = None):
     """Joint refinement of the free cameras and the active points on the device (csrc/ba.hip): device tensors as
     op_bundle_adjust takes them (cams the DEVICE records float64 [n_images, 18]), mode the HOST int32 [n_images]; T, n_obs, n: the sizes to
     state when a tensor is a stand-in for an empty one (default: the tensors' own).  -> (the views of ba_views, and what must stay alive
     until the launches have run).  Asynchronous; no host read.  solver='pcg': GIMS_AUX_BUNDLE_ADJUST_PCG with cg_iters and cg_tol
-    (DESIGN.md 4.21), the views of ba_pcg_views; with 'dense' the two are not used."""
+    (DESIGN.md 4.21), the views of ba_pcg_views; with 'dense' the two are not used.  group (HOST int32 [n_images], solver='pcg' only):
+    GIMS_AUX_BUNDLE_ADJUST_FOCAL, the views of ba_focal_views."""
     if solver not in ("dense", "pcg"):
         raise ValueError(f"bundle_adjust: solver must be 'dense' or 'pcg', got {solver!r}")
+    if group is not None and solver != "pcg":
+        raise ValueError("bundle_adjust: focal groups need solver='pcg'")
     mode = np.ascontiguousarray(mode, dtype=np.int32).reshape(-1)
     T = indptr.numel() - 1 if T is None else T
     n_obs = obs_image.numel() if n_obs is None else n_obs
     n = kpts.shape[0] if n is None else n
     n_free = int((mode == BA_FREE).sum())
+    if group is not None:
+        group = np.ascontiguousarray(group, dtype=np.int32).reshape(-1)
+        n_groups = ba_focal_groups(mode, group)
+        table = ba_table(indptr, obs_image, obs_keypoint, obs_use, point_use, cg_iters=cg_iters, cg_tol=cg_tol, group=group)
+        out = torch.empty(ba_focal_out_layout(T, n_obs, mode.size, iters, n_free, n_groups)["bytes"], dtype=torch.uint8, device=xyz.device)
+        run_ops(make_ops([op_bundle_adjust_focal(table, kpts, xyz, cams, mode, out, T, n_obs, n, iters, huber, lambda0)]))
+        return (ba_focal_views(out, T, n_obs, mode.size, iters, n_free, n_groups),
+                (table, mode, group, out, indptr, obs_image, obs_keypoint, obs_use, point_use, kpts, xyz, cams))
     if solver == "pcg":
         table = ba_table(indptr, obs_image, obs_keypoint, obs_use, point_use, cg_iters=cg_iters, cg_tol=cg_tol)
         out = torch.empty(ba_pcg_out_layout(T, n_obs, mode.size, iters, n_free)["bytes"], dtype=torch.uint8, device=xyz.device)

@@ -752,7 +752,64 @@ int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t
  * which costs the square of a slot's list length over 256 threads).  A wave per slot forms U*, b, M_s and its factor in registers; a
  * thread per track forms y; a wave per slot forms q_s; one workgroup of 256 does the dot products, the vector updates and M^-1, and one
  * thread of it decides.  There are no float atomics and no sum whose order depends on the grid: the output bytes are identical across
- * runs and graph replays. */
+ * runs and graph replays.
+ *
+ * GIMS_AUX_BUNDLE_ADJUST_FOCAL is the ninth: GIMS_AUX_BUNDLE_ADJUST_PCG with the focal lengths as unknowns.  Every posed
+ * image belongs to at most one FOCAL GROUP; a group has one unknown, the relative scale ds of the focal lengths of all its images: fx' =
+ * fx (1 + ds), fy' = fy (1 + ds); cx, cy and the ratio fx / fy stay.  Everything not stated here is GIMS_AUX_BUNDLE_ADJUST_PCG's, word for
+ * word (activity, status bits, held cameras, the lambda schedule, TAKEN with float32-rounded costs, GIMS_BA_MAX_REJECTS, cg_iters, cg_tol,
+ * cg_used, cg_res, the two-buffer state); functions 13 and 14 are unchanged.  kernels: ba_focal_*_kernel, gims_amd/csrc/ba.hip;
+ * tests/ba_focal_ref.py is the restatement.
+ *   p[], i[] and f[] as for GIMS_AUX_BUNDLE_ADJUST_PCG (i[5] is the form word: read first, must be 0), except table word 7: the HOST
+ *               address of int32 group [n_images], 4-byte aligned, read during the call like mode: -1 = the image's intrinsics stay
+ *               fixed, 0 .. n_images - 1 = a group id.  n_groups = 1 + the largest id of a posed image (counted on the host before any
+ *               HIP call).  The entry of an absent image is ignored.  A group without a posed image is held.
+ *   p[5] out    the nine output regions of GIMS_AUX_BUNDLE_ADJUST_PCG at their offsets, then
+ *                 double focal_scale [n_groups] | int32 group_obs [n_groups] |
+ *                 scratch: 256 bytes of state | int32 [n_images] x 2 | int32 [n_images + 1] | int32 [n_free] | int32 [n_images] |
+ *                 double [T][3] | double [n_images][18] | uint8 [T] | uint8 [n_obs] | int32 [n_obs] x 4 | double [T][9] | double [n_obs][50]
+ *                 | double [T] | double [T][3] | double [n_free][42] | double [n_free][6] x 6 | int32 [n_images] x 3 | double [n_images][4] |
+ *                 double [n_images][2] | double [n_obs][8] | int32 [n_groups + 1] | int32 [n_groups] | double [n_groups] | double
+ *                 [n_groups][2] | double [n_groups] x 5
+ *               every region on a 256-byte boundary (hip.ba_focal_out_layout has the offsets): linear in T, n_obs, n_images, n_free and
+ *               n_groups.  focal_scale[g] = the product of the (1 + ds) of the rounds that were taken (1 for a held group); group_obs[g]
+ *               = the active observations of the group's posed images.  In the cams region the words fx, fy of every image of a group
+ *               that moves hold the refined values; every other word follows the copy-through rule of GIMS_AUX_BUNDLE_ADJUST.
+ *   With every entry of group equal to -1 (n_groups = 0) the launches are those of GIMS_AUX_BUNDLE_ADJUST_PCG and the nine shared regions
+ *   hold its bytes.
+ * The model.  A group collects the active observations of ALL its posed images, those of fixed and held cameras included (fixing a pose
+ *   fixes the gauge, not the lens).  A group is HELD iff group_obs < 4; a held group keeps its place in the system as an identity entry
+ *   with a zero right-hand side.  For an active observation o of an image of a group that moves: Fu = fx x_c[0] / z, Fv = fy x_c[1] / z
+ *   (the products first, as in the residual), both multiplied by the Huber factor sqrt(huber / e) when e > huber, like the other Jacobian
+ *   words; G_o[m] = Fu Pu[m] + Fv Pv[m]; GI_o[m] = (G_o[0] I[0][m] + G_o[1] I[1][m]) + G_o[2] I[2][m].
+ *   "The image's order": lane l of 64 adds the terms of the entries l, l + 64, ... of the image's list (its active observations ascending
+ *   in o; a list exists for every posed image that is a slot or lies in a group), then a butterfly (offsets 32 .. 1).  "The group's
+ *   order": the per-image sums are added by the scheme of the cost: thread j of 256 adds the group's posed images j, j + 256, ... in
+ *   ascending image index, a butterfly per wave, the four waves in order.
+ *   Per group that moves, each sum in the image's order and then the group's order: A = sum Fu Fu + Fv Fv, A* = A + lambda max(A, 1e-6);
+ *   g_g = sum Fu ru + Fv rv; b_g = -g_g + sum (GI_o[0] g_p[0] + GI_o[1] g_p[1]) + GI_o[2] g_p[2]; M_g = A* - sum (GI_o[0] G_o[0] + GI_o[1]
+ *   G_o[1]) + GI_o[2] G_o[2].  Per slot that moves and whose group moves, in the image's order: C_s[c] = sum Ju[c] Fu + Jv[c] Fv.
+ *   The unknowns are [6 words per slot | 1 word per group]; S = [[U*, C], [C^T, A*]] - sum over the points of E V*^-1 E^T, where E stacks
+ *   the W_o and G_o rows of the point's observations.  The product q = S v: per active point, s = 0, then over its active observations in
+ *   ascending o: first, when the camera moves, for c ascending s[m] += W_o[c][m] v[6 k + c]; then, when the group moves, s[m] += G_o[m]
+ *   v_g; y = I s as before.  q_s[r] = (U*[r] . v_s + C_s[r] v_g(s)) - sum W_o[r] . y (the C term only where both move; U*[r] . v_s and the
+ *   sum as in function 14).  q_g = (A*_g v_g + sum over the group's images of C_s . v_s) - sum G_o . y, where C_s . v_s is the dot product
+ *   of six of function 14 (0 for an image that is no moving slot) and sum G_o . y = sum (G_o[0] y[0] + G_o[1] y[1]) + G_o[2] y[2] in the
+ *   image's order; both sums over the images in the group's order.  A held group has q_g = v_g.
+ *   The preconditioner: M_s of function 14 unchanged, and the scalar M_g: z_g = r_g / M_g.  A dot product is the slot sum of function 14,
+ *   then the group sum sum v_g w_g by the same 256-thread scheme over the groups; the two are added in that order.  The iteration is
+ *   function 14's on the longer vectors.  REGULAR needs, in addition, every M_g finite and > 0.
+ *   Back-substitution: per active point s = g_p, then over its active observations in ascending o: the camera term of function 14, then s[m]
+ *   += G_o[m] ds_g.  The candidate of a group that moves: fx' = fx (1 + ds), fy' = fy (1 + ds) for every image of the group, scale' = scale
+ *   (1 + ds); 1 + ds <= 0 or a non-finite fx' or fy' makes the round not TAKEN.  An irregular round has ds = 0.
+ * GIMS_EINVAL before any HIP call, each with a message naming bundle_adjust: everything GIMS_AUX_BUNDLE_ADJUST_PCG refuses except table word
+ * 7; table word 7 NULL while n_images > 0; table word 7 not 4-byte aligned; the group of a posed image outside -1 .. n_images - 1.
+ * Nothing outside out is written.  With n_groups > 0: the memset nodes, the upload of the slot, list and group tables and 8 + iters
+ * (10 + 4 cg_iters) + 2 launches: init, classify, groups, lists, fill, sort, back, decide; per round point, focal-point, setup, image, group,
+ * cg-init, cg_iters x {y, S p, q_g, step}, candidate, focal-candidate, back, decide; finish, focal-finish -- without setup when n_free == 0
+ * (poses fixed, lens and points refined: a valid call) and without lists, fill, sort, image and S p when no image is listed.  The sequence
+ * depends on iters, cg_iters, n_free == 0, n_groups == 0 and on whether any image is listed, never on device data.  No host
+ * synchronisation; capturable.  No cooperative launch; no float atomics; no sum whose order depends on the grid. */
 #define GIMS_OP_AUX 2
 #define GIMS_AUX_SPLIT_SPL32 0
 #define GIMS_AUX_SAGE_MEAN_SPLIT 1
@@ -784,6 +841,8 @@ int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t
 #define GIMS_AUX_BUNDLE_ADJUST_PCG 14
 #define GIMS_BA_PCG_MAX_FREE_CAMERAS 65536
 #define GIMS_BA_PCG_MAX_CG_ITERS 256
+/* 15 is unassigned and stays refused as an unknown auxiliary function */
+#define GIMS_AUX_BUNDLE_ADJUST_FOCAL 16
 typedef struct gims_aux_args { int32_t fn, reserved; const void* p[6]; int64_t i[6]; float f[2]; } gims_aux_args;
 typedef struct gims_op { int32_t kind; int32_t reserved; union { gims_linear_args lin; gims_attn_args att; gims_aux_args aux; } u; } gims_op;
 int gims_run_ops(const gims_op* ops /* HOST */, int32_t n_ops, void* stream);
