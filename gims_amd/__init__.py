@@ -13,7 +13,9 @@ from .tracks import Tracks, build_tracks  # noqa: F401
 from .triangulate import Points3D, cameras_from_pose, triangulate_tracks  # noqa: F401
 from .resect import Poses, absolute_pose, resect_images  # noqa: F401
 from .bundle import Adjusted, bundle_adjust  # noqa: F401
+from .pairs import PairSelection, select_pairs  # noqa: F401
 
 __all__ = ["GMatcher", "ImageFeatures", "Matching", "nndr", "mnn", "nn_match_pairs", "ColorAug", "ColorAugPlan", "find_homography", "find_fundamental", "verify_pairs",
            "estimate_pose", "pose_error", "epipolar_error", "pose_summary", "build_tracks", "Tracks",
-           "triangulate_tracks", "Points3D", "cameras_from_pose", "resect_images", "Poses", "absolute_pose", "bundle_adjust", "Adjusted"]
+           "triangulate_tracks", "Points3D", "cameras_from_pose", "resect_images", "Poses", "absolute_pose", "bundle_adjust", "Adjusted",
+           "select_pairs", "PairSelection"]

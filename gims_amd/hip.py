@@ -87,6 +87,11 @@ BA_TABLE_WORDS, BA_MAX_FREE_CAMERAS, BA_MAX_REJECTS = _K["GIMS_BA_TABLE_WORDS"],
 AUX_BUNDLE_ADJUST_PCG = _K["GIMS_AUX_BUNDLE_ADJUST_PCG"]     # the same with a matrix-free conjugate-gradient reduced solve: no 128-camera cap
 BA_PCG_MAX_FREE_CAMERAS, BA_PCG_MAX_CG_ITERS = _K["GIMS_BA_PCG_MAX_FREE_CAMERAS"], _K["GIMS_BA_PCG_MAX_CG_ITERS"]
 AUX_BUNDLE_ADJUST_FOCAL = _K["GIMS_AUX_BUNDLE_ADJUST_FOCAL"]  # the conjugate-gradient form with a focal scale per group of images; 15 is unassigned
+AUX_SELECT_PAIRS = _K["GIMS_AUX_SELECT_PAIRS"]               # which image pairs to match, from a coarse int8 pre-match: likewise
+PAIRS_TABLE_WORDS, PAIRS_SCALE_GIVEN = _K["GIMS_PAIRS_TABLE_WORDS"], _K["GIMS_PAIRS_SCALE_GIVEN"]
+PAIRS_MAX_IMAGES, PAIRS_MAX_ROWS, PAIRS_MAX_D = _K["GIMS_PAIRS_MAX_IMAGES"], _K["GIMS_PAIRS_MAX_ROWS"], _K["GIMS_PAIRS_MAX_D"]
+PAIRS_QUERY_TILE = _K["GIMS_PAIRS_QUERY_TILE"]               # pooled rows per workgroup of the vote kernel, 32 per wave: the seams of m_i
+PAIRS_COUNTERS = ("n_pairs", "n_rows", "n_short_images", "n_bad_rows", "n_nonfinite")
 BA_COUNTERS = ("n_free", "n_fixed", "n_held", "n_points", "n_active_obs", "n_bad_obs", "rounds_taken", "status")
 BA_BAD_CAMERA, BA_BAD_START = 1, 2                           # the bits of the status counter
 BA_ABSENT, BA_FIXED, BA_FREE = 0, 1, 2                       # the modes of a camera
@@ -1289,6 +1294,68 @@ def build_tracks(entries, counts, device, min_length: int = 2, keep_conflicting:
     run_ops(make_ops([op_build_tracks(dev_tab, start, track_of, out, counters, work, len(entries), n_images, n, min_length, keep_conflicting,
                                       0.0 if min_score is None else min_score)]))
     return track_of, out, counters, start, (dev_tab, work, entries)
+
+
+def pairs_pool(ms) -> int:
+    """Rows of the pooled int8 matrix of GIMS_AUX_SELECT_PAIRS for images of ms selected rows each (include/gims_hip.h): every image on a
+    multiple of 32 rows, the whole on a multiple of PAIRS_QUERY_TILE."""
+    rows = max(sum((int(m) + 31) // 32 * 32 for m in ms), 1)
+    return (rows + PAIRS_QUERY_TILE - 1) // PAIRS_QUERY_TILE * PAIRS_QUERY_TILE
+
+
+def pairs_work_bytes(ms, d: int) -> int:
+    """The workspace of GIMS_AUX_SELECT_PAIRS: the formula of include/gims_hip.h (csrc/pairs.hip prs_layout carves it)."""
+    al = lambda x: (x + 255) & ~255
+    n, pool = len(ms), pairs_pool(ms)
+    dp = 32
+    while dp < d:
+        dp *= 2
+    return 256 + al(8 * PAIRS_TABLE_WORDS * n) + al(4 * pool // 32) + al(pool * dp) + al(4 * pool) + al(n * n) + 2 * al(4 * n)
+
+
+def pairs_out_layout(n: int, k: int):
+    """Word offsets into the int32 output buffer of GIMS_AUX_SELECT_PAIRS: (pairs, pair_votes, total words, cap); cap = min(n k, n (n - 1) / 2)
+    pairs at the most, pairs is [cap][2]."""
+    cap = min(n * k, n * (n - 1) // 2)
+    return 0, 2 * cap, 3 * cap, cap
+
+
+def pairs_rq(ratio) -> int:
+    """The ratio test of GIMS_AUX_SELECT_PAIRS in integers: rint(ratio^2 * 65536) of the float32 ratio, the products in float64."""
+    r = float(np.float32(ratio))
+    return int(np.rint(r * r * 65536.0))
+
+
+def pairs_table(images, rq: int, work_bytes: int, scale_given: bool = False) -> np.ndarray:
+    """The HOST table of GIMS_AUX_SELECT_PAIRS (include/gims_hip.h): int64 [N + 1, 8].  images: (descriptors, row stride in floats, n, index
+    list or None, m) each; descriptors and the index list are device tensors or raw addresses.  The array must stay alive during the call."""
+    tab = np.zeros((len(images) + 1, PAIRS_TABLE_WORDS), dtype=np.int64)
+    addr = lambda t: 0 if t is None else (int(t) if isinstance(t, int) else t.data_ptr())
+    for i, (desc, ld, n, idx, m) in enumerate(images):
+        tab[i, :5] = (addr(desc), int(ld), int(n), addr(idx), int(m))
+    tab[len(images), :3] = (int(rq), PAIRS_SCALE_GIVEN if scale_given else 0, int(work_bytes))
+    return tab
+
+
+def op_select_pairs(table: np.ndarray, votes, out, counters, work, n: int, d: int, per_image: int, k: int, min_votes: int, scale: float = 0.0) -> Op:
+    """GIMS_AUX_SELECT_PAIRS as an op of gims_run_ops (include/gims_hip.h): the one way to reach it.  table: pairs_table's HOST array (keep it
+    alive while the op is run); votes int32 [n, n]; out int32 [pairs_out_layout(n, k)[2]]; counters int32 [8]; work uint8 [pairs_work_bytes]."""
+    return op_aux(AUX_SELECT_PAIRS, (int(table.ctypes.data), votes, out, counters, work, None), (n, d, per_image, k, min_votes, 0), (scale,))
+
+
+def select_pairs(images, d: int, device, k: int, per_image: int, rq: int, min_votes: int, scale: float | None = None, out=None):
+    """The pair selection of an image set on the device (csrc/pairs.hip): images as pairs_table takes them.  -> (votes int32
+    [N, N], out int32 -- see pairs_out_layout --, counters int32 [8], and what must stay alive until the launches have run).  out: a buffer
+    to write into instead of a new one.  Asynchronous; no host read."""
+    n, ms = len(images), [int(im[4]) for im in images]
+    work = torch.empty(pairs_work_bytes(ms, d), dtype=torch.uint8, device=device)
+    tab = pairs_table(images, rq, work.numel(), scale is not None)
+    votes = torch.empty((n, n), dtype=torch.int32, device=device)
+    if out is None:
+        out = torch.zeros(max(pairs_out_layout(n, k)[2], 1), dtype=torch.int32, device=device)
+    counters = torch.empty(8, dtype=torch.int32, device=device)
+    run_ops(make_ops([op_select_pairs(tab, votes, out, counters, work, n, d, per_image, k, min_votes, 0.0 if scale is None else scale)]))
+    return votes, out, counters, (work, images)
 
 
 def triangulate_out_layout(T: int, n_obs: int) -> dict:

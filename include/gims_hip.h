@@ -809,7 +809,45 @@ int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t
  * cg-init, cg_iters x {y, S p, q_g, step}, candidate, focal-candidate, back, decide; finish, focal-finish -- without setup when n_free == 0
  * (poses fixed, lens and points refined: a valid call) and without lists, fill, sort, image and S p when no image is listed.  The sequence
  * depends on iters, cg_iters, n_free == 0, n_groups == 0 and on whether any image is listed, never on device data.  No host
- * synchronisation; capturable.  No cooperative launch; no float atomics; no sum whose order depends on the grid. */
+ * synchronisation; capturable.  No cooperative launch; no float atomics; no sum whose order depends on the grid.
+ *
+ * GIMS_AUX_SELECT_PAIRS is the tenth function of this table without a stand-alone entry point, for the same reason.  It decides which pairs of
+ * an image set are worth matching: a coarse pre-match of a few hundred int8-quantised descriptors per image, all images
+ * against all images, a vote per row and the k best partners per image.  This library's own specification: the reference matches one pair and
+ * has no counterpart.  kernels: pairs_*_kernel, gims_amd/csrc/pairs.hip; tests/pairs_ref.py is the restatement.  Every decision is taken in
+ * integers, so every output is a function of the inputs alone.
+ *   p[0] table    HOST int64 [N + 1][GIMS_PAIRS_TABLE_WORDS], 8-byte aligned, read during the call only.  Entry i < N = {address of the
+ *                 descriptors of image i (const float* on the device, [n_i][D] with a row stride, 4-byte aligned; may be NULL when m_i = 0),
+ *                 row stride in floats (>= D), n_i, address of the selected rows (const int32_t* on the device, m_i entries, 4-byte aligned;
+ *                 NULL: rows 0 .. m_i - 1), m_i (0 .. per_image), 0, 0, 0}.  Entry N = {rq, flags, work_bytes, 0, 0, 0, 0, 0}: rq = (int) rint
+ *                 ((double) ratio * (double) ratio * 65536) for the float ratio in [0, 1]; the one flag is GIMS_PAIRS_SCALE_GIVEN.
+ *   p[1] votes    device int32 [N][N]: votes[i][j] = the rows of image i that vote for image j; the diagonal is 0.  Written whole.
+ *   p[2] out      device int32 [3 cap], cap = min(N k, N (N - 1) / 2): pairs [cap][2], then pair_votes [cap].  The call writes the first n_pairs
+ *                 entries of each; what lies behind them is left as it was.
+ *   p[3] counters device int32 [8] = {n_pairs, n_rows (sum of m_i), n_short_images (m_i < 2), n_bad_rows, n_nonfinite (saturating), 0, 0, 0}
+ *   p[4] work     device scratch, 16-byte aligned, of at least the table's work_bytes bytes.  With P_i = m_i rounded up to a multiple of 32,
+ *                 pool = max(sum P_i, 1) rounded up to a multiple of GIMS_PAIRS_QUERY_TILE, Dp = the smallest power of two >= D and al256(x) =
+ *                 (x + 255) & ~255 the call needs 256 + al256(8 * GIMS_PAIRS_TABLE_WORDS * N) + al256(4 * pool / 32) + al256(pool * Dp) +
+ *                 al256(4 pool) + al256(N * N) + 2 al256(4 N) bytes.
+ *   p[5] NULL (reserved).   i = {N, D, per_image, k, min_votes, 0 (the form word, read first)}   f = {scale (read with GIMS_PAIRS_SCALE_GIVEN)}
+ *   1 Scale.  With GIMS_PAIRS_SCALE_GIVEN s = scale.  Otherwise maxabs = the largest |x| over the finite selected values (an integer maximum
+ *     on the float bits) and s = 127.0f / maxabs in float32, 0 when maxabs is 0.  s stays in device memory.
+ *   2 Quantise.  q = clamp(rintf(x * s), -127, 127) as int8: one float32 product, rounded half to even; a NaN product (0 times an s that
+ *     overflowed) is 0.  A non-finite x is 0 and is counted (n_nonfinite).  A selected index outside 0 .. n_i - 1 is counted (n_bad_rows);
+ *     such a row does not exist: it neither votes nor is a neighbour.  |q|^2 per row is int32.
+ *   3 Two smallest.  For a row r of image i that exists and an image j != i: d^2 (r, c) = |q_r|^2 + |q_c|^2 - 2 q_r . q_c in int32 over the
+ *     rows c of image j that exist; d1 <= d2 are its two smallest values as a multiset.
+ *   4 Vote.  r votes for j iff image j has two rows that exist and (int64) d1 * 65536 < (int64) rq * d2.
+ *   5 Select.  S[i][j] = votes[i][j] + votes[j][i].  The partners of i are the first min(k, N - 1) of {j != i: S[i][j] >= min_votes} ordered
+ *     by (-S[i][j], j); the result is the union over i of (min(i, j), max(i, j)), each once, ascending; pair_votes is S of the pair.
+ * GIMS_EINVAL before any HIP call, each with a message naming select_pairs: N outside 2 .. GIMS_PAIRS_MAX_IMAGES; D no multiple of 32 or
+ * outside 32 .. GIMS_PAIRS_MAX_D; per_image outside 0 .. GIMS_PAIRS_MAX_ROWS; an m_i outside 0 .. per_image; k < 1; min_votes < 0; rq outside
+ * 0 .. 65536; a NULL table, votes, out, counters or work; a NULL descriptor pointer with m_i > 0; a misaligned pointer; a row stride below D; a
+ * non-zero reserved word (i[5], p[5], table words 5 .. 7, words 3 .. 7 and the unknown flags of entry N); a scale that is not finite and >= 0;
+ * work_bytes below what the call needs.  What the descriptors and the index lists HOLD is not trusted.
+ * The launches: the uploads of the table and of the image of every 32 pooled rows, three memset nodes, maxabs (without a given scale),
+ * quantise, vote, select, count, scan, fill.  They are fixed by N, the m_i, D and the flag, never by device data.  No host synchronisation;
+ * capturable.  Integer atomics only. */
 #define GIMS_OP_AUX 2
 #define GIMS_AUX_SPLIT_SPL32 0
 #define GIMS_AUX_SAGE_MEAN_SPLIT 1
@@ -843,6 +881,13 @@ int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t
 #define GIMS_BA_PCG_MAX_CG_ITERS 256
 /* 15 is unassigned and stays refused as an unknown auxiliary function */
 #define GIMS_AUX_BUNDLE_ADJUST_FOCAL 16
+#define GIMS_AUX_SELECT_PAIRS 17
+#define GIMS_PAIRS_TABLE_WORDS 8
+#define GIMS_PAIRS_MAX_IMAGES 8192
+#define GIMS_PAIRS_MAX_ROWS 4096
+#define GIMS_PAIRS_MAX_D 1024
+#define GIMS_PAIRS_QUERY_TILE 128
+#define GIMS_PAIRS_SCALE_GIVEN 1
 typedef struct gims_aux_args { int32_t fn, reserved; const void* p[6]; int64_t i[6]; float f[2]; } gims_aux_args;
 typedef struct gims_op { int32_t kind; int32_t reserved; union { gims_linear_args lin; gims_attn_args att; gims_aux_args aux; } u; } gims_op;
 int gims_run_ops(const gims_op* ops /* HOST */, int32_t n_ops, void* stream);
