@@ -14,8 +14,9 @@ from .triangulate import Points3D, cameras_from_pose, triangulate_tracks  # noqa
 from .resect import Poses, absolute_pose, resect_images  # noqa: F401
 from .bundle import Adjusted, bundle_adjust  # noqa: F401
 from .pairs import PairSelection, select_pairs  # noqa: F401
+from .guided import guided_match_features, guided_match_pairs  # noqa: F401
 
 __all__ = ["GMatcher", "ImageFeatures", "Matching", "nndr", "mnn", "nn_match_pairs", "ColorAug", "ColorAugPlan", "find_homography", "find_fundamental", "verify_pairs",
            "estimate_pose", "pose_error", "epipolar_error", "pose_summary", "build_tracks", "Tracks",
            "triangulate_tracks", "Points3D", "cameras_from_pose", "resect_images", "Poses", "absolute_pose", "bundle_adjust", "Adjusted",
-           "select_pairs", "PairSelection"]
+           "select_pairs", "PairSelection", "guided_match_pairs", "guided_match_features"]

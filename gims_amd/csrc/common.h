@@ -190,6 +190,8 @@ int bundle_adjust_pcg_aux(const gims_aux_args& x, hipStream_t st);
 int bundle_adjust_focal_aux(const gims_aux_args& x, hipStream_t st);
 // pairs.hip: GIMS_AUX_SELECT_PAIRS, likewise
 int select_pairs_aux(const gims_aux_args& x, hipStream_t st);
+// nn.hip: GIMS_AUX_GUIDED_MATCH, likewise
+int guided_match_aux(const gims_aux_args& x, hipStream_t st);
 
 // sinkhorn2d.hip: the 2-D on-chip Sinkhorn (all iterations in one launch; see that file's header)
 struct OtR2Host { const float* z; int64_t ld; int n, m; float* u; float* v; float* status; float norm, log_mu_bin, log_nu_bin; };

@@ -396,6 +396,8 @@ extern "C" int gims_run_ops(const gims_op* ops, int32_t n_ops, void* stream) {
         rc = bundle_adjust_focal_aux(x, (hipStream_t)stream);
       else if (x.fn == GIMS_AUX_SELECT_PAIRS)
         rc = select_pairs_aux(x, (hipStream_t)stream);
+      else if (x.fn == GIMS_AUX_GUIDED_MATCH)
+        rc = guided_match_aux(x, (hipStream_t)stream);
       else
         GIMS_CHECK_ARG(false, "gims_run_ops: op %d: unknown auxiliary function %d", i, x.fn);
     } else {

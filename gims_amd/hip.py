@@ -92,6 +92,9 @@ PAIRS_TABLE_WORDS, PAIRS_SCALE_GIVEN = _K["GIMS_PAIRS_TABLE_WORDS"], _K["GIMS_PA
 PAIRS_MAX_IMAGES, PAIRS_MAX_ROWS, PAIRS_MAX_D = _K["GIMS_PAIRS_MAX_IMAGES"], _K["GIMS_PAIRS_MAX_ROWS"], _K["GIMS_PAIRS_MAX_D"]
 PAIRS_QUERY_TILE = _K["GIMS_PAIRS_QUERY_TILE"]               # pooled rows per workgroup of the vote kernel, 32 per wave: the seams of m_i
 PAIRS_COUNTERS = ("n_pairs", "n_rows", "n_short_images", "n_bad_rows", "n_nonfinite")
+AUX_GUIDED_MATCH = _K["GIMS_AUX_GUIDED_MATCH"]               # the descriptor match again under a verified pair's model: likewise
+GUIDED_TABLE_WORDS = _K["GIMS_GUIDED_TABLE_WORDS"]
+GUIDED_INFO = ("fallback_rows0", "fallback_rows1", "n_fixed", "n_bad_prior", "n_dup_prior", "no_model", "n_added")
 BA_COUNTERS = ("n_free", "n_fixed", "n_held", "n_points", "n_active_obs", "n_bad_obs", "rounds_taken", "status")
 BA_BAD_CAMERA, BA_BAD_START = 1, 2                           # the bits of the status counter
 BA_ABSENT, BA_FIXED, BA_FREE = 0, 1, 2                       # the modes of a camera
@@ -842,6 +845,117 @@ def nn_match(items, flags: int = 0, work=None):
         work = torch.empty(need, dtype=torch.uint8, device=items[0]["a"].device)
     _check(lib.gims_nn_match(arr, len(items), int(flags), _p(work), work.numel() * work.element_size(), _stream()), "gims_nn_match")
     return work
+
+
+# ------------------------------------------------------------------------------------------------ guided matching
+GUIDED_OUTPUTS = (("nn1", torch.int32), ("nn2", torch.int32), ("d1", torch.float32), ("d2", torch.float32), ("ratio", torch.float32),
+                  ("n_admissible", torch.int32), ("matches0", torch.int64), ("scores0", torch.float32), ("added0", torch.uint8))
+_GUIDED_WORDS = ("a", "b", "lda", "ldb", "n0", "n1", "d", "kpts0", "kpts1", "model", "kind", "ok", "prior", "prior_mask", "prior_scores", "mutual",
+                 "nn1", "nn2", "d1", "d2", "ratio", "n_admissible", "matches0", "scores0", "added0", "cnn1", "matches1", "info", "thresh", "threshold",
+                 "max_distance", "reserved")
+GUIDED_WORD = {name: k for k, name in enumerate(_GUIDED_WORDS)}       # the words of one pair in the table of GIMS_AUX_GUIDED_MATCH
+
+
+def guided_layout(sizes, flags: int = 0) -> dict:
+    """The workspace of GIMS_AUX_GUIDED_MATCH: the formula of include/gims_hip.h (csrc/nn.hip carves it).  sizes: (n0, n1, mutual) per pair.
+    -> {'bytes', 'csplit' (per problem, pair by pair: A against B, with mutual then B against A), 'items' (workgroups of the candidate pass)}."""
+    al = lambda x: (x + 255) & ~255                                    # noqa: E731
+    cd = lambda a, b: -(-a // b)                                       # noqa: E731
+    forced = bool(flags & NN_EXHAUSTIVE)
+    probs = []
+    for n0, n1, mutual in sizes:
+        probs.append((int(n0), int(n1), 0))
+        if mutual:
+            probs.append((int(n1), int(n0), 1))
+    P, Q = len(sizes), len(probs)
+    want = min(max(cd(512, sum(cd(nx, 128) for nx, _, _ in probs)), 1), 8)
+    total = al(160 * Q) + al(200 * P) + al(16 * P) + al(48 * Q) + al(232 * P) + al(16 * P) + al(4 * sum(int(s[1]) for s in sizes))
+    for n0, n1, _ in sizes:
+        n0, n1 = int(n0), int(n1)
+        total += al(8 * n0) + al(8 * n1) + al(4 * n0) + al(4 * n1) + al(32 * n0) + al(32 * n1) + al(n0)
+    csplits, items = [], 0
+    for nx, ny, second in probs:
+        tiles = cd(ny, 128)
+        tiles_per = cd(tiles, min(want, tiles))
+        csplit = cd(tiles, tiles_per)
+        csplits.append(csplit)
+        items += cd(nx, 128) * csplit
+        total += al(4 * nx) + (3 * al(4 * nx) if second else 0)
+        if not forced:
+            total += 2 * al(64 * nx * csplit) + al(16 * nx * csplit)
+    return dict(bytes=total, csplit=csplits, items=items)
+
+
+def _f32_bits(v) -> int:
+    return int(np.float32(v).view(np.uint32))
+
+
+def guided_table(items) -> np.ndarray:
+    """The HOST table of GIMS_AUX_GUIDED_MATCH (include/gims_hip.h): int64 [P, GUIDED_TABLE_WORDS].  items: dicts keyed by the words of
+    GUIDED_WORD -- device tensors or raw addresses for the pointers (None -> 0), numbers for the rest; `thresh`, `threshold` (the ratio) and
+    `max_distance` (None: +inf) are stored as the bits of a float32.  The array must stay alive during the call."""
+    tab = np.zeros((len(items), GUIDED_TABLE_WORDS), dtype=np.int64)
+    addr = lambda t: 0 if t is None else (int(t) if isinstance(t, (int, np.integer)) else t.data_ptr())      # noqa: E731
+    for p, it in enumerate(items):
+        for name, k in GUIDED_WORD.items():
+            v = it.get(name)
+            if name in ("lda", "ldb", "n0", "n1", "d", "kind", "reserved"):
+                tab[p, k] = int(v or 0)
+            elif name == "mutual":
+                tab[p, k] = int(bool(v))
+            elif name in ("thresh", "threshold", "max_distance"):
+                tab[p, k] = _f32_bits(float("inf") if (v is None and name == "max_distance") else v)
+            else:
+                tab[p, k] = addr(v)
+    return tab
+
+
+def op_guided_match(table: np.ndarray, work, work_bytes: int, flags: int = 0) -> Op:
+    """GIMS_AUX_GUIDED_MATCH as an op of gims_run_ops (include/gims_hip.h): the one way to reach it.  table: guided_table's HOST array (keep
+    it alive while the op is run); work: uint8 [work_bytes] on the device, 256-byte aligned."""
+    return op_aux(AUX_GUIDED_MATCH, (int(table.ctypes.data), work, None, None, None, None), (table.shape[0], flags, work_bytes, 0, 0, 0), (0.0, 0.0))
+
+
+def guided_match(items, flags: int = 0, work=None):
+    """Guided matching of a batch of pairs on the device (csrc/nn.hip).  items: dicts with device tensors a [n0, d] / b [n1, d]
+    (float32, rows contiguous), kpts0 [n0, 2] / kpts1 [n1, 2] (float32, contiguous), model float32 [9] (or [3, 3]), kind ('homography' / 0 or
+    'fundamental' / 1), optionally ok (a float32 tensor whose first element is read), prior int64 [n0], prior_mask uint8 [n0], prior_scores
+    float32 [n0]; `mutual`, `thresh`, `threshold`, `max_distance`; and the outputs of GUIDED_OUTPUTS [n0], info int32 [8], with `mutual` also
+    cnn1 int32 [n1] and matches1 int64 [n1].  One asynchronous call; returns (workspace, table): keep both alive until the stream has passed."""
+    rows = []
+    for it in items:
+        a, b = it["a"], it["b"]
+        if a.dtype != torch.float32 or b.dtype != torch.float32 or a.dim() != 2 or b.dim() != 2 or a.stride(1) != 1 or b.stride(1) != 1:
+            raise GimsHipError("guided_match: a / b must be float32 [n, d] with contiguous rows")
+        n0, n1 = int(a.shape[0]), int(b.shape[0])
+        for k, n in ((it["kpts0"], n0), (it["kpts1"], n1)):
+            if k.dtype != torch.float32 or not k.is_contiguous() or tuple(k.shape) != (n, 2):
+                raise GimsHipError("guided_match: kpts0 / kpts1 must be contiguous float32 [n0, 2] / [n1, 2]")
+        if it["model"].dtype != torch.float32 or it["model"].numel() != 9 or not it["model"].is_contiguous():
+            raise GimsHipError("guided_match: model must be 9 contiguous float32")
+        kind = verify_model(it.get("kind", "fundamental"))
+        mutual = bool(it.get("mutual", True))
+        for name, dt in GUIDED_OUTPUTS + ((("cnn1", torch.int32), ("matches1", torch.int64)) if mutual else ()):
+            n = n1 if name in ("cnn1", "matches1") else n0
+            if it[name].dtype != dt or it[name].numel() < n or not it[name].is_contiguous():
+                raise GimsHipError(f"guided_match: output {name} must be a contiguous {dt} tensor of {n} elements")
+        if it["info"].dtype != torch.int32 or it["info"].numel() < 8:
+            raise GimsHipError("guided_match: info must be int32 [8]")
+        for name, dt in (("prior", torch.int64), ("prior_mask", torch.uint8), ("prior_scores", torch.float32)):
+            t = it.get(name)
+            if t is not None and (t.dtype != dt or t.numel() != n0 or not t.is_contiguous()):
+                raise GimsHipError(f"guided_match: {name} must be a contiguous {dt} tensor of n0 elements")
+        if it.get("ok") is not None and it["ok"].dtype != torch.float32:
+            raise GimsHipError("guided_match: ok must be a float32 tensor")
+        lda, ldb = (a.stride(0) if n0 > 1 else a.shape[1]), (b.stride(0) if n1 > 1 else b.shape[1])
+        rows.append(dict(it, lda=lda, ldb=ldb, n0=n0, n1=n1, d=int(a.shape[1]), kind=kind, mutual=mutual, thresh=it.get("thresh", 3.0),
+                         threshold=it.get("threshold", 0.8), max_distance=it.get("max_distance"), reserved=0))
+    need = guided_layout([(r["n0"], r["n1"], r["mutual"]) for r in rows], flags)["bytes"]
+    if work is None or work.numel() * work.element_size() < need:
+        work = torch.empty(need, dtype=torch.uint8, device=items[0]["a"].device)
+    tab = guided_table(rows)
+    run_ops(make_ops([op_guided_match(tab, work, work.numel() * work.element_size(), flags)]))
+    return work, tab
 
 
 # ------------------------------------------------------------------------------------------------ CAR-HyNet ops (NHWC f32)

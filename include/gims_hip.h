@@ -847,7 +847,72 @@ int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t
  * work_bytes below what the call needs.  What the descriptors and the index lists HOLD is not trusted.
  * The launches: the uploads of the table and of the image of every 32 pooled rows, three memset nodes, maxabs (without a given scale),
  * quantise, vote, select, count, scan, fill.  They are fixed by N, the m_i, D and the flag, never by device data.  No host synchronisation;
- * capturable.  Integer atomics only. */
+ * capturable.  Integer atomics only.
+ *
+ * GIMS_AUX_GUIDED_MATCH is the eleventh, for the same reason.  GUIDED MATCHING runs the descriptor match of gims_nn_match
+ * again between the two keypoint sets of a verified pair, counting only partners that agree with the pair's model, and adds what it finds
+ * to the matches that are already fixed.  This library's own specification: no part of the reference does this.  kernels: gd_*_kernel and
+ * the gated instances of the nn_* bodies, gims_amd/csrc/nn.hip; tests/guided_ref.py is the restatement.
+ *   p[0] table    HOST int64 [n_pairs][GIMS_GUIDED_TABLE_WORDS], 8-byte aligned, read during the call only.  The words of one pair:
+ *                  0 A, 1 B          const float* DEVICE, [n0][d] / [n1][d], point-major, gims_nn_match's pitch and alignment rules
+ *                  2 lda, 3 ldb      row pitches in floats     4 n0, 5 n1 (1 .. 32768 each; n1 = 1 is served)     6 d (a multiple of 32 in 32 .. 512)
+ *                  7 kpts0, 8 kpts1  const float* DEVICE [n0][2] / [n1][2], pixels
+ *                  9 model           const float* DEVICE [9], row-major       10 kind: GIMS_VERIFY_MODEL_HOMOGRAPHY (x1 ~ H x0) or _FUNDAMENTAL
+ *                 11 ok              const float* DEVICE, one word (the ok column of a gims_verify_pairs record), or 0
+ *                 12 prior           const int64_t* DEVICE [n0] or 0;  13 prior_mask const uint8_t* DEVICE [n0] or 0;  14 prior_scores const
+ *                                    float* DEVICE [n0] or 0 (13 and 14 are read with a prior only)
+ *                 15 mutual          non-zero adds the mutual test and the outputs cnn1 and matches1
+ *                 16 nn1, 17 nn2 int32 [n0];  18 d1, 19 d2, 20 ratio float32 [n0];  21 n_admissible int32 [n0];  22 matches0 int64 [n0];
+ *                 23 scores0 float32 [n0];  24 added0 uint8 [n0];  25 cnn1 int32 [n1] and 26 matches1 int64 [n1] (read with mutual only);
+ *                 27 info int32 [8]  -- all DEVICE, caller-owned, required
+ *                 28 thresh, 29 ratio, 30 max_distance: the BITS of a float32 in the low half of the word (pixels, finite, > 0; the ratio
+ *                                    threshold; +inf for none)        31 reserved, 0
+ *   p[1] work     device scratch, 256-byte aligned.  p[2] .. p[5] NULL (reserved).
+ *   i = {n_pairs, flags (GIMS_NN_EXHAUSTIVE or 0), work_bytes, 0, 0, 0 (the form word, read first)}     f = {0, 0} (reserved)
+ *   work_bytes: every region on 256 bytes (al256).  P pairs; Q problems (nx, ny): (n0, n1) per pair and with mutual also (n1, n0).  As in
+ *   gims_nn_match, want = ceil(512 / sum over the problems of ceil(nx / 128)) clamped to 1 .. 8 and per problem tiles = ceil(ny / 128),
+ *   tiles_per = ceil(tiles / min(want, tiles)), csplit = ceil(tiles / tiles_per).  The call needs
+ *     al256(160 Q) + al256(200 P) + al256(16 P) + al256(48 Q) + al256(232 P) + al256(16 P) + al256(4 sum n1)
+ *     + per pair     al256(8 n0) + al256(8 n1) + al256(4 n0) + al256(4 n1) + al256(32 n0) + al256(32 n1) + al256(n0)
+ *     + per problem  al256(4 nx), for the (n1, n0) problem also 3 al256(4 nx), and without GIMS_NN_EXHAUSTIVE 2 al256(64 nx csplit) +
+ *                    al256(16 nx csplit)
+ *   bytes; hip.guided_layout in gims_amd/hip.py restates it.
+ * All of it is decided in float64, every product and every sum rounded on its own (no contraction), division correctly rounded; the float32
+ * inputs are widened first.
+ *   1 Has a model.  Iff ok is 0 (no pointer) or *ok != 0, and all nine entries of the model are finite.  Without a model no row searches:
+ *     the output is the fixed rows of 2 alone and info[5] = 1.
+ *   2 Fixed rows, taken columns.  Row i CLAIMS column prior[i] iff a prior is given, the mask is absent or mask[i] != 0, and 0 <= prior[i] <
+ *     n1.  Row i is FIXED iff it is the lowest row that claims its column (the integer minimum over the claimants).  A claimed value other
+ *     than -1 outside 0 .. n1 - 1 is counted in info[3] and never used as an index (a row the mask switches off is not read).  A claimant
+ *     that lost its column is counted in info[4], is not fixed and searches like an unmatched row.  The column of a fixed row is TAKEN.
+ *   3 Per-row words, computed ONCE by a prologue launch and read by every later pass.
+ *     fundamental, row i of A (u, v):  la = (F00 u + F01 v) + F02, lb and lc likewise from rows 1 and 2 of F, g = la^2 + lb^2
+ *     fundamental, row j of B (u', v'): ma = (F00 u' + F10 v') + F20, mb = (F01 u' + F11 v') + F21, h = ma^2 + mb^2
+ *     homography, row i:  p = H (u, v, 1) in the same order of operations, a = (px / pw, py / pw); valid iff fabs(pw) > 0
+ *     homography, row j:  q = C (u', v', 1), C the transposed matrix of cofactors of H (C00 = H11 H22 - H12 H21, C01 = H02 H21 - H01 H22,
+ *       C02 = H01 H12 - H02 H11, C10 = H12 H20 - H10 H22, C11 = H00 H22 - H02 H20, C12 = H02 H10 - H00 H12, C20 = H10 H21 - H11 H20,
+ *       C21 = H01 H20 - H00 H21, C22 = H00 H11 - H01 H10; no division by the determinant), b = (qx / qw, qy / qw); valid iff fabs(qw) > 0
+ *   4 Admissible(i, j), symmetric by construction; both directions use this one definition.  Neither i fixed nor j taken, and
+ *     fundamental: n = (la u' + lb v') + lc; g > 0, h > 0, n^2 <= t^2 g and n^2 <= t^2 h (the distance of each point to the other's epipolar
+ *       line), t^2 = double(thresh)^2
+ *     homography: both rows valid, (ax - u')^2 + (ay - v')^2 <= t^2 and (bx - u)^2 + (by - v)^2 <= t^2
+ *     A comparison with a NaN is false.  n_admissible[i] is the count over all j.
+ *   5 Two nearest.  S(i, j) is gims_nn_match's exact squared distance.  nn1 / nn2 are the two nearest ADMISSIBLE columns by (S, j).  One
+ *     admissible column: nn2 = -1, d2 = +inf, ratio 0.  None: nn1 = -1, d1 = +inf, ratio NaN.  d1, d2, ratio float32 as in gims_nn_match.
+ *   6 Match.  match = ratio < threshold && d1 <= max_distance, with mutual also cnn1[nn1[i]] == i (cnn1[j] = j's nearest admissible row
+ *     of A, -1 when it has none).  A searching row: matches0 = match ? nn1 : -1, scores0 = match ? 1 - ratio : 0, added0 = match.  A fixed
+ *     row: matches0 = prior[i], added0 = 0, scores0 = prior_scores[i] when given, else 1; it is not searched: nn1 = prior[i], nn2 = -1,
+ *     d1 = d2 = +inf, ratio = NaN, n_admissible = 0.  With mutual matches1 is the inverse of matches0, fixed rows included: one-to-one.
+ *   7 info = {rows of A re-solved exhaustively, rows of B re-solved exhaustively, n_fixed, n_bad_prior, n_dup_prior, no_model, n_added, 0}.
+ * A row's outputs are bit-identical whichever way it went, and under GIMS_NN_EXHAUSTIVE.  The certificate is gims_nn_match's with one rule
+ * added: a row all of whose candidate lists are short has every admissible column listed and is certified without the inequality.
+ * GIMS_EINVAL before any HIP call, each with a message naming guided_match: the size and alignment rules of gims_nn_match (with n1 >= 1); an
+ * unknown kind; a thresh that is not finite and > 0; a max_distance that is NaN or negative; a NULL required pointer; a non-zero reserved
+ * word (i[3], i[4], p[2] .. p[5], f, word 31, the high halves of words 28 .. 30); unknown flags; a workspace below work_bytes' need.  What
+ * the arrays HOLD is never trusted.
+ * The launches: four table uploads, three memset nodes, claim, prologue, norms, candidate and refine (not under GIMS_NN_EXHAUSTIVE),
+ * exhaustive, finish -- each ONE launch for all directions of all pairs, fixed by the sizes and flags, never by device data.  No host
+ * synchronisation; capturable.  Integer atomics only. */
 #define GIMS_OP_AUX 2
 #define GIMS_AUX_SPLIT_SPL32 0
 #define GIMS_AUX_SAGE_MEAN_SPLIT 1
@@ -888,6 +953,8 @@ int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t
 #define GIMS_PAIRS_MAX_D 1024
 #define GIMS_PAIRS_QUERY_TILE 128
 #define GIMS_PAIRS_SCALE_GIVEN 1
+#define GIMS_AUX_GUIDED_MATCH 18
+#define GIMS_GUIDED_TABLE_WORDS 32
 typedef struct gims_aux_args { int32_t fn, reserved; const void* p[6]; int64_t i[6]; float f[2]; } gims_aux_args;
 typedef struct gims_op { int32_t kind; int32_t reserved; union { gims_linear_args lin; gims_attn_args att; gims_aux_args aux; } u; } gims_op;
 int gims_run_ops(const gims_op* ops /* HOST */, int32_t n_ops, void* stream);
