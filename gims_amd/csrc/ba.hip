@@ -58,8 +58,8 @@ struct BaOut {
   int32_t *cg_used, *list_tmp, *cursor;                        // the conjugate-gradient form only, from here on (rhs is its x, S stays NULL)
   double *cg_res, *y, *slot_rec, *vr, *vz, *vp, *vq;
 };
-static size_t ba_layout(void* base, int64_t T, int64_t n_obs, int64_t n_images, int64_t iters, int64_t n_free, BaOut& w) {
-  WsLayout L(base);
+static size_t ba_layout(void* base, int64_t T, int64_t n_obs, int64_t n_images, int64_t iters, int64_t n_free, BaOut& w, WsRecord* rec = nullptr) {
+  WsLayout L(base, rec);
   const size_t n = (size_t)(6 * n_free);
   w.xyz = L.take<double>((size_t)T * 3);
   w.cams = L.take<double>((size_t)n_images * BA_CAM);
@@ -68,7 +68,8 @@ static size_t ba_layout(void* base, int64_t T, int64_t n_obs, int64_t n_images, 
   w.history = L.take<double>((size_t)(iters + 1) * 2);
   w.taken = L.take<uint8_t>((size_t)iters);
   w.counters = L.take<int32_t>(BA_COUNTERS);
-  w.st = (BaState*)L.take<double>(32);                         // scratch from here on
+  L.scratch_from_here();
+  w.st = (BaState*)L.take<double>(32);
   w.slot_of = L.take<int32_t>((size_t)n_images);
   w.slot_cam = L.take<int32_t>((size_t)n_free);
   w.slot_ptr = L.take<int32_t>((size_t)n_free + 1);
@@ -659,8 +660,8 @@ constexpr int BA_PCG_MAX_ITERS = GIMS_BA_PCG_MAX_CG_ITERS;
 constexpr int BA_SORT_SPLIT = 16;                              // workgroups that share the ordering of one slot's list, 256 entries at a time
 constexpr int BA_SLOT_REC = 42;                                // per slot: U* (the upper triangle by rows, 21) | L of M_s = L L^T (the lower triangle by rows, 21)
 
-static size_t ba_pcg_layout(void* base, int64_t T, int64_t n_obs, int64_t n_images, int64_t iters, int64_t n_free, BaOut& w) {
-  WsLayout L(base);
+static size_t ba_pcg_layout(void* base, int64_t T, int64_t n_obs, int64_t n_images, int64_t iters, int64_t n_free, BaOut& w, WsRecord* rec = nullptr) {
+  WsLayout L(base, rec);
   w.xyz = L.take<double>((size_t)T * 3);
   w.cams = L.take<double>((size_t)n_images * BA_CAM);
   w.obs_error = L.take<float>((size_t)n_obs);
@@ -670,7 +671,8 @@ static size_t ba_pcg_layout(void* base, int64_t T, int64_t n_obs, int64_t n_imag
   w.counters = L.take<int32_t>(BA_COUNTERS);
   w.cg_used = L.take<int32_t>((size_t)iters);
   w.cg_res = L.take<double>((size_t)iters);
-  w.st = (BaState*)L.take<double>(32);                         // scratch from here on
+  L.scratch_from_here();
+  w.st = (BaState*)L.take<double>(32);
   w.slot_of = L.take<int32_t>((size_t)n_images);
   w.slot_cam = L.take<int32_t>((size_t)n_free);
   w.slot_ptr = L.take<int32_t>((size_t)n_free + 1);
@@ -1150,8 +1152,9 @@ struct BaFocal {                                               // what the focal
   double *obs_frec, *img_part, *img_q, *cvec, *grec, *gx, *gr, *gz, *gp, *gq;
 };
 
-static size_t ba_focal_layout(void* base, int64_t T, int64_t n_obs, int64_t n_images, int64_t iters, int64_t n_free, int64_t n_groups, BaOut& w, BaFocal& f) {
-  WsLayout L(base);
+static size_t ba_focal_layout(void* base, int64_t T, int64_t n_obs, int64_t n_images, int64_t iters, int64_t n_free, int64_t n_groups, BaOut& w, BaFocal& f,
+                              WsRecord* rec = nullptr) {
+  WsLayout L(base, rec);
   w.xyz = L.take<double>((size_t)T * 3);
   w.cams = L.take<double>((size_t)n_images * BA_CAM);
   w.obs_error = L.take<float>((size_t)n_obs);
@@ -1163,7 +1166,8 @@ static size_t ba_focal_layout(void* base, int64_t T, int64_t n_obs, int64_t n_im
   w.cg_res = L.take<double>((size_t)iters);
   f.scale = L.take<double>((size_t)n_groups);
   f.group_obs = L.take<int32_t>((size_t)n_groups);
-  w.st = (BaState*)L.take<double>(32);                         // scratch from here on
+  L.scratch_from_here();
+  w.st = (BaState*)L.take<double>(32);
   w.slot_of = L.take<int32_t>((size_t)n_images);
   w.slot_cam = L.take<int32_t>((size_t)n_images);              // the image of every list: the slots, then the other listed images
   w.slot_ptr = L.take<int32_t>((size_t)n_images + 1);
@@ -1717,6 +1721,37 @@ static int ba_focal_launches(const BaArgs& a, const BaFocal& f, unsigned g_all, 
   return GIMS_OK;
 }
 
+// the sizes that lay the buffer out and come as op arguments: the op and gims_aux_layout refuse the same values
+static int ba_check_sizes(int64_t T, int64_t n_obs, int64_t n_images) {
+  GIMS_CHECK_ARG(T >= 0 && T <= (1 << 30), "bundle_adjust: T = %lld is out of range (0 .. 2^30)", (long long)T);
+  GIMS_CHECK_ARG(n_obs >= 0 && n_obs <= (1 << 30), "bundle_adjust: n_obs = %lld is out of range (0 .. 2^30)", (long long)n_obs);
+  GIMS_CHECK_ARG(n_images >= 0 && n_images <= (1 << 24), "bundle_adjust: n_images = %lld is out of range (0 .. 2^24)", (long long)n_images);
+  return GIMS_OK;
+}
+
+// gims_aux_layout for the three forms: sizes = {T, n_obs, n_images, iters, n_free}, the focal form adds n_groups.  iters, n_free and n_groups
+// have the bounds of ba_aux below (the op counts n_free from mode and n_groups from group, so each is at most n_images there).
+static int ba_aux_layout(const int64_t* sizes, int n, WsRecord& rec, const int form) {
+  const bool pcg = form != 0, focal = form == 2;
+  GIMS_CHECK_ARG(n == (focal ? 6 : 5), "bundle_adjust: the layout takes %d sizes {T, n_obs, n_images, iters, n_free%s}, not %d", focal ? 6 : 5,
+                 focal ? ", n_groups" : "", n);
+  const int64_t T = sizes[0], n_obs = sizes[1], n_images = sizes[2], iters = sizes[3], n_free = sizes[4], n_groups = focal ? sizes[5] : 0;
+  if (const int rc = ba_check_sizes(T, n_obs, n_images)) return rc;
+  GIMS_CHECK_ARG(iters >= 0 && iters <= 255, "bundle_adjust: iters = %lld is out of range (0 .. 255)", (long long)iters);
+  GIMS_CHECK_ARG(n_free >= 0 && n_free <= (pcg ? BA_PCG_MAX_FREE : BA_MAX_FREE), "bundle_adjust: %lld free cameras, at most %d", (long long)n_free,
+                 pcg ? BA_PCG_MAX_FREE : BA_MAX_FREE);
+  GIMS_CHECK_ARG(n_groups >= 0 && n_groups <= (1 << 24), "bundle_adjust: n_groups = %lld is out of range (0 .. 2^24)", (long long)n_groups);
+  BaOut w;
+  BaFocal f;
+  rec.bytes = focal ? ba_focal_layout(nullptr, T, n_obs, n_images, iters, n_free, n_groups, w, f, &rec)
+              : pcg ? ba_pcg_layout(nullptr, T, n_obs, n_images, iters, n_free, w, &rec)
+                    : ba_layout(nullptr, T, n_obs, n_images, iters, n_free, w, &rec);
+  return GIMS_OK;
+}
+int bundle_adjust_aux_layout(const int64_t* sizes, int n, WsRecord& rec) { return ba_aux_layout(sizes, n, rec, 0); }
+int bundle_adjust_pcg_aux_layout(const int64_t* sizes, int n, WsRecord& rec) { return ba_aux_layout(sizes, n, rec, 1); }
+int bundle_adjust_focal_aux_layout(const int64_t* sizes, int n, WsRecord& rec) { return ba_aux_layout(sizes, n, rec, 2); }
+
 // GIMS_AUX_BUNDLE_ADJUST, GIMS_AUX_BUNDLE_ADJUST_PCG and GIMS_AUX_BUNDLE_ADJUST_FOCAL of gims_run_ops (include/gims_hip.h): every argument
 // check precedes the first HIP call.  form: 0 dense, 1 conjugate gradients, 2 conjugate gradients with focal groups.
 static int ba_aux(const gims_aux_args& x, hipStream_t st, const int form) {
@@ -1726,9 +1761,7 @@ static int ba_aux(const gims_aux_args& x, hipStream_t st, const int form) {
   // i[5] is where a later form of this function (a blocked or iterative reduced solve) would be selected: it is read FIRST
   GIMS_CHECK_ARG(x.i[5] == 0, "gims_run_ops: unknown auxiliary function form: bundle_adjust with i[5] = %lld (i[5] is reserved and must be 0)",
                  (long long)x.i[5]);
-  GIMS_CHECK_ARG(T >= 0 && T <= (1 << 30), "bundle_adjust: T = %lld is out of range (0 .. 2^30)", (long long)T);
-  GIMS_CHECK_ARG(n_obs >= 0 && n_obs <= (1 << 30), "bundle_adjust: n_obs = %lld is out of range (0 .. 2^30)", (long long)n_obs);
-  GIMS_CHECK_ARG(n_images >= 0 && n_images <= (1 << 24), "bundle_adjust: n_images = %lld is out of range (0 .. 2^24)", (long long)n_images);
+  if (const int rc = ba_check_sizes(T, n_obs, n_images)) return rc;
   GIMS_CHECK_ARG(N >= 0 && N <= (1 << 30), "bundle_adjust: N = %lld is out of range (0 .. 2^30)", (long long)N);
   GIMS_CHECK_ARG(iters >= 0 && iters <= 255, "bundle_adjust: iters = %lld is out of range (0 .. 255)", (long long)iters);
   GIMS_CHECK_ARG(huber - huber == 0.f && huber >= 0.f, "bundle_adjust: huber = %g must be finite and >= 0", (double)huber);

@@ -5,6 +5,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <vector>
+
 #include "../../include/gims_hip.h"
 
 namespace gims {
@@ -135,12 +137,25 @@ static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 // Caller-allocated scratch workspaces.  Every region starts on a 256-byte boundary.  Each workspace has ONE layout routine that walks a
 // WsLayout through its takes; the size query runs it on a null base (take returns nullptr, bytes() is the answer) and the launch runs the
 // same routine on the caller's buffer, then compares bytes() with the size it was given before anything is enqueued.
+// With a WsRecord attached the walk also writes down the offset of every take, and where the scratch begins: gims_aux_layout reports that.
 static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+struct WsRecord {
+  std::vector<size_t> offsets;   // of every take, in order
+  size_t n_outputs = 0;          // the index of the first scratch take (0: the buffer is scratch only)
+  size_t bytes = 0;              // the total: set by the op's xx_aux_layout
+};
 struct WsLayout {
   char* base;          // nullptr: sizing only
   size_t off = 0;
-  explicit WsLayout(void* b) : base((char*)b) {}
-  template <typename T> T* take(size_t count) { const size_t o = off; off += al256(sizeof(T) * count); return base ? (T*)(base + o) : nullptr; }
+  WsRecord* rec;       // nullptr: nothing is written down
+  explicit WsLayout(void* b, WsRecord* r = nullptr) : base((char*)b), rec(r) {}
+  template <typename T> T* take(size_t count) {
+    const size_t o = off;
+    off += al256(sizeof(T) * count);
+    if (rec) rec->offsets.push_back(o);
+    return base ? (T*)(base + o) : nullptr;
+  }
+  void scratch_from_here() { if (rec) rec->n_outputs = rec->offsets.size(); }      // the takes so far are the op's outputs
   size_t bytes() const { return off; }     // the total so far: also the offset of the next take
 };
 // An integer knob from the environment: its value, or dflt when the variable is not set.  Every call reads the environment: a knob that is
@@ -174,24 +189,33 @@ int mlp_fused_launch(const gims_linear_args& a, hipStream_t s);
 int sift_describe_aux(const gims_aux_args& x, hipStream_t st);
 // nms.hip: GIMS_AUX_DIOU_NMS, likewise reached through gims_run_ops only
 int diou_nms_aux(const gims_aux_args& x, hipStream_t st);
+int diou_nms_aux_layout(const int64_t* sizes, int n, WsRecord& rec);      // gims_aux_layout: the sizes as include/gims_hip.h lists them
 // features.hip: GIMS_AUX_ASSEMBLE_ROWS, likewise
 int assemble_rows_aux(const gims_aux_args& x, hipStream_t st);
 // tracks.hip: GIMS_AUX_BUILD_TRACKS, likewise
 int build_tracks_aux(const gims_aux_args& x, hipStream_t st);
+int build_tracks_aux_layout(const int64_t* sizes, int n, WsRecord& rec);      // gims_aux_layout: the sizes as include/gims_hip.h lists them
 // triangulate.hip: GIMS_AUX_TRIANGULATE_TRACKS, likewise
 int triangulate_tracks_aux(const gims_aux_args& x, hipStream_t st);
+int triangulate_tracks_aux_layout(const int64_t* sizes, int n, WsRecord& rec);      // gims_aux_layout: the sizes as include/gims_hip.h lists them
 // resect.hip: GIMS_AUX_RESECT_IMAGES, likewise
 int resect_images_aux(const gims_aux_args& x, hipStream_t st);
+int resect_images_aux_layout(const int64_t* sizes, int n, WsRecord& rec);      // gims_aux_layout: the sizes as include/gims_hip.h lists them
 // ba.hip: GIMS_AUX_BUNDLE_ADJUST, likewise
 int bundle_adjust_aux(const gims_aux_args& x, hipStream_t st);
+int bundle_adjust_aux_layout(const int64_t* sizes, int n, WsRecord& rec);      // gims_aux_layout: the sizes as include/gims_hip.h lists them
 // ba.hip: GIMS_AUX_BUNDLE_ADJUST_PCG, likewise
 int bundle_adjust_pcg_aux(const gims_aux_args& x, hipStream_t st);
+int bundle_adjust_pcg_aux_layout(const int64_t* sizes, int n, WsRecord& rec);      // gims_aux_layout: the sizes as include/gims_hip.h lists them
 // ba.hip: GIMS_AUX_BUNDLE_ADJUST_FOCAL, likewise
 int bundle_adjust_focal_aux(const gims_aux_args& x, hipStream_t st);
+int bundle_adjust_focal_aux_layout(const int64_t* sizes, int n, WsRecord& rec);      // gims_aux_layout: the sizes as include/gims_hip.h lists them
 // pairs.hip: GIMS_AUX_SELECT_PAIRS, likewise
 int select_pairs_aux(const gims_aux_args& x, hipStream_t st);
+int select_pairs_aux_layout(const int64_t* sizes, int n, WsRecord& rec);      // gims_aux_layout: the sizes as include/gims_hip.h lists them
 // nn.hip: GIMS_AUX_GUIDED_MATCH, likewise
 int guided_match_aux(const gims_aux_args& x, hipStream_t st);
+int guided_match_aux_layout(const int64_t* sizes, int n, WsRecord& rec);      // gims_aux_layout: the sizes as include/gims_hip.h lists them
 
 // sinkhorn2d.hip: the 2-D on-chip Sinkhorn (all iterations in one launch; see that file's header)
 struct OtR2Host { const float* z; int64_t ld; int n, m; float* u; float* v; float* status; float norm, log_mu_bin, log_nu_bin; };

@@ -408,6 +408,37 @@ extern "C" int gims_run_ops(const gims_op* ops, int32_t n_ops, void* stream) {
   return GIMS_OK;
 }
 
+// Where the layout routine of an auxiliary function puts every region of its caller-allocated buffer: the routine the launch runs, walked on a
+// null base with a WsRecord attached.  Host arithmetic only: no HIP call.
+extern "C" int gims_aux_layout(int32_t fn, const int64_t* sizes, int32_t n_sizes, int64_t* offsets, int32_t capacity, int32_t* n_regions,
+                               int32_t* n_outputs, size_t* bytes) {
+  using namespace gims;
+  GIMS_CHECK_ARG(sizes && n_sizes >= 0 && capacity >= 0 && (offsets || capacity == 0) && n_regions && n_outputs && bytes, "gims_aux_layout: bad arguments");
+  int (*layout)(const int64_t*, int, WsRecord&) = fn == GIMS_AUX_DIOU_NMS             ? diou_nms_aux_layout
+                                                  : fn == GIMS_AUX_BUILD_TRACKS       ? build_tracks_aux_layout
+                                                  : fn == GIMS_AUX_TRIANGULATE_TRACKS ? triangulate_tracks_aux_layout
+                                                  : fn == GIMS_AUX_RESECT_IMAGES      ? resect_images_aux_layout
+                                                  : fn == GIMS_AUX_BUNDLE_ADJUST      ? bundle_adjust_aux_layout
+                                                  : fn == GIMS_AUX_BUNDLE_ADJUST_PCG  ? bundle_adjust_pcg_aux_layout
+                                                  : fn == GIMS_AUX_BUNDLE_ADJUST_FOCAL ? bundle_adjust_focal_aux_layout
+                                                  : fn == GIMS_AUX_SELECT_PAIRS       ? select_pairs_aux_layout
+                                                  : fn == GIMS_AUX_GUIDED_MATCH       ? guided_match_aux_layout
+                                                                                      : nullptr;
+  GIMS_CHECK_ARG(layout, "gims_aux_layout: auxiliary function %d is unknown or has no buffer that a layout routine carves", fn);
+  WsRecord rec;
+  if (layout(sizes, n_sizes, rec) != GIMS_OK) {                // the op's own message, behind this function's name
+    const std::string why(g_err);
+    set_error("gims_aux_layout: %s", why.c_str());
+    return GIMS_EINVAL;
+  }
+  *n_regions = (int32_t)rec.offsets.size(), *n_outputs = (int32_t)rec.n_outputs, *bytes = rec.bytes;
+  if (!offsets) return GIMS_OK;                                // the counts and the bytes only
+  GIMS_CHECK_ARG((size_t)capacity >= rec.offsets.size(), "gims_aux_layout: function %d: capacity = %d is below the %zu regions of these sizes", fn, capacity,
+                 rec.offsets.size());
+  for (size_t r = 0; r < rec.offsets.size(); ++r) offsets[r] = (int64_t)rec.offsets[r];
+  return GIMS_OK;
+}
+
 // The same replay with a HIP event recorded on `stream` before the first op and after every op (events[0 .. n_ops]): the
 // per-kernel durations of the production path, measured on the stream the kernels are launched on.
 extern "C" int gims_run_ops_timed(const gims_op* ops, int32_t n_ops, void* stream, void* const* events) {

@@ -24,7 +24,7 @@ constexpr int NMS_LDS_STATUS = 32768;     // images of up to this many keypoints
 constexpr int NMS_CELL_SLACK = 64;        // an image of m keypoints may use up to 2 m + NMS_CELL_SLACK grid cells
 enum : uint8_t { NMS_UNDECIDED = 0, NMS_KEPT = 1, NMS_SUPPRESSED = 2 };
 
-// The workspace of GIMS_AUX_DIOU_NMS (the formula of include/gims_hip.h; hip.diou_nms_workspace_bytes mirrors it)
+// The workspace of GIMS_AUX_DIOU_NMS (the formula of include/gims_hip.h; gims_aux_layout reports this routine's offsets)
 struct NmsWs {
   float4* box;        // [n] x1, y1, x2, y2 of position j
   float4* aux;        // [n] area, cx, cy, row (int bits)
@@ -258,11 +258,27 @@ __global__ __launch_bounds__(NMS_THREADS) void diou_nms_kernel(const float* __re
 
 }  // namespace
 
+// the sizes that lay the workspace out: the op and gims_aux_layout refuse the same values
+static int nms_check_sizes(int64_t n, int64_t n_images) {
+  GIMS_CHECK_ARG(n >= 0 && n <= (1 << 29), "diou_nms: n = %lld is out of range (0 .. 2^29)", (long long)n);
+  GIMS_CHECK_ARG(n_images >= 1 && n_images <= (1 << 20), "diou_nms: n_images = %lld (1 .. 2^20)", (long long)n_images);
+  return GIMS_OK;
+}
+
+// gims_aux_layout for GIMS_AUX_DIOU_NMS: sizes = {n, n_images}, the workspace
+int diou_nms_aux_layout(const int64_t* sizes, int n, WsRecord& rec) {
+  GIMS_CHECK_ARG(n == 2, "diou_nms: the layout takes 2 sizes {n, n_images}, not %d", n);
+  if (const int rc = nms_check_sizes(sizes[0], sizes[1])) return rc;
+  WsLayout L(nullptr, &rec);
+  nms_layout(L, sizes[0], sizes[1]);
+  rec.bytes = L.bytes();
+  return GIMS_OK;
+}
+
 int diou_nms_aux(const gims_aux_args& x, hipStream_t st) {
   const int64_t n = x.i[0], n_images = x.i[1], h = x.i[2], w = x.i[3], work_bytes = x.i[4];
   const float radius = x.f[0], thr = x.f[1];
-  GIMS_CHECK_ARG(n >= 0 && n <= (1 << 29), "diou_nms: n = %lld is out of range (0 .. 2^29)", (long long)n);
-  GIMS_CHECK_ARG(n_images >= 1 && n_images <= (1 << 20), "diou_nms: n_images = %lld (1 .. 2^20)", (long long)n_images);
+  if (const int rc = nms_check_sizes(n, n_images)) return rc;
   GIMS_CHECK_ARG(h >= 1 && w >= 1 && h <= INT32_MAX && w <= INT32_MAX, "diou_nms: extent %lld x %lld (height and width are at least 1)", (long long)h,
                  (long long)w);
   GIMS_CHECK_ARG(isfinite(radius) && radius >= 0.f, "diou_nms: radius = %g (finite, > 0 for fixed boxes, 0 for boxes from the size)", (double)radius);

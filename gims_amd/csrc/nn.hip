@@ -637,13 +637,17 @@ __global__ __launch_bounds__(256) void gd_finish_kernel(const GdPairDev* __restr
 
 // ---------------------------------------------------------------------------------------------- host
 // guided: the rules of GIMS_AUX_GUIDED_MATCH, where a row may have one admissible column or none and n1 = 1 (or n0 = 1 with mutual) is served
+static const char* nn_rows_why(int64_t n0, int64_t n1, bool mutual, bool guided) {      // the row counts, which are what lays the workspace out
+  if (guided && (n0 < 1 || n1 < 1)) return "needs n0 >= 1 and n1 >= 1";
+  if (!guided && (n0 < 1 || n1 < 2)) return "needs n0 >= 1 and n1 >= 2 (a second neighbour in B)";
+  if (!guided && mutual && n0 < 2) return "the mutual test needs n0 >= 2 (a second neighbour in A)";
+  if (n0 > NN_MAX_N || n1 > NN_MAX_N) return "more than 32768 rows";
+  return nullptr;
+}
 static bool nn_pair_ok(const gims_nn_pair& p, int i, bool report, bool guided = false) {
   const char* why = nullptr;
   if (p.d < 32 || p.d > 64 * NN_MAXT || p.d % 32 != 0) why = "d must be a multiple of 32 in [32, 512]";
-  else if (guided && (p.n0 < 1 || p.n1 < 1)) why = "needs n0 >= 1 and n1 >= 1";
-  else if (!guided && (p.n0 < 1 || p.n1 < 2)) why = "needs n0 >= 1 and n1 >= 2 (a second neighbour in B)";
-  else if (!guided && p.mutual && p.n0 < 2) why = "the mutual test needs n0 >= 2 (a second neighbour in A)";
-  else if (p.n0 > NN_MAX_N || p.n1 > NN_MAX_N) why = "more than 32768 rows";
+  else if ((why = nn_rows_why(p.n0, p.n1, p.mutual != 0, guided))) ;
   else if (!p.a || !p.b || !p.nn1 || !p.nn2 || !p.d1 || !p.d2 || !p.ratio || !p.match || !p.matches0 || !p.scores0 || !p.info) why = "null pointer";
   else if (p.mutual && !p.matches1) why = "null matches1 with mutual set";
   else if (p.lda < p.d || p.ldb < p.d || p.lda % 4 != 0 || p.ldb % 4 != 0) why = "row pitch below d or not a multiple of 4";
@@ -719,14 +723,47 @@ static NnWs nn_layout(const gims_nn_pair* pairs, int n_pairs, int flags, WsLayou
   return w;
 }
 
-// GIMS_AUX_GUIDED_MATCH of gims_run_ops (include/gims_hip.h): every argument check precedes the first HIP call.  The workspace is nn_layout's
-// for the same sizes (match = added0), then the regions of the gate.
+// The workspace of GIMS_AUX_GUIDED_MATCH: nn_layout's for the same sizes (match = added0), then the regions of the gate.  probs and pd are
+// filled as nn_layout fills them, on a null base too.
+struct GdWs {
+  NnWs nn;
+  GdProb* dgates;
+  GdPairDev* dgpairs;
+  int32_t *cnt, *claim;
+  size_t claims;
+  std::vector<double*> wa, wb;       // per pair
+  std::vector<uint8_t*> fixed;       // per pair
+  std::vector<int32_t*> lcnt;        // per problem (null with GIMS_NN_EXHAUSTIVE)
+};
+static GdWs gd_layout(const gims_nn_pair* pairs, int np, int flags, WsLayout& L, std::vector<NnProb>& probs, std::vector<NnPairDev>& pd) {
+  const bool forced = (flags & GIMS_NN_EXHAUSTIVE) != 0;
+  GdWs w;
+  w.nn = nn_layout(pairs, np, flags, L, &probs, &pd);
+  w.dgates = L.take<GdProb>(probs.size());
+  w.dgpairs = L.take<GdPairDev>((size_t)np);
+  w.cnt = L.take<int32_t>(4 * (size_t)np);
+  w.claims = 0;
+  for (int i = 0; i < np; ++i) w.claims += (size_t)pairs[i].n1;
+  w.claim = L.take<int32_t>(w.claims);
+  size_t k = 0;
+  for (int i = 0; i < np; ++i) {
+    const gims_nn_pair& p = pairs[i];
+    w.wa.push_back(L.take<double>((size_t)GD_W * p.n0));
+    w.wb.push_back(L.take<double>((size_t)GD_W * p.n1));
+    w.fixed.push_back(L.take<uint8_t>((size_t)p.n0));
+    for (int dir = 0; dir < (p.mutual ? 2 : 1); ++dir, ++k)
+      w.lcnt.push_back(forced ? nullptr : L.take<int32_t>((size_t)probs[k].nx * 4 * probs[k].csplit));
+  }
+  return w;
+}
+
+// GIMS_AUX_GUIDED_MATCH of gims_run_ops (include/gims_hip.h): every argument check precedes the first HIP call.
 enum { GD_A, GD_B, GD_LDA, GD_LDB, GD_N0, GD_N1, GD_D, GD_KPTS0, GD_KPTS1, GD_MODEL, GD_KIND, GD_OK, GD_PRIOR, GD_PMASK, GD_PSCORE, GD_MUTUAL,
        GD_NN1, GD_NN2, GD_D1, GD_D2, GD_RATIO, GD_NADM, GD_MATCHES0, GD_SCORES0, GD_ADDED0, GD_CNN1, GD_MATCHES1, GD_INFO, GD_THRESH, GD_RATIO_THR,
        GD_MAX_DIST, GD_RESERVED };
 static_assert(GD_RESERVED + 1 == GIMS_GUIDED_TABLE_WORDS, "the table of GIMS_AUX_GUIDED_MATCH");
 static_assert(sizeof(GdProb) == 48 && sizeof(GdPairDev) == 232 && sizeof(NnProb) == 160 && sizeof(NnPairDev) == 200,
-              "the workspace formula of include/gims_hip.h, restated by hip.guided_layout");
+              "the workspace formula of include/gims_hip.h");
 static float gd_float(int64_t word) {
   const uint32_t b = (uint32_t)word;
   float f;
@@ -734,14 +771,43 @@ static float gd_float(int64_t word) {
   return f;
 }
 
+// the number of pairs of one call and its flags: the op and gims_aux_layout refuse the same values
+static int gd_check_call(int64_t n, int64_t flags) {
+  GIMS_CHECK_ARG(n >= 1 && (size_t)n * 2 * sizeof(NnProb) <= ((size_t)1 << 20), "guided_match: %lld pairs in one call (1 .. %zu)", (long long)n,
+                 ((size_t)1 << 20) / (2 * sizeof(NnProb)));
+  GIMS_CHECK_ARG((flags & ~(int64_t)GIMS_NN_EXHAUSTIVE) == 0, "guided_match: unknown flag bits 0x%llx", (long long)flags);
+  return GIMS_OK;
+}
+
+// gims_aux_layout for GIMS_AUX_GUIDED_MATCH: sizes = {flags, P, (n0, n1, mutual) x P}, the workspace
+int guided_match_aux_layout(const int64_t* sizes, int n, WsRecord& rec) {
+  GIMS_CHECK_ARG(n >= 2 && sizes[1] >= 0 && (int64_t)n - 2 == 3 * sizes[1], "guided_match: the layout takes 2 + 3 P sizes {flags, P, (n0, n1, mutual) x P}, not %d", n);
+  const int64_t flags = sizes[0], np = sizes[1];
+  if (const int rc = gd_check_call(np, flags)) return rc;
+  std::vector<gims_nn_pair> pairs((size_t)np);
+  for (int64_t i = 0; i < np; ++i) {
+    const int64_t n0 = sizes[2 + 3 * i], n1 = sizes[3 + 3 * i], mutual = sizes[4 + 3 * i];
+    const char* why = mutual != 0 && mutual != 1 ? "mutual must be 0 or 1" : nn_rows_why(n0, n1, mutual != 0, true);
+    GIMS_CHECK_ARG(!why, "guided_match: pair %lld (n0 = %lld, n1 = %lld): %s", (long long)i, (long long)n0, (long long)n1, why);
+    gims_nn_pair& p = pairs[(size_t)i];
+    memset(&p, 0, sizeof(p));
+    p.n0 = (int32_t)n0, p.n1 = (int32_t)n1, p.mutual = (int32_t)mutual;
+    p.cnn1 = mutual ? (int32_t*)&p : nullptr;                  // the op refuses a mutual pair without the caller's cnn1: nn_layout takes none (never read here)
+  }
+  std::vector<NnProb> probs;
+  std::vector<NnPairDev> pd;
+  WsLayout L(nullptr, &rec);
+  gd_layout(pairs.data(), (int)np, (int)flags, L, probs, pd);
+  rec.bytes = L.bytes();
+  return GIMS_OK;
+}
+
 int guided_match_aux(const gims_aux_args& x, hipStream_t st) {
   // i[5] is where a later form of this function would be selected: it is read FIRST (see assemble_rows_aux)
   GIMS_CHECK_ARG(x.i[5] == 0, "gims_run_ops: unknown auxiliary function form: guided_match with i[5] = %lld (i[5] is reserved and must be 0)",
                  (long long)x.i[5]);
   const int64_t n = x.i[0], flags = x.i[1], work_bytes = x.i[2];
-  GIMS_CHECK_ARG(n >= 1 && (size_t)n * 2 * sizeof(NnProb) <= ((size_t)1 << 20), "guided_match: %lld pairs in one call (1 .. %zu)", (long long)n,
-                 ((size_t)1 << 20) / (2 * sizeof(NnProb)));
-  GIMS_CHECK_ARG((flags & ~(int64_t)GIMS_NN_EXHAUSTIVE) == 0, "guided_match: unknown flag bits 0x%llx", (long long)flags);
+  if (const int rc = gd_check_call(n, flags)) return rc;
   GIMS_CHECK_ARG(x.i[3] == 0 && x.i[4] == 0 && !x.p[2] && !x.p[3] && !x.p[4] && !x.p[5] && x.f[0] == 0.f && x.f[1] == 0.f,
                  "guided_match: a reserved word of the call is not 0 (i[3], i[4], p[2] .. p[5], f[0], f[1])");
   GIMS_CHECK_ARG(x.p[0] && x.p[1], "guided_match: the table or the workspace is NULL");
@@ -777,15 +843,14 @@ int guided_match_aux(const gims_aux_args& x, hipStream_t st) {
   std::vector<NnPairDev> pd;
   WsLayout L((void*)x.p[1]);
   const int iflags = (int)flags;
-  const NnWs w = nn_layout(pairs.data(), np, iflags, L, &probs, &pd);
+  const GdWs W = gd_layout(pairs.data(), np, iflags, L, probs, pd);
+  const NnWs& w = W.nn;
   const bool forced = (flags & GIMS_NN_EXHAUSTIVE) != 0;
   const int nprob = (int)probs.size();
-  GdProb* dgates = L.take<GdProb>((size_t)nprob);
-  GdPairDev* dgpairs = L.take<GdPairDev>((size_t)np);
-  int32_t* cnt = L.take<int32_t>(4 * (size_t)np);
-  size_t claims = 0;
-  for (int i = 0; i < np; ++i) claims += (size_t)pairs[(size_t)i].n1;
-  int32_t* claim = L.take<int32_t>(claims);
+  GdProb* dgates = W.dgates;
+  GdPairDev* dgpairs = W.dgpairs;
+  int32_t *cnt = W.cnt, *claim = W.claim;
+  const size_t claims = W.claims;
   std::vector<GdProb> gates;
   std::vector<GdPairDev> gp;
   int k = 0, max_rows = 0, max_nx = 0, max_n0 = 0;
@@ -798,9 +863,7 @@ int guided_match_aux(const gims_aux_args& x, hipStream_t st) {
     D.prior = (const int64_t*)e[GD_PRIOR]; D.pmask = (const uint8_t*)e[GD_PMASK]; D.pscore = (const float*)e[GD_PSCORE];
     D.n0 = p.n0; D.n1 = p.n1; D.kind = (int32_t)e[GD_KIND]; D.mutual = p.mutual ? 1 : 0; D.forced = forced;
     D.ratio_thr = p.threshold; D.max_dist = gd_float(e[GD_MAX_DIST]);
-    D.wa = L.take<double>((size_t)GD_W * p.n0);
-    D.wb = L.take<double>((size_t)GD_W * p.n1);
-    D.fixed = L.take<uint8_t>((size_t)p.n0);
+    D.wa = W.wa[(size_t)i], D.wb = W.wb[(size_t)i], D.fixed = W.fixed[(size_t)i];
     D.claim = claim; claim += p.n1;
     D.cnt = cnt + 4 * (size_t)i;
     D.nn1 = p.nn1; D.nn2 = p.nn2; D.d1 = p.d1; D.d2 = p.d2; D.cnn1 = pd[(size_t)i].cnn1;
@@ -808,11 +871,10 @@ int guided_match_aux(const gims_aux_args& x, hipStream_t st) {
     D.ratio = p.ratio; D.matches0 = p.matches0; D.scores0 = p.scores0; D.added0 = p.match; D.matches1 = p.matches1; D.info = p.info;
     const double t = (double)gd_float(e[GD_THRESH]);
     for (int dir = 0; dir < (p.mutual ? 2 : 1); ++dir, ++k) {
-      const NnProb& Q = probs[(size_t)k];
       GdProb G;
       memset(&G, 0, sizeof(G));
       G.qw = dir ? D.wb : D.wa; G.cw = dir ? D.wa : D.wb;
-      G.lcnt = forced ? nullptr : L.take<int32_t>((size_t)Q.nx * 4 * Q.csplit);
+      G.lcnt = W.lcnt[(size_t)k];
       G.nadm = dir ? nullptr : (int32_t*)e[GD_NADM];
       G.t2 = t * t; G.kind = D.kind;
       gates.push_back(G);

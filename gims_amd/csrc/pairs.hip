@@ -37,8 +37,14 @@ typedef int i32x16 __attribute__((ext_vector_type(16)));
 
 static inline int64_t prs_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 static inline int prs_dp(int d) { int p = 32; while (p < d) p <<= 1; return p; }        // the channel count of Q: D up to a power of two, zeros behind D
+// the rows of the pooled matrix: every image's m (m[0], m[stride], ...) up to a whole block, the whole up to a query tile (at least one)
+static inline int64_t prs_pool(const int64_t* m, int64_t stride, int64_t n) {
+  int64_t pool = 0;
+  for (int64_t i = 0; i < n; ++i) pool += prs_up(m[stride * i], PRS_BLOCK);
+  return prs_up(pool > 0 ? pool : 1, PRS_TILE);
+}
 
-// The workspace (the formula of include/gims_hip.h; hip.pairs_work_bytes mirrors it)
+// The workspace (the formula of include/gims_hip.h; gims_aux_layout reports this routine's offsets)
 struct PrsWs {
   uint32_t* head;              // {maxabs bits, scale bits, n_bad_rows, 0, non-finite count lo, hi}
   int64_t* tab;                // [N][8]: the caller's table with word 5 = pstart_i and word 6 = P_i
@@ -48,8 +54,8 @@ struct PrsWs {
   uint8_t* map;                // [N][N]
   int32_t *rowcnt, *rowoff;    // [N]
 };
-static size_t prs_layout(void* base, int64_t n, int64_t pool, int dp, PrsWs& w) {
-  WsLayout L(base);
+static size_t prs_layout(void* base, int64_t n, int64_t pool, int dp, PrsWs& w, WsRecord* rec = nullptr) {
+  WsLayout L(base, rec);
   w.head = L.take<uint32_t>(8);
   w.tab = L.take<int64_t>((size_t)n * PRS_WORDS);
   w.blk_img = L.take<int32_t>((size_t)(pool / PRS_BLOCK));
@@ -403,6 +409,27 @@ static int prs_vote_launch(const PrsWs& w, int n, int pool, int rq, int32_t* vot
   return GIMS_OK;
 }
 
+// the sizes that lay the workspace out (with every image's m): the op and gims_aux_layout refuse the same values
+static int prs_check_sizes(int64_t n, int64_t d) {
+  GIMS_CHECK_ARG(n >= 2 && n <= GIMS_PAIRS_MAX_IMAGES, "select_pairs: N = %lld is out of range (2 .. %d)", (long long)n, GIMS_PAIRS_MAX_IMAGES);
+  GIMS_CHECK_ARG(d >= 32 && d <= GIMS_PAIRS_MAX_D && d % 32 == 0, "select_pairs: D = %lld is not served (a multiple of 32 in 32 .. %d)", (long long)d,
+                 GIMS_PAIRS_MAX_D);
+  return GIMS_OK;
+}
+
+// gims_aux_layout for GIMS_AUX_SELECT_PAIRS: sizes = {D, N, m_0 .. m_{N-1}}, the workspace
+int select_pairs_aux_layout(const int64_t* sizes, int n, WsRecord& rec) {
+  GIMS_CHECK_ARG(n >= 2 && sizes[1] == (int64_t)n - 2, "select_pairs: the layout takes 2 + N sizes {D, N, m_0 .. m_{N-1}}, not %d", n);
+  const int64_t d = sizes[0], n_img = sizes[1];
+  if (const int rc = prs_check_sizes(n_img, d)) return rc;
+  for (int64_t i = 0; i < n_img; ++i)
+    GIMS_CHECK_ARG(sizes[2 + i] >= 0 && sizes[2 + i] <= GIMS_PAIRS_MAX_ROWS, "select_pairs: image %lld: m = %lld is outside 0 .. %d", (long long)i,
+                   (long long)sizes[2 + i], GIMS_PAIRS_MAX_ROWS);
+  PrsWs w;
+  rec.bytes = prs_layout(nullptr, n_img, prs_pool(sizes + 2, 1, n_img), prs_dp((int)d), w, &rec);
+  return GIMS_OK;
+}
+
 // GIMS_AUX_SELECT_PAIRS of gims_run_ops (include/gims_hip.h): every argument check precedes the first HIP call
 int select_pairs_aux(const gims_aux_args& x, hipStream_t st) {
   const int64_t n = x.i[0], d = x.i[1], per_image = x.i[2], k = x.i[3], min_votes = x.i[4];
@@ -410,9 +437,7 @@ int select_pairs_aux(const gims_aux_args& x, hipStream_t st) {
   // i[5] is where a later form of this function would be selected: it is read FIRST (see assemble_rows_aux)
   GIMS_CHECK_ARG(x.i[5] == 0, "gims_run_ops: unknown auxiliary function form: select_pairs with i[5] = %lld (i[5] is reserved and must be 0)",
                  (long long)x.i[5]);
-  GIMS_CHECK_ARG(n >= 2 && n <= GIMS_PAIRS_MAX_IMAGES, "select_pairs: N = %lld is out of range (2 .. %d)", (long long)n, GIMS_PAIRS_MAX_IMAGES);
-  GIMS_CHECK_ARG(d >= 32 && d <= GIMS_PAIRS_MAX_D && d % 32 == 0, "select_pairs: D = %lld is not served (a multiple of 32 in 32 .. %d)", (long long)d,
-                 GIMS_PAIRS_MAX_D);
+  if (const int rc = prs_check_sizes(n, d)) return rc;
   GIMS_CHECK_ARG(per_image >= 0 && per_image <= GIMS_PAIRS_MAX_ROWS, "select_pairs: per_image = %lld is out of range (0 .. %d)", (long long)per_image,
                  GIMS_PAIRS_MAX_ROWS);
   GIMS_CHECK_ARG(k >= 1, "select_pairs: k = %lld must be at least 1", (long long)k);
@@ -431,7 +456,7 @@ int select_pairs_aux(const gims_aux_args& x, hipStream_t st) {
                  "select_pairs: a reserved word of the table's last entry is not 0 (GIMS_PAIRS_SCALE_GIVEN is the only flag)");
   const bool scale_given = (flags & GIMS_PAIRS_SCALE_GIVEN) != 0;
   GIMS_CHECK_ARG(!scale_given || (scale >= 0.0f && scale <= 3.402823466e38f), "select_pairs: scale must be finite and >= 0");
-  int64_t pool = 0, n_rows = 0, n_short = 0;
+  int64_t n_rows = 0, n_short = 0;
   for (int64_t i = 0; i < n; ++i) {
     const int64_t* e = tab + PRS_WORDS * i;
     GIMS_CHECK_ARG(e[4] >= 0 && e[4] <= per_image, "select_pairs: image %lld: m = %lld is outside 0 .. per_image = %lld", (long long)i, (long long)e[4],
@@ -441,11 +466,10 @@ int select_pairs_aux(const gims_aux_args& x, hipStream_t st) {
     GIMS_CHECK_ARG(e[1] >= d, "select_pairs: image %lld: the row stride %lld is below D = %lld", (long long)i, (long long)e[1], (long long)d);
     GIMS_CHECK_ARG(e[2] >= 0 && e[2] <= 0x7fffffff, "select_pairs: image %lld: n = %lld is out of range", (long long)i, (long long)e[2]);
     GIMS_CHECK_ARG(e[5] == 0 && e[6] == 0 && e[7] == 0, "select_pairs: image %lld: a reserved word of the table is not 0", (long long)i);
-    pool += prs_up(e[4], PRS_BLOCK);
     n_rows += e[4];
     n_short += e[4] < 2;
   }
-  pool = prs_up(pool > 0 ? pool : 1, PRS_TILE);
+  const int64_t pool = prs_pool(tab + 4, PRS_WORDS, n);
   const int dp = prs_dp((int)d);
   PrsWs w;
   const size_t need = prs_layout(nullptr, n, pool, dp, w);

@@ -41,8 +41,8 @@ struct RsOut {
   RsEntry* ent;
   double* corr;
 };
-static size_t rs_layout(void* base, int64_t m, int64_t S, int64_t iters, RsOut& w) {
-  WsLayout L(base);
+static size_t rs_layout(void* base, int64_t m, int64_t S, int64_t iters, RsOut& w, WsRecord* rec = nullptr) {
+  WsLayout L(base, rec);
   w.pose = L.take<double>((size_t)m * 12);
   w.n_corr = L.take<int32_t>((size_t)m);
   w.ok = L.take<int32_t>((size_t)m);
@@ -54,7 +54,8 @@ static size_t rs_layout(void* base, int64_t m, int64_t S, int64_t iters, RsOut& 
   w.kp_inlier = L.take<uint8_t>((size_t)S);
   w.kp_error = L.take<float>((size_t)S);
   w.counters = L.take<int32_t>(RS_COUNTERS);
-  w.ent = L.take<RsEntry>((size_t)m);                        // scratch from here on
+  L.scratch_from_here();
+  w.ent = L.take<RsEntry>((size_t)m);
   w.corr = L.take<double>((size_t)S * RS_REC);
   w.hypscore = L.take<int32_t>((size_t)m * (size_t)iters);
   return L.bytes();
@@ -559,6 +560,18 @@ __global__ __launch_bounds__(RS_FT) void resect_finish_kernel(RsArgs a) {
     if (K) atomicAdd(a.out.counters + RS_N_CORR, K);
     if (ok) atomicAdd(a.out.counters + RS_N_INLIER, n_in);
   }
+}
+
+// gims_aux_layout for GIMS_AUX_RESECT_IMAGES: sizes = {m, S, iters}, S the sum of the entries' n_k; the bounds are the op's below
+int resect_images_aux_layout(const int64_t* sizes, int n, WsRecord& rec) {
+  GIMS_CHECK_ARG(n == 3, "resect_images: the layout takes 3 sizes {m, S, iters}, not %d", n);
+  const int64_t m = sizes[0], S = sizes[1], iters = sizes[2];
+  GIMS_CHECK_ARG(m >= 0 && m <= (1 << 24), "resect_images: m = %lld is out of range (0 .. 2^24)", (long long)m);
+  GIMS_CHECK_ARG(S >= 0 && S <= (1 << 30), "resect_images: the entries have S = %lld keypoints in all (out of range: 0 .. 2^30)", (long long)S);
+  GIMS_CHECK_ARG(iters >= 0 && iters <= 65535, "resect_images: iters = %lld is out of range (0 .. 65535)", (long long)iters);
+  RsOut w;
+  rec.bytes = rs_layout(nullptr, m, S, iters, w, &rec);
+  return GIMS_OK;
 }
 
 // GIMS_AUX_RESECT_IMAGES of gims_run_ops (include/gims_hip.h): every argument check precedes the first HIP call

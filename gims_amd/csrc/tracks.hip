@@ -25,14 +25,14 @@ enum { TRK_N_TRACKS = 0, TRK_N_OBS, TRK_N_CONFLICTING, TRK_N_EDGES, TRK_N_BAD, T
 // A component of more than trk_huge(n) nodes is huge; there are at most trk_cap_huge(n) <= 1024 of them
 static inline int64_t trk_huge(int64_t n) { return n / 1024 > TRK_LONG ? n / 1024 : TRK_LONG; }
 static inline int64_t trk_cap_huge(int64_t n) { return n / (trk_huge(n) + 1); }
-// The workspace (the formula of include/gims_hip.h; hip.tracks_work_bytes mirrors it): twelve int32 [N] arrays, the tile sums of the scan, the
+// The workspace (the formula of include/gims_hip.h; gims_aux_layout reports this routine's offsets): twelve int32 [N] arrays, the tile sums of the scan, the
 // per-tile member counts of the huge components and one counter
 struct TrkWs {
   int32_t *parent, *root, *size, *off, *members, *img, *pos, *keep, *ksize, *tid, *kofs, *confl, *sums, *hcnt, *n_huge;
   int32_t* cursor() const { return parent; }                   // the claim counters: parent is dead once root is written
 };
-static size_t trk_layout(void* base, int64_t n, TrkWs& w) {
-  WsLayout L(base);
+static size_t trk_layout(void* base, int64_t n, TrkWs& w, WsRecord* rec = nullptr) {
+  WsLayout L(base, rec);
   int32_t** a[12] = {&w.parent, &w.root, &w.size, &w.off, &w.members, &w.img, &w.pos, &w.keep, &w.ksize, &w.tid, &w.kofs, &w.confl};
   for (auto p : a) *p = L.take<int32_t>((size_t)n);
   w.sums = L.take<int32_t>((size_t)(n / TRK_TILE + 2));
@@ -446,6 +446,15 @@ __global__ __launch_bounds__(TRK_THREADS) void trk_write_kernel(const int32_t* _
     }
   }
   track_of[g] = t;
+}
+
+// gims_aux_layout for GIMS_AUX_BUILD_TRACKS: sizes = {N}, the workspace; the bound is the op's below
+int build_tracks_aux_layout(const int64_t* sizes, int n, WsRecord& rec) {
+  GIMS_CHECK_ARG(n == 1, "build_tracks: the layout takes 1 size {N}, not %d", n);
+  GIMS_CHECK_ARG(sizes[0] >= 0 && sizes[0] <= (1 << 30), "build_tracks: N = %lld is out of range (0 .. 2^30)", (long long)sizes[0]);
+  TrkWs w;
+  rec.bytes = trk_layout(nullptr, sizes[0], w, &rec);
+  return GIMS_OK;
 }
 
 // GIMS_AUX_BUILD_TRACKS of gims_run_ops (include/gims_hip.h): every argument check precedes the first HIP call

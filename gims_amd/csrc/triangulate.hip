@@ -25,15 +25,15 @@ enum { TRI_N_OK = 0, TRI_N_LOW_ANGLE, TRI_N_NO_MODEL, TRI_N_TOO_SHORT, TRI_N_TOO
 enum { TRI_TOO_SHORT = 1, TRI_NO_MODEL = 2, TRI_LOW_ANGLE = 4, TRI_TOO_LONG = 8 };
 enum { TRI_CLS_SHORT = 1, TRI_CLS_MID = 2, TRI_CLS_LONG = 3 };
 
-// The output buffer and, behind it, the scratch (the formula of include/gims_hip.h; hip.triangulate_out_layout mirrors it)
+// The output buffer and, behind it, the scratch (the formula of include/gims_hip.h; gims_aux_layout reports this routine's offsets)
 struct TriOut {
   double* xyz;
   float *max_angle, *rms, *obs_error;
   int32_t *n_inliers, *counters, *list_mid, *list_long, *n_list;
   uint8_t *status, *obs_inlier;
 };
-static size_t tri_layout(void* base, int64_t T, int64_t n_obs, TriOut& w) {
-  WsLayout L(base);
+static size_t tri_layout(void* base, int64_t T, int64_t n_obs, TriOut& w, WsRecord* rec = nullptr) {
+  WsLayout L(base, rec);
   w.xyz = L.take<double>((size_t)T * 3);
   w.max_angle = L.take<float>((size_t)T);
   w.rms = L.take<float>((size_t)T);
@@ -42,7 +42,8 @@ static size_t tri_layout(void* base, int64_t T, int64_t n_obs, TriOut& w) {
   w.status = L.take<uint8_t>((size_t)T);
   w.obs_inlier = L.take<uint8_t>((size_t)n_obs);
   w.counters = L.take<int32_t>(TRI_COUNTERS);
-  w.list_mid = L.take<int32_t>((size_t)T);                     // scratch from here on
+  L.scratch_from_here();
+  w.list_mid = L.take<int32_t>((size_t)T);
   w.list_long = L.take<int32_t>((size_t)T);
   w.n_list = L.take<int32_t>(2);
   return L.bytes();
@@ -479,6 +480,22 @@ __global__ __launch_bounds__(THREADS) void tri_track_kernel(TriArgs a) {
   if (threadIdx.x < TRI_COUNTERS && s_cnt[threadIdx.x]) atomicAdd(a.out.counters + threadIdx.x, s_cnt[threadIdx.x]);
 }
 
+// the sizes that lay the buffer out: the op and gims_aux_layout refuse the same values
+static int tri_check_sizes(int64_t T, int64_t n_obs) {
+  GIMS_CHECK_ARG(T >= 0 && T <= (1 << 30), "triangulate_tracks: T = %lld is out of range (0 .. 2^30)", (long long)T);
+  GIMS_CHECK_ARG(n_obs >= 0 && n_obs <= (1 << 30), "triangulate_tracks: n_obs = %lld is out of range (0 .. 2^30)", (long long)n_obs);
+  return GIMS_OK;
+}
+
+// gims_aux_layout for GIMS_AUX_TRIANGULATE_TRACKS: sizes = {T, n_obs}
+int triangulate_tracks_aux_layout(const int64_t* sizes, int n, WsRecord& rec) {
+  GIMS_CHECK_ARG(n == 2, "triangulate_tracks: the layout takes 2 sizes {T, n_obs}, not %d", n);
+  if (const int rc = tri_check_sizes(sizes[0], sizes[1])) return rc;
+  TriOut w;
+  rec.bytes = tri_layout(nullptr, sizes[0], sizes[1], w, &rec);
+  return GIMS_OK;
+}
+
 // GIMS_AUX_TRIANGULATE_TRACKS of gims_run_ops (include/gims_hip.h): every argument check precedes the first HIP call
 int triangulate_tracks_aux(const gims_aux_args& x, hipStream_t st) {
   const int64_t T = x.i[0], n_obs = x.i[1], n_images = x.i[2], N = x.i[3], mode = x.i[4];
@@ -486,8 +503,7 @@ int triangulate_tracks_aux(const gims_aux_args& x, hipStream_t st) {
   // i[5] is where a later form of this function would be selected: it is read FIRST (see assemble_rows_aux)
   GIMS_CHECK_ARG(x.i[5] == 0, "gims_run_ops: unknown auxiliary function form: triangulate_tracks with i[5] = %lld (i[5] is reserved and must be 0)",
                  (long long)x.i[5]);
-  GIMS_CHECK_ARG(T >= 0 && T <= (1 << 30), "triangulate_tracks: T = %lld is out of range (0 .. 2^30)", (long long)T);
-  GIMS_CHECK_ARG(n_obs >= 0 && n_obs <= (1 << 30), "triangulate_tracks: n_obs = %lld is out of range (0 .. 2^30)", (long long)n_obs);
+  if (const int rc = tri_check_sizes(T, n_obs)) return rc;
   GIMS_CHECK_ARG(n_images >= 0 && n_images <= (1 << 24), "triangulate_tracks: n_images = %lld is out of range (0 .. 2^24)", (long long)n_images);
   GIMS_CHECK_ARG(N >= 0 && N <= (1 << 30), "triangulate_tracks: N = %lld is out of range (0 .. 2^30)", (long long)N);
   const int64_t max_hyp = mode & 0xffff, refine_iters = mode >> 16;

@@ -857,22 +857,17 @@ GUIDED_WORD = {name: k for k, name in enumerate(_GUIDED_WORDS)}       # the word
 
 
 def guided_layout(sizes, flags: int = 0) -> dict:
-    """The workspace of GIMS_AUX_GUIDED_MATCH: the formula of include/gims_hip.h (csrc/nn.hip carves it).  sizes: (n0, n1, mutual) per pair.
-    -> {'bytes', 'csplit' (per problem, pair by pair: A against B, with mutual then B against A), 'items' (workgroups of the candidate pass)}."""
-    al = lambda x: (x + 255) & ~255                                    # noqa: E731
+    """The workspace of GIMS_AUX_GUIDED_MATCH (include/gims_hip.h has the formula; csrc/nn.hip gd_layout carves it and gims_aux_layout sizes
+    it).  sizes: (n0, n1, mutual) per pair.  -> {'bytes', 'csplit' (per problem, pair by pair: A against B, with mutual then B against A),
+    'items' (workgroups of the candidate pass)}.  'csplit' and 'items' are a restatement of the library's plan, kept for the tests that
+    check it: nothing sizes a buffer from them."""
     cd = lambda a, b: -(-a // b)                                       # noqa: E731
-    forced = bool(flags & NN_EXHAUSTIVE)
     probs = []
     for n0, n1, mutual in sizes:
         probs.append((int(n0), int(n1), 0))
         if mutual:
             probs.append((int(n1), int(n0), 1))
-    P, Q = len(sizes), len(probs)
     want = min(max(cd(512, sum(cd(nx, 128) for nx, _, _ in probs)), 1), 8)
-    total = al(160 * Q) + al(200 * P) + al(16 * P) + al(48 * Q) + al(232 * P) + al(16 * P) + al(4 * sum(int(s[1]) for s in sizes))
-    for n0, n1, _ in sizes:
-        n0, n1 = int(n0), int(n1)
-        total += al(8 * n0) + al(8 * n1) + al(4 * n0) + al(4 * n1) + al(32 * n0) + al(32 * n1) + al(n0)
     csplits, items = [], 0
     for nx, ny, second in probs:
         tiles = cd(ny, 128)
@@ -880,9 +875,7 @@ def guided_layout(sizes, flags: int = 0) -> dict:
         csplit = cd(tiles, tiles_per)
         csplits.append(csplit)
         items += cd(nx, 128) * csplit
-        total += al(4 * nx) + (3 * al(4 * nx) if second else 0)
-        if not forced:
-            total += 2 * al(64 * nx * csplit) + al(16 * nx * csplit)
+    total = _aux_layout(AUX_GUIDED_MATCH, (flags, len(sizes), *(int(v) for s in sizes for v in s)))[2]
     return dict(bytes=total, csplit=csplits, items=items)
 
 
@@ -1222,11 +1215,78 @@ def sift_describe(pyr: torch.Tensor, h: int, w: int, n_images: int, kp4: torch.T
     return out, bad
 
 
+def _aux_layout(fn: int, sizes):
+    """gims_aux_layout (include/gims_hip.h): where the layout routine of auxiliary function fn puts every region of its caller-allocated
+    buffer, for the sizes that routine takes.  -> (byte offset of every region, number of output regions, bytes in all).  Host arithmetic
+    inside the library: no device is needed."""
+    lib = load()
+    arr = (C.c_int64 * max(len(sizes), 1))(*[int(s) for s in sizes])
+    n_regions, n_outputs, total = C.c_int32(), C.c_int32(), C.c_size_t()
+    _check(lib.gims_aux_layout(fn, arr, len(sizes), None, 0, C.byref(n_regions), C.byref(n_outputs), C.byref(total)), "gims_aux_layout")
+    offsets = (C.c_int64 * max(n_regions.value, 1))()
+    _check(lib.gims_aux_layout(fn, arr, len(sizes), offsets, n_regions.value, C.byref(n_regions), C.byref(n_outputs), C.byref(total)), "gims_aux_layout")
+    return list(offsets[:n_regions.value]), n_outputs.value, total.value
+
+
+# The output regions of the ops that write into one caller-allocated buffer, in the order their layout routines take them: (name, dtype,
+# shape) for the sizes gims_aux_layout takes.  The offsets come from the library; these tables only name and type the regions.
+def _tri_regions(T, n_obs):
+    return (("xyz", torch.float64, (T, 3)), ("max_angle", torch.float32, (T,)), ("rms_error", torch.float32, (T,)), ("n_inliers", torch.int32, (T,)),
+            ("obs_error", torch.float32, (n_obs,)), ("status", torch.uint8, (T,)), ("obs_inlier", torch.uint8, (n_obs,)), ("counters", torch.int32, (8,)))
+
+
+def _resect_regions(m, S, iters):
+    return (("pose", torch.float64, (m, 12)), *((k, torch.int32, (m,)) for k in ("n_corr", "ok", "n_inliers", "best_hyp", "best_hyp_inliers", "lo_rounds")),
+            ("rms_error", torch.float32, (m,)), ("kp_inlier", torch.uint8, (S,)), ("kp_error", torch.float32, (S,)), ("counters", torch.int32, (8,)))
+
+
+def _ba_regions(T, n_obs, n_images, iters, n_free):
+    return (("xyz", torch.float64, (T, 3)), ("cams", torch.float64, (n_images, TRI_CAMERA_WORDS)), ("obs_error", torch.float32, (n_obs,)),
+            ("cam_obs", torch.int32, (n_images,)), ("history", torch.float64, (iters + 1, 2)), ("taken", torch.uint8, (iters,)), ("counters", torch.int32, (8,)))
+
+
+def _ba_pcg_regions(T, n_obs, n_images, iters, n_free):
+    return _ba_regions(T, n_obs, n_images, iters, n_free) + (("cg_used", torch.int32, (iters,)), ("cg_res", torch.float64, (iters,)))
+
+
+def _ba_focal_regions(T, n_obs, n_images, iters, n_free, n_groups):
+    return _ba_pcg_regions(T, n_obs, n_images, iters, n_free) + (("focal_scale", torch.float64, (n_groups,)), ("group_obs", torch.int32, (n_groups,)))
+
+
+_AUX_REGIONS = {AUX_TRIANGULATE_TRACKS: _tri_regions, AUX_RESECT_IMAGES: _resect_regions, AUX_BUNDLE_ADJUST: _ba_regions,
+                AUX_BUNDLE_ADJUST_PCG: _ba_pcg_regions, AUX_BUNDLE_ADJUST_FOCAL: _ba_focal_regions}
+
+
+def _out_layout(fn: int, sizes) -> dict:
+    """BYTE offsets into the one buffer of auxiliary function fn: the name of every output region of _AUX_REGIONS -> its offset, 'outputs' =
+    'scratch' = the offset of the kernels' scratch behind the outputs, 'bytes' = the whole buffer.  All numbers are the library's
+    (_aux_layout); a region whose extent there is not that of its dtype and shape here raises, so that a table that has drifted from the
+    layout routine fails where the buffer is allocated."""
+    regions = _AUX_REGIONS[fn](*sizes)
+    offsets, n_outputs, total = _aux_layout(fn, sizes)
+    if n_outputs != len(regions) or n_outputs >= len(offsets):
+        raise GimsHipError(f"auxiliary function {fn}: the library lays out {n_outputs} output regions of {len(offsets)}, the binding names {len(regions)}")
+    off = {}
+    for r, (name, dt, shape) in enumerate(regions):
+        want, got = (math.prod(shape) * dt.itemsize + 255) & ~255, offsets[r + 1] - offsets[r]
+        if got != want:
+            raise GimsHipError(f"auxiliary function {fn}: region {name}: {got} bytes in the library's layout, {want} for {dt} {list(shape)}")
+        off[name] = offsets[r]
+    off["outputs"] = off["scratch"] = offsets[n_outputs]
+    off["bytes"] = total
+    return off
+
+
+def _out_views(fn: int, sizes, out: torch.Tensor) -> dict:
+    """The typed views of the output regions of fn's buffer, by _out_layout."""
+    o = _out_layout(fn, sizes)
+    return {name: out[o[name]:o[name] + math.prod(shape) * dt.itemsize].view(dt).view(shape) for name, dt, shape in _AUX_REGIONS[fn](*sizes)}
+
+
 def diou_nms_workspace_bytes(n: int, n_images: int) -> int:
-    """The workspace of GIMS_AUX_DIOU_NMS for n keypoints in n_images images: the formula of include/gims_hip.h (csrc/nms.hip nms_layout
-    carves it), every region rounded up to 256 bytes.  Plain arithmetic: the library has no size query for it."""
-    al = lambda x: (x + 255) & ~255
-    return 2 * al(16 * n) + 3 * al(4 * n) + al(4 * (2 * n + 64 * n_images)) + al(n)
+    """The workspace of GIMS_AUX_DIOU_NMS for n keypoints in n_images images (include/gims_hip.h has the formula; the library evaluates it
+    with the routine that carves the workspace, csrc/nms.hip nms_layout)."""
+    return _aux_layout(AUX_DIOU_NMS, (n, n_images))[2]
 
 
 def op_diou_nms(kp4, order, offsets, keep, count, work, n_images, height, width, radius, iou_thresh) -> Op:
@@ -1362,10 +1422,9 @@ def tracks_table(entries, counts, device) -> np.ndarray:
 
 
 def tracks_work_bytes(n_pairs: int, n_images: int, n: int) -> int:
-    """The workspace of GIMS_AUX_BUILD_TRACKS for n keypoints in all: the formula of include/gims_hip.h (csrc/tracks.hip trk_layout carves
-    it).  It depends on neither n_pairs nor n_images: the pair table is read where it lies."""
-    al = lambda x: (x + 255) & ~255
-    return 12 * al(4 * n) + al(4 * (n // TRACKS_SCAN_TILE + 2)) + al(4 * (n // (tracks_huge(n) + 1) + 1) * (n // TRACKS_SCAN_TILE + 1)) + 256
+    """The workspace of GIMS_AUX_BUILD_TRACKS for n keypoints in all (include/gims_hip.h has the formula; csrc/tracks.hip trk_layout carves
+    it and, through gims_aux_layout, sizes it).  It depends on neither n_pairs nor n_images: the pair table is read where it lies."""
+    return _aux_layout(AUX_BUILD_TRACKS, (n,))[2]
 
 
 def tracks_huge(n: int) -> int:
@@ -1418,13 +1477,9 @@ def pairs_pool(ms) -> int:
 
 
 def pairs_work_bytes(ms, d: int) -> int:
-    """The workspace of GIMS_AUX_SELECT_PAIRS: the formula of include/gims_hip.h (csrc/pairs.hip prs_layout carves it)."""
-    al = lambda x: (x + 255) & ~255
-    n, pool = len(ms), pairs_pool(ms)
-    dp = 32
-    while dp < d:
-        dp *= 2
-    return 256 + al(8 * PAIRS_TABLE_WORDS * n) + al(4 * pool // 32) + al(pool * dp) + al(4 * pool) + al(n * n) + 2 * al(4 * n)
+    """The workspace of GIMS_AUX_SELECT_PAIRS (include/gims_hip.h has the formula; csrc/pairs.hip prs_layout carves it and, through
+    gims_aux_layout, sizes it)."""
+    return _aux_layout(AUX_SELECT_PAIRS, (d, len(ms), *ms))[2]
 
 
 def pairs_out_layout(n: int, k: int):
@@ -1473,19 +1528,11 @@ def select_pairs(images, d: int, device, k: int, per_image: int, rq: int, min_vo
 
 
 def triangulate_out_layout(T: int, n_obs: int) -> dict:
-    """BYTE offsets into the one buffer of GIMS_AUX_TRIANGULATE_TRACKS (include/gims_hip.h; csrc/triangulate.hip tri_layout carves it): xyz
-    float64 [T, 3], max_angle / rms_error float32 [T], n_inliers int32 [T], obs_error float32 [n_obs], status uint8 [T], obs_inlier uint8
-    [n_obs], counters int32 [8]; 'outputs' = the bytes of all of these, 'scratch' = the offset of the kernels' scratch behind them (the same
-    value), 'bytes' = the whole buffer.  Every region starts on a 256-byte boundary."""
-    al = lambda x: (x + 255) & ~255      # noqa: E731
-    off, at = {}, 0
-    for name, size in (("xyz", 24 * T), ("max_angle", 4 * T), ("rms_error", 4 * T), ("n_inliers", 4 * T), ("obs_error", 4 * n_obs), ("status", T),
-                       ("obs_inlier", n_obs), ("counters", 32)):
-        off[name] = at
-        at += al(size)
-    off["outputs"] = off["scratch"] = at
-    off["bytes"] = at + 2 * al(4 * T) + al(8)
-    return off
+    """BYTE offsets into the one buffer of GIMS_AUX_TRIANGULATE_TRACKS (include/gims_hip.h; csrc/triangulate.hip tri_layout carves it and
+    gims_aux_layout reports it): xyz float64 [T, 3], max_angle / rms_error float32 [T], n_inliers int32 [T], obs_error float32 [n_obs], status
+    uint8 [T], obs_inlier uint8 [n_obs], counters int32 [8]; 'outputs' = the bytes of all of these, 'scratch' = the offset of the kernels'
+    scratch behind them (the same value), 'bytes' = the whole buffer.  Every region starts on a 256-byte boundary."""
+    return _out_layout(AUX_TRIANGULATE_TRACKS, (T, n_obs))
 
 
 def triangulate_cameras(K, R, t, counts) -> np.ndarray:
@@ -1513,12 +1560,7 @@ def op_triangulate_tracks(indptr, obs_image, obs_keypoint, kpts, cams, out, T: i
 
 def triangulate_views(out: torch.Tensor, T: int, n_obs: int) -> dict:
     """The typed views of the op's buffer, by triangulate_out_layout."""
-    o = triangulate_out_layout(T, n_obs)
-    cut = lambda name, size, dt: out[o[name]:o[name] + size].view(dt)      # noqa: E731
-    return dict(xyz=cut("xyz", 24 * T, torch.float64).view(T, 3), max_angle=cut("max_angle", 4 * T, torch.float32),
-                rms_error=cut("rms_error", 4 * T, torch.float32), n_inliers=cut("n_inliers", 4 * T, torch.int32),
-                obs_error=cut("obs_error", 4 * n_obs, torch.float32), status=cut("status", T, torch.uint8),
-                obs_inlier=cut("obs_inlier", n_obs, torch.uint8), counters=cut("counters", 32, torch.int32))
+    return _out_views(AUX_TRIANGULATE_TRACKS, (T, n_obs), out)
 
 
 def triangulate_tracks(indptr, obs_image, obs_keypoint, kpts, cams: np.ndarray, thresh: float = 4.0, min_angle: float = 1.5, max_hyp: int = 64,
@@ -1562,21 +1604,13 @@ def _resect_slots(cams) -> np.ndarray:
 
 
 def resect_out_layout(cams, iters: int = 0) -> dict:
-    """BYTE offsets into the one buffer of GIMS_AUX_RESECT_IMAGES (include/gims_hip.h; csrc/resect.hip rs_layout carves it) for the host
-    records cams [m, 6]: pose float64 [m, 12], n_corr / ok / n_inliers / best_hyp / best_hyp_inliers / lo_rounds int32 [m], rms_error float32
+    """BYTE offsets into the one buffer of GIMS_AUX_RESECT_IMAGES (include/gims_hip.h; csrc/resect.hip rs_layout carves it and
+    gims_aux_layout reports it) for the host records cams [m, 6]: pose float64 [m, 12], n_corr / ok / n_inliers / best_hyp / best_hyp_inliers / lo_rounds int32 [m], rms_error float32
     [m], kp_inlier uint8 [S], kp_error float32 [S], counters int32 [8], S = the sum of n_k; 'outputs' = the bytes of all of these = 'scratch',
     the offset of the kernels' scratch (which holds iters counters per entry), 'bytes' = the whole buffer; 'slots' = the m + 1 offsets of
     the entries in kp_inlier / kp_error.  Every region starts on a 256-byte boundary."""
-    al = lambda x: (x + 255) & ~255      # noqa: E731
     slots = _resect_slots(cams)
-    m, S = len(slots) - 1, int(slots[-1])
-    off, at = {}, 0
-    for name, size in (("pose", 96 * m), ("n_corr", 4 * m), ("ok", 4 * m), ("n_inliers", 4 * m), ("best_hyp", 4 * m), ("best_hyp_inliers", 4 * m),
-                       ("lo_rounds", 4 * m), ("rms_error", 4 * m), ("kp_inlier", S), ("kp_error", 4 * S), ("counters", 32)):
-        off[name] = at
-        at += al(size)
-    off["outputs"] = off["scratch"] = at
-    off["bytes"] = at + al(56 * m) + al(48 * S) + al(4 * m * int(iters))
+    off = _out_layout(AUX_RESECT_IMAGES, (len(slots) - 1, int(slots[-1]), int(iters)))
     off["slots"] = [int(s) for s in slots]
     return off
 
@@ -1598,14 +1632,8 @@ def op_resect_images(track_of, xyz, use, kpts, cams: np.ndarray, out, n: int, T:
 
 def resect_views(out: torch.Tensor, cams, iters: int = 0) -> dict:
     """The typed views of the op's buffer, by resect_out_layout."""
-    o = resect_out_layout(cams, iters)
-    m, S = len(o["slots"]) - 1, o["slots"][-1]
-    cut = lambda name, size, dt: out[o[name]:o[name] + size].view(dt)      # noqa: E731
-    v = {k: cut(k, 4 * m, torch.int32) for k in ("n_corr", "ok", "n_inliers", "best_hyp", "best_hyp_inliers", "lo_rounds")}
-    v.update(pose=cut("pose", 96 * m, torch.float64).view(m, 12), rms_error=cut("rms_error", 4 * m, torch.float32),
-             kp_inlier=cut("kp_inlier", S, torch.uint8), kp_error=cut("kp_error", 4 * S, torch.float32), counters=cut("counters", 32, torch.int32),
-             slots=o["slots"])
-    return v
+    slots = [int(s) for s in _resect_slots(cams)]
+    return dict(_out_views(AUX_RESECT_IMAGES, (len(slots) - 1, slots[-1], int(iters)), out), slots=slots)
 
 
 def resect_images(track_of, xyz, use, kpts, cams: np.ndarray, thresh: float = 4.0, iters: int = 1024, lo_iters: int = 8, min_inliers: int = 12,
@@ -1623,55 +1651,25 @@ def resect_images(track_of, xyz, use, kpts, cams: np.ndarray, thresh: float = 4.
 
 
 def ba_out_layout(T: int, n_obs: int, n_images: int, iters: int, n_free: int) -> dict:
-    """BYTE offsets into the one buffer of GIMS_AUX_BUNDLE_ADJUST (include/gims_hip.h; csrc/ba.hip ba_layout carves it): xyz float64 [T, 3],
-    cams float64 [n_images, 18], obs_error float32 [n_obs], cam_obs int32 [n_images], history float64 [iters + 1, 2], taken uint8 [iters],
+    """BYTE offsets into the one buffer of GIMS_AUX_BUNDLE_ADJUST (include/gims_hip.h; csrc/ba.hip ba_layout carves it and gims_aux_layout
+    reports it): xyz float64 [T, 3], cams float64 [n_images, 18], obs_error float32 [n_obs], cam_obs int32 [n_images], history float64 [iters + 1, 2], taken uint8 [iters],
     counters int32 [8]; 'outputs' = the bytes of all of these = 'scratch', the offset of the kernels' scratch (which holds the 6 n_free square
     reduced system), 'bytes' = the whole buffer.  Every region starts on a 256-byte boundary."""
-    al = lambda x: (x + 255) & ~255      # noqa: E731
-    n = 6 * n_free
-    off, at = {}, 0
-    for name, size in (("xyz", 24 * T), ("cams", 144 * n_images), ("obs_error", 4 * n_obs), ("cam_obs", 4 * n_images), ("history", 16 * (iters + 1)),
-                       ("taken", iters), ("counters", 32)):
-        off[name] = at
-        at += al(size)
-    off["outputs"] = off["scratch"] = at
-    off["bytes"] = at + (256 + al(4 * n_images) + 2 * al(4 * n_free) + al(4 * n_free + 4) + al(24 * T) + al(144 * n_images) + al(T) + al(n_obs)
-                         + 5 * al(4 * n_obs) + al(72 * T) + al(400 * n_obs) + al(8 * T) + al(8 * n * n) + al(8 * n))
-    return off
+    return _out_layout(AUX_BUNDLE_ADJUST, (T, n_obs, n_images, iters, n_free))
 
 
 def ba_pcg_out_layout(T: int, n_obs: int, n_images: int, iters: int, n_free: int) -> dict:
     """BYTE offsets into the one buffer of GIMS_AUX_BUNDLE_ADJUST_PCG (include/gims_hip.h; csrc/ba.hip ba_pcg_layout carves it): the seven
     output regions of ba_out_layout at the same offsets, then cg_used int32 [iters] and cg_res float64 [iters]; 'outputs' = 'scratch' =
     the offset of the kernels' scratch, which is linear in every size (no reduced system is stored), 'bytes' = the whole buffer."""
-    al = lambda x: (x + 255) & ~255      # noqa: E731
-    off, at = {}, 0
-    for name, size in (("xyz", 24 * T), ("cams", 144 * n_images), ("obs_error", 4 * n_obs), ("cam_obs", 4 * n_images), ("history", 16 * (iters + 1)),
-                       ("taken", iters), ("counters", 32), ("cg_used", 4 * iters), ("cg_res", 8 * iters)):
-        off[name] = at
-        at += al(size)
-    off["outputs"] = off["scratch"] = at
-    off["bytes"] = at + (256 + al(4 * n_images) + 3 * al(4 * n_free) + al(4 * n_free + 4) + al(24 * T) + al(144 * n_images) + al(T) + al(n_obs)
-                         + 4 * al(4 * n_obs) + al(72 * T) + al(400 * n_obs) + al(8 * T) + al(24 * T) + al(336 * n_free) + 5 * al(48 * n_free))
-    return off
+    return _out_layout(AUX_BUNDLE_ADJUST_PCG, (T, n_obs, n_images, iters, n_free))
 
 
 def ba_focal_out_layout(T: int, n_obs: int, n_images: int, iters: int, n_free: int, n_groups: int) -> dict:
     """BYTE offsets into the one buffer of GIMS_AUX_BUNDLE_ADJUST_FOCAL (include/gims_hip.h; csrc/ba.hip ba_focal_layout carves it): the nine
     output regions of ba_pcg_out_layout at the same offsets, then focal_scale float64 [n_groups] and group_obs int32 [n_groups]; 'outputs'
     = 'scratch' = the offset of the kernels' scratch, which is linear in every size, 'bytes' = the whole buffer."""
-    al = lambda x: (x + 255) & ~255      # noqa: E731
-    off, at = {}, 0
-    for name, size in (("xyz", 24 * T), ("cams", 144 * n_images), ("obs_error", 4 * n_obs), ("cam_obs", 4 * n_images), ("history", 16 * (iters + 1)),
-                       ("taken", iters), ("counters", 32), ("cg_used", 4 * iters), ("cg_res", 8 * iters), ("focal_scale", 8 * n_groups), ("group_obs", 4 * n_groups)):
-        off[name] = at
-        at += al(size)
-    off["outputs"] = off["scratch"] = at
-    off["bytes"] = at + (256 + 3 * al(4 * n_images) + al(4 * n_images + 4) + al(4 * n_free) + al(24 * T) + al(144 * n_images) + al(T) + al(n_obs)
-                         + 4 * al(4 * n_obs) + al(72 * T) + al(400 * n_obs) + al(8 * T) + al(24 * T) + al(336 * n_free) + 6 * al(48 * n_free)
-                         + 3 * al(4 * n_images) + al(32 * n_images) + al(16 * n_images) + al(64 * n_obs) + al(4 * n_groups + 4) + al(4 * n_groups)
-                         + al(8 * n_groups) + al(16 * n_groups) + 5 * al(8 * n_groups))
-    return off
+    return _out_layout(AUX_BUNDLE_ADJUST_FOCAL, (T, n_obs, n_images, iters, n_free, n_groups))
 
 
 def ba_table(indptr, obs_image, obs_keypoint, obs_use, point_use, cg_iters: int = 0, cg_tol: float = 0.0, group=None) -> np.ndarray:
@@ -1707,12 +1705,7 @@ def op_bundle_adjust(table: np.ndarray, kpts, xyz, cams, mode: np.ndarray, out, 
 
 def ba_views(out: torch.Tensor, T: int, n_obs: int, n_images: int, iters: int, n_free: int) -> dict:
     """The typed views of the op's buffer, by ba_out_layout."""
-    o = ba_out_layout(T, n_obs, n_images, iters, n_free)
-    cut = lambda name, size, dt: out[o[name]:o[name] + size].view(dt)      # noqa: E731
-    return dict(xyz=cut("xyz", 24 * T, torch.float64).view(T, 3), cams=cut("cams", 144 * n_images, torch.float64).view(n_images, TRI_CAMERA_WORDS),
-                obs_error=cut("obs_error", 4 * n_obs, torch.float32), cam_obs=cut("cam_obs", 4 * n_images, torch.int32),
-                history=cut("history", 16 * (iters + 1), torch.float64).view(iters + 1, 2), taken=cut("taken", iters, torch.uint8),
-                counters=cut("counters", 32, torch.int32))
+    return _out_views(AUX_BUNDLE_ADJUST, (T, n_obs, n_images, iters, n_free), out)
 
 
 def op_bundle_adjust_pcg(table: np.ndarray, kpts, xyz, cams, mode: np.ndarray, out, T: int, n_obs: int, n: int, iters: int = 20, huber: float = 0.0,
@@ -1726,11 +1719,7 @@ def op_bundle_adjust_pcg(table: np.ndarray, kpts, xyz, cams, mode: np.ndarray, o
 
 def ba_pcg_views(out: torch.Tensor, T: int, n_obs: int, n_images: int, iters: int, n_free: int) -> dict:
     """The typed views of the buffer of GIMS_AUX_BUNDLE_ADJUST_PCG, by ba_pcg_out_layout: those of ba_views, cg_used and cg_res."""
-    o = ba_pcg_out_layout(T, n_obs, n_images, iters, n_free)
-    views = ba_views(out, T, n_obs, n_images, iters, n_free)      # (the seven regions lie at the offsets of the dense form)
-    views["cg_used"] = out[o["cg_used"]:o["cg_used"] + 4 * iters].view(torch.int32)
-    views["cg_res"] = out[o["cg_res"]:o["cg_res"] + 8 * iters].view(torch.float64)
-    return views
+    return _out_views(AUX_BUNDLE_ADJUST_PCG, (T, n_obs, n_images, iters, n_free), out)
 
 
 def op_bundle_adjust_focal(table: np.ndarray, kpts, xyz, cams, mode: np.ndarray, out, T: int, n_obs: int, n: int, iters: int = 20, huber: float = 0.0,
@@ -1750,11 +1739,7 @@ def ba_focal_groups(mode: np.ndarray, group: np.ndarray) -> int:
 
 def ba_focal_views(out: torch.Tensor, T: int, n_obs: int, n_images: int, iters: int, n_free: int, n_groups: int) -> dict:
     """The typed views of the buffer of GIMS_AUX_BUNDLE_ADJUST_FOCAL, by ba_focal_out_layout: those of ba_pcg_views, focal_scale, group_obs."""
-    o = ba_focal_out_layout(T, n_obs, n_images, iters, n_free, n_groups)
-    views = ba_pcg_views(out, T, n_obs, n_images, iters, n_free)      # (the nine regions lie at the offsets of function 14)
-    views["focal_scale"] = out[o["focal_scale"]:o["focal_scale"] + 8 * n_groups].view(torch.float64)
-    views["group_obs"] = out[o["group_obs"]:o["group_obs"] + 4 * n_groups].view(torch.int32)
-    return views
+    return _out_views(AUX_BUNDLE_ADJUST_FOCAL, (T, n_obs, n_images, iters, n_free, n_groups), out)
 
 
 def bundle_adjust(indptr, obs_image, obs_keypoint, obs_use, point_use, kpts, xyz, cams, mode: np.ndarray, iters: int = 20, huber: float = 0.0,

@@ -26,7 +26,8 @@
 extern "C" {
 #endif
 
-#define GIMS_ABI_VERSION 4   /* 4: the superseded CAR-HyNet entry points and the 3x3-convolution gather mode of gims_linear are gone; gims_linear_args keeps its size, conv_* became reserved0 / probe_delay.
+#define GIMS_ABI_VERSION 5   /* 5: gims_aux_layout is new (the layout of the auxiliary functions' buffers, from their own routines); nothing else changed.
+                             4: the superseded CAR-HyNet entry points and the 3x3-convolution gather mode of gims_linear are gone; gims_linear_args keeps its size, conv_* became reserved0 / probe_delay.
                              Still 4 (the version is pinned), but NOT layout-compatible with earlier builds of 4: gims_pack_image grew from 80 to 96 bytes (src_row, in_off;
                              gims_pack_graphs indexes a device array of them by sizeof) and two reserved words of gims_linear_args became residual_rows -- header,
                              library and binding of one build go together */
@@ -463,7 +464,7 @@ int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t
  *                        double xyz [T][3] | float max_angle [T] | float rms_error [T] | int32 n_inliers [T] | float obs_error [n_obs] |
  *                        uint8 status [T] | uint8 obs_inlier [n_obs] | int32 counters [8] | scratch: int32 [T] | int32 [T] | int32 [2]
  *                      that is al256(24 T) + 3 al256(4 T) + al256(4 n_obs) + al256(T) + al256(n_obs) + 256 bytes of outputs and
- *                      2 al256(4 T) + 256 bytes of scratch behind them (hip.triangulate_out_layout has the offsets).
+ *                      2 al256(4 T) + 256 bytes of scratch behind them (gims_aux_layout reports the offsets).
  *                      counters = {n_ok, n_low_angle, n_no_model, n_too_short, n_too_long, n_bad_obs, n_inlier_obs, 0}.
  *   i = {T, n_obs, n_images, N, max_hyp | refine_iters << 16, 0}     f = {thresh (pixels), min_angle (degrees)}
  * Observation.  Observation o of a track is (image k, keypoint i) = (obs_image, obs_keypoint)[indptr[t] + o].  Its pixel (u, v) is
@@ -532,7 +533,7 @@ int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t
  *                    int32 best_hyp_inliers [m] | int32 lo_rounds [m] | float rms_error [m] | uint8 kp_inlier [S] | float kp_error [S] |
  *                    int32 counters [8] | scratch: 56 m bytes | double [S][6] | int32 [m][iters]
  *                  that is al256(96 m) + 7 al256(4 m) + al256(S) + al256(4 S) + 256 bytes of outputs and al256(56 m) + al256(48 S) +
- *                  al256(4 m iters) bytes of scratch behind them (hip.resect_out_layout has the offsets).  The slots of entry e in kp_inlier and
+ *                  al256(4 m iters) bytes of scratch behind them (gims_aux_layout reports the offsets).  The slots of entry e in kp_inlier and
  *                  kp_error are [o_e, o_e + n_k), o_e = the sum of n_k over the entries in front: the entries lie back to back, a duplicated
  *                  image has slots of its own.  counters = {n_ok, n_failed, n_corr_total, n_inlier_total, 0, 0, 0, 0}.
  *   i = {m, N, T, iters | lo_iters << 16 | min_inliers << 24, seed (its 64 bits), 0}     f = {thresh (pixels), 0}
@@ -621,7 +622,7 @@ int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t
  *               that is al256(24 T) + al256(144 n_images) + al256(4 n_obs) + al256(4 n_images) + al256(16 (iters + 1)) + al256(iters) + 256
  *               bytes of outputs and 256 + al256(4 n_images) + 2 al256(4 n_free) + al256(4 n_free + 4) + al256(24 T) + al256(144 n_images) +
  *               al256(T) + al256(n_obs) + 5 al256(4 n_obs) + al256(72 T) + al256(400 n_obs) + al256(8 T) + al256(8 n^2) + al256(8 n) bytes of
- *               scratch behind them (hip.ba_out_layout has the offsets).  The cams region has the format of p[3]: it can be handed to a later
+ *               scratch behind them (gims_aux_layout reports the offsets).  The cams region has the format of p[3]: it can be handed to a later
  *               GIMS_AUX_TRIANGULATE_TRACKS op as its p[4], and xyz to a later GIMS_AUX_RESECT_IMAGES op as its p[1].
  *               counters = {n_free, n_fixed, n_held, n_points, n_active_obs, n_bad_obs, rounds_taken, status}.
  *   i = {T, n_obs, n_images, N, iters, 0}     f = {huber (pixels; 0: the squared loss), lambda0}
@@ -708,7 +709,7 @@ int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t
  *               every region on a 256-byte boundary: the outputs of GIMS_AUX_BUNDLE_ADJUST + al256(4 iters) + al256(8 iters) bytes of outputs
  *               and 256 + al256(4 n_images) + 3 al256(4 n_free) + al256(4 n_free + 4) + al256(24 T) + al256(144 n_images) + al256(T) +
  *               al256(n_obs) + 4 al256(4 n_obs) + al256(72 T) + al256(400 n_obs) + al256(8 T) + al256(24 T) + al256(336 n_free) +
- *               5 al256(48 n_free) bytes of scratch (hip.ba_pcg_out_layout has the offsets): linear in T, n_obs, n_images and n_free,
+ *               5 al256(48 n_free) bytes of scratch (gims_aux_layout reports the offsets): linear in T, n_obs, n_images and n_free,
  *               there is no n x n region.  cg_used[r] = the conjugate-gradient iterations that did work in round r, cg_res[r] =
  *               sqrt(rho_stop / rho_0) of round r; both 0 for a round that did nothing, for every round when n_free == 0, and cg_res = 0
  *               for a round that is not regular or has rho_0 = 0.
@@ -771,7 +772,7 @@ int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t
  *                 | double [T] | double [T][3] | double [n_free][42] | double [n_free][6] x 6 | int32 [n_images] x 3 | double [n_images][4] |
  *                 double [n_images][2] | double [n_obs][8] | int32 [n_groups + 1] | int32 [n_groups] | double [n_groups] | double
  *                 [n_groups][2] | double [n_groups] x 5
- *               every region on a 256-byte boundary (hip.ba_focal_out_layout has the offsets): linear in T, n_obs, n_images, n_free and
+ *               every region on a 256-byte boundary (gims_aux_layout reports the offsets): linear in T, n_obs, n_images, n_free and
  *               n_groups.  focal_scale[g] = the product of the (1 + ds) of the rounds that were taken (1 for a held group); group_obs[g]
  *               = the active observations of the group's posed images.  In the cams region the words fx, fy of every image of a group
  *               that moves hold the refined values; every other word follows the copy-through rule of GIMS_AUX_BUNDLE_ADJUST.
@@ -876,7 +877,7 @@ int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t
  *     + per pair     al256(8 n0) + al256(8 n1) + al256(4 n0) + al256(4 n1) + al256(32 n0) + al256(32 n1) + al256(n0)
  *     + per problem  al256(4 nx), for the (n1, n0) problem also 3 al256(4 nx), and without GIMS_NN_EXHAUSTIVE 2 al256(64 nx csplit) +
  *                    al256(16 nx csplit)
- *   bytes; hip.guided_layout in gims_amd/hip.py restates it.
+ *   bytes; gims_aux_layout reports it from the routine that carves it.
  * All of it is decided in float64, every product and every sum rounded on its own (no contraction), division correctly rounded; the float32
  * inputs are widened first.
  *   1 Has a model.  Iff ok is 0 (no pointer) or *ok != 0, and all nine entries of the model are finite.  Without a model no row searches:
@@ -958,6 +959,25 @@ int gims_attention_launch_counts(uint64_t* counts /* host */, int32_t n, int32_t
 typedef struct gims_aux_args { int32_t fn, reserved; const void* p[6]; int64_t i[6]; float f[2]; } gims_aux_args;
 typedef struct gims_op { int32_t kind; int32_t reserved; union { gims_linear_args lin; gims_attn_args att; gims_aux_args aux; } u; } gims_op;
 int gims_run_ops(const gims_op* ops /* HOST */, int32_t n_ops, void* stream);
+/* Where an auxiliary function puts every region of its caller-allocated buffer, for the sizes given: the function's own layout routine (the
+ * one its launch runs) walked without a buffer.  Host arithmetic only, no HIP call: it works with no device present.  fn and sizes:
+ *   GIMS_AUX_TRIANGULATE_TRACKS   {T, n_obs}                                     the buffer p[5]
+ *   GIMS_AUX_RESECT_IMAGES        {m, S, iters}, S = the sum of the entries' n_k  the buffer p[5]
+ *   GIMS_AUX_BUNDLE_ADJUST        {T, n_obs, n_images, iters, n_free}            the buffer p[5]
+ *   GIMS_AUX_BUNDLE_ADJUST_PCG    {T, n_obs, n_images, iters, n_free}            the buffer p[5]
+ *   GIMS_AUX_BUNDLE_ADJUST_FOCAL  {T, n_obs, n_images, iters, n_free, n_groups}  the buffer p[5]
+ *   GIMS_AUX_DIOU_NMS             {n, n_images}                                  the workspace p[5]
+ *   GIMS_AUX_BUILD_TRACKS         {N}                                            the workspace p[5]
+ *   GIMS_AUX_SELECT_PAIRS         {D, N, m_0 .. m_{N-1}}                         the workspace p[4]
+ *   GIMS_AUX_GUIDED_MATCH         {flags, P, (n0, n1, mutual) x P}               the workspace p[1]
+ * offsets[r] receives the byte offset of region r, in the order of the function's description (every region on a 256-byte boundary, so
+ * region r extends to offsets[r + 1], the last one to *bytes); *n_regions their number; *n_outputs the index of the first scratch region,
+ * i.e. the number of output regions (0 for a workspace, which is scratch only); *bytes the size of the whole buffer.  offsets may be NULL
+ * with capacity 0 to ask for the counts and the bytes only.  GIMS_EINVAL, with a message naming gims_aux_layout: a function that is
+ * unknown or has no such buffer (GIMS_AUX_SIFT_DESCRIBE, GIMS_AUX_ASSEMBLE_ROWS); a wrong n_sizes; a size outside the range the function
+ * itself accepts; a capacity below *n_regions. */
+int gims_aux_layout(int32_t fn, const int64_t* h_sizes /* HOST */, int32_t n_sizes, int64_t* h_offsets /* HOST, or NULL */, int32_t capacity,
+                    int32_t* n_regions, int32_t* n_outputs, size_t* bytes);
 /* The same replay with a HIP event recorded on `stream` before the first op and after every op: events is a HOST array of
  * n_ops + 1 event handles from gims_events_create.  gims_events_elapsed (after the stream has been synchronised) returns the
  * n - 1 intervals between n consecutive events in milliseconds: per-kernel durations of the production path, taken on the

@@ -146,7 +146,7 @@ def test_abi_constant_and_pins():
     assert hip.AUX_BUNDLE_ADJUST == 13 == hip.ABI.constants["GIMS_AUX_BUNDLE_ADJUST"]
     assert 12 not in [v for k, v in hip.ABI.constants.items() if k.startswith("GIMS_AUX_")]
     # the feature adds no export, no struct and no ABI version
-    assert len(hip.EXPORTS) == 89 and len(hip.ABI.structs) == 28 and hip.ABI_VERSION == 4 == hip.load().gims_abi_version()
+    assert len(hip.EXPORTS) == 90 and len(hip.ABI.structs) == 28 and hip.ABI_VERSION == 5 == hip.load().gims_abi_version()
     assert not any("bundle" in name.lower() or "ba_" in name.lower() for name in hip.EXPORTS)
     assert hip.BA_TABLE_WORDS == 8 and hip.BA_MAX_FREE_CAMERAS == 128 == B.MAX_FREE and hip.BA_MAX_REJECTS == 5 == B.MAX_REJECTS
     assert hip.BA_COUNTERS == B.COUNTERS and hip.TRI_CAMERA_WORDS == B.CAMERA_WORDS and hip.TRI_MAX_OBS == B.MAX_OBS

@@ -135,7 +135,7 @@ def test_abi_constant_and_pins():
     used = [v for k, v in hip.ABI.constants.items() if k.startswith("GIMS_AUX_")]
     assert 12 not in used and 15 not in used and 99 not in used and -1 not in used
     # the feature adds a constant and a table entry: no export, no struct and no ABI version
-    assert len(hip.EXPORTS) == 89 and len(hip.ABI.structs) == 28 and hip.ABI_VERSION == 4 == hip.load().gims_abi_version()
+    assert len(hip.EXPORTS) == 90 and len(hip.ABI.structs) == 28 and hip.ABI_VERSION == 5 == hip.load().gims_abi_version()
     assert not any("bundle" in name.lower() or "ba_" in name.lower() or "focal" in name.lower() for name in hip.EXPORTS)
     assert hip.BA_TABLE_WORDS == 8
 

@@ -87,7 +87,7 @@ def test_abi_constant_and_pins():
     assert hip.AUX_BUNDLE_ADJUST_PCG == 14 == hip.ABI.constants["GIMS_AUX_BUNDLE_ADJUST_PCG"] and hip.AUX_BUNDLE_ADJUST == 13
     assert 12 not in [v for k, v in hip.ABI.constants.items() if k.startswith("GIMS_AUX_")]
     # the feature adds a constant and a table entry: no export, no struct and no ABI version
-    assert len(hip.EXPORTS) == 89 and len(hip.ABI.structs) == 28 and hip.ABI_VERSION == 4 == hip.load().gims_abi_version()
+    assert len(hip.EXPORTS) == 90 and len(hip.ABI.structs) == 28 and hip.ABI_VERSION == 5 == hip.load().gims_abi_version()
     assert not any("bundle" in name.lower() or "ba_" in name.lower() or "pcg" in name.lower() for name in hip.EXPORTS)
     assert hip.BA_PCG_MAX_FREE_CAMERAS == 65536 == P.MAX_FREE and hip.BA_PCG_MAX_CG_ITERS == 256 == P.MAX_CG_ITERS and hip.BA_MAX_FREE_CAMERAS == 128
     assert hip.BA_TABLE_WORDS == 8

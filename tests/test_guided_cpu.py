@@ -17,7 +17,7 @@ W = hip.GUIDED_WORD
 def test_abi_constant_and_pins():
     assert hip.AUX_GUIDED_MATCH == 18 == hip.ABI.constants["GIMS_AUX_GUIDED_MATCH"] and hip.GUIDED_TABLE_WORDS == 32 == len(W)
     # the feature adds no export, no struct and no ABI version
-    assert len(hip.EXPORTS) == 89 and len(hip.ABI.structs) == 28 and hip.ABI_VERSION == 4 == hip.load().gims_abi_version()
+    assert len(hip.EXPORTS) == 90 and len(hip.ABI.structs) == 28 and hip.ABI_VERSION == 5 == hip.load().gims_abi_version()
     assert not any("guided" in name.lower() for name in hip.EXPORTS)
     assert gims_amd.guided_match_pairs is gims_amd.guided.guided_match_pairs and gims_amd.guided_match_features is gims_amd.guided.guided_match_features
     assert "guided_match_pairs" in gims_amd.__all__ and "guided_match_features" in gims_amd.__all__

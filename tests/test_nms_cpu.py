@@ -32,7 +32,7 @@ NAMES = [n for n, _, _ in N.FIXTURES]
 def test_abi_constant_and_pins():
     assert hip.AUX_DIOU_NMS == 7 == hip.ABI.constants["GIMS_AUX_DIOU_NMS"]
     # the thinning adds no export, no struct and no ABI version
-    assert len(hip.EXPORTS) == 89 and len(hip.ABI.structs) == 28 and hip.ABI_VERSION == 4 == hip.load().gims_abi_version()
+    assert len(hip.EXPORTS) == 90 and len(hip.ABI.structs) == 28 and hip.ABI_VERSION == 5 == hip.load().gims_abi_version()
     assert not any("nms" in name.lower() for name in hip.EXPORTS)
 
 
@@ -75,7 +75,7 @@ def test_argument_checks_come_before_any_hip_call():
 
 @pytest.mark.parametrize("n,n_images", [(0, 1), (1, 1), (5, 2), (1023, 3), (15382, 1), (100000, 16), (1 << 20, 7)])
 def test_workspace_formula_is_the_library_s(n, n_images):
-    """hip.diou_nms_workspace_bytes is plain arithmetic; the library states what it needs when it refuses one byte less."""
+    """hip.diou_nms_workspace_bytes is the library's own figure (gims_aux_layout); the op states the same need when it refuses one byte less."""
     wb = hip.diou_nms_workspace_bytes(n, n_images)
     rc, msg = _run([0x1000] * 6, [n, n_images, 10, 10, wb - 1, 0])
     assert rc == hip.GIMS_EINVAL and int(re.search(rb"(\d+) needed", msg).group(1)) == wb, msg

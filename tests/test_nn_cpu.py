@@ -76,7 +76,7 @@ def test_pair_struct_layout_matches_header(tmp_path):
     assert got == [ctypes.sizeof(hip.NnPair)] + [getattr(hip.NnPair, f).offset for f in fields]
     assert got[0] == 152 and hip.NnPair.debug.offset == 144
     assert "gims_nn_match" in hip.EXPORTS and "gims_nn_workspace_bytes" in hip.EXPORTS
-    assert hip.load().gims_abi_version() == hip.ABI_VERSION == 4
+    assert hip.load().gims_abi_version() == hip.ABI_VERSION == 5
 
 
 def _fake_pair(n0=300, n1=200, d=256, mutual=0, **kw):

@@ -14,7 +14,7 @@ from tests import pairs_ref as R
 def test_abi_constant_and_pins():
     assert hip.AUX_SELECT_PAIRS == 17 == hip.ABI.constants["GIMS_AUX_SELECT_PAIRS"]
     # the feature adds no export, no struct and no ABI version
-    assert len(hip.EXPORTS) == 89 and len(hip.ABI.structs) == 28 and hip.ABI_VERSION == 4 == hip.load().gims_abi_version()
+    assert len(hip.EXPORTS) == 90 and len(hip.ABI.structs) == 28 and hip.ABI_VERSION == 5 == hip.load().gims_abi_version()
     # (two exports from before this op carry "pairs" in their name; the op adds none, under that word or its own)
     assert sorted(name for name in hip.EXPORTS if "pairs" in name.lower()) == ["gims_eval_pairs", "gims_verify_pairs"]
     assert not any("select" in name.lower() for name in hip.EXPORTS)

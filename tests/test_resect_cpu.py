@@ -119,7 +119,7 @@ def reference(name, m, iters, lo_iters, order="forward"):
 def test_abi_constant_and_pins():
     assert hip.AUX_RESECT_IMAGES == 11 == hip.ABI.constants["GIMS_AUX_RESECT_IMAGES"]
     # the feature adds no export, no struct and no ABI version
-    assert len(hip.EXPORTS) == 89 and len(hip.ABI.structs) == 28 and hip.ABI_VERSION == 4 == hip.load().gims_abi_version()
+    assert len(hip.EXPORTS) == 90 and len(hip.ABI.structs) == 28 and hip.ABI_VERSION == 5 == hip.load().gims_abi_version()
     assert not any("resect" in name.lower() for name in hip.EXPORTS)
     assert hip.RESECT_CAMERA_WORDS == 6 == R.CAMERA_WORDS and hip.RESECT_HB == HB == R.HB and hip.RESECT_COUNTERS == R.COUNTERS
     for name in ("resect_images", "Poses", "absolute_pose"):

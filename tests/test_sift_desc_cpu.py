@@ -32,7 +32,7 @@ def _small():
 def test_abi_constant_and_pins():
     assert hip.AUX_SIFT_DESCRIBE == 6 == hip.ABI.constants["GIMS_AUX_SIFT_DESCRIBE"]
     # the descriptor stage adds no export, no struct and no ABI version
-    assert len(hip.EXPORTS) == 89 and len(hip.ABI.structs) == 28 and hip.ABI_VERSION == 4 == hip.load().gims_abi_version()
+    assert len(hip.EXPORTS) == 90 and len(hip.ABI.structs) == 28 and hip.ABI_VERSION == 5 == hip.load().gims_abi_version()
     assert not any("describe" in name for name in hip.EXPORTS)
 
 

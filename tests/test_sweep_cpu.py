@@ -91,7 +91,7 @@ def test_params_struct_layout_matches_header(tmp_path):
     got = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
     P = hip.AgcParams
     assert got == [ctypes.sizeof(P), P.radius.offset, P.percentile.offset, P.min_size.offset, P.reserved.offset] == [24, 0, 8, 16, 20]
-    assert "gims_agc_build" in hip.EXPORTS and hip.load().gims_abi_version() == 4
+    assert "gims_agc_build" in hip.EXPORTS and hip.load().gims_abi_version() == 5
     with pytest.raises(ValueError, match="parameter triples"):
         hip.agc_build_each([object(), object()], [(15, 2, 7)], None)
 

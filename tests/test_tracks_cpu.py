@@ -34,7 +34,7 @@ def same(got, want):
 def test_abi_constant_and_pins():
     assert hip.AUX_BUILD_TRACKS == 9 == hip.ABI.constants["GIMS_AUX_BUILD_TRACKS"]
     # the feature adds no export, no struct and no ABI version
-    assert len(hip.EXPORTS) == 89 and len(hip.ABI.structs) == 28 and hip.ABI_VERSION == 4 == hip.load().gims_abi_version()
+    assert len(hip.EXPORTS) == 90 and len(hip.ABI.structs) == 28 and hip.ABI_VERSION == 5 == hip.load().gims_abi_version()
     assert not any("track" in name.lower() for name in hip.EXPORTS)
     assert gims_amd.build_tracks is gims_amd.tracks.build_tracks and gims_amd.Tracks is gims_amd.tracks.Tracks
     assert "build_tracks" in gims_amd.__all__ and "Tracks" in gims_amd.__all__

@@ -143,7 +143,7 @@ def prefix(ref, sc, T):
 def test_abi_constant_and_pins():
     assert hip.AUX_TRIANGULATE_TRACKS == 10 == hip.ABI.constants["GIMS_AUX_TRIANGULATE_TRACKS"]
     # the feature adds no export, no struct and no ABI version
-    assert len(hip.EXPORTS) == 89 and len(hip.ABI.structs) == 28 and hip.ABI_VERSION == 4 == hip.load().gims_abi_version()
+    assert len(hip.EXPORTS) == 90 and len(hip.ABI.structs) == 28 and hip.ABI_VERSION == 5 == hip.load().gims_abi_version()
     assert not any("triang" in name.lower() for name in hip.EXPORTS)
     assert hip.TRI_CAMERA_WORDS == 18 == R.CAMERA_WORDS and hip.TRI_MAX_OBS == 1024 == R.MAX_OBS and hip.TRI_COUNTERS == R.COUNTERS
     assert 2 <= hip.TRI_SHORT_TRACK <= 64 and 64 % hip.TRI_SHORT_TRACK == 0

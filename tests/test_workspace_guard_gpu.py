@@ -257,3 +257,152 @@ def test_delaunay_build(hip, n):
         return outs
 
     _guarded(hip.delaunay_workspace_bytes(_graph_images(hip, data)[1]), run)
+
+
+# ------------------------------------------------------------------------------------------------ the auxiliary functions of gims_run_ops
+# Their buffers are laid out by the library's routines and sized through gims_aux_layout (hip.*_out_layout, hip.*_work_bytes,
+# hip.diou_nms_workspace_bytes, hip.guided_layout).  Triangulation, resection and the three forms of bundle adjustment write their outputs
+# into the buffer itself and take no byte count: `need` is the whole buffer and the outputs are its output regions, compared as bytes.
+# The inputs are the smallest fixtures of the ops' own tests that reach every region.
+def _region_bytes(views):
+    return [v.clone().reshape(-1).view(torch.uint8) for v in views.values() if isinstance(v, torch.Tensor)]
+
+
+def test_triangulate_tracks(hip):
+    """Tracks of 2 .. 65 observations: the short ones, the list of the mid and the list of the long ones."""
+    from tests import test_triangulate_gpu as G
+    B = G._buffers(G.scene("seams"))
+
+    def run(out, nbytes):
+        hip.run_ops(hip.make_ops([G._op(dict(B, out=out), (64, 10))]))
+        return _region_bytes(hip.triangulate_views(out, B["T"], B["n_obs"]))
+
+    _guarded(B["layout"]["bytes"], run)
+
+
+def test_resect_images(hip):
+    """Two entries, one of them without keypoints; 17 hypotheses each (one more than a workgroup of the scoring kernel takes)."""
+    from tests import test_resect_gpu as G
+    B = G._buffers(G.scene("batch"), G.entries("batch", 2), 17)
+
+    def run(out, nbytes):
+        hip.run_ops(hip.make_ops([G._op(dict(B, out=out), 8)]))
+        return _region_bytes(hip.resect_views(out, B["cams"], 17))
+
+    _guarded(B["layout"]["bytes"], run)
+
+
+def _two_free(sc):
+    """Five images, the first two fixed: the third one fixed as well, which leaves two free cameras."""
+    mode = np.array(sc["mode"], np.int32)
+    mode[2] = 1
+    assert (mode == 2).sum() == 2
+    return dict(sc, mode=mode)
+
+
+def test_bundle_adjust(hip):
+    from tests import test_ba_gpu as G
+    B = G._buffers(_two_free(G.scene("c5")), 2)
+
+    def run(out, nbytes):
+        hip.run_ops(hip.make_ops([G._op(dict(B, out=out), 0.0, 1e-4)]))
+        return _region_bytes(hip.ba_views(out, *B["dims"], 2))
+
+    _guarded(B["layout"]["bytes"], run)
+
+
+def test_bundle_adjust_pcg(hip):
+    from tests import test_ba_pcg_gpu as G
+    B = G._buffers(_two_free(G.scene("c5")), 2, 8, 1e-6)
+
+    def run(out, nbytes):
+        hip.run_ops(hip.make_ops([G._op(dict(B, out=out), 0.0, 1e-4)]))
+        return _region_bytes(hip.ba_pcg_views(out, *B["dims"], 2))
+
+    _guarded(B["layout"]["bytes"], run)
+
+
+def test_bundle_adjust_focal(hip):
+    """One focal group over all five images."""
+    from tests import test_ba_focal_gpu as G
+    sc, group = G.fixture("shared5")
+    B = G._buffers(_two_free(sc), group, 2, 8, 1e-6)
+    assert B["dims"][4] == 1
+
+    def run(out, nbytes):
+        hip.run_ops(hip.make_ops([G._op(dict(B, out=out), 0.0, 1e-4)]))
+        return _region_bytes(hip.ba_focal_views(out, *B["dims"][:4], 2, 1))
+
+    _guarded(B["layout"]["bytes"], run)
+
+
+def test_diou_nms(hip):
+    """Three images of 0, 63 and 257 keypoints."""
+    from tests import nms_ref
+    from tests import test_nms_gpu as G
+    sizes = [0, 63, 257]
+    parts = [G._dense(m, 300 + b) for b, m in enumerate(sizes)]
+    offsets = np.concatenate([[0], np.cumsum(sizes)])
+    kp4, offs = _dev(G._kp4(np.concatenate([p[0] for p in parts]))), _dev(offsets.astype(np.int32))
+    order = _dev(np.concatenate([nms_ref.make_order(p[1]) + offsets[b] for b, p in enumerate(parts)]).astype(np.int32))
+
+    def run(work, nbytes):
+        keep, count = torch.zeros(offsets[-1], dtype=torch.int32, device="cuda"), torch.zeros(len(sizes) + 1, dtype=torch.int32, device="cuda")
+        hip.run_ops(hip.make_ops([hip.op_diou_nms(kp4, order, offs, keep, count, work[:nbytes], len(sizes), 200, 260, 4.0, 0.3)]))
+        return [keep, count]
+
+    _guarded(hip.diou_nms_workspace_bytes(int(offsets[-1]), len(sizes)), run)
+
+
+def test_build_tracks(hip):
+    """Scene A of the op's own tests: six images, more nodes than one scan tile."""
+    from tests import test_tracks_gpu as G
+    from tests import tracks_ref
+    counts, pairs, matches = tracks_ref.scene(**G.SCENE_A)
+    B = G._buffers(counts, pairs, matches, None, None)
+    assert B["n"] > hip.TRACKS_SCAN_TILE
+
+    def run(work, nbytes):
+        outs = dict(track_of=torch.zeros_like(B["track_of"]), out=torch.zeros_like(B["out"]), counters=torch.zeros_like(B["counters"]))
+        hip.run_ops(hip.make_ops([G._op(dict(B, work=work.view(torch.int32), work_bytes=nbytes, **outs), None, 2, "keep")]))
+        return list(outs.values())
+
+    _guarded(B["work_bytes"], run)
+
+
+def test_select_pairs(hip):
+    """Four images of 33, 64, 31 and 70 rows, 64 channels: blocks of 32 rows that are full, ragged and one more."""
+    from tests import test_pairs_gpu as G
+    descs = G.scene([33, 64, 31, 70], 64, 5)
+    images, keep = G._device(descs, None)
+    images = [(t, ld, n, r, n) for t, ld, n, r, _ in images]
+    n, d, k = len(descs), 64, 2
+
+    def run(work, nbytes):
+        tab = hip.pairs_table(images, hip.pairs_rq(0.8), nbytes)
+        outs = [torch.zeros((n, n), dtype=torch.int32, device="cuda"), torch.zeros(hip.pairs_out_layout(n, k)[2], dtype=torch.int32, device="cuda"),
+                torch.zeros(8, dtype=torch.int32, device="cuda")]
+        hip.run_ops(hip.make_ops([hip.op_select_pairs(tab, *outs, work, n, d, 512, k, 1)]))
+        return outs
+
+    _guarded(hip.pairs_work_bytes([im[4] for im in images], d), run)
+
+
+@pytest.mark.parametrize("flags", [0, 1])
+def test_guided_match(hip, flags):
+    """One mutual pair under a fundamental matrix and one plain pair under a homography; flag 1 = GIMS_NN_EXHAUSTIVE (no candidate lists)."""
+    from tests import test_guided_gpu as G
+    cases = [G.case(G.scene(127, 129, 128, G.R.FUNDAMENTAL)), G.case(G.scene(64, 65, 32, G.R.HOMOGRAPHY), mutual=False)]
+
+    def run(work, nbytes):
+        items = G.device_items(cases)
+        got, tab = hip.guided_match(items, flags, work=work[:nbytes])
+        assert got.data_ptr() == work.data_ptr()
+        outs = []
+        for it in items:
+            n0, n1 = it["a"].shape[0], it["b"].shape[0]
+            outs += [it[name][:8 if name == "info" else n1 if name in ("cnn1", "matches1") else n0] for name in G._names(it)]
+        torch.cuda.synchronize()                                # (the table is host memory the op reads while it is enqueued; the outputs are read after)
+        return outs
+
+    _guarded(hip.guided_layout([(127, 129, True), (64, 65, False)], flags)["bytes"], run)

@@ -328,6 +328,26 @@ int main() {
       EXPECT(carved(gims_nn_match(nn.data(), 5, flags, work, need, nullptr)));
       EXPECT(gims_nn_match(nn.data(), 5, flags, work, need - 1, nullptr) == GIMS_EINVAL && strstr(gims_last_error(), "gims_nn_match"));
     }
+    {   // gims_aux_layout: the layout routines of the auxiliary functions with the recorder attached, counts only and with the offsets
+      struct { int fn; std::vector<int64_t> sizes; } aux[] = {
+          {GIMS_AUX_TRIANGULATE_TRACKS, {257, 1300}}, {GIMS_AUX_RESECT_IMAGES, {3, 1350, 65}}, {GIMS_AUX_BUNDLE_ADJUST, {257, 1300, 7, 20, 5}},
+          {GIMS_AUX_BUNDLE_ADJUST_PCG, {257, 1300, 7, 20, 65536}}, {GIMS_AUX_BUNDLE_ADJUST_FOCAL, {257, 1300, 7, 20, 5, 3}}, {GIMS_AUX_DIOU_NMS, {700, 5}},
+          {GIMS_AUX_BUILD_TRACKS, {3000000}}, {GIMS_AUX_SELECT_PAIRS, {96, 3, 33, 0, 64}}, {GIMS_AUX_GUIDED_MATCH, {0, 2, 257, 4097, 1, 700, 650, 0}},
+          {GIMS_AUX_GUIDED_MATCH, {GIMS_NN_EXHAUSTIVE, 1, 1, 1, 1}}};
+      for (auto& q : aux) {
+        int32_t nr = 0, no = 0;
+        size_t bytes = 0;
+        EXPECT(gims_aux_layout(q.fn, q.sizes.data(), (int)q.sizes.size(), nullptr, 0, &nr, &no, &bytes) == GIMS_OK && nr > 0 && no <= nr && bytes % 256 == 0);
+        std::vector<int64_t> off((size_t)nr);
+        EXPECT(gims_aux_layout(q.fn, q.sizes.data(), (int)q.sizes.size(), off.data(), nr, &nr, &no, &bytes) == GIMS_OK && off[0] == 0 &&
+               (size_t)off[(size_t)nr - 1] < bytes);
+        EXPECT(gims_aux_layout(q.fn, q.sizes.data(), (int)q.sizes.size(), off.data(), nr - 1, &nr, &no, &bytes) == GIMS_EINVAL);
+        EXPECT(gims_aux_layout(q.fn, q.sizes.data(), (int)q.sizes.size() - 1, nullptr, 0, &nr, &no, &bytes) == GIMS_EINVAL && strstr(gims_last_error(), "gims_aux_layout"));
+      }
+      int32_t nr = 0, no = 0;
+      int64_t one = 1;
+      EXPECT(gims_aux_layout(GIMS_AUX_SIFT_DESCRIBE, &one, 1, nullptr, 0, &nr, &no, &need) == GIMS_EINVAL && strstr(gims_last_error(), "gims_aux_layout"));
+    }
   }
   // ---- a call that reaches the HIP runtime: no device in this container -> a clean GIMS_EHIP / error string, no crash
   char host_table[64] = {0};
